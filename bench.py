@@ -24,6 +24,14 @@ path: no RCCL anywhere, as BASELINE.json's north_star states):
                and the latency of a batch-of-one resquiggle_read.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--preset cfg1..cfg4|longtail] ...
+                    [--full] [--dump-outputs DIR]
+
+A plain run measures `value` and `ms_per_step` only: set-up, warm-up, the K timed resident passes,
+the success rate of the batch, the JSON line.  --full adds everything else: the CPU baseline legs,
+the digest / traceback-verifier check of the resident batch, end_to_end, api, the rocprofv3 counter
+passes behind roofline.traffic and (N > 1) the short job of distinct reads.  --dump-outputs DIR
+writes what the last timed pass handed back (dump_outputs) as float64 .npy files; the inputs are a
+function of the arguments alone, so two builds can be compared output for output.
 
 With --gpus N > 1 and no torchrun environment the script launches its own N ranks (one process
 per GPU).  Prints ONE JSON line on rank 0.
@@ -344,6 +352,69 @@ def pack_lists(raws, seqs, samp_ind):
                 samp_ind=samp_ind)
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_ROWS = 200000        # reads whose per-read results are written (all of them up to this count)
+DUMP_SAMPLE_BYTES = 40 << 20  # boundaries + normalised signal of a sample of reads ...
+DUMP_SAMPLE_READS = 4096      # ... of at most this many reads
+
+
+def dump_outputs(out_dir, plan, engines, downloads, n_raw, seq_len, seed=20261016):
+    """--dump-outputs: what the last timed pass hands a caller of the engine (Engine.download per
+    resident batch), in read order, as float64 DIR/<name>.npy:
+      read_index            the reads whose per-read results follow (every read up to DUMP_MAX_ROWS)
+      status, read_start_rel_to_raw, norm_len, sig_match_score, norm_params_changed   one per read
+      scale_values          [reads, 4]: shift, scale, lower_lim, upper_lim
+      sample_read_index     a seeded sample of the reads, bounded by DUMP_SAMPLE_BYTES / _READS
+      segs, segs_offsets    the sample's base boundaries (reads with status 0; CSR)
+      norm_signal, norm_signal_offsets   the sample's normalised signal (status 0; CSR)
+    Both samples are drawn from the read count and the INPUT lengths alone, so every build of the
+    project dumps the same reads for the same arguments."""
+    n = int(n_raw.shape[0])
+    order = np.concatenate(plan)
+    where = np.zeros((n, 2), np.int64)    # read -> (resident batch, row in it)
+    for j, idx in enumerate(plan):
+        where[idx, 0], where[idx, 1] = j, np.arange(len(idx))
+    rng = np.random.RandomState(seed)
+    perm = rng.permutation(n)
+    rows = np.sort(perm[:DUMP_MAX_ROWS])
+
+    def per_read(key):
+        col = np.concatenate([d[key] for d in downloads]).astype(np.float64)
+        full = np.zeros((n,) + col.shape[1:])
+        full[order] = col
+        return full[rows]
+
+    out = {'read_index': rows.astype(np.float64), 'status': per_read('status'),
+           'read_start_rel_to_raw': per_read('read_start'), 'norm_len': per_read('norm_len'),
+           'sig_match_score': per_read('score'), 'norm_params_changed': per_read('changed'),
+           'scale_values': per_read('sv')}
+    sample, used = [], 0
+    for i in perm:
+        if len(sample) == DUMP_SAMPLE_READS:
+            break
+        cost = 8 * (int(n_raw[i]) + int(seq_len[i]) + 1)   # bounds of the signal + boundaries it can have
+        if used + cost <= DUMP_SAMPLE_BYTES:
+            sample.append(int(i))
+            used += cost
+    segs, sigs = [], []
+    for i in sorted(sample):
+        j, k = where[i]
+        d, eng = downloads[j], engines[j]
+        ok = d['status'][k] == 0
+        segs.append(d['segs'][eng.seg_off[k]:eng.seg_off[k + 1]] if ok else np.zeros(0))
+        sigs.append(d['norm'][eng.raw_off[k]:eng.raw_off[k] + d['norm_len'][k]] if ok else np.zeros(0))
+    for name, parts in (('segs', segs), ('norm_signal', sigs)):
+        out[name] = np.concatenate([np.zeros(0)] + parts).astype(np.float64)
+        out[name + '_offsets'] = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.float64)
+    out['sample_read_index'] = np.array(sorted(sample), np.float64)
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes over the %d-byte bound' % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+
+
 # ---- self-launch of N ranks ------------------------------------------------------------------
 def self_launch(n):
     """N ranks of this script, one per GPU.  The rendezvous store is created HERE on a port the
@@ -584,9 +655,14 @@ def main():
     ap.add_argument('--reads', type=int, default=10000, help='reads per GPU per step')
     ap.add_argument('--bases', type=int, default=10000)
     ap.add_argument('--bandwidth', type=int, default=500)
+    ap.add_argument('--full', action='store_true',
+                    help='besides value / ms_per_step: CPU baseline legs, batch digest, end_to_end, api, '
+                         'counter passes, the N > 1 distinct-read job')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the outputs of the last timed pass to DIR/<name>.npy (float64, at most 64 MB)')
     ap.add_argument('--cpu-sample', type=int, default=150, help='reads of the 1-thread CPU leg')
     ap.add_argument('--cpu-per-core', type=int, default=4, help='reads per core of the all-core CPU leg')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline legs')
     ap.add_argument('--preset', choices=['cfg2', 'cfg3', 'cfg1', 'cfg4', 'cfg5', 'longtail'], default=None,
                     help='BASELINE.json configs: cfg2 10kb/W=500 (default), cfg3 10kb/W=300, '
                          'cfg1 2kb/W=100, cfg4 RNA 3kb/W=500; cfg5: one job of --job-reads DISTINCT 10 kb '
@@ -597,10 +673,10 @@ def main():
                     help='cfg5: reads of the whole job (default 125000 per rank = a million on 8 GPUs; '
                          'given explicitly the job is fixed and the scaling strong)')
     ap.add_argument('--job-seed', type=int, default=20260927, help='cfg5: seed of the job (read r of the job is a function of (seed, r) alone)')
-    ap.add_argument('--e2e', choices=['compact', 'full', 'none'], default='compact',
+    ap.add_argument('--e2e', choices=['compact', 'full', 'none'], default=None,
                     help='end-to-end (reads in -> results out) measurement: int16 in / records + '
                          'int32 boundaries out, float64 in / float64 signal + int64 boundaries '
-                         'out, or skipped')
+                         'out, or skipped (default: compact with --full, else none)')
     ap.add_argument('--subsample', choices=['device', 'numpy'], default='device',
                     help='end-to-end leg: Theil-Sen subsample drawn on the device (keyed permutation) '
                          'or by np.random.choice on the feeder thread (the seeded-parity mode)')
@@ -622,8 +698,9 @@ def main():
                     help='longtail preset: clip of the log-normal read lengths (round 2 used 100000)')
     ap.add_argument('--tail-bases', type=int, default=30000,
                     help='longtail preset: reads longer than this form batches of their own (planner.plan_batches)')
-    ap.add_argument('--api-reads', type=int, default=5000, help='reads of the resquiggle_batch API leg (0: skip)')
-    ap.add_argument('--no-pmc', action='store_true', help='skip the rocprofv3 counter passes behind roofline.traffic')
+    ap.add_argument('--api-reads', type=int, default=None,
+                    help='reads of the resquiggle_batch API leg (0: skip; default: 5000 with --full, else 0)')
+    ap.add_argument('--no-pmc', action='store_true', help='(--full) skip the rocprofv3 counter passes behind roofline.traffic')
     ap.add_argument('--pmc-reads', type=int, default=1 << 30,
                     help='reads of the counter passes: the whole timed batch by default (a 2 048-read sub-batch read 5 %% low in round 5: '
                          'per-workgroup tiles amortise differently); they take the dispatch forms of the timed batch whatever this is')
@@ -635,8 +712,17 @@ def main():
         return pmc_child(a.pmc_child)
     if a.cpu_child:
         return cpu_child(a.cpu_child)
+    if a.dump_outputs and a.preset == 'cfg5':
+        ap.error('--dump-outputs: the cfg5 job hands its results batch by batch to the pipeline, '
+                 'there is no resident last pass to dump')
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return self_launch(a.gpus)
+    if not a.full:
+        a.no_cpu_baseline = a.no_pmc = True
+    if a.e2e is None:
+        a.e2e = 'compact' if a.full else 'none'
+    if a.api_reads is None:
+        a.api_reads = 5000 if a.full else 0
     samp_name = 'DNA'
     if a.preset == 'cfg3':
         a.bandwidth = 300
@@ -772,7 +858,8 @@ def main():
     o = _native.make_opts(outlier_thresh=5.0, sig_match_thresh=SIG_MATCH_THRESH[samp_name],
                           stall_params=stall_params)
 
-    if cfg5 or (world > 1 and not longtail and not rna and a.bandwidth == 500 and a.bases == 10000):
+    short_job = a.full and world > 1 and not longtail and not rna and a.bandwidth == 500 and a.bases == 10000
+    if cfg5 or short_job:
         # the job of BASELINE.json's cfg5: distinct reads, made on the device batch by batch
         job_reads = a.job_reads if (cfg5 and a.job_reads) else (125000 if cfg5 else 4 * a.reads) * world
         ctx = dict(_native=_native, streaming=streaming, sharding=sharding, model=model, params=params, samp=samp,
@@ -826,7 +913,9 @@ def main():
     def batch_digest():
         """CRC of every resident batch's boundaries + status, and the rows the traceback's verifier disagreed on
         (TBA_GET_TB_VERIFY_FAIL): taken after the warm-up and again after the last timed pass, outside the clock --
-        the timed passes run ONE resident batch again and again, so the two must be equal and the count zero"""
+        the timed passes run ONE resident batch again and again, so the two must be equal and the count zero (--full)"""
+        if not a.full:
+            return None, None
         if stub is not None:
             return None, 0
         crc, vf = 0, 0
@@ -855,8 +944,16 @@ def main():
     dt = max_over_ranks(time.perf_counter() - t0)
     steps_done = int(round(sum_over_ranks(float(my_steps))))
     n_ok = 0
+    dump = a.dump_outputs is not None and rank == 0
+    outs = []
     for eng in engines:
-        n_ok += int((eng.download(want_norm=False)['status'] == 0).sum())
+        d = eng.download(want_norm=dump)
+        n_ok += int((d['status'] == 0).sum())
+        if dump:
+            outs.append(d)
+    if dump:
+        dump_outputs(a.dump_outputs, plan, engines, outs, n_raw, seq_len)
+    del outs
     digest_last, vf_last = batch_digest()
     if os.environ.get('TBA_DBG_PHASES'):
         # profiling aid: per-read debug counters of a -DTBA_PHASE_DEBUG / -DTBA_SWEEP_STATS build
@@ -904,7 +1001,7 @@ def main():
                     resident_reads_per_s=round(a.reads * my_steps / my_dt, 2) if my_steps else 0.0,
                     resident_busy_s=round(my_dt, 4),
                     digest_stable=None if digest_first is None else bool(digest_first == digest_last),
-                    tb_verify_fail_rows=int(vf_first + vf_last))
+                    tb_verify_fail_rows=None if vf_first is None else int(vf_first + vf_last))
 
     # ---- phase 2: end to end through the streaming pipeline ---------------------------------
     e2e = None
@@ -1129,7 +1226,7 @@ def main():
 
     # ---- phase 4 (N > 1, the default configuration): a short job of distinct reads ---------------
     job = None
-    if world > 1 and not longtail and not rna and a.bandwidth == 500 and a.bases == 10000:
+    if short_job:
         job = run_job(ctx, job_reads, a.reads, a.bases, a.job_seed)
         rank_rec.update(job_batches=job['my_batches'], job_reads=job['my_reads'])
     rank_rec.update(host_threads=workers, waited_for_cpu_legs_s=round(t_wait_cpu, 1))
@@ -1200,7 +1297,8 @@ def main():
                        # the resident batch gave the same boundaries + status after the warm-up and after the last
                        # timed pass (every rank), and the traceback's verifier found nothing (rows, all ranks)
                        'digest_stable': None if any(r['digest_stable'] is None for r in per_rank) else all(r['digest_stable'] for r in per_rank),
-                       'tb_verify_fail_rows': sum(r['tb_verify_fail_rows'] for r in per_rank),
+                       'tb_verify_fail_rows': None if any(r['tb_verify_fail_rows'] is None for r in per_rank) else
+                                              sum(r['tb_verify_fail_rows'] for r in per_rank),
                        'parallelism': 'reads sharded over %d process(es) through a shared batch '
                                       'counter; no collective on the data path, gloo control plane' % world,
                        'devices': [r['device'] for r in per_rank], 'visible_devices': ndev,

@@ -78,7 +78,12 @@ def install(_native):
             return ms
 
         def download(self, want_norm=True):
-            return dict(status=np.zeros(self.n, np.int32))
+            n = self.n
+            n_raw = np.diff(self.raw_off)
+            return dict(status=np.zeros(n, np.int32), segs=np.arange(int(self.seg_off[-1]), dtype=np.int64),
+                        read_start=np.full(n, 7, np.int64), norm_len=n_raw - 1,
+                        norm=np.arange(self.n_raw_total) % 11 - 5.0 if want_norm else None,
+                        sv=np.tile([0.5, 2.0, -5.0, 5.0], (n, 1)), score=np.ones(n), changed=np.zeros(n, np.int32))
 
         def download_async(self, results=None, segs32=None, segs64=None, norm=None):
             if results is not None:

@@ -1,22 +1,25 @@
 """`python bench.py --gpus 2` end to end on CPU with a stub engine: the self-launch, the gloo
 control plane, the shared work queue, the feeder / streaming slots and the JSON line of an N > 1
-run (cpu_baseline, roofline and per_rank must be there at every N)."""
+run (with --full, cpu_baseline, roofline and per_rank must be there at every N), and the plain run:
+the headline figures alone, and --dump-outputs."""
 import os
 import sys
 import json
 import subprocess
 
+import numpy as np
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 
 
-def _run(extra):
+def _run(extra, full=True):
     env = dict(os.environ)
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT', 'TBA_STORE_PORT'):
         env.pop(k, None)
     out = subprocess.run(
         [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '1', '--reads', '12',
          '--bases', '400', '--cpu-sample', '2', '--cpu-per-core', '0', '--stream-batch', '5',
-         '--engine-stub', os.path.join(ROOT, 'tests', 'stub_engine.py')] + extra,
+         '--engine-stub', os.path.join(ROOT, 'tests', 'stub_engine.py')] + (['--full'] if full else []) + extra,
         cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [x for x in out.stdout.decode().splitlines() if x.strip()]
@@ -62,7 +65,7 @@ def test_four_ranks_under_torch_distributed_run():
         [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '4',
          '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'),
          '--gpus', '4', '--steps', '3', '--warmup', '1', '--reads', '12', '--bases', '400', '--cpu-sample', '2',
-         '--cpu-per-core', '0', '--stream-batch', '5', '--engine-stub',
+         '--cpu-per-core', '0', '--stream-batch', '5', '--full', '--engine-stub',
          os.path.join(ROOT, 'tests', 'stub_engine.py')],
         cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
@@ -118,6 +121,43 @@ def test_default_two_rank_run_carries_the_distinct_read_job():
     job = r['distinct_read_job']
     assert job['job_reads'] == 24 and job['reads_done'] == 24 and job['batches'] == 8
     assert sum(x['job_reads'] for x in r['per_rank']) == 24
+
+
+def test_plain_run_measures_the_headline_only():
+    """without --full: no CPU legs, no digest, no end-to-end / API / counter legs, no N > 1 job; --steps
+    timed passes and the keys every consumer of the line reads"""
+    for extra in ([], ['--gpus', '2']):
+        r = _run(['--steps', '5'] + extra, full=False)
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup'):
+            assert k in r, k
+        assert r['unit'] == 'reads/s' and r['higher_is_better'] is True and r['dtype'] == 'f64'
+        assert r['steps'] == 5 and sum(x['steps'] for x in r['per_rank']) == 5 * r['n_gpus']
+        assert r['value'] > 0 and r['ms_per_step'] > 0
+        assert 'cpu_baseline' not in r and r['end_to_end'] is None and r['api'] is None
+        assert r['distinct_read_job'] is None and r['roofline']['traffic'] is None
+        assert r['config']['digest_stable'] is None and r['config']['tb_verify_fail_rows'] is None
+        assert r['config']['setup_s']['cpu_legs'] < 1.0 and r['config']['success_rate'] == 1.0
+
+
+def test_dump_outputs_is_float_bounded_and_repeatable(tmp_path):
+    """--dump-outputs DIR: the last timed pass's outputs as float .npy files within 64 MB, the same
+    for two runs with the same arguments"""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ('run%d' % k)
+        _run(['--dump-outputs', str(d)], full=False)
+        dumps.append({f.name[:-4]: np.load(str(f)) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and 'status' in a and 'norm_signal' in a and 'segs' in a
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    assert a['read_index'].tolist() == list(range(12)) and a['status'].shape == (12,)
+    assert a['scale_values'].shape == (12, 4)
+    off = a['norm_signal_offsets']
+    assert off.shape == (len(a['sample_read_index']) + 1,) and off[-1] == a['norm_signal'].shape[0] > 0
+    assert a['segs_offsets'][-1] == a['segs'].shape[0] > 0
 
 
 def test_make_reads_through_shared_memory_equals_inline():

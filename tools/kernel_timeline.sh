@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 rm -rf /tmp/tr
-rocprofv3 --kernel-trace -d /tmp/tr -- python $R/bench.py --preset longtail --steps 2 --no-cpu-baseline --no-pmc --api-reads 0 --slots 3 > /tmp/tr.json 2>/dev/null
+rocprofv3 --kernel-trace -d /tmp/tr -- python $R/bench.py --full --preset longtail --steps 2 --no-cpu-baseline --no-pmc --api-reads 0 --slots 3 > /tmp/tr.json 2>/dev/null
 db=$(find /tmp/tr -name "*.db" | head -1)
 python - <<PY
 import sqlite3, json

@@ -10,11 +10,11 @@ for lib in "$@"; do
   if [ "$lib" = "-" ]; then unset TBA_LIB_PATH; else export TBA_LIB_PATH=$R/$lib; fi
   for pa in "${presets[@]}"; do
     cfg=${pa%%:*}; extra=""; [ "$pa" != "$cfg" ] && extra=${pa#*:}
-    timeout 600 python bench.py --preset $cfg --steps 8 --warmup 1 --no-pmc --no-cpu-baseline --api-reads 0 $extra 2>gpurun_out/ab_err.log | python -c "
+    timeout 600 python bench.py --full --preset $cfg --steps 8 --warmup 1 --no-pmc --no-cpu-baseline --api-reads 0 $extra 2>$out.err | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$cfg', '$extra', '$lib', 'ms_per_step %.2f' % d['ms_per_step'], 'resident %.0f' % d['value'], 'e2e', (d.get('end_to_end') or {}).get('value'), 'stage_ms', {k: round(v, 2) for k, v in d['config'].get('stage_ms', {}).items() if v > 0.3})
-" >> $out 2>&1 || tail -5 gpurun_out/ab_err.log >> $out
+" >> $out 2>&1 || tail -5 $out.err >> $out
   done
 done
 unset TBA_LIB_PATH

@@ -21,7 +21,7 @@ cd $R
 for lib in - alt_builds/lib_vgpr120.so alt_builds/lib_vgpr112.so; do
   if [ "$lib" = "-" ]; then unset TBA_LIB_PATH; else export TBA_LIB_PATH=$R/$lib; fi
   for cfg in cfg2 cfg4; do
-    timeout 400 python bench.py --preset $cfg --steps 8 --warmup 1 $Q 2>$O/ab_err.log | python -c "
+    timeout 400 python bench.py --full --preset $cfg --steps 8 --warmup 1 $Q 2>$O/ab_err.log | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$cfg', '$lib', 'ms_per_step %.2f' % d['ms_per_step'], 'resident %.0f' % d['value'], 'e2e', d.get('end_to_end', {}).get('value'), 'stage_ms', {k: round(v, 2) for k, v in d['config'].get('stage_ms', {}).items() if v > 0.3})
