@@ -28,7 +28,8 @@ INJECT_FLAGS = ['-DTBA_TB_INJECT=5']
 
 def build(force=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU): libtombo_amd.so and,
-    beside it, the fault-injection build one GPU test loads in a child process."""
+    beside it, the fault-injection build one GPU test loads in a child process.  Returns the in-tree library's
+    path: a TBA_LIB_PATH build is neither built nor checked here."""
     tree_lib = os.path.join(_HERE, 'libtombo_amd.so')
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + \
         [os.path.join(_HERE, '..', 'include', 'tombo_amd.h')]
@@ -42,7 +43,7 @@ def build(force=False):
     for path, p in jobs:
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, 'hipcc -> ' + path)
-    return LIB_PATH
+    return tree_lib
 
 
 class Params(C.Structure):
@@ -586,7 +587,6 @@ class Engine(object):
             GET_SAMP_IND: (np.int64, (n, 1000)),
             GET_TB_PARALLEL: (np.int32, n), GET_ED_FUSED: (np.int32, n), GET_DP_WORKGROUP: (np.int32, n),
             GET_ED_FORM: (np.int32, n), GET_TB_FORM: (np.int32, n), GET_TB_VERIFY_FAIL: (np.int32, n),
-            97: (np.int64, 2 * max(int(self.seg_off[-1]), 1)),  # (a -DTBA_TB_B2 experiment build: phase B's second / third array)
             GET_ED_TAKEN_POS: (np.int32, 2 * self.n_raw_total), GET_ED_N_TAKEN: (np.int64, n),
         }
         if what in (GET_VALID_CPTS, GET_EVENT_MEANS):

@@ -97,12 +97,8 @@ __global__ __launch_bounds__(256, 2) void k_detect(ReadState *rs, i64 n_reads, c
     const int tid = threadIdx.x, lane = tid & 63;
     // roles: 0 scan, 1 loader, 2 / 3 greedy.  Two workgroups share a CU, one wavefront of each per
     // SIMD: with the roles rotated by two in every other workgroup a SIMD holds one of the two heavy
-    // (greedy) wavefronts and one light one instead of two heavy ones (TBA_DT_NO_ROTATE: A/B switch)
-#ifdef TBA_DT_NO_ROTATE
-    const int wave = tid >> 6;
-#else
+    // (greedy) wavefronts and one light one instead of two heavy ones
     const int wave = ((tid >> 6) + 2 * (int)(blockIdx.x & 1)) & 3;
-#endif
     const i64 r0 = (i64)blockIdx.x * DT_READS;
     const int w = (int)dp->p.running_stat_width, w2 = 2 * w;
     if (tid < DT_READS) {
@@ -741,9 +737,7 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_detect_tt(ReadState *rs, const De
             // One wavefront against seven scorers, and the step ends when BOTH are done: at equal
             // priority the arbiter stretched this wavefront's ~3 k cycles of issue over 13 k (of a 16 k
             // step; -DTBA_PHASE_DEBUG=9).  It goes first; the scorers fill what it leaves.
-#ifndef TBA_TT_NO_PRIO
             __builtin_amdgcn_s_setprio(3);
-#endif
             const int h = lane;
             const int pos0 = P0 - 32 + 32 * h;
             const double *row = sb + 33 * h;
@@ -856,9 +850,7 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_detect_tt(ReadState *rs, const De
 #pragma unroll
             for (int d = 1; d <= R; d++) prevX[d] = (u32)__shfl((int)X[d], TT_WORDS - 2, 64);
             prev_emitted = (u32)__shfl((int)T, TT_WORDS - 1, 64);
-#ifndef TBA_TT_NO_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
         }
         TT_T1();
         __syncthreads();

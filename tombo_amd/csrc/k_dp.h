@@ -41,10 +41,6 @@ enum { DP_START_TRY = 0, DP_START_RETRY = 1, DP_MAIN = 2, DP_DIRECT = 3 };
 struct DpMultiClass { int cpl, rpw; };
 __host__ __device__ inline DpMultiClass dp_multi_class(i64 W)
 {
-#ifdef TBA_NO_DP_MULTI
-    (void)W;
-    return {0, 0};
-#else
     // Measured (MI355X, 10 k reads x 10 kb unless noted; profiles/r03_dp_multi_classes.txt):
     //   W = 100 (2 kb reads): 2 reads x 32 lanes x 4 cells 7.6 ms, 4 x 16 x 8 8.0 ms, k_dp<4> 8.4 ms
     //           (40 k reads per launch: 24.7 / 28.9 / 28.8 ms)
@@ -53,18 +49,9 @@ __host__ __device__ inline DpMultiClass dp_multi_class(i64 W)
     //   W = 300: 2 x 32 x 10 cells 62 ms (508 VALU instructions per 2-read row = 254 per read against
     //           ~290, but 2.75 waves per SIMD instead of 4 and an LDS round trip on the row chain:
     //           66 % VALU utilisation), k_dp<5> 57 ms
-    // so only the narrowest class is dispatched; -DTBA_DPM_WIDE builds the other two for A/B runs.
-#ifdef TBA_DPM_128_84
-    if (W <= 128) return {8, 4};
-#else
+    // so only the narrowest class is dispatched (the switches that built the other classes are retired).
     if (W <= 128) return {4, 2};
-#endif
-#ifdef TBA_DPM_WIDE
-    if (W <= 256) return {8, 2};
-    if (W <= 320) return {10, 2};
-#endif
     return {0, 0};
-#endif
 }
 
 // one forward pass described explicitly (per-kernel C ABI entry points, tba_c_*): same row
@@ -150,16 +137,11 @@ __host__ __device__ inline i64 mv_row_bytes(i64 W)
 #define MV_STRIP_BYTES 16
 __host__ __device__ inline int mv_strip_s0(i64 W)
 {
-#ifdef TBA_NO_MV_STRIP
-    (void)W;
-    return -1;
-#else
     const int c = cpl_class(W);
     if (!(c == 4 || c == 8 || c == 16 || c == 32)) return -1;
     const int unit = c > 16 ? c : 16;                 // dword- and lane-aligned
     const int s0 = (((int)(W / 2) - 40) / unit) * unit; // the centre (W / 2 - 1) sits ~41 cells into the strip
     return s0 >= 0 && s0 + MV_STRIP_CELLS <= 64 * c ? s0 : -1;
-#endif
 }
 
 // wave-uniform values the compiler cannot prove uniform (they come from vector loads or
@@ -209,18 +191,16 @@ __device__ __forceinline__ void shifted_row(const double (&Q)[CPL], double left,
 // diag / skip candidates of one row for band offset D (pyx:220-231, first cell pyx:392-401):
 // A[j] is cell j's diagonal source and cell j-1's skip source.  Instantiated per offset so the
 // previous row is read straight out of its registers (no renaming moves).  tk bit j: skip taken.
-// -DTBA_DP_SWEEP1_FUSED (A/B switch, off): the FIRST sweep of the stay chain inside this block, so that
-// its dependent adds are scheduled between the independent candidate arithmetic.  Measured round 5:
-// main_dp 59.97 against 59.63 ms -- with four wavefronts per SIMD the f64 pipe is busy whatever the
-// order inside one of them (tools/valu_rates.hip), and nine copies of the sweep cost instruction cache.
+// (Round 5 measured the FIRST sweep of the stay chain inside this block, so that its dependent adds are
+// scheduled between the independent candidate arithmetic: main_dp 59.97 against 59.63 ms -- with four
+// wavefronts per SIMD the f64 pipe is busy whatever the order inside one of them (tools/valu_rates.hip),
+// and nine copies of the sweep cost instruction cache.  Its switch is retired.)
 template <int CPL, int D>
 __device__ __forceinline__ void cand_row(const double (&Q)[CPL], double left,
-    const double (&z)[CPL], double skip_pen, double stay_pen, bool first_is_skip, bool lane0, double (&cv)[CPL],
-    bool (&tk)[CPL], double &exit0)
+    const double (&z)[CPL], double skip_pen, bool first_is_skip, bool lane0, double (&cv)[CPL], bool (&tk)[CPL])
 {
     double A[CPL + 1];
     shifted_row<CPL, D>(Q, left, A);
-    double x = -INFINITY;
 #pragma unroll
     for (int j = 0; j < CPL; j++) {
         const double d = A[j] + z[j];
@@ -235,11 +215,7 @@ __device__ __forceinline__ void cand_row(const double (&Q)[CPL], double left,
             cv[j] = max_f64_raw(s, d);
         }
         tk[j] = take_s;
-#ifdef TBA_DP_SWEEP1_FUSED
-        x = max_f64_raw(cv[j], (x - stay_pen) + z[j]);
-#endif
     }
-    exit0 = x;
 }
 // Q <- Q shifted by S cells (S <= CPL); returns the cell just left of the new Q[0]
 template <int CPL, int S>
@@ -285,18 +261,9 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
     constexpr int S = CPL < 8 ? CPL : 8;     // band offsets 0..S take the register-renaming path
     constexpr int RING = CPL <= 4 ? 512 : CPL <= 8 ? 1024 : CPL <= 16 ? 2048 : CPL <= 32 ? 4096 : 8192; // power of two >= 128*CPL
     constexpr int BPL = mv_bpl(CPL);
-#ifdef TBA_DP_LDS_PAD
-    // experiment: cap the kernel at fewer waves per SIMD through its LDS footprint, so that the
-    // memory-bound kernels of another sub-batch (other stream) find registers beside it
-    __shared__ double ring[RING + CPL + TBA_DP_LDS_PAD];
-#else
     __shared__ double ring[RING + CPL];      // + mirror of the first CPL slots: reads never wrap
-#endif
-#ifdef TBA_DP_VGPR_PAD
-    // experiment (profiles/r06_coresidency_ab.txt): a named clobber raises the kernel's VGPR allocation -- "v135": 136
-    // registers, three wavefronts on a SIMD and 104 registers left for another stream's kernels, LDS untouched
-    asm volatile("" ::: TBA_DP_VGPR_PAD);
-#endif
+    // (Round 6 held this kernel to three wavefronts per SIMD, by a VGPR or an LDS pad, to leave room for another
+    // stream's kernels: main_dp 69.6 / 77.5 against 65.0 ms, profiles/r06_coresidency_ab.txt.  Its switches are retired.)
     ReadState &r = rs[DIRECT ? 0 : blockIdx.x];
     if (!DIRECT && r.status != TBA_OK) return;
     const tba_params &P = dp->p;
@@ -355,7 +322,6 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         winsor = P.do_winsorize_z != 0;
         fill_masked = dp->fill_masked;
     }
-#ifndef TBA_NO_DP_PRIO
     // The SIMD's arbiter serves the oldest wavefront first.  Workgroups are dispatched in index
     // order, so the last ones of the launch -- the wavefronts its end waits for -- are the youngest
     // on their SIMDs for all of their lives: they wait while the older ones run at lone speed and
@@ -367,14 +333,10 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
     // +4 % at W = 300.)
     if (!DIRECT && mode == DP_MAIN) {
         const unsigned from_end = gridDim.x - 1u - blockIdx.x;
-#ifndef TBA_DP_PRIO_LEVELS
-#define TBA_DP_PRIO_LEVELS 3
-#endif
-        if (from_end < 1024u) __builtin_amdgcn_s_setprio(TBA_DP_PRIO_LEVELS);
-        else if (TBA_DP_PRIO_LEVELS > 1 && from_end < 2048u) __builtin_amdgcn_s_setprio(TBA_DP_PRIO_LEVELS - 1);
-        else if (TBA_DP_PRIO_LEVELS > 2 && from_end < 3072u) __builtin_amdgcn_s_setprio(TBA_DP_PRIO_LEVELS - 2);
+        if (from_end < 1024u) __builtin_amdgcn_s_setprio(3);
+        else if (from_end < 2048u) __builtin_amdgcn_s_setprio(2);
+        else if (from_end < 3072u) __builtin_amdgcn_s_setprio(1);
     }
-#endif
     // everything above came through vector loads: make it scalar once
     W = uni(W); n_rows = uni(n_rows); n_static = uni(n_static); n_ev = uni(n_ev); row0 = uni(row0);
     identity = uni(identity); winsor = uni(winsor);
@@ -458,19 +420,12 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
 
     // expected level, sd and its reciprocal of 64 rows at a time: lane l holds row blk0 + l
     // (one coalesced load and one true division per 64 rows), a row reads its lane
-#ifndef TBA_DP_DIV4
     double mu_v = 0, sd_v = 1, y_v = 1;
-#else
-    double mu_v = 0, sd_v = 1, y_v = 1, yl_v = 0;   // (yl_v: the low word of the reciprocal, div_by_recip2)
-#endif
     auto load_levels = [&](int first) {
         int rc = first + lane;
         rc = rc < n_rows ? rc : n_rows - 1;
         mu_v = rmu[rc]; sd_v = rsd[rc];
         y_v = 1.0 / sd_v;
-#ifdef TBA_DP_DIV4
-        yl_v = recip_low(sd_v, y_v);
-#endif
         // the loads end HERE, once per 64 rows: left pending, the rows' read of these registers
         // sits behind a conditional load and the compiler guards it with s_waitcnt vmcnt(0) in
         // EVERY row (which on gfx9 also waits for the previous row's stores)
@@ -516,16 +471,10 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
     auto row_step = [&](const int row, auto adapt_tag) __attribute__((always_inline)) -> bool {
         constexpr bool ADAPT = decltype(adapt_tag)::value;
         double mu = 0, sd = 1, y = 1;
-#ifdef TBA_DP_DIV4
-        double yl = 0;
-#endif
         if (!use_z) {
             const int sel = (row - row0) & 63;
             if (sel == 0 && row != row0) load_levels(row);
             mu = readlane_f64(mu_v, sel); sd = readlane_f64(sd_v, sel); y = readlane_f64(y_v, sel);
-#ifdef TBA_DP_DIV4
-            yl = readlane_f64(yl_v, sel);
-#endif
         }
         int cur_start;
         int lo, hi;
@@ -573,11 +522,7 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
             const double *er = ring + ((cur_start + RING + b0) & (RING - 1)); // + j < RING + CPL
 #pragma unroll
             for (int j = 0; j < CPL; j++) {
-#ifndef TBA_DP_DIV4
                 double pz = fabs(div_by_recip(er[j] - mu, sd, y));
-#else
-                double pz = fabs(div_by_recip2(er[j] - mu, sd, y, yl));
-#endif
                 pz = __builtin_fmin(pz, zcap);
                 z[j] = zs[j] - pz; // cells past the band: -inf - pz = -inf, stays -inf for good
             }
@@ -601,7 +546,6 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         // pp[j] is cell j's diagonal source and cell j-1's skip source
         double cv[CPL];
         bool tk[CPL];
-        double exit0 = NEG_INF;
         {
             int rem = diff_i;
             double left = NEG_INF;
@@ -609,15 +553,15 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
             const bool fs = diff_i == 0, l0 = lane == 0;
             switch (rem) {
             case 0: left = diff_i == 0 ? wave_shr1_f64(v[CPL - 1], NEG_INF) : left;
-                    cand_row<CPL, 0>(v, left, z, skip_pen, stay_pen, fs, l0, cv, tk, exit0); break;
-            case 1: cand_row<CPL, 1>(v, left, z, skip_pen, stay_pen, fs, l0, cv, tk, exit0); break;
-            case 2: if constexpr (S >= 2) cand_row<CPL, 2>(v, left, z, skip_pen, stay_pen, fs, l0, cv, tk, exit0); break;
-            case 3: if constexpr (S >= 3) cand_row<CPL, 3>(v, left, z, skip_pen, stay_pen, fs, l0, cv, tk, exit0); break;
-            case 4: if constexpr (S >= 4) cand_row<CPL, 4>(v, left, z, skip_pen, stay_pen, fs, l0, cv, tk, exit0); break;
-            case 5: if constexpr (S >= 5) cand_row<CPL, 5>(v, left, z, skip_pen, stay_pen, fs, l0, cv, tk, exit0); break;
-            case 6: if constexpr (S >= 6) cand_row<CPL, 6>(v, left, z, skip_pen, stay_pen, fs, l0, cv, tk, exit0); break;
-            case 7: if constexpr (S >= 7) cand_row<CPL, 7>(v, left, z, skip_pen, stay_pen, fs, l0, cv, tk, exit0); break;
-            default: if constexpr (S >= 8) cand_row<CPL, 8>(v, left, z, skip_pen, stay_pen, fs, l0, cv, tk, exit0); break;
+                    cand_row<CPL, 0>(v, left, z, skip_pen, fs, l0, cv, tk); break;
+            case 1: cand_row<CPL, 1>(v, left, z, skip_pen, fs, l0, cv, tk); break;
+            case 2: if constexpr (S >= 2) cand_row<CPL, 2>(v, left, z, skip_pen, fs, l0, cv, tk); break;
+            case 3: if constexpr (S >= 3) cand_row<CPL, 3>(v, left, z, skip_pen, fs, l0, cv, tk); break;
+            case 4: if constexpr (S >= 4) cand_row<CPL, 4>(v, left, z, skip_pen, fs, l0, cv, tk); break;
+            case 5: if constexpr (S >= 5) cand_row<CPL, 5>(v, left, z, skip_pen, fs, l0, cv, tk); break;
+            case 6: if constexpr (S >= 6) cand_row<CPL, 6>(v, left, z, skip_pen, fs, l0, cv, tk); break;
+            case 7: if constexpr (S >= 7) cand_row<CPL, 7>(v, left, z, skip_pen, fs, l0, cv, tk); break;
+            default: if constexpr (S >= 8) cand_row<CPL, 8>(v, left, z, skip_pen, fs, l0, cv, tk); break;
             }
         }
         // stay chain: monotone fixed-point sweeps, chunk exit values shifted one lane up.
@@ -629,7 +573,6 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         // and the cells themselves are written once, in the pass that also derives the move flags.
         // The sequence of incoming values is the same as with full sweeps, so is the sweep count.
         DP_PH(1);
-#ifndef TBA_DP_SHR_FILL
         // Band cell 0 has no stay move (pyx:392-401): nothing may come into lane 0.  Instead of
         // handing lane 0 an incoming -inf with every lane shift (two v_mov per sweep to prepare the
         // DPP destination), lane 0's z[0] is -inf for the chain from here on (the candidates above were
@@ -637,32 +580,22 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         // there, (x - stay_pen) + -inf = -inf, exactly the value the reference's missing move has.
         z[0] = lane == 0 ? NEG_INF : z[0];
         double in = lane == 0 ? 0.0 : NEG_INF;
-#define DP_SHR(x_) wave_shr1_f64_zero(x_)
-#else
-        double in = NEG_INF;
-#define DP_SHR(x_) wave_shr1_f64(x_, NEG_INF)
-#endif
         bool converged = false;
-#ifndef TBA_DP_SWEEP1_FUSED
-        {
-            double x = NEG_INF;
+        double exit0 = NEG_INF;                // sweep 1
 #pragma unroll
-            for (int j = 0; j < CPL; j++) x = max_f64_raw(cv[j], (x - stay_pen) + z[j]);
-            exit0 = x;
-        }
-#endif
+        for (int j = 0; j < CPL; j++) exit0 = max_f64_raw(cv[j], (exit0 - stay_pen) + z[j]);
 #ifdef TBA_SWEEP_STATS
         i64 sw_row = 1;
 #endif
         {
-            double nin = DP_SHR(exit0);
+            double nin = wave_shr1_f64_zero(exit0);
             for (int it = 0; it < 66; it++) { // <= 64 sweeps by induction over lanes (NaN-proof bound)
                 if (__ballot(nin != in) == 0) { converged = true; break; }
                 in = nin;
                 double c = in;
 #pragma unroll
                 for (int j = 0; j < CPL; j++) c = (c - stay_pen) + z[j];
-                nin = DP_SHR(max_f64_raw(exit0, c));
+                nin = wave_shr1_f64_zero(max_f64_raw(exit0, c));
 #ifdef TBA_SWEEP_STATS
                 sw_row++;
 #endif
@@ -671,7 +604,6 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
 #ifdef TBA_SWEEP_STATS
         sw_total += sw_row;
 #endif
-#undef DP_SHR
         if (!converged) { // only reachable with NaNs in the signal
             if (lane == 0) { if (DIRECT) job->status = TBA_INTERNAL; else r.status = TBA_INTERNAL; }
             return true;

@@ -32,25 +32,28 @@
 //     (tests/test_tb_par_model.py, CPU); on the GPU every parity test compares read_tb with the oracle's;
 //   * k_tb_par_verify, behind the kernel boundary: under every chunk top it walks the first TBR rows
 //     again from the entry above (compare only) and hands any read with a disagreement to the serial
-//     kernels, counted (ReadState.tb_verify_fail, TBA_GET_TB_VERIFY_FAIL: asserted zero by the GPU tests
-//     and by bench.py).  A status that rests on a phase B (its error, or a broken chain) is never final
-//     either: such a read is the serial kernels' too.  _trim_traceback and top_pos are written by the
-//     verifier, after it has agreed -- until then the serial walk can still start from top_pos;
+//     kernels, counted (ReadState.tb_verify_fail, TBA_GET_TB_VERIFY_FAIL: asserted zero by the GPU tests,
+//     reported by bench.py --full as tb_verify_fail_rows).  A status that rests on a phase B (its error,
+//     or a broken chain) is never final either: such a read is the serial kernels' too.  _trim_traceback
+//     and top_pos are written by the verifier, after it has agreed -- until then the serial walk can
+//     still start from top_pos;
 //   * the register allocation.  Round 5 found a few wavefronts per 10 000-read RNA batch whose result
 //     depended on the run and "fixed" them with two repair passes; round 6 found what it was
-//     (profiles/r06_traceback_rootcause.txt).  Not the handoff through memory: with read_tb poisoned
-//     before the kernel, and with phase B's stores diverted into a second array, phase B entered with
-//     the same state every run and still computed a different FIRST ROW (path one event too high in
-//     every lane of the wavefront where the move was a diagonal) -- a computation, not a stale load.
+//     (profiles/r06_traceback_rootcause.txt; the experiment builds of that hunt are retired).  Not the
+//     handoff through memory: with read_tb poisoned before the kernel, and with phase B's stores
+//     diverted into a second array, phase B entered with the same state every run and still computed a
+//     different FIRST ROW (path one event too high in every lane of the wavefront where the move was a
+//     diagonal) -- a computation, not a stale load.
 //     The same machine code (hand-assembled, tools/asm_variant.py) fails in 8-16 of 24 runs when the
 //     kernel descriptor allocates 224 VGPRs (28 granules: what the compiler had chosen, two wavefronts
 //     per SIMD) and in 0 of 24 with 225-256, the instructions untouched; s_nop / s_waitcnt padding
-//     anywhere in the failing binary changes nothing.  The moment is known too: in every failing
-//     wavefront the SIMD's other wavefront terminated inside the failing one's phase B (time stamps,
-//     -DTBA_TB_TIMES) -- that is what "only second residents" was.  Idle and read-verify probes of a 224-register
-//     allocation (tools/vgpr_probe) see no register change, so the trigger needs this kernel's
-//     activity and is not understood further; the kernels here keep away from that allocation
-//     (TBP_NOT_224_VGPRS, and tests/test_kernel_resources.py holds every kernel of the library to it).
+//     anywhere in the failing binary changes nothing, and with one wavefront per SIMD (LDS padding) it
+//     never failed.  The moment is known too: in every failing wavefront the SIMD's other wavefront
+//     terminated inside the failing one's phase B (time stamps per wavefront) -- that is what "only
+//     second residents" was.  Idle and read-verify probes of a 224-register allocation
+//     (tools/vgpr_probe) see no register change, so the trigger needs this kernel's activity and is
+//     not understood further; the kernels here keep away from that allocation (TBP_NOT_224_VGPRS, and
+//     tests/test_kernel_resources.py holds every kernel of the library to it).
 #pragma once
 #include "k_dp.h"
 
@@ -69,17 +72,6 @@
 #define TBP_NOT_224_VGPRS() ((void)0)
 #else
 #define TBP_NOT_224_VGPRS() asm volatile("" ::: "v231")
-#endif
-// Experiment builds of the round-6 hunt (tools/tb_hunt.py): -DTBA_TB_B2 diverts phase B's stores into a
-// second array behind read_tb and records the state every lane enters phase B with in a third
-// (read_tb is allocated three arrays long), so that what phase B computed can be compared from run to
-// run without phase A's values in the way; -DTBA_TB_WAVES1 pads the workgroup with LDS until only one
-// wavefront fits on a SIMD (never failed).  The results of such a build are NOT the traceback.
-#ifdef TBA_TB_B2
-__device__ i64 TBA_TB_B2_OFF;
-#define TBP_B_STORE(tb_, i_, v_) ((tb_)[(i_) + TBA_TB_B2_OFF] = (v_))
-#else
-#define TBP_B_STORE(tb_, i_, v_) ((tb_)[(i_)] = (v_))
 #endif
 enum { TBP_A = 0, TBP_B = 1, TBP_V = 2 };
 
@@ -224,7 +216,7 @@ __device__ __forceinline__ void tbp_block(const unsigned char *mv, int rowb, int
                 if (VER) { if (oldv[k] != cur_ev + 1) ++*dbg_stores; }
                 else if (EXT && rr - 1 >= cmp_lo && oldv[k] == cur_ev + 1) merged_row = rr - 1;
                 else {
-                    if (EXT) TBP_B_STORE(tb, rr - 1, cur_ev + 1); else { sa = true; sv = cur_ev + 1; }
+                    if (EXT) tb[rr - 1] = cur_ev + 1; else { sa = true; sv = cur_ev + 1; }
                     if (EXT && dbg_stores) ++*dbg_stores;
                 }
             }
@@ -272,15 +264,6 @@ __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, 
     constexpr int RPW = 64 / LPR;
     const int lane = threadIdx.x, g = lane / LPR, c = lane % LPR, gbase = g * LPR;
     TBP_NOT_224_VGPRS();
-#ifdef TBA_TB_WAVES1
-    __shared__ volatile int occ_pad[40 * 256];      // (40 KB per one-wavefront workgroup: four wavefronts on a CU)
-    if (n_reads < 0) occ_pad[lane] = lane;
-#endif
-#ifdef TBA_TB_TIMES
-    // (experiment: when and where the wavefront ran -- start / end on the 100 MHz counter and HW_ID into the read's dbg[],
-    // to see which wavefronts shared a SIMD with one that failed; profiles/r06_traceback_rootcause.txt)
-    const i64 tt0 = (i64)__builtin_amdgcn_s_memrealtime();
-#endif
     const i64 slot = (i64)blockIdx.x * RPW + g;
     const bool have = slot < n_reads;
     const i64 ri = have ? (idx ? (i64)idx[slot] : slot) : 0;
@@ -339,9 +322,6 @@ __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, 
     const i64 lo2 = c + 1 >= n_chunks - 1 || lo - L < 0 ? 0 : lo - L; // lo of chunk c + 1
     i64 merged_row = TBP_NONE;
     int rcB = TBA_OK;
-#ifdef TBA_TB_TIMES
-    const i64 ttB0 = (i64)__builtin_amdgcn_s_memrealtime();
-#endif
 #if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 12
     int dbg_st = 0;
     int *dbg_stp = &dbg_st;
@@ -353,9 +333,6 @@ __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, 
         bool walking = ext;
         if (ext && cur == nxt_start) { merged_row = lo; walking = false; } // (entering row lo = its hi)
         i64 r0 = lo;
-#ifdef TBA_TB_B2
-        if (ext) tb[lo + 2 * TBA_TB_B2_OFF] = cur | ((i64)guess << 40);   // (third array: the state phase B starts from)
-#endif
         while (__any(walking)) {
             if (walking) {
                 tbp_block<TBP_B>(mv, rowb, roww, st, Wi, thresh, r0, lo2, cur, guess, rcB, tb, viol_lo, nxt_wrote_lo, merged_row, strip, strip_s0, n_stat, dbg_stp);
@@ -364,9 +341,6 @@ __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, 
             }
         }
     }
-#ifdef TBA_TB_TIMES
-    const i64 ttB1 = (i64)__builtin_amdgcn_s_memrealtime();
-#endif
 #ifdef TBA_TB_INJECT
     // (test build, libtombo_amd_inject.so: the round-5 fault made deterministic -- the first row under the second
     // chunk top of every TBA_TB_INJECT-th read comes out one event too high; tests/test_gpu_determinism.py
@@ -407,19 +381,6 @@ __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, 
     // the read to the serial kernels (tb_done stays 0, top_pos untouched); a finished chain goes to
     // k_tb_par_verify (tb_done = 2), which trims.  An error of a phase A on the true path is the
     // serial walk's own error at that row.
-#ifdef TBA_TB_DRAIN
-    // (experiment: no load of this wavefront is still in flight when it terminates -- the rows a phase B prefetched and
-    // never looked at are otherwise pending at s_endpgm)
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
-#ifdef TBA_TB_TIMES
-    if (have && c == 0) {
-        r.dbg[0] = tt0; r.dbg[1] = (i64)__builtin_amdgcn_s_memrealtime();
-        r.dbg[2] = (i64)(u32)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |   // HW_ID
-                   ((i64)(u32)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32); // XCC_ID
-        r.dbg[3] = (i64)blockIdx.x; r.dbg[4] = ttB0; r.dbg[5] = ttB1;
-    }
-#endif
     if (!on || c != 0 || broken || (status != TBA_OK && from_b)) return;
     r.tb_form = LPR; // TBA_TB_FORM_PAR16 / TBA_TB_FORM_PAR64
     if (status != TBA_OK) { r.tb_done = 1; r.status = status; return; }

@@ -148,8 +148,9 @@ __device__ __forceinline__ double div_by_recip(double a, double b, double y)
 // div_by_recip.  Not three instructions: a quotient of two doubles can sit 2^-107 from a rounding
 // boundary, closer than q0's error bound.  100 M random and edge quotients equal a / b on the host
 // (gcc fma), and tests/test_gpu_kernel_abi.py::test_row_constant_division_is_ieee holds both forms.
-// k_dp uses it under -DTBA_DP_DIV4 only: eight float64 instructions less per row and two v_readlane
-// more came out 1.0 ms SLOWER on cfg2 (profiles/r06_k_dp_division_ab.txt).
+// No kernel uses it: in k_dp, eight float64 instructions less per row and two v_readlane more came out
+// 1.0 ms SLOWER on cfg2 (profiles/r06_k_dp_division_ab.txt; the switch that built that form is retired).
+// tba_selftest_approx_quotient keeps it tested.
 __device__ __forceinline__ double div_by_recip2(double a, double b, double yh, double yl)
 {
     const double p = a * yl;

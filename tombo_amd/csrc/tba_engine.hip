@@ -373,11 +373,7 @@ static void for_each_batch_buffer(tba_engine *e, const tba_params *p, const tba_
     BUF(d_bst, Bt * 8);
     BUF(d_lo, Bt * 4);
     BUF(d_hi, Bt * 4);
-#ifdef TBA_TB_B2
-    BUF(d_readtb, (Bt + N) * 8 * 3);
-#else
     BUF(d_readtb, (Bt + N) * 8);
-#endif
     BUF(d_dpsegs, (Bt + N) * 8);
     BUF(d_segs, (Bt + N) * 8);
     BUF(d_win, (Bt + N) * 24);
@@ -595,10 +591,7 @@ static void launch_dp_multi_t(tba_engine *e)
 static void launch_dp_multi(tba_engine *e)
 {
     const DpMultiClass c = dp_multi_class(e->hp.p.bandwidth);
-    if (c.cpl == 8 && c.rpw == 4) launch_dp_multi_t<8, 4>(e);
-    else if (c.cpl == 4 && c.rpw == 2) launch_dp_multi_t<4, 2>(e);
-    else if (c.cpl == 8 && c.rpw == 2) launch_dp_multi_t<8, 2>(e);
-    else if (c.cpl == 10 && c.rpw == 2) launch_dp_multi_t<10, 2>(e);
+    if (c.cpl == 4 && c.rpw == 2) launch_dp_multi_t<4, 2>(e);
 }
 static void launch_dp(tba_engine *e, int cpl, int mode)
 {
@@ -647,19 +640,14 @@ static int enqueue_stages(tba_engine *e, int first, int last)
     const bool rna = P.use_t_test_seg != 0;
     const int rdt = e->raw_dtype;
     HIP_TRY(hipEventRecord(e->ev[15], s));                 // start of the sequence (the `total` bracket)
-    // A full run forks the side stream here (-DTBA_NO_SIDE_STREAM / TBA_NO_SIDE_STREAM=1: everything on
-    // the main stream, in this order); a partial run (stepwise API) stays on one stream.
-#ifdef TBA_NO_SIDE_STREAM
-    const bool side = false;
-    e->last_side = false;
-#else
+    // A full run forks the side stream here (TBA_NO_SIDE_STREAM=1: everything on the main stream, in
+    // this order); a partial run (stepwise API) stays on one stream.
     static const bool side_off = getenv("TBA_NO_SIDE_STREAM") != nullptr;
     const bool side = !side_off && first == TBA_STAGE_SEGMENT && last == TBA_STAGE_RESCALE && e->side_mode != 0 &&
                       (e->side_mode == 1 || (e->device < TBA_MAX_DEVICES &&
                        std::max(e->n_sharing, g_live_engines[e->device].load()) <= side_stream_max_engines()));
     e->last_side = side;
     if (side && !e->stream2) HIP_TRY(hipStreamCreate(&e->stream2)); // (created on first use: a stream takes a queue slot)
-#endif
     hipStream_t s2 = side ? e->stream2 : s;
     if (side) {
         HIP_TRY(hipEventRecord(e->ev_fork, s));
@@ -696,21 +684,13 @@ static int enqueue_stages(tba_engine *e, int first, int last)
     const bool fused_scores = 2 * P.running_stat_width <= 64; // cumsum + scores in one kernel
     // DNA defaults: the scores never reach memory (k_detect.h); what that form leaves (flagged reads)
     // goes through the kernels below as before
-#ifdef TBA_NO_FUSED_DETECT
-    const bool fused_detect = false;
-#else
     const bool fused_detect = !rna && 2 * P.running_stat_width <= DT_W2MAX && P.min_obs_per_base == 3;
-#endif
     // A handful of reads cannot hide the scan's serial chain behind each other: k_detect /
     // k_cumsum_scores pay a pipeline step (barrier, memory round trip, greedy: ~7 us) per 128 samples
     // whatever the batch, 5 ms for a 10 kb read; a workgroup per read (k_long.h: the step is 1 856
     // dependent adds long) does the same in 0.5 ms.  (resquiggle_read, a batch of one: 20.4 -> 16 ms.)
     const bool wg_scan = !rna && fused_scores && n <= e->small_batch && (size_t)n * 4 <= e->d_order.cap;
-#ifdef TBA_NO_FUSED_DETECT
-    const bool fused_tt = false;
-#else
     const bool fused_tt = rna && P.min_obs_per_base == 6 && P.running_stat_width <= TT_MAXW; // RNA defaults: radius 5
-#endif
     const int only_flagged = (fused_detect && !wg_scan) || fused_tt ? 1 : 0;
     // (with k_detect on the way its loader writes the normalised signal: k_normalize only finds the
     // scale values then, and normalises the long reads, which k_detect leaves to k_long.h)
@@ -800,22 +780,9 @@ static int enqueue_stages(tba_engine *e, int first, int last)
     }
     MARK(); // 10 main tb
     if (ON(TBA_STAGE_ASSIGN)) {
-#ifndef TBA_NO_TB_PAR
         // rows of a read over several lanes (k_tb_par.h): 16 lanes per read when the reads fill the
         // machine, a wavefront per read for small batches and for the long reads; what it leaves
         // (static bands, failed verification) is walked by the lane-per-read kernels below
-#ifdef TBA_TB_POISON
-        // (experiment build: read_tb holds the previous run's finished paths -- take them away, so that nothing
-        // stale can compare equal; profiles/r06_traceback_rootcause.txt)
-        HIP_TRY(hipMemsetAsync(e->d_readtb.p, 0xFF, (size_t)(e->B_tot + e->n_reads) * 8, s));
-#endif
-#ifdef TBA_TB_B2
-        {   // (experiment build: d_readtb is three arrays long -- read_tb, phase B's stores, phase B's entry states)
-            const i64 off_words = (i64)(e->B_tot + e->n_reads);
-            HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(TBA_TB_B2_OFF), &off_words, sizeof(off_words)));
-            HIP_TRY(hipMemsetAsync(e->d_readtb.as<i64>() + off_words, 0xFF, (size_t)off_words * 16, s));
-        }
-#endif
         if (n > e->tb_wave_below) k_main_tb_par<16><<<(unsigned)((n + 3) / 4), 64, 0, s>>>(rs, n, nullptr, dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
         else k_main_tb_par<64><<<nb, 64, 0, s>>>(rs, n, nullptr, dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
         if (e->n_long > 0 && n > e->tb_wave_below) k_main_tb_par<64><<<(unsigned)e->n_long, 64, 0, s>>>(rs, e->n_long, e->d_long.as<i32>(), dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
@@ -825,7 +792,6 @@ static int enqueue_stages(tba_engine *e, int first, int last)
         if (n > e->tb_wave_below) k_tb_par_verify<16><<<(unsigned)((n + 3) / 4), 64, 0, s>>>(rs, n, nullptr, dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
         else k_tb_par_verify<64><<<nb, 64, 0, s>>>(rs, n, nullptr, dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
         if (e->n_long > 0 && n > e->tb_wave_below) k_tb_par_verify<64><<<(unsigned)e->n_long, 64, 0, s>>>(rs, e->n_long, e->d_long.as<i32>(), dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
-#endif
 #endif
         k_main_tb<<<(unsigned)((n + TB_LANES - 1) / TB_LANES), TB_LANES, 0, s>>>(rs, n, dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
         if (e->n_long > 0) k_main_tb_long<<<(unsigned)e->n_long, 64, 0, s>>>(rs, e->d_long.as<i32>(), dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
@@ -1102,13 +1068,6 @@ extern "C" int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_byt
         HIP_TRY(hipMemcpy(rs.data(), e->d_rs.p, N * sizeof(ReadState), hipMemcpyDeviceToHost));
         return 0;
     };
-#ifdef TBA_TB_B2
-    if (what == 97) { // phase B's second and third array (experiment build)
-        const size_t words = (size_t)(e->B_tot + e->n_reads);
-        HIP_TRY(hipMemcpy(out, e->d_readtb.as<i64>() + words, std::min((size_t)out_bytes, words * 16), hipMemcpyDeviceToHost));
-        return 0;
-    }
-#endif
     switch (what) {
     case TBA_GET_VALID_CPTS: return copy(e->d_cpts, (size_t)e->E_tot * 8);
     case TBA_GET_EVENT_MEANS: return copy(e->d_evm, (size_t)e->E_tot * 8);

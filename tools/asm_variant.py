@@ -30,47 +30,14 @@ def edit(lines, variant):
         return lines, 0
     if variant.startswith('L1_'):
         k = next(i for i in range(pa, pb) if re.match(r'\s*v_subbrev_co_u32_e32 v64, vcc, 0, v215, vcc', lines[i]))
-        smem = ['\ts_getpc_b64 s[40:41]', '\ts_add_u32 s40, s40, TBA_TB_B2_OFF@rel32@lo+4', '\ts_addc_u32 s41, s41, TBA_TB_B2_OFF@rel32@hi+12',
-                '\ts_load_dwordx2 s[40:41], s[40:41], 0x0']
         movs = ['\tv_lshl_add_u64 v[224:225], v[88:89], 3, v[72:73]', '\tv_mov_b32_e32 v226, v216', '\tv_mov_b32_e32 v227, v215',
                 '\tv_mov_b32_e32 v228, v64', '\tv_mov_b32_e32 v229, vcc_lo', '\tv_mov_b32_e32 v230, s2', '\tv_mov_b32_e32 v231, s3']
         ins = {'L1_nop16': ['\ts_nop 7', '\ts_nop 7'], 'L1_lgkm0': ['\ts_waitcnt lgkmcnt(0)'], 'L1_vm0': ['\ts_waitcnt vmcnt(0)'],
                'L1_none_desc': [], 'L1_nop0_nodesc': ['\ts_nop 0'], 'L1_lgkm0_nodesc': ['\ts_waitcnt lgkmcnt(0)'], 'L1_nop16_nodesc': ['\ts_nop 7', '\ts_nop 7'],
-               'L1_movs': movs, 'L1_smem': smem + ['\ts_waitcnt lgkmcnt(0)'],
-               'L1_nostores': smem + movs + ['\ts_waitcnt lgkmcnt(0)', '\ts_lshl_b64 s[40:41], s[40:41], 4', '\tv_lshl_add_u64 v[224:225], s[40:41], 0, v[224:225]']}[variant]
+               'L1_movs': movs}[variant]
         lines = lines[:k + 1] + ins + lines[k + 1:]
         d = next(i for i, l in enumerate(lines) if l.strip().startswith('.amdhsa_kernel ' + KERNEL))
         for i in range(d, d + 40 if not variant.endswith('_nodesc') else d):
-            lines[i] = lines[i].replace('.amdhsa_next_free_vgpr 224', '.amdhsa_next_free_vgpr 232').replace(
-                '.amdhsa_accum_offset 224', '.amdhsa_accum_offset 232').replace('.amdhsa_next_free_sgpr 40', '.amdhsa_next_free_sgpr 42')
-        return lines, len(ins)
-    if variant == 'trace_m':
-        # row 0 of phase B: what the move selection produced, stored into the B2 build's third array under the
-        # entry state (slots lo-1 .. lo-3 of the boundary): m | bp << 32, bp' | vcc_lo << 32, s[2:3]
-        k = next(i for i in range(pa, pb) if re.match(r'\s*v_subbrev_co_u32_e32 v64, vcc, 0, v215, vcc', lines[i]))
-        ins = """	s_getpc_b64 s[40:41]
-	s_add_u32 s40, s40, TBA_TB_B2_OFF@rel32@lo+4
-	s_addc_u32 s41, s41, TBA_TB_B2_OFF@rel32@hi+12
-	s_load_dwordx2 s[40:41], s[40:41], 0x0
-	v_lshl_add_u64 v[224:225], v[88:89], 3, v[72:73]
-	v_mov_b32_e32 v226, v216
-	v_mov_b32_e32 v227, v215
-	v_mov_b32_e32 v228, v64
-	v_mov_b32_e32 v229, vcc_lo
-	v_mov_b32_e32 v230, s2
-	v_mov_b32_e32 v231, s3
-	s_waitcnt lgkmcnt(0)
-	s_lshl_b64 s[40:41], s[40:41], 4
-	v_lshl_add_u64 v[224:225], s[40:41], 0, v[224:225]
-	global_store_dwordx2 v[224:225], v[226:227], off offset:-8
-	global_store_dwordx2 v[224:225], v[228:229], off offset:-16
-	global_store_dwordx2 v[224:225], v[230:231], off offset:-24""".split('\n')
-        lines = lines[:k + 1] + ins + lines[k + 1:]
-        lines = [l.replace('.amdhsa_next_free_vgpr 224', '.amdhsa_next_free_vgpr 232').replace('.amdhsa_accum_offset 224', '.amdhsa_accum_offset 232')
-                 .replace('.amdhsa_next_free_sgpr 40', '.amdhsa_next_free_sgpr 42') if a < 0 else l for l in lines]
-        # (the kernel descriptor of this kernel only)
-        d = next(i for i, l in enumerate(lines) if l.strip().startswith('.amdhsa_kernel ' + KERNEL))
-        for i in range(d, d + 40):
             lines[i] = lines[i].replace('.amdhsa_next_free_vgpr 224', '.amdhsa_next_free_vgpr 232').replace(
                 '.amdhsa_accum_offset 224', '.amdhsa_accum_offset 232').replace('.amdhsa_next_free_sgpr 40', '.amdhsa_next_free_sgpr 42')
         return lines, len(ins)

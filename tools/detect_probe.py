@@ -1,5 +1,5 @@
 """Event detection of one synthetic batch under the library TBA_LIB_PATH names: change points,
-fused-path flags and stage times into an .npz (compare two builds: fused / -DTBA_NO_FUSED_DETECT).
+fused-path flags and stage times into an .npz (compare the runs of two builds).
 python tools/detect_probe.py out.npz [n_reads] [n_bases] [dac]"""
 import os
 import sys

@@ -1,7 +1,7 @@
 """Latency of a lone read: `resquiggle_read` (batch of one, 10 kb DNA, W = 500) called back to back,
-and the main-DP stage time inside it -- at the clocks the idle-ish GPU picks by itself and, when
-`--pin` is given, again after `rocm-smi --setperflevel high` (needs root; the setting dies with
-the box).  A lone wavefront is latency bound, so its row time follows the shader clock directly."""
+and the main-DP stage time inside it, at the clocks the idle-ish GPU picks by itself (reported read-only
+through `rocm-smi --showclocks`).  A lone wavefront is latency bound, so its row time follows the shader
+clock directly."""
 import os
 import sys
 import time
@@ -43,14 +43,6 @@ def main():
     params = ts.load_resquiggle_parameters(samp)._replace(bandwidth=500)
     mrs = [synth.synth_map_res(model, 10000, 300 + k, **synth.DNA_SYNTH) for k in range(24)]
     measure('default clocks', mrs, model, params, samp)
-    if '--pin' in sys.argv:
-        r = subprocess.run(['rocm-smi', '--setperflevel', 'high'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                           timeout=60)
-        print('setperflevel high: rc %d %s' % (r.returncode, r.stdout.decode().strip().replace('\n', ' ')[:200]))
-        time.sleep(1.0)
-        measure('perf level high', mrs, model, params, samp)
-        subprocess.run(['rocm-smi', '--setperflevel', 'auto'], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
-                       timeout=60)
 
 
 if __name__ == '__main__':

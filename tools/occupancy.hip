@@ -46,9 +46,6 @@ int main()
     report("k_dp<5,false>", k_dp<5, false>, 64);
     report("k_dp<12,false>", k_dp<12, false>, 64);
     report("k_dp_multi<4,2>", k_dp_multi<4, 2>, 64);
-    report("k_dp_multi<8,4>", k_dp_multi<8, 4>, 64);
-    report("k_dp_multi<8,2>", k_dp_multi<8, 2>, 64);
-    report("k_dp_multi<10,2>", k_dp_multi<10, 2>, 64);
     report("k_cumsum_scores<32,i16,1>", k_cumsum_scores<32, int16_t, 1>, 256);
     report("k_stall_metric<7>", k_stall_metric<7>, 256);
     report("k_cumsum_scores_long<f64,0>", k_cumsum_scores_long<double, 0>, 256);
