@@ -1,6 +1,8 @@
 """GPU: the per-kernel C ABI entry points (tba_c_*, bound with the Cython module's names in
 tombo_amd/_c_dynamic_programming.py and _c_helper.py) against the oracle's kernel-level
 restatements, on data from a synthetic read."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -434,3 +436,203 @@ def test_llh_ratio_kernels_match_reference_vectors():
             <= 1e-12 * max(1.0, abs(g['llh_var'][i]))
         assert abs(ch.c_calc_scaled_llh_ratio_const_var(m[sl], r[sl], a[sl], rv[i], sf, hf, hp)
                    - g['llh_scaled'][i]) <= 1e-12 * max(1.0, abs(g['llh_scaled'][i]))
+
+
+# ---- host-side argument checks and early returns of the per-kernel entries ---------------------
+# Each row passes one bad input straight to the C entry (the Python wrappers reject most of these
+# before the call) and pins the return code and the tba_last_error() text.  Every call is either
+# rejected on the host or runs a normal small kernel.  A row whose expected text is None must not
+# touch the last error: it is set to a sentinel before the call.
+E_ARG, INTERNAL = -1, 100
+_SENTINEL = 'engine is NULL'
+
+
+def _v(a):
+    return a.ctypes.data_as(C.c_void_p)  # (keeps a temporary array alive until the call returns)
+
+
+def _f(*shape):
+    return np.zeros(shape, np.float64)
+
+
+def _i(*shape):
+    return np.zeros(shape, np.int64)
+
+
+def _adaptive_fwd(L, e, b, starts, bandwidth):
+    n_bases, n_events = 10, 50
+    fwd, tb = _f((n_bases + 1) * 8), _i((n_bases + 1) * 8)
+    return L.tba_c_adaptive_banded_forward_pass_z(
+        e, _v(fwd), _v(tb), C.c_int64(n_bases), C.c_int64(bandwidth), _v(starts),
+        _v(_f(n_events)), C.c_int64(n_events), _v(_f(n_bases)), _v(np.ones(n_bases)),
+        C.c_double(0.0), C.c_double(1.0), C.c_double(1.0), C.c_int64(3), C.c_double(0.0),
+        C.c_int(0), C.c_double(5.0), None)
+
+
+def _banded_fwd(L, e, b):
+    n_bases, bw = 6, 8
+    starts = np.array([-1, 0, 1, 2, 3, 4], np.int64)
+    return L.tba_c_banded_forward_pass(e, _v(_f(n_bases, bw)), C.c_int64(n_bases), C.c_int64(bw),
+                                       _v(starts), C.c_double(1.0), C.c_double(1.0),
+                                       _v(_f(n_bases + 1, bw)), _v(_i(n_bases + 1, bw)))
+
+
+def _banded_tb(L, e, b):
+    n_bases, bw = 6, 8
+    return L.tba_c_banded_traceback(e, _v(_i(n_bases + 1, bw)), C.c_int64(n_bases), C.c_int64(bw),
+                                    _v(np.arange(n_bases, dtype=np.int64)), C.c_int64(bw),
+                                    C.c_int64(10), _v(_i(n_bases + 1)))
+
+
+def _new_means(L, e, b, stds):
+    sig, segs = _f(20), np.array([0, 5, 21], np.int64)
+    if stds:
+        return L.tba_c_new_mean_stds(e, _v(sig), C.c_int64(20), _v(segs), C.c_int64(2),
+                                     _v(_f(2)), _v(_f(2)))
+    return L.tba_c_new_means(e, _v(sig), C.c_int64(20), _v(segs), C.c_int64(2), _v(_f(2)))
+
+
+def _slopes(L, e, b):
+    n = 65536
+    return L.tba_c_compute_slopes(e, _v(_f(n)), _v(_f(n)), C.c_int64(n), C.c_double(1.0), _v(_f(1)))
+
+
+def _reg_z(L, e, b, n_b_starts, z_cap):
+    n_sig, n_bases, reg_start, reg_end = 100, 10, 2, 5
+    b_starts = np.arange(0, 110, 10, dtype=np.int64)
+    bounds, z_off = _i(2 * (reg_end - reg_start)), np.full(reg_end - reg_start + 1, -7, np.int64)
+    rc = L.tba_c_reg_z_scores(
+        e, _v(np.linspace(-1.0, 1.0, n_sig)), C.c_int64(n_sig), _v(_f(n_bases)), _v(np.ones(n_bases)),
+        C.c_int64(n_bases), _v(b_starts), C.c_int64(n_b_starts), C.c_int64(reg_start),
+        C.c_int64(reg_end), C.c_int64(0), C.c_int64(1), C.c_int(0), C.c_double(5.0), _v(bounds),
+        _v(z_off), _v(_f(max(z_cap, 1))), C.c_int64(z_cap))
+    if z_cap < 30 and n_b_starts > reg_end:  # filled before the capacity is checked
+        assert z_off.tolist() == [0, 10, 20, 30]
+        assert not bounds.any()
+    return rc
+
+
+def _base_fwd(L, e, b, b_start, b_end):
+    b_fwd, last = np.full(4, 3.5), np.full(4, 9, np.int64)
+    rc = L.tba_c_base_forward_pass(e, _v(_f(4)), C.c_int64(b_start), C.c_int64(b_end), _v(_f(2)),
+                                   C.c_int64(0), C.c_int64(2), _v(_f(2)), _v(_i(2)), C.c_int64(1),
+                                   _v(b_fwd), _v(last))
+    assert (b_fwd == 3.5).all() and (last == 9).all()  # untouched on a non-OK status
+    return rc
+
+
+def _valid_cpts(L, e, b):
+    n, width = 10, 6
+    return L.tba_c_valid_cpts_w_cap(e, _v(_f(n)), C.c_int64(n), C.c_int64(3), C.c_int64(width),
+                                    C.c_int64(2), _v(_i(2)))
+
+
+def _llh(L, e, b, kind, starts):
+    n = 10
+    return L.tba_llh_ratio_windows(e, C.c_int(kind), _v(_f(n)), _v(_f(n)), _v(_f(n)), _v(np.ones(n)),
+                                   _v(np.ones(n)), C.c_int64(n), C.c_int64(3), _v(starts),
+                                   C.c_int64(starts.shape[0]), _v(_f(3)), _v(_f(starts.shape[0])))
+
+
+def _pvals(L, e, b, off):
+    n_reads = off.shape[0] - 1
+    return L.tba_read_pvals(e, _v(_f(8)), _v(_f(8)), _v(np.ones(8)), _v(off), C.c_int64(n_reads),
+                            C.c_int64(1), C.c_int(1), C.c_double(1e-50), _v(_f(8)))
+
+
+def _stalls(L, e, b):
+    n_ints = np.full(1, -7, np.int64)
+    rc = L.tba_identify_stalls(e, _v(_f(500)), C.c_int(0), C.c_int64(500), C.c_int64(100),
+                               C.c_int64(7), C.c_int64(20), C.c_double(1.0), C.c_int64(100),
+                               C.c_int64(10), _v(_i(8)), C.c_int64(4), _v(n_ints))
+    assert n_ints[0] == -7
+    return rc
+
+
+def _division(L, e, b):
+    return L.tba_selftest_division(e, _v(_f(1)), _v(np.ones(1)), C.c_int64(0), _v(_f(1)))
+
+
+def _batch_get(L, e, b, what, short):
+    h, n = b
+    out = np.full(n, -7, np.int32)
+    nbytes = out.nbytes - (4 if short else 0)
+    rc = L.tba_batch_get(h, C.c_int(what), _v(out), C.c_int64(nbytes))
+    assert (out == -7).all()
+    return rc
+
+
+def _empty(L, e, b, fn):
+    out = np.full(3, 2.5)
+    if fn == 'tba_c_base_z_scores':
+        rc = L.tba_c_base_z_scores(e, _v(_f(3)), C.c_int64(0), C.c_double(0.0), C.c_double(1.0),
+                                   C.c_int(1), C.c_double(5.0), _v(out))
+    else:
+        rc = L.tba_c_apply_outlier_thresh(e, _v(_f(3)), C.c_int64(0), C.c_double(-1.0),
+                                          C.c_double(1.0), _v(out))
+    assert (out == 2.5).all()
+    return rc
+
+
+_DEC = np.array([0, 3, 2, 4, 5, 6, 7, 8, 9, 10], np.int64)
+_INC = np.array([0, 2, 3, 4, 5, 6, 7, 8, 9, 10], np.int64)
+_GUARD_ROWS = [
+    ('adaptive_fwd_decreasing_starts', lambda L, e, b: _adaptive_fwd(L, e, b, _DEC, 8), E_ARG,
+     'event_starts must be non-decreasing inside [0, n_events)'),
+    ('adaptive_fwd_bandwidth_1', lambda L, e, b: _adaptive_fwd(L, e, b, _INC, 1), E_ARG, 'bad arguments'),
+    ('banded_fwd_negative_start', _banded_fwd, E_ARG, 'event_starts must be non-negative and non-decreasing'),
+    ('banded_tb_band_pos', _banded_tb, E_ARG, 'bad arguments'),
+    ('new_means_past_signal', lambda L, e, b: _new_means(L, e, b, False), E_ARG,
+     'segment boundaries outside the signal'),
+    ('new_mean_stds_past_signal', lambda L, e, b: _new_means(L, e, b, True), E_ARG,
+     'segment boundaries outside the signal'),
+    ('slopes_too_many_points', _slopes, E_ARG, 'too many points'),
+    ('reg_z_region_outside', lambda L, e, b: _reg_z(L, e, b, 5, 100), E_ARG,
+     'region outside the bases / base starts'),
+    ('reg_z_cap_too_small', lambda L, e, b: _reg_z(L, e, b, 11, 5), E_ARG, 'z-score buffer too small'),
+    ('base_fwd_empty_interval', lambda L, e, b: _base_fwd(L, e, b, 3, 3), E_ARG, 'empty base interval'),
+    ('base_fwd_status_internal', lambda L, e, b: _base_fwd(L, e, b, 10, 12), INTERNAL, None),
+    ('valid_cpts_too_wide', _valid_cpts, INTERNAL, None),
+    ('llh_kind_3', lambda L, e, b: _llh(L, e, b, 3, np.array([0], np.int64)), E_ARG, 'bad arguments'),
+    ('llh_window_outside', lambda L, e, b: _llh(L, e, b, 1, np.array([0, 8], np.int64)), E_ARG,
+     'window outside the arrays'),
+    ('pvals_offset_start', lambda L, e, b: _pvals(L, e, b, np.array([1, 4, 8], np.int64)), E_ARG,
+     'offset arrays must start at 0'),
+    ('pvals_offset_decreasing', lambda L, e, b: _pvals(L, e, b, np.array([0, 5, 4], np.int64)), E_ARG,
+     'offset arrays must be non-decreasing'),
+    ('stalls_window_size', _stalls, E_ARG, 'bad stall detection parameters'),
+    ('selftest_division_n0', _division, E_ARG, 'bad arguments'),
+    ('batch_get_unknown_selector', lambda L, e, b: _batch_get(L, e, b, 1000, False), E_ARG,
+     'unknown TBA_GET_* selector'),
+    ('batch_get_short_output', lambda L, e, b: _batch_get(L, e, b, 18, True), E_ARG,  # (TBA_GET_STATUS)
+     'output buffer too small'),
+    ('base_z_scores_n0', lambda L, e, b: _empty(L, e, b, 'tba_c_base_z_scores'), 0, None),
+    ('apply_outlier_thresh_n0', lambda L, e, b: _empty(L, e, b, 'tba_c_apply_outlier_thresh'), 0, None),
+]
+
+
+@pytest.fixture(scope='module')
+def run_batch(read):
+    """a private engine holding one finished batch of the module's read (for tba_batch_get)"""
+    from tombo_amd import _native as N, tombo_stats as ts
+    eng = N.Engine(0)
+    m = read['model']
+    eng.set_model(m.level_means, m.level_sds, m.kmer_width, m.central_pos)
+    eng.upload(N.make_params(read['params']), N.make_opts(outlier_thresh=5.0),
+               [read['raw']] * 2, [ts.encode_seq(read['seq'])] * 2)
+    eng.run()
+    yield eng
+    eng.close()
+
+
+@pytest.mark.parametrize('row', _GUARD_ROWS, ids=[r[0] for r in _GUARD_ROWS])
+def test_entry_argument_checks_and_early_returns(row, run_batch):
+    from tombo_amd import _native as N
+    from tombo_amd import resquiggle as rq
+    _, call, want_rc, want_msg = row
+    L = N.lib()
+    assert L.tba_batch_sync(None) == E_ARG
+    assert L.tba_last_error().decode() == _SENTINEL
+    rc = call(L, rq.get_engine(0)._h, (run_batch._h, 2))
+    assert rc == want_rc
+    assert L.tba_last_error().decode() == (_SENTINEL if want_msg is None else want_msg)

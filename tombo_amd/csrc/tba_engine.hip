@@ -17,10 +17,12 @@
 #include "k_synth.h"
 
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 static thread_local std::string g_last_error;
@@ -593,19 +595,21 @@ static void launch_dp_multi(tba_engine *e)
     const DpMultiClass c = dp_multi_class(e->hp.p.bandwidth);
     if (c.cpl == 4 && c.rpw == 2) launch_dp_multi_t<4, 2>(e);
 }
+// the band classes of k_dp (cpl_class, k_dp.h): `list` in the order the main DP launches them;
+// dispatch(cpl, f) calls f(std::integral_constant<int, CPL>()) for the run-time class (nothing for 0)
+template <int... CPL>
+struct CplClasses {
+    static constexpr int list[] = {CPL...};
+    template <class F> static void dispatch(int cpl, F f)
+    {
+        (void)((cpl == CPL && (f(std::integral_constant<int, CPL>()), true)) || ...);
+    }
+};
+typedef CplClasses<4, 5, 8, 12, 16, 24, 32, 48> DpClasses;
+
 static void launch_dp(tba_engine *e, int cpl, int mode)
 {
-    switch (cpl) {
-    case 4: launch_dp_t<4>(e, mode); break;
-    case 5: launch_dp_t<5>(e, mode); break;
-    case 8: launch_dp_t<8>(e, mode); break;
-    case 12: launch_dp_t<12>(e, mode); break;
-    case 16: launch_dp_t<16>(e, mode); break;
-    case 24: launch_dp_t<24>(e, mode); break;
-    case 32: launch_dp_t<32>(e, mode); break;
-    case 48: launch_dp_t<48>(e, mode); break;
-    default: break;
-    }
+    DpClasses::dispatch(cpl, [&](auto c) { launch_dp_t<decltype(c)::value>(e, mode); });
 }
 
 static int enqueue_stages(tba_engine *e, int first, int last)
@@ -772,8 +776,7 @@ static int enqueue_stages(tba_engine *e, int first, int last)
     }
     MARK(); // 9 main dp
     if (ON(TBA_STAGE_ASSIGN)) {
-        const int cls[] = {4, 5, 8, 12, 16, 24, 32, 48};
-        for (int c : cls) launch_dp(e, c, DP_MAIN);
+        for (int c : DpClasses::list) launch_dp(e, c, DP_MAIN);
         launch_dp_multi(e); // narrow adaptive bands: several reads per wavefront
         if (e->wide_w) // a static band wider than every class is possible in this batch
             k_dp_wide<<<WIDE_BLOCKS, 64, 0, s>>>(rs, n, dp, e->d_evm.as<double>(), e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_bst.as<i64>(), e->d_moves.as<unsigned char>(), e->d_wide.as<double>(), e->wide_w);
@@ -1051,6 +1054,13 @@ extern "C" int tba_batch_query(tba_engine *e)
     return set_err(TBA_E_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(rc));
 }
 
+template <class T, size_t K> static std::array<T, K> to_array(const T (&a)[K])
+{
+    std::array<T, K> v;
+    std::copy(a, a + K, v.begin());
+    return v;
+}
+
 extern "C" int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_bytes)
 {
     if (!e || !e->ran || !out) return set_err(TBA_E_STATE, "no batch has been run");
@@ -1092,76 +1102,58 @@ extern "C" int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_byt
     default: break;
     }
     if (int rc = fetch_rs()) return rc;
-    if (what == TBA_GET_START_FAIL) {
-        if ((size_t)out_bytes < N * 4) return set_err(TBA_E_ARG, "output buffer too small");
-        for (size_t i = 0; i < N; i++) ((i32 *)out)[i] = rs[i].pad0;
-        return 0;
-    }
-    if (what == TBA_GET_STATUS) {
-        if ((size_t)out_bytes < N * 4) return set_err(TBA_E_ARG, "output buffer too small");
-        for (size_t i = 0; i < N; i++) ((i32 *)out)[i] = rs[i].status;
-        return 0;
-    }
-    if (what == TBA_GET_ED_FUSED) { // (by the form the kernels recorded, not by the absence of a flag)
-        if ((size_t)out_bytes < N * 4) return set_err(TBA_E_ARG, "output buffer too small");
-        for (size_t i = 0; i < N; i++)
-            ((i32 *)out)[i] = rs[i].ed_form == TBA_ED_FORM_DETECT_PICK || rs[i].ed_form == TBA_ED_FORM_DETECT_TT_PICK;
-        return 0;
-    }
-    if (what == TBA_GET_TB_PARALLEL) {
-        if ((size_t)out_bytes < N * 4) return set_err(TBA_E_ARG, "output buffer too small");
-        for (size_t i = 0; i < N; i++) ((i32 *)out)[i] = rs[i].tb_done;
-        return 0;
-    }
-    if (what == TBA_GET_ED_FORM || what == TBA_GET_TB_FORM || what == TBA_GET_TB_VERIFY_FAIL) {
-        if ((size_t)out_bytes < N * 4) return set_err(TBA_E_ARG, "output buffer too small");
-        for (size_t i = 0; i < N; i++)
-            ((i32 *)out)[i] = what == TBA_GET_ED_FORM ? rs[i].ed_form : what == TBA_GET_TB_FORM ? rs[i].tb_form : rs[i].tb_verify_fail;
-        return 0;
-    }
-    if (what == TBA_GET_DP_WORKGROUP) {
-        if ((size_t)out_bytes < N * 4) return set_err(TBA_E_ARG, "output buffer too small");
-        for (size_t i = 0; i < N; i++) ((i32 *)out)[i] = rs[i].dp_wg;
-        return 0;
-    }
-    if (what == TBA_GET_ED_N_TAKEN) {
-        if ((size_t)out_bytes < N * 8) return set_err(TBA_E_ARG, "output buffer too small");
-        for (size_t i = 0; i < N; i++) ((i64 *)out)[i] = rs[i].n_taken;
-        return 0;
-    }
-    if (what == TBA_GET_N_CPTS || what == TBA_GET_DP_READ_START || what == TBA_GET_N_STALL ||
-        what == TBA_GET_STALL_OFF) {
-        if ((size_t)out_bytes < N * 8) return set_err(TBA_E_ARG, "output buffer too small");
-        for (size_t i = 0; i < N; i++)
-            ((i64 *)out)[i] = what == TBA_GET_N_CPTS ? rs[i].n_cpts : what == TBA_GET_N_STALL ? rs[i].n_stall
-                              : what == TBA_GET_STALL_OFF ? rs[i].stall_off : rs[i].dp_read_start;
-        return 0;
-    }
-    if (what == TBA_GET_SEG_SV || what == TBA_GET_START || what == TBA_GET_THEIL_SEN) {
-        if ((size_t)out_bytes < N * 32) return set_err(TBA_E_ARG, "output buffer too small");
-        double *o = (double *)out;
-        for (size_t i = 0; i < N; i++)
-            for (int k = 0; k < 4; k++)
-                o[4 * i + k] = what == TBA_GET_START ? rs[i].start_res[k]
-                               : what == TBA_GET_THEIL_SEN ? rs[i].ts[k]
-                               : (k == 0 ? rs[i].shift : k == 1 ? rs[i].scale : k == 2 ? rs[i].lower : rs[i].upper);
-        return 0;
-    }
-    if (what == TBA_GET_DEBUG_COUNTERS) { // phase cycle / sweep counters of a profiling build
-        if ((size_t)out_bytes < N * 64) return set_err(TBA_E_ARG, "output buffer too small");
-        for (size_t i = 0; i < N; i++) memcpy((char *)out + 64 * i, rs[i].dbg, 64);
-        return 0;
-    }
-    if (what == TBA_GET_PATH) {
-        if ((size_t)out_bytes < N * 16) return set_err(TBA_E_ARG, "output buffer too small");
-        i32 *o = (i32 *)out;
+    // the per-read selectors: one T per read, from the read's ReadState `r`
+    auto per_read = [&](auto get) -> int {
+        typedef decltype(get(rs[0])) T;
+        if ((size_t)out_bytes < N * sizeof(T)) return set_err(TBA_E_ARG, "output buffer too small");
         for (size_t i = 0; i < N; i++) {
-            o[4 * i + 0] = rs[i].path; o[4 * i + 1] = (i32)rs[i].n_static;
-            o[4 * i + 2] = (i32)rs[i].W; o[4 * i + 3] = rs[i].n_start_calls;
+            const T v = get(rs[i]);
+            memcpy((char *)out + i * sizeof(T), &v, sizeof(T));
         }
         return 0;
+    };
+#define PER_READ(T, ...) per_read([](const ReadState &r) -> T { return __VA_ARGS__; })
+    typedef std::array<double, 4> D4;
+    typedef std::array<i32, 4> I4;
+    typedef std::array<i64, 8> I8;
+    switch (what) {
+    case TBA_GET_START_FAIL: return PER_READ(i32, r.pad0);
+    case TBA_GET_STATUS: return PER_READ(i32, r.status);
+    // (by the form the kernels recorded, not by the absence of a flag)
+    case TBA_GET_ED_FUSED: return PER_READ(i32, r.ed_form == TBA_ED_FORM_DETECT_PICK || r.ed_form == TBA_ED_FORM_DETECT_TT_PICK);
+    case TBA_GET_TB_PARALLEL: return PER_READ(i32, r.tb_done);
+    case TBA_GET_ED_FORM: return PER_READ(i32, r.ed_form);
+    case TBA_GET_TB_FORM: return PER_READ(i32, r.tb_form);
+    case TBA_GET_TB_VERIFY_FAIL: return PER_READ(i32, r.tb_verify_fail);
+    case TBA_GET_DP_WORKGROUP: return PER_READ(i32, r.dp_wg);
+    case TBA_GET_ED_N_TAKEN: return PER_READ(i64, r.n_taken);
+    case TBA_GET_N_CPTS: return PER_READ(i64, r.n_cpts);
+    case TBA_GET_DP_READ_START: return PER_READ(i64, r.dp_read_start);
+    case TBA_GET_N_STALL: return PER_READ(i64, r.n_stall);
+    case TBA_GET_STALL_OFF: return PER_READ(i64, r.stall_off);
+    case TBA_GET_SEG_SV: return PER_READ(D4, D4{r.shift, r.scale, r.lower, r.upper});
+    case TBA_GET_START: return PER_READ(D4, to_array(r.start_res));
+    case TBA_GET_THEIL_SEN: return PER_READ(D4, to_array(r.ts));
+    case TBA_GET_PATH: return PER_READ(I4, I4{r.path, (i32)r.n_static, (i32)r.W, r.n_start_calls});
+    case TBA_GET_DEBUG_COUNTERS: return PER_READ(I8, to_array(r.dbg)); // phase cycle / sweep counters of a profiling build
+    default: break;
     }
+#undef PER_READ
     return set_err(TBA_E_ARG, "unknown TBA_GET_* selector");
+}
+
+// workgroups per read of the per-base kernels over a finished batch
+static unsigned base_blocks(const tba_engine *e) { return (unsigned)std::min<i64>(std::max<i64>((e->max_B + 255) / 256, 1), 128); }
+
+// per-base means and stds of the final signal into e->d_stat (B_tot means, then B_tot stds)
+static int launch_base_stats(tba_engine *e)
+{
+    if (e->d_stat.ensure((size_t)e->B_tot * 16)) return set_err(TBA_E_NOMEM, "hipMalloc failed");
+    double *d_m = e->d_stat.as<double>();
+    k_base_stats<<<dim3(base_blocks(e), (unsigned)e->n_reads), 256, 0, e->stream>>>(e->d_rs.as<ReadState>(),
+        e->d_dp.as<DevParams>(), e->hp.o.skip_norm_out ? nullptr : e->d_norm_out.as<double>(),
+        e->d_norm.as<double>(), e->d_segs.as<i64>(), d_m, d_m + e->B_tot);
+    return 0;
 }
 
 extern "C" int tba_batch_base_stats(tba_engine *e, double *means, double *stds, int64_t n_values)
@@ -1171,16 +1163,12 @@ extern "C" int tba_batch_base_stats(tba_engine *e, double *means, double *stds, 
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->B_tot == 0) return 0;
-    if (e->d_stat.ensure((size_t)e->B_tot * 16)) return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    double *d_m = e->d_stat.as<double>(), *d_s = d_m + e->B_tot;
-    const unsigned gB = (unsigned)std::min<i64>(std::max<i64>((e->max_B + 255) / 256, 1), 128);
-    k_base_stats<<<dim3(gB, (unsigned)e->n_reads), 256, 0, e->stream>>>(e->d_rs.as<ReadState>(),
-        e->d_dp.as<DevParams>(), e->hp.o.skip_norm_out ? nullptr : e->d_norm_out.as<double>(),
-        e->d_norm.as<double>(), e->d_segs.as<i64>(), d_m, d_s);
+    if (int rc = launch_base_stats(e)) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));
+    const double *d_m = e->d_stat.as<double>();
     HIP_TRY(hipMemcpy(means, d_m, (size_t)e->B_tot * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(stds, d_s, (size_t)e->B_tot * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(stds, d_m + e->B_tot, (size_t)e->B_tot * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1197,35 +1185,70 @@ extern "C" const char *tba_stage_name(int i) { return i >= 0 && i < N_STAGE ? ST
 // ---------------------------------------------------------------------------------------------
 // per-kernel entry points (tba_c_*): host buffers in, host buffers out, batch of one
 namespace {
-struct Tmp { // scoped device allocation
-    void *p = nullptr;
-    int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8) == hipSuccess ? 0 : 1; }
-    ~Tmp() { if (p) (void)hipFree(p); }
-    template <class T> T *as() { return (T *)p; }
+// The device scratch of one call, freed on return.  The first failure is kept (its code in `rc`,
+// its message through set_err) and turns every later step into a no-op, so an entry checks `rc`
+// once, after its buffers.  Copies block: inputs are on the device before the launches that read
+// them, outputs are read back after sync().
+struct Scratch {
+    int rc = 0;
+    std::vector<void *> bufs;
+    ~Scratch() { for (void *p : bufs) (void)hipFree(p); }
+    int hip(hipError_t err, const char *what)
+    {
+        if (err != hipSuccess && !rc) rc = set_err(TBA_E_HIP, std::string(what) + ": " + hipGetErrorString(err));
+        return rc;
+    }
+    // n elements of T (at least 8 bytes); NULL after a failure
+    template <class T> T *out(size_t n)
+    {
+        void *p = nullptr;
+        if (rc) return nullptr;
+        if (hipMalloc(&p, std::max<size_t>(n * sizeof(T), 8)) != hipSuccess) {
+            rc = set_err(TBA_E_NOMEM, "hipMalloc failed");
+            return nullptr;
+        }
+        bufs.push_back(p);
+        return (T *)p;
+    }
+    // n elements copied in from the host, followed by `pad` zeroed bytes
+    template <class T> T *in(const T *host, size_t n, size_t pad = 0)
+    {
+        char *p = out<char>(n * sizeof(T) + pad);
+        if (p && pad) hip(hipMemset(p + n * sizeof(T), 0, pad), "hipMemset");
+        if (p && !rc) hip(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
+        return rc ? nullptr : (T *)p;
+    }
+    // a zeroed status word for a kernel of k_cabi.h that reports one (read back by sync)
+    i32 *status(hipStream_t s)
+    {
+        i32 *p = out<i32>(1);
+        if (p) hip(hipMemsetAsync(p, 0, 4, s), "hipMemsetAsync");
+        return p;
+    }
+    // after the launches: their errors, then the stream.  Returns rc after a failure, else the
+    // status word (0 without one).
+    int sync(hipStream_t s, const i32 *d_status = nullptr)
+    {
+        if (rc || hip(hipGetLastError(), "hipGetLastError") || hip(hipStreamSynchronize(s), "hipStreamSynchronize")) return rc;
+        i32 st = 0;
+        if (d_status && get(&st, d_status, 1)) return rc;
+        return st;
+    }
+    // n elements back to the host (after sync); returns rc
+    template <class T> int get(T *host, const T *dev, size_t n)
+    {
+        return rc ? rc : hip(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost), "hipMemcpy");
+    }
 };
-#define C_TRY(expr) HIP_TRY(expr)
 static unsigned grid_for(i64 n) { return (unsigned)std::min<i64>(std::max<i64>((n + 255) / 256, 1), 4096); }
 
-template <int CPL>
-static void launch_direct_t(tba_engine *e, DpJob *job)
-{
-    k_dp<CPL, true><<<dim3(1), dim3(64), 0, e->stream>>>(
-        e->d_rs.as<ReadState>(), e->d_dp.as<DevParams>(), DP_DIRECT, nullptr, nullptr, nullptr,
-        nullptr, nullptr, nullptr, nullptr, 0, nullptr, job);
-}
 static void launch_direct(tba_engine *e, int cpl, DpJob *job)
 {
-    switch (cpl) {
-    case 4: launch_direct_t<4>(e, job); break;
-    case 5: launch_direct_t<5>(e, job); break;
-    case 8: launch_direct_t<8>(e, job); break;
-    case 12: launch_direct_t<12>(e, job); break;
-    case 16: launch_direct_t<16>(e, job); break;
-    case 24: launch_direct_t<24>(e, job); break;
-    case 32: launch_direct_t<32>(e, job); break;
-    case 48: launch_direct_t<48>(e, job); break;
-    default: break;
-    }
+    DpClasses::dispatch(cpl, [&](auto c) {
+        k_dp<decltype(c)::value, true><<<dim3(1), dim3(64), 0, e->stream>>>(
+            e->d_rs.as<ReadState>(), e->d_dp.as<DevParams>(), DP_DIRECT, nullptr, nullptr, nullptr,
+            nullptr, nullptr, nullptr, nullptr, 0, nullptr, job);
+    });
 }
 
 // shared by the two forward-pass entry points
@@ -1234,38 +1257,40 @@ static int run_direct_dp(tba_engine *e, DpJob hj, int cpl, i64 n_rows, i64 W, i6
 {
     const i64 stride = (i64)cpl * 64;            // forward rows
     const i64 mstride = mv_class_rowb(cpl);      // packed 2-bit move rows
-    Tmp d_fwd, d_mv, d_job;
-    if (d_fwd.alloc((size_t)(n_rows + 1) * stride * 8) || d_mv.alloc((size_t)(n_rows + 1) * mstride) ||
-        d_job.alloc(sizeof(DpJob)))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
+    Scratch sc;
+    double *d_fwd = sc.out<double>((size_t)(n_rows + 1) * stride);
+    unsigned char *d_mv = sc.out<unsigned char>((size_t)(n_rows + 1) * mstride);
+    hj.fwd_out = d_fwd;
+    hj.mv = d_mv;
+    hj.status = TBA_OK;
+    DpJob *d_job = sc.in(&hj, 1);
+    if (sc.rc) return sc.rc;
     // the kernel needs *some* ReadState / DevParams to bind its references to
     if (e->d_rs.ensure(sizeof(ReadState)) || e->d_dp.ensure(sizeof(DevParams))) return TBA_E_NOMEM;
-    hj.fwd_out = d_fwd.as<double>();
-    hj.mv = d_mv.as<unsigned char>();
-    hj.status = TBA_OK;
-    C_TRY(hipMemcpyAsync(d_job.p, &hj, sizeof(DpJob), hipMemcpyHostToDevice, e->stream));
-    launch_direct(e, cpl, d_job.as<DpJob>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipMemcpyAsync(&hj, d_job.p, sizeof(DpJob), hipMemcpyDeviceToHost, e->stream));
-    std::vector<unsigned char> mv((size_t)(n_rows + 1) * mstride);
-    C_TRY(hipMemcpyAsync(mv.data(), d_mv.p, mv.size(), hipMemcpyDeviceToHost, e->stream));
-    C_TRY(hipStreamSynchronize(e->stream));
+    launch_direct(e, cpl, d_job);
+    if (sc.sync(e->stream) || sc.get(&hj, d_job, 1)) return sc.rc;
     if (hj.status != TBA_OK) return hj.status;
+    std::vector<unsigned char> mv((size_t)(n_rows + 1) * mstride);
+    std::vector<double> fw((size_t)(n_rows + 1) * stride);
+    if (sc.get(mv.data(), d_mv, mv.size()) || sc.get(fw.data(), d_fwd, fw.size())) return sc.rc;
     // rows row0+1 .. n_rows are new (row 0 too when starting from scratch); device rows are
     // padded to the moves stride
-    {
-        std::vector<double> fw((size_t)(n_rows + 1) * stride);
-        C_TRY(hipMemcpy(fw.data(), d_fwd.p, fw.size() * 8, hipMemcpyDeviceToHost));
-        for (i64 r = row0 == 0 ? 0 : row0 + 1; r <= n_rows; r++)
-            memcpy(fwd_host + r * W, fw.data() + r * stride, (size_t)W * 8);
-    }
+    for (i64 r = row0 == 0 ? 0 : row0 + 1; r <= n_rows; r++)
+        memcpy(fwd_host + r * W, fw.data() + r * stride, (size_t)W * 8);
     for (i64 r = row0 + 1; r <= n_rows; r++)
         for (i64 b = 0; b < W; b++)
             tb_host[r * W + b] = (mv[(size_t)(r * mstride + (b >> 2))] >> (2 * (b & 3))) & 3;
-    if (starts_host)
-        C_TRY(hipMemcpy(starts_host + starts_from, hj.starts + starts_from,
-                        (size_t)(n_rows - starts_from) * 8, hipMemcpyDeviceToHost));
+    if (starts_host) return sc.get(starts_host + starts_from, hj.starts + starts_from, (size_t)(n_rows - starts_from));
     return TBA_OK;
+}
+
+// boundaries of n_segs segments: non-decreasing inside [0, n_sig]
+static int check_segs(const int64_t *segs, i64 n_segs, i64 n_sig)
+{
+    for (i64 i = 0; i <= n_segs; i++)
+        if (segs[i] < 0 || segs[i] > n_sig || (i > 0 && segs[i] < segs[i - 1]))
+            return set_err(TBA_E_ARG, "segment boundaries outside the signal");
+    return 0;
 }
 } // namespace
 
@@ -1286,29 +1311,24 @@ extern "C" int tba_c_adaptive_banded_forward_pass_z(tba_engine *e, double *fwd_p
         if (event_starts[i] < 0 || event_starts[i] >= n_events || (i > 0 && event_starts[i] < event_starts[i - 1]))
             return set_err(TBA_E_ARG, "event_starts must be non-decreasing inside [0, n_events)");
     HIP_TRY(hipSetDevice(e->device));
-    Tmp d_ev, d_mu, d_sd, d_st, d_init, d_z;
-    const size_t z_bytes = (size_t)(n_bases - start_seq_pos) * (size_t)bandwidth * 8;
-    if (z_scores && z_bytes && d_z.alloc(z_bytes)) return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    if (d_ev.alloc((size_t)n_events * 8) || d_mu.alloc((size_t)n_bases * 8) ||
-        d_sd.alloc((size_t)n_bases * 8) || d_st.alloc((size_t)n_bases * 8) ||
-        d_init.alloc((size_t)bandwidth * 8))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_ev.p, event_means, (size_t)n_events * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_mu.p, r_ref_means, (size_t)n_bases * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_sd.p, r_ref_sds, (size_t)n_bases * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_st.p, event_starts, (size_t)n_bases * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_init.p, fwd_pass + start_seq_pos * bandwidth, (size_t)bandwidth * 8, hipMemcpyHostToDevice));
+    const size_t n_z = (size_t)(n_bases - start_seq_pos) * (size_t)bandwidth;
     DpJob j;
     memset(&j, 0, sizeof(j));
+    Scratch sc;
+    j.z_out = z_scores && n_z ? sc.out<double>(n_z) : nullptr;
+    j.ev = sc.in(event_means, n_events);
+    j.mu = sc.in(r_ref_means, n_bases);
+    j.sd = sc.in(r_ref_sds, n_bases);
+    j.starts = sc.in(event_starts, n_bases);
+    j.init_row = sc.in(fwd_pass + start_seq_pos * bandwidth, bandwidth);
+    if (sc.rc) return sc.rc;
     j.W = bandwidth; j.n_rows = n_bases; j.row0 = start_seq_pos; j.n_static = start_seq_pos;
-    j.n_ev = n_events; j.ev = d_ev.as<double>(); j.mu = d_mu.as<double>(); j.sd = d_sd.as<double>();
-    j.zmat = nullptr; j.starts = d_st.as<i64>(); j.init_row = d_init.as<double>();
-    j.z_out = z_scores && z_bytes ? d_z.as<double>() : nullptr;
+    j.n_ev = n_events; j.zmat = nullptr;
     j.z_shift = z_shift; j.skip_pen = skip_pen; j.stay_pen = stay_pen; j.max_half_z = max_half_z_score;
     j.fill = mask_fill_z_score; j.winsor = do_winsorize_z ? 1 : 0;
     const int rc = run_direct_dp(e, j, cpl, n_bases, bandwidth, start_seq_pos, fwd_pass, fwd_pass_tb,
                                  event_starts, start_seq_pos);
-    if (rc == TBA_OK && j.z_out) C_TRY(hipMemcpy(z_scores, d_z.p, z_bytes, hipMemcpyDeviceToHost));
+    if (rc == TBA_OK && j.z_out) return sc.get(z_scores, j.z_out, n_z);
     return rc;
 }
 
@@ -1337,15 +1357,14 @@ extern "C" int tba_c_banded_forward_pass(tba_engine *e, const double *shifted_z_
         if (event_starts[i] < 0 || (i > 0 && event_starts[i] < event_starts[i - 1]))
             return set_err(TBA_E_ARG, "event_starts must be non-negative and non-decreasing");
     HIP_TRY(hipSetDevice(e->device));
-    Tmp d_z, d_st;
-    if (d_z.alloc((size_t)n_bases * bandwidth * 8) || d_st.alloc((size_t)n_bases * 8))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_z.p, shifted_z_scores, (size_t)n_bases * bandwidth * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_st.p, event_starts, (size_t)n_bases * 8, hipMemcpyHostToDevice));
     DpJob j;
     memset(&j, 0, sizeof(j));
+    Scratch sc;
+    j.zmat = sc.in(shifted_z_scores, (size_t)n_bases * bandwidth);
+    j.starts = sc.in(event_starts, n_bases);
+    if (sc.rc) return sc.rc;
     j.W = bandwidth; j.n_rows = n_bases; j.row0 = 0; j.n_static = n_bases; j.n_ev = 0;
-    j.zmat = d_z.as<double>(); j.starts = d_st.as<i64>(); j.init_row = nullptr;
+    j.init_row = nullptr;
     j.skip_pen = skip_pen; j.stay_pen = stay_pen;
     int rc = run_direct_dp(e, j, cpl, n_bases, bandwidth, 0, fwd_pass, fwd_pass_tb, nullptr, 0);
     if (rc == TBA_OK) // row 0 of the move matrix is never read; the reference leaves it empty
@@ -1364,20 +1383,16 @@ extern "C" int tba_c_banded_traceback(tba_engine *e, const int64_t *fwd_pass_tb,
     const size_t cells = (size_t)(n_bases + 1) * bandwidth;
     std::vector<unsigned char> mv(cells);
     for (size_t i = 0; i < cells; i++) mv[i] = (unsigned char)fwd_pass_tb[i];
-    Tmp d_mv, d_st, d_out, d_status;
-    if (d_mv.alloc(cells) || d_st.alloc((size_t)n_bases * 8) || d_out.alloc((size_t)(n_bases + 1) * 8) ||
-        d_status.alloc(4))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_mv.p, mv.data(), cells, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_st.p, event_starts, (size_t)n_bases * 8, hipMemcpyHostToDevice));
-    k_c_traceback<<<1, 64, 0, e->stream>>>(d_mv.as<unsigned char>(), bandwidth, n_bases, bandwidth,
-                                           d_st.as<i64>(), band_pos, band_boundary_thresh,
-                                           d_out.as<i64>(), d_status.as<i32>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    i32 st = 0;
-    C_TRY(hipMemcpy(&st, d_status.p, 4, hipMemcpyDeviceToHost));
-    if (st == TBA_OK) C_TRY(hipMemcpy(seq_poss, d_out.p, (size_t)(n_bases + 1) * 8, hipMemcpyDeviceToHost));
+    Scratch sc;
+    const unsigned char *d_mv = sc.in(mv.data(), cells);
+    const i64 *d_st = sc.in(event_starts, n_bases);
+    i64 *d_out = sc.out<i64>(n_bases + 1);
+    i32 *d_status = sc.status(e->stream);
+    if (sc.rc) return sc.rc;
+    k_c_traceback<<<1, 64, 0, e->stream>>>(d_mv, bandwidth, n_bases, bandwidth, d_st, band_pos,
+                                           band_boundary_thresh, d_out, d_status);
+    const int st = sc.sync(e->stream, d_status);
+    if (st == TBA_OK) return sc.get(seq_poss, d_out, n_bases + 1);
     return st;
 }
 
@@ -1387,15 +1402,14 @@ extern "C" int tba_c_base_z_scores(tba_engine *e, const double *b_sig, int64_t n
     if (!e || !b_sig || !out || n < 0) return set_err(TBA_E_ARG, "bad arguments");
     if (n == 0) return TBA_OK;
     HIP_TRY(hipSetDevice(e->device));
-    Tmp d_in, d_out;
-    if (d_in.alloc((size_t)n * 8) || d_out.alloc((size_t)n * 8)) return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_in.p, b_sig, (size_t)n * 8, hipMemcpyHostToDevice));
-    k_c_base_z_scores<<<grid_for(n), 256, 0, e->stream>>>(d_in.as<double>(), n, ref_mean, ref_sd,
-                                                          do_winsorize_z, max_half_z_score, d_out.as<double>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    C_TRY(hipMemcpy(out, d_out.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return TBA_OK;
+    Scratch sc;
+    const double *d_in = sc.in(b_sig, n);
+    double *d_out = sc.out<double>(n);
+    if (sc.rc) return sc.rc;
+    k_c_base_z_scores<<<grid_for(n), 256, 0, e->stream>>>(d_in, n, ref_mean, ref_sd,
+                                                          do_winsorize_z, max_half_z_score, d_out);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(out, d_out, n);
 }
 
 extern "C" int tba_c_new_means(tba_engine *e, const double *norm_signal, int64_t n_sig,
@@ -1404,36 +1418,30 @@ extern "C" int tba_c_new_means(tba_engine *e, const double *norm_signal, int64_t
     if (!e || !norm_signal || !new_segs || !means || n_segs < 0 || n_sig < 0)
         return set_err(TBA_E_ARG, "bad arguments");
     if (n_segs == 0) return TBA_OK;
-    for (i64 i = 0; i <= n_segs; i++)
-        if (new_segs[i] < 0 || new_segs[i] > n_sig || (i > 0 && new_segs[i] < new_segs[i - 1]))
-            return set_err(TBA_E_ARG, "segment boundaries outside the signal");
+    if (int rc = check_segs(new_segs, n_segs, n_sig)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     // the batch pipeline's own kernel on a one-read batch (k_event_means: wave-cooperative, software-
     // pipelined segment sums, k_select.h) -- the slice size picked as the batch pipeline picks it,
     // by the mean segment length (+ 64 bytes: a 16-byte access may touch the element past an odd end)
-    Tmp d_sig, d_segs, d_out, d_rs, d_dp;
-    if (d_sig.alloc((size_t)n_sig * 8 + 64) || d_segs.alloc((size_t)(n_segs + 1) * 8) || d_out.alloc((size_t)n_segs * 8) ||
-        d_rs.alloc(sizeof(ReadState)) || d_dp.alloc(sizeof(DevParams)))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
     ReadState r;
     memset(&r, 0, sizeof(r));
     r.n_raw = n_sig; r.n_cpts = n_segs + 1; r.status = TBA_OK;
     DevParams dp;
     memset(&dp, 0, sizeof(dp));
-    C_TRY(hipMemset(d_sig.p, 0, (size_t)n_sig * 8 + 64));
-    C_TRY(hipMemcpy(d_sig.p, norm_signal, (size_t)n_sig * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_segs.p, new_segs, (size_t)(n_segs + 1) * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_rs.p, &r, sizeof(r), hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_dp.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
+    Scratch sc;
+    const double *d_sig = sc.in(norm_signal, n_sig, 64);
+    const i64 *d_segs = sc.in(new_segs, n_segs + 1);
+    double *d_out = sc.out<double>(n_segs);
+    ReadState *d_rs = sc.in(&r, 1);
+    const DevParams *d_dp = sc.in(&dp, 1);
+    if (sc.rc) return sc.rc;
     const unsigned g = (unsigned)std::min<i64>(std::max<i64>((n_segs + 255) / 256, 1), 128);
     if (n_sig >= 10 * n_segs)
-        k_event_means<double, 1280><<<dim3(g, 1), 256, 0, e->stream>>>(d_rs.as<ReadState>(), d_dp.as<DevParams>(), d_sig.as<double>(), d_segs.as<i64>(), d_out.as<double>(), 0);
+        k_event_means<double, 1280><<<dim3(g, 1), 256, 0, e->stream>>>(d_rs, d_dp, d_sig, d_segs, d_out, 0);
     else
-        k_event_means<double><<<dim3(g, 1), 256, 0, e->stream>>>(d_rs.as<ReadState>(), d_dp.as<DevParams>(), d_sig.as<double>(), d_segs.as<i64>(), d_out.as<double>(), 0);
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    C_TRY(hipMemcpy(means, d_out.p, (size_t)n_segs * 8, hipMemcpyDeviceToHost));
-    return TBA_OK;
+        k_event_means<double><<<dim3(g, 1), 256, 0, e->stream>>>(d_rs, d_dp, d_sig, d_segs, d_out, 0);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(means, d_out, n_segs);
 }
 
 extern "C" int tba_c_apply_outlier_thresh(tba_engine *e, const double *sig, int64_t n,
@@ -1442,14 +1450,13 @@ extern "C" int tba_c_apply_outlier_thresh(tba_engine *e, const double *sig, int6
     if (!e || !sig || !out || n < 0) return set_err(TBA_E_ARG, "bad arguments");
     if (n == 0) return TBA_OK;
     HIP_TRY(hipSetDevice(e->device));
-    Tmp d_in, d_out;
-    if (d_in.alloc((size_t)n * 8) || d_out.alloc((size_t)n * 8)) return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_in.p, sig, (size_t)n * 8, hipMemcpyHostToDevice));
-    k_c_clip<<<grid_for(n), 256, 0, e->stream>>>(d_in.as<double>(), n, lower_lim, upper_lim, d_out.as<double>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    C_TRY(hipMemcpy(out, d_out.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return TBA_OK;
+    Scratch sc;
+    const double *d_in = sc.in(sig, n);
+    double *d_out = sc.out<double>(n);
+    if (sc.rc) return sc.rc;
+    k_c_clip<<<grid_for(n), 256, 0, e->stream>>>(d_in, n, lower_lim, upper_lim, d_out);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(out, d_out, n);
 }
 
 // the two change-point detectors run the batch kernels on a one-read batch
@@ -1460,59 +1467,58 @@ static int c_valid_cpts(tba_engine *e, const double *sig, int64_t n, int64_t min
         return set_err(TBA_E_ARG, "bad arguments");
     if ((ttest ? n - 2 * width : n + 1 - 2 * width) <= 0) return TBA_INTERNAL;
     HIP_TRY(hipSetDevice(e->device));
-    Tmp d_sig, d_csum, d_score, d_state, d_cpts, d_rs, d_dp;
-    if (d_sig.alloc((size_t)n * 8) || d_csum.alloc((size_t)(n + 1) * 8) || d_score.alloc((size_t)n * 8) ||
-        d_state.alloc((size_t)n) || d_cpts.alloc((size_t)num_cpts * 8) || d_rs.alloc(sizeof(ReadState)) ||
-        d_dp.alloc(sizeof(DevParams)))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    ReadState r;
-    memset(&r, 0, sizeof(r));
-    r.n_raw = n; r.num_events = num_cpts; r.status = TBA_OK;
-    DevParams dp;
-    memset(&dp, 0, sizeof(dp));
-    dp.p.running_stat_width = width; dp.p.min_obs_per_base = min_base_obs;
-    C_TRY(hipMemcpy(d_sig.p, sig, (size_t)n * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_rs.p, &r, sizeof(r), hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_dp.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
-    hipStream_t s = e->stream;
-    const unsigned g = grid_for(n) > 128 ? 128 : grid_for(n);
     // The score-free kernels of the batch pipeline (k_detect.h) when the engine's dispatch sends a
     // batch of one read through the throughput form (tba_engine_set_dispatch(0, ...): the parity tests
     // of this entry in both forms) and for the t-test scores at RNA's defaults; the kernels that keep
     // the scores then run on what those left (flagged reads) -- exactly the batch pipeline's sequence.
-    int only_flagged = 0;
-    if (!ttest && e->small_batch < 1 && 2 * width <= DT_W2MAX && min_base_obs == 3) {
-        // (shift 0, scale 1, no limits: the loader's normalised copy of the signal is the signal)
-        Tmp d_norm;
-        if (d_norm.alloc((size_t)(n + 2) * 8 + 64)) return set_err(TBA_E_NOMEM, "hipMalloc failed");
+    const bool detect = !ttest && e->small_batch < 1 && 2 * width <= DT_W2MAX && min_base_obs == 3;
+    const bool detect_tt = ttest && e->small_batch < 1 && min_base_obs == 6 && width <= TT_MAXW;
+    ReadState r;
+    memset(&r, 0, sizeof(r));
+    r.n_raw = n; r.num_events = num_cpts; r.status = TBA_OK;
+    if (detect) { // (shift 0, scale 1, no limits: the loader's normalised copy of the signal is the signal)
         r.shift = 0.0; r.scale = 1.0;
         r.is_long = n > TBA_LONG_RAW;
-        C_TRY(hipMemcpy(d_rs.p, &r, sizeof(r), hipMemcpyHostToDevice));
-        k_detect<2, double><<<1, 256, 0, s>>>(d_rs.as<ReadState>(), 1, d_dp.as<DevParams>(), d_sig.as<double>(), d_norm.as<double>(), d_csum.as<double>(), d_score.as<double>(), n);
-        k_pick<<<1, SEL_NT, 0, s>>>(d_rs.as<ReadState>(), d_dp.as<DevParams>(), d_csum.as<double>(), d_score.as<double>(), d_cpts.as<i64>(), 0);
-        C_TRY(hipStreamSynchronize(s)); // (d_norm is released at the end of this scope)
-        only_flagged = 1;
-    } else if (ttest && e->small_batch < 1 && min_base_obs == 6 && width <= TT_MAXW) {
-        if (width == 12) k_detect_tt<5, 12, double><<<1, SEL_NT, 0, s>>>(d_rs.as<ReadState>(), d_dp.as<DevParams>(), d_sig.as<double>(), d_csum.as<double>(), d_score.as<double>());
-        else k_detect_tt<5, 0, double><<<1, SEL_NT, 0, s>>>(d_rs.as<ReadState>(), d_dp.as<DevParams>(), d_sig.as<double>(), d_csum.as<double>(), d_score.as<double>());
-        k_pick<<<1, SEL_NT, 0, s>>>(d_rs.as<ReadState>(), d_dp.as<DevParams>(), d_csum.as<double>(), d_score.as<double>(), d_cpts.as<i64>(), 1);
-        only_flagged = 1;
     }
+    DevParams dp;
+    memset(&dp, 0, sizeof(dp));
+    dp.p.running_stat_width = width; dp.p.min_obs_per_base = min_base_obs;
+    Scratch sc;
+    const double *d_sig = sc.in(sig, n);
+    double *d_csum = sc.out<double>(n + 1);
+    double *d_score = sc.out<double>(n);
+    unsigned char *d_state = sc.out<unsigned char>(n);
+    i64 *d_cpts = sc.out<i64>(num_cpts);
+    ReadState *d_rs = sc.in(&r, 1);
+    const DevParams *d_dp = sc.in(&dp, 1);
+    if (sc.rc) return sc.rc;
+    hipStream_t s = e->stream;
+    const unsigned g = grid_for(n) > 128 ? 128 : grid_for(n);
+    if (detect) {
+        Scratch norm; // (released at the end of this scope, before the launches below)
+        double *d_norm = norm.out<double>(n + 2 + 8); // (+ 64 bytes past the n + 2 values)
+        if (norm.rc) return norm.rc;
+        k_detect<2, double><<<1, 256, 0, s>>>(d_rs, 1, d_dp, d_sig, d_norm, d_csum, d_score, n);
+        k_pick<<<1, SEL_NT, 0, s>>>(d_rs, d_dp, d_csum, d_score, d_cpts, 0);
+        if (norm.sync(s)) return norm.rc;
+    } else if (detect_tt) {
+        if (width == 12) k_detect_tt<5, 12, double><<<1, SEL_NT, 0, s>>>(d_rs, d_dp, d_sig, d_csum, d_score);
+        else k_detect_tt<5, 0, double><<<1, SEL_NT, 0, s>>>(d_rs, d_dp, d_sig, d_csum, d_score);
+        k_pick<<<1, SEL_NT, 0, s>>>(d_rs, d_dp, d_csum, d_score, d_cpts, 1);
+    }
+    const int only_flagged = detect || detect_tt ? 1 : 0;
     if (!ttest && 2 * width <= 64) { // the batch pipeline's fused form
-        k_cumsum_scores<32><<<1, 256, 0, s>>>(d_rs.as<ReadState>(), 1, d_dp.as<DevParams>(), d_sig.as<double>(), d_score.as<double>(), only_flagged);
+        k_cumsum_scores<32><<<1, 256, 0, s>>>(d_rs, 1, d_dp, d_sig, d_score, only_flagged);
     } else if (!ttest) {
-        k_cumsum<<<1, 64, 0, s>>>(d_rs.as<ReadState>(), 1, d_sig.as<double>(), d_csum.as<double>());
-        k_scores_dna<<<dim3(g, 1), 256, 0, s>>>(d_rs.as<ReadState>(), d_dp.as<DevParams>(), d_csum.as<double>(), d_score.as<double>());
+        k_cumsum<<<1, 64, 0, s>>>(d_rs, 1, d_sig, d_csum);
+        k_scores_dna<<<dim3(g, 1), 256, 0, s>>>(d_rs, d_dp, d_csum, d_score);
     } else {
-        k_scores_ttest<double><<<dim3(g, 1), 256, 0, s>>>(d_rs.as<ReadState>(), d_dp.as<DevParams>(), d_sig.as<double>(), d_score.as<double>(), only_flagged);
+        k_scores_ttest<double><<<dim3(g, 1), 256, 0, s>>>(d_rs, d_dp, d_sig, d_score, only_flagged);
     }
-    launch_peaks(min_base_obs, 1, s, d_rs.as<ReadState>(), d_dp.as<DevParams>(), d_score.as<double>(),
-                                 d_state.as<unsigned char>(), d_csum.as<double>(), d_cpts.as<i64>(), ttest, only_flagged,
-                                 ttest ? TBA_ED_FORM_TTEST_PEAKS : TBA_ED_FORM_SCORES_PEAKS);
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(s));
-    C_TRY(hipMemcpy(&r, d_rs.p, sizeof(r), hipMemcpyDeviceToHost));
-    if (r.status == TBA_OK) C_TRY(hipMemcpy(cpts, d_cpts.p, (size_t)num_cpts * 8, hipMemcpyDeviceToHost));
+    launch_peaks(min_base_obs, 1, s, d_rs, d_dp, d_score, d_state, d_csum, d_cpts, ttest, only_flagged,
+                 ttest ? TBA_ED_FORM_TTEST_PEAKS : TBA_ED_FORM_SCORES_PEAKS);
+    if (sc.sync(s) || sc.get(&r, d_rs, 1)) return sc.rc;
+    if (r.status == TBA_OK && sc.get(cpts, d_cpts, num_cpts)) return sc.rc;
     e->last_c_ed_form = r.ed_form;
     return r.status;
 }
@@ -1538,23 +1544,17 @@ extern "C" int tba_c_new_mean_stds(tba_engine *e, const double *norm_signal, int
     if (!e || !norm_signal || !new_segs || !means || !stds || n_segs < 0 || n_sig < 0)
         return set_err(TBA_E_ARG, "bad arguments");
     if (n_segs == 0) return TBA_OK;
-    for (i64 i = 0; i <= n_segs; i++)
-        if (new_segs[i] < 0 || new_segs[i] > n_sig || (i > 0 && new_segs[i] < new_segs[i - 1]))
-            return set_err(TBA_E_ARG, "segment boundaries outside the signal");
+    if (int rc = check_segs(new_segs, n_segs, n_sig)) return rc;
     HIP_TRY(hipSetDevice(e->device));
-    Tmp d_sig, d_segs, d_m, d_s;
-    if (d_sig.alloc((size_t)n_sig * 8) || d_segs.alloc((size_t)(n_segs + 1) * 8) ||
-        d_m.alloc((size_t)n_segs * 8) || d_s.alloc((size_t)n_segs * 8))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_sig.p, norm_signal, (size_t)n_sig * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_segs.p, new_segs, (size_t)(n_segs + 1) * 8, hipMemcpyHostToDevice));
-    k_c_new_mean_stds<<<grid_for(n_segs), 256, 0, e->stream>>>(d_sig.as<double>(),
-        d_segs.as<i64>(), n_segs, d_m.as<double>(), d_s.as<double>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    C_TRY(hipMemcpy(means, d_m.p, (size_t)n_segs * 8, hipMemcpyDeviceToHost));
-    C_TRY(hipMemcpy(stds, d_s.p, (size_t)n_segs * 8, hipMemcpyDeviceToHost));
-    return TBA_OK;
+    Scratch sc;
+    const double *d_sig = sc.in(norm_signal, n_sig);
+    const i64 *d_segs = sc.in(new_segs, n_segs + 1);
+    double *d_m = sc.out<double>(n_segs);
+    double *d_s = sc.out<double>(n_segs);
+    if (sc.rc) return sc.rc;
+    k_c_new_mean_stds<<<grid_for(n_segs), 256, 0, e->stream>>>(d_sig, d_segs, n_segs, d_m, d_s);
+    if (sc.sync(e->stream) || sc.get(means, d_m, n_segs)) return sc.rc;
+    return sc.get(stds, d_s, n_segs);
 }
 
 extern "C" int tba_c_compute_slopes(tba_engine *e, const double *r_event_means,
@@ -1566,17 +1566,14 @@ extern "C" int tba_c_compute_slopes(tba_engine *e, const double *r_event_means,
     if (n > 65535) return set_err(TBA_E_ARG, "too many points");
     const size_t ns = (size_t)n * (size_t)(n - 1) / 2;
     HIP_TRY(hipSetDevice(e->device));
-    Tmp d_ev, d_md, d_out;
-    if (d_ev.alloc((size_t)n * 8) || d_md.alloc((size_t)n * 8) || d_out.alloc(ns * 8))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_ev.p, r_event_means, (size_t)n * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_md.p, r_model_means, (size_t)n * 8, hipMemcpyHostToDevice));
-    k_c_compute_slopes<<<dim3((unsigned)(n - 1)), 256, 0, e->stream>>>(d_ev.as<double>(),
-        d_md.as<double>(), n, max_slope, d_out.as<double>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    C_TRY(hipMemcpy(slopes, d_out.p, ns * 8, hipMemcpyDeviceToHost));
-    return TBA_OK;
+    Scratch sc;
+    const double *d_ev = sc.in(r_event_means, n);
+    const double *d_md = sc.in(r_model_means, n);
+    double *d_out = sc.out<double>(ns);
+    if (sc.rc) return sc.rc;
+    k_c_compute_slopes<<<dim3((unsigned)(n - 1)), 256, 0, e->stream>>>(d_ev, d_md, n, max_slope, d_out);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(slopes, d_out, ns);
 }
 
 extern "C" int tba_c_reg_z_scores(tba_engine *e, const double *r_sig, int64_t n_sig,
@@ -1593,37 +1590,31 @@ extern "C" int tba_c_reg_z_scores(tba_engine *e, const double *r_sig, int64_t n_
         max_base_shift < 0)
         return set_err(TBA_E_ARG, "region outside the bases / base starts");
     HIP_TRY(hipSetDevice(e->device));
-    Tmp d_sig, d_mu, d_sd, d_bs, d_ss, d_se, d_off, d_z, d_st;
-    if (d_sig.alloc((size_t)n_sig * 8) || d_mu.alloc((size_t)n_bases * 8) ||
-        d_sd.alloc((size_t)n_bases * 8) || d_bs.alloc((size_t)n_b_starts * 8) ||
-        d_ss.alloc((size_t)reg_len * 8) || d_se.alloc((size_t)reg_len * 8) ||
-        d_off.alloc((size_t)(reg_len + 1) * 8) || d_z.alloc((size_t)z_cap * 8) || d_st.alloc(4))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_sig.p, r_sig, (size_t)n_sig * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_mu.p, r_ref_means, (size_t)n_bases * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_sd.p, r_ref_sds, (size_t)n_bases * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_bs.p, r_b_starts, (size_t)n_b_starts * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemsetAsync(d_st.p, 0, 4, e->stream));
-    k_c_reg_bounds<<<1, 64, 0, e->stream>>>(d_bs.as<i64>(), reg_start, reg_end, max_base_shift,
-        min_obs_per_base, d_ss.as<i64>(), d_se.as<i64>(), d_off.as<i64>());
-    k_c_reg_z<<<dim3((unsigned)reg_len), 64, 0, e->stream>>>(d_sig.as<double>(), n_sig,
-        d_mu.as<double>(), d_sd.as<double>(), reg_start, d_ss.as<i64>(), d_se.as<i64>(),
-        d_off.as<i64>(), z_cap, do_winsorize_z, max_half_z_score, d_z.as<double>(),
-        d_st.as<i32>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
+    Scratch sc;
+    const double *d_sig = sc.in(r_sig, n_sig);
+    const double *d_mu = sc.in(r_ref_means, n_bases);
+    const double *d_sd = sc.in(r_ref_sds, n_bases);
+    const i64 *d_bs = sc.in(r_b_starts, n_b_starts);
+    i64 *d_ss = sc.out<i64>(reg_len);
+    i64 *d_se = sc.out<i64>(reg_len);
+    i64 *d_off = sc.out<i64>(reg_len + 1);
+    double *d_z = sc.out<double>(z_cap);
+    i32 *d_st = sc.status(e->stream);
+    if (sc.rc) return sc.rc;
+    k_c_reg_bounds<<<1, 64, 0, e->stream>>>(d_bs, reg_start, reg_end, max_base_shift,
+        min_obs_per_base, d_ss, d_se, d_off);
+    k_c_reg_z<<<dim3((unsigned)reg_len), 64, 0, e->stream>>>(d_sig, n_sig, d_mu, d_sd, reg_start,
+        d_ss, d_se, d_off, z_cap, do_winsorize_z, max_half_z_score, d_z, d_st);
     std::vector<i64> ss(reg_len), se(reg_len);
-    i32 st = 0;
-    C_TRY(hipMemcpy(&st, d_st.p, 4, hipMemcpyDeviceToHost));
-    C_TRY(hipMemcpy(ss.data(), d_ss.p, (size_t)reg_len * 8, hipMemcpyDeviceToHost));
-    C_TRY(hipMemcpy(se.data(), d_se.p, (size_t)reg_len * 8, hipMemcpyDeviceToHost));
-    C_TRY(hipMemcpy(z_off, d_off.p, (size_t)(reg_len + 1) * 8, hipMemcpyDeviceToHost));
+    const int st = sc.sync(e->stream, d_st);
+    if (sc.rc || sc.get(ss.data(), d_ss, reg_len) || sc.get(se.data(), d_se, reg_len) ||
+        sc.get(z_off, d_off, reg_len + 1))
+        return sc.rc;
     if (z_off[reg_len] > z_cap) return set_err(TBA_E_ARG, "z-score buffer too small");
     if (st != 0) return set_err(TBA_E_ARG, "base intervals outside the signal");
     const i64 base = r_b_starts[reg_start];
     for (i64 i = 0; i < reg_len; i++) { bounds[2 * i] = ss[i] - base; bounds[2 * i + 1] = se[i] - base; }
-    if (z_off[reg_len] > 0)
-        C_TRY(hipMemcpy(z, d_z.p, (size_t)z_off[reg_len] * 8, hipMemcpyDeviceToHost));
+    if (z_off[reg_len] > 0) return sc.get(z, d_z, z_off[reg_len]);
     return TBA_OK;
 }
 
@@ -1638,28 +1629,21 @@ extern "C" int tba_c_base_forward_pass(tba_engine *e, const double *b_data, int6
     const i64 b_len = b_end - b_start, plen = prev_b_end - prev_b_start;
     if (b_len <= 0 || plen <= 0) return set_err(TBA_E_ARG, "empty base interval");
     HIP_TRY(hipSetDevice(e->device));
-    Tmp d_b, d_pb, d_pf, d_pl, d_cum, d_f, d_l, d_st;
-    if (d_b.alloc((size_t)b_len * 8) || d_pb.alloc((size_t)plen * 8) ||
-        d_pf.alloc((size_t)plen * 8) || d_pl.alloc((size_t)plen * 8) ||
-        d_cum.alloc((size_t)plen * 8) || d_f.alloc((size_t)b_len * 8) ||
-        d_l.alloc((size_t)b_len * 8) || d_st.alloc(4))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_b.p, b_data, (size_t)b_len * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_pb.p, prev_b_data, (size_t)plen * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_pf.p, prev_b_fwd_data, (size_t)plen * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_pl.p, prev_b_last_diag, (size_t)plen * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemsetAsync(d_st.p, 0, 4, e->stream));
-    k_c_base_forward_pass<<<1, 64, 0, e->stream>>>(d_b.as<double>(), b_start, b_end,
-        d_pb.as<double>(), prev_b_start, prev_b_end, d_pf.as<double>(), d_pl.as<i64>(),
-        min_obs_per_base, d_cum.as<double>(), d_f.as<double>(), d_l.as<i64>(), d_st.as<i32>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    i32 st = 0;
-    C_TRY(hipMemcpy(&st, d_st.p, 4, hipMemcpyDeviceToHost));
-    if (st != 0) return st;
-    C_TRY(hipMemcpy(b_fwd_data, d_f.p, (size_t)b_len * 8, hipMemcpyDeviceToHost));
-    C_TRY(hipMemcpy(b_last_diag, d_l.p, (size_t)b_len * 8, hipMemcpyDeviceToHost));
-    return TBA_OK;
+    Scratch sc;
+    const double *d_b = sc.in(b_data, b_len);
+    const double *d_pb = sc.in(prev_b_data, plen);
+    const double *d_pf = sc.in(prev_b_fwd_data, plen);
+    const i64 *d_pl = sc.in(prev_b_last_diag, plen);
+    double *d_cum = sc.out<double>(plen);
+    double *d_f = sc.out<double>(b_len);
+    i64 *d_l = sc.out<i64>(b_len);
+    i32 *d_st = sc.status(e->stream);
+    if (sc.rc) return sc.rc;
+    k_c_base_forward_pass<<<1, 64, 0, e->stream>>>(d_b, b_start, b_end, d_pb, prev_b_start, prev_b_end,
+        d_pf, d_pl, min_obs_per_base, d_cum, d_f, d_l, d_st);
+    if (int st = sc.sync(e->stream, d_st)) return st;
+    if (sc.get(b_fwd_data, d_f, b_len)) return sc.rc;
+    return sc.get(b_last_diag, d_l, b_len);
 }
 
 extern "C" int tba_c_base_traceback(tba_engine *e, const double *curr_b_data, int64_t curr_len,
@@ -1669,23 +1653,16 @@ extern "C" int tba_c_base_traceback(tba_engine *e, const double *curr_b_data, in
     if (!e || !curr_b_data || !next_b_data || !sig_pos || curr_len <= 0 || next_len <= 0)
         return set_err(TBA_E_ARG, "bad arguments");
     HIP_TRY(hipSetDevice(e->device));
-    Tmp d_c, d_n, d_out, d_st;
-    if (d_c.alloc((size_t)curr_len * 8) || d_n.alloc((size_t)next_len * 8) || d_out.alloc(8) ||
-        d_st.alloc(4))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_c.p, curr_b_data, (size_t)curr_len * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_n.p, next_b_data, (size_t)next_len * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemsetAsync(d_st.p, 0, 4, e->stream));
-    k_c_base_traceback<<<1, 64, 0, e->stream>>>(d_c.as<double>(), curr_len, curr_start,
-        d_n.as<double>(), next_len, next_start, next_end, sig_start, min_obs_per_base,
-        d_out.as<i64>(), d_st.as<i32>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    i32 st = 0;
-    C_TRY(hipMemcpy(&st, d_st.p, 4, hipMemcpyDeviceToHost));
-    if (st != 0) return st;
-    C_TRY(hipMemcpy(sig_pos, d_out.p, 8, hipMemcpyDeviceToHost));
-    return TBA_OK;
+    Scratch sc;
+    const double *d_c = sc.in(curr_b_data, curr_len);
+    const double *d_n = sc.in(next_b_data, next_len);
+    i64 *d_out = sc.out<i64>(1);
+    i32 *d_st = sc.status(e->stream);
+    if (sc.rc) return sc.rc;
+    k_c_base_traceback<<<1, 64, 0, e->stream>>>(d_c, curr_len, curr_start, d_n, next_len, next_start,
+        next_end, sig_start, min_obs_per_base, d_out, d_st);
+    if (int st = sc.sync(e->stream, d_st)) return st;
+    return sc.get(sig_pos, d_out, 1);
 }
 
 extern "C" int tba_llh_ratio_windows(tba_engine *e, int kind, const double *means,
@@ -1702,25 +1679,19 @@ extern "C" int tba_llh_ratio_windows(tba_engine *e, int kind, const double *mean
         if (starts[i] < 0 || starts[i] + width > n_values || (kind != 0 && starts[i] >= n_values))
             return set_err(TBA_E_ARG, "window outside the arrays");
     HIP_TRY(hipSetDevice(e->device));
-    const size_t nb = (size_t)n_values * 8;
-    Tmp d_m, d_r, d_a, d_rv, d_av, d_s, d_o;
-    if (d_m.alloc(nb) || d_r.alloc(nb) || d_a.alloc(nb) || d_rv.alloc(nb) || d_av.alloc(nb) ||
-        d_s.alloc((size_t)n_windows * 8) || d_o.alloc((size_t)n_windows * 8))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_m.p, means, nb, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_r.p, ref_means, nb, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_a.p, alt_means, nb, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_rv.p, ref_vars, nb, hipMemcpyHostToDevice));
-    if (alt_vars) C_TRY(hipMemcpy(d_av.p, alt_vars, nb, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_s.p, starts, (size_t)n_windows * 8, hipMemcpyHostToDevice));
-    k_c_llh_windows<<<grid_for(n_windows), 256, 0, e->stream>>>(kind, d_m.as<double>(),
-        d_r.as<double>(), d_a.as<double>(), d_rv.as<double>(), d_av.as<double>(), width,
-        d_s.as<i64>(), n_windows, par ? par[0] : 0.0, par ? par[1] : 0.0, par ? par[2] : 0.0,
-        d_o.as<double>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    C_TRY(hipMemcpy(out, d_o.p, (size_t)n_windows * 8, hipMemcpyDeviceToHost));
-    return TBA_OK;
+    Scratch sc;
+    const double *d_m = sc.in(means, n_values);
+    const double *d_r = sc.in(ref_means, n_values);
+    const double *d_a = sc.in(alt_means, n_values);
+    const double *d_rv = sc.in(ref_vars, n_values);
+    const double *d_av = alt_vars ? sc.in(alt_vars, n_values) : sc.out<double>(n_values);
+    const i64 *d_s = sc.in(starts, n_windows);
+    double *d_o = sc.out<double>(n_windows);
+    if (sc.rc) return sc.rc;
+    k_c_llh_windows<<<grid_for(n_windows), 256, 0, e->stream>>>(kind, d_m, d_r, d_a, d_rv, d_av, width,
+        d_s, n_windows, par ? par[0] : 0.0, par ? par[1] : 0.0, par ? par[2] : 0.0, d_o);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(out, d_o, n_windows);
 }
 
 extern "C" int tba_read_pvals(tba_engine *e, const double *means, const double *ref_means,
@@ -1737,20 +1708,17 @@ extern "C" int tba_read_pvals(tba_engine *e, const double *means, const double *
     const i64 total = off[n_reads];
     if (total == 0) return TBA_OK;
     HIP_TRY(hipSetDevice(e->device));
-    const size_t nb = (size_t)total * 8;
-    Tmp d_m, d_r, d_s, d_off, d_o;
-    if (d_m.alloc(nb) || d_r.alloc(nb) || d_s.alloc(nb) || d_off.alloc((size_t)(n_reads + 1) * 8) || d_o.alloc(nb))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_m.p, means, nb, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_r.p, ref_means, nb, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_s.p, ref_sds, nb, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_off.p, off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice));
-    k_read_pvals<<<grid_for(total), 256, 0, e->stream>>>(d_m.as<double>(), d_r.as<double>(),
-        d_s.as<double>(), d_off.as<i64>(), n_reads, total, fm_offset, floor_out, smallest_pval, d_o.as<double>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    C_TRY(hipMemcpy(pvals, d_o.p, nb, hipMemcpyDeviceToHost));
-    return TBA_OK;
+    Scratch sc;
+    const double *d_m = sc.in(means, total);
+    const double *d_r = sc.in(ref_means, total);
+    const double *d_s = sc.in(ref_sds, total);
+    const i64 *d_off = sc.in(off, n_reads + 1);
+    double *d_o = sc.out<double>(total);
+    if (sc.rc) return sc.rc;
+    k_read_pvals<<<grid_for(total), 256, 0, e->stream>>>(d_m, d_r, d_s, d_off, n_reads, total, fm_offset,
+        floor_out, smallest_pval, d_o);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(pvals, d_o, total);
 }
 
 // testable slice of every read -> CSR offsets into a packed copy of (means, levels); one thread
@@ -1792,12 +1760,9 @@ extern "C" int tba_batch_de_novo_stats(tba_engine *e, int64_t fm_offset, double 
     const size_t N = (size_t)e->n_reads;
     const i64 K = e->hp.kmer_width, cp = e->hp.central_pos, dn = K - cp - 1;
     // per-base means of the final signal (the Events table's norm_mean), on the device
-    if (e->d_stat.ensure((size_t)e->B_tot * 16)) return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    double *d_m = e->d_stat.as<double>(), *d_s = d_m + e->B_tot;
-    const unsigned gB = (unsigned)std::min<i64>(std::max<i64>((e->max_B + 255) / 256, 1), 128);
-    k_base_stats<<<dim3(gB, (unsigned)N), 256, 0, e->stream>>>(e->d_rs.as<ReadState>(),
-        e->d_dp.as<DevParams>(), e->hp.o.skip_norm_out ? nullptr : e->d_norm_out.as<double>(),
-        e->d_norm.as<double>(), e->d_segs.as<i64>(), d_m, d_s);
+    if (int rc = launch_base_stats(e)) return rc;
+    const double *d_m = e->d_stat.as<double>();
+    const unsigned gB = base_blocks(e);
     // testable positions of every successful read, packed
     std::vector<ReadState> rs(N);
     HIP_TRY(hipMemcpy(rs.data(), e->d_rs.p, N * sizeof(ReadState), hipMemcpyDeviceToHost));
@@ -1809,58 +1774,52 @@ extern "C" int tba_batch_de_novo_stats(tba_engine *e, int64_t fm_offset, double 
         pk[i + 1] = pk[i] + cnt;
     }
     const i64 total = pk[N];
-    Tmp d_pk, d_pm, d_pr, d_ps, d_pp, d_out;
-    if (d_pk.alloc((N + 1) * 8) || d_pm.alloc((size_t)total * 8) || d_pr.alloc((size_t)total * 8) ||
-        d_ps.alloc((size_t)total * 8) || d_pp.alloc((size_t)total * 8) || d_out.alloc((size_t)e->B_tot * 8))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    HIP_TRY(hipMemcpyAsync(d_pk.p, pk.data(), (N + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    Scratch sc;
+    const i64 *d_pk = sc.in(pk.data(), N + 1);
+    double *d_pm = sc.out<double>(total);
+    double *d_pr = sc.out<double>(total);
+    double *d_ps = sc.out<double>(total);
+    double *d_pp = sc.out<double>(total);
+    double *d_out = sc.out<double>(e->B_tot);
+    if (sc.rc) return sc.rc;
     if (total > 0) {
         k_denovo_pack<<<dim3(gB, (unsigned)N), 256, 0, e->stream>>>(e->d_rs.as<ReadState>(), e->n_reads,
-            e->d_dp.as<DevParams>(), d_m, e->d_refm.as<double>(), e->d_refs.as<double>(),
-            d_pk.as<i64>(), d_pm.as<double>(), d_pr.as<double>(), d_ps.as<double>());
-        k_read_pvals<<<grid_for(total), 256, 0, e->stream>>>(d_pm.as<double>(), d_pr.as<double>(),
-            d_ps.as<double>(), d_pk.as<i64>(), (i64)N, total, fm_offset, 1, smallest_pval, d_pp.as<double>());
+            e->d_dp.as<DevParams>(), d_m, e->d_refm.as<double>(), e->d_refs.as<double>(), d_pk, d_pm, d_pr, d_ps);
+        k_read_pvals<<<grid_for(total), 256, 0, e->stream>>>(d_pm, d_pr, d_ps, d_pk, (i64)N, total, fm_offset, 1,
+            smallest_pval, d_pp);
     }
     k_denovo_unpack<<<dim3(gB, (unsigned)N), 256, 0, e->stream>>>(e->d_rs.as<ReadState>(),
-        e->d_dp.as<DevParams>(), d_pk.as<i64>(), d_pp.as<double>(), d_out.as<double>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(pvals, d_out.p, (size_t)e->B_tot * 8, hipMemcpyDeviceToHost));
-    return 0;
+        e->d_dp.as<DevParams>(), d_pk, d_pp, d_out);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(pvals, d_out, e->B_tot);
+}
+
+// the two division self-tests: out[i] from (a[i], b[i])
+static int c_div_selftest(tba_engine *e, void (*kernel)(const double *, const double *, i64, double *),
+                          const double *a, const double *b, int64_t n, double *out)
+{
+    if (!e || !a || !b || !out || n < 1) return set_err(TBA_E_ARG, "bad arguments");
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    const double *d_a = sc.in(a, n);
+    const double *d_b = sc.in(b, n);
+    double *d_o = sc.out<double>(n);
+    if (sc.rc) return sc.rc;
+    kernel<<<grid_for(n), 256, 0, e->stream>>>(d_a, d_b, n, d_o);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(out, d_o, n);
 }
 
 extern "C" int tba_selftest_division(tba_engine *e, const double *a, const double *b, int64_t n,
                                      double *out)
 {
-    if (!e || !a || !b || !out || n < 1) return set_err(TBA_E_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(e->device));
-    Tmp d_a, d_b, d_o;
-    if (d_a.alloc((size_t)n * 8) || d_b.alloc((size_t)n * 8) || d_o.alloc((size_t)n * 8))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_a.p, a, (size_t)n * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_b.p, b, (size_t)n * 8, hipMemcpyHostToDevice));
-    k_c_div_check<<<grid_for(n), 256, 0, e->stream>>>(d_a.as<double>(), d_b.as<double>(), n, d_o.as<double>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    C_TRY(hipMemcpy(out, d_o.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return TBA_OK;
+    return c_div_selftest(e, k_c_div_check, a, b, n, out);
 }
 
 extern "C" int tba_selftest_approx_quotient(tba_engine *e, const double *a, const double *b,
                                             int64_t n, double *out)
 {
-    if (!e || !a || !b || !out || n < 1) return set_err(TBA_E_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(e->device));
-    Tmp d_a, d_b, d_o;
-    if (d_a.alloc((size_t)n * 8) || d_b.alloc((size_t)n * 8) || d_o.alloc((size_t)n * 8))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    C_TRY(hipMemcpy(d_a.p, a, (size_t)n * 8, hipMemcpyHostToDevice));
-    C_TRY(hipMemcpy(d_b.p, b, (size_t)n * 8, hipMemcpyHostToDevice));
-    k_c_rcp_check<<<grid_for(n), 256, 0, e->stream>>>(d_a.as<double>(), d_b.as<double>(), n, d_o.as<double>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    C_TRY(hipMemcpy(out, d_o.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return TBA_OK;
+    return c_div_selftest(e, k_c_rcp_check, a, b, n, out);
 }
 
 // ---- ts.identify_stalls (tombo_stats.py:269-368), one read, host buffers --------------------
@@ -1888,36 +1847,32 @@ extern "C" int tba_identify_stalls(tba_engine *e, const void *raw, int raw_dtype
     hp.o.stall_mini_window_size = mini_window_size; hp.o.stall_threshold = threshold;
     hp.o.stall_min_consecutive_obs = min_consecutive_obs; hp.o.stall_edge_buffer = edge_buffer;
     const i64 dev_cap = n / (min_consecutive_obs + 1) + 2;
-    Tmp d_r, d_p, d_raw, d_csum, d_bits, d_ints;
-    if (d_r.alloc(sizeof(r)) || d_p.alloc(sizeof(hp)) || d_raw.alloc((size_t)n * raw_elem_bytes(raw_dtype)) ||
-        d_csum.alloc((size_t)(n + 2) * 8) || d_bits.alloc((size_t)(n / 64 + 2) * 8) ||
-        d_ints.alloc((size_t)dev_cap * 16))
-        return set_err(TBA_E_NOMEM, "hipMalloc failed");
+    Scratch sc;
+    ReadState *rs = sc.in(&r, 1);
+    const DevParams *dp = sc.in(&hp, 1);
+    char *d_raw = sc.in((const char *)raw, (size_t)n * raw_elem_bytes(raw_dtype));
+    double *d_csum = sc.out<double>(n + 2);
+    u64 *d_bits = sc.out<u64>(n / 64 + 2);
+    i64 *d_ints = sc.out<i64>(dev_cap * 2);
+    if (sc.rc) return sc.rc;
     hipStream_t s = e->stream;
-    C_TRY(hipMemcpyAsync(d_r.p, &r, sizeof(r), hipMemcpyHostToDevice, s));
-    C_TRY(hipMemcpyAsync(d_p.p, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
-    C_TRY(hipMemcpyAsync(d_raw.p, raw, (size_t)n * raw_elem_bytes(raw_dtype), hipMemcpyHostToDevice, s));
-    ReadState *rs = d_r.as<ReadState>();
-    const DevParams *dp = d_p.as<DevParams>();
     if (raw_dtype == TBA_RAW_I16 && window_size <= SI_MAXW) {
         const unsigned gq = (unsigned)std::min<i64>(std::max<i64>((n + SI_T - 1) / SI_T, 1), 1024);
-        if (n_windows == 7) k_stall_metric_i16<7><<<dim3(gq, 1), 256, 0, s>>>(rs, dp, d_raw.as<int16_t>(), d_bits.as<u64>());
-        else k_stall_metric_i16<0><<<dim3(gq, 1), 256, 0, s>>>(rs, dp, d_raw.as<int16_t>(), d_bits.as<u64>());
+        if (n_windows == 7) k_stall_metric_i16<7><<<dim3(gq, 1), 256, 0, s>>>(rs, dp, (int16_t *)d_raw, d_bits);
+        else k_stall_metric_i16<0><<<dim3(gq, 1), 256, 0, s>>>(rs, dp, (int16_t *)d_raw, d_bits);
     } else {
-        RAW_DISPATCH(raw_dtype, (k_cumsum_scores<32, RT, 1><<<1, 256, 0, s>>>(rs, 1, dp, d_raw.as<RT>(), d_csum.as<double>())));
+        RAW_DISPATCH(raw_dtype, (k_cumsum_scores<32, RT, 1><<<1, 256, 0, s>>>(rs, 1, dp, (RT *)d_raw, d_csum)));
         const unsigned gq2 = (unsigned)std::min<i64>(std::max<i64>((n + SM_T - 1) / SM_T, 1), 1024);
-        if (n_windows == 7) k_stall_metric<7><<<dim3(gq2, 1), 256, 0, s>>>(rs, dp, d_csum.as<double>(), d_bits.as<u64>());
-        else k_stall_metric<0><<<dim3(gq2, 1), 256, 0, s>>>(rs, dp, d_csum.as<double>(), d_bits.as<u64>());
+        if (n_windows == 7) k_stall_metric<7><<<dim3(gq2, 1), 256, 0, s>>>(rs, dp, d_csum, d_bits);
+        else k_stall_metric<0><<<dim3(gq2, 1), 256, 0, s>>>(rs, dp, d_csum, d_bits);
     }
-    k_stall_runs<<<dim3(grid_for(n / 64 + 1), 1), 256, 0, s>>>(rs, dp, d_bits.as<u64>(), d_ints.as<i64>());
-    k_stall_merge<<<1, 64, 0, s>>>(rs, 1, dp, d_ints.as<i64>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipMemcpyAsync(&r, d_r.p, sizeof(r), hipMemcpyDeviceToHost, s));
-    C_TRY(hipStreamSynchronize(s));
+    k_stall_runs<<<dim3(grid_for(n / 64 + 1), 1), 256, 0, s>>>(rs, dp, d_bits, d_ints);
+    k_stall_merge<<<1, 64, 0, s>>>(rs, 1, dp, d_ints);
+    if (sc.sync(s) || sc.get(&r, rs, 1)) return sc.rc;
     if (r.status != TBA_OK) return r.status;
     *n_ints = r.n_stall;
     if (r.n_stall > cap) return set_err(TBA_E_ARG, "interval buffer too small (n_ints holds the count)");
-    if (r.n_stall > 0) C_TRY(hipMemcpy(ints, d_ints.p, (size_t)r.n_stall * 16, hipMemcpyDeviceToHost));
+    if (r.n_stall > 0) return sc.get(ints, d_ints, r.n_stall * 2);
     return TBA_OK;
 }
 
@@ -1934,13 +1889,12 @@ extern "C" int tba_selftest_subsample(tba_engine *e, int64_t n, uint64_t seed, i
 {
     if (!e || !out || n < 1 || count < 1 || count > n) return set_err(TBA_E_ARG, "bad arguments");
     HIP_TRY(hipSetDevice(e->device));
-    Tmp d_o;
-    if (d_o.alloc((size_t)count * 8)) return set_err(TBA_E_NOMEM, "hipMalloc failed");
-    k_c_perm_check<<<grid_for(count), 256, 0, e->stream>>>(n, seed, read_index, count, d_o.as<i64>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(e->stream));
-    C_TRY(hipMemcpy(out, d_o.p, (size_t)count * 8, hipMemcpyDeviceToHost));
-    return TBA_OK;
+    Scratch sc;
+    i64 *d_o = sc.out<i64>(count);
+    if (sc.rc) return sc.rc;
+    k_c_perm_check<<<grid_for(count), 256, 0, e->stream>>>(n, seed, read_index, count, d_o);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(out, d_o, count);
 }
 
 // ---- host-side packer: per-read arrays -> the CSR buffers of tba_batch_upload_async ----------
