@@ -459,6 +459,38 @@ int tba_llh_ratio_windows(tba_engine *e, int kind, const double *means, const do
 int tba_read_pvals(tba_engine *e, const double *means, const double *ref_means,
     const double *ref_sds, const int64_t *off, int64_t n_reads, int64_t fm_offset, int floor_out,
     double smallest_pval, double *pvals);
+/* ---- level pileups across reads: level_sample_compare and the control reference levels ------
+ * A batch of regions in one call.  Region r: genomic [reg_start[r], reg_end[r]), strand
+ * reg_strand[r] (0 '+', 1 '-', 2 none: no strand filter), its reads reg_read_off[r] ..
+ * reg_read_off[r + 1] - 1 of the read arrays; read q: genomic start read_start[q], strand
+ * read_strand[q] (0 / 1), read-centric levels means[read_off[q] .. read_off[q + 1]) (NaN: no
+ * level); read_ctrl[q] != 0 puts it in the control group.  Reads of the other strand are skipped.
+ * Outputs are laid out by the extended regions [reg_start - fm_offset, reg_end + fm_offset): region
+ * r owns entries from P_r = sum over earlier regions of their extended lengths.
+ *
+ * tba_group_level_stats: compute_group_reg_stats (tombo_stats.py:4236-4398).  stat_kind 0 KS, 1 U,
+ * 2 t; return_p 1: p-values (Fisher's method over 2 fm_offset + 1 positions when fm_offset > 0,
+ * floored at smallest_pval), 0: statistics (window means).  Per region out_counts[r] tested
+ * positions, compacted at P_r: out_stats, out_poss (genomic), out_cov / out_ctrl_cov (sample /
+ * control coverage).  U ranks equal values sample first. */
+int tba_group_level_stats(tba_engine *e, int stat_kind, int return_p, int64_t fm_offset,
+    int64_t min_test_reads, int64_t n_regions, const int64_t *reg_start, const int64_t *reg_end,
+    const int8_t *reg_strand, const int64_t *reg_read_off, int64_t n_reads,
+    const int64_t *read_start, const int8_t *read_strand, const int8_t *read_ctrl,
+    const int64_t *read_off, const double *means, double smallest_pval, double *out_stats,
+    int64_t *out_poss, int64_t *out_cov, int64_t *out_ctrl_cov, int64_t *out_counts);
+/* get_reads_ref (tombo_stats.py:3627-3673): every read is one group.  Per extended position:
+ * out_cov, and where out_cov >= min_test_reads the median (est_mean: mean) and population sd of
+ * the levels, else NaN.  prior_means / prior_sds (both or neither; per extended position): the
+ * posterior blend with weights prior_w_mean / prior_w_sd (compute_posterior_samp_dists).  Zero
+ * sd becomes NaN in both outputs. */
+int tba_reads_ref_levels(tba_engine *e, int est_mean, int64_t fm_offset, int64_t min_test_reads,
+    int64_t n_regions, const int64_t *reg_start, const int64_t *reg_end, const int8_t *reg_strand,
+    const int64_t *reg_read_off, int64_t n_reads, const int64_t *read_start,
+    const int8_t *read_strand, const int64_t *read_off, const double *means,
+    const double *prior_means, const double *prior_sds, double prior_w_mean, double prior_w_sd,
+    double *out_means, double *out_sds, int64_t *out_cov);
+
 /* The de novo statistic of every read of the finished resident batch, nothing uploaded: per-base
  * means (c_new_means over the final signal and boundaries, as tba_batch_base_stats) against the
  * batch's own expected levels, which are the canonical model's levels of the read sequence --

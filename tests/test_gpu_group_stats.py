@@ -1,0 +1,243 @@
+"""level_sample_compare (compute_group_reg_stats) and get_reads_ref on the device against the live
+reference (tests/golden/stats_group.npz, written by gen_golden_group_stats.py).
+
+Tolerances:
+  positions, coverages: exact;
+  KS / U / t statistics and window means of statistics (windows of at most 7 values, where
+  numpy's pairwise sum is the sequential one): bit-equal;
+  medians: bit-equal; np.std and np.mean: bit-equal (numpy's pairwise order is restated: blocks of
+  8192, eight accumulators, 8-aligned halves);
+  p-values: 1e-12 relative for KS / U / Fisher (device exp / log / erfc / pow), 1e-11 for the t
+  test (the t CDF goes through lgamma and an incomplete-beta continued fraction; measured against
+  scipy: at most 3e-13 relative above 1e-300).
+"""
+import numpy as np
+import pytest
+from scipy import stats as sps
+
+from tombo_amd import tombo_stats as ts, tombo_helper as th
+
+
+def _read(start, end, strand, read_id, means):
+    return th.resquiggledRead(start, end, False, 0, strand, None, None, False, read_id=read_id,
+                              means=means)
+
+
+pytestmark = pytest.mark.gpu
+
+STATS = ['ks_test', 'u_test', 't_test', 'ks_stat_test', 'u_stat_test', 't_stat_test']
+
+
+@pytest.fixture(scope='module')
+def gold():
+    import os
+    return np.load(os.path.join(os.path.dirname(__file__), 'golden', 'stats_group.npz'))
+
+
+def _regions(g):
+    """golden reads -> (sample regions, control regions), reads in the generator's order"""
+    off = np.concatenate([[0], np.cumsum(g['rd_len'])])
+    samp, ctrl = [], []
+    for ri in range(g['reg_start'].shape[0]):
+        strand = '-' if g['reg_minus'][ri] else '+'
+        rs = {0: [], 1: []}
+        for q in np.flatnonzero(g['rd_reg'] == ri):
+            s, n = int(g['rd_start'][q]), int(g['rd_len'][q])
+            rs[int(g['rd_ctrl'][q])].append(_read(
+                start=s, end=s + n, strand='-' if g['rd_minus'][q] else '+', read_id='r%d' % q,
+                means=g['rd_means'][off[q]:off[q + 1]]))
+        args = ('chr1', strand, int(g['reg_start'][ri]), int(g['reg_end'][ri]))
+        samp.append(th.regionData(*args, reads=rs[0]))
+        ctrl.append(th.regionData(*args, reads=rs[1]))
+    return samp, ctrl
+
+
+def _close(got, want, rtol):
+    assert got.shape == want.shape
+    assert np.array_equal(np.isnan(got), np.isnan(want))
+    ok = ~np.isnan(want)
+    if rtol == 0:
+        assert np.array_equal(got[ok], want[ok])
+    else:
+        np.testing.assert_allclose(got[ok], want[ok], rtol=rtol, atol=1e-300)
+
+
+@pytest.mark.parametrize('stat_type', STATS)
+@pytest.mark.parametrize('fm', [0, 1, 3])
+def test_group_reg_stats_golden(gold, stat_type, fm):
+    samp, ctrl = _regions(gold)
+    rtol = 0 if 'stat' in stat_type else (1e-11 if stat_type == 't_test' else 1e-12)
+    for mtr in (3, 5):
+        res = ts.compute_group_reg_stats_batch(samp, ctrl, fm, mtr, stat_type)
+        for ri in range(len(samp)):
+            key = 'g_%s_fm%d_m%d_r%d' % (stat_type, fm, mtr, ri)
+            assert len(res[ri]) == int(gold[key + '_n']), key
+            if not res[ri]:
+                continue
+            name, gs = res[ri][0]
+            assert name == stat_type and gs.chrm == 'chr1' and gs.start == samp[ri].start
+            assert np.array_equal(gs.reg_poss, gold[key + '_poss']), key
+            assert np.array_equal(gs.reg_cov, gold[key + '_cov']), key
+            assert np.array_equal(gs.ctrl_cov, gold[key + '_ctrl_cov']), key
+            _close(gs.reg_stats, gold[key + '_stats'], rtol)
+
+
+def test_group_reg_stats_single_region_form(gold):
+    samp, ctrl = _regions(gold)
+    one = ts.compute_group_reg_stats(samp[0], ctrl[0], 1, 3, ts.KS_TEST_TXT)
+    both = ts.compute_group_reg_stats_batch(samp[:1], ctrl[:1], 1, 3, ts.KS_TEST_TXT)[0]
+    assert np.array_equal(one[0][1].reg_stats, both[0][1].reg_stats, equal_nan=True)
+
+
+def _ref_regions(g):
+    _, ctrl = _regions(g)
+    genome = g['genome'].tobytes().decode()
+    return ctrl, genome
+
+
+@pytest.mark.parametrize('use_ref', [False, True])
+def test_reads_ref_golden(gold, use_ref):
+    ctrl, genome = _ref_regions(gold)
+    std_ref = ts.TomboModel(seq_samp_type=th.seqSampleType('DNA', False)) if use_ref else None
+    for fm in (0, 1):
+        for est_mean in (False, True):
+            regs = ctrl
+            if use_ref:
+                K = std_ref.kmer_width
+                regs = [th.regionData(r.chrm, r.strand, r.start, r.end, r.reads,
+                                      seq=genome[r.start - fm - K + 1:r.end + fm + K - 1]) for r in ctrl]
+            res = ts.get_reads_ref_batch(regs, 3, fm, std_ref, None, est_mean)
+            for ri, (lm, ls, cov) in enumerate(res):
+                key = 'ref_r%d_fm%d_e%d_s%d' % (ri, fm, est_mean, use_ref)
+                _close(lm, gold[key + '_means'], 0)
+                _close(ls, gold[key + '_sds'], 0)
+                assert sorted(cov) == gold[key + '_cov_pos'].tolist()
+                assert [cov[k] for k in sorted(cov)] == gold[key + '_cov'].tolist()
+
+
+def test_reads_ref_feeds_sample_compare(gold):
+    """get_reads_ref's control levels are the ctrl_means / ctrl_sds of the per-read
+    model_sample_compare statistics"""
+    samp, ctrl = _regions(gold)
+    reg, fm = ctrl[0], 1
+    lm, ls, _ = ts.get_reads_ref(reg, 3, fm)
+    assert lm.shape[0] == reg.end - reg.start + 2 * fm
+    reads = [r for r in samp[0].reads
+             if r.strand == reg.strand and r.start >= reg.start - fm and r.end <= reg.end + fm]
+    assert reads
+    res = ts.compute_sample_compare_read_stats_batch(reads, lm, ls, fm, reg_data=reg)
+    n_ok = 0
+    for rd, r in zip(reads, res):
+        if isinstance(r, Exception):
+            continue
+        pv, poss = r
+        assert np.all((poss >= reg.start - fm) & (poss < reg.end + fm))
+        assert np.all((pv >= 0) & (pv <= 1))
+        n_ok += 1
+    assert n_ok > 0
+
+
+# ---- what the golden file cannot hold --------------------------------------------------------
+def _np_group_stat(stat_type, s, c):
+    """the reference's per-position formulas (compute_ks_tests / compute_u_tests /
+    compute_t_tests) restated in numpy / scipy"""
+    s, c = np.sort(s), np.sort(c)
+    ns, nc = s.shape[0], c.shape[0]
+    if stat_type.startswith('ks'):
+        al = np.concatenate([s, c])
+        d = np.max(np.abs(np.searchsorted(s, al, side='right') / ns -
+                          np.searchsorted(c, al, side='right') / nc))
+        if stat_type == 'ks_stat_test':
+            return 1 - d
+        en = np.sqrt(ns * nc / float(ns + nc))
+        return sps.distributions.kstwobign.sf((en + 0.12 + 0.11 / en) * d)
+    if stat_type.startswith('u'):
+        al = np.concatenate([s, c])
+        ranks = np.empty(ns + nc, int)
+        ranks[al.argsort(kind='stable')] = np.arange(1, ns + nc + 1)
+        tot = ns * nc
+        u1 = ranks[:ns].sum() - (ns * (ns + 1)) / 2
+        u = min(u1, tot - u1)
+        mu = tot / 2
+        if stat_type == 'u_stat_test':
+            return (u - mu) / mu
+        return sps.norm.cdf((u - mu) / np.sqrt(tot * (tot + 1) / 12)) * 2.0
+    sm, ssd = np.mean(s), np.std(s)
+    cm, csd = np.mean(c), np.std(c)
+    if stat_type == 't_stat_test':
+        return -np.abs(sm - cm) / np.sqrt(((ssd ** 2) + (csd ** 2)) / 2)
+    sp = np.sqrt((((ns - 1) * (ssd ** 2)) + (nc - 1) * (csd ** 2)) / (ns + nc - 2))
+    t = -np.abs(sm - cm) / (sp * np.sqrt((1 / ns) + (1 / nc)))
+    return sps.t.cdf(t, ns + nc - 2) * 2.0
+
+
+def _flat_region(start, n_pos, depth_s, depth_c, rng, shift=0.15, quantum=None):
+    """reads spanning [start, start + n_pos) on '+': depth_s sample and depth_c control reads"""
+    reads = {}
+    for g, depth in ((0, depth_s), (1, depth_c)):
+        m = rng.normal(g * shift, 1.0, (depth, n_pos))
+        if quantum:
+            m = np.round(m / quantum) * quantum
+        reads[g] = [_read(start=start, end=start + n_pos, strand='+', read_id='x',
+                                       means=m[k]) for k in range(depth)]
+    return (th.regionData('c', '+', start, start + n_pos, reads[0]),
+            th.regionData('c', '+', start, start + n_pos, reads[1]), reads)
+
+
+@pytest.mark.parametrize('stat_type', STATS)
+def test_global_sort_class(stat_type):
+    """pileups beyond the workgroup's LDS (more than 4096 levels of a group at a position) sort in
+    global memory; drawn from a seed here, checked against the numpy restatement.  Per-position
+    sums of the t test run over the sorted levels on the device and in np.mean's pairwise order
+    here: 1e-12 relative there."""
+    rng = np.random.default_rng(7)
+    samp, ctrl, reads = _flat_region(100, 3, 5000, 4200, rng)
+    res = ts.compute_group_reg_stats(samp, ctrl, 0, 10, stat_type)
+    gs = res[0][1]
+    assert gs.reg_poss.tolist() == [100, 101, 102]
+    assert gs.reg_cov.tolist() == [5000] * 3 and gs.ctrl_cov.tolist() == [4200] * 3
+    for i in range(3):
+        s = np.array([r.means[i] for r in reads[0]])
+        c = np.array([r.means[i] for r in reads[1]])
+        want = _np_group_stat(stat_type, s, c)
+        if stat_type.startswith('t'):
+            np.testing.assert_allclose(gs.reg_stats[i], want, rtol=1e-11)
+        elif stat_type in ('ks_stat_test', 'u_stat_test'):
+            assert gs.reg_stats[i] == want
+        else:
+            np.testing.assert_allclose(gs.reg_stats[i], want, rtol=1e-12)
+
+
+def test_global_class_reads_ref_median_and_std():
+    rng = np.random.default_rng(8)
+    _, ctrl, reads = _flat_region(50, 2, 10, 9000, rng)
+    lm, ls, cov = ts.get_reads_ref(ctrl, 5, 0)
+    for i in range(2):
+        v = np.array([r.means[i] for r in reads[1]])
+        assert lm[i] == np.median(v) and ls[i] == np.std(v)
+    assert cov == {50: 9000, 51: 9000}
+
+
+def test_u_ties_between_extremes():
+    """Tied levels across the groups: the device ranks sample first; its U lies between the
+    all-sample-first and all-control-first rankings (stable sorts of the two concatenations)"""
+    rng = np.random.default_rng(9)
+    samp, ctrl, reads = _flat_region(10, 20, 30, 40, rng, quantum=0.5)
+    res = ts.compute_group_reg_stats(samp, ctrl, 0, 5, ts.U_STAT_TEST_TXT)[0][1]
+    n_tied = 0
+    for i in range(20):
+        s = np.sort([r.means[i] for r in reads[0]])
+        c = np.sort([r.means[i] for r in reads[1]])
+        n_tied += np.intersect1d(s, c).shape[0] > 0
+        ns, nc = s.shape[0], c.shape[0]
+        us = []
+        for first in ('s', 'c'):
+            al = np.concatenate([s, c] if first == 's' else [c, s])
+            ranks = np.empty(ns + nc, int)
+            ranks[al.argsort(kind='stable')] = np.arange(1, ns + nc + 1)
+            rs = ranks[:ns].sum() if first == 's' else ranks[nc:].sum()
+            u1 = rs - (ns * (ns + 1)) / 2
+            u = min(u1, ns * nc - u1)
+            us.append((u - ns * nc / 2) / (ns * nc / 2))
+        assert min(us) <= res.reg_stats[i] <= max(us)
+    assert n_tied > 10

@@ -46,3 +46,8 @@ SAMP_COMP_TXT = 'sample_compare'
 DE_NOVO_TXT = 'de_novo'
 ALT_MODEL_TXT = 'model_compare'
 CONST_SD_MODEL = True
+
+# get_reads_ref: prior weights of the model levels in the control reference levels
+# (tombo/_default_parameters.py)
+MEAN_PRIOR_CONST = 5
+SD_PRIOR_CONST = 40

@@ -15,6 +15,7 @@
 #include "k_tail.h"
 #include "k_cabi.h"
 #include "k_synth.h"
+#include "k_group.h"
 
 #include <algorithm>
 #include <array>
@@ -1719,6 +1720,167 @@ extern "C" int tba_read_pvals(tba_engine *e, const double *means, const double *
         floor_out, smallest_pval, d_o);
     if (sc.sync(e->stream)) return sc.rc;
     return sc.get(pvals, d_o, total);
+}
+
+// ---- level pileups across reads (k_group.h): level_sample_compare and get_reads_ref ----------
+namespace {
+// the device side of one pileup call: inputs checked and uploaded, pileup, scan, fill and sort
+// enqueued.  Host work is O(regions + reads): the level buffer of region r starts at the sum of
+// its reads' overlaps with the earlier regions' extended intervals (an upper bound of their
+// valid levels), so no coverage comes back to the host between the steps.
+struct Pileup {
+    GrpArgs a{};
+    i64 n_pos = 0;
+    i32 *cov = nullptr, *run_a = nullptr, *run_b = nullptr;
+    i64 *lv_off = nullptr, *out_idx = nullptr, *counts = nullptr;
+    double *levels = nullptr;
+};
+
+static int grp_pileup(tba_engine *e, Scratch &sc, Pileup &P, i64 fm, i64 min_reads, int two_groups,
+    i64 min_run, bool sort, i64 n_regions, const int64_t *reg_start, const int64_t *reg_end,
+    const int8_t *reg_strand, const int64_t *reg_read_off, i64 n_reads, const int64_t *read_start,
+    const int8_t *read_strand, const int8_t *read_ctrl, const int64_t *read_off, const double *means)
+{
+    if (reg_read_off[0] != 0 || reg_read_off[n_regions] > n_reads || read_off[0] != 0)
+        return set_err(TBA_E_ARG, "offset arrays must start at 0 and stay inside the reads");
+    std::vector<i64> pos_off(n_regions + 1, 0), lvl_base(n_regions + 1, 0);
+    for (i64 r = 0; r < n_regions; r++) {
+        if (reg_end[r] <= reg_start[r] || reg_strand[r] < 0 || reg_strand[r] > 2 ||
+            reg_read_off[r + 1] < reg_read_off[r])
+            return set_err(TBA_E_ARG, "bad region");
+        const i64 lo = reg_start[r] - fm, hi = reg_end[r] + fm;
+        pos_off[r + 1] = pos_off[r] + (hi - lo);
+        i64 acc = 0;
+        for (i64 q = reg_read_off[r]; q < reg_read_off[r + 1]; q++) {
+            const i64 s = read_start[q], t = s + (read_off[q + 1] - read_off[q]);
+            const i64 ov = std::min(t, hi) - std::max(s, lo);
+            acc += ov > 0 ? ov : 0;
+        }
+        lvl_base[r + 1] = lvl_base[r] + acc;
+    }
+    for (i64 q = 0; q < n_reads; q++)
+        if (read_off[q + 1] < read_off[q] || read_strand[q] < 0 || read_strand[q] > 1)
+            return set_err(TBA_E_ARG, "bad read");
+    const i64 n_pos = pos_off[n_regions], n_lv = lvl_base[n_regions], n_means = read_off[n_reads];
+    GrpArgs &a = P.a;
+    a.n_regions = n_regions; a.n_pos = n_pos; a.fm = fm;
+    a.reg_start = sc.in(reg_start, n_regions);
+    a.reg_end = sc.in(reg_end, n_regions);
+    a.reg_read_off = sc.in(reg_read_off, n_regions + 1);
+    a.pos_off = sc.in(pos_off.data(), n_regions + 1);
+    a.lvl_base = sc.in(lvl_base.data(), n_regions + 1);
+    a.reg_strand = sc.in(reg_strand, n_regions);
+    a.read_start = sc.in(read_start, n_reads);
+    a.read_off = sc.in(read_off, n_reads + 1);
+    a.read_strand = sc.in(read_strand, n_reads);
+    a.read_ctrl = read_ctrl ? sc.in(read_ctrl, n_reads) : nullptr;
+    if (!read_ctrl) { int8_t *z = sc.out<int8_t>(n_reads); if (z) sc.hip(hipMemsetAsync(z, 0, n_reads, e->stream), "hipMemsetAsync"); a.read_ctrl = z; }
+    a.means = sc.in(means, n_means);
+    P.n_pos = n_pos;
+    P.cov = sc.out<i32>(2 * n_pos);
+    P.run_a = sc.out<i32>(n_pos);
+    P.run_b = sc.out<i32>(n_pos);
+    P.lv_off = sc.out<i64>(2 * n_pos);
+    P.out_idx = sc.out<i64>(n_pos);
+    P.counts = sc.out<i64>(n_regions);
+    P.levels = sc.out<double>(n_lv);
+    i64 *lists = sc.out<i64>(6 * n_pos);
+    u32 *cls = sc.out<u32>(3);
+    if (sc.rc) return sc.rc;
+    sc.hip(hipMemsetAsync(cls, 0, 3 * sizeof(u32), e->stream), "hipMemsetAsync");
+    if (sc.rc) return sc.rc;
+    k_grp_pileup<false><<<grid_for(n_pos), 256, 0, e->stream>>>(a, P.cov, nullptr, nullptr);
+    k_grp_scan<<<(unsigned)n_regions, 64, 0, e->stream>>>(a, P.cov, min_reads, two_groups, min_run,
+        P.lv_off, P.run_a, P.run_b, P.out_idx, P.counts);
+    k_grp_pileup<true><<<grid_for(n_pos), 256, 0, e->stream>>>(a, P.cov, P.lv_off, P.levels);
+    if (sort) {
+        k_grp_classify<<<grid_for(2 * n_pos), 256, 0, e->stream>>>(n_pos, P.cov, P.out_idx, lists, cls);
+        k_grp_sort_wave<<<1024, 256, 0, e->stream>>>(lists, cls, P.cov, P.lv_off, P.levels);
+        k_grp_sort_wg<<<1024, 256, 0, e->stream>>>(lists + 2 * n_pos, cls + 1, P.cov, P.lv_off, P.levels, 0);
+        k_grp_sort_wg<<<256, 256, 0, e->stream>>>(lists + 4 * n_pos, cls + 2, P.cov, P.lv_off, P.levels, 1);
+    }
+    return sc.hip(hipGetLastError(), "launch");
+}
+}  // namespace
+
+extern "C" int tba_group_level_stats(tba_engine *e, int stat_kind, int return_p, int64_t fm_offset,
+    int64_t min_test_reads, int64_t n_regions, const int64_t *reg_start, const int64_t *reg_end,
+    const int8_t *reg_strand, const int64_t *reg_read_off, int64_t n_reads,
+    const int64_t *read_start, const int8_t *read_strand, const int8_t *read_ctrl,
+    const int64_t *read_off, const double *means, double smallest_pval, double *out_stats,
+    int64_t *out_poss, int64_t *out_cov, int64_t *out_ctrl_cov, int64_t *out_counts)
+{
+    if (!e || stat_kind < 0 || stat_kind > 2 || fm_offset < 0 || fm_offset > 64 || min_test_reads < 1 ||
+        n_regions < 0 || n_reads < 0 || !reg_start || !reg_end || !reg_strand || !reg_read_off ||
+        !read_start || !read_strand || !read_ctrl || !read_off || !means || !out_stats || !out_poss ||
+        !out_cov || !out_ctrl_cov || !out_counts)
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (n_regions == 0) return TBA_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    Pileup P;
+    if (const int rc = grp_pileup(e, sc, P, fm_offset, min_test_reads, 1, 2 * fm_offset + 1, true,
+            n_regions, reg_start, reg_end, reg_strand, reg_read_off, n_reads, read_start, read_strand,
+            read_ctrl, read_off, means))
+        return rc;
+    const i64 n_pos = P.n_pos;
+    double *raw = sc.out<double>(n_pos), *d_stats = sc.out<double>(n_pos);
+    i64 *d_poss = sc.out<i64>(n_pos), *d_cov = sc.out<i64>(n_pos), *d_ccov = sc.out<i64>(n_pos);
+    if (sc.rc) return sc.rc;
+    k_grp_test<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, stat_kind, return_p, P.cov, P.lv_off,
+        P.out_idx, P.levels, raw);
+    k_grp_window<<<grid_for(n_pos), 256, 0, e->stream>>>(P.a, return_p, smallest_pval, P.cov, P.run_a,
+        P.run_b, P.out_idx, raw, d_stats, d_poss, d_cov, d_ccov);
+    if (sc.sync(e->stream)) return sc.rc;
+    // the compacted outputs of region r start at its first extended position (unused tails are
+    // left as they are)
+    if (sc.get(out_counts, P.counts, n_regions) || sc.get(out_stats, d_stats, n_pos) ||
+        sc.get(out_poss, d_poss, n_pos) || sc.get(out_cov, d_cov, n_pos))
+        return sc.rc;
+    return sc.get(out_ctrl_cov, d_ccov, n_pos);
+}
+
+extern "C" int tba_reads_ref_levels(tba_engine *e, int est_mean, int64_t fm_offset,
+    int64_t min_test_reads, int64_t n_regions, const int64_t *reg_start, const int64_t *reg_end,
+    const int8_t *reg_strand, const int64_t *reg_read_off, int64_t n_reads,
+    const int64_t *read_start, const int8_t *read_strand, const int64_t *read_off,
+    const double *means, const double *prior_means, const double *prior_sds, double prior_w_mean,
+    double prior_w_sd, double *out_means, double *out_sds, int64_t *out_cov)
+{
+    if (!e || fm_offset < 0 || min_test_reads < 1 || n_regions < 0 || n_reads < 0 || !reg_start ||
+        !reg_end || !reg_strand || !reg_read_off || !read_start || !read_strand || !read_off ||
+        !means || !out_means || !out_sds || !out_cov || (!prior_means) != (!prior_sds))
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (n_regions == 0) return TBA_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    Pileup P;
+    if (const int rc = grp_pileup(e, sc, P, fm_offset, min_test_reads, 0, 1, false, n_regions, reg_start,
+            reg_end, reg_strand, reg_read_off, n_reads, read_start, read_strand, nullptr, read_off, means))
+        return rc;
+    const i64 n_pos = P.n_pos;
+    double *mean = sc.out<double>(n_pos), *sd = sc.out<double>(n_pos);
+    double *d_m = sc.out<double>(n_pos), *d_s = sc.out<double>(n_pos);
+    i64 *d_c = sc.out<i64>(n_pos);
+    const double *d_pm = prior_means ? sc.in(prior_means, n_pos) : nullptr;
+    const double *d_ps = prior_sds ? sc.in(prior_sds, n_pos) : nullptr;
+    i64 *lists = sc.out<i64>(6 * n_pos);
+    u32 *cls = sc.out<u32>(3);
+    if (sc.rc) return sc.rc;
+    sc.hip(hipMemsetAsync(cls, 0, 3 * sizeof(u32), e->stream), "hipMemsetAsync");
+    // moments in read order first, then the sort for the median
+    k_ref_moments<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, P.cov, P.lv_off, P.out_idx, P.levels, mean, sd);
+    if (!est_mean) {
+        k_grp_classify<<<grid_for(2 * n_pos), 256, 0, e->stream>>>(n_pos, P.cov, P.out_idx, lists, cls);
+        k_grp_sort_wave<<<1024, 256, 0, e->stream>>>(lists, cls, P.cov, P.lv_off, P.levels);
+        k_grp_sort_wg<<<1024, 256, 0, e->stream>>>(lists + 2 * n_pos, cls + 1, P.cov, P.lv_off, P.levels, 0);
+        k_grp_sort_wg<<<256, 256, 0, e->stream>>>(lists + 4 * n_pos, cls + 2, P.cov, P.lv_off, P.levels, 1);
+    }
+    k_ref_finish<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, est_mean, P.cov, P.lv_off, P.out_idx,
+        P.levels, mean, sd, d_pm, d_ps, prior_w_mean, prior_w_sd, d_m, d_s, d_c);
+    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.get(out_means, d_m, n_pos) || sc.get(out_sds, d_s, n_pos)) return sc.rc;
+    return sc.get(out_cov, d_c, n_pos);
 }
 
 // testable slice of every read -> CSR offsets into a packed copy of (means, levels); one thread

@@ -359,3 +359,21 @@ def write_new_fast5_group(fast5_data, corr_grp_slot, rsqgl_res, norm_type, compu
     except Exception:
         raise TomboError('Error writing resquiggle information back into fast5 file.')
     return event_data
+
+
+# ---- group statistics over a pileup of reads (level_sample_compare) ---------------------------
+groupStats = namedtuple('groupStats', (
+    'reg_stats', 'reg_poss', 'chrm', 'strand', 'start', 'reg_cov', 'ctrl_cov'))   # tombo_helper.py:315-317
+
+INVALID_BASE_RUNS = re.compile('[^ACGT]+')
+
+
+class regionData(object):
+    """A genomic region with its reads (the part of the reference's intervalData the statistics
+    read): `reads` are `resquiggledRead`s (genomic `start`, `strand`, read-centric `means`);
+    `seq`: the genome sequence the prior blend of get_reads_ref needs, over the region extended
+    by fm_offset and the k-mer lags.  Any object with these attributes works."""
+
+    def __init__(self, chrm, strand, start, end, reads, seq=None):
+        self.chrm, self.strand, self.start, self.end = chrm, strand, int(start), int(end)
+        self.reads, self.seq = reads, seq

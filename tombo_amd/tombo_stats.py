@@ -108,6 +108,23 @@ class TomboModel(object):
             idx = idx[::-1]
         return self.level_means[idx], self.level_sds[idx]
 
+    def get_exp_levels_from_seq_with_gaps(self, reg_seq, rev_strand):
+        """tombo_stats.py:886-915: levels of every k-mer of reg_seq, NaN for k-mers that touch a
+        non-ACGT run"""
+        K = self.kmer_width
+        means, sds = np.full(len(reg_seq) - K + 1, np.nan), np.full(len(reg_seq) - K + 1, np.nan)
+        prev = 0
+        for m in th.INVALID_BASE_RUNS.finditer(reg_seq):
+            if m.start() - prev >= K:
+                means[prev:m.start() - K + 1], sds[prev:m.start() - K + 1] = \
+                    self.get_exp_levels_from_seq(reg_seq[prev:m.start()])
+            prev = m.end()
+        if prev <= len(reg_seq) - K:
+            means[prev:], sds[prev:] = self.get_exp_levels_from_seq(reg_seq[prev:])
+        if rev_strand:
+            means, sds = means[::-1], sds[::-1]
+        return means, sds
+
 
 def get_dynamic_prog_params(match_evalue):
     return HALF_NORM_EXPECTED_VAL + match_evalue, match_evalue
@@ -458,3 +475,197 @@ def compute_alt_model_read_stats(r_data, std_ref, alt_refs, use_standard_llhr=Fa
     if isinstance(res, Exception):
         raise res
     return res[0], res[1], r_data.read_id
+
+
+# ---------------------------------------------------------------------------------------------
+# level_sample_compare and the control reference levels of model_sample_compare: a pileup of the
+# levels of many reads at each genomic position (compute_group_reg_stats, tombo_stats.py:4236-4398;
+# get_reads_ref, :3627-3673).  The reference loops over positions in numpy; here a list of regions
+# is one engine call (`tba_group_level_stats`, `tba_reads_ref_levels`, kernels in csrc/k_group.h).
+# A region is a `th.regionData` (or anything with chrm / strand / start / end / reads [/ seq]).
+from ._default_parameters import MEAN_PRIOR_CONST, SD_PRIOR_CONST   # noqa: E402
+
+KS_TEST_TXT = 'ks_test'
+U_TEST_TXT = 'u_test'
+T_TEST_TXT = 't_test'
+KS_STAT_TEST_TXT = 'ks_stat_test'
+U_STAT_TEST_TXT = 'u_stat_test'
+T_STAT_TEST_TXT = 't_stat_test'
+_GROUP_KINDS = {KS_TEST_TXT: (0, 1), U_TEST_TXT: (1, 1), T_TEST_TXT: (2, 1),
+                KS_STAT_TEST_TXT: (0, 0), U_STAT_TEST_TXT: (1, 0), T_STAT_TEST_TXT: (2, 0)}
+_STRAND_CODE = {'+': 0, '-': 1, None: 2}
+
+
+def _pileup_inputs(regions, groups, fm_offset):
+    """CSR arrays of a list of regions: per region its reads (as many lists as `groups`, the group
+    index of each list going to read_ctrl)"""
+    reg_start, reg_end, reg_strand, reg_read_off = [], [], [], [0]
+    read_start, read_strand, read_ctrl, lens, means = [], [], [], [], []
+    for reg_lists in zip(*groups):
+        reg = reg_lists[0]
+        if reg.end <= reg.start:
+            raise ValueError('region end must be greater than its start')
+        if reg.strand not in _STRAND_CODE:
+            raise ValueError('region strand must be "+", "-" or None')
+        reg_start.append(int(reg.start))
+        reg_end.append(int(reg.end))
+        reg_strand.append(_STRAND_CODE[reg.strand])
+        for g, rg in enumerate(reg_lists):
+            if rg.reads is None or len(rg.reads) == 0:
+                raise th.TomboError('Must annotate region with reads (see `TomboInterval.add_reads`) '
+                                    'to extract base levels.')
+            for rd in rg.reads:
+                m = rd.means
+                if m is None:
+                    continue   # get_read_reg_events: a read without levels is left out
+                m = np.asarray(m, dtype=np.float64)
+                if rd.strand not in ('+', '-'):
+                    raise ValueError('read strand must be "+" or "-"')
+                if rd.end is not None and rd.end - rd.start != m.shape[0]:
+                    raise ValueError('read %r: end - start differs from its number of levels'
+                                     % (rd.read_id,))
+                read_start.append(int(rd.start))
+                read_strand.append(_STRAND_CODE[rd.strand])
+                read_ctrl.append(g)
+                lens.append(m.shape[0])
+                means.append(m)
+        reg_read_off.append(len(read_start))
+    i64, i8 = np.int64, np.int8
+    arr = lambda v, t: np.ascontiguousarray(np.array(v, dtype=t))
+    read_off = np.concatenate([[0], np.cumsum(lens, dtype=i64)]).astype(i64)
+    ext = np.array(reg_end, dtype=i64) - np.array(reg_start, dtype=i64) + 2 * fm_offset
+    return dict(reg_start=arr(reg_start, i64), reg_end=arr(reg_end, i64),
+                reg_strand=arr(reg_strand, i8), reg_read_off=arr(reg_read_off, i64),
+                read_start=arr(read_start, i64), read_strand=arr(read_strand, i8),
+                read_ctrl=arr(read_ctrl, i8), read_off=np.ascontiguousarray(read_off),
+                means=np.ascontiguousarray(np.concatenate(means) if means else np.empty(0)),
+                pos_off=np.concatenate([[0], np.cumsum(ext)]).astype(i64))
+
+
+def _check_group_args(fm_offset, min_test_reads):
+    if int(fm_offset) != fm_offset or fm_offset < 0 or fm_offset > 64:
+        raise ValueError('fm_offset must be an integer in [0, 64]')
+    if int(min_test_reads) != min_test_reads or min_test_reads < 1:
+        raise ValueError('min_test_reads must be a positive integer')
+
+
+def compute_group_reg_stats_batch(regions, ctrl_regions, fm_offset, min_test_reads, stat_type,
+                                  engine=None):
+    """compute_group_reg_stats for a list of regions (sample) and their control regions (same
+    coordinates), ONE engine call; per region what the reference returns: [] or
+    [(stat_type, th.groupStats)].  U ranks equal sample and control levels sample first."""
+    import ctypes as C
+    from . import resquiggle as rq
+    if stat_type not in _GROUP_KINDS:
+        raise NotImplementedError('Unrecognized test type.')
+    _check_group_args(fm_offset, min_test_reads)
+    if len(regions) != len(ctrl_regions):
+        raise ValueError('one control region per sample region')
+    for reg, ctrl in zip(regions, ctrl_regions):
+        if (reg.start, reg.end) != (ctrl.start, ctrl.end):
+            raise ValueError('sample and control regions must have the same coordinates')
+    if len(regions) == 0:
+        return []
+    fm_offset, min_test_reads = int(fm_offset), int(min_test_reads)
+    kind, ret_p = _GROUP_KINDS[stat_type]
+    d = _pileup_inputs(regions, [regions, ctrl_regions], fm_offset)
+    n_pos = int(d['pos_off'][-1])
+    stats_o = np.empty(n_pos)
+    poss, cov, ccov = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
+    counts = np.empty(len(regions), dtype=np.int64)
+    eng = rq.get_engine() if engine is None else engine
+    pd, pi, pb = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int8)
+    P = lambda a, t: a.ctypes.data_as(t)
+    eng._check(eng._L.tba_group_level_stats(
+        eng._h, C.c_int(kind), C.c_int(ret_p), C.c_int64(fm_offset), C.c_int64(min_test_reads),
+        C.c_int64(len(regions)), P(d['reg_start'], pi), P(d['reg_end'], pi), P(d['reg_strand'], pb),
+        P(d['reg_read_off'], pi), C.c_int64(d['read_start'].shape[0]), P(d['read_start'], pi),
+        P(d['read_strand'], pb), P(d['read_ctrl'], pb), P(d['read_off'], pi), P(d['means'], pd),
+        C.c_double(SMALLEST_PVAL), P(stats_o, pd), P(poss, pi), P(cov, pi), P(ccov, pi),
+        P(counts, pi)), 'tba_group_level_stats')
+    out = []
+    for r, reg in enumerate(regions):
+        a, b = int(d['pos_off'][r]), int(d['pos_off'][r]) + int(counts[r])
+        if b == a:
+            out.append([])
+            continue
+        out.append([(stat_type, th.groupStats(
+            stats_o[a:b].copy(), poss[a:b].copy(), reg.chrm, reg.strand, reg.start,
+            cov[a:b].copy(), ccov[a:b].copy()))])
+    return out
+
+
+def compute_group_reg_stats(reg_data, ctrl_reg_data, fm_offset, min_test_reads, stat_type):
+    """tombo_stats.py:4336-4398 for one region (a batch of one)"""
+    return compute_group_reg_stats_batch([reg_data], [ctrl_reg_data], fm_offset, min_test_reads,
+                                         stat_type)[0]
+
+
+def get_reads_ref_batch(regions, min_test_reads, fm_offset, std_ref=None, prior_weights=None,
+                        est_mean=False, engine=None):
+    """get_reads_ref for a list of regions in ONE engine call: per region
+    (level_means, level_sds, cov_dict) over [start - fm_offset, end + fm_offset).  With std_ref
+    the levels are blended with the model's (compute_posterior_samp_dists); each region then needs
+    `seq`, the '+' strand genome over [start - fm_offset - K + 1, end + fm_offset + K - 1)."""
+    import ctypes as C
+    from . import resquiggle as rq
+    _check_group_args(fm_offset, min_test_reads)
+    if len(regions) == 0:
+        return []
+    fm_offset, min_test_reads = int(fm_offset), int(min_test_reads)
+    d = _pileup_inputs(regions, [regions], fm_offset)
+    n_pos = int(d['pos_off'][-1])
+    prior_m = prior_s = None
+    w_m = w_s = 0.0
+    if std_ref is not None:
+        if prior_weights is None:
+            prior_weights = (MEAN_PRIOR_CONST, SD_PRIOR_CONST)
+        w_m, w_s = float(prior_weights[0]), float(prior_weights[1])
+        K, cp = std_ref.kmer_width, std_ref.central_pos
+        dn = K - cp - 1
+        pm, ps = [], []
+        for reg in regions:
+            if reg.seq is None:
+                raise ValueError('the prior blend needs the region sequence (regionData.seq)')
+            want = reg.end - reg.start + 2 * fm_offset + 2 * (K - 1)
+            if len(reg.seq) != want:
+                raise ValueError('region sequence must span [start - fm_offset - K + 1, '
+                                 'end + fm_offset + K - 1) (%d bases, got %d)' % (want, len(reg.seq)))
+            b_lag, e_lag = (cp, dn) if reg.strand == '+' else (dn, cp)
+            seq = reg.seq[K - 1 - b_lag:len(reg.seq) - (K - 1 - e_lag)]
+            if reg.strand == '-':
+                seq = th.rev_comp(seq)
+            m, s = std_ref.get_exp_levels_from_seq_with_gaps(seq, reg.strand == '-')
+            pm.append(m)
+            ps.append(s)
+        prior_m = np.ascontiguousarray(np.concatenate(pm), dtype=np.float64)
+        prior_s = np.ascontiguousarray(np.concatenate(ps), dtype=np.float64)
+    lm, ls = np.empty(n_pos), np.empty(n_pos)
+    cov = np.empty(n_pos, dtype=np.int64)
+    eng = rq.get_engine() if engine is None else engine
+    pd, pi, pb = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int8)
+    P = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    eng._check(eng._L.tba_reads_ref_levels(
+        eng._h, C.c_int(int(bool(est_mean))), C.c_int64(fm_offset), C.c_int64(min_test_reads),
+        C.c_int64(len(regions)), P(d['reg_start'], pi), P(d['reg_end'], pi), P(d['reg_strand'], pb),
+        P(d['reg_read_off'], pi), C.c_int64(d['read_start'].shape[0]), P(d['read_start'], pi),
+        P(d['read_strand'], pb), P(d['read_off'], pi), P(d['means'], pd), P(prior_m, pd),
+        P(prior_s, pd), C.c_double(w_m), C.c_double(w_s), P(lm, pd), P(ls, pd), P(cov, pi)),
+        'tba_reads_ref_levels')
+    out = []
+    for r, reg in enumerate(regions):
+        a, b = int(d['pos_off'][r]), int(d['pos_off'][r + 1])
+        if not (cov[a:b] >= min_test_reads).any():   # no covered position: no blend, no dict
+            out.append((np.full(b - a, np.nan), np.full(b - a, np.nan), {}))
+            continue
+        out.append((lm[a:b].copy(), ls[a:b].copy(),
+                    dict(zip(range(reg.start - fm_offset, reg.end + fm_offset), cov[a:b].tolist()))))
+    return out
+
+
+def get_reads_ref(reg_data, min_test_reads, fm_offset, std_ref=None, prior_weights=None,
+                  est_mean=False):
+    """tombo_stats.py:3627-3673 for one region: (level_means, level_sds, cov_dict); the first two
+    feed compute_sample_compare_read_stats(_batch) as ctrl_means / ctrl_sds"""
+    return get_reads_ref_batch([reg_data], min_test_reads, fm_offset, std_ref, prior_weights,
+                               est_mean)[0]
