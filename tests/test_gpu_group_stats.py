@@ -3,17 +3,17 @@ reference (tests/golden/stats_group.npz, written by gen_golden_group_stats.py).
 
 Tolerances:
   positions, coverages: exact;
-  KS / U / t statistics and window means of statistics (windows of at most 7 values, where
-  numpy's pairwise sum is the sequential one): bit-equal;
+  KS / U / t statistics and window means of statistics: bit-equal (windows of at most 7 values
+  here; wider windows, up to fm_offset 64, in test_gpu_stats_edges.py);
   medians: bit-equal; np.std and np.mean: bit-equal (numpy's pairwise order is restated: blocks of
   8192, eight accumulators, 8-aligned halves);
-  p-values: 1e-12 relative for KS / U / Fisher (device exp / log / erfc / pow), 1e-11 for the t
+  p-values: 1e-12 relative for KS / U / Fisher (device exp / log / erfc / pow / lgamma; Fisher's
+  chi2.sf by chi2_sf_even, accurate where exp(-hx) underflows), 1e-11 for the t
   test (the t CDF goes through lgamma and an incomplete-beta continued fraction; measured against
   scipy: at most 3e-13 relative above 1e-300).
 """
 import numpy as np
 import pytest
-from scipy import stats as sps
 
 from tombo_amd import tombo_stats as ts, tombo_helper as th
 
@@ -138,37 +138,9 @@ def test_reads_ref_feeds_sample_compare(gold):
 
 
 # ---- what the golden file cannot hold --------------------------------------------------------
-def _np_group_stat(stat_type, s, c):
-    """the reference's per-position formulas (compute_ks_tests / compute_u_tests /
-    compute_t_tests) restated in numpy / scipy"""
-    s, c = np.sort(s), np.sort(c)
-    ns, nc = s.shape[0], c.shape[0]
-    if stat_type.startswith('ks'):
-        al = np.concatenate([s, c])
-        d = np.max(np.abs(np.searchsorted(s, al, side='right') / ns -
-                          np.searchsorted(c, al, side='right') / nc))
-        if stat_type == 'ks_stat_test':
-            return 1 - d
-        en = np.sqrt(ns * nc / float(ns + nc))
-        return sps.distributions.kstwobign.sf((en + 0.12 + 0.11 / en) * d)
-    if stat_type.startswith('u'):
-        al = np.concatenate([s, c])
-        ranks = np.empty(ns + nc, int)
-        ranks[al.argsort(kind='stable')] = np.arange(1, ns + nc + 1)
-        tot = ns * nc
-        u1 = ranks[:ns].sum() - (ns * (ns + 1)) / 2
-        u = min(u1, tot - u1)
-        mu = tot / 2
-        if stat_type == 'u_stat_test':
-            return (u - mu) / mu
-        return sps.norm.cdf((u - mu) / np.sqrt(tot * (tot + 1) / 12)) * 2.0
-    sm, ssd = np.mean(s), np.std(s)
-    cm, csd = np.mean(c), np.std(c)
-    if stat_type == 't_stat_test':
-        return -np.abs(sm - cm) / np.sqrt(((ssd ** 2) + (csd ** 2)) / 2)
-    sp = np.sqrt((((ns - 1) * (ssd ** 2)) + (nc - 1) * (csd ** 2)) / (ns + nc - 2))
-    t = -np.abs(sm - cm) / (sp * np.sqrt((1 / ns) + (1 / nc)))
-    return sps.t.cdf(t, ns + nc - 2) * 2.0
+# the reference's per-position formulas (compute_ks_tests / compute_u_tests / compute_t_tests),
+# restated in numpy / scipy; the t test's moments as c_mean_std (sequential, sorted levels)
+from stats_reference import group_stat as _np_group_stat  # noqa: E402
 
 
 def _flat_region(start, n_pos, depth_s, depth_c, rng, shift=0.15, quantum=None):

@@ -2,10 +2,11 @@
 against vectors recorded from the live reference (tests/golden/gen_golden_stats.py), and the
 resident-batch de novo statistic against the array form.
 
-Tolerance: the p-values go through erfc / log / exp of the device library against scipy's
-(cephes) norm.cdf / chi2.sf -- 1e-12 relative (observed ~1e-15); log-likelihood ratios: the
-constant-variance form is bit-equal, the scaled form (exp, pow) 1e-12.  Positions are integers:
-exact.  Error messages are the reference's strings."""
+Tolerance: the p-values go through erfc / log / exp / lgamma of the device library against
+scipy's (cephes) norm.cdf / chi2.sf -- 1e-12 relative (observed ~1e-15; window log sums in
+numpy's order; wide windows and saturated p-values: test_gpu_stats_edges.py); log-likelihood
+ratios: the constant-variance form is bit-equal, the scaled form (exp, pow) 1e-12.  Positions are
+integers: exact.  Error messages are the reference's strings."""
 import os
 import json
 

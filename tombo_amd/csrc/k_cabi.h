@@ -270,11 +270,13 @@ __global__ void k_c_llh_windows(int kind, const double *means, const double *ref
 //   z = |mean - ref_mean| / ref_sd;  p = norm.cdf(-z) * 2  (NaN where z is NaN);
 //   fm_offset > 0: Fisher's method over windows of 2 * fm_offset + 1 p-values
 //   (calc_window_fishers_method, tombo_stats.py:2252-2271): p floored at `smallest`, logs summed in
-//   index order, chi2.sf(-2 * sum, 2 * width) in its closed form for even degrees of freedom
-//   exp(-x/2) * sum_{i < width} (x/2)^i / i!; the first / last fm_offset positions are NaN;
+//   numpy's order (as_strided(...).sum(-1): np_sum_by, pairwise from 9 values on),
+//   chi2.sf(-2 * sum, 2 * width) by chi2_sf_even (tba_common.h: the closed form for even degrees
+//   of freedom, factored in log space where exp(-x/2) would underflow); the first / last
+//   fm_offset positions are NaN;
 //   floor_out (de novo): the result is floored at `smallest` once more (np.maximum keeps NaN).
-// Reads are CSR slices off[r]..off[r+1]; one thread per base.  erfc / log / exp are the device
-// library's: parity with scipy is a stated tolerance (tests: 1e-12 relative).
+// Reads are CSR slices off[r]..off[r+1]; one thread per base.  erfc / log / exp / lgamma are the
+// device library's: parity with scipy is a stated tolerance (tests: 1e-12 relative).
 __global__ void k_read_pvals(const double *means, const double *ref_means, const double *ref_sds,
     const i64 *off, i64 n_reads, i64 total, i64 fm, int floor_out, double smallest, double *out)
 {
@@ -291,16 +293,12 @@ __global__ void k_read_pvals(const double *means, const double *ref_means, const
         if (fm <= 0) res = pval(i);
         else if (i - a < fm || b - i <= fm) res = NAN;
         else {
-            double ls = 0.0;
-            for (i64 k = i - fm; k <= i + fm; k++) {
-                double p = pval(k);
+            const double ls = np_sum_by([&](i64 k) {
+                double p = pval(i - fm + k);
                 p = p < smallest ? smallest : p; // np.maximum: NaN stays NaN (comparison false)
-                ls += log(p);
-            }
-            const double hx = -ls;                // x / 2 with x = -2 * log_sum
-            double term = 1.0, acc = 1.0;
-            for (i64 q = 1; q < 2 * fm + 1; q++) { term = term * hx / (double)q; acc += term; }
-            res = exp(-hx) * acc;
+                return log(p);
+            }, 2 * fm + 1);
+            res = chi2_sf_even(-ls, 2 * fm + 1);  // -ls = x / 2 with x = -2 * log_sum
         }
         if (floor_out && res < smallest) res = smallest;
         out[i] = res;

@@ -338,40 +338,6 @@ __device__ double grp_stdtr(i64 k, double t)
     return 0.5 + 0.5 * p;
 }
 
-// numpy's float64 add.reduce over a contiguous run: blocks of 8192 values added in order, each
-// by pairwise_sum (eight accumulators up to 128 values, halves on 8-aligned splits beyond)
-template <class F>
-__device__ __attribute__((noinline)) double np_pw_leaf(F f, i64 a, i64 n)
-{
-    if (n < 8) { double res = 0.; for (i64 i = 0; i < n; i++) res += f(a + i); return res; }
-    double r[8];
-    for (int j = 0; j < 8; j++) r[j] = f(a + j);
-    i64 i = 8;
-    for (; i < n - (n % 8); i += 8)
-        for (int j = 0; j < 8; j++) r[j] += f(a + i + j);
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res += f(a + i);
-    return res;
-}
-template <int D, class F>
-__device__ double np_pw(F f, i64 a, i64 n)
-{
-    if constexpr (D == 0) return np_pw_leaf(f, a, n);
-    else {
-        if (n <= 128) return np_pw_leaf(f, a, n);
-        i64 n2 = n / 2;
-        n2 -= n2 % 8;
-        return np_pw<D - 1>(f, a, n2) + np_pw<D - 1>(f, a + n2, n - n2);
-    }
-}
-template <class F>
-__device__ double np_sum(F f, i64 n)
-{
-    double acc = 0.0;
-    for (i64 c = 0; c < n; c += 8192) acc += np_pw<7>(f, c, n - c < 8192 ? n - c : 8192);
-    return acc;
-}
-
 // ---- per-position tests -----------------------------------------------------------------------
 // kind 0 KS, 1 U, 2 t; return_p: p-value, else the statistic.  s / c: the sorted sample and
 // control levels.  U: equal values rank sample first (the reference's unstable argsort leaves
@@ -440,9 +406,9 @@ __global__ void k_grp_test(i64 n_pos, int kind, int return_p, const i32 *cov, co
 }
 
 // Windows over each run (fm > 0): Fisher's method for p-values (calc_window_fishers_method,
-// :2252-2271; chi2.sf for even degrees of freedom in closed form, as k_read_pvals), the window
-// mean for statistics (calc_window_means, :2273-2287); sums in numpy's order; the first and last
-// fm positions of a run are NaN.  Writes the compacted outputs.
+// :2252-2271; chi2.sf for even degrees of freedom by chi2_sf_even, tba_common.h, as k_read_pvals),
+// the window mean for statistics (calc_window_means, :2273-2287); sums in numpy's order
+// (np_sum_by); the first and last fm positions of a run are NaN.  Writes the compacted outputs.
 __global__ void k_grp_window(GrpArgs a, int return_p, double smallest, const i32 *cov,
     const i32 *run_a, const i32 *run_b, const i64 *out_idx, const double *raw, double *out_stats,
     i64 *out_poss, i64 *out_cov, i64 *out_ctrl_cov)
@@ -459,17 +425,14 @@ __global__ void k_grp_window(GrpArgs a, int return_p, double smallest, const i32
         else {
             const i64 w = 2 * fm + 1, b = gp - fm;
             if (return_p) {
-                const double ls = np_sum([&](i64 k) {
+                const double ls = np_sum_by([&](i64 k) {
                     double p = raw[b + k];
                     p = p < smallest ? smallest : p;   // np.maximum: NaN stays NaN
                     return log(p);
                 }, w);
-                const double hx = -ls;
-                double term = 1.0, acc = 1.0;
-                for (i64 q = 1; q < w; q++) { term = term * hx / (double)q; acc += term; }
-                res = exp(-hx) * acc;
+                res = chi2_sf_even(-ls, w);
             } else {
-                res = np_sum([&](i64 k) { return raw[b + k]; }, w) / (double)w;
+                res = np_sum_by([&](i64 k) { return raw[b + k]; }, w) / (double)w;
             }
         }
         out_stats[o] = res;
@@ -487,9 +450,9 @@ __global__ void k_ref_moments(i64 n_pos, const i32 *cov, const i64 *lv_off, cons
         if (out_idx[gp] < 0) continue;
         const double *v = levels + lv_off[2 * gp];
         const i64 n = cov[2 * gp];
-        const double m = np_sum([&](i64 k) { return v[k]; }, n) / (double)n;
+        const double m = np_sum_by([&](i64 k) { return v[k]; }, n) / (double)n;
         mean[gp] = m;
-        sd[gp] = sqrt(np_sum([&](i64 k) { const double d = v[k] - m; return d * d; }, n) / (double)n);
+        sd[gp] = sqrt(np_sum_by([&](i64 k) { const double d = v[k] - m; return d * d; }, n) / (double)n);
     }
 }
 

@@ -306,6 +306,59 @@ __device__ inline double np_sum(const double *a, i64 n)
     return acc;
 }
 
+// np_sum of the values f(0) .. f(n - 1), computed on the fly: numpy's float64 add.reduce over a
+// contiguous run, blocks of 8192 values added in order, each by pairwise_sum (eight accumulators
+// up to 128 values, halves on 8-aligned splits beyond)
+template <class F>
+__device__ __attribute__((noinline)) double np_pw_leaf(F f, i64 a, i64 n)
+{
+    if (n < 8) { double res = 0.; for (i64 i = 0; i < n; i++) res += f(a + i); return res; }
+    double r[8];
+    for (int j = 0; j < 8; j++) r[j] = f(a + j);
+    i64 i = 8;
+    for (; i < n - (n % 8); i += 8)
+        for (int j = 0; j < 8; j++) r[j] += f(a + i + j);
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; i++) res += f(a + i);
+    return res;
+}
+template <int D, class F>
+__device__ double np_pw(F f, i64 a, i64 n)
+{
+    if constexpr (D == 0) return np_pw_leaf(f, a, n);
+    else {
+        if (n <= 128) return np_pw_leaf(f, a, n);
+        i64 n2 = n / 2;
+        n2 -= n2 % 8;
+        return np_pw<D - 1>(f, a, n2) + np_pw<D - 1>(f, a + n2, n - n2);
+    }
+}
+template <class F>
+__device__ double np_sum_by(F f, i64 n)
+{
+    double acc = 0.0;
+    for (i64 c = 0; c < n; c += 8192) acc += np_pw<7>(f, c, n - c < 8192 ? n - c : 8192);
+    return acc;
+}
+
+// chi2.sf(2 hx, 2 w) for an integer w >= 1 (Fisher's method over w p-values, hx = -sum log p):
+// the closed form exp(-hx) sum_{q < w} hx^q / q!.  Where exp(-hx) is no longer a normal double
+// (hx > 700) the largest term, the last (hx > 700 > w - 1), is factored out in log space:
+// exp(-hx + (w - 1) log hx - lgamma(w)) times the sum of the ratios prod (q / hx) <= 1, so no
+// intermediate underflows or overflows (a plain exp(-hx) is 0 above hx ~ 745, and the partial sum
+// overflows to inf for w >= 125).  NaN stays NaN.
+__device__ __forceinline__ double chi2_sf_even(double hx, i64 w)
+{
+    if (hx > 700.0) {
+        double r = 1.0, acc = 1.0;
+        for (i64 q = w - 1; q >= 1; q--) { r = r * ((double)q / hx); acc += r; }
+        return exp(-hx + (double)(w - 1) * log(hx) - lgamma((double)w)) * acc;
+    }
+    double term = 1.0, acc = 1.0;
+    for (i64 q = 1; q < w; q++) { term = term * hx / (double)q; acc += term; }
+    return exp(-hx) * acc;
+}
+
 // np.linspace(start, stop, num)[i]
 __device__ __forceinline__ double np_linspace_at(double start, double stop, i64 num, i64 i)
 {
