@@ -491,6 +491,41 @@ int tba_reads_ref_levels(tba_engine *e, int est_mean, int64_t fm_offset, int64_t
     const double *prior_means, const double *prior_sds, double prior_w_mean, double prior_w_sd,
     double *out_means, double *out_sds, int64_t *out_cov);
 
+/* ---- per-site modified fractions of the model-based tests ------------------------------------
+ * compute_reg_stats / collate_reg_stats / apply_per_read_thresh (tombo_stats.py:4084-4229) and
+ * calc_damp_fraction (:2537-2552) for a batch of n_tracks tracks in one call.  A track is one
+ * (region, statistic name): genomic interval [trk_start[t], trk_end[t]) in which its statistics
+ * lie; outputs are laid out by the tracks: track t owns entries from P_t = sum over earlier tracks
+ * of their lengths.  The per-read statistics are computed on the device by the code of
+ * tba_read_pvals / tba_llh_ratio_windows (same results) and stay there.
+ *   form 0 (de_novo, sample_compare): means / ref_means / ref_sds / off / n_reads / fm_offset /
+ *     floor_out / smallest_pval as tba_read_pvals; read r belongs to track read_track[r] and its
+ *     first value lies at genomic position read_pos[r].  The window arguments are ignored.
+ *   form 1 (model_compare): kind / means / ref_means / alt_means / ref_vars / alt_vars / n_values /
+ *     width / starts / n_windows / par as tba_llh_ratio_windows; window w belongs to track
+ *     win_track[w] at genomic position win_pos[w].  The read arguments are ignored.
+ * Every non-NaN statistic counts as coverage of its (track, position); it is valid coverage when
+ * stat <= *lower_thresh || stat >= single_read_thresh (lower_thresh given), else in form 1 when
+ * |stat| >= single_read_thresh, else always.  Per track out_counts[t] positions with coverage, in
+ * ascending order, compacted at P_t: out_frac = (valid statistics >= single_read_thresh) /
+ * valid coverage (NaN without valid coverage), out_pos (genomic), out_cov, out_valid_cov;
+ * out_n_stats[t] = the track's non-NaN statistics.  damp_counts = {unmod, mod} pseudo-counts and
+ * out_damp_frac (both or neither): (rint(frac * valid) + unmod) / (valid + unmod + mod).
+ * out_per_read (may be NULL): the statistics themselves, in the layout of tba_read_pvals' pvals
+ * (form 0) or tba_llh_ratio_windows' out (form 1); without it nothing per read is copied back.
+ * TBA_E_ARG: NULL pointers, offsets that do not start at 0 or decrease, a read / window whose
+ * positions leave its track, fm_offset outside [0, 64]. */
+int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, const int64_t *trk_start,
+    const int64_t *trk_end, const double *means, const double *ref_means, const double *ref_sds,
+    const int64_t *off, int64_t n_reads, const int64_t *read_track, const int64_t *read_pos,
+    int64_t fm_offset, int floor_out, double smallest_pval, int kind, const double *alt_means,
+    const double *ref_vars, const double *alt_vars, int64_t n_values, int64_t width,
+    const int64_t *starts, int64_t n_windows, const double *par, const int64_t *win_track,
+    const int64_t *win_pos, double single_read_thresh, const double *lower_thresh,
+    const double *damp_counts, double *out_frac, int64_t *out_pos, int64_t *out_cov,
+    int64_t *out_valid_cov, double *out_damp_frac, int64_t *out_counts, int64_t *out_n_stats,
+    double *out_per_read);
+
 /* The de novo statistic of every read of the finished resident batch, nothing uploaded: per-base
  * means (c_new_means over the final signal and boundaries, as tba_batch_base_stats) against the
  * batch's own expected levels, which are the canonical model's levels of the read sequence --
@@ -560,7 +595,7 @@ int tba_synth_dwell_thresholds(const tba_synth_params *p, uint32_t *thr, int64_t
 /* out[0..2] = sizeof(tba_params), sizeof(tba_opts), sizeof(tba_read_result) of this build, out[3]
  * (n >= 4) = TBA_ABI_VERSION: lets a binding without a C compiler (ctypes) check its struct mirrors
  * and refuse a stale build of the library */
-#define TBA_ABI_VERSION 9
+#define TBA_ABI_VERSION 10
 int tba_abi_sizes(int64_t *out, int64_t n);
 
 /* self-test: out[t] = index t of the subsample tba_opts.device_subsample draws for read

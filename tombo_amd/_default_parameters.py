@@ -51,3 +51,11 @@ CONST_SD_MODEL = True
 # (tombo/_default_parameters.py)
 MEAN_PRIOR_CONST = 5
 SD_PRIOR_CONST = 40
+
+# compute_reg_stats: (lower, single read) thresholds of the per-site fractions by sample type and
+# the (un-modified, modified) pseudo-counts of the dampened fraction
+# (tombo/_default_parameters.py:107-118,190)
+LLR_THRESH = {DNA_SAMP_TYPE: (-1.5, 2.5), RNA_SAMP_TYPE: (-2.5, 2.5)}
+SAMP_COMP_THRESH = {DNA_SAMP_TYPE: (0.15, 0.5), RNA_SAMP_TYPE: (0.05, 0.4)}
+DE_NOVO_THRESH = {DNA_SAMP_TYPE: (0.15, 0.5), RNA_SAMP_TYPE: (0.05, 0.4)}
+COV_DAMP_COUNTS = [2, 0]

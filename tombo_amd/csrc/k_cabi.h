@@ -221,47 +221,54 @@ __global__ void k_c_base_traceback(const double *curr, i64 curr_len, i64 curr_st
 // window, terms accumulated in index order like the reference.  kind 0: per-base variances;
 // 1: constant variance ref_vars[starts[i]]; 2: the scaled form (par = scale, height, power).
 // log / exp / pow are the device library's (not glibc's): parity is a stated tolerance here.
+__device__ __forceinline__ double dev_llh_window(int kind, const double *means,
+    const double *ref_means, const double *alt_means, const double *ref_vars, const double *alt_vars,
+    i64 width, i64 s, double par0, double par1, double par2)
+{
+    if (kind == 0) {
+        double ref_z = 0.0, ref_lv = 0.0, alt_z = 0.0, alt_lv = 0.0;
+        for (i64 i = s; i < s + width; i++) {
+            const double rd = means[i] - ref_means[i];
+            ref_z += (rd * rd) / ref_vars[i];
+            ref_lv += log(ref_vars[i]);
+            const double ad = means[i] - alt_means[i];
+            alt_z += (ad * ad) / alt_vars[i];
+            alt_lv += log(alt_vars[i]);
+        }
+        return alt_z + alt_lv - ref_z - ref_lv;
+    }
+    if (kind == 1) {
+        const double cv = ref_vars[s];
+        double run = 0.0;
+        for (i64 i = s; i < s + width; i++) {
+            const double obs = means[i], rd = obs - ref_means[i], ad = obs - alt_means[i];
+            run += ((ad * ad) - (rd * rd)) / cv;
+        }
+        return run;
+    }
+    const double cv = ref_vars[s];
+    double run = 0.0;
+    for (i64 i = s; i < s + width; i++) {
+        const double rm = ref_means[i], am = alt_means[i];
+        if (rm == am) continue;
+        const double obs = means[i];
+        const double sm = (am + rm) / 2;
+        const double rd = obs - rm, ad = obs - am, sd = obs - sm;
+        double md = am - rm;
+        if (md < 0) md = md * -1;
+        run += exp(-(sd * sd) / (par0 * cv)) * ((ad * ad) - (rd * rd)) / (cv * pow(md, par2) * par1);
+    }
+    return run;
+}
+
+// (the per-site kernels of k_site.h call dev_llh_window / dev_read_pval too: one copy of each formula)
 __global__ void k_c_llh_windows(int kind, const double *means, const double *ref_means,
     const double *alt_means, const double *ref_vars, const double *alt_vars, i64 width,
     const i64 *starts, i64 n_windows, double par0, double par1, double par2, double *out)
 {
-    for (i64 w = (i64)blockIdx.x * blockDim.x + threadIdx.x; w < n_windows; w += (i64)gridDim.x * blockDim.x) {
-        const i64 s = starts[w];
-        if (kind == 0) {
-            double ref_z = 0.0, ref_lv = 0.0, alt_z = 0.0, alt_lv = 0.0;
-            for (i64 i = s; i < s + width; i++) {
-                const double rd = means[i] - ref_means[i];
-                ref_z += (rd * rd) / ref_vars[i];
-                ref_lv += log(ref_vars[i]);
-                const double ad = means[i] - alt_means[i];
-                alt_z += (ad * ad) / alt_vars[i];
-                alt_lv += log(alt_vars[i]);
-            }
-            out[w] = alt_z + alt_lv - ref_z - ref_lv;
-        } else if (kind == 1) {
-            const double cv = ref_vars[s];
-            double run = 0.0;
-            for (i64 i = s; i < s + width; i++) {
-                const double obs = means[i], rd = obs - ref_means[i], ad = obs - alt_means[i];
-                run += ((ad * ad) - (rd * rd)) / cv;
-            }
-            out[w] = run;
-        } else {
-            const double cv = ref_vars[s];
-            double run = 0.0;
-            for (i64 i = s; i < s + width; i++) {
-                const double rm = ref_means[i], am = alt_means[i];
-                if (rm == am) continue;
-                const double obs = means[i];
-                const double sm = (am + rm) / 2;
-                const double rd = obs - rm, ad = obs - am, sd = obs - sm;
-                double md = am - rm;
-                if (md < 0) md = md * -1;
-                run += exp(-(sd * sd) / (par0 * cv)) * ((ad * ad) - (rd * rd)) / (cv * pow(md, par2) * par1);
-            }
-            out[w] = run;
-        }
-    }
+    for (i64 w = (i64)blockIdx.x * blockDim.x + threadIdx.x; w < n_windows; w += (i64)gridDim.x * blockDim.x)
+        out[w] = dev_llh_window(kind, means, ref_means, alt_means, ref_vars, alt_vars, width, starts[w],
+                                par0, par1, par2);
 }
 
 
@@ -277,30 +284,42 @@ __global__ void k_c_llh_windows(int kind, const double *means, const double *ref
 //   floor_out (de novo): the result is floored at `smallest` once more (np.maximum keeps NaN).
 // Reads are CSR slices off[r]..off[r+1]; one thread per base.  erfc / log / exp / lgamma are the
 // device library's: parity with scipy is a stated tolerance (tests: 1e-12 relative).
+// row of flat index i in the CSR offsets off[n_rows + 1] (binary search)
+__device__ __forceinline__ i64 dev_csr_row(const i64 *off, i64 n_rows, i64 i)
+{
+    i64 lo = 0, hi = n_rows - 1;
+    while (lo < hi) { const i64 mid = (lo + hi + 1) >> 1; if (off[mid] <= i) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
+// the statistic of flat position i of a read that covers [a, b) of the three arrays
+__device__ __forceinline__ double dev_read_pval(const double *means, const double *ref_means,
+    const double *ref_sds, i64 a, i64 b, i64 i, i64 fm, int floor_out, double smallest)
+{
+    auto pval = [&](i64 k) {
+        const double z = fabs(means[k] - ref_means[k]) / ref_sds[k];
+        return z != z ? z : erfc(z * 0.70710678118654752440);
+    };
+    double res;
+    if (fm <= 0) res = pval(i);
+    else if (i - a < fm || b - i <= fm) res = NAN;
+    else {
+        const double ls = np_sum_by([&](i64 k) {
+            double p = pval(i - fm + k);
+            p = p < smallest ? smallest : p; // np.maximum: NaN stays NaN (comparison false)
+            return log(p);
+        }, 2 * fm + 1);
+        res = chi2_sf_even(-ls, 2 * fm + 1);  // -ls = x / 2 with x = -2 * log_sum
+    }
+    if (floor_out && res < smallest) res = smallest;
+    return res;
+}
+
 __global__ void k_read_pvals(const double *means, const double *ref_means, const double *ref_sds,
     const i64 *off, i64 n_reads, i64 total, i64 fm, int floor_out, double smallest, double *out)
 {
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (i64)gridDim.x * blockDim.x) {
-        // read of position i: binary search in off[]
-        i64 lo = 0, hi = n_reads - 1;
-        while (lo < hi) { const i64 mid = (lo + hi + 1) >> 1; if (off[mid] <= i) lo = mid; else hi = mid - 1; }
-        const i64 a = off[lo], b = off[lo + 1];
-        auto pval = [&](i64 k) {
-            const double z = fabs(means[k] - ref_means[k]) / ref_sds[k];
-            return z != z ? z : erfc(z * 0.70710678118654752440);
-        };
-        double res;
-        if (fm <= 0) res = pval(i);
-        else if (i - a < fm || b - i <= fm) res = NAN;
-        else {
-            const double ls = np_sum_by([&](i64 k) {
-                double p = pval(i - fm + k);
-                p = p < smallest ? smallest : p; // np.maximum: NaN stays NaN (comparison false)
-                return log(p);
-            }, 2 * fm + 1);
-            res = chi2_sf_even(-ls, 2 * fm + 1);  // -ls = x / 2 with x = -2 * log_sum
-        }
-        if (floor_out && res < smallest) res = smallest;
-        out[i] = res;
+        const i64 r = dev_csr_row(off, n_reads, i);
+        out[i] = dev_read_pval(means, ref_means, ref_sds, off[r], off[r + 1], i, fm, floor_out, smallest);
     }
 }

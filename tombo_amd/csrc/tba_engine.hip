@@ -16,6 +16,7 @@
 #include "k_cabi.h"
 #include "k_synth.h"
 #include "k_group.h"
+#include "k_site.h"
 
 #include <algorithm>
 #include <array>
@@ -1881,6 +1882,120 @@ extern "C" int tba_reads_ref_levels(tba_engine *e, int est_mean, int64_t fm_offs
     if (sc.sync(e->stream)) return sc.rc;
     if (sc.get(out_means, d_m, n_pos) || sc.get(out_sds, d_s, n_pos)) return sc.rc;
     return sc.get(out_cov, d_c, n_pos);
+}
+
+// ---- per-site modified fractions (k_site.h): compute_reg_stats for a batch of tracks -----------
+extern "C" int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, const int64_t *trk_start,
+    const int64_t *trk_end, const double *means, const double *ref_means, const double *ref_sds,
+    const int64_t *off, int64_t n_reads, const int64_t *read_track, const int64_t *read_pos,
+    int64_t fm_offset, int floor_out, double smallest_pval, int kind, const double *alt_means,
+    const double *ref_vars, const double *alt_vars, int64_t n_values, int64_t width,
+    const int64_t *starts, int64_t n_windows, const double *par, const int64_t *win_track,
+    const int64_t *win_pos, double single_read_thresh, const double *lower_thresh,
+    const double *damp_counts, double *out_frac, int64_t *out_pos, int64_t *out_cov,
+    int64_t *out_valid_cov, double *out_damp_frac, int64_t *out_counts, int64_t *out_n_stats,
+    double *out_per_read)
+{
+    if (!e || (form != 0 && form != 1) || n_tracks < 0 || !trk_start || !trk_end || !means ||
+        !ref_means || !out_frac || !out_pos || !out_cov || !out_valid_cov || !out_counts ||
+        !out_n_stats || (!damp_counts) != (!out_damp_frac))
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (form == 0 && (!ref_sds || !off || !read_track || !read_pos || n_reads < 0 || fm_offset < 0 ||
+                      fm_offset > 64))
+        return set_err(TBA_E_ARG, "bad arguments (z form)");
+    if (form == 1 && (!alt_means || !ref_vars || !starts || !win_track || !win_pos || kind < 0 ||
+                      kind > 2 || (kind == 0 && !alt_vars) || (kind == 2 && !par) || n_values < 0 ||
+                      width < 0 || n_windows < 0))
+        return set_err(TBA_E_ARG, "bad arguments (window form)");
+    if (n_tracks == 0) return TBA_OK;
+    std::vector<i64> pos_off(n_tracks + 1, 0);
+    for (i64 t = 0; t < n_tracks; t++) {
+        if (trk_end[t] < trk_start[t]) return set_err(TBA_E_ARG, "bad track");
+        pos_off[t + 1] = pos_off[t] + (trk_end[t] - trk_start[t]);
+    }
+    const i64 n_pos = pos_off[n_tracks];
+    i64 total = 0;
+    if (form == 0) {
+        if (n_reads > 0 && off[0] != 0) return set_err(TBA_E_ARG, "offset arrays must start at 0");
+        for (i64 r = 0; r < n_reads; r++) {
+            if (off[r + 1] < off[r]) return set_err(TBA_E_ARG, "offset arrays must be non-decreasing");
+            const i64 t = read_track[r];
+            if (t < 0 || t >= n_tracks) return set_err(TBA_E_ARG, "read outside the tracks");
+            if (off[r + 1] > off[r] && (read_pos[r] < trk_start[t] || read_pos[r] + (off[r + 1] - off[r]) > trk_end[t]))
+                return set_err(TBA_E_ARG, "statistic position outside its track");
+        }
+        total = n_reads > 0 ? off[n_reads] : 0;
+    } else {
+        for (i64 w = 0; w < n_windows; w++) {
+            if (starts[w] < 0 || starts[w] + width > n_values || (kind != 0 && starts[w] >= n_values))
+                return set_err(TBA_E_ARG, "window outside the arrays");
+            const i64 t = win_track[w];
+            if (t < 0 || t >= n_tracks) return set_err(TBA_E_ARG, "window outside the tracks");
+            if (win_pos[w] < trk_start[t] || win_pos[w] >= trk_end[t])
+                return set_err(TBA_E_ARG, "statistic position outside its track");
+        }
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    SiteArgs a{};
+    a.n_tracks = n_tracks;
+    a.trk_start = sc.in(trk_start, n_tracks);
+    a.pos_off = sc.in(pos_off.data(), n_tracks + 1);
+    a.valid_mode = lower_thresh ? 0 : form == 1 ? 1 : 2;
+    a.single = single_read_thresh;
+    a.lower = lower_thresh ? *lower_thresh : 0.0;
+    a.cnt = sc.out<i32>(3 * n_pos);
+    if (a.cnt) sc.hip(hipMemsetAsync(a.cnt, 0, 3 * n_pos * sizeof(i32), e->stream), "hipMemsetAsync");
+    double *d_pr = nullptr;
+    const i64 n_stats = form == 0 ? total : n_windows;
+    if (form == 0 && total > 0) {
+        const double *d_m = sc.in(means, total);
+        const double *d_r = sc.in(ref_means, total);
+        const double *d_s = sc.in(ref_sds, total);
+        const i64 *d_off = sc.in(off, n_reads + 1);
+        const i64 *d_rt = sc.in(read_track, n_reads);
+        const i64 *d_rp = sc.in(read_pos, n_reads);
+        if (out_per_read || fm_offset > 0) d_pr = sc.out<double>(total);
+        if (sc.rc) return sc.rc;
+        if (fm_offset == 0)
+            k_site_z<<<grid_for(total), 256, 0, e->stream>>>(a, d_m, d_r, d_s, d_off, n_reads, total, d_rt,
+                d_rp, floor_out, smallest_pval, d_pr);
+        else {
+            k_read_pvals<<<grid_for(total), 256, 0, e->stream>>>(d_m, d_r, d_s, d_off, n_reads, total,
+                fm_offset, floor_out, smallest_pval, d_pr);
+            k_site_stat<<<grid_for(total), 256, 0, e->stream>>>(a, d_pr, d_off, n_reads, total, d_rt, d_rp);
+        }
+    } else if (form == 1 && n_windows > 0) {
+        const double *d_m = sc.in(means, n_values);
+        const double *d_r = sc.in(ref_means, n_values);
+        const double *d_a = sc.in(alt_means, n_values);
+        const double *d_rv = sc.in(ref_vars, n_values);
+        const double *d_av = alt_vars ? sc.in(alt_vars, n_values) : sc.out<double>(n_values);
+        const i64 *d_st = sc.in(starts, n_windows);
+        const i64 *d_wt = sc.in(win_track, n_windows);
+        const i64 *d_wp = sc.in(win_pos, n_windows);
+        if (out_per_read) d_pr = sc.out<double>(n_windows);
+        if (sc.rc) return sc.rc;
+        k_site_win<<<grid_for(n_windows), 256, 0, e->stream>>>(a, kind, d_m, d_r, d_a, d_rv, d_av, width,
+            d_st, n_windows, par ? par[0] : 0.0, par ? par[1] : 0.0, par ? par[2] : 0.0, d_wt, d_wp, d_pr);
+    }
+    double *d_frac = sc.out<double>(n_pos), *d_damp = damp_counts ? sc.out<double>(n_pos) : nullptr;
+    i64 *d_pos = sc.out<i64>(n_pos), *d_cov = sc.out<i64>(n_pos), *d_valid = sc.out<i64>(n_pos);
+    i64 *d_counts = sc.out<i64>(n_tracks), *d_ns = sc.out<i64>(n_tracks);
+    if (sc.rc) return sc.rc;
+    k_site_finish<<<(unsigned)n_tracks, 64, 0, e->stream>>>(a, damp_counts ? damp_counts[0] : 0.0,
+        damp_counts ? damp_counts[0] + damp_counts[1] : 0.0, d_frac, d_pos, d_cov, d_valid, d_damp,
+        d_counts, d_ns);
+    if (sc.sync(e->stream)) return sc.rc;
+    // the compacted outputs of track t start at its first position (unused tails are left as
+    // they are)
+    if (sc.get(out_counts, d_counts, n_tracks) || sc.get(out_n_stats, d_ns, n_tracks) ||
+        sc.get(out_frac, d_frac, n_pos) || sc.get(out_pos, d_pos, n_pos) ||
+        sc.get(out_cov, d_cov, n_pos) || sc.get(out_valid_cov, d_valid, n_pos))
+        return sc.rc;
+    if (d_damp && sc.get(out_damp_frac, d_damp, n_pos)) return sc.rc;
+    if (out_per_read && d_pr) return sc.get(out_per_read, d_pr, n_stats);
+    return TBA_OK;
 }
 
 // testable slice of every read -> CSR offsets into a packed copy of (means, levels); one thread

@@ -365,6 +365,14 @@ def write_new_fast5_group(fast5_data, corr_grp_slot, rsqgl_res, norm_type, compu
 groupStats = namedtuple('groupStats', (
     'reg_stats', 'reg_poss', 'chrm', 'strand', 'start', 'reg_cov', 'ctrl_cov'))   # tombo_helper.py:315-317
 
+class regionStats(namedtuple('regionStats', (
+        'reg_frac_standard_base', 'reg_poss', 'chrm', 'strand', 'start', 'reg_cov', 'ctrl_cov',
+        'valid_cov'))):
+    """Per-site statistics of one region and statistic name (tombo_helper.py:299-301).
+    `compute_reg_stats_batch(..., cov_damp_counts=...)` also sets the attribute `damp_frac` (the
+    dampened fractions, computed on the device)."""
+
+
 INVALID_BASE_RUNS = re.compile('[^ACGT]+')
 
 

@@ -261,41 +261,47 @@ def _fm_guard(n, fm_offset):
         raise th.TomboError("P-values vector too short for Fisher's Method window compuation.")
 
 
+def _prep_de_novo_read(rd, std_ref, fm_offset, reg_data):
+    """the per-read preparation of compute_de_novo_read_stats (:3796-3855): region clip, strand
+    flip, k-mer levels, lags -> (means, ref_means, ref_sds, first position, end position)"""
+    K, cp = std_ref.kmer_width, std_ref.central_pos
+    dn = K - cp - 1
+    if rd.means is None or rd.seq is None:
+        raise th.TomboError('Read does not contain valid re-squiggled data.')
+    reg_start = reg_data.start if reg_data is not None else rd.start
+    reg_size = (reg_data.end - reg_data.start) if reg_data is not None else rd.end - rd.start
+    lag_b, lag_e = (cp, dn) if rd.strand == '+' else (dn, cp)
+    means, seq = np.asarray(rd.means, dtype=np.float64), rd.seq
+    read_start, read_end = rd.start, rd.end
+    # clip to the region (positions outside are not tested), :3815-3836
+    if read_start + lag_b + fm_offset < reg_start:
+        c = reg_start - (read_start + lag_b + fm_offset)
+        read_start = reg_start - lag_b - fm_offset
+        means, seq = (means[c:], seq[c:]) if rd.strand == '+' else (means[:-c], seq[:-c])
+    if read_end - lag_e - fm_offset > reg_start + reg_size:
+        c = (read_end - lag_e - fm_offset) - (reg_start + reg_size)
+        read_end = reg_start + reg_size + lag_e + fm_offset
+        means, seq = (means[:-c], seq[:-c]) if rd.strand == '+' else (means[c:], seq[c:])
+    if len(seq) < K:
+        raise th.TomboError('Read does not contain information in this region.')
+    ref_m, ref_s = std_ref.get_exp_levels_from_seq(seq, rd.strand == '-')
+    if rd.strand == '-':
+        means = means[::-1]
+    means = means[lag_b:means.shape[0] - lag_e]
+    read_start += lag_b
+    read_end -= lag_e
+    _fm_guard(means.shape[0], fm_offset)
+    return means, ref_m, ref_s, read_start, read_end
+
+
 def compute_de_novo_read_stats_batch(reads, std_ref, fm_offset=FM_OFFSET_DEFAULT, reg_data=None,
                                      engine=None):
     """compute_de_novo_read_stats (tombo_stats.py:3771-3873) for a list of `th.resquiggledRead`;
     per read (pvals, positions) or the TomboError the reference raises."""
-    K, cp = std_ref.kmer_width, std_ref.central_pos
-    dn = K - cp - 1
     prep, out = [], [None] * len(reads)
     for i, rd in enumerate(reads):
         try:
-            if rd.means is None or rd.seq is None:
-                raise th.TomboError('Read does not contain valid re-squiggled data.')
-            reg_start = reg_data.start if reg_data is not None else rd.start
-            reg_size = (reg_data.end - reg_data.start) if reg_data is not None else rd.end - rd.start
-            lag_b, lag_e = (cp, dn) if rd.strand == '+' else (dn, cp)
-            means, seq = np.asarray(rd.means, dtype=np.float64), rd.seq
-            read_start, read_end = rd.start, rd.end
-            # clip to the region (positions outside are not tested), :3815-3836
-            if read_start + lag_b + fm_offset < reg_start:
-                c = reg_start - (read_start + lag_b + fm_offset)
-                read_start = reg_start - lag_b - fm_offset
-                means, seq = (means[c:], seq[c:]) if rd.strand == '+' else (means[:-c], seq[:-c])
-            if read_end - lag_e - fm_offset > reg_start + reg_size:
-                c = (read_end - lag_e - fm_offset) - (reg_start + reg_size)
-                read_end = reg_start + reg_size + lag_e + fm_offset
-                means, seq = (means[:-c], seq[:-c]) if rd.strand == '+' else (means[c:], seq[c:])
-            if len(seq) < K:
-                raise th.TomboError('Read does not contain information in this region.')
-            ref_m, ref_s = std_ref.get_exp_levels_from_seq(seq, rd.strand == '-')
-            if rd.strand == '-':
-                means = means[::-1]
-            means = means[lag_b:means.shape[0] - lag_e]
-            read_start += lag_b
-            read_end -= lag_e
-            _fm_guard(means.shape[0], fm_offset)
-            prep.append((i, means, ref_m, ref_s, read_start, read_end))
+            prep.append((i,) + _prep_de_novo_read(rd, std_ref, fm_offset, reg_data))
         except th.TomboError as e:
             out[i] = e
     if prep:
@@ -314,6 +320,35 @@ def compute_de_novo_read_stats(r_data, std_ref, fm_offset=FM_OFFSET_DEFAULT, reg
     return {DE_NOVO_TXT: res[0]}, {DE_NOVO_TXT: res[1]}, r_data.read_id
 
 
+def _prep_sample_compare_read(rd, cm, cs, fm_offset, reg_data):
+    """the per-read preparation of compute_sample_compare_read_stats (:3700-3750): region clip,
+    strand flip, the control levels under the read -> (means, ctrl_means, ctrl_sds, first position)"""
+    if rd.means is None:
+        raise th.TomboError('Read does not contain re-squiggled level means.')
+    reg_start = reg_data.start if reg_data is not None else rd.start
+    reg_size = (reg_data.end - reg_data.start) if reg_data is not None else rd.end - rd.start
+    means = np.asarray(rd.means, dtype=np.float64)
+    read_start, read_end = rd.start, rd.end
+    if read_start + fm_offset < reg_start:
+        c = reg_start - (read_start + fm_offset)
+        read_start = reg_start - fm_offset
+        means = means[c:] if rd.strand == '+' else means[:-c]
+    if read_end - fm_offset > reg_start + reg_size:
+        c = (read_end - fm_offset) - (reg_start + reg_size)
+        read_end = reg_start + reg_size + fm_offset
+        means = means[:-c] if rd.strand == '+' else means[c:]
+    if rd.strand == '-':
+        means = means[::-1]
+    a, b = read_start - reg_start + fm_offset, read_end - reg_start + fm_offset
+    if a < 0 or b > cm.shape[0] or b - a != means.shape[0]:
+        raise ValueError('control levels do not cover the read inside the region')
+    zvalid = ~(np.isnan(means) | np.isnan(cm[a:b]) | np.isnan(cs[a:b]))
+    if not zvalid.any():
+        raise th.TomboError('No valid z-scores in read.')
+    _fm_guard(means.shape[0], fm_offset)
+    return means, cm[a:b], cs[a:b], read_start
+
+
 def compute_sample_compare_read_stats_batch(reads, ctrl_means, ctrl_sds,
                                             fm_offset=FM_OFFSET_DEFAULT, reg_data=None,
                                             engine=None):
@@ -329,28 +364,7 @@ def compute_sample_compare_read_stats_batch(reads, ctrl_means, ctrl_sds,
                 raise th.TomboError('Read does not contain re-squiggled level means.')
             cm = np.asarray(ctrl_means_l[i] if ctrl_means_l is not None else ctrl_means, dtype=np.float64)
             cs = np.asarray(ctrl_sds[i] if ctrl_means_l is not None else ctrl_sds, dtype=np.float64)
-            reg_start = reg_data.start if reg_data is not None else rd.start
-            reg_size = (reg_data.end - reg_data.start) if reg_data is not None else rd.end - rd.start
-            means = np.asarray(rd.means, dtype=np.float64)
-            read_start, read_end = rd.start, rd.end
-            if read_start + fm_offset < reg_start:
-                c = reg_start - (read_start + fm_offset)
-                read_start = reg_start - fm_offset
-                means = means[c:] if rd.strand == '+' else means[:-c]
-            if read_end - fm_offset > reg_start + reg_size:
-                c = (read_end - fm_offset) - (reg_start + reg_size)
-                read_end = reg_start + reg_size + fm_offset
-                means = means[:-c] if rd.strand == '+' else means[c:]
-            if rd.strand == '-':
-                means = means[::-1]
-            a, b = read_start - reg_start + fm_offset, read_end - reg_start + fm_offset
-            if a < 0 or b > cm.shape[0] or b - a != means.shape[0]:
-                raise ValueError('control levels do not cover the read inside the region')
-            zvalid = ~(np.isnan(means) | np.isnan(cm[a:b]) | np.isnan(cs[a:b]))
-            if not zvalid.any():
-                raise th.TomboError('No valid z-scores in read.')
-            _fm_guard(means.shape[0], fm_offset)
-            prep.append((i, means, cm[a:b], cs[a:b], read_start))
+            prep.append((i,) + _prep_sample_compare_read(rd, cm, cs, fm_offset, reg_data))
         except th.TomboError as e:
             out[i] = e
     if prep:
@@ -411,6 +425,48 @@ def trim_seq_and_means(seq, means, r_start, reg_start, reg_end, strand, kmer_wid
     return kmers, means, r_start, motif_search_seq
 
 
+def _alt_motif_bounds(alt_refs):
+    return (max(ar.motif.mod_pos - 1 for _, ar in alt_refs),
+            max(ar.motif.motif_len - ar.motif.mod_pos for _, ar in alt_refs))
+
+
+def _prep_alt_model_read(rd, std_ref, alt_refs, use_standard_llhr, reg_data, max_bb, max_ab):
+    """the per-read preparation of compute_alt_model_read_stats (:3995-4076): trim, motif search,
+    levels -> per alternate model (name, positions, windows); a window is
+    (means[K], ref_means[K], alt_means[K], ref_vars[K], alt_vars[K])"""
+    K = std_ref.kmer_width
+    if rd.means is None or rd.seq is None:
+        raise th.TomboError('Read does not contain valid re-squiggled data.')
+    reg_start = reg_data.start if reg_data is not None else rd.start
+    reg_end = reg_data.end if reg_data is not None else rd.end
+    kmers, means, r_start, msseq = trim_seq_and_means(
+        rd.seq, np.asarray(rd.means, dtype=np.float64), rd.start, reg_start, reg_end,
+        rd.strand, K, std_ref.central_pos, max_bb, max_ab)
+    testable_len = means.shape[0] - K + 1
+    idx = np.array([std_ref._kmer_code(k) for k in kmers], dtype=np.int64)
+    ref_m, ref_v = std_ref.level_means[idx], np.square(std_ref.level_sds[idx])
+    res = []
+    for name, ar in alt_refs:
+        s_seq = msseq[max_bb - (ar.motif.mod_pos - 1):]
+        cut = max_ab - (ar.motif.motif_len - ar.motif.mod_pos)
+        if cut > 0:
+            s_seq = s_seq[:-cut]
+        poss, wins = [], []
+        for m in ar.motif.motif_pat.finditer(s_seq):
+            ap = m.start()
+            poss.append(r_start + ap if rd.strand == '+' else r_start + testable_len - ap - 1)
+            am, asd = ar.get_exp_levels_from_kmers(kmers[ap:ap + ar.kmer_width])
+            if not CONST_SD_MODEL and not use_standard_llhr:
+                raise th.TomboError('Variable SD scaled likelihood ratio not implemented.')
+            wins.append((means[ap:ap + K], ref_m[ap:ap + K], am, ref_v[ap:ap + K], np.square(asd)))
+        res.append((name, np.array(poss), wins))
+    return res
+
+
+def _llh_kind(use_standard_llhr):
+    return (1 if use_standard_llhr else 2) if CONST_SD_MODEL else 0
+
+
 def compute_alt_model_read_stats_batch(reads, std_ref, alt_refs, use_standard_llhr=False,
                                        reg_data=None, engine=None):
     """compute_alt_model_read_stats (tombo_stats.py:3972-4083) for a list of reads: per read
@@ -418,43 +474,21 @@ def compute_alt_model_read_stats_batch(reads, std_ref, alt_refs, use_standard_ll
     and model becomes one window of ONE `tba_llh_ratio_windows` launch."""
     from ._c_helper import llh_ratio_windows
     K = std_ref.kmer_width
-    max_bb = max(ar.motif.mod_pos - 1 for _, ar in alt_refs)
-    max_ab = max(ar.motif.motif_len - ar.motif.mod_pos for _, ar in alt_refs)
+    max_bb, max_ab = _alt_motif_bounds(alt_refs)
     out = [None] * len(reads)
-    wins = []   # (read, alt name, genomic position, means[K], ref_means[K], alt_means[K], vars)
+    wins = []   # (read, alt name, means[K], ref_means[K], alt_means[K], vars)
     for i, rd in enumerate(reads):
         try:
-            if rd.means is None or rd.seq is None:
-                raise th.TomboError('Read does not contain valid re-squiggled data.')
-            reg_start = reg_data.start if reg_data is not None else rd.start
-            reg_end = reg_data.end if reg_data is not None else rd.end
-            kmers, means, r_start, msseq = trim_seq_and_means(
-                rd.seq, np.asarray(rd.means, dtype=np.float64), rd.start, reg_start, reg_end,
-                rd.strand, K, std_ref.central_pos, max_bb, max_ab)
-            testable_len = means.shape[0] - K + 1
-            idx = np.array([std_ref._kmer_code(k) for k in kmers], dtype=np.int64)
-            ref_m, ref_v = std_ref.level_means[idx], np.square(std_ref.level_sds[idx])
+            res = _prep_alt_model_read(rd, std_ref, alt_refs, use_standard_llhr, reg_data, max_bb, max_ab)
             out[i] = ({}, {})
-            for name, ar in alt_refs:
-                s_seq = msseq[max_bb - (ar.motif.mod_pos - 1):]
-                cut = max_ab - (ar.motif.motif_len - ar.motif.mod_pos)
-                if cut > 0:
-                    s_seq = s_seq[:-cut]
-                poss = []
-                for m in ar.motif.motif_pat.finditer(s_seq):
-                    ap = m.start()
-                    poss.append(r_start + ap if rd.strand == '+' else r_start + testable_len - ap - 1)
-                    am, asd = ar.get_exp_levels_from_kmers(kmers[ap:ap + ar.kmer_width])
-                    if not CONST_SD_MODEL and not use_standard_llhr:
-                        raise th.TomboError('Variable SD scaled likelihood ratio not implemented.')
-                    wins.append((i, name, means[ap:ap + K], ref_m[ap:ap + K], am,
-                                 ref_v[ap:ap + K], np.square(asd)))
-                out[i][1][name] = np.array(poss)
+            for name, poss, w in res:
+                wins.extend((i, name) + x for x in w)
+                out[i][1][name] = poss
                 out[i][0][name] = np.empty(len(poss))
         except th.TomboError as e:
             out[i] = e
     if wins:
-        kind = (1 if use_standard_llhr else 2) if CONST_SD_MODEL else 0
+        kind = _llh_kind(use_standard_llhr)
         cat = lambda k: np.concatenate([w[k] for w in wins])
         vals = llh_ratio_windows(
             kind, cat(2), cat(3), cat(4), cat(5), np.arange(len(wins), dtype=np.int64) * K, K,
@@ -669,3 +703,324 @@ def get_reads_ref(reg_data, min_test_reads, fm_offset, std_ref=None, prior_weigh
     feed compute_sample_compare_read_stats(_batch) as ctrl_means / ctrl_sds"""
     return get_reads_ref_batch([reg_data], min_test_reads, fm_offset, std_ref, prior_weights,
                                est_mean)[0]
+
+
+# ---------------------------------------------------------------------------------------------
+# Per-site modified fractions of the model-based tests: compute_reg_stats (tombo_stats.py:4180-4229)
+# with collate_reg_stats (:4124-4178), apply_per_read_thresh (:4084-4122) and calc_damp_fraction
+# (:2537-2552).  The reference concatenates, argsorts, splits and thresholds the per-read
+# statistics of one region in numpy; here a list of regions is one engine call
+# (`tba_site_fractions`, kernels in csrc/k_site.h): the per-read statistics are computed on the
+# device and only the per-site records come back.  A track is one (region, statistic name).
+def _damp_pair(cov_damp_counts):
+    if cov_damp_counts is None:
+        return None
+    if isinstance(cov_damp_counts, dict):
+        return float(cov_damp_counts['unmod']), float(cov_damp_counts['mod'])
+    unmod, mod = cov_damp_counts
+    return float(unmod), float(mod)
+
+
+def _site_fractions(form, trk_start, trk_end, single_read_thresh, lower_thresh, cov_damp_counts,
+                    return_per_read, engine, z=None, win=None):
+    """one `tba_site_fractions` call -> dict of the flat outputs (compacted per track at pos_off)"""
+    import ctypes as C
+    from . import resquiggle as rq
+    i64a = lambda v: np.ascontiguousarray(v, dtype=np.int64)
+    f64a = lambda v: np.ascontiguousarray(v, dtype=np.float64)
+    trk_start, trk_end = i64a(trk_start), i64a(trk_end)
+    n_trk = trk_start.shape[0]
+    pos_off = np.concatenate([[0], np.cumsum(trk_end - trk_start)]).astype(np.int64)
+    n_pos = int(pos_off[-1])
+    pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    P = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    frac = np.empty(n_pos)
+    poss, cov, valid = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
+    counts, n_stats = np.empty(n_trk, dtype=np.int64), np.empty(n_trk, dtype=np.int64)
+    damp_pair = _damp_pair(cov_damp_counts)
+    damp = np.empty(n_pos) if damp_pair is not None else None
+    damp_c = None if damp_pair is None else (C.c_double * 2)(*damp_pair)
+    lower_c = None if lower_thresh is None else (C.c_double * 1)(float(lower_thresh))
+    nul_d, nul_i = C.cast(None, pd), C.cast(None, pi)
+    if form == 0:
+        means, ref_m, ref_s = (f64a(z[k]) for k in ('means', 'ref_means', 'ref_sds'))
+        off, r_trk, r_pos = (i64a(z[k]) for k in ('off', 'read_track', 'read_pos'))
+        if not (means.shape[0] == ref_m.shape[0] == ref_s.shape[0] == int(off[-1])) or \
+                not (off.shape[0] - 1 == r_trk.shape[0] == r_pos.shape[0]):
+            raise ValueError('per-base arrays, offsets and per-read arrays disagree')
+        per_read = np.empty(means.shape[0]) if return_per_read else None
+        z_args = (P(means, pd), P(ref_m, pd), P(ref_s, pd), P(off, pi), C.c_int64(r_trk.shape[0]),
+                  P(r_trk, pi), P(r_pos, pi), C.c_int64(int(z['fm_offset'])),
+                  C.c_int(int(z['floor_out'])), C.c_double(SMALLEST_PVAL))
+        w_args = (C.c_int(0), nul_d, nul_d, nul_d, C.c_int64(0), C.c_int64(0), nul_i, C.c_int64(0),
+                  nul_d, nul_i, nul_i)
+    else:
+        means, ref_m, alt_m, ref_v = (f64a(win[k]) for k in ('means', 'ref_means', 'alt_means', 'ref_vars'))
+        alt_v = None if win.get('alt_vars') is None else f64a(win['alt_vars'])
+        starts, w_trk, w_pos = (i64a(win[k]) for k in ('starts', 'win_track', 'win_pos'))
+        n = means.shape[0]
+        if not (ref_m.shape[0] == alt_m.shape[0] == ref_v.shape[0] == n) or \
+                (alt_v is not None and alt_v.shape[0] != n) or \
+                not (starts.shape[0] == w_trk.shape[0] == w_pos.shape[0]):
+            raise ValueError('window arrays disagree')
+        per_read = np.empty(starts.shape[0]) if return_per_read else None
+        par = (C.c_double * 3)(OCLLHR_SCALE, OCLLHR_HEIGHT, OCLLHR_POWER)
+        z_args = (P(means, pd), P(ref_m, pd), nul_d, nul_i, C.c_int64(0), nul_i, nul_i, C.c_int64(0),
+                  C.c_int(0), C.c_double(SMALLEST_PVAL))
+        w_args = (C.c_int(int(win['kind'])), P(alt_m, pd), P(ref_v, pd), P(alt_v, pd), C.c_int64(n),
+                  C.c_int64(int(win['width'])), P(starts, pi), C.c_int64(starts.shape[0]), par,
+                  P(w_trk, pi), P(w_pos, pi))
+    eng = rq.get_engine() if engine is None else engine
+    eng._check(eng._L.tba_site_fractions(
+        eng._h, C.c_int(form), C.c_int64(n_trk), P(trk_start, pi), P(trk_end, pi), *z_args, *w_args,
+        C.c_double(float(single_read_thresh)), lower_c, damp_c, P(frac, pd), P(poss, pi), P(cov, pi),
+        P(valid, pi), P(damp, pd), P(counts, pi), P(n_stats, pi), P(per_read, pd)),
+        'tba_site_fractions')
+    return dict(pos_off=pos_off, frac=frac, poss=poss, cov=cov, valid=valid, damp=damp,
+                counts=counts, n_stats=n_stats, per_read=per_read,
+                bytes_back=sum(a.nbytes for a in (frac, poss, cov, valid, damp, counts, n_stats, per_read)
+                               if a is not None))
+
+
+def _check_reg_stats_args(regions, fm_offset, min_test_reads, ctrl_regions, std_ref, alt_refs,
+                          stat_type):
+    if stat_type not in (SAMP_COMP_TXT, DE_NOVO_TXT, ALT_MODEL_TXT):
+        raise NotImplementedError('Unrecognized test type.')
+    _check_group_args(fm_offset, min_test_reads)
+    if stat_type == SAMP_COMP_TXT:
+        if ctrl_regions is None or len(ctrl_regions) != len(regions):
+            raise ValueError('one control region per sample region')
+        for reg, ctrl in zip(regions, ctrl_regions):
+            if (reg.start, reg.end) != (ctrl.start, ctrl.end):
+                raise ValueError('sample and control regions must have the same coordinates')
+    elif std_ref is None:
+        raise ValueError('%s needs the canonical model (std_ref)' % stat_type)
+    if stat_type == ALT_MODEL_TXT and not alt_refs:
+        raise ValueError('%s needs alternate models (alt_refs)' % stat_type)
+    for reg in regions:
+        if reg.end <= reg.start:
+            raise ValueError('region end must be greater than its start')
+
+
+def _read_id_str(rid):
+    return rid.decode() if isinstance(rid, bytes) else rid
+
+
+def _per_read_block(poss, stats, ids):
+    """the per-read block of collate_reg_stats (:4136-4154): (pos, stat, read_id) records and the
+    read-id lookup; ids are numbered in order of first appearance (the reference numbers them by
+    iterating a set, so only the mapping back to the strings is defined)"""
+    lookup = {}
+    conv = np.array([lookup.setdefault(r, len(lookup)) for r in ids], dtype=np.uint32)
+    block = np.empty(poss.shape[0], dtype=[('pos', 'u4'), ('stat', 'f8'), ('read_id', 'u4')])
+    block['pos'], block['stat'], block['read_id'] = poss, stats, conv
+    return block, lookup
+
+
+def _reg_stats_z_inputs(regions, fm_offset, std_ref, stat_type, ctrl_levels=None):
+    """flat inputs of the z form for a list of regions (one track per region): the arrays
+    `tba_read_pvals` takes plus per read its track, first position and id, and per region the
+    number of reads that did not fail.  ctrl_levels[r]: (ctrl_means, ctrl_sds) or None (region
+    already failed)."""
+    means, ref_m, ref_s, lens, r_trk, r_pos, r_ids = [], [], [], [], [], [], []
+    n_ok = [0] * len(regions)
+    for t, reg in enumerate(regions):
+        if ctrl_levels is not None and ctrl_levels[t] is None:
+            continue
+        for rd in (reg.reads or ()):
+            try:
+                if stat_type == DE_NOVO_TXT:
+                    m, a, b, rs, _ = _prep_de_novo_read(rd, std_ref, fm_offset, reg)
+                else:
+                    m, a, b, rs = _prep_sample_compare_read(
+                        rd, ctrl_levels[t][0], ctrl_levels[t][1], fm_offset, reg)
+            except th.TomboError:
+                continue   # compute_reg_stats :4210-4211
+            means.append(m); ref_m.append(a); ref_s.append(b)
+            lens.append(m.shape[0]); r_trk.append(t); r_pos.append(rs); r_ids.append(rd.read_id)
+            n_ok[t] += 1
+    cat = lambda v: np.ascontiguousarray(np.concatenate(v) if v else np.empty(0), dtype=np.float64)
+    off = np.concatenate([[0], np.cumsum(lens, dtype=np.int64)]).astype(np.int64)
+    r_trk, r_pos = np.array(r_trk, dtype=np.int64), np.array(r_pos, dtype=np.int64)
+    # a track spans the region extended by fm_offset, widened to its reads where they reach further
+    trk_start = np.array([reg.start - fm_offset for reg in regions], dtype=np.int64)
+    trk_end = np.array([reg.end + fm_offset for reg in regions], dtype=np.int64)
+    if r_trk.shape[0]:
+        np.minimum.at(trk_start, r_trk, r_pos)
+        np.maximum.at(trk_end, r_trk, r_pos + np.diff(off))
+    return dict(means=cat(means), ref_means=cat(ref_m), ref_sds=cat(ref_s), off=off,
+                read_track=r_trk, read_pos=r_pos, read_ids=r_ids, n_ok=n_ok, fm_offset=int(fm_offset),
+                floor_out=stat_type == DE_NOVO_TXT, trk_start=trk_start, trk_end=trk_end)
+
+
+def _reg_stats_win_inputs(regions, std_ref, alt_refs, use_standard_llhr):
+    """flat inputs of the window form: one track per (region, alternate model), track index
+    region * len(alt_refs) + model"""
+    K, n_alt = std_ref.kmer_width, len(alt_refs)
+    max_bb, max_ab = _alt_motif_bounds(alt_refs)
+    cols = [[] for _ in range(5)]
+    w_trk, w_pos, w_ids = [], [], []
+    n_ok = [0] * len(regions)
+    for r, reg in enumerate(regions):
+        for rd in (reg.reads or ()):
+            try:
+                res = _prep_alt_model_read(rd, std_ref, alt_refs, use_standard_llhr, reg, max_bb, max_ab)
+            except th.TomboError:
+                continue
+            n_ok[r] += 1
+            for k, (_, poss, wins) in enumerate(res):
+                for p, w in zip(poss, wins):
+                    for c, x in zip(cols, w):
+                        c.append(x)
+                    w_trk.append(r * n_alt + k); w_pos.append(int(p)); w_ids.append(rd.read_id)
+    cat = lambda v: np.ascontiguousarray(np.concatenate(v) if v else np.empty(0), dtype=np.float64)
+    w_trk, w_pos = np.array(w_trk, dtype=np.int64), np.array(w_pos, dtype=np.int64)
+    trk_start = np.repeat(np.array([reg.start for reg in regions], dtype=np.int64), n_alt)
+    trk_end = np.repeat(np.array([reg.end for reg in regions], dtype=np.int64), n_alt)
+    if w_trk.shape[0]:
+        np.minimum.at(trk_start, w_trk, w_pos)
+        np.maximum.at(trk_end, w_trk, w_pos + 1)
+    kind = _llh_kind(use_standard_llhr)
+    return dict(kind=kind, means=cat(cols[0]), ref_means=cat(cols[1]), alt_means=cat(cols[2]),
+                ref_vars=cat(cols[3]), alt_vars=cat(cols[4]) if kind == 0 else None, width=K,
+                starts=np.arange(w_trk.shape[0], dtype=np.int64) * K, win_track=w_trk, win_pos=w_pos,
+                win_ids=w_ids, n_ok=n_ok, trk_start=trk_start, trk_end=trk_end)
+
+
+def compute_reg_stats_batch(regions, fm_offset, min_test_reads, single_read_thresh, lower_thresh,
+                            ctrl_regions, std_ref, alt_refs, use_standard_llhr, stat_type,
+                            prior_weights, cov_damp_counts=None, return_per_read=False, engine=None):
+    """compute_reg_stats for a list of regions in ONE `tba_site_fractions` call (sample_compare:
+    after one `get_reads_ref_batch` call for the control levels).  Per region either the list
+    [(stat_name, th.regionStats), ...] the reference returns or the th.TomboError it raises.
+    With cov_damp_counts ((unmod, mod) or the reference's dict) the dampened fractions are computed on
+    the device too: attribute `damp_frac` of each regionStats (same values as `calc_damp_fraction`).  return_per_read: returns
+    (results, per_read) where per_read[r] lists (stat_name, (block, read_id_lookup, chrm, strand,
+    start)) as the reference puts them on its per_read_q."""
+    _check_reg_stats_args(regions, fm_offset, min_test_reads, ctrl_regions, std_ref, alt_refs,
+                          stat_type)
+    if len(regions) == 0:
+        return ([], []) if return_per_read else []
+    fm_offset, min_test_reads = int(fm_offset), int(min_test_reads)
+    n_reg = len(regions)
+    out = [None] * n_reg
+    ctrl_cov = [None] * n_reg
+    if stat_type == SAMP_COMP_TXT:
+        levels = [None] * n_reg
+        have = []
+        for r, ctrl in enumerate(ctrl_regions):
+            if ctrl.reads is None or len(ctrl.reads) == 0:   # get_base_levels of get_reads_ref
+                out[r] = th.TomboError('Must annotate region with reads (see '
+                                       '`TomboInterval.add_reads`) to extract base levels.')
+            else:
+                have.append(r)
+        if have:
+            refs = get_reads_ref_batch([ctrl_regions[r] for r in have], min_test_reads, fm_offset,
+                                       std_ref, prior_weights, engine=engine)
+            for r, (lm, ls, cov) in zip(have, refs):
+                levels[r], ctrl_cov[r] = (lm, ls), cov
+        inp = _reg_stats_z_inputs(regions, fm_offset, None, stat_type, levels)
+    elif stat_type == DE_NOVO_TXT:
+        inp = _reg_stats_z_inputs(regions, fm_offset, std_ref, stat_type)
+    else:
+        inp = _reg_stats_win_inputs(regions, std_ref, alt_refs, use_standard_llhr)
+    form = 1 if stat_type == ALT_MODEL_TXT else 0
+    if not any(inp['n_ok']):   # nothing to compute: no engine call
+        no_stats = [e if e is not None else th.TomboError('Reads contains no statistics in this region.')
+                    for e in out]
+        return (no_stats, [[] for _ in range(n_reg)]) if return_per_read else no_stats
+    res = _site_fractions(form, inp['trk_start'], inp['trk_end'], single_read_thresh, lower_thresh,
+                          cov_damp_counts, return_per_read, engine,
+                          z=inp if form == 0 else None, win=inp if form == 1 else None)
+    names = [stat_type] if form == 0 else [n for n, _ in alt_refs]
+    per_read = [[] for _ in range(n_reg)]
+    if return_per_read:
+        pr = res['per_read']
+        if form == 0:
+            lens = np.diff(inp['off'])
+            s_trk = np.repeat(inp['read_track'], lens)
+            s_pos = np.repeat(inp['read_pos'] - inp['off'][:-1], lens) + np.arange(pr.shape[0])
+            s_rd = np.repeat(np.arange(lens.shape[0]), lens)
+            ids = inp['read_ids']
+        else:
+            s_trk, s_pos, s_rd, ids = inp['win_track'], inp['win_pos'], np.arange(pr.shape[0]), inp['win_ids']
+        ok = ~np.isnan(pr)
+    for r, reg in enumerate(regions):
+        if out[r] is not None:
+            continue
+        if inp['n_ok'][r] == 0:
+            out[r] = th.TomboError('Reads contains no statistics in this region.')
+            continue
+        reg_out = []
+        for k, name in enumerate(names):
+            t = r * len(names) + k
+            if return_per_read:
+                sel = np.flatnonzero(ok & (s_trk == t))
+                block, lookup = _per_read_block(s_pos[sel], pr[sel], [_read_id_str(ids[q]) for q in s_rd[sel]])
+                per_read[r].append((name, (block, lookup, reg.chrm, reg.strand, reg.start)))
+            if res['n_stats'][t] == 0:
+                # (for model_compare the reference's list comprehension fails the whole region)
+                reg_out = th.TomboError('No valid positions in this region.')
+                break
+            a = int(res['pos_off'][t])
+            b = a + int(res['counts'][t])
+            poss, cov = res['poss'][a:b].copy(), res['cov'][a:b].copy()
+            if stat_type == SAMP_COMP_TXT:
+                # one entry per statistic in sorted-position order (apply_per_read_thresh iterates
+                # stat_locs, not the unique positions)
+                cc = ctrl_cov[r] or {}
+                cc_list = np.repeat(np.array([cc.get(int(p), 0) for p in poss], dtype=np.int64), cov).tolist()
+            else:
+                cc_list = [0] * int(cov.sum())
+            rs = th.regionStats(res['frac'][a:b].copy(), poss, reg.chrm, reg.strand, reg.start, cov,
+                                cc_list, res['valid'][a:b].copy())
+            if res['damp'] is not None:
+                rs.damp_frac = res['damp'][a:b].copy()
+            reg_out.append((name, rs))
+        out[r] = reg_out
+    return (out, per_read) if return_per_read else out
+
+
+def compute_reg_stats(reg_data, fm_offset, min_test_reads, single_read_thresh, lower_thresh,
+                      ctrl_reg_data, std_ref, alt_refs, use_standard_llhr, per_read_q, stat_type,
+                      prior_weights):
+    """tombo_stats.py:4180-4229 for one region (a batch of one): raises the region's TomboError;
+    a per_read_q that is not None receives the per-read blocks through `.put`"""
+    res = compute_reg_stats_batch(
+        [reg_data], fm_offset, min_test_reads, single_read_thresh, lower_thresh,
+        None if ctrl_reg_data is None else [ctrl_reg_data], std_ref, alt_refs, use_standard_llhr,
+        stat_type, prior_weights, return_per_read=per_read_q is not None)
+    if per_read_q is not None:
+        res, per_read = res
+        for item in per_read[0]:
+            per_read_q.put(item)
+    if isinstance(res[0], Exception):
+        raise res[0]
+    return res[0]
+
+
+def calc_damp_fraction(cov_damp_counts, fracs, valid_cov):
+    """tombo_stats.py:2537-2552: (round(frac * valid) + unmod) / (valid + unmod + mod), np.round
+    being round-half-even"""
+    cd = cov_damp_counts
+    unmod, total = (cd['unmod'], sum(list(cd.values()))) if isinstance(cd, dict) else (cd[0], cd[0] + cd[1])
+    fracs, valid_cov = np.asarray(fracs), np.asarray(valid_cov)
+    return (np.round(fracs * valid_cov) + unmod) / (valid_cov + total)
+
+
+def region_stats_block(reg_stats, cov_damp_counts):
+    """the record array ModelStats._write_stat_block builds from a regionStats (:2752-2764): rows
+    with a NaN dampened fraction dropped; control_cov is reg_stats.ctrl_cov zipped against the
+    per-site arrays, i.e. truncated to their length"""
+    damp = calc_damp_fraction(cov_damp_counts, reg_stats.reg_frac_standard_base, reg_stats.valid_cov)
+    n = min(damp.shape[0], len(reg_stats.ctrl_cov))
+    keep = np.flatnonzero(~np.isnan(damp[:n]))
+    block = np.empty(keep.shape[0], dtype=[('damp_frac', 'f8'), ('frac', 'f8'), ('pos', 'u4'),
+                                           ('cov', 'u4'), ('control_cov', 'u4'), ('valid_cov', 'u4')])
+    block['damp_frac'] = damp[keep]
+    block['frac'] = np.asarray(reg_stats.reg_frac_standard_base)[keep]
+    block['pos'] = np.asarray(reg_stats.reg_poss)[keep]
+    block['cov'] = np.asarray(reg_stats.reg_cov)[keep]
+    block['control_cov'] = np.asarray(reg_stats.ctrl_cov[:n], dtype=np.int64)[keep]
+    block['valid_cov'] = np.asarray(reg_stats.valid_cov)[keep]
+    return block
