@@ -15,7 +15,8 @@ import numpy as np
 import pytest
 
 import stats_reference as sr
-from tombo_amd import tombo_stats as ts, tombo_helper as th
+from tombo_amd import tombo_stats as ts, tombo_helper as th, resquiggle as rq
+from tombo_amd._default_parameters import SMALLEST_PVAL
 
 pytestmark = pytest.mark.gpu
 
@@ -92,8 +93,8 @@ def test_fisher_sweep_per_read(fm):
         assert np.array_equal(g[1], want_pos)
         _close(g[0], want_p, 1e-12)
     off = np.concatenate([[0], np.cumsum([d[0].shape[0] for d in dn])])
-    pv = ts._read_pvals(np.concatenate([d[0] for d in dn]), np.concatenate([d[1] for d in dn]),
-                        np.concatenate([d[2] for d in dn]), off, fm, True)
+    pv = rq.get_engine().read_pvals(np.concatenate([d[0] for d in dn]), np.concatenate([d[1] for d in dn]),
+                                    np.concatenate([d[2] for d in dn]), off, fm, True, SMALLEST_PVAL)
     for k, d in enumerate(dn):
         _close(pv[off[k]:off[k + 1]], sr.de_novo_pvals(d[0], d[1], d[2], fm), 1e-12)
         _assert_hx_band(sr.window_hx(sr.z_pvals(d[0], d[1], d[2]), fm), fm)

@@ -93,7 +93,8 @@ def c_compute_slopes(r_event_means, r_model_means, max_slope=1000.0):
 
 
 def llh_ratio_windows(kind, means, ref_means, alt_means, ref_vars, starts, width, alt_vars=None,
-                      scale_factor=None, density_height_factor=None, density_height_power=None):
+                      scale_factor=None, density_height_factor=None, density_height_power=None,
+                      engine=None):
     """Log-likelihood ratios of many k-mer-width windows in one call (kind 0: per-base variances,
     1: constant variance ref_vars[start], 2: the scaled form) -- the loop body of
     tombo_stats.py:4042-4074 over all tested positions of a read."""
@@ -108,16 +109,9 @@ def llh_ratio_windows(kind, means, ref_means, alt_means, ref_vars, starts, width
     st = _i8(np.asarray(starts, dtype=np.int64), 'starts')
     if st.shape[0] == 0:
         return np.empty(0, dtype=np.float64)
-    out = np.empty(st.shape[0], dtype=np.float64)
-    par = (C.c_double * 3)(scale_factor or 0.0, density_height_factor or 0.0,
-                           density_height_power or 0.0)
-    eng = _engine()
-    _raise(eng._L.tba_llh_ratio_windows(
-        eng._h, C.c_int(kind), m.ctypes.data_as(_pd), r.ctypes.data_as(_pd), a.ctypes.data_as(_pd),
-        rv.ctypes.data_as(_pd), None if av is None else av.ctypes.data_as(_pd),
-        C.c_int64(m.shape[0]), C.c_int64(int(width)), st.ctypes.data_as(_pi),
-        C.c_int64(st.shape[0]), par, out.ctypes.data_as(_pd)), eng)
-    return out
+    return (_engine() if engine is None else engine).llh_ratio_windows(
+        kind, m, r, a, rv, st, width, av,
+        (scale_factor or 0.0, density_height_factor or 0.0, density_height_power or 0.0))
 
 
 def c_calc_llh_ratio(reg_means, reg_ref_means, reg_alt_means, reg_ref_vars, reg_alt_vars):

@@ -6,6 +6,7 @@ box without a GPU), but creating an engine raises when no gfx950 device is usabl
 import os
 import ctypes as C
 import subprocess
+from collections import namedtuple
 
 import numpy as np
 
@@ -142,6 +143,27 @@ def lib():
 
 def _p(a, t):
     return None if a is None else a.ctypes.data_as(C.POINTER(t))
+
+
+def _f64(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _i64(a):
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+# what one tba_site_fractions call gives back: the per-site arrays compacted per track at pos_off
+# (counts[t] records from pos_off[t]), per track the number of statistics, the statistics themselves
+SiteFractions = namedtuple('SiteFractions', 'pos_off frac poss cov valid damp counts n_stats per_read')
+
+
+def _site_other_form(form):
+    """typed nulls and zeros for the arguments of tba_site_fractions that the form in use leaves out"""
+    nd, ni = C.cast(None, C.POINTER(f64)), C.cast(None, C.POINTER(i64))
+    if form == 1:
+        return (nd, ni, i64(0), ni, ni, i64(0), C.c_int(0), f64(0.0))
+    return (C.c_int(0), nd, nd, nd, i64(0), i64(0), ni, i64(0), nd, ni, ni)
 
 
 def make_params(rp):
@@ -646,6 +668,110 @@ class Engine(object):
             self._h, i64(int(fm_offset)), f64(float(smallest_pval)), _p(out, f64), i64(nb)),
             'tba_batch_de_novo_stats')
         return out[:nb]
+
+    # ---- statistics over host arrays (numpy in, numpy out; pileup: the CSR bundle of tombo_stats) ----
+    def read_pvals(self, means, ref_means, ref_sds, off, fm_offset, floor_out, smallest_pval):
+        """tba_read_pvals: z-test p-values (Fisher's method over 2 * fm_offset + 1) of reads concatenated by `off`"""
+        m, r, s, off = _f64(means), _f64(ref_means), _f64(ref_sds), _i64(off)
+        if not (m.shape[0] == r.shape[0] == s.shape[0] == int(off[-1])):
+            raise ValueError('per-base arrays and offsets disagree')
+        out = np.empty(m.shape[0], dtype=np.float64)
+        self._check(self._L.tba_read_pvals(
+            self._h, _p(m, f64), _p(r, f64), _p(s, f64), _p(off, i64), i64(off.shape[0] - 1),
+            i64(int(fm_offset)), C.c_int(int(floor_out)), f64(smallest_pval), _p(out, f64)), 'tba_read_pvals')
+        return out
+
+    def llh_ratio_windows(self, kind, means, ref_means, alt_means, ref_vars, starts, width, alt_vars, par):
+        """tba_llh_ratio_windows: one ratio per window [start, start + width) of the first array's length"""
+        m, r, a, rv, av, st = _f64(means), _f64(ref_means), _f64(alt_means), _f64(ref_vars), _f64(alt_vars), _i64(starts)
+        if min(x.shape[0] for x in (r, a, rv, av) if x is not None) < m.shape[0]:
+            raise ValueError('window arrays disagree')
+        out = np.empty(st.shape[0], dtype=np.float64)
+        self._check(self._L.tba_llh_ratio_windows(
+            self._h, C.c_int(int(kind)), _p(m, f64), _p(r, f64), _p(a, f64), _p(rv, f64), _p(av, f64),
+            i64(m.shape[0]), i64(int(width)), _p(st, i64), i64(st.shape[0]), (f64 * 3)(*par), _p(out, f64)),
+            'tba_llh_ratio_windows')
+        return out
+
+    def _pileup_args(self, pl, with_ctrl):
+        return (i64(pl.reg_start.shape[0]), _p(pl.reg_start, i64), _p(pl.reg_end, i64), _p(pl.reg_strand, C.c_int8),
+                _p(pl.reg_read_off, i64), i64(pl.read_start.shape[0]), _p(pl.read_start, i64),
+                _p(pl.read_strand, C.c_int8)) + ((_p(pl.read_ctrl, C.c_int8),) if with_ctrl else ()) + \
+            (_p(pl.read_off, i64), _p(pl.means, f64))
+
+    def group_level_stats(self, kind, return_p, fm_offset, min_test_reads, pileup, smallest_pval):
+        """-> (stats, positions, coverage, control coverage, counts): counts[r] records from pileup.pos_off[r]"""
+        n_pos = int(pileup.pos_off[-1])
+        stats = np.empty(n_pos, dtype=np.float64)
+        poss, cov, ccov = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
+        counts = np.empty(pileup.reg_start.shape[0], dtype=np.int64)
+        self._check(self._L.tba_group_level_stats(
+            self._h, C.c_int(kind), C.c_int(return_p), i64(fm_offset), i64(min_test_reads),
+            *self._pileup_args(pileup, True), f64(smallest_pval), _p(stats, f64), _p(poss, i64), _p(cov, i64),
+            _p(ccov, i64), _p(counts, i64)), 'tba_group_level_stats')
+        return stats, poss, cov, ccov, counts
+
+    def reads_ref_levels(self, est_mean, fm_offset, min_test_reads, pileup, prior_means, prior_sds, w_mean, w_sd):
+        """-> (level means, level sds, coverage) at pileup.pos_off; priors (both or neither) blended in"""
+        n_pos = int(pileup.pos_off[-1])
+        pm, ps = _f64(prior_means), _f64(prior_sds)
+        lm, ls = np.empty(n_pos, dtype=np.float64), np.empty(n_pos, dtype=np.float64)
+        cov = np.empty(n_pos, dtype=np.int64)
+        self._check(self._L.tba_reads_ref_levels(
+            self._h, C.c_int(int(bool(est_mean))), i64(fm_offset), i64(min_test_reads),
+            *self._pileup_args(pileup, False), _p(pm, f64), _p(ps, f64), f64(w_mean), f64(w_sd), _p(lm, f64),
+            _p(ls, f64), _p(cov, i64)), 'tba_reads_ref_levels')
+        return lm, ls, cov
+
+    def _site_fractions(self, form, trk_start, trk_end, z_args, win_args, n_stats, single_read_thresh,
+                        lower_thresh, damp_counts, return_per_read):
+        trk_start, trk_end = _i64(trk_start), _i64(trk_end)
+        pos_off = np.concatenate([[0], np.cumsum(trk_end - trk_start)]).astype(np.int64)
+        n_trk, n_pos = trk_start.shape[0], int(pos_off[-1])
+        frac = np.empty(n_pos, dtype=np.float64)
+        poss, cov, valid = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
+        counts, trk_stats = np.empty(n_trk, dtype=np.int64), np.empty(n_trk, dtype=np.int64)
+        damp = None if damp_counts is None else np.empty(n_pos, dtype=np.float64)
+        per_read = np.empty(n_stats, dtype=np.float64) if return_per_read else None
+        self._check(self._L.tba_site_fractions(
+            self._h, C.c_int(form), i64(n_trk), _p(trk_start, i64), _p(trk_end, i64), *z_args, *win_args,
+            f64(float(single_read_thresh)), None if lower_thresh is None else (f64 * 1)(float(lower_thresh)),
+            None if damp_counts is None else (f64 * 2)(*damp_counts), _p(frac, f64), _p(poss, i64), _p(cov, i64),
+            _p(valid, i64), _p(damp, f64), _p(counts, i64), _p(trk_stats, i64), _p(per_read, f64)),
+            'tba_site_fractions')
+        return SiteFractions(pos_off, frac, poss, cov, valid, damp, counts, trk_stats, per_read)
+
+    def site_fractions_z(self, trk_start, trk_end, means, ref_means, ref_sds, off, read_track, read_pos,
+                         fm_offset, floor_out, smallest_pval, single_read_thresh, lower_thresh=None,
+                         damp_counts=None, return_per_read=False):
+        """tba_site_fractions, z form: the statistics of read_pvals, read r on track read_track[r] from
+        position read_pos[r], collated per position of each track -> SiteFractions.  damp_counts: (unmod, mod)"""
+        m, r, s = _f64(means), _f64(ref_means), _f64(ref_sds)
+        off, r_trk, r_pos = _i64(off), _i64(read_track), _i64(read_pos)
+        if not (m.shape[0] == r.shape[0] == s.shape[0] == int(off[-1])) or \
+                not (off.shape[0] - 1 == r_trk.shape[0] == r_pos.shape[0]):
+            raise ValueError('per-base arrays, offsets and per-read arrays disagree')
+        z_args = (_p(m, f64), _p(r, f64), _p(s, f64), _p(off, i64), i64(r_trk.shape[0]), _p(r_trk, i64),
+                  _p(r_pos, i64), i64(int(fm_offset)), C.c_int(int(floor_out)), f64(smallest_pval))
+        return self._site_fractions(0, trk_start, trk_end, z_args, _site_other_form(0), m.shape[0],
+                                    single_read_thresh, lower_thresh, damp_counts, return_per_read)
+
+    def site_fractions_windows(self, trk_start, trk_end, kind, means, ref_means, alt_means, ref_vars, alt_vars,
+                               starts, width, win_track, win_pos, par, single_read_thresh, lower_thresh=None,
+                               damp_counts=None, return_per_read=False):
+        """tba_site_fractions, window form: the statistics of llh_ratio_windows (all value arrays
+        of one length), window w on track win_track[w] at position win_pos[w] -> SiteFractions"""
+        m, r, a, rv, av = _f64(means), _f64(ref_means), _f64(alt_means), _f64(ref_vars), _f64(alt_vars)
+        st, w_trk, w_pos = _i64(starts), _i64(win_track), _i64(win_pos)
+        n = m.shape[0]
+        if not (r.shape[0] == a.shape[0] == rv.shape[0] == n) or (av is not None and av.shape[0] != n) or \
+                not (st.shape[0] == w_trk.shape[0] == w_pos.shape[0]):
+            raise ValueError('window arrays disagree')
+        win_args = (C.c_int(int(kind)), _p(a, f64), _p(rv, f64), _p(av, f64), i64(n), i64(int(width)),
+                    _p(st, i64), i64(st.shape[0]), (f64 * 3)(*par), _p(w_trk, i64), _p(w_pos, i64))
+        return self._site_fractions(1, trk_start, trk_end, (_p(m, f64), _p(r, f64)) + _site_other_form(1),
+                                    win_args, st.shape[0], single_read_thresh, lower_thresh, damp_counts,
+                                    return_per_read)
 
     def stats(self):
         a, c = f64(0), f64(0)

@@ -1667,6 +1667,21 @@ extern "C" int tba_c_base_traceback(tba_engine *e, const double *curr_b_data, in
     return sc.get(sig_pos, d_out, 1);
 }
 
+static int check_csr_off(const int64_t *off, i64 n)   // (this and check_windows: shared with tba_site_fractions)
+{
+    if (n > 0 && off[0] != 0) return set_err(TBA_E_ARG, "offset arrays must start at 0");
+    for (i64 i = 0; i < n; i++)
+        if (off[i + 1] < off[i]) return set_err(TBA_E_ARG, "offset arrays must be non-decreasing");
+    return TBA_OK;
+}
+static int check_windows(int kind, const int64_t *starts, i64 n_windows, i64 width, i64 n_values)
+{
+    for (i64 i = 0; i < n_windows; i++)
+        if (starts[i] < 0 || starts[i] + width > n_values || (kind != 0 && starts[i] >= n_values))
+            return set_err(TBA_E_ARG, "window outside the arrays");
+    return TBA_OK;
+}
+
 extern "C" int tba_llh_ratio_windows(tba_engine *e, int kind, const double *means,
     const double *ref_means, const double *alt_means, const double *ref_vars,
     const double *alt_vars, int64_t n_values, int64_t width, const int64_t *starts,
@@ -1677,9 +1692,7 @@ extern "C" int tba_llh_ratio_windows(tba_engine *e, int kind, const double *mean
         n_windows < 0)
         return set_err(TBA_E_ARG, "bad arguments");
     if (n_windows == 0) return TBA_OK;
-    for (i64 i = 0; i < n_windows; i++)
-        if (starts[i] < 0 || starts[i] + width > n_values || (kind != 0 && starts[i] >= n_values))
-            return set_err(TBA_E_ARG, "window outside the arrays");
+    if (const int rc = check_windows(kind, starts, n_windows, width, n_values)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     Scratch sc;
     const double *d_m = sc.in(means, n_values);
@@ -1704,9 +1717,7 @@ extern "C" int tba_read_pvals(tba_engine *e, const double *means, const double *
         fm_offset > 64)
         return set_err(TBA_E_ARG, "bad arguments");
     if (n_reads == 0) return TBA_OK;
-    if (off[0] != 0) return set_err(TBA_E_ARG, "offset arrays must start at 0");
-    for (i64 i = 0; i < n_reads; i++)
-        if (off[i + 1] < off[i]) return set_err(TBA_E_ARG, "offset arrays must be non-decreasing");
+    if (const int rc = check_csr_off(off, n_reads)) return rc;
     const i64 total = off[n_reads];
     if (total == 0) return TBA_OK;
     HIP_TRY(hipSetDevice(e->device));
@@ -1731,11 +1742,22 @@ namespace {
 // valid levels), so no coverage comes back to the host between the steps.
 struct Pileup {
     GrpArgs a{};
-    i64 n_pos = 0;
     i32 *cov = nullptr, *run_a = nullptr, *run_b = nullptr;
     i64 *lv_off = nullptr, *out_idx = nullptr, *counts = nullptr;
     double *levels = nullptr;
 };
+
+// the levels of every position sorted in place, one kernel per class of pileup size (a failure stays in sc.rc)
+static void grp_sort_levels(tba_engine *e, Scratch &sc, const Pileup &P)
+{
+    i64 *lists = sc.out<i64>(6 * P.a.n_pos);
+    u32 *cls = sc.out<u32>(3);
+    if (sc.rc || sc.hip(hipMemsetAsync(cls, 0, 3 * sizeof(u32), e->stream), "hipMemsetAsync")) return;
+    k_grp_classify<<<grid_for(2 * P.a.n_pos), 256, 0, e->stream>>>(P.a.n_pos, P.cov, P.out_idx, lists, cls);
+    k_grp_sort_wave<<<1024, 256, 0, e->stream>>>(lists, cls, P.cov, P.lv_off, P.levels);
+    k_grp_sort_wg<<<1024, 256, 0, e->stream>>>(lists + 2 * P.a.n_pos, cls + 1, P.cov, P.lv_off, P.levels, 0);
+    k_grp_sort_wg<<<256, 256, 0, e->stream>>>(lists + 4 * P.a.n_pos, cls + 2, P.cov, P.lv_off, P.levels, 1);
+}
 
 static int grp_pileup(tba_engine *e, Scratch &sc, Pileup &P, i64 fm, i64 min_reads, int two_groups,
     i64 min_run, bool sort, i64 n_regions, const int64_t *reg_start, const int64_t *reg_end,
@@ -1777,7 +1799,6 @@ static int grp_pileup(tba_engine *e, Scratch &sc, Pileup &P, i64 fm, i64 min_rea
     a.read_ctrl = read_ctrl ? sc.in(read_ctrl, n_reads) : nullptr;
     if (!read_ctrl) { int8_t *z = sc.out<int8_t>(n_reads); if (z) sc.hip(hipMemsetAsync(z, 0, n_reads, e->stream), "hipMemsetAsync"); a.read_ctrl = z; }
     a.means = sc.in(means, n_means);
-    P.n_pos = n_pos;
     P.cov = sc.out<i32>(2 * n_pos);
     P.run_a = sc.out<i32>(n_pos);
     P.run_b = sc.out<i32>(n_pos);
@@ -1785,21 +1806,12 @@ static int grp_pileup(tba_engine *e, Scratch &sc, Pileup &P, i64 fm, i64 min_rea
     P.out_idx = sc.out<i64>(n_pos);
     P.counts = sc.out<i64>(n_regions);
     P.levels = sc.out<double>(n_lv);
-    i64 *lists = sc.out<i64>(6 * n_pos);
-    u32 *cls = sc.out<u32>(3);
-    if (sc.rc) return sc.rc;
-    sc.hip(hipMemsetAsync(cls, 0, 3 * sizeof(u32), e->stream), "hipMemsetAsync");
     if (sc.rc) return sc.rc;
     k_grp_pileup<false><<<grid_for(n_pos), 256, 0, e->stream>>>(a, P.cov, nullptr, nullptr);
     k_grp_scan<<<(unsigned)n_regions, 64, 0, e->stream>>>(a, P.cov, min_reads, two_groups, min_run,
         P.lv_off, P.run_a, P.run_b, P.out_idx, P.counts);
     k_grp_pileup<true><<<grid_for(n_pos), 256, 0, e->stream>>>(a, P.cov, P.lv_off, P.levels);
-    if (sort) {
-        k_grp_classify<<<grid_for(2 * n_pos), 256, 0, e->stream>>>(n_pos, P.cov, P.out_idx, lists, cls);
-        k_grp_sort_wave<<<1024, 256, 0, e->stream>>>(lists, cls, P.cov, P.lv_off, P.levels);
-        k_grp_sort_wg<<<1024, 256, 0, e->stream>>>(lists + 2 * n_pos, cls + 1, P.cov, P.lv_off, P.levels, 0);
-        k_grp_sort_wg<<<256, 256, 0, e->stream>>>(lists + 4 * n_pos, cls + 2, P.cov, P.lv_off, P.levels, 1);
-    }
+    if (sort) grp_sort_levels(e, sc, P);
     return sc.hip(hipGetLastError(), "launch");
 }
 }  // namespace
@@ -1824,7 +1836,7 @@ extern "C" int tba_group_level_stats(tba_engine *e, int stat_kind, int return_p,
             n_regions, reg_start, reg_end, reg_strand, reg_read_off, n_reads, read_start, read_strand,
             read_ctrl, read_off, means))
         return rc;
-    const i64 n_pos = P.n_pos;
+    const i64 n_pos = P.a.n_pos;
     double *raw = sc.out<double>(n_pos), *d_stats = sc.out<double>(n_pos);
     i64 *d_poss = sc.out<i64>(n_pos), *d_cov = sc.out<i64>(n_pos), *d_ccov = sc.out<i64>(n_pos);
     if (sc.rc) return sc.rc;
@@ -1859,24 +1871,15 @@ extern "C" int tba_reads_ref_levels(tba_engine *e, int est_mean, int64_t fm_offs
     if (const int rc = grp_pileup(e, sc, P, fm_offset, min_test_reads, 0, 1, false, n_regions, reg_start,
             reg_end, reg_strand, reg_read_off, n_reads, read_start, read_strand, nullptr, read_off, means))
         return rc;
-    const i64 n_pos = P.n_pos;
-    double *mean = sc.out<double>(n_pos), *sd = sc.out<double>(n_pos);
-    double *d_m = sc.out<double>(n_pos), *d_s = sc.out<double>(n_pos);
+    const i64 n_pos = P.a.n_pos;
+    double *mean = sc.out<double>(n_pos), *sd = sc.out<double>(n_pos), *d_m = sc.out<double>(n_pos), *d_s = sc.out<double>(n_pos);
     i64 *d_c = sc.out<i64>(n_pos);
     const double *d_pm = prior_means ? sc.in(prior_means, n_pos) : nullptr;
     const double *d_ps = prior_sds ? sc.in(prior_sds, n_pos) : nullptr;
-    i64 *lists = sc.out<i64>(6 * n_pos);
-    u32 *cls = sc.out<u32>(3);
     if (sc.rc) return sc.rc;
-    sc.hip(hipMemsetAsync(cls, 0, 3 * sizeof(u32), e->stream), "hipMemsetAsync");
     // moments in read order first, then the sort for the median
     k_ref_moments<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, P.cov, P.lv_off, P.out_idx, P.levels, mean, sd);
-    if (!est_mean) {
-        k_grp_classify<<<grid_for(2 * n_pos), 256, 0, e->stream>>>(n_pos, P.cov, P.out_idx, lists, cls);
-        k_grp_sort_wave<<<1024, 256, 0, e->stream>>>(lists, cls, P.cov, P.lv_off, P.levels);
-        k_grp_sort_wg<<<1024, 256, 0, e->stream>>>(lists + 2 * n_pos, cls + 1, P.cov, P.lv_off, P.levels, 0);
-        k_grp_sort_wg<<<256, 256, 0, e->stream>>>(lists + 4 * n_pos, cls + 2, P.cov, P.lv_off, P.levels, 1);
-    }
+    if (!est_mean) grp_sort_levels(e, sc, P);
     k_ref_finish<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, est_mean, P.cov, P.lv_off, P.out_idx,
         P.levels, mean, sd, d_pm, d_ps, prior_w_mean, prior_w_sd, d_m, d_s, d_c);
     if (sc.sync(e->stream)) return sc.rc;
@@ -1914,21 +1917,18 @@ extern "C" int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, con
         pos_off[t + 1] = pos_off[t] + (trk_end[t] - trk_start[t]);
     }
     const i64 n_pos = pos_off[n_tracks];
-    i64 total = 0;
+    const i64 total = form == 0 && n_reads > 0 ? off[n_reads] : 0;
     if (form == 0) {
-        if (n_reads > 0 && off[0] != 0) return set_err(TBA_E_ARG, "offset arrays must start at 0");
+        if (const int rc = check_csr_off(off, n_reads)) return rc;
         for (i64 r = 0; r < n_reads; r++) {
-            if (off[r + 1] < off[r]) return set_err(TBA_E_ARG, "offset arrays must be non-decreasing");
             const i64 t = read_track[r];
             if (t < 0 || t >= n_tracks) return set_err(TBA_E_ARG, "read outside the tracks");
             if (off[r + 1] > off[r] && (read_pos[r] < trk_start[t] || read_pos[r] + (off[r + 1] - off[r]) > trk_end[t]))
                 return set_err(TBA_E_ARG, "statistic position outside its track");
         }
-        total = n_reads > 0 ? off[n_reads] : 0;
     } else {
+        if (const int rc = check_windows(kind, starts, n_windows, width, n_values)) return rc;
         for (i64 w = 0; w < n_windows; w++) {
-            if (starts[w] < 0 || starts[w] + width > n_values || (kind != 0 && starts[w] >= n_values))
-                return set_err(TBA_E_ARG, "window outside the arrays");
             const i64 t = win_track[w];
             if (t < 0 || t >= n_tracks) return set_err(TBA_E_ARG, "window outside the tracks");
             if (win_pos[w] < trk_start[t] || win_pos[w] >= trk_end[t])

@@ -11,12 +11,17 @@ The numeric kernels (normalisation, event detection, DP ...) live in csrc/ and a
 through tombo_amd.resquiggle.
 """
 import os
+from collections import namedtuple
+
 import numpy as np
 
-from . import tombo_helper as th
+from . import tombo_helper as th, _native
+from ._c_helper import llh_ratio_windows
 from ._default_parameters import (
     ALGN_PARAMS_TABLE, SEG_PARAMS_TABLE, RNA_SAMP_TYPE, DNA_SAMP_TYPE, STANDARD_MODELS,
-    HALF_NORM_EXPECTED_VAL, MIN_EVENT_TO_SEQ_RATIO, STALL_PARAMS)
+    HALF_NORM_EXPECTED_VAL, MIN_EVENT_TO_SEQ_RATIO, STALL_PARAMS, SMALLEST_PVAL, FM_OFFSET_DEFAULT,
+    SAMP_COMP_TXT, DE_NOVO_TXT, ALT_MODEL_TXT, CONST_SD_MODEL, OCLLHR_SCALE, OCLLHR_HEIGHT,
+    OCLLHR_POWER, MEAN_PRIOR_CONST, SD_PRIOR_CONST)
 
 _MODEL_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tombo_models')
 _BASE_CODE = np.full(256, 255, dtype=np.uint8)
@@ -126,6 +131,14 @@ class TomboModel(object):
         return means, sds
 
 
+def _engine(engine=None):
+    """the engine a statistics call runs on: the given one, else the process-wide engine"""
+    if engine is not None:
+        return engine
+    from . import resquiggle as rq   # (resquiggle imports this module)
+    return rq.get_engine()
+
+
 def get_dynamic_prog_params(match_evalue):
     return HALF_NORM_EXPECTED_VAL + match_evalue, match_evalue
 
@@ -169,12 +182,11 @@ def identify_stalls(all_raw_signal, stall_params=None, return_metric=False):
     taken as they are (DAC sums are exact, float sums keep np.cumsum's order)."""
     if return_metric:
         raise NotImplementedError('the per-sample stall metric stays on the device')
-    from . import _native, resquiggle as rq
     sp = th.stallParams(**STALL_PARAMS) if stall_params is None else stall_params
     if sp.lower_pctl is not None and sp.upper_pctl is not None:
         raise NotImplementedError('the percentile stall detector (PCTL_STALL_PARAMS) is not the '
                                   'reference default and not part of this engine')
-    return list(_native.identify_stalls(rq.get_engine(), all_raw_signal, sp))
+    return list(_native.identify_stalls(_engine(), all_raw_signal, sp))
 
 
 def remove_stall_cpts(stall_ints, valid_cpts):
@@ -202,15 +214,10 @@ def remove_stall_cpts(stall_ints, valid_cpts):
 # reference loads `norm_mean` / `base` of one read from its FAST5 file and computes with numpy /
 # scipy / Cython, one read per call; here the read is a `th.resquiggledRead` (the same columns in
 # memory, e.g. straight from `resquiggle_batch_events`), the `*_batch` forms take a list of reads
-# and run ONE kernel launch for all tested positions of all reads (`tba_read_pvals`,
-# `tba_llh_ratio_windows`); the single-read functions are batches of one and keep the reference's
-# return shape ({name: stats}, {name: positions}, read_id).  Host code only does what the
-# reference does with slices: clipping to the region, strand flips, motif search.
-from ._default_parameters import (   # noqa: E402
-    SMALLEST_PVAL, FM_OFFSET_DEFAULT, SAMP_COMP_TXT, DE_NOVO_TXT, ALT_MODEL_TXT, CONST_SD_MODEL,
-    OCLLHR_SCALE, OCLLHR_HEIGHT, OCLLHR_POWER)
-
-
+# and run ONE kernel launch for all tested positions of all reads (`Engine.read_pvals`,
+# `Engine.llh_ratio_windows`); the single-read functions are batches of one and keep the
+# reference's return shape ({name: stats}, {name: positions}, read_id).  Host code only does what
+# the reference does with slices: clipping to the region, strand flips, motif search.
 class AltModel(object):
     """Alternate-base k-mer model (tombo_stats.py:922-1125), from
     `kmer_ref=[(kmer, pos, mean, sd), ...]`: expected level of a k-mer when the base at `pos` is
@@ -239,26 +246,43 @@ class AltModel(object):
                 np.array([self.sds.get((k, p), nan) for k, p in zip(seq_kmers, pos_range)]))
 
 
-def _read_pvals(means, ref_means, ref_sds, off, fm_offset, floor_out, engine=None):
-    import ctypes as C
-    from . import _native, resquiggle as rq
-    eng = rq.get_engine() if engine is None else engine
-    m, r, s = (np.ascontiguousarray(a, dtype=np.float64) for a in (means, ref_means, ref_sds))
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    if not (m.shape[0] == r.shape[0] == s.shape[0] == int(off[-1])):
-        raise ValueError('per-base arrays and offsets disagree')
-    out = np.empty(m.shape[0], dtype=np.float64)
-    pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int64)
-    eng._check(eng._L.tba_read_pvals(
-        eng._h, m.ctypes.data_as(pd), r.ctypes.data_as(pd), s.ctypes.data_as(pd),
-        off.ctypes.data_as(pi), C.c_int64(off.shape[0] - 1), C.c_int64(int(fm_offset)),
-        C.c_int(int(floor_out)), C.c_double(SMALLEST_PVAL), out.ctypes.data_as(pd)), 'tba_read_pvals')
-    return out
+def _csr_offsets(lengths):
+    """int64 [0, l0, l0 + l1, ...]"""
+    return np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)]).astype(np.int64)
+
+
+def _concat_f64(arrays):
+    return np.ascontiguousarray(np.concatenate(arrays) if arrays else np.empty(0), dtype=np.float64)
+
+
+def _only(batch_of_one):
+    """the result of a batch of one; an exception stored in its place is raised"""
+    if isinstance(batch_of_one[0], Exception):
+        raise batch_of_one[0]
+    return batch_of_one[0]
 
 
 def _fm_guard(n, fm_offset):
     if fm_offset > 0 and n < 2 * fm_offset + 1:   # calc_window_fishers_method, :2257-2259
         raise th.TomboError("P-values vector too short for Fisher's Method window compuation.")
+
+
+def _clip_to_region(rd, reg_data, fm_offset, lags, *cols):
+    """the region clip the z tests start with (:3815-3836, :3716-3737): the read-centric columns lose
+    what lies further outside the region than fm_offset plus the k-mer lag of that end (`lags`:
+    (before, after) on '+') -> (region start, read start, read end, the two lags, clipped columns)"""
+    reg_start, reg_end = (rd.start, rd.end) if reg_data is None else (reg_data.start, reg_data.end)
+    lag_b, lag_e = lags if rd.strand == '+' else lags[::-1]
+    read_start, read_end = rd.start, rd.end
+    if read_start + lag_b + fm_offset < reg_start:
+        c = reg_start - (read_start + lag_b + fm_offset)
+        read_start = reg_start - lag_b - fm_offset
+        cols = [x[c:] if rd.strand == '+' else x[:-c] for x in cols]
+    if read_end - lag_e - fm_offset > reg_end:
+        c = (read_end - lag_e - fm_offset) - reg_end
+        read_end = reg_end + lag_e + fm_offset
+        cols = [x[:-c] if rd.strand == '+' else x[c:] for x in cols]
+    return reg_start, read_start, read_end, lag_b, lag_e, cols
 
 
 def _prep_de_novo_read(rd, std_ref, fm_offset, reg_data):
@@ -268,55 +292,47 @@ def _prep_de_novo_read(rd, std_ref, fm_offset, reg_data):
     dn = K - cp - 1
     if rd.means is None or rd.seq is None:
         raise th.TomboError('Read does not contain valid re-squiggled data.')
-    reg_start = reg_data.start if reg_data is not None else rd.start
-    reg_size = (reg_data.end - reg_data.start) if reg_data is not None else rd.end - rd.start
-    lag_b, lag_e = (cp, dn) if rd.strand == '+' else (dn, cp)
-    means, seq = np.asarray(rd.means, dtype=np.float64), rd.seq
-    read_start, read_end = rd.start, rd.end
-    # clip to the region (positions outside are not tested), :3815-3836
-    if read_start + lag_b + fm_offset < reg_start:
-        c = reg_start - (read_start + lag_b + fm_offset)
-        read_start = reg_start - lag_b - fm_offset
-        means, seq = (means[c:], seq[c:]) if rd.strand == '+' else (means[:-c], seq[:-c])
-    if read_end - lag_e - fm_offset > reg_start + reg_size:
-        c = (read_end - lag_e - fm_offset) - (reg_start + reg_size)
-        read_end = reg_start + reg_size + lag_e + fm_offset
-        means, seq = (means[:-c], seq[:-c]) if rd.strand == '+' else (means[c:], seq[c:])
+    _, read_start, read_end, lag_b, lag_e, (means, seq) = _clip_to_region(
+        rd, reg_data, fm_offset, (cp, dn), np.asarray(rd.means, dtype=np.float64), rd.seq)
     if len(seq) < K:
         raise th.TomboError('Read does not contain information in this region.')
     ref_m, ref_s = std_ref.get_exp_levels_from_seq(seq, rd.strand == '-')
     if rd.strand == '-':
         means = means[::-1]
     means = means[lag_b:means.shape[0] - lag_e]
-    read_start += lag_b
-    read_end -= lag_e
     _fm_guard(means.shape[0], fm_offset)
-    return means, ref_m, ref_s, read_start, read_end
+    return means, ref_m, ref_s, read_start + lag_b, read_end - lag_e
+
+
+def _read_pvals(means, ref_means, ref_sds, off, fm_offset, floor_out, engine=None):
+    return _engine(engine).read_pvals(means, ref_means, ref_sds, off, fm_offset, floor_out, SMALLEST_PVAL)
+
+
+def _z_pvals_per_read(prep, fm_offset, floor_out, engine):
+    """one `read_pvals` call for prepared reads (means, ref_means, ref_sds, ...) -> p-values per read"""
+    off = _csr_offsets([p[0].shape[0] for p in prep])
+    pv = _read_pvals(*(np.concatenate([p[k] for p in prep]) for k in range(3)), off, fm_offset, floor_out, engine)
+    return [pv[a:b] for a, b in zip(off[:-1], off[1:])]
 
 
 def compute_de_novo_read_stats_batch(reads, std_ref, fm_offset=FM_OFFSET_DEFAULT, reg_data=None,
                                      engine=None):
     """compute_de_novo_read_stats (tombo_stats.py:3771-3873) for a list of `th.resquiggledRead`;
     per read (pvals, positions) or the TomboError the reference raises."""
-    prep, out = [], [None] * len(reads)
+    prep, out = {}, [None] * len(reads)
     for i, rd in enumerate(reads):
         try:
-            prep.append((i,) + _prep_de_novo_read(rd, std_ref, fm_offset, reg_data))
+            prep[i] = _prep_de_novo_read(rd, std_ref, fm_offset, reg_data)
         except th.TomboError as e:
             out[i] = e
     if prep:
-        off = np.concatenate([[0], np.cumsum([p[1].shape[0] for p in prep])])
-        pv = _read_pvals(np.concatenate([p[1] for p in prep]), np.concatenate([p[2] for p in prep]),
-                         np.concatenate([p[3] for p in prep]), off, fm_offset, True, engine)
-        for k, (i, _, _, _, rs, re_) in enumerate(prep):
-            out[i] = (pv[off[k]:off[k + 1]].copy(), np.arange(rs, re_))
+        for (i, p), pv in zip(prep.items(), _z_pvals_per_read(list(prep.values()), fm_offset, True, engine)):
+            out[i] = (pv.copy(), np.arange(p[3], p[4]))
     return out
 
 
 def compute_de_novo_read_stats(r_data, std_ref, fm_offset=FM_OFFSET_DEFAULT, reg_data=None):
-    res = compute_de_novo_read_stats_batch([r_data], std_ref, fm_offset, reg_data)[0]
-    if isinstance(res, Exception):
-        raise res
+    res = _only(compute_de_novo_read_stats_batch([r_data], std_ref, fm_offset, reg_data))
     return {DE_NOVO_TXT: res[0]}, {DE_NOVO_TXT: res[1]}, r_data.read_id
 
 
@@ -325,18 +341,8 @@ def _prep_sample_compare_read(rd, cm, cs, fm_offset, reg_data):
     strand flip, the control levels under the read -> (means, ctrl_means, ctrl_sds, first position)"""
     if rd.means is None:
         raise th.TomboError('Read does not contain re-squiggled level means.')
-    reg_start = reg_data.start if reg_data is not None else rd.start
-    reg_size = (reg_data.end - reg_data.start) if reg_data is not None else rd.end - rd.start
-    means = np.asarray(rd.means, dtype=np.float64)
-    read_start, read_end = rd.start, rd.end
-    if read_start + fm_offset < reg_start:
-        c = reg_start - (read_start + fm_offset)
-        read_start = reg_start - fm_offset
-        means = means[c:] if rd.strand == '+' else means[:-c]
-    if read_end - fm_offset > reg_start + reg_size:
-        c = (read_end - fm_offset) - (reg_start + reg_size)
-        read_end = reg_start + reg_size + fm_offset
-        means = means[:-c] if rd.strand == '+' else means[c:]
+    reg_start, read_start, read_end, _, _, (means,) = _clip_to_region(
+        rd, reg_data, fm_offset, (0, 0), np.asarray(rd.means, dtype=np.float64))
     if rd.strand == '-':
         means = means[::-1]
     a, b = read_start - reg_start + fm_offset, read_end - reg_start + fm_offset
@@ -356,35 +362,28 @@ def compute_sample_compare_read_stats_batch(reads, ctrl_means, ctrl_sds,
     `ctrl_means` / `ctrl_sds`: control-sample levels over the region extended by fm_offset on
     both sides (NaN where the control has no coverage); with reg_data=None every read is its own
     region, so they are per-read lists."""
-    ctrl_means_l = ctrl_means if reg_data is None else None
-    prep, out = [], [None] * len(reads)
+    prep, out = {}, [None] * len(reads)
     for i, rd in enumerate(reads):
         try:
             if rd.means is None:
                 raise th.TomboError('Read does not contain re-squiggled level means.')
-            cm = np.asarray(ctrl_means_l[i] if ctrl_means_l is not None else ctrl_means, dtype=np.float64)
-            cs = np.asarray(ctrl_sds[i] if ctrl_means_l is not None else ctrl_sds, dtype=np.float64)
-            prep.append((i,) + _prep_sample_compare_read(rd, cm, cs, fm_offset, reg_data))
+            cm = np.asarray(ctrl_means[i] if reg_data is None else ctrl_means, dtype=np.float64)
+            cs = np.asarray(ctrl_sds[i] if reg_data is None else ctrl_sds, dtype=np.float64)
+            prep[i] = _prep_sample_compare_read(rd, cm, cs, fm_offset, reg_data)
         except th.TomboError as e:
             out[i] = e
     if prep:
-        off = np.concatenate([[0], np.cumsum([p[1].shape[0] for p in prep])])
-        pv = _read_pvals(np.concatenate([p[1] for p in prep]), np.concatenate([p[2] for p in prep]),
-                         np.concatenate([p[3] for p in prep]), off, fm_offset, False, engine)
-        for k, (i, _, _, _, rs) in enumerate(prep):
-            p = pv[off[k]:off[k + 1]]
-            poss = np.where(~np.isnan(p))[0]
-            out[i] = (p[poss].copy(), poss + rs)
+        for (i, p), pv in zip(prep.items(), _z_pvals_per_read(list(prep.values()), fm_offset, False, engine)):
+            poss = np.where(~np.isnan(pv))[0]
+            out[i] = (pv[poss].copy(), poss + p[3])
     return out
 
 
 def compute_sample_compare_read_stats(r_data, ctrl_means, ctrl_sds, fm_offset=FM_OFFSET_DEFAULT,
                                       reg_data=None):
-    res = compute_sample_compare_read_stats_batch(
+    res = _only(compute_sample_compare_read_stats_batch(
         [r_data], [ctrl_means] if reg_data is None else ctrl_means,
-        [ctrl_sds] if reg_data is None else ctrl_sds, fm_offset, reg_data)[0]
-    if isinstance(res, Exception):
-        raise res
+        [ctrl_sds] if reg_data is None else ctrl_sds, fm_offset, reg_data))
     return {SAMP_COMP_TXT: res[0]}, {SAMP_COMP_TXT: res[1]}, r_data.read_id
 
 
@@ -437,8 +436,7 @@ def _prep_alt_model_read(rd, std_ref, alt_refs, use_standard_llhr, reg_data, max
     K = std_ref.kmer_width
     if rd.means is None or rd.seq is None:
         raise th.TomboError('Read does not contain valid re-squiggled data.')
-    reg_start = reg_data.start if reg_data is not None else rd.start
-    reg_end = reg_data.end if reg_data is not None else rd.end
+    reg_start, reg_end = (rd.start, rd.end) if reg_data is None else (reg_data.start, reg_data.end)
     kmers, means, r_start, msseq = trim_seq_and_means(
         rd.seq, np.asarray(rd.means, dtype=np.float64), rd.start, reg_start, reg_end,
         rd.strand, K, std_ref.central_pos, max_bb, max_ab)
@@ -471,8 +469,7 @@ def compute_alt_model_read_stats_batch(reads, std_ref, alt_refs, use_standard_ll
                                        reg_data=None, engine=None):
     """compute_alt_model_read_stats (tombo_stats.py:3972-4083) for a list of reads: per read
     ({alt_name: llhrs}, {alt_name: positions}) or the TomboError.  Every motif hit of every read
-    and model becomes one window of ONE `tba_llh_ratio_windows` launch."""
-    from ._c_helper import llh_ratio_windows
+    and model becomes one window of ONE `llh_ratio_windows` launch."""
     K = std_ref.kmer_width
     max_bb, max_ab = _alt_motif_bounds(alt_refs)
     out = [None] * len(reads)
@@ -489,11 +486,11 @@ def compute_alt_model_read_stats_batch(reads, std_ref, alt_refs, use_standard_ll
             out[i] = e
     if wins:
         kind = _llh_kind(use_standard_llhr)
-        cat = lambda k: np.concatenate([w[k] for w in wins])
+        cols = [np.concatenate([w[k] for w in wins]) for k in range(2, 7)]
         vals = llh_ratio_windows(
-            kind, cat(2), cat(3), cat(4), cat(5), np.arange(len(wins), dtype=np.int64) * K, K,
-            alt_vars=cat(6) if kind == 0 else None, scale_factor=OCLLHR_SCALE,
-            density_height_factor=OCLLHR_HEIGHT, density_height_power=OCLLHR_POWER)
+            kind, *cols[:4], np.arange(len(wins), dtype=np.int64) * K, K,
+            alt_vars=cols[4] if kind == 0 else None, scale_factor=OCLLHR_SCALE,
+            density_height_factor=OCLLHR_HEIGHT, density_height_power=OCLLHR_POWER, engine=engine)
         fill = {}
         for (i, name, *_), v in zip(wins, vals):
             k = fill.get((i, name), 0)
@@ -504,10 +501,8 @@ def compute_alt_model_read_stats_batch(reads, std_ref, alt_refs, use_standard_ll
 
 def compute_alt_model_read_stats(r_data, std_ref, alt_refs, use_standard_llhr=False,
                                  reg_data=None):
-    res = compute_alt_model_read_stats_batch([r_data], std_ref, alt_refs, use_standard_llhr,
-                                             reg_data)[0]
-    if isinstance(res, Exception):
-        raise res
+    res = _only(compute_alt_model_read_stats_batch([r_data], std_ref, alt_refs, use_standard_llhr,
+                                                   reg_data))
     return res[0], res[1], r_data.read_id
 
 
@@ -515,10 +510,9 @@ def compute_alt_model_read_stats(r_data, std_ref, alt_refs, use_standard_llhr=Fa
 # level_sample_compare and the control reference levels of model_sample_compare: a pileup of the
 # levels of many reads at each genomic position (compute_group_reg_stats, tombo_stats.py:4236-4398;
 # get_reads_ref, :3627-3673).  The reference loops over positions in numpy; here a list of regions
-# is one engine call (`tba_group_level_stats`, `tba_reads_ref_levels`, kernels in csrc/k_group.h).
-# A region is a `th.regionData` (or anything with chrm / strand / start / end / reads [/ seq]).
-from ._default_parameters import MEAN_PRIOR_CONST, SD_PRIOR_CONST   # noqa: E402
-
+# is one engine call (`Engine.group_level_stats`, `Engine.reads_ref_levels`, kernels in
+# csrc/k_group.h).  A region is a `th.regionData` (or anything with chrm / strand / start / end /
+# reads [/ seq]).
 KS_TEST_TXT = 'ks_test'
 U_TEST_TXT = 'u_test'
 T_TEST_TXT = 't_test'
@@ -528,31 +522,42 @@ T_STAT_TEST_TXT = 't_stat_test'
 _GROUP_KINDS = {KS_TEST_TXT: (0, 1), U_TEST_TXT: (1, 1), T_TEST_TXT: (2, 1),
                 KS_STAT_TEST_TXT: (0, 0), U_STAT_TEST_TXT: (1, 0), T_STAT_TEST_TXT: (2, 0)}
 _STRAND_CODE = {'+': 0, '-': 1, None: 2}
+_NO_READS_MSG = 'Must annotate region with reads (see `TomboInterval.add_reads`) to extract base levels.'
+
+# CSR arrays of a list of regions and their reads; pos_off: the regions' extended positions
+Pileup = namedtuple('Pileup', 'reg_start reg_end reg_strand reg_read_off read_start read_strand '
+                              'read_ctrl read_off means pos_off')
+
+
+def _check_regions(regions, ctrl_regions=None, paired=False):
+    """region coordinates (paired: one control region with the same coordinates per region)"""
+    if paired:
+        if ctrl_regions is None or len(regions) != len(ctrl_regions):
+            raise ValueError('one control region per sample region')
+        for reg, ctrl in zip(regions, ctrl_regions):
+            if (reg.start, reg.end) != (ctrl.start, ctrl.end):
+                raise ValueError('sample and control regions must have the same coordinates')
+    for reg in regions:
+        if reg.end <= reg.start:
+            raise ValueError('region end must be greater than its start')
 
 
 def _pileup_inputs(regions, groups, fm_offset):
-    """CSR arrays of a list of regions: per region its reads (as many lists as `groups`, the group
+    """the Pileup of a list of regions: per region its reads (as many lists as `groups`, the group
     index of each list going to read_ctrl)"""
-    reg_start, reg_end, reg_strand, reg_read_off = [], [], [], [0]
-    read_start, read_strand, read_ctrl, lens, means = [], [], [], [], []
+    reg_strand, reg_read_off = [], [0]
+    read_start, read_strand, read_ctrl, means = [], [], [], []
     for reg_lists in zip(*groups):
-        reg = reg_lists[0]
-        if reg.end <= reg.start:
-            raise ValueError('region end must be greater than its start')
-        if reg.strand not in _STRAND_CODE:
+        if reg_lists[0].strand not in _STRAND_CODE:
             raise ValueError('region strand must be "+", "-" or None')
-        reg_start.append(int(reg.start))
-        reg_end.append(int(reg.end))
-        reg_strand.append(_STRAND_CODE[reg.strand])
+        reg_strand.append(_STRAND_CODE[reg_lists[0].strand])
         for g, rg in enumerate(reg_lists):
             if rg.reads is None or len(rg.reads) == 0:
-                raise th.TomboError('Must annotate region with reads (see `TomboInterval.add_reads`) '
-                                    'to extract base levels.')
+                raise th.TomboError(_NO_READS_MSG)
             for rd in rg.reads:
-                m = rd.means
-                if m is None:
+                if rd.means is None:
                     continue   # get_read_reg_events: a read without levels is left out
-                m = np.asarray(m, dtype=np.float64)
+                m = np.asarray(rd.means, dtype=np.float64)
                 if rd.strand not in ('+', '-'):
                     raise ValueError('read strand must be "+" or "-"')
                 if rd.end is not None and rd.end - rd.start != m.shape[0]:
@@ -561,19 +566,15 @@ def _pileup_inputs(regions, groups, fm_offset):
                 read_start.append(int(rd.start))
                 read_strand.append(_STRAND_CODE[rd.strand])
                 read_ctrl.append(g)
-                lens.append(m.shape[0])
                 means.append(m)
         reg_read_off.append(len(read_start))
     i64, i8 = np.int64, np.int8
-    arr = lambda v, t: np.ascontiguousarray(np.array(v, dtype=t))
-    read_off = np.concatenate([[0], np.cumsum(lens, dtype=i64)]).astype(i64)
-    ext = np.array(reg_end, dtype=i64) - np.array(reg_start, dtype=i64) + 2 * fm_offset
-    return dict(reg_start=arr(reg_start, i64), reg_end=arr(reg_end, i64),
-                reg_strand=arr(reg_strand, i8), reg_read_off=arr(reg_read_off, i64),
-                read_start=arr(read_start, i64), read_strand=arr(read_strand, i8),
-                read_ctrl=arr(read_ctrl, i8), read_off=np.ascontiguousarray(read_off),
-                means=np.ascontiguousarray(np.concatenate(means) if means else np.empty(0)),
-                pos_off=np.concatenate([[0], np.cumsum(ext)]).astype(i64))
+    reg_start = np.array([int(reg.start) for reg in regions], dtype=i64)
+    reg_end = np.array([int(reg.end) for reg in regions], dtype=i64)
+    return Pileup(reg_start, reg_end, np.array(reg_strand, dtype=i8), np.array(reg_read_off, dtype=i64),
+                  np.array(read_start, dtype=i64), np.array(read_strand, dtype=i8),
+                  np.array(read_ctrl, dtype=i8), _csr_offsets([m.shape[0] for m in means]),
+                  _concat_f64(means), _csr_offsets(reg_end - reg_start + 2 * fm_offset))
 
 
 def _check_group_args(fm_offset, min_test_reads):
@@ -588,44 +589,22 @@ def compute_group_reg_stats_batch(regions, ctrl_regions, fm_offset, min_test_rea
     """compute_group_reg_stats for a list of regions (sample) and their control regions (same
     coordinates), ONE engine call; per region what the reference returns: [] or
     [(stat_type, th.groupStats)].  U ranks equal sample and control levels sample first."""
-    import ctypes as C
-    from . import resquiggle as rq
     if stat_type not in _GROUP_KINDS:
         raise NotImplementedError('Unrecognized test type.')
     _check_group_args(fm_offset, min_test_reads)
-    if len(regions) != len(ctrl_regions):
-        raise ValueError('one control region per sample region')
-    for reg, ctrl in zip(regions, ctrl_regions):
-        if (reg.start, reg.end) != (ctrl.start, ctrl.end):
-            raise ValueError('sample and control regions must have the same coordinates')
+    _check_regions(regions, ctrl_regions, paired=True)
     if len(regions) == 0:
         return []
     fm_offset, min_test_reads = int(fm_offset), int(min_test_reads)
-    kind, ret_p = _GROUP_KINDS[stat_type]
-    d = _pileup_inputs(regions, [regions, ctrl_regions], fm_offset)
-    n_pos = int(d['pos_off'][-1])
-    stats_o = np.empty(n_pos)
-    poss, cov, ccov = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
-    counts = np.empty(len(regions), dtype=np.int64)
-    eng = rq.get_engine() if engine is None else engine
-    pd, pi, pb = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int8)
-    P = lambda a, t: a.ctypes.data_as(t)
-    eng._check(eng._L.tba_group_level_stats(
-        eng._h, C.c_int(kind), C.c_int(ret_p), C.c_int64(fm_offset), C.c_int64(min_test_reads),
-        C.c_int64(len(regions)), P(d['reg_start'], pi), P(d['reg_end'], pi), P(d['reg_strand'], pb),
-        P(d['reg_read_off'], pi), C.c_int64(d['read_start'].shape[0]), P(d['read_start'], pi),
-        P(d['read_strand'], pb), P(d['read_ctrl'], pb), P(d['read_off'], pi), P(d['means'], pd),
-        C.c_double(SMALLEST_PVAL), P(stats_o, pd), P(poss, pi), P(cov, pi), P(ccov, pi),
-        P(counts, pi)), 'tba_group_level_stats')
+    pileup = _pileup_inputs(regions, [regions, ctrl_regions], fm_offset)
+    stats, poss, cov, ccov, counts = _engine(engine).group_level_stats(
+        *_GROUP_KINDS[stat_type], fm_offset, min_test_reads, pileup, SMALLEST_PVAL)
     out = []
-    for r, reg in enumerate(regions):
-        a, b = int(d['pos_off'][r]), int(d['pos_off'][r]) + int(counts[r])
-        if b == a:
-            out.append([])
-            continue
+    for reg, a, n in zip(regions, pileup.pos_off.tolist(), counts.tolist()):
+        b = a + n
         out.append([(stat_type, th.groupStats(
-            stats_o[a:b].copy(), poss[a:b].copy(), reg.chrm, reg.strand, reg.start,
-            cov[a:b].copy(), ccov[a:b].copy()))])
+            stats[a:b].copy(), poss[a:b].copy(), reg.chrm, reg.strand, reg.start,
+            cov[a:b].copy(), ccov[a:b].copy()))] if n else [])
     return out
 
 
@@ -635,60 +614,50 @@ def compute_group_reg_stats(reg_data, ctrl_reg_data, fm_offset, min_test_reads, 
                                          stat_type)[0]
 
 
+def _prior_levels(regions, fm_offset, std_ref):
+    """the model's levels over every region's extended positions (compute_posterior_samp_dists)"""
+    K, cp = std_ref.kmer_width, std_ref.central_pos
+    dn = K - cp - 1
+    pm, ps = [], []
+    for reg in regions:
+        if reg.seq is None:
+            raise ValueError('the prior blend needs the region sequence (regionData.seq)')
+        want = reg.end - reg.start + 2 * fm_offset + 2 * (K - 1)
+        if len(reg.seq) != want:
+            raise ValueError('region sequence must span [start - fm_offset - K + 1, '
+                             'end + fm_offset + K - 1) (%d bases, got %d)' % (want, len(reg.seq)))
+        b_lag, e_lag = (cp, dn) if reg.strand == '+' else (dn, cp)
+        seq = reg.seq[K - 1 - b_lag:len(reg.seq) - (K - 1 - e_lag)]
+        if reg.strand == '-':
+            seq = th.rev_comp(seq)
+        m, s = std_ref.get_exp_levels_from_seq_with_gaps(seq, reg.strand == '-')
+        pm.append(m)
+        ps.append(s)
+    return _concat_f64(pm), _concat_f64(ps)
+
+
 def get_reads_ref_batch(regions, min_test_reads, fm_offset, std_ref=None, prior_weights=None,
                         est_mean=False, engine=None):
     """get_reads_ref for a list of regions in ONE engine call: per region
     (level_means, level_sds, cov_dict) over [start - fm_offset, end + fm_offset).  With std_ref
     the levels are blended with the model's (compute_posterior_samp_dists); each region then needs
     `seq`, the '+' strand genome over [start - fm_offset - K + 1, end + fm_offset + K - 1)."""
-    import ctypes as C
-    from . import resquiggle as rq
     _check_group_args(fm_offset, min_test_reads)
+    _check_regions(regions)
     if len(regions) == 0:
         return []
     fm_offset, min_test_reads = int(fm_offset), int(min_test_reads)
-    d = _pileup_inputs(regions, [regions], fm_offset)
-    n_pos = int(d['pos_off'][-1])
-    prior_m = prior_s = None
-    w_m = w_s = 0.0
+    pileup = _pileup_inputs(regions, [regions], fm_offset)
+    prior_m, prior_s, w_m, w_s = None, None, 0.0, 0.0
     if std_ref is not None:
         if prior_weights is None:
             prior_weights = (MEAN_PRIOR_CONST, SD_PRIOR_CONST)
         w_m, w_s = float(prior_weights[0]), float(prior_weights[1])
-        K, cp = std_ref.kmer_width, std_ref.central_pos
-        dn = K - cp - 1
-        pm, ps = [], []
-        for reg in regions:
-            if reg.seq is None:
-                raise ValueError('the prior blend needs the region sequence (regionData.seq)')
-            want = reg.end - reg.start + 2 * fm_offset + 2 * (K - 1)
-            if len(reg.seq) != want:
-                raise ValueError('region sequence must span [start - fm_offset - K + 1, '
-                                 'end + fm_offset + K - 1) (%d bases, got %d)' % (want, len(reg.seq)))
-            b_lag, e_lag = (cp, dn) if reg.strand == '+' else (dn, cp)
-            seq = reg.seq[K - 1 - b_lag:len(reg.seq) - (K - 1 - e_lag)]
-            if reg.strand == '-':
-                seq = th.rev_comp(seq)
-            m, s = std_ref.get_exp_levels_from_seq_with_gaps(seq, reg.strand == '-')
-            pm.append(m)
-            ps.append(s)
-        prior_m = np.ascontiguousarray(np.concatenate(pm), dtype=np.float64)
-        prior_s = np.ascontiguousarray(np.concatenate(ps), dtype=np.float64)
-    lm, ls = np.empty(n_pos), np.empty(n_pos)
-    cov = np.empty(n_pos, dtype=np.int64)
-    eng = rq.get_engine() if engine is None else engine
-    pd, pi, pb = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int8)
-    P = lambda a, t: None if a is None else a.ctypes.data_as(t)
-    eng._check(eng._L.tba_reads_ref_levels(
-        eng._h, C.c_int(int(bool(est_mean))), C.c_int64(fm_offset), C.c_int64(min_test_reads),
-        C.c_int64(len(regions)), P(d['reg_start'], pi), P(d['reg_end'], pi), P(d['reg_strand'], pb),
-        P(d['reg_read_off'], pi), C.c_int64(d['read_start'].shape[0]), P(d['read_start'], pi),
-        P(d['read_strand'], pb), P(d['read_off'], pi), P(d['means'], pd), P(prior_m, pd),
-        P(prior_s, pd), C.c_double(w_m), C.c_double(w_s), P(lm, pd), P(ls, pd), P(cov, pi)),
-        'tba_reads_ref_levels')
+        prior_m, prior_s = _prior_levels(regions, fm_offset, std_ref)
+    lm, ls, cov = _engine(engine).reads_ref_levels(est_mean, fm_offset, min_test_reads, pileup, prior_m,
+                                                   prior_s, w_m, w_s)
     out = []
-    for r, reg in enumerate(regions):
-        a, b = int(d['pos_off'][r]), int(d['pos_off'][r + 1])
+    for reg, a, b in zip(regions, pileup.pos_off[:-1].tolist(), pileup.pos_off[1:].tolist()):
         if not (cov[a:b] >= min_test_reads).any():   # no covered position: no blend, no dict
             out.append((np.full(b - a, np.nan), np.full(b - a, np.nan), {}))
             continue
@@ -710,76 +679,15 @@ def get_reads_ref(reg_data, min_test_reads, fm_offset, std_ref=None, prior_weigh
 # with collate_reg_stats (:4124-4178), apply_per_read_thresh (:4084-4122) and calc_damp_fraction
 # (:2537-2552).  The reference concatenates, argsorts, splits and thresholds the per-read
 # statistics of one region in numpy; here a list of regions is one engine call
-# (`tba_site_fractions`, kernels in csrc/k_site.h): the per-read statistics are computed on the
-# device and only the per-site records come back.  A track is one (region, statistic name).
+# (`Engine.site_fractions_z` / `Engine.site_fractions_windows`, kernels in csrc/k_site.h): the
+# per-read statistics are computed on the device and only the per-site records come back.  A
+# track is one (region, statistic name).
 def _damp_pair(cov_damp_counts):
     if cov_damp_counts is None:
         return None
-    if isinstance(cov_damp_counts, dict):
-        return float(cov_damp_counts['unmod']), float(cov_damp_counts['mod'])
-    unmod, mod = cov_damp_counts
+    cd = cov_damp_counts
+    unmod, mod = (cd['unmod'], cd['mod']) if isinstance(cd, dict) else cd
     return float(unmod), float(mod)
-
-
-def _site_fractions(form, trk_start, trk_end, single_read_thresh, lower_thresh, cov_damp_counts,
-                    return_per_read, engine, z=None, win=None):
-    """one `tba_site_fractions` call -> dict of the flat outputs (compacted per track at pos_off)"""
-    import ctypes as C
-    from . import resquiggle as rq
-    i64a = lambda v: np.ascontiguousarray(v, dtype=np.int64)
-    f64a = lambda v: np.ascontiguousarray(v, dtype=np.float64)
-    trk_start, trk_end = i64a(trk_start), i64a(trk_end)
-    n_trk = trk_start.shape[0]
-    pos_off = np.concatenate([[0], np.cumsum(trk_end - trk_start)]).astype(np.int64)
-    n_pos = int(pos_off[-1])
-    pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int64)
-    P = lambda a, t: None if a is None else a.ctypes.data_as(t)
-    frac = np.empty(n_pos)
-    poss, cov, valid = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
-    counts, n_stats = np.empty(n_trk, dtype=np.int64), np.empty(n_trk, dtype=np.int64)
-    damp_pair = _damp_pair(cov_damp_counts)
-    damp = np.empty(n_pos) if damp_pair is not None else None
-    damp_c = None if damp_pair is None else (C.c_double * 2)(*damp_pair)
-    lower_c = None if lower_thresh is None else (C.c_double * 1)(float(lower_thresh))
-    nul_d, nul_i = C.cast(None, pd), C.cast(None, pi)
-    if form == 0:
-        means, ref_m, ref_s = (f64a(z[k]) for k in ('means', 'ref_means', 'ref_sds'))
-        off, r_trk, r_pos = (i64a(z[k]) for k in ('off', 'read_track', 'read_pos'))
-        if not (means.shape[0] == ref_m.shape[0] == ref_s.shape[0] == int(off[-1])) or \
-                not (off.shape[0] - 1 == r_trk.shape[0] == r_pos.shape[0]):
-            raise ValueError('per-base arrays, offsets and per-read arrays disagree')
-        per_read = np.empty(means.shape[0]) if return_per_read else None
-        z_args = (P(means, pd), P(ref_m, pd), P(ref_s, pd), P(off, pi), C.c_int64(r_trk.shape[0]),
-                  P(r_trk, pi), P(r_pos, pi), C.c_int64(int(z['fm_offset'])),
-                  C.c_int(int(z['floor_out'])), C.c_double(SMALLEST_PVAL))
-        w_args = (C.c_int(0), nul_d, nul_d, nul_d, C.c_int64(0), C.c_int64(0), nul_i, C.c_int64(0),
-                  nul_d, nul_i, nul_i)
-    else:
-        means, ref_m, alt_m, ref_v = (f64a(win[k]) for k in ('means', 'ref_means', 'alt_means', 'ref_vars'))
-        alt_v = None if win.get('alt_vars') is None else f64a(win['alt_vars'])
-        starts, w_trk, w_pos = (i64a(win[k]) for k in ('starts', 'win_track', 'win_pos'))
-        n = means.shape[0]
-        if not (ref_m.shape[0] == alt_m.shape[0] == ref_v.shape[0] == n) or \
-                (alt_v is not None and alt_v.shape[0] != n) or \
-                not (starts.shape[0] == w_trk.shape[0] == w_pos.shape[0]):
-            raise ValueError('window arrays disagree')
-        per_read = np.empty(starts.shape[0]) if return_per_read else None
-        par = (C.c_double * 3)(OCLLHR_SCALE, OCLLHR_HEIGHT, OCLLHR_POWER)
-        z_args = (P(means, pd), P(ref_m, pd), nul_d, nul_i, C.c_int64(0), nul_i, nul_i, C.c_int64(0),
-                  C.c_int(0), C.c_double(SMALLEST_PVAL))
-        w_args = (C.c_int(int(win['kind'])), P(alt_m, pd), P(ref_v, pd), P(alt_v, pd), C.c_int64(n),
-                  C.c_int64(int(win['width'])), P(starts, pi), C.c_int64(starts.shape[0]), par,
-                  P(w_trk, pi), P(w_pos, pi))
-    eng = rq.get_engine() if engine is None else engine
-    eng._check(eng._L.tba_site_fractions(
-        eng._h, C.c_int(form), C.c_int64(n_trk), P(trk_start, pi), P(trk_end, pi), *z_args, *w_args,
-        C.c_double(float(single_read_thresh)), lower_c, damp_c, P(frac, pd), P(poss, pi), P(cov, pi),
-        P(valid, pi), P(damp, pd), P(counts, pi), P(n_stats, pi), P(per_read, pd)),
-        'tba_site_fractions')
-    return dict(pos_off=pos_off, frac=frac, poss=poss, cov=cov, valid=valid, damp=damp,
-                counts=counts, n_stats=n_stats, per_read=per_read,
-                bytes_back=sum(a.nbytes for a in (frac, poss, cov, valid, damp, counts, n_stats, per_read)
-                               if a is not None))
 
 
 def _check_reg_stats_args(regions, fm_offset, min_test_reads, ctrl_regions, std_ref, alt_refs,
@@ -787,42 +695,63 @@ def _check_reg_stats_args(regions, fm_offset, min_test_reads, ctrl_regions, std_
     if stat_type not in (SAMP_COMP_TXT, DE_NOVO_TXT, ALT_MODEL_TXT):
         raise NotImplementedError('Unrecognized test type.')
     _check_group_args(fm_offset, min_test_reads)
-    if stat_type == SAMP_COMP_TXT:
-        if ctrl_regions is None or len(ctrl_regions) != len(regions):
-            raise ValueError('one control region per sample region')
-        for reg, ctrl in zip(regions, ctrl_regions):
-            if (reg.start, reg.end) != (ctrl.start, ctrl.end):
-                raise ValueError('sample and control regions must have the same coordinates')
-    elif std_ref is None:
+    _check_regions(regions, ctrl_regions, paired=stat_type == SAMP_COMP_TXT)
+    if stat_type != SAMP_COMP_TXT and std_ref is None:
         raise ValueError('%s needs the canonical model (std_ref)' % stat_type)
     if stat_type == ALT_MODEL_TXT and not alt_refs:
         raise ValueError('%s needs alternate models (alt_refs)' % stat_type)
-    for reg in regions:
-        if reg.end <= reg.start:
-            raise ValueError('region end must be greater than its start')
 
 
 def _read_id_str(rid):
     return rid.decode() if isinstance(rid, bytes) else rid
 
 
-def _per_read_block(poss, stats, ids):
-    """the per-read block of collate_reg_stats (:4136-4154): (pos, stat, read_id) records and the
-    read-id lookup; ids are numbered in order of first appearance (the reference numbers them by
-    iterating a set, so only the mapping back to the strings is defined)"""
-    lookup = {}
-    conv = np.array([lookup.setdefault(r, len(lookup)) for r in ids], dtype=np.uint32)
-    block = np.empty(poss.shape[0], dtype=[('pos', 'u4'), ('stat', 'f8'), ('read_id', 'u4')])
-    block['pos'], block['stat'], block['read_id'] = poss, stats, conv
-    return block, lookup
+def _widen_tracks(trk_start, trk_end, trk, first, end):
+    if trk.shape[0]:   # (widened to the statistics that reach further out than their region)
+        np.minimum.at(trk_start, trk, first)
+        np.maximum.at(trk_end, trk, end)
+
+
+class _ZInputs(namedtuple('_ZInputs', 'means ref_means ref_sds off read_track read_pos read_ids n_ok '
+                                      'fm_offset floor_out trk_start trk_end')):
+    """flat inputs of the z form, one track per region: the arrays `read_pvals` takes plus per read its
+    track, first position and id; n_ok: per region the number of reads that did not fail"""
+
+    def site_fractions(self, eng, *thresholds):
+        return eng.site_fractions_z(self.trk_start, self.trk_end, self.means, self.ref_means, self.ref_sds,
+                                    self.off, self.read_track, self.read_pos, self.fm_offset, self.floor_out,
+                                    SMALLEST_PVAL, *thresholds)
+
+    def __getitem__(self, key):   # (fields by name too, as in the dict this bundle replaced)
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+    def stat_index(self):
+        """per statistic: its track, its position, the index of its read in the ids; the ids"""
+        lens = np.diff(self.off)
+        return (np.repeat(self.read_track, lens),
+                np.repeat(self.read_pos - self.off[:-1], lens) + np.arange(self.off[-1]),
+                np.repeat(np.arange(lens.shape[0]), lens), self.read_ids)
+
+
+class _WinInputs(namedtuple('_WinInputs', 'kind means ref_means alt_means ref_vars alt_vars width starts '
+                                          'win_track win_pos win_ids n_ok trk_start trk_end')):
+    """flat inputs of the window form (alternate models): the arrays `llh_ratio_windows` takes plus
+    per window its track (region * number of models + model), position and read id"""
+
+    def site_fractions(self, eng, *thresholds):
+        return eng.site_fractions_windows(
+            self.trk_start, self.trk_end, self.kind, self.means, self.ref_means, self.alt_means, self.ref_vars,
+            self.alt_vars, self.starts, self.width, self.win_track, self.win_pos,
+            (OCLLHR_SCALE, OCLLHR_HEIGHT, OCLLHR_POWER), *thresholds)
+
+    def stat_index(self):
+        return self.win_track, self.win_pos, np.arange(self.win_pos.shape[0]), self.win_ids
 
 
 def _reg_stats_z_inputs(regions, fm_offset, std_ref, stat_type, ctrl_levels=None):
-    """flat inputs of the z form for a list of regions (one track per region): the arrays
-    `tba_read_pvals` takes plus per read its track, first position and id, and per region the
-    number of reads that did not fail.  ctrl_levels[r]: (ctrl_means, ctrl_sds) or None (region
+    """the _ZInputs of a list of regions.  ctrl_levels[r]: (ctrl_means, ctrl_sds) or None (region
     already failed)."""
-    means, ref_m, ref_s, lens, r_trk, r_pos, r_ids = [], [], [], [], [], [], []
+    cols, r_trk, r_pos, r_ids = ([], [], []), [], [], []
     n_ok = [0] * len(regions)
     for t, reg in enumerate(regions):
         if ctrl_levels is not None and ctrl_levels[t] is None:
@@ -830,32 +759,27 @@ def _reg_stats_z_inputs(regions, fm_offset, std_ref, stat_type, ctrl_levels=None
         for rd in (reg.reads or ()):
             try:
                 if stat_type == DE_NOVO_TXT:
-                    m, a, b, rs, _ = _prep_de_novo_read(rd, std_ref, fm_offset, reg)
+                    prep = _prep_de_novo_read(rd, std_ref, fm_offset, reg)
                 else:
-                    m, a, b, rs = _prep_sample_compare_read(
-                        rd, ctrl_levels[t][0], ctrl_levels[t][1], fm_offset, reg)
+                    prep = _prep_sample_compare_read(rd, *ctrl_levels[t], fm_offset, reg)
             except th.TomboError:
                 continue   # compute_reg_stats :4210-4211
-            means.append(m); ref_m.append(a); ref_s.append(b)
-            lens.append(m.shape[0]); r_trk.append(t); r_pos.append(rs); r_ids.append(rd.read_id)
+            for c, x in zip(cols, prep):
+                c.append(x)
+            r_trk.append(t); r_pos.append(prep[3]); r_ids.append(rd.read_id)
             n_ok[t] += 1
-    cat = lambda v: np.ascontiguousarray(np.concatenate(v) if v else np.empty(0), dtype=np.float64)
-    off = np.concatenate([[0], np.cumsum(lens, dtype=np.int64)]).astype(np.int64)
+    off = _csr_offsets([m.shape[0] for m in cols[0]])
     r_trk, r_pos = np.array(r_trk, dtype=np.int64), np.array(r_pos, dtype=np.int64)
-    # a track spans the region extended by fm_offset, widened to its reads where they reach further
+    # a track spans the region extended by fm_offset
     trk_start = np.array([reg.start - fm_offset for reg in regions], dtype=np.int64)
     trk_end = np.array([reg.end + fm_offset for reg in regions], dtype=np.int64)
-    if r_trk.shape[0]:
-        np.minimum.at(trk_start, r_trk, r_pos)
-        np.maximum.at(trk_end, r_trk, r_pos + np.diff(off))
-    return dict(means=cat(means), ref_means=cat(ref_m), ref_sds=cat(ref_s), off=off,
-                read_track=r_trk, read_pos=r_pos, read_ids=r_ids, n_ok=n_ok, fm_offset=int(fm_offset),
-                floor_out=stat_type == DE_NOVO_TXT, trk_start=trk_start, trk_end=trk_end)
+    _widen_tracks(trk_start, trk_end, r_trk, r_pos, r_pos + np.diff(off))
+    return _ZInputs(*(_concat_f64(c) for c in cols), off, r_trk, r_pos, r_ids, n_ok, int(fm_offset),
+                    stat_type == DE_NOVO_TXT, trk_start, trk_end)
 
 
 def _reg_stats_win_inputs(regions, std_ref, alt_refs, use_standard_llhr):
-    """flat inputs of the window form: one track per (region, alternate model), track index
-    region * len(alt_refs) + model"""
+    """the _WinInputs of a list of regions"""
     K, n_alt = std_ref.kmer_width, len(alt_refs)
     max_bb, max_ab = _alt_motif_bounds(alt_refs)
     cols = [[] for _ in range(5)]
@@ -873,18 +797,81 @@ def _reg_stats_win_inputs(regions, std_ref, alt_refs, use_standard_llhr):
                     for c, x in zip(cols, w):
                         c.append(x)
                     w_trk.append(r * n_alt + k); w_pos.append(int(p)); w_ids.append(rd.read_id)
-    cat = lambda v: np.ascontiguousarray(np.concatenate(v) if v else np.empty(0), dtype=np.float64)
     w_trk, w_pos = np.array(w_trk, dtype=np.int64), np.array(w_pos, dtype=np.int64)
     trk_start = np.repeat(np.array([reg.start for reg in regions], dtype=np.int64), n_alt)
     trk_end = np.repeat(np.array([reg.end for reg in regions], dtype=np.int64), n_alt)
-    if w_trk.shape[0]:
-        np.minimum.at(trk_start, w_trk, w_pos)
-        np.maximum.at(trk_end, w_trk, w_pos + 1)
+    _widen_tracks(trk_start, trk_end, w_trk, w_pos, w_pos + 1)
     kind = _llh_kind(use_standard_llhr)
-    return dict(kind=kind, means=cat(cols[0]), ref_means=cat(cols[1]), alt_means=cat(cols[2]),
-                ref_vars=cat(cols[3]), alt_vars=cat(cols[4]) if kind == 0 else None, width=K,
-                starts=np.arange(w_trk.shape[0], dtype=np.int64) * K, win_track=w_trk, win_pos=w_pos,
-                win_ids=w_ids, n_ok=n_ok, trk_start=trk_start, trk_end=trk_end)
+    return _WinInputs(kind, *(_concat_f64(c) for c in cols[:4]), _concat_f64(cols[4]) if kind == 0 else None,
+                      K, np.arange(w_trk.shape[0], dtype=np.int64) * K, w_trk, w_pos, w_ids, n_ok,
+                      trk_start, trk_end)
+
+
+def _ctrl_levels(ctrl_regions, min_test_reads, fm_offset, std_ref, prior_weights, engine):
+    """sample_compare: per region the control levels (means, sds) and coverage dict of one
+    `get_reads_ref_batch` call, or the TomboError of a control region without reads"""
+    levels, ctrl_cov = [None] * len(ctrl_regions), [None] * len(ctrl_regions)
+    failed = [th.TomboError(_NO_READS_MSG) if ctrl.reads is None or len(ctrl.reads) == 0 else None
+              for ctrl in ctrl_regions]   # get_base_levels of get_reads_ref
+    have = [r for r, e in enumerate(failed) if e is None]
+    if have:
+        refs = get_reads_ref_batch([ctrl_regions[r] for r in have], min_test_reads, fm_offset,
+                                   std_ref, prior_weights, engine=engine)
+        for r, (lm, ls, cov) in zip(have, refs):
+            levels[r], ctrl_cov[r] = (lm, ls), cov
+    return levels, ctrl_cov, failed
+
+
+def _reported_tracks(n_stats, r, n_names):
+    """the tracks of region r up to and including its first one without statistics: there the
+    reference's loop over the names ends, after that name's per-read block went out"""
+    trks = list(range(r * n_names, (r + 1) * n_names))
+    empty = [t for t in trks if n_stats[t] == 0]
+    return trks[:trks.index(empty[0]) + 1] if empty else trks
+
+
+def _per_read_blocks(inp, res, regions, names, failed):
+    """per region the (name, (block, read_id_lookup, chrm, strand, start)) items of its reported
+    tracks; a block is the per-read block of collate_reg_stats (:4136-4154): (pos, stat, read_id)
+    records, the ids numbered in order of first appearance (the reference numbers them by iterating
+    a set, so only the lookup back to the strings is defined)"""
+    s_trk, s_pos, s_rd, ids = inp.stat_index()
+    ok = ~np.isnan(res.per_read)
+    out = [[] for _ in regions]
+    for r, reg in enumerate(regions):
+        for t in ([] if failed[r] is not None else _reported_tracks(res.n_stats, r, len(names))):
+            sel = np.flatnonzero(ok & (s_trk == t))
+            lookup = {}
+            block = np.empty(sel.shape[0], dtype=[('pos', 'u4'), ('stat', 'f8'), ('read_id', 'u4')])
+            block['pos'], block['stat'] = s_pos[sel], res.per_read[sel]
+            block['read_id'] = [lookup.setdefault(_read_id_str(ids[q]), len(lookup)) for q in s_rd[sel]]
+            out[r].append((names[t % len(names)], (block, lookup, reg.chrm, reg.strand, reg.start)))
+    return out
+
+
+def _region_stats(reg, r, names, res, ctrl_cov):
+    """[(name, th.regionStats), ...] of region r from the flat outputs, or its TomboError.
+    ctrl_cov: the control coverage dict (sample_compare) or None"""
+    out = []
+    for t in _reported_tracks(res.n_stats, r, len(names)):
+        if res.n_stats[t] == 0:
+            # (for model_compare the reference's list comprehension fails the whole region)
+            return th.TomboError('No valid positions in this region.')
+        a = int(res.pos_off[t])
+        b = a + int(res.counts[t])
+        poss, cov = res.poss[a:b].copy(), res.cov[a:b].copy()
+        if ctrl_cov is None:
+            cc_list = [0] * int(cov.sum())
+        else:
+            # one entry per statistic in sorted-position order (apply_per_read_thresh iterates
+            # stat_locs, not the unique positions)
+            cc_list = np.repeat(np.array([ctrl_cov.get(int(p), 0) for p in poss], dtype=np.int64), cov).tolist()
+        rs = th.regionStats(res.frac[a:b].copy(), poss, reg.chrm, reg.strand, reg.start, cov, cc_list,
+                            res.valid[a:b].copy())
+        if res.damp is not None:
+            rs.damp_frac = res.damp[a:b].copy()
+        out.append((names[t % len(names)], rs))
+    return out
 
 
 def compute_reg_stats_batch(regions, fm_offset, min_test_reads, single_read_thresh, lower_thresh,
@@ -899,85 +886,28 @@ def compute_reg_stats_batch(regions, fm_offset, min_test_reads, single_read_thre
     start)) as the reference puts them on its per_read_q."""
     _check_reg_stats_args(regions, fm_offset, min_test_reads, ctrl_regions, std_ref, alt_refs,
                           stat_type)
-    if len(regions) == 0:
-        return ([], []) if return_per_read else []
     fm_offset, min_test_reads = int(fm_offset), int(min_test_reads)
-    n_reg = len(regions)
-    out = [None] * n_reg
-    ctrl_cov = [None] * n_reg
+    failed = ctrl_cov = [None] * len(regions)
+    names = [stat_type]
     if stat_type == SAMP_COMP_TXT:
-        levels = [None] * n_reg
-        have = []
-        for r, ctrl in enumerate(ctrl_regions):
-            if ctrl.reads is None or len(ctrl.reads) == 0:   # get_base_levels of get_reads_ref
-                out[r] = th.TomboError('Must annotate region with reads (see '
-                                       '`TomboInterval.add_reads`) to extract base levels.')
-            else:
-                have.append(r)
-        if have:
-            refs = get_reads_ref_batch([ctrl_regions[r] for r in have], min_test_reads, fm_offset,
-                                       std_ref, prior_weights, engine=engine)
-            for r, (lm, ls, cov) in zip(have, refs):
-                levels[r], ctrl_cov[r] = (lm, ls), cov
+        levels, ctrl_cov, failed = _ctrl_levels(ctrl_regions, min_test_reads, fm_offset, std_ref,
+                                                prior_weights, engine)
         inp = _reg_stats_z_inputs(regions, fm_offset, None, stat_type, levels)
     elif stat_type == DE_NOVO_TXT:
         inp = _reg_stats_z_inputs(regions, fm_offset, std_ref, stat_type)
     else:
         inp = _reg_stats_win_inputs(regions, std_ref, alt_refs, use_standard_llhr)
-    form = 1 if stat_type == ALT_MODEL_TXT else 0
-    if not any(inp['n_ok']):   # nothing to compute: no engine call
-        no_stats = [e if e is not None else th.TomboError('Reads contains no statistics in this region.')
-                    for e in out]
-        return (no_stats, [[] for _ in range(n_reg)]) if return_per_read else no_stats
-    res = _site_fractions(form, inp['trk_start'], inp['trk_end'], single_read_thresh, lower_thresh,
-                          cov_damp_counts, return_per_read, engine,
-                          z=inp if form == 0 else None, win=inp if form == 1 else None)
-    names = [stat_type] if form == 0 else [n for n, _ in alt_refs]
-    per_read = [[] for _ in range(n_reg)]
-    if return_per_read:
-        pr = res['per_read']
-        if form == 0:
-            lens = np.diff(inp['off'])
-            s_trk = np.repeat(inp['read_track'], lens)
-            s_pos = np.repeat(inp['read_pos'] - inp['off'][:-1], lens) + np.arange(pr.shape[0])
-            s_rd = np.repeat(np.arange(lens.shape[0]), lens)
-            ids = inp['read_ids']
-        else:
-            s_trk, s_pos, s_rd, ids = inp['win_track'], inp['win_pos'], np.arange(pr.shape[0]), inp['win_ids']
-        ok = ~np.isnan(pr)
-    for r, reg in enumerate(regions):
-        if out[r] is not None:
-            continue
-        if inp['n_ok'][r] == 0:
-            out[r] = th.TomboError('Reads contains no statistics in this region.')
-            continue
-        reg_out = []
-        for k, name in enumerate(names):
-            t = r * len(names) + k
-            if return_per_read:
-                sel = np.flatnonzero(ok & (s_trk == t))
-                block, lookup = _per_read_block(s_pos[sel], pr[sel], [_read_id_str(ids[q]) for q in s_rd[sel]])
-                per_read[r].append((name, (block, lookup, reg.chrm, reg.strand, reg.start)))
-            if res['n_stats'][t] == 0:
-                # (for model_compare the reference's list comprehension fails the whole region)
-                reg_out = th.TomboError('No valid positions in this region.')
-                break
-            a = int(res['pos_off'][t])
-            b = a + int(res['counts'][t])
-            poss, cov = res['poss'][a:b].copy(), res['cov'][a:b].copy()
-            if stat_type == SAMP_COMP_TXT:
-                # one entry per statistic in sorted-position order (apply_per_read_thresh iterates
-                # stat_locs, not the unique positions)
-                cc = ctrl_cov[r] or {}
-                cc_list = np.repeat(np.array([cc.get(int(p), 0) for p in poss], dtype=np.int64), cov).tolist()
-            else:
-                cc_list = [0] * int(cov.sum())
-            rs = th.regionStats(res['frac'][a:b].copy(), poss, reg.chrm, reg.strand, reg.start, cov,
-                                cc_list, res['valid'][a:b].copy())
-            if res['damp'] is not None:
-                rs.damp_frac = res['damp'][a:b].copy()
-            reg_out.append((name, rs))
-        out[r] = reg_out
+        names = [n for n, _ in alt_refs]
+    failed = [e if e is not None or n else th.TomboError('Reads contains no statistics in this region.')
+              for e, n in zip(failed, inp.n_ok)]
+    out, per_read = failed, [[] for _ in regions]
+    if any(inp.n_ok):   # (else nothing to compute: no engine call)
+        res = inp.site_fractions(_engine(engine), single_read_thresh, lower_thresh, _damp_pair(cov_damp_counts),
+                                 return_per_read)
+        out = [e if e is not None else _region_stats(reg, r, names, res, ctrl_cov[r] if stat_type == SAMP_COMP_TXT else None)
+               for r, (reg, e) in enumerate(zip(regions, failed))]
+        if return_per_read:
+            per_read = _per_read_blocks(inp, res, regions, names, failed)
     return (out, per_read) if return_per_read else out
 
 
@@ -994,9 +924,7 @@ def compute_reg_stats(reg_data, fm_offset, min_test_reads, single_read_thresh, l
         res, per_read = res
         for item in per_read[0]:
             per_read_q.put(item)
-    if isinstance(res[0], Exception):
-        raise res[0]
-    return res[0]
+    return _only(res)
 
 
 def calc_damp_fraction(cov_damp_counts, fracs, valid_cov):

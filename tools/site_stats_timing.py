@@ -4,7 +4,7 @@
 
 On the seeded de_novo batch of tests/site_stats_reference.py (64 regions x 10 000 positions x 50
 reads), after a warm-up of each route, five rounds alternating in ONE process:
-  (a) parent route: `tba_read_pvals` through `_read_pvals`, every per-read p-value copied back, then
+  (a) parent route: `tba_read_pvals` through `Engine.read_pvals`, every per-read p-value copied back, then
       the numpy collation of tests/site_stats_reference.py region by region;
   (b) `compute_reg_stats_batch` without the per-read output.
 Both routes run the same host preparation (`_reg_stats_z_inputs`) inside the timed span.  Host clock
@@ -21,6 +21,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 from tombo_amd import tombo_stats as ts, tombo_helper as th, resquiggle as rq  # noqa: E402
+from tombo_amd._default_parameters import SMALLEST_PVAL  # noqa: E402
 import site_stats_reference as ssr  # noqa: E402
 
 FM, SINGLE, LOWER = 1, 0.5, 0.15
@@ -28,10 +29,10 @@ FM, SINGLE, LOWER = 1, 0.5, 0.15
 
 def route_parent(regions, model):
     inp = ts._reg_stats_z_inputs(regions, FM, model, ts.DE_NOVO_TXT)
-    pv = ts._read_pvals(inp['means'], inp['ref_means'], inp['ref_sds'], inp['off'], FM, True)
-    lens = np.diff(inp['off'])
-    locs = np.repeat(inp['read_pos'] - inp['off'][:-1], lens) + np.arange(pv.shape[0])
-    trk = np.repeat(inp['read_track'], lens)
+    pv = rq.get_engine().read_pvals(inp.means, inp.ref_means, inp.ref_sds, inp.off, FM, True, SMALLEST_PVAL)
+    lens = np.diff(inp.off)
+    locs = np.repeat(inp.read_pos - inp.off[:-1], lens) + np.arange(pv.shape[0])
+    trk = np.repeat(inp.read_track, lens)
     bounds = np.concatenate([[0], np.flatnonzero(np.diff(trk)) + 1, [trk.shape[0]]])
     out = [ssr.collate(pv[bounds[r]:bounds[r + 1]], locs[bounds[r]:bounds[r + 1]], SINGLE, LOWER, False)
            for r in range(len(regions))]
