@@ -164,6 +164,9 @@ int  tba_engine_get_dispatch(tba_engine *e, int64_t *small_batch_reads, int64_t 
  * other; 0: never; 1: always.  tba_engine_last_side_stream: whether the last full run used it. */
 int  tba_engine_set_side_stream(tba_engine *e, int mode);
 int  tba_engine_last_side_stream(tba_engine *e);
+/* whether the last run launched k_dp8_lowreg, the register-capped build of the 8-cell forward pass, in place of
+ * k_dp<8> (the choice tba_engine_set_sharing describes; per read: TBA_GET_DP_FORM) */
+int  tba_engine_last_dp_lowreg(tba_engine *e);
 /* TBA_ED_FORM_* of the last tba_c_valid_cpts_w_cap / tba_c_valid_cpts_w_cap_t_test call on this engine
  * (those entries follow the engine's dispatch like a batch of one read) */
 int  tba_c_last_ed_form(tba_engine *e);
@@ -299,6 +302,12 @@ enum {
                                * by the lane-per-read kernel, so its result is the serial walk's either way.  Zero for
                                * every read is the expected state: a binding should treat anything else as a fault of
                                * the machine or the build worth reporting (ABI 9) */
+    TBA_GET_DP_FORM = 32,     /* int32[n][4]: the forward-pass kernels that took the read (ABI 11): TBA_DP_FORM_* of the
+                               * main pass, its cells-per-lane class (0: wide, none), TBA_DP_START_* of start discovery,
+                               * the class of the retry kernel (0: no retry).  DERIVED on the host, not written by the
+                               * kernels: the launch decisions the engine recorded when it enqueued the run, and per read
+                               * the predicates by which the kernels select their reads (k_dp.h, k_dp_multi.h, k_dp_wg.h)
+                               * over the state the run left (TBA_GET_PATH, TBA_GET_START_FAIL, start state) */
     TBA_GET_DEBUG_COUNTERS = 99 /* int64[n][8]: ReadState.dbg, only filled by -DTBA_PHASE_DEBUG /
                                    -DTBA_SWEEP_STATS profiling builds (zeros otherwise) */
 };
@@ -317,6 +326,19 @@ enum {
     TBA_TB_FORM_LONG = 2,           /* k_main_tb_long */
     TBA_TB_FORM_PAR16 = 16,         /* k_main_tb_par<16>: throughput form */
     TBA_TB_FORM_PAR64 = 64          /* k_main_tb_par<64>: latency form, and the long reads of any batch */
+};
+enum {                              /* TBA_GET_DP_FORM column 0 */
+    TBA_DP_FORM_NONE = 0,           /* no main forward pass: the read had failed before */
+    TBA_DP_FORM_K_DP = 1,           /* k_dp<CPL>: a wavefront per read */
+    TBA_DP_FORM_K_DP8_LOWREG = 2,   /* k_dp8_lowreg: the 8-cell class under 112 registers (tba_engine_set_sharing) */
+    TBA_DP_FORM_MULTI = 3,          /* k_dp_multi: narrow adaptive bands, several reads per wavefront */
+    TBA_DP_FORM_WIDE = 4            /* k_dp_wide: a static band wider than every class */
+};
+enum {                              /* TBA_GET_DP_FORM column 2 */
+    TBA_DP_START_NONE = 0,          /* no start discovery: static whole-read assignment (short read), or failed before */
+    TBA_DP_START_FIRST_TRY = 1,     /* the first try (k_dp<class of start_bw>) only */
+    TBA_DP_START_RETRY_WG = 2,      /* ... and the retry over start_save_bw by k_dp_wg<CPL>: a workgroup per read */
+    TBA_DP_START_RETRY_K_DP = 3     /* ... and the retry by k_dp<CPL> (start_n_bases beyond k_dp_wg's rows) */
 };
 int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_bytes);
 /* ---- stepwise execution (the reference's public per-stage API, resquiggle.py:63-67) ---------
@@ -595,7 +617,7 @@ int tba_synth_dwell_thresholds(const tba_synth_params *p, uint32_t *thr, int64_t
 /* out[0..2] = sizeof(tba_params), sizeof(tba_opts), sizeof(tba_read_result) of this build, out[3]
  * (n >= 4) = TBA_ABI_VERSION: lets a binding without a C compiler (ctypes) check its struct mirrors
  * and refuse a stale build of the library */
-#define TBA_ABI_VERSION 10
+#define TBA_ABI_VERSION 11
 int tba_abi_sizes(int64_t *out, int64_t n);
 
 /* self-test: out[t] = index t of the subsample tba_opts.device_subsample draws for read

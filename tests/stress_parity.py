@@ -11,6 +11,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))  # (this directory)
 import oracle  # noqa: E402  (checker)
 from tombo_amd import synth, tombo_stats as ts, tombo_helper as th  # noqa: E402
 from test_gpu_parity import run_batch, compare_batch  # noqa: E402
+from test_gpu_dp_forms import RETRY_SETS  # noqa: E402  (every retry kernel: the table the suite runs, with more reads)
 
 
 def retry_heavy():
@@ -18,7 +19,7 @@ def retry_heavy():
     samp = th.seqSampleType('DNA', False)
     model = ts.TomboModel(seq_samp_type=samp)
     rng = np.random.default_rng(1)
-    for save_bw, start_bw, nbases in ((2500, 750, 250), (900, 300, 120), (1800, 500, 200), (3000, 1000, 250), (640, 200, 60)):
+    for save_bw, start_bw, nbases in [row[:3] for row in RETRY_SETS]:
         aln = (4.2, 4.2, 300, 1500, 20.0, 40, start_bw, save_bw, nbases)
         params = ts.load_resquiggle_parameters(samp, aln)
         reads = []

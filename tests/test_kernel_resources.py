@@ -16,6 +16,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 BUDGET = {
     '_Z4k_dpILi8ELb0EE': (128, False),        # W = 500: 4 wavefronts per SIMD
     '_Z4k_dpILi5ELb0EE': (96, False),         # W = 300: 5
+    '_Z12k_dp8_lowreg': (112, True),          # W = 500 beside another engine's kernels: spills four registers by design
     '_Z11k_normalizeIdE': (128, False),       # 2 workgroups of 512 per CU
     '_Z11k_normalizeIsE': (128, False),
     '_Z7k_peaksILi2EE': (80, False),          # 3 workgroups per CU

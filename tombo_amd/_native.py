@@ -97,18 +97,22 @@ GET_VALID_CPTS, GET_N_CPTS, GET_EVENT_MEANS, GET_SEG_NORM, GET_SEG_SV, GET_START
     GET_BAND_STARTS, GET_READ_TB, GET_DP_SEGS, GET_THEIL_SEN, GET_PATH, GET_LAST_ROW, \
     GET_DP_READ_START, GET_KERNEL_MS, GET_REF_MEANS, GET_REF_SDS, GET_SEGS, GET_STATUS, GET_START_FAIL, \
     GET_STALL_INTS, GET_N_STALL, GET_STALL_OFF, GET_SAMP_IND, GET_TB_PARALLEL, GET_ED_FUSED, GET_ED_TAKEN_POS, GET_ED_N_TAKEN, \
-    GET_DP_WORKGROUP, GET_ED_FORM, GET_TB_FORM, GET_TB_VERIFY_FAIL = range(1, 32)
+    GET_DP_WORKGROUP, GET_ED_FORM, GET_TB_FORM, GET_TB_VERIFY_FAIL, GET_DP_FORM = range(1, 33)
 # TBA_ED_FORM_* / TBA_TB_FORM_*: which kernels produced a read's change points / main traceback
 ED_FORM_NONE, ED_FORM_WG_SCAN_PEAKS, ED_FORM_DETECT_PICK, ED_FORM_SCORES_PEAKS, ED_FORM_DETECT_TT_PICK, \
     ED_FORM_TTEST_PEAKS = range(6)
 TB_FORM_NONE, TB_FORM_LANE, TB_FORM_LONG, TB_FORM_PAR16, TB_FORM_PAR64 = 0, 1, 2, 16, 64
+# TBA_GET_DP_FORM, int32[n][4]: (TBA_DP_FORM_* of the main forward pass, its cells-per-lane class, TBA_DP_START_* of
+# start discovery, class of the retry kernel); derived on the host from the run's launch decisions and per-read state
+DP_FORM_NONE, DP_FORM_K_DP, DP_FORM_K_DP8_LOWREG, DP_FORM_MULTI, DP_FORM_WIDE = range(5)
+DP_START_NONE, DP_START_FIRST_TRY, DP_START_RETRY_WG, DP_START_RETRY_K_DP = range(4)
 GET_DEBUG_COUNTERS = 99  # ReadState.dbg of a -DTBA_PHASE_DEBUG / -DTBA_SWEEP_STATS profiling build
 STAGE_SEGMENT, STAGE_EVENT_MEANS, STAGE_REF_LEVELS, STAGE_START, STAGE_ASSIGN, STAGE_SKIP, \
     STAGE_RESCALE = range(7)
 PUT_VALID_CPTS, PUT_EVENT_MEANS, PUT_NORM, PUT_REF_MEANS, PUT_REF_SDS, PUT_DP_SEGS, \
     PUT_START_STATE = range(1, 8)
 MAX_BAND = 3072
-ABI_VERSION = 10  # TBA_ABI_VERSION of include/tombo_amd.h
+ABI_VERSION = 11  # TBA_ABI_VERSION of include/tombo_amd.h
 STAGE_NAMES = ["normalize", "cumsum", "scores", "peaks", "event_means", "ref_levels",
                "start_dp", "start_tb", "prep", "main_dp", "main_tb", "skip_resolve", "theil_sen",
                "rescale_score", "stalls", "total"]
@@ -528,6 +532,10 @@ class Engine(object):
     def last_side_stream(self):
         return bool(self._L.tba_engine_last_side_stream(self._h))
 
+    def last_dp_lowreg(self):
+        """whether the last run launched k_dp8_lowreg in place of k_dp<8> (tba_engine_last_dp_lowreg)"""
+        return bool(self._L.tba_engine_last_dp_lowreg(self._h))
+
     def get_dispatch(self):
         a, b = i64(0), i64(0)
         self._check(self._L.tba_engine_get_dispatch(self._h, C.byref(a), C.byref(b)), 'tba_engine_get_dispatch')
@@ -594,7 +602,7 @@ class Engine(object):
         shapes = {
             GET_N_CPTS: (np.int64, n), GET_DP_READ_START: (np.int64, n),
             GET_SEG_SV: (np.float64, (n, 4)), GET_START: (np.float64, (n, 4)),
-            GET_THEIL_SEN: (np.float64, (n, 4)), GET_PATH: (np.int32, (n, 4)),
+            GET_THEIL_SEN: (np.float64, (n, 4)), GET_PATH: (np.int32, (n, 4)), GET_DP_FORM: (np.int32, (n, 4)),
             GET_LAST_ROW: (np.float64, (n, MAX_BAND)), GET_KERNEL_MS: (np.float32, 32),
             GET_DEBUG_COUNTERS: (np.int64, (n, 8)),
             GET_SEG_NORM: (np.float64, self.n_raw_total),

@@ -120,6 +120,12 @@ struct tba_engine {
     int n_sharing = 1;            // engines fed concurrently on this device (tba_engine_set_sharing)
     int side_mode = -1;           // tba_engine_set_side_stream: -1 by the engines alive, 0 never, 1 always
     bool last_side = false;       // the last full run used the side stream
+    // The forward-pass launches of the last run (TBA_GET_DP_FORM, tba_engine_last_dp_lowreg): a run from the first
+    // stage clears them, a stage that runs records its own.
+    struct DpLaunches {
+        bool start = false, main = false, lowreg = false, wide = false;
+        int retry_wcpl = 0;       // class of the retry's k_dp_wg; 0: k_dp<class of start_save_bw> in retry mode
+    } last_dp;
     // latency / throughput forms of event detection and traceback (tba_engine_set_dispatch)
     i64 small_batch = TBA_SMALL_BATCH, tb_wave_below = TBP_WAVE_BELOW;
     int last_c_ed_form = 0;       // tba_c_last_ed_form
@@ -626,8 +632,10 @@ static int enqueue_stages(tba_engine *e, int first, int last)
     ReadState *rs = e->d_rs.as<ReadState>();
     const DevParams *dp = e->d_dp.as<DevParams>();
     // starting from the top discards the state of a previous run of the same batch
-    if (first == 0)
+    if (first == 0) {
         HIP_TRY(hipMemcpyAsync(e->d_rs.p, e->h_rs.p, (size_t)n * sizeof(ReadState), hipMemcpyHostToDevice, s));
+        e->last_dp = tba_engine::DpLaunches();
+    }
     const unsigned nb = (unsigned)n;
     const unsigned tpr = (unsigned)((n + 63) / 64); // blocks for thread-per-read kernels
     // workgroups per read of the (blocks, reads) kernels: 256 items per workgroup when the batch is
@@ -763,6 +771,8 @@ static int enqueue_stages(tba_engine *e, int first, int last)
     if (ON(TBA_STAGE_START)) {
         // the retry of the few reads whose first try failed: one workgroup per read (k_dp_wg.h)
         const int wcpl = P.start_n_bases <= WG_MAX_ROWS ? dp_wg_cpl(P.start_save_bw) : 0;
+        e->last_dp.start = true;
+        e->last_dp.retry_wcpl = wcpl;
 #define WG_ARGS rs, dp, e->d_evm.as<double>(), e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_smoves.as<unsigned char>(), e->start_moves_stride, e->d_lastrow.as<double>()
         if (wcpl == 4) k_dp_wg<4><<<nb, 256, 0, s>>>(WG_ARGS);
         else if (wcpl == 8) k_dp_wg<8><<<nb, 256, 0, s>>>(WG_ARGS);
@@ -778,6 +788,9 @@ static int enqueue_stages(tba_engine *e, int first, int last)
     }
     MARK(); // 9 main dp
     if (ON(TBA_STAGE_ASSIGN)) {
+        e->last_dp.main = true;
+        e->last_dp.lowreg = dp_lowreg(e); // (launch_dp_t's choice for the 8-cell class)
+        e->last_dp.wide = e->wide_w != 0;
         for (int c : DpClasses::list) launch_dp(e, c, DP_MAIN);
         launch_dp_multi(e); // narrow adaptive bands: several reads per wavefront
         if (e->wide_w) // a static band wider than every class is possible in this batch
@@ -1138,6 +1151,37 @@ extern "C" int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_byt
     case TBA_GET_THEIL_SEN: return PER_READ(D4, to_array(r.ts));
     case TBA_GET_PATH: return PER_READ(I4, I4{r.path, (i32)r.n_static, (i32)r.W, r.n_start_calls});
     case TBA_GET_DEBUG_COUNTERS: return PER_READ(I8, to_array(r.dbg)); // phase cycle / sweep counters of a profiling build
+    case TBA_GET_DP_FORM: {
+        // Derived: what enqueue_stages launched, and per read the kernels' own selection predicates over the
+        // state the run left -- k_prep / k_scan_arena leave a path only on reads that go into the main pass,
+        // and nothing after start discovery touches start_state, n_start_calls or the first try's failure.
+        const tba_params &P = e->hp.p;
+        const tba_engine::DpLaunches L = e->last_dp;
+        const int multi_cpl = dp_multi_class(P.bandwidth).cpl;
+        const int retry_cpl = L.retry_wcpl ? L.retry_wcpl : cpl_class(P.start_save_bw);
+        return per_read([&](const ReadState &r) -> I4 {
+            I4 f{TBA_DP_FORM_NONE, 0, TBA_DP_START_NONE, 0};
+            if (L.main && r.path != PATH_NONE) {
+                const int c = cpl_class(r.W);
+                if (r.path == PATH_ADAPTIVE && r.W == P.bandwidth && multi_cpl != 0) // k_dp_multi.h:89, k_dp.h:296
+                    f[0] = TBA_DP_FORM_MULTI, f[1] = multi_cpl;
+                else if (c != 0)                                                     // k_dp.h:294
+                    f[0] = c == 8 && L.lowreg ? TBA_DP_FORM_K_DP8_LOWREG : TBA_DP_FORM_K_DP, f[1] = c;
+                else if (r.path == PATH_STATIC && L.wide)                            // k_dp.h:789
+                    f[0] = TBA_DP_FORM_WIDE;
+            }
+            // the retry took the reads in ST_RETRY (k_dp.h:304, k_dp_wg.h:34): it left ST_OK and two calls, or
+            // its status and the state as it was; the first try those in ST_TRY: one call, the reason it failed
+            // (TBA_GET_START_FAIL), or -- an internal error -- the state as it was
+            const bool retried = r.n_start_calls == 2 || r.start_state == ST_RETRY;
+            const bool tried = retried || r.n_start_calls == 1 || r.pad0 != 0 || r.start_state == ST_TRY;
+            if (L.start && retried)
+                f[2] = L.retry_wcpl ? TBA_DP_START_RETRY_WG : TBA_DP_START_RETRY_K_DP, f[3] = retry_cpl;
+            else if (L.start && tried)
+                f[2] = TBA_DP_START_FIRST_TRY;
+            return f;
+        });
+    }
     default: break;
     }
 #undef PER_READ
@@ -2436,6 +2480,11 @@ extern "C" int tba_engine_set_side_stream(tba_engine *e, int mode)
 extern "C" int tba_engine_last_side_stream(tba_engine *e)
 {
     return e ? (e->last_side ? 1 : 0) : 0;
+}
+
+extern "C" int tba_engine_last_dp_lowreg(tba_engine *e)
+{
+    return e ? (e->last_dp.lowreg ? 1 : 0) : 0;
 }
 
 extern "C" int tba_engine_set_sharing(tba_engine *e, int n_engines)
