@@ -548,6 +548,36 @@ int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, const int64_t 
     int64_t *out_valid_cov, double *out_damp_frac, int64_t *out_counts, int64_t *out_n_stats,
     double *out_per_read);
 
+/* ---- alternate-base model estimation (estimate_alt_model, tombo_stats.py:1747-2098) -----------
+ * The base levels of a batch of reads gathered by k-mer (_parse_base_levels_worker, :1747-1776).
+ * means / codes: read-centric levels and base codes (0..3 = ACGT, anything else: not a base) of
+ * the reads, both CSR by read_off[n_reads + 1].  Window i of a read is bases i .. i + kmer_width - 1
+ * and pairs with the read's level central_pos + i; a window with a non-ACGT code and a window
+ * whose k-mer (index: first base most significant) has completed[kmer] set are skipped; a NaN
+ * level is kept; a read shorter than kmer_width contributes nothing.
+ * out_counts[4^K]: levels per k-mer.  out_lv_off[4^K + 1] (may be NULL in the count form): their
+ * exclusive prefix.  out_levels NULL: the count form, nothing else is written.  Else the fill
+ * form: out_levels[out_lv_off[k] .. out_lv_off[k + 1]) = the levels of k-mer k in read order and,
+ * inside a read, position order -- bit-identical from run to run; levels_cap is the capacity of
+ * out_levels (the windows of the batch, sum of max(len - K + 1, 0), always suffice).
+ * TBA_E_ARG: NULL pointers, offsets that do not start at 0 or decrease, kmer_width outside
+ * [1, 10], central_pos outside [0, kmer_width), 2^31 bases or more, levels_cap too small. */
+int tba_kmer_levels(tba_engine *e, const double *means, const uint8_t *codes,
+    const int64_t *read_off, int64_t n_reads, int64_t kmer_width, int64_t central_pos,
+    const uint8_t *completed, int64_t *out_counts, int64_t *out_lv_off, double *out_levels,
+    int64_t levels_cap);
+/* Gaussian kernel densities (est_kernel_density, :1914-1939).  levels: n_seg segments, CSR by
+ * lv_off[n_seg + 1] (any order inside a segment; the input is not changed).
+ * out_dens[s * n_x + g] = sum_i exp(-0.5 ((x[g] - l_i) / bandwidth)^2) / (n bandwidth sqrt(2 pi))
+ * over the n levels of segment s: scipy.stats.gaussian_kde(l, bw_method=bandwidth /
+ * l.std(ddof=1)).evaluate(x).  The sum runs over the sorted levels in a fixed order: the output
+ * is bit-identical from run to run.  A segment of fewer than two levels (scipy raises) or with a
+ * NaN level gives a row of NaN.
+ * TBA_E_ARG: NULL pointers, offsets that do not start at 0 or decrease, a bandwidth that is not
+ * positive and finite, more than 65535 * 256 grid points. */
+int tba_kde_eval(tba_engine *e, const double *levels, const int64_t *lv_off, int64_t n_seg,
+    const double *x, int64_t n_x, double bandwidth, double *out_dens);
+
 /* The de novo statistic of every read of the finished resident batch, nothing uploaded: per-base
  * means (c_new_means over the final signal and boundaries, as tba_batch_base_stats) against the
  * batch's own expected levels, which are the canonical model's levels of the read sequence --
@@ -617,7 +647,7 @@ int tba_synth_dwell_thresholds(const tba_synth_params *p, uint32_t *thr, int64_t
 /* out[0..2] = sizeof(tba_params), sizeof(tba_opts), sizeof(tba_read_result) of this build, out[3]
  * (n >= 4) = TBA_ABI_VERSION: lets a binding without a C compiler (ctypes) check its struct mirrors
  * and refuse a stale build of the library */
-#define TBA_ABI_VERSION 11
+#define TBA_ABI_VERSION 12
 int tba_abi_sizes(int64_t *out, int64_t n);
 
 /* self-test: out[t] = index t of the subsample tba_opts.device_subsample draws for read

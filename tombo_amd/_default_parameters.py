@@ -59,3 +59,13 @@ LLR_THRESH = {DNA_SAMP_TYPE: (-1.5, 2.5), RNA_SAMP_TYPE: (-2.5, 2.5)}
 SAMP_COMP_THRESH = {DNA_SAMP_TYPE: (0.15, 0.5), RNA_SAMP_TYPE: (0.05, 0.4)}
 DE_NOVO_THRESH = {DNA_SAMP_TYPE: (0.15, 0.5), RNA_SAMP_TYPE: (0.05, 0.4)}
 COV_DAMP_COUNTS = [2, 0]
+
+# alternate-base model estimation (tombo/_default_parameters.py:147-151,164; the bandwidth is the
+# default of `tombo build_model estimate_alt_reference --kernel-density-bandwidth`)
+ALT_EST_BATCH = 1000
+MAX_KMER_OBS = 10000
+MIN_KMER_OBS_TO_EST = 50
+KERNEL_DENSITY_RANGE = (-5, 5)
+ALT_EST_PCTL = 5
+NUM_DENS_POINTS = 500
+KERNEL_DENSITY_BW = 0.05

@@ -112,7 +112,7 @@ STAGE_SEGMENT, STAGE_EVENT_MEANS, STAGE_REF_LEVELS, STAGE_START, STAGE_ASSIGN, S
 PUT_VALID_CPTS, PUT_EVENT_MEANS, PUT_NORM, PUT_REF_MEANS, PUT_REF_SDS, PUT_DP_SEGS, \
     PUT_START_STATE = range(1, 8)
 MAX_BAND = 3072
-ABI_VERSION = 11  # TBA_ABI_VERSION of include/tombo_amd.h
+ABI_VERSION = 12  # TBA_ABI_VERSION of include/tombo_amd.h
 STAGE_NAMES = ["normalize", "cumsum", "scores", "peaks", "event_means", "ref_levels",
                "start_dp", "start_tb", "prep", "main_dp", "main_tb", "skip_resolve", "theil_sen",
                "rescale_score", "stalls", "total"]
@@ -155,6 +155,46 @@ def _f64(a):
 
 def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _check_offsets(off, what):
+    off = np.asarray(off)
+    if off.dtype != np.int64 or off.ndim != 1 or off.shape[0] < 1:
+        raise ValueError('%s must be a one-dimensional int64 array' % what)
+    if off[0] != 0 or (np.diff(off) < 0).any():
+        raise ValueError('%s must start at 0 and be non-decreasing' % what)
+    return np.ascontiguousarray(off)
+
+
+def _check_kmer_levels_args(means, codes, read_off, kmer_width, central_pos, completed):
+    """the argument checks of Engine.kmer_levels (shared with the tests' stand-in engine): dtypes are
+    checked, not converted -> contiguous (means, codes, read_off, completed)"""
+    means, codes, completed = np.asarray(means), np.asarray(codes), np.asarray(completed)
+    if means.dtype != np.float64 or codes.dtype != np.uint8 or completed.dtype != np.uint8:
+        raise ValueError('means must be float64, codes and completed uint8')
+    if int(kmer_width) != kmer_width or not 1 <= kmer_width <= 10:
+        raise ValueError('kmer_width must be an integer in [1, 10]')
+    if int(central_pos) != central_pos or not 0 <= central_pos < kmer_width:
+        raise ValueError('central_pos must be an integer in [0, kmer_width)')
+    off = _check_offsets(read_off, 'read_off')
+    if means.ndim != 1 or codes.ndim != 1 or not (means.shape[0] == codes.shape[0] == int(off[-1])):
+        raise ValueError('per-base arrays and offsets disagree')
+    if completed.shape != (4 ** int(kmer_width),):
+        raise ValueError('completed must have 4**kmer_width entries')
+    return np.ascontiguousarray(means), np.ascontiguousarray(codes), off, np.ascontiguousarray(completed)
+
+
+def _check_kde_eval_args(levels, lv_off, x, bandwidth):
+    """the argument checks of Engine.kde_eval -> contiguous (levels, lv_off, x)"""
+    levels, x = np.asarray(levels), np.asarray(x)
+    if levels.dtype != np.float64 or x.dtype != np.float64 or levels.ndim != 1 or x.ndim != 1:
+        raise ValueError('levels and x must be one-dimensional float64 arrays')
+    off = _check_offsets(lv_off, 'lv_off')
+    if levels.shape[0] != int(off[-1]):
+        raise ValueError('levels and offsets disagree')
+    if not (bandwidth > 0 and np.isfinite(bandwidth)):
+        raise ValueError('bandwidth must be positive and finite')
+    return np.ascontiguousarray(levels), off, np.ascontiguousarray(x)
 
 
 # what one tba_site_fractions call gives back: the per-site arrays compacted per track at pos_off
@@ -780,6 +820,31 @@ class Engine(object):
         return self._site_fractions(1, trk_start, trk_end, (_p(m, f64), _p(r, f64)) + _site_other_form(1),
                                     win_args, st.shape[0], single_read_thresh, lower_thresh, damp_counts,
                                     return_per_read)
+
+    def kmer_levels(self, means, codes, read_off, kmer_width, central_pos, completed):
+        """tba_kmer_levels: the levels of a batch of reads (means / codes CSR by read_off) gathered by k-mer
+        -> (counts int64[4**K], levels float64, lv_off int64[4**K + 1]); the levels of a k-mer in read order,
+        then position order"""
+        m, codes, off, done = _check_kmer_levels_args(means, codes, read_off, kmer_width, central_pos, completed)
+        n_kmers = 4 ** int(kmer_width)
+        counts, lv_off = np.empty(n_kmers, dtype=np.int64), np.empty(n_kmers + 1, dtype=np.int64)
+        cap = int(np.maximum(np.diff(off) - (int(kmer_width) - 1), 0).sum())   # every window of the batch
+        levels = np.empty(cap, dtype=np.float64)
+        self._check(self._L.tba_kmer_levels(
+            self._h, _p(m, f64), _p(codes, C.c_uint8), _p(off, i64), i64(off.shape[0] - 1), i64(int(kmer_width)),
+            i64(int(central_pos)), _p(done, C.c_uint8), _p(counts, i64), _p(lv_off, i64), _p(levels, f64), i64(cap)),
+            'tba_kmer_levels')
+        return counts, levels[:int(lv_off[-1])].copy(), lv_off
+
+    def kde_eval(self, levels, lv_off, x, bandwidth):
+        """tba_kde_eval: the Gaussian kernel density of every segment of `levels` (CSR by lv_off) on the grid x
+        -> float64[n_seg, G]; NaN rows for segments of fewer than two levels or with a NaN level"""
+        lv, off, x = _check_kde_eval_args(levels, lv_off, x, bandwidth)
+        out = np.empty((off.shape[0] - 1, x.shape[0]), dtype=np.float64)
+        self._check(self._L.tba_kde_eval(
+            self._h, _p(lv, f64), _p(off, i64), i64(off.shape[0] - 1), _p(x, f64), i64(x.shape[0]),
+            f64(float(bandwidth)), _p(out, f64)), 'tba_kde_eval')
+        return out
 
     def stats(self):
         a, c = f64(0), f64(0)

@@ -17,6 +17,7 @@
 #include "k_synth.h"
 #include "k_group.h"
 #include "k_site.h"
+#include "k_kde.h"
 
 #include <algorithm>
 #include <array>
@@ -2040,6 +2041,90 @@ extern "C" int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, con
     if (d_damp && sc.get(out_damp_frac, d_damp, n_pos)) return sc.rc;
     if (out_per_read && d_pr) return sc.get(out_per_read, d_pr, n_stats);
     return TBA_OK;
+}
+
+// ---- estimate_alt_model (k_kde.h): levels gathered by k-mer, kernel densities ----------------
+extern "C" int tba_kmer_levels(tba_engine *e, const double *means, const uint8_t *codes,
+    const int64_t *read_off, int64_t n_reads, int64_t kmer_width, int64_t central_pos,
+    const uint8_t *completed, int64_t *out_counts, int64_t *out_lv_off, double *out_levels,
+    int64_t levels_cap)
+{
+    if (!e || !read_off || !completed || !out_counts || n_reads < 0 || kmer_width < 1 || kmer_width > 10 ||
+        central_pos < 0 || central_pos >= kmer_width || (out_levels && (!out_lv_off || levels_cap < 0)))
+        return set_err(TBA_E_ARG, "bad arguments");
+    const i64 n_kmers = (i64)1 << (2 * kmer_width);
+    if (const int rc = check_csr_off(read_off, n_reads)) return rc;
+    const i64 total = n_reads > 0 ? read_off[n_reads] : 0;
+    if (total >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "more than 2^31 - 1 bases in one batch");
+    if (total > 0 && (!means || !codes)) return set_err(TBA_E_ARG, "bad arguments");
+    if (total == 0) {
+        for (i64 q = 0; q < n_kmers; q++) out_counts[q] = 0;
+        if (out_lv_off) for (i64 q = 0; q <= n_kmers; q++) out_lv_off[q] = 0;
+        return TBA_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    KmerArgs a{};
+    // at most 1024 chunks and at most 2^24 counters: a chunk is a multiple of 64 positions
+    const i64 max_chunks = std::max<i64>(1, std::min<i64>(1024, ((i64)1 << 24) / n_kmers));
+    a.chunk = std::max<i64>(4096, ((total + max_chunks - 1) / max_chunks + 63) / 64 * 64);
+    const i64 n_chunks = (total + a.chunk - 1) / a.chunk;
+    a.n_reads = n_reads; a.total = total; a.K = (int)kmer_width; a.cp = (int)central_pos;
+    a.read_off = sc.in(read_off, n_reads + 1);
+    a.codes = sc.in(codes, total);
+    a.completed = sc.in(completed, n_kmers);
+    a.means = sc.in(means, total);
+    u32 *rows = sc.out<u32>(n_chunks * n_kmers);
+    i64 *d_counts = sc.out<i64>(n_kmers), *d_off = sc.out<i64>(n_kmers + 1);
+    if (sc.rc || sc.hip(hipMemsetAsync(rows, 0, n_chunks * n_kmers * sizeof(u32), e->stream), "hipMemsetAsync"))
+        return sc.rc;
+    k_kmer_gather<false><<<(unsigned)n_chunks, 64, 0, e->stream>>>(a, rows, nullptr, nullptr);
+    k_kmer_colscan<<<grid_for(n_kmers), 256, 0, e->stream>>>(n_kmers, n_chunks, rows, d_counts);
+    k_kmer_offsets<<<1, 64, 0, e->stream>>>(n_kmers, d_counts, d_off);
+    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.get(out_counts, d_counts, n_kmers)) return sc.rc;
+    if (out_lv_off && sc.get(out_lv_off, d_off, n_kmers + 1)) return sc.rc;
+    if (!out_levels) return TBA_OK;
+    const i64 n_lv = out_lv_off[n_kmers];
+    if (n_lv > levels_cap) return set_err(TBA_E_ARG, "levels_cap is smaller than the number of gathered levels");
+    if (n_lv == 0) return TBA_OK;
+    double *d_lv = sc.out<double>(n_lv);
+    if (sc.rc) return sc.rc;
+    k_kmer_gather<true><<<(unsigned)n_chunks, 64, 0, e->stream>>>(a, rows, d_off, d_lv);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(out_levels, d_lv, n_lv);
+}
+
+extern "C" int tba_kde_eval(tba_engine *e, const double *levels, const int64_t *lv_off, int64_t n_seg,
+    const double *x, int64_t n_x, double bandwidth, double *out_dens)
+{
+    if (!e || !lv_off || n_seg < 0 || n_x < 0 || !(bandwidth > 0) || !(bandwidth < INFINITY) ||
+        n_x > (int64_t)65535 * 256 || (n_x > 0 && !x) || (n_seg > 0 && n_x > 0 && !out_dens))
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (n_seg == 0 || n_x == 0) return TBA_OK;
+    if (const int rc = check_csr_off(lv_off, n_seg)) return rc;
+    for (i64 s = 0; s < n_seg; s++)
+        if (lv_off[s + 1] - lv_off[s] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "segment of more than 2^31 - 1 levels");
+    const i64 n_lv = lv_off[n_seg];
+    if (n_lv > 0 && !levels) return set_err(TBA_E_ARG, "bad arguments");
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    double *d_lv = n_lv > 0 ? sc.in(levels, n_lv) : sc.out<double>(1);
+    const i64 *d_off = sc.in(lv_off, n_seg + 1);
+    const double *d_x = sc.in(x, n_x);
+    i32 *cov = sc.out<i32>(n_seg), *has_nan = sc.out<i32>(n_seg);
+    i64 *lists = sc.out<i64>(3 * n_seg);
+    u32 *cls = sc.out<u32>(3);
+    double *d_dens = sc.out<double>(n_seg * n_x);
+    if (sc.rc || sc.hip(hipMemsetAsync(cls, 0, 3 * sizeof(u32), e->stream), "hipMemsetAsync")) return sc.rc;
+    k_kde_classify<<<grid_for(64 * n_seg), 256, 0, e->stream>>>(n_seg, d_off, d_lv, cov, has_nan, lists, cls);
+    k_grp_sort_wave<<<1024, 256, 0, e->stream>>>(lists, cls, cov, d_off, d_lv);
+    k_grp_sort_wg<<<1024, 256, 0, e->stream>>>(lists + n_seg, cls + 1, cov, d_off, d_lv, 0);
+    k_grp_sort_wg<<<256, 256, 0, e->stream>>>(lists + 2 * n_seg, cls + 2, cov, d_off, d_lv, 1);
+    k_kde_eval<<<dim3((unsigned)std::min<i64>(n_seg, 65535), (unsigned)((n_x + 255) / 256)), 256, 0, e->stream>>>(
+        n_seg, cov, has_nan, d_off, d_lv, d_x, n_x, bandwidth, d_dens);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(out_dens, d_dens, n_seg * n_x);
 }
 
 // testable slice of every read -> CSR offsets into a packed copy of (means, levels); one thread

@@ -10,7 +10,10 @@ Mirrors the part of /root/reference/tombo/tombo_stats.py the hot path touches:
 The numeric kernels (normalisation, event detection, DP ...) live in csrc/ and are reached
 through tombo_amd.resquiggle.
 """
+import io
 import os
+import re
+import warnings
 from collections import namedtuple
 
 import numpy as np
@@ -21,7 +24,8 @@ from ._default_parameters import (
     ALGN_PARAMS_TABLE, SEG_PARAMS_TABLE, RNA_SAMP_TYPE, DNA_SAMP_TYPE, STANDARD_MODELS,
     HALF_NORM_EXPECTED_VAL, MIN_EVENT_TO_SEQ_RATIO, STALL_PARAMS, SMALLEST_PVAL, FM_OFFSET_DEFAULT,
     SAMP_COMP_TXT, DE_NOVO_TXT, ALT_MODEL_TXT, CONST_SD_MODEL, OCLLHR_SCALE, OCLLHR_HEIGHT,
-    OCLLHR_POWER, MEAN_PRIOR_CONST, SD_PRIOR_CONST)
+    OCLLHR_POWER, MEAN_PRIOR_CONST, SD_PRIOR_CONST, ALT_EST_BATCH, MAX_KMER_OBS, MIN_KMER_OBS_TO_EST,
+    KERNEL_DENSITY_RANGE, NUM_DENS_POINTS)
 
 _MODEL_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tombo_models')
 _BASE_CODE = np.full(256, 255, dtype=np.uint8)
@@ -244,6 +248,20 @@ class AltModel(object):
         nan = float('nan')
         return (np.array([self.means.get((k, p), nan) for k, p in zip(seq_kmers, pos_range)]),
                 np.array([self.sds.get((k, p), nan) for k, p in zip(seq_kmers, pos_range)]))
+
+    def write_model(self, ref_fp):
+        """tombo_stats.py:929-953 into `ref_fp`, any object with the h5py group interface (an open
+        h5py.File, like `tombo_helper.write_new_fast5_group` takes one): the record array `model`
+        (kmer, pos, mean, sd) and the attributes central_pos, model_name, alt_base, motif, mod_pos"""
+        tab = np.array([(kmer, pos, self.means[(kmer, pos)], self.sds[(kmer, pos)]) for kmer, pos in self.means],
+                       dtype=[(str('kmer'), 'S%d' % self.kmer_width), (str('pos'), 'u4'), (str('mean'), 'f8'),
+                              (str('sd'), 'f8')])
+        ref_fp.create_dataset('model', data=tab, compression='gzip')
+        ref_fp.attrs['central_pos'] = self.central_pos
+        ref_fp.attrs['model_name'] = self.name
+        ref_fp.attrs['alt_base'] = self.alt_base
+        ref_fp.attrs['motif'] = self.motif.raw_motif
+        ref_fp.attrs['mod_pos'] = self.motif.mod_pos
 
 
 def _csr_offsets(lengths):
@@ -952,3 +970,224 @@ def region_stats_block(reg_stats, cov_damp_counts):
     block['control_cov'] = np.asarray(reg_stats.ctrl_cov[:n], dtype=np.int64)[keep]
     block['valid_cov'] = np.asarray(reg_stats.valid_cov)[keep]
     return block
+
+
+# ---------------------------------------------------------------------------------------------
+# Alternate-base model estimation: `tombo build_model estimate_alt_reference`, estimate_alt_model
+# (tombo_stats.py:1747-2098).  The reference bins the levels of every read by k-mer in worker
+# processes and fits one scipy gaussian_kde per k-mer; here a batch of reads is one
+# `Engine.kmer_levels` call and the densities of all k-mers one `Engine.kde_eval` call (kernels in
+# csrc/k_kde.h).  The density isolation that follows is 4**K x num_dens_points values and stays in
+# numpy.  Reads are lists of `th.resquiggledRead`; k-mers are in lexicographic order throughout.
+def _all_kmers(kmer_width):
+    from itertools import product
+    return [''.join(p) for p in product('ACGT', repeat=kmer_width)]
+
+
+def _kmer_levels_batch(reads, kmer_width, central_pos, completed, engine):
+    """one `kmer_levels` call for a list of reads -> (counts, levels, lv_off); a read without levels is left out"""
+    reads = [rd for rd in reads if rd.means is not None]
+    n_kmers = 4 ** kmer_width
+    if not reads:
+        return np.zeros(n_kmers, dtype=np.int64), np.empty(0), np.zeros(n_kmers + 1, dtype=np.int64)
+    means = [np.asarray(rd.means, dtype=np.float64) for rd in reads]
+    codes = [encode_seq(rd.seq) for rd in reads]
+    for rd, m, c in zip(reads, means, codes):
+        if m.shape[0] != c.shape[0]:
+            raise ValueError('read %r: levels and bases differ in number' % (rd.read_id,))
+    return _engine(engine).kmer_levels(
+        _concat_f64(means), np.ascontiguousarray(np.concatenate(codes), dtype=np.uint8),
+        _csr_offsets([m.shape[0] for m in means]), kmer_width, central_pos, completed)
+
+
+def parse_base_levels(reads, std_ref, parse_levels_batch_size, kmer_obs_thresh, max_kmer_obs,
+                      min_kmer_obs_to_est, engine=None):
+    """tombo_stats.py:1811-1884: the levels of `reads` grouped by k-mer -> (levels, lv_off), the
+    levels of k-mer k (lexicographic index) being levels[lv_off[k]:lv_off[k + 1]] in the order the
+    reads were given and, inside a read, position order.  Reads are taken in batches of
+    parse_levels_batch_size; a k-mer whose total exceeds max_kmer_obs after a batch is complete
+    and skipped from then on; the loop ends once the rarest k-mer still open after a batch exceeds
+    kmer_obs_thresh, or with the reads.  Raises th.TomboError where the reference exits (fewer than
+    min_kmer_obs_to_est observations of some k-mer), warns where it warns.  Deterministic: the
+    caller shuffles."""
+    K = std_ref.kmer_width
+    n_kmers = 4 ** K
+    bs = int(parse_levels_batch_size)
+    if bs < 1:
+        raise ValueError('parse_levels_batch_size must be positive')
+    completed = np.zeros(n_kmers, dtype=np.uint8)
+    totals = np.zeros(n_kmers, dtype=np.int64)
+    batches = []   # (counts, levels, lv_off) per batch, on the host
+    reads = list(reads)
+    pos = 0
+    while True:
+        batch, pos = reads[pos:pos + bs], pos + bs
+        no_more_reads = len(batch) < bs
+        is_open = completed == 0
+        if not is_open.any():
+            break   # (every k-mer complete: the reference's min() of nothing)
+        counts, levels, lv_off = _kmer_levels_batch(batch, K, std_ref.central_pos, completed, engine)
+        batches.append((counts, levels, lv_off))
+        totals += counts
+        completed[is_open & (totals > max_kmer_obs)] = 1
+        if totals[is_open].min() > kmer_obs_thresh or no_more_reads:
+            break
+    fewest = int(totals.min())
+    if fewest < kmer_obs_thresh:
+        if fewest < min_kmer_obs_to_est:
+            raise th.TomboError(
+                'Too few minimal k-mer observations to continue to alternative estimation. Minimal k-mer has ' +
+                str(fewest) + ' total observations and ' + str(min_kmer_obs_to_est) +
+                ' observations per k-mer are required.')
+        warnings.warn('Requested minimal k-mer observations not found in all reads. Continuing to estimation '
+                      'using a k-mer with ' + str(fewest) + ' total observations')
+    # the one concatenation per k-mer: batch b's levels of k-mer k follow those of the earlier batches
+    out_off = _csr_offsets(totals)
+    out = np.empty(int(out_off[-1]), dtype=np.float64)
+    before = np.zeros(n_kmers, dtype=np.int64)
+    for counts, levels, lv_off in batches:
+        out[np.repeat(out_off[:-1] + before - lv_off[:-1], counts) + np.arange(levels.shape[0])] = levels
+        before += counts
+    return out, out_off
+
+
+def write_kmer_densities_file(dens_fn, kmer_dens, save_x):
+    """tombo_stats.py:1886-1893: one `Kmer<TAB>Signal<TAB>Density` line per k-mer and grid point"""
+    with io.open(dens_fn, 'wt') as fp:
+        fp.write('Kmer\tSignal\tDensity\n')
+        for kmer, dens_i in kmer_dens.items():
+            for x, y in zip(save_x, dens_i):
+                fp.write('%s\t%s\t%s\n' % (kmer, str(x), str(y)))
+
+
+def parse_kmer_densities_file(dens_fn):
+    """tombo_stats.py:1895-1912 -> {kmer: densities} in file order"""
+    raw = {}
+    with io.open(dens_fn) as fp:
+        fp.readline()   # header
+        for line in fp:
+            kmer, _, dens_i = line.split()
+            raw.setdefault(kmer, []).append(float(dens_i))
+    first_len = None
+    kmer_dens = {}
+    for kmer, dens_i in raw.items():
+        if first_len is None:
+            first_len = len(dens_i)
+        if len(dens_i) != first_len:
+            raise th.TomboError('Density file is valid.')   # (the reference's own wording)
+        kmer_dens[kmer] = np.array(dens_i)
+    return kmer_dens
+
+
+def est_kernel_density(reads, std_ref, kmer_obs_thresh, density_basename, save_x, kernel_dens_bw,
+                       alt_or_stnd_name='alt', parse_levels_batch_size=ALT_EST_BATCH,
+                       max_kmer_obs=MAX_KMER_OBS, min_kmer_obs_to_est=MIN_KMER_OBS_TO_EST, engine=None,
+                       shuffle=True):
+    """tombo_stats.py:1914-1939 -> {kmer: density on save_x}: the Gaussian kernel density (bandwidth
+    kernel_dens_bw in level units) of every k-mer's levels, ONE `kde_eval` call for all k-mers.
+    shuffle: np.random.shuffle of the reads first, as the reference does."""
+    reads = list(reads)
+    if shuffle:
+        np.random.shuffle(reads)
+    levels, lv_off = parse_base_levels(reads, std_ref, parse_levels_batch_size, kmer_obs_thresh,
+                                       max_kmer_obs, min_kmer_obs_to_est, engine)
+    if (np.diff(lv_off) < 2).any():   # (scipy's gaussian_kde raises for a single observation)
+        raise th.TomboError('Kernel density estimation requires at least two observations per k-mer.')
+    dens = _engine(engine).kde_eval(levels, lv_off, np.ascontiguousarray(save_x, dtype=np.float64),
+                                    float(kernel_dens_bw))
+    kmer_dens = dict(zip(_all_kmers(std_ref.kmer_width), dens))
+    if density_basename is not None:
+        write_kmer_densities_file(density_basename + '.' + alt_or_stnd_name + '_density.txt', kmer_dens, save_x)
+    return kmer_dens
+
+
+def estimate_kmer_densities(reads, ctrl_reads, std_ref, kmer_obs_thresh, density_basename, kernel_dens_bw,
+                            save_x, engine=None, **kwargs):
+    """tombo_stats.py:1941-1961 -> (alt_dens, std_dens, std_ref); kwargs go to est_kernel_density"""
+    alt_dens = est_kernel_density(reads, std_ref, kmer_obs_thresh, density_basename, save_x, kernel_dens_bw,
+                                  'alternate', engine=engine, **kwargs)
+    std_dens = est_kernel_density(ctrl_reads, std_ref, kmer_obs_thresh, density_basename, save_x,
+                                  kernel_dens_bw, 'control', engine=engine, **kwargs)
+    return alt_dens, std_dens, std_ref
+
+
+def load_kmer_densities(alt_dens_fn, std_dens_fn, std_ref):
+    """tombo_stats.py:1963-1989 -> (alt_dens, std_dens, std_ref, save_x)"""
+    alt_dens = parse_kmer_densities_file(alt_dens_fn)
+    std_dens = parse_kmer_densities_file(std_dens_fn)
+    num_dens_points = next(v for v in alt_dens.values()).shape[0]
+    if num_dens_points != next(v for v in std_dens.values()).shape[0]:
+        raise th.TomboError('Alternative and standard density estimates do not correspond.')
+    save_x = np.linspace(KERNEL_DENSITY_RANGE[0], KERNEL_DENSITY_RANGE[1], num_dens_points)
+    return alt_dens, std_dens, std_ref, save_x
+
+
+def isolate_alt_density(alt_dens, std_dens, alt_base, alt_frac_pctl, std_ref, save_x):
+    """tombo_stats.py:1991-2071 (host only, no engine): the alternate sample's densities shifted onto
+    the standard sample's (a quadratic fit of the mean shift of the k-mers without the alternate
+    base), the standard-base fraction of the sample from the matched peaks of the k-mers with one
+    alternate base (its alt_frac_pctl-th percentile), and per k-mer with the alternate base the mean
+    of what is left of its shifted density after that fraction of the standard density is taken
+    away -> AltModel.  Same operations in the same order as the reference."""
+    def calc_mean(dens):
+        keep = dens > 1e-10
+        return np.average(save_x[keep], weights=dens[keep])
+
+    no_alt_std_means, no_alt_mean_diffs = [], []
+    for kmer in std_dens:
+        if alt_base in kmer:
+            continue
+        no_alt_std_means.append(calc_mean(std_dens[kmer]))
+        no_alt_mean_diffs.append(calc_mean(alt_dens[kmer]) - no_alt_std_means[-1])
+    calc_offset = np.poly1d(np.polyfit(no_alt_std_means, no_alt_mean_diffs, 2))
+    save_x_unit = save_x[1] - save_x[0]
+
+    shifted_alt_dens = {}
+    for kmer, kmer_alt_dens in alt_dens.items():
+        est_offset = int(calc_offset(calc_mean(std_dens[kmer])) / save_x_unit)
+        if est_offset < 0:   # standard mean above: the alternate density moves right
+            shifted_alt_dens[kmer] = np.concatenate([np.zeros(-est_offset), kmer_alt_dens[:est_offset]])
+        else:
+            shifted_alt_dens[kmer] = np.concatenate([kmer_alt_dens[est_offset:], np.zeros(est_offset)])
+
+    def get_peak_frac(kmer_std_dens, kmer_alt_dens):
+        std_peak = np.argmax(kmer_std_dens)
+        inner = kmer_alt_dens[1:-1]
+        alt_local_peaks = np.flatnonzero((inner > kmer_alt_dens[:-2]) & (inner > kmer_alt_dens[2:])) + 1
+        matched = alt_local_peaks[np.argmin(abs(alt_local_peaks - std_peak))]
+        return kmer_alt_dens[matched] / kmer_std_dens[std_peak]
+
+    std_frac = np.percentile([get_peak_frac(std_dens[kmer], shifted_alt_dens[kmer])
+                              for kmer in std_dens if kmer.count(alt_base) == 1], alt_frac_pctl)
+    if std_frac >= 1:
+        warnings.warn('Alternative base incorporation rate estimate is approximately 0. Consider lowering '
+                      '--alt-fraction-percentile.')
+    model_sd = np.mean(list(std_ref.sds.values()))
+    alt_ref = []
+    for kmer in std_ref.means:
+        n_alt = kmer.count(alt_base)
+        if n_alt == 0:
+            continue
+        with np.errstate(under='ignore'):
+            diff_dens = shifted_alt_dens[kmer] - (std_dens[kmer] * std_frac ** n_alt)
+            diff_dens[diff_dens < 0] = 0
+            alt_level = np.average(save_x, weights=diff_dens)
+        for m in re.finditer(alt_base, kmer):
+            alt_ref.append((kmer, m.start(), alt_level, model_sd))
+    return AltModel(kmer_ref=alt_ref, central_pos=std_ref.central_pos, alt_base=alt_base)
+
+
+def estimate_alt_model(reads, ctrl_reads, std_ref, alt_base, alt_frac_pctl, kmer_obs_thresh,
+                       density_basename, kernel_dens_bw, alt_dens_fn, std_dens_fn,
+                       num_dens_points=NUM_DENS_POINTS, engine=None, **kwargs):
+    """tombo_stats.py:2073-2098: an alternate-base model from a sample with one known, randomly
+    incorporated alternate base (`reads`) and a standard sample (`ctrl_reads`), or from two density
+    files written by an earlier run (then the reads are not used).  kwargs go to est_kernel_density."""
+    if alt_dens_fn is None or std_dens_fn is None:
+        save_x = np.linspace(KERNEL_DENSITY_RANGE[0], KERNEL_DENSITY_RANGE[1], num_dens_points)
+        alt_dens, std_dens, std_ref = estimate_kmer_densities(
+            reads, ctrl_reads, std_ref, kmer_obs_thresh, density_basename, kernel_dens_bw, save_x,
+            engine=engine, **kwargs)
+    else:
+        alt_dens, std_dens, std_ref, save_x = load_kmer_densities(alt_dens_fn, std_dens_fn, std_ref)
+    return isolate_alt_density(alt_dens, std_dens, alt_base, alt_frac_pctl, std_ref, save_x)
