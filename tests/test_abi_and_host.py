@@ -344,6 +344,45 @@ def test_planner_tail_batches():
     assert planner.plan_batches(S, L, p, o, 6, 3e9, tail_bases=10 ** 9)[0].shape[0] > 0   # no tail: plain plan
 
 
+def _footprint_cases():
+    """(name, bytes recorded from the library before the engine's buffer list and batch sizes were
+    each brought to one place, params, opts, k-mer width, raw dtype, n_raw[4], seq_len[4])"""
+    from tombo_amd import _native, tombo_stats as ts, tombo_helper as th
+    from tombo_amd._default_parameters import MEAN_STALL_PARAMS
+    hdr = open(os.path.join(os.path.dirname(__file__), '..', 'include', 'tombo_amd.h')).read()
+    max_band = int(re.search(r'#define\s+TBA_MAX_BAND\s+(\d+)', hdr).group(1))
+    dna = ts.load_resquiggle_parameters(th.seqSampleType('DNA', False))
+    rna = ts.load_resquiggle_parameters(th.seqSampleType('RNA', False))
+    stalls = th.stallParams(**MEAN_STALL_PARAMS)
+    assert stalls.window_size <= 1024       # SI_MAXW (k_prep_raw.h): the int16 detector keeps no cumulative sum
+    S, L = [3000, 9000, 0, 400], [300, 900, 50, 3]
+    # the longest read with more events than the widest band class: the wide static kernel's rows
+    S_wide = [3000, int(dna.mean_obs_per_event) * (max_band + 200), 0, 400]
+    L_wide = [300, 1200, 50, 3]
+    mk = _native.make_opts
+    return [
+        ('dna_f64', 380747435.0, dna, mk(outlier_thresh=5.0), 6, np.float64, S, L),
+        ('dna_i16', 380663735.0, dna, mk(outlier_thresh=5.0), 6, np.int16, S, L),
+        ('dna_skip_norm_out', 380635507.0, dna, mk(outlier_thresh=5.0, skip_norm_out=True), 6, np.float64, S, L),
+        ('stalls_i16', 380667304.0, dna, mk(outlier_thresh=5.0, stall_params=stalls), 6, np.int16, S, L),
+        ('stalls_f64', 380862968.0, dna, mk(outlier_thresh=5.0, stall_params=stalls), 6, np.float64, S, L),
+        ('rna', 380904261.0, rna, mk(outlier_thresh=5.0), 5, np.float64, S, L),
+        ('dna_wide', 385015361.0, dna, mk(outlier_thresh=5.0), 6, np.float64, S_wide, L_wide),
+    ]
+
+
+def test_batch_footprint_is_what_it_was_before_the_buffer_list_moved():
+    """tba_batch_footprint (host only) over every branch of the size table -- raw sample type, norm_out,
+    the stall detector's scratch in both of its forms, the RNA parameter set, the wide static band --
+    with failing reads (no signal, a sequence shorter than the k-mer) in the batch: the integer it
+    returned before the engine's host code was reorganised"""
+    from tombo_amd import planner, _native
+    for name, want, params, o, K, dt, S, L in _footprint_cases():
+        got = planner.exact_bytes(S, L, _native.make_params(params), o, K, dt)
+        print(name, repr(got))
+        assert got == want and got == int(got), (name, got, want)
+
+
 def test_stream_pipeline_any_slot_and_feeder_staging(monkeypatch):
     """in_order=False: a batch takes the first slot that is free or has finished (never waiting
     behind a long one while another is idle), results come back as they complete; ReadFeeder hands

@@ -38,46 +38,29 @@ static int set_err(int code, const std::string &msg) { g_last_error = msg; retur
             return set_err(TBA_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));      \
     } while (0)
 
-struct DevBuf {
+// A grow-only buffer: device memory (DevBuf), or page-locked host memory (PinBuf: engine-owned staging of the
+// small per-batch records, so that the "async" upload never falls back to HIP's blocking pageable path).
+template <bool PINNED>
+struct GrowBuf {
     void *p = nullptr;
     size_t cap = 0;
     int ensure(size_t bytes)
     {
         if (bytes <= cap) return 0;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        release();
         size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return set_err(TBA_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+        hipError_t e = PINNED ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
+        if (e != hipSuccess) { p = nullptr; return set_err(TBA_E_NOMEM, std::string(PINNED ? "hipHostMalloc: " : "hipMalloc: ") + hipGetErrorString(e)); }
         cap = want;
         return 0;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void release() { if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
     template <class T> T *as() const { return (T *)p; }
 };
-// page-locked host buffer (engine-owned staging of the small per-batch records, so that the
-// "async" upload never falls back to HIP's blocking pageable path)
-struct PinBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes)
-    {
-        if (bytes <= cap) return 0;
-        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) { p = nullptr; return set_err(TBA_E_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
-        cap = want;
-        return 0;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    template <class T> T *as() const { return (T *)p; }
-};
+typedef GrowBuf<false> DevBuf; typedef GrowBuf<true> PinBuf;
 
-enum { N_STAGE = 16 };
-static const char *STAGE_NAMES[N_STAGE] = {
-    "normalize", "cumsum", "scores", "peaks", "event_means", "ref_levels", "start_dp",
-    "start_tb", "prep", "main_dp", "main_tb", "skip_resolve", "theil_sen", "rescale_score",
-    "stalls", "total"};
+// timing slots (TBA_GET_KERNEL_MS, tba_stage_name): one per pipeline step (STEPS, below), then these two
+enum { N_STEP = 14, SLOT_STALLS = N_STEP, SLOT_TOTAL, N_STAGE };
 
 #define WIDE_BLOCKS 64 // workgroups of k_dp_wide (each owns two scratch rows)
 #define TB_LANES 16    // reads per wavefront of the latency-bound lane-per-read kernels
@@ -89,15 +72,36 @@ static const char *STAGE_NAMES[N_STAGE] = {
 
 // k_peaks is compiled per exclusion radius (min_obs_per_base - 1): 2 and 5 are the defaults of
 // the DNA / RNA parameter sets, anything else takes the generic kernel
-static void launch_peaks(i64 min_obs_per_base, unsigned n_blocks, hipStream_t s, ReadState *rs,
-                         const DevParams *dp, const double *score, unsigned char *state,
-                         double *dense, i64 *valid_cpts, int ttest, int only_flagged = 0,
-                         int form = TBA_ED_FORM_SCORES_PEAKS)
+static void launch_peaks(i64 min_obs_per_base, unsigned n_blocks, hipStream_t s, ReadState *rs, const DevParams *dp, const double *score,
+                         unsigned char *state, double *dense, i64 *valid_cpts, int ttest, int only_flagged = 0, int form = TBA_ED_FORM_SCORES_PEAKS)
 {
-    if (min_obs_per_base - 1 == 2) k_peaks<2><<<n_blocks, SEL_NT, 0, s>>>(rs, dp, score, state, dense, valid_cpts, ttest, only_flagged, form);
-    else if (min_obs_per_base - 1 == 5) k_peaks<5><<<n_blocks, SEL_NT, 0, s>>>(rs, dp, score, state, dense, valid_cpts, ttest, only_flagged, form);
-    else k_peaks<0><<<n_blocks, SEL_NT, 0, s>>>(rs, dp, score, state, dense, valid_cpts, ttest, only_flagged, form);
+    const i64 r = min_obs_per_base - 1;
+    (r == 2 ? k_peaks<2> : r == 5 ? k_peaks<5> : k_peaks<0>)<<<n_blocks, SEL_NT, 0, s>>>(rs, dp, score, state, dense, valid_cpts, ttest, only_flagged, form);
 }
+
+// Everything the device buffers of a batch depend on, from the per-read lengths alone: plan_batch's
+// output, kept by the engine for the uploaded batch.
+struct BatchSizes {
+    i64 S_tot = 0, seq_tot = 0, B_tot = 0, E_tot = 0, max_raw = 0, max_B = 0, max_nev = 0;
+    i64 moves_need = 0, start_moves_stride = 0, moves_arena = 0, skip_arena = 0, wide_w = 0, n_stall = 0;
+    double algo_bytes = 0, cells = 0;
+};
+
+// Every device buffer of the engine, once: the members, release_all() and tba_engine_held_bytes() are made
+// from this list (the sizes of a batch: for_each_batch_buffer).  Its order is the order of release.
+#define TBA_ENGINE_DEVBUFS(X)                                                                                         \
+    X(d_rs); X(d_dp);                 /* ReadState[n] / DevParams */                                                  \
+    X(d_kmeans); X(d_ksds);           /* the model's level table (tba_set_model) */                                   \
+    /* the batch as uploaded (d_raw, d_seq, d_sv_in, d_samp, d_stall: or as detected) and what the steps hand on */   \
+    X(d_raw); X(d_norm); X(d_norm_out); X(d_csum); X(d_score); X(d_state); X(d_cpts); X(d_evm); X(d_seq); X(d_refm); X(d_refs); X(d_bst); \
+    X(d_lo); X(d_hi); X(d_readtb); X(d_dpsegs); X(d_segs); X(d_win); X(d_absz); X(d_sv_in); X(d_samp); X(d_stall); X(d_lastrow);          \
+    X(d_startvals); X(d_smoves); X(d_moves); X(d_dscr); X(d_wide);                                                    \
+    X(d_stat);                        /* per-base means / stds of a finished batch (launch_base_stats) */             \
+    X(d_res); X(d_segs32);            /* packed results of tba_batch_download_async */                                \
+    X(d_skipq);                       /* window queues of k_skip_dp_wave */                                           \
+    X(d_order); X(d_long);            /* read indices by decreasing length (k_dp_multi's grouping); the long reads (k_long.h) */ \
+    X(d_stall_csum); X(d_stall_bits); /* the stall detector's own scratch (it runs beside event detection) */
+
 struct tba_engine {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -108,16 +112,16 @@ struct tba_engine {
     // (SQ_WAIT_ANY 60-80 % of their wave cycles): together they fill what each leaves idle.
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_stalls = nullptr, ev_levels = nullptr, ev_st0 = nullptr, ev_st1 = nullptr, ev_skip0 = nullptr, ev_skip1 = nullptr;
-    hipEvent_t ev[N_STAGE + 1] = {};
+    hipEvent_t ev[N_STAGE + 1] = {}; // ev[i], ev[i + 1]: around step i of the pipeline; ev[N_STEP]: its end, ev[SLOT_TOTAL]: its start
     float stage_ms[32] = {};
     bool have_model = false, have_batch = false, ran = false;
     bool finished = false; // the last stage (rescale + score) has run on the uploaded batch
     DevParams hp;
-    i64 n_reads = 0, S_tot = 0, seq_tot = 0, B_tot = 0, E_tot = 0, max_raw = 0, max_B = 0;
-    i64 start_moves_stride = 0, moves_arena = 0, skip_arena = 0, wide_w = 0, n_stall_cap = 0;
+    i64 n_reads = 0;
+    BatchSizes z;                 // of the uploaded batch
+    size_t n_segs() const { return (size_t)(z.B_tot + n_reads); } // segment boundaries of the batch: B + 1 per read
     bool any_stall = false, have_samp = false, have_sv = false;
     std::vector<i64> ne_override; // per-read num_events for the next upload (stepwise API)
-    double algo_bytes = 0, dp_cells = 0;
     int n_sharing = 1;            // engines fed concurrently on this device (tba_engine_set_sharing)
     int side_mode = -1;           // tba_engine_set_side_stream: -1 by the engines alive, 0 never, 1 always
     bool last_side = false;       // the last full run used the side stream
@@ -132,29 +136,15 @@ struct tba_engine {
     int last_c_ed_form = 0;       // tba_c_last_ed_form
     int raw_dtype = TBA_RAW_F64;
     PinBuf h_rs, h_dp;            // ReadState[n] / DevParams as uploaded (pinned)
-    DevBuf d_res, d_segs32;       // packed results of tba_batch_download_async
-    DevBuf d_skipq;               // window queues of k_skip_dp_wave
-    DevBuf d_rs, d_dp, d_kmeans, d_ksds, d_raw, d_norm, d_norm_out, d_csum, d_score, d_state,
-        d_cpts, d_evm, d_seq, d_refm, d_refs, d_bst, d_lo, d_hi, d_readtb, d_dpsegs, d_segs,
-        d_win, d_absz, d_sv_in, d_samp, d_stall, d_lastrow, d_startvals, d_smoves,
-        d_moves, d_dscr, d_wide, d_stat, d_order, d_long,
-        d_stall_csum, d_stall_bits;  // the stall detector's own scratch (it runs beside event detection)
-    PinBuf h_order;               // read indices by decreasing length (k_dp_multi's grouping)
-    PinBuf h_long;                // indices of the long reads (k_long.h)
+#define DEVBUF_MEMBER(name_) DevBuf name_
+    TBA_ENGINE_DEVBUFS(DEVBUF_MEMBER)
+    template <class F> void for_each_devbuf(F f) { TBA_ENGINE_DEVBUFS(f) }
+    PinBuf h_order, h_long;       // d_order / d_long as uploaded (pinned)
     i64 n_long = 0;
     void release_all()
     {
-        DevBuf *all[] = {&d_rs, &d_dp, &d_kmeans, &d_ksds, &d_raw, &d_norm, &d_norm_out, &d_csum,
-                         &d_score, &d_state, &d_cpts, &d_evm, &d_seq, &d_refm, &d_refs, &d_bst,
-                         &d_lo, &d_hi, &d_readtb, &d_dpsegs, &d_segs, &d_win, &d_absz,
-                         &d_sv_in, &d_samp, &d_stall, &d_lastrow, &d_startvals, &d_smoves,
-                         &d_moves, &d_dscr, &d_wide, &d_stat, &d_res, &d_segs32, &d_skipq, &d_order, &d_long,
-                         &d_stall_csum, &d_stall_bits};
-        for (DevBuf *b : all) b->release();
-        h_order.release();
-        h_long.release();
-        h_rs.release();
-        h_dp.release();
+        for_each_devbuf([](DevBuf &b) { b.release(); });
+        for (PinBuf *h : {&h_order, &h_long, &h_rs, &h_dp}) h->release();
     }
 };
 
@@ -163,21 +153,15 @@ extern "C" const char *tba_last_error(void) { return g_last_error.c_str(); }
 extern "C" int tba_device_count(void)
 {
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
+    return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
 }
 
-// engines alive per device in this process: the side stream (enqueue_stages) is only used while the
+// engines alive per device in this process: the side stream (run_prelude) is only used while the
 // process's streams fit the device's hardware queues (four by default) -- beyond that streams share
 // a queue, and a side stream queued behind ANOTHER engine's half-second forward pass holds its own
 // engine's main stream at the join (measured: eight resident long-tail batches 37.8 k -> 31.4 k reads/s)
 #define TBA_MAX_DEVICES 64
 static std::atomic<int> g_live_engines[TBA_MAX_DEVICES];
-static int side_stream_max_engines()
-{
-    static const int v = [] { const char *x = getenv("TBA_SIDE_STREAM_MAX_ENGINES"); return x ? atoi(x) : 2; }();
-    return v;
-}
 
 extern "C" int tba_engine_create(int device, tba_engine **out)
 {
@@ -273,16 +257,8 @@ extern "C" int tba_pinned_free(void *p)
     } while (0)
 
 // ---- batch sizing -----------------------------------------------------------------------------
-// Everything the device buffers of a batch depend on, from the per-read lengths alone (shared by
-// tba_batch_upload_async and tba_batch_footprint).
+// (BatchSizes: shared by tba_batch_upload_async and tba_batch_footprint)
 static size_t raw_elem_bytes(int dt) { return dt == TBA_RAW_I16 ? 2 : dt == TBA_RAW_F32 ? 4 : 8; }
-
-struct BatchSizes {
-    i64 S_tot = 0, seq_tot = 0, B_tot = 0, E_tot = 0, max_raw = 0, max_B = 0, max_nev = 0;
-    i64 moves_need = 0, start_moves_stride = 0, moves_arena = 0, skip_arena = 0, wide_w = 0;
-    i64 n_stall = 0;
-    double algo_bytes = 0, cells = 0;
-};
 
 // per-read geometry; rs may be NULL (footprint only).  Returns 0 or TBA_E_ARG.
 static int plan_batch(const tba_params *p, const tba_opts *o, i64 K, i64 n, const i64 *raw_off,
@@ -365,8 +341,7 @@ static void for_each_batch_buffer(tba_engine *e, const tba_params *p, const tba_
 {
     const size_t S = (size_t)std::max<i64>(z.S_tot, 1), Bt = (size_t)std::max<i64>(z.B_tot, 1),
                  Et = (size_t)std::max<i64>(z.E_tot, 1), N = (size_t)n;
-    tba_engine *q = e; // q == NULL: sizes only
-#define BUF(name_, bytes_) f(q ? &q->name_ : (DevBuf *)nullptr, (size_t)(bytes_))
+#define BUF(name_, bytes_) f(e ? &e->name_ : (DevBuf *)nullptr, (size_t)(bytes_)) // (e == NULL: sizes only)
     BUF(d_rs, N * sizeof(ReadState));
     BUF(d_dp, sizeof(DevParams));
     // (+ 64 bytes: the 16-byte accesses of a pass over a signal may touch the element past an odd end)
@@ -479,9 +454,7 @@ extern "C" int tba_batch_upload_async(tba_engine *e, const tba_params *p, const 
     HIP_TRY(hipSetDevice(e->device));
     // the previous batch of this engine must be done with the buffers (and with h_rs)
     HIP_TRY(hipStreamSynchronize(e->stream));
-    e->have_batch = false;
-    e->ran = false;
-    e->finished = false;
+    e->have_batch = e->ran = e->finished = false;
     e->hp.p = *p;
     e->hp.o = *o;
     e->hp.fill_masked = (MASK_FILL_Z_SCORE - p->z_shift) + p->z_shift;
@@ -492,22 +465,14 @@ extern "C" int tba_batch_upload_async(tba_engine *e, const tba_params *p, const 
     }
     const i64 n = n_reads;
     if (e->h_rs.ensure((size_t)n * sizeof(ReadState)) || e->h_dp.ensure(sizeof(DevParams))) return TBA_E_NOMEM;
-    BatchSizes z;
+    BatchSizes &z = e->z = BatchSizes();
     if (int rc = plan_batch(p, o, e->hp.kmer_width, n, raw_off, nullptr, seq_off, nullptr, ne_override,
                             sv_flags, stalls ? stall_off : nullptr, e->h_rs.as<ReadState>(), z))
         return rc;
-    e->n_reads = n;
-    e->S_tot = z.S_tot; e->seq_tot = z.seq_tot; e->B_tot = z.B_tot; e->E_tot = z.E_tot;
-    e->max_raw = z.max_raw; e->max_B = z.max_B; e->wide_w = z.wide_w;
-    e->algo_bytes = z.algo_bytes; e->dp_cells = z.cells;
+    e->n_reads = n, e->raw_dtype = raw_dtype;
     e->any_stall = (stalls && stall_off[n] > 0) || o->detect_stalls;
-    e->n_stall_cap = z.n_stall;
     e->have_samp = samp_ind != nullptr;
     e->have_sv = sv_in != nullptr && sv_flags != nullptr;
-    e->start_moves_stride = z.start_moves_stride;
-    e->moves_arena = z.moves_arena;
-    e->skip_arena = z.skip_arena;
-    e->raw_dtype = raw_dtype;
     int rc = 0;
     for_each_batch_buffer(e, p, o, n, z, raw_dtype, [&](DevBuf *b, size_t bytes) { rc |= b->ensure(bytes); });
     if (rc) return TBA_E_NOMEM;
@@ -533,8 +498,8 @@ extern "C" int tba_batch_upload_async(tba_engine *e, const tba_params *p, const 
     HIP_TRY(hipMemcpyAsync(e->d_rs.p, e->h_rs.p, N * sizeof(ReadState), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(e->d_dp.p, e->h_dp.p, sizeof(DevParams), hipMemcpyHostToDevice, s));
     // (raw / seq may be device memory -- a batch made by tba_synth_generate: the kind is taken from the pointer)
-    HIP_TRY(hipMemcpyAsync(e->d_raw.p, raw, (size_t)e->S_tot * raw_elem_bytes(raw_dtype), hipMemcpyDefault, s));
-    HIP_TRY(hipMemcpyAsync(e->d_seq.p, seq, (size_t)e->seq_tot, hipMemcpyDefault, s));
+    HIP_TRY(hipMemcpyAsync(e->d_raw.p, raw, (size_t)z.S_tot * raw_elem_bytes(raw_dtype), hipMemcpyDefault, s));
+    HIP_TRY(hipMemcpyAsync(e->d_seq.p, seq, (size_t)z.seq_tot, hipMemcpyDefault, s));
     if (e->have_sv) HIP_TRY(hipMemcpyAsync(e->d_sv_in.p, sv_in, N * 32, hipMemcpyHostToDevice, s));
     if (e->have_samp)
         HIP_TRY(hipMemcpyAsync(e->d_samp.p, samp_ind, N * MAX_TS_POINTS * 8, hipMemcpyHostToDevice, s));
@@ -555,9 +520,8 @@ extern "C" int tba_batch_upload(tba_engine *e, const tba_params *p, const tba_op
                                 const int32_t *sv_flags, const int64_t *samp_ind,
                                 const int64_t *stall_ints, const int64_t *stall_off)
 {
-    int rc = tba_batch_upload_async(e, p, o, n_reads, raw, TBA_RAW_F64, raw_off, seq, seq_off, sv_in,
-                                    sv_flags, samp_ind, stall_ints, stall_off);
-    if (rc) return rc;
+    if (int rc = tba_batch_upload_async(e, p, o, n_reads, raw, TBA_RAW_F64, raw_off, seq, seq_off, sv_in,
+                                        sv_flags, samp_ind, stall_ints, stall_off)) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     return 0;
 }
@@ -573,36 +537,67 @@ extern "C" int tba_set_num_events(tba_engine *e, const int64_t *num_events, int6
 // k_dp<8> or its 112-register build (k_dp.h): the latter when other engines run their kernels beside
 // this one (streaming slots) and the batch has more than 0.04 samples per DP cell, i.e. event
 // detection and normalisation, not the DP, are most of the work (RNA 3 kb: 0.087, DNA 10 kb: 0.018)
-static bool dp_lowreg(const tba_engine *e)
-{
-    return e->n_sharing > 1 && e->dp_cells > 0 && (double)e->S_tot > 0.04 * e->dp_cells;
-}
+static bool dp_lowreg(const tba_engine *e) { return e->n_sharing > 1 && e->z.cells > 0 && (double)e->z.S_tot > 0.04 * e->z.cells; }
+
+// ---- the pipeline -----------------------------------------------------------------------------
+// One run over the uploaded batch, as its steps see it: the engine, its streams, the grid sizes, the kernel
+// forms, and the device buffers as typed pointers (each cast made here, once).
+struct Run {
+    tba_engine *const e;
+    const tba_params &P = e->hp.p;
+    const tba_opts &O = e->hp.o;
+    const hipStream_t s = e->stream;
+    hipStream_t s2 = s; // (run_prelude) the side stream of a full run, else the main stream
+    bool side = false;  // ... which implies the whole stage range
+    const i64 n = e->n_reads;
+    const unsigned nb = (unsigned)n, tpr = (unsigned)((n + 63) / 64); // (tpr: blocks for thread-per-read kernels)
+    // workgroups per read of the (blocks, reads) kernels: 256 items per workgroup when the batch is
+    // small (parallelism), up to 4096 when the reads alone fill the machine -- short-lived
+    // workgroups cost more in launches than they win in balance (RNA, 10 k reads: 113 -> 107 ms)
+    unsigned gx(i64 items) const
+    {
+        const i64 fine = (items + 255) / 256, coarse = (items + 4095) / 4096;
+        const i64 want = (16384 + n - 1) / n; // enough workgroups in all for ~8 per CU-slot
+        return (unsigned)std::min<i64>(std::max<i64>(std::max<i64>(coarse, std::min<i64>(fine, want)), 1), 128);
+    }
+    const unsigned gS = gx(e->z.max_raw), gB = gx(e->z.max_B), gE = gx(e->z.max_raw / std::max<i64>(P.mean_obs_per_event, 1) + 1);
+    const bool rna = P.use_t_test_seg != 0;
+    const bool fused_scores = 2 * P.running_stat_width <= 64; // cumsum + scores in one kernel
+    // DNA defaults: the scores never reach memory (k_detect.h); what that form leaves (flagged reads)
+    // goes through the kernels of the other forms as before
+    const bool fused_detect = !rna && 2 * P.running_stat_width <= DT_W2MAX && P.min_obs_per_base == 3;
+    // A handful of reads cannot hide the scan's serial chain behind each other: k_detect /
+    // k_cumsum_scores pay a pipeline step (barrier, memory round trip, greedy: ~7 us) per 128 samples
+    // whatever the batch, 5 ms for a 10 kb read; a workgroup per read (k_long.h: the step is 1 856
+    // dependent adds long) does the same in 0.5 ms.  (resquiggle_read, a batch of one: 20.4 -> 16 ms.)
+    const bool wg_scan = !rna && fused_scores && n <= e->small_batch && (size_t)n * 4 <= e->d_order.cap;
+    const bool fused_tt = rna && P.min_obs_per_base == 6 && P.running_stat_width <= TT_MAXW; // RNA defaults: radius 5
+    const int only_flagged = (fused_detect && !wg_scan) || fused_tt ? 1 : 0;
+    const int rdt = e->raw_dtype;
+    void *raw = e->d_raw.p; // samples of that type: (RT *) under RAW_DISPATCH(c.rdt, ...)
+    ReadState *rs = e->d_rs.as<ReadState>();
+    const DevParams *dp = e->d_dp.as<DevParams>();
+    uint8_t *seq = e->d_seq.as<uint8_t>();
+    unsigned char *state = e->d_state.as<unsigned char>(), *smoves = e->d_smoves.as<unsigned char>(), *moves = e->d_moves.as<unsigned char>();
+    i32 *order = e->d_order.as<i32>(), *lng = e->d_long.as<i32>(), *lo = e->d_lo.as<i32>(), *hi = e->d_hi.as<i32>();
+    i64 *cpts = e->d_cpts.as<i64>(), *samp = e->d_samp.as<i64>(), *stall = e->d_stall.as<i64>(), *bst = e->d_bst.as<i64>(), *readtb = e->d_readtb.as<i64>(),
+        *dpsegs = e->d_dpsegs.as<i64>(), *segs = e->d_segs.as<i64>(), *win = e->d_win.as<i64>(), *skipq = e->d_skipq.as<i64>();
+    u64 *stall_bits = e->d_stall_bits.as<u64>();
+    double *kmeans = e->d_kmeans.as<double>(), *ksds = e->d_ksds.as<double>(), *sv_in = e->d_sv_in.as<double>(), *norm = e->d_norm.as<double>(),
+           *norm_out = e->d_norm_out.as<double>(), *csum = e->d_csum.as<double>(), *score = e->d_score.as<double>(), *evm = e->d_evm.as<double>(),
+           *refm = e->d_refm.as<double>(), *refs = e->d_refs.as<double>(), *lastrow = e->d_lastrow.as<double>(), *startvals = e->d_startvals.as<double>(),
+           *wide = e->d_wide.as<double>(), *dscr = e->d_dscr.as<double>(), *absz = e->d_absz.as<double>(), *stall_csum = e->d_stall_csum.as<double>();
+};
 template <int CPL>
-static void launch_dp_t(tba_engine *e, int mode)
+static void launch_dp_t(Run &c, int mode)
 {
-#define DP_LAUNCH_ARGS e->d_rs.as<ReadState>(), e->d_dp.as<DevParams>(), mode, e->d_evm.as<double>(), \
-        e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_bst.as<i64>(), e->d_lo.as<i32>(), \
-        e->d_hi.as<i32>(), \
-        mode == DP_MAIN ? e->d_moves.as<unsigned char>() : e->d_smoves.as<unsigned char>(), \
-        e->start_moves_stride, e->d_lastrow.as<double>(), nullptr
-    if (CPL == 8 && mode == DP_MAIN && dp_lowreg(e))
-        k_dp8_lowreg<<<dim3((unsigned)e->n_reads), dim3(64), 0, e->stream>>>(DP_LAUNCH_ARGS);
-    else
-        k_dp<CPL, false><<<dim3((unsigned)e->n_reads), dim3(64), 0, e->stream>>>(DP_LAUNCH_ARGS);
-#undef DP_LAUNCH_ARGS
+    const auto k = CPL == 8 && mode == DP_MAIN && dp_lowreg(c.e) ? k_dp8_lowreg : k_dp<CPL, false>;
+    k<<<dim3(c.nb), dim3(64), 0, c.s>>>(c.rs, c.dp, mode, c.evm, c.refm, c.refs, c.bst, c.lo, c.hi, mode == DP_MAIN ? c.moves : c.smoves, c.e->z.start_moves_stride, c.lastrow, nullptr);
 }
 template <int CPL, int RPW>
-static void launch_dp_multi_t(tba_engine *e)
+static void launch_dp_multi_t(Run &c)
 {
-    k_dp_multi<CPL, RPW><<<dim3((unsigned)((e->n_reads + RPW - 1) / RPW)), dim3(64), 0, e->stream>>>(
-        e->d_rs.as<ReadState>(), e->n_reads, e->d_order.as<i32>(), e->d_dp.as<DevParams>(),
-        e->d_evm.as<double>(), e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_bst.as<i64>(),
-        e->d_lo.as<i32>(), e->d_hi.as<i32>(), e->d_moves.as<unsigned char>(), e->d_lastrow.as<double>());
-}
-static void launch_dp_multi(tba_engine *e)
-{
-    const DpMultiClass c = dp_multi_class(e->hp.p.bandwidth);
-    if (c.cpl == 4 && c.rpw == 2) launch_dp_multi_t<4, 2>(e);
+    k_dp_multi<CPL, RPW><<<dim3((unsigned)((c.n + RPW - 1) / RPW)), dim3(64), 0, c.s>>>(c.rs, c.n, c.order, c.dp, c.evm, c.refm, c.refs, c.bst, c.lo, c.hi, c.moves, c.lastrow);
 }
 // the band classes of k_dp (cpl_class, k_dp.h): `list` in the order the main DP launches them;
 // dispatch(cpl, f) calls f(std::integral_constant<int, CPL>()) for the run-time class (nothing for 0)
@@ -616,257 +611,278 @@ struct CplClasses {
 };
 typedef CplClasses<4, 5, 8, 12, 16, 24, 32, 48> DpClasses;
 
-static void launch_dp(tba_engine *e, int cpl, int mode)
-{
-    DpClasses::dispatch(cpl, [&](auto c) { launch_dp_t<decltype(c)::value>(e, mode); });
-}
+static void launch_dp(Run &c, int cpl, int mode) { DpClasses::dispatch(cpl, [&](auto cls) { launch_dp_t<decltype(cls)::value>(c, mode); }); }
 
-static int enqueue_stages(tba_engine *e, int first, int last)
+// Before the first step: a run from the top starts from the uploaded state; the `total` bracket opens; a
+// full run forks the side stream, which takes stall detection and the expected levels.
+static int run_prelude(Run &c, int first, int last)
 {
-    if (!e || !e->have_batch) return set_err(TBA_E_STATE, "no batch uploaded");
-    if (first < 0 || last > TBA_STAGE_RESCALE || first > last) return set_err(TBA_E_ARG, "bad stage range");
-    if (first > 0 && !e->ran) return set_err(TBA_E_STATE, "stages before `first` have not been run or injected");
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = e->stream;
-    const i64 n = e->n_reads;
-    const tba_params &P = e->hp.p;
-    ReadState *rs = e->d_rs.as<ReadState>();
-    const DevParams *dp = e->d_dp.as<DevParams>();
+    tba_engine *e = c.e;
+    const hipStream_t s = c.s;
     // starting from the top discards the state of a previous run of the same batch
-    if (first == 0) {
-        HIP_TRY(hipMemcpyAsync(e->d_rs.p, e->h_rs.p, (size_t)n * sizeof(ReadState), hipMemcpyHostToDevice, s));
+    if (first == TBA_STAGE_SEGMENT) {
+        HIP_TRY(hipMemcpyAsync(e->d_rs.p, e->h_rs.p, (size_t)c.n * sizeof(ReadState), hipMemcpyHostToDevice, s));
         e->last_dp = tba_engine::DpLaunches();
     }
-    const unsigned nb = (unsigned)n;
-    const unsigned tpr = (unsigned)((n + 63) / 64); // blocks for thread-per-read kernels
-    // workgroups per read of the (blocks, reads) kernels: 256 items per workgroup when the batch is
-    // small (parallelism), up to 4096 when the reads alone fill the machine -- short-lived
-    // workgroups cost more in launches than they win in balance (RNA, 10 k reads: 113 -> 107 ms)
-    auto gx = [n](i64 items) {
-        const i64 fine = (items + 255) / 256, coarse = (items + 4095) / 4096;
-        const i64 want = (16384 + n - 1) / n; // enough workgroups in all for ~8 per CU-slot
-        const i64 g = std::max<i64>(coarse, std::min<i64>(fine, want));
-        return (unsigned)std::min<i64>(std::max<i64>(g, 1), 128);
-    };
-    const unsigned gS = gx(e->max_raw), gB = gx(e->max_B), gE = gx(e->max_raw / std::max<i64>(P.mean_obs_per_event, 1) + 1);
-    int st = 0;
-#define MARK() HIP_TRY(hipEventRecord(e->ev[st++], s))
-#define ON(stage_) ((stage_) >= first && (stage_) <= last)
-    const bool rna = P.use_t_test_seg != 0;
-    const int rdt = e->raw_dtype;
-    HIP_TRY(hipEventRecord(e->ev[15], s));                 // start of the sequence (the `total` bracket)
+    HIP_TRY(hipEventRecord(e->ev[SLOT_TOTAL], s));         // start of the sequence (the `total` bracket)
     // A full run forks the side stream here (TBA_NO_SIDE_STREAM=1: everything on the main stream, in
     // this order); a partial run (stepwise API) stays on one stream.
     static const bool side_off = getenv("TBA_NO_SIDE_STREAM") != nullptr;
-    const bool side = !side_off && first == TBA_STAGE_SEGMENT && last == TBA_STAGE_RESCALE && e->side_mode != 0 &&
-                      (e->side_mode == 1 || (e->device < TBA_MAX_DEVICES &&
-                       std::max(e->n_sharing, g_live_engines[e->device].load()) <= side_stream_max_engines()));
-    e->last_side = side;
-    if (side && !e->stream2) HIP_TRY(hipStreamCreate(&e->stream2)); // (created on first use: a stream takes a queue slot)
-    hipStream_t s2 = side ? e->stream2 : s;
-    if (side) {
+    static const int max_engines = [] { const char *x = getenv("TBA_SIDE_STREAM_MAX_ENGINES"); return x ? atoi(x) : 2; }();
+    c.side = !side_off && first == TBA_STAGE_SEGMENT && last == TBA_STAGE_RESCALE && e->side_mode != 0 &&
+             (e->side_mode == 1 || (e->device < TBA_MAX_DEVICES &&
+              std::max(e->n_sharing, g_live_engines[e->device].load()) <= max_engines));
+    e->last_side = c.side;
+    if (c.side && !e->stream2) HIP_TRY(hipStreamCreate(&e->stream2)); // (created on first use: a stream takes a queue slot)
+    const hipStream_t s2 = c.s2 = c.side ? e->stream2 : s;
+    if (c.side) {
         HIP_TRY(hipEventRecord(e->ev_fork, s));
         HIP_TRY(hipStreamWaitEvent(s2, e->ev_fork, 0));
     }
     // caller-side preparation: ts.identify_stalls over the raw samples (its own scratch: it runs beside
     // event detection)
     HIP_TRY(hipEventRecord(e->ev_st0, s2));
-    if (ON(TBA_STAGE_SEGMENT) && e->hp.o.detect_stalls) {
-        double *csum = e->d_stall_csum.as<double>();
-        u64 *bits = e->d_stall_bits.as<u64>();
-        const unsigned gq = gx(e->max_raw / 8 + 1); // chunks of SI_T positions
-        if (rdt == TBA_RAW_I16 && e->hp.o.stall_window_size <= SI_MAXW) { // exact integer sums: no cumulative sum in memory
-            if (e->hp.o.stall_n_windows == 7) k_stall_metric_i16<7><<<dim3(gq, nb), 256, 0, s2>>>(rs, dp, e->d_raw.as<int16_t>(), bits);
-            else k_stall_metric_i16<0><<<dim3(gq, nb), 256, 0, s2>>>(rs, dp, e->d_raw.as<int16_t>(), bits);
+    if (first == TBA_STAGE_SEGMENT && c.O.detect_stalls) {
+        const unsigned gq = c.gx(e->z.max_raw / 8 + 1); // chunks of SI_T positions
+        if (c.rdt == TBA_RAW_I16 && c.O.stall_window_size <= SI_MAXW) { // exact integer sums: no cumulative sum in memory
+            (c.O.stall_n_windows == 7 ? k_stall_metric_i16<7> : k_stall_metric_i16<0>)<<<dim3(gq, c.nb), 256, 0, s2>>>(c.rs, c.dp, (int16_t *)c.raw, c.stall_bits);
         } else {
-        if (cs_reads_for(n) == 20) RAW_DISPATCH(rdt, (k_cumsum_scores<20, RT, 1><<<(unsigned)((n + 19) / 20), 256, 0, s2>>>(rs, n, dp, e->d_raw.as<RT>(), csum)));
-        else RAW_DISPATCH(rdt, (k_cumsum_scores<32, RT, 1><<<(unsigned)((n + 31) / 32), 256, 0, s2>>>(rs, n, dp, e->d_raw.as<RT>(), csum)));
-        if (e->n_long > 0) RAW_DISPATCH(rdt, (k_cumsum_scores_long<RT, 1><<<(unsigned)e->n_long, 256, 0, s2>>>(rs, e->d_long.as<i32>(), dp, e->d_raw.as<RT>(), csum)));
-        if (e->hp.o.stall_n_windows == 7) k_stall_metric<7><<<dim3(gq, nb), 256, 0, s2>>>(rs, dp, csum, bits);
-        else k_stall_metric<0><<<dim3(gq, nb), 256, 0, s2>>>(rs, dp, csum, bits);
+            if (cs_reads_for(c.n) == 20) RAW_DISPATCH(c.rdt, (k_cumsum_scores<20, RT, 1><<<(unsigned)((c.n + 19) / 20), 256, 0, s2>>>(c.rs, c.n, c.dp, (RT *)c.raw, c.stall_csum)));
+            else RAW_DISPATCH(c.rdt, (k_cumsum_scores<32, RT, 1><<<(unsigned)((c.n + 31) / 32), 256, 0, s2>>>(c.rs, c.n, c.dp, (RT *)c.raw, c.stall_csum)));
+            if (e->n_long > 0) RAW_DISPATCH(c.rdt, (k_cumsum_scores_long<RT, 1><<<(unsigned)e->n_long, 256, 0, s2>>>(c.rs, c.lng, c.dp, (RT *)c.raw, c.stall_csum)));
+            (c.O.stall_n_windows == 7 ? k_stall_metric<7> : k_stall_metric<0>)<<<dim3(gq, c.nb), 256, 0, s2>>>(c.rs, c.dp, c.stall_csum, c.stall_bits);
         }
-        k_stall_runs<<<dim3(gx(e->max_raw / 64 + 1), nb), 256, 0, s2>>>(rs, dp, bits, e->d_stall.as<i64>());
-        k_stall_merge<<<tpr, 64, 0, s2>>>(rs, n, dp, e->d_stall.as<i64>());
+        k_stall_runs<<<dim3(c.gx(e->z.max_raw / 64 + 1), c.nb), 256, 0, s2>>>(c.rs, c.dp, c.stall_bits, c.stall);
+        k_stall_merge<<<c.tpr, 64, 0, s2>>>(c.rs, c.n, c.dp, c.stall);
     }
     HIP_TRY(hipEventRecord(e->ev_st1, s2));
-    if (side) {
+    if (c.side) {
         HIP_TRY(hipEventRecord(e->ev_stalls, s2));
         // the expected levels need the sequence and the model only
-        k_ref_levels<<<dim3(gB, nb), 256, 0, s2>>>(rs, dp, e->d_seq.as<uint8_t>(), e->d_kmeans.as<double>(), e->d_ksds.as<double>(), e->d_refm.as<double>(), e->d_refs.as<double>(), 1);
+        k_ref_levels<<<dim3(c.gB, c.nb), 256, 0, s2>>>(c.rs, c.dp, c.seq, c.kmeans, c.ksds, c.refm, c.refs, 1);
         HIP_TRY(hipEventRecord(e->ev_levels, s2));
     }
-    MARK(); // 0 normalize
-    const bool fused_scores = 2 * P.running_stat_width <= 64; // cumsum + scores in one kernel
-    // DNA defaults: the scores never reach memory (k_detect.h); what that form leaves (flagged reads)
-    // goes through the kernels below as before
-    const bool fused_detect = !rna && 2 * P.running_stat_width <= DT_W2MAX && P.min_obs_per_base == 3;
-    // A handful of reads cannot hide the scan's serial chain behind each other: k_detect /
-    // k_cumsum_scores pay a pipeline step (barrier, memory round trip, greedy: ~7 us) per 128 samples
-    // whatever the batch, 5 ms for a 10 kb read; a workgroup per read (k_long.h: the step is 1 856
-    // dependent adds long) does the same in 0.5 ms.  (resquiggle_read, a batch of one: 20.4 -> 16 ms.)
-    const bool wg_scan = !rna && fused_scores && n <= e->small_batch && (size_t)n * 4 <= e->d_order.cap;
-    const bool fused_tt = rna && P.min_obs_per_base == 6 && P.running_stat_width <= TT_MAXW; // RNA defaults: radius 5
-    const int only_flagged = (fused_detect && !wg_scan) || fused_tt ? 1 : 0;
+    return 0;
+}
+
+// The steps: what runs between the timing events ev[i] and ev[i + 1], in the order of STEPS below.
+static int step_normalize(Run &c)
+{
     // (with k_detect on the way its loader writes the normalised signal: k_normalize only finds the
     // scale values then, and normalises the long reads, which k_detect leaves to k_long.h)
-    if (ON(TBA_STAGE_SEGMENT) && !rna)
-        RAW_DISPATCH(rdt, (k_normalize<RT><<<nb, SEL_NT, 0, s>>>(rs, dp, e->d_raw.as<RT>(), e->d_norm.as<double>(), e->d_sv_in.as<double>(), 0, fused_detect && !wg_scan ? 2 : 1)));
-    MARK(); // 1 cumsum
-    if (ON(TBA_STAGE_SEGMENT) && !rna && wg_scan) {
-        k_cumsum_scores_long<double, 0><<<nb, 256, 0, s>>>(rs, e->d_order.as<i32>(), dp, e->d_norm.as<double>(), e->d_score.as<double>());
-    } else if (ON(TBA_STAGE_SEGMENT) && !rna) {
-        if (fused_detect) {
-            RAW_DISPATCH(rdt, (k_detect<2, RT><<<(unsigned)((n + DT_READS - 1) / DT_READS), 256, 0, s>>>(rs, n, dp, e->d_raw.as<RT>(), e->d_norm.as<double>(), e->d_csum.as<double>(), e->d_score.as<double>(), e->S_tot)));
-            k_pick<<<nb, SEL_NT, 0, s>>>(rs, dp, e->d_csum.as<double>(), e->d_score.as<double>(), e->d_cpts.as<i64>(), 0);
-        }
-        if (fused_scores) {
-            if (cs_reads_for(n) == 20) k_cumsum_scores<20><<<(unsigned)((n + 19) / 20), 256, 0, s>>>(rs, n, dp, e->d_norm.as<double>(), e->d_score.as<double>(), only_flagged);
-            else k_cumsum_scores<32><<<(unsigned)((n + 31) / 32), 256, 0, s>>>(rs, n, dp, e->d_norm.as<double>(), e->d_score.as<double>(), only_flagged);
-            if (e->n_long > 0) k_cumsum_scores_long<double, 0><<<(unsigned)e->n_long, 256, 0, s>>>(rs, e->d_long.as<i32>(), dp, e->d_norm.as<double>(), e->d_score.as<double>());
-        }
-        else k_cumsum<<<tpr, 64, 0, s>>>(rs, n, e->d_norm.as<double>(), e->d_csum.as<double>());
+    if (!c.rna) RAW_DISPATCH(c.rdt, (k_normalize<RT><<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, (RT *)c.raw, c.norm, c.sv_in, 0, c.fused_detect && !c.wg_scan ? 2 : 1)));
+    return 0;
+}
+static int step_cumsum(Run &c)
+{
+    const i64 n = c.n;
+    if (c.rna) return 0;
+    if (c.wg_scan) {
+        k_cumsum_scores_long<double, 0><<<c.nb, 256, 0, c.s>>>(c.rs, c.order, c.dp, c.norm, c.score);
+        return 0;
     }
-    MARK(); // 2 scores
-    if (ON(TBA_STAGE_SEGMENT)) {
-        if (!rna) { if (!fused_scores) k_scores_dna<<<dim3(gS, nb), 256, 0, s>>>(rs, dp, e->d_csum.as<double>(), e->d_score.as<double>()); }
-        else {
-            if (fused_tt) {
-                if (P.running_stat_width == 12) RAW_DISPATCH(rdt, (k_detect_tt<5, 12, RT><<<nb, SEL_NT, 0, s>>>(rs, dp, e->d_raw.as<RT>(), e->d_csum.as<double>(), e->d_score.as<double>())));
-                else RAW_DISPATCH(rdt, (k_detect_tt<5, 0, RT><<<nb, SEL_NT, 0, s>>>(rs, dp, e->d_raw.as<RT>(), e->d_csum.as<double>(), e->d_score.as<double>())));
-                k_pick<<<nb, SEL_NT, 0, s>>>(rs, dp, e->d_csum.as<double>(), e->d_score.as<double>(), e->d_cpts.as<i64>(), 1);
-            }
-            RAW_DISPATCH(rdt, (k_scores_ttest<RT><<<dim3(gS, nb), 256, 0, s>>>(rs, dp, e->d_raw.as<RT>(), e->d_score.as<double>(), only_flagged)));
-        }
+    if (c.fused_detect) {
+        RAW_DISPATCH(c.rdt, (k_detect<2, RT><<<(unsigned)((n + DT_READS - 1) / DT_READS), 256, 0, c.s>>>(c.rs, n, c.dp, (RT *)c.raw, c.norm, c.csum, c.score, c.e->z.S_tot)));
+        k_pick<<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, c.csum, c.score, c.cpts, 0);
     }
-    MARK(); // 3 peaks
-    if (ON(TBA_STAGE_SEGMENT)) {
-        launch_peaks(P.min_obs_per_base, nb, s, rs, dp, e->d_score.as<double>(), e->d_state.as<unsigned char>(), e->d_csum.as<double>(), e->d_cpts.as<i64>(), rna ? 1 : 0, only_flagged,
-                     rna ? TBA_ED_FORM_TTEST_PEAKS : wg_scan ? TBA_ED_FORM_WG_SCAN_PEAKS : TBA_ED_FORM_SCORES_PEAKS);
-        if (side) HIP_TRY(hipStreamWaitEvent(s, e->ev_stalls, 0)); // the stall intervals (and nothing else of the side stream)
-        if (e->any_stall) k_remove_stalls<<<nb, SEL_NT, 0, s>>>(rs, n, e->d_stall.as<i64>(), e->d_cpts.as<i64>(), e->d_csum.as<double>());
-        if (rna) { // RNA normalises after event detection (segment_signal, resquiggle.py:1073-1098)
-            RAW_DISPATCH(rdt, (k_event_means<RT, 1280><<<dim3(gE, nb), 256, 0, s>>>(rs, dp, e->d_raw.as<RT>(), e->d_cpts.as<i64>(), e->d_evm.as<double>(), 1)));
-            k_rna_event_scale<<<nb, SEL_NT, 0, s>>>(rs, dp, e->d_evm.as<double>());
-            RAW_DISPATCH(rdt, (k_normalize<RT><<<nb, SEL_NT, 0, s>>>(rs, dp, e->d_raw.as<RT>(), e->d_norm.as<double>(), e->d_sv_in.as<double>(), 1, 1)));
-        }
+    if (c.fused_scores) {
+        if (cs_reads_for(n) == 20) k_cumsum_scores<20><<<(unsigned)((n + 19) / 20), 256, 0, c.s>>>(c.rs, n, c.dp, c.norm, c.score, c.only_flagged);
+        else k_cumsum_scores<32><<<(unsigned)((n + 31) / 32), 256, 0, c.s>>>(c.rs, n, c.dp, c.norm, c.score, c.only_flagged);
+        if (c.e->n_long > 0) k_cumsum_scores_long<double, 0><<<(unsigned)c.e->n_long, 256, 0, c.s>>>(c.rs, c.lng, c.dp, c.norm, c.score);
     }
-    MARK(); // 4 event means
-    if (ON(TBA_STAGE_EVENT_MEANS)) {
-        // long events (RNA: mean_obs_per_event 15): the wide staging slice
-        if (P.mean_obs_per_event >= 10) k_event_means<double, 1280><<<dim3(gE, nb), 256, 0, s>>>(rs, dp, e->d_norm.as<double>(), e->d_cpts.as<i64>(), e->d_evm.as<double>(), 0);
-        else k_event_means<double><<<dim3(gE, nb), 256, 0, s>>>(rs, dp, e->d_norm.as<double>(), e->d_cpts.as<i64>(), e->d_evm.as<double>(), 0);
+    else k_cumsum<<<c.tpr, 64, 0, c.s>>>(c.rs, n, c.norm, c.csum);
+    return 0;
+}
+static int step_scores(Run &c)
+{
+    if (!c.rna) {
+        if (!c.fused_scores) k_scores_dna<<<dim3(c.gS, c.nb), 256, 0, c.s>>>(c.rs, c.dp, c.csum, c.score);
+        return 0;
     }
-    MARK(); // 5 ref levels
-    if (side) {                                                    // (computed on the side stream)
-        HIP_TRY(hipStreamWaitEvent(s, e->ev_levels, 0));
-        k_seq_status<<<tpr, 64, 0, s>>>(rs, n);
-    } else if (ON(TBA_STAGE_REF_LEVELS))
-        k_ref_levels<<<dim3(gB, nb), 256, 0, s>>>(rs, dp, e->d_seq.as<uint8_t>(), e->d_kmeans.as<double>(), e->d_ksds.as<double>(), e->d_refm.as<double>(), e->d_refs.as<double>());
-    MARK(); // 6 start dp (+7 start tb): find_seq_start_in_events, first try then retry
-    if (ON(TBA_STAGE_START)) {
-        k_path0<<<tpr, 64, 0, s>>>(rs, n, dp);
-        launch_dp(e, cpl_class(P.start_bw), DP_START_TRY);
-        k_start_tb<<<(unsigned)((n + TB_LANES - 1) / TB_LANES), TB_LANES, 0, s>>>(rs, n, dp, DP_START_TRY, e->d_evm.as<double>(), e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_smoves.as<unsigned char>(), e->start_moves_stride, e->d_readtb.as<i64>(), e->d_startvals.as<double>());
+    if (c.fused_tt) {
+        if (c.P.running_stat_width == 12) RAW_DISPATCH(c.rdt, (k_detect_tt<5, 12, RT><<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, (RT *)c.raw, c.csum, c.score)));
+        else RAW_DISPATCH(c.rdt, (k_detect_tt<5, 0, RT><<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, (RT *)c.raw, c.csum, c.score)));
+        k_pick<<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, c.csum, c.score, c.cpts, 1);
     }
-    MARK(); // 7
-    if (ON(TBA_STAGE_START)) {
-        // the retry of the few reads whose first try failed: one workgroup per read (k_dp_wg.h)
-        const int wcpl = P.start_n_bases <= WG_MAX_ROWS ? dp_wg_cpl(P.start_save_bw) : 0;
-        e->last_dp.start = true;
-        e->last_dp.retry_wcpl = wcpl;
-#define WG_ARGS rs, dp, e->d_evm.as<double>(), e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_smoves.as<unsigned char>(), e->start_moves_stride, e->d_lastrow.as<double>()
-        if (wcpl == 4) k_dp_wg<4><<<nb, 256, 0, s>>>(WG_ARGS);
-        else if (wcpl == 8) k_dp_wg<8><<<nb, 256, 0, s>>>(WG_ARGS);
-        else if (wcpl == 12) k_dp_wg<12><<<nb, 256, 0, s>>>(WG_ARGS);
-        else launch_dp(e, cpl_class(P.start_save_bw), DP_START_RETRY);
-#undef WG_ARGS
-        k_start_tb<<<(unsigned)((n + TB_LANES - 1) / TB_LANES), TB_LANES, 0, s>>>(rs, n, dp, DP_START_RETRY, e->d_evm.as<double>(), e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_smoves.as<unsigned char>(), e->start_moves_stride, e->d_readtb.as<i64>(), e->d_startvals.as<double>());
+    RAW_DISPATCH(c.rdt, (k_scores_ttest<RT><<<dim3(c.gS, c.nb), 256, 0, c.s>>>(c.rs, c.dp, (RT *)c.raw, c.score, c.only_flagged)));
+    return 0;
+}
+static int step_peaks(Run &c)
+{
+    launch_peaks(c.P.min_obs_per_base, c.nb, c.s, c.rs, c.dp, c.score, c.state, c.csum, c.cpts, c.rna ? 1 : 0, c.only_flagged,
+                 c.rna ? TBA_ED_FORM_TTEST_PEAKS : c.wg_scan ? TBA_ED_FORM_WG_SCAN_PEAKS : TBA_ED_FORM_SCORES_PEAKS);
+    if (c.side) HIP_TRY(hipStreamWaitEvent(c.s, c.e->ev_stalls, 0)); // the stall intervals (and nothing else of the side stream)
+    if (c.e->any_stall) k_remove_stalls<<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.n, c.stall, c.cpts, c.csum);
+    if (c.rna) { // RNA normalises after event detection (segment_signal, resquiggle.py:1073-1098)
+        RAW_DISPATCH(c.rdt, (k_event_means<RT, 1280><<<dim3(c.gE, c.nb), 256, 0, c.s>>>(c.rs, c.dp, (RT *)c.raw, c.cpts, c.evm, 1)));
+        k_rna_event_scale<<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, c.evm);
+        RAW_DISPATCH(c.rdt, (k_normalize<RT><<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, (RT *)c.raw, c.norm, c.sv_in, 1, 1)));
     }
-    MARK(); // 8 prep
-    if (ON(TBA_STAGE_ASSIGN)) {
-        k_prep<<<tpr, 64, 0, s>>>(rs, n, dp, e->d_bst.as<i64>(), e->d_lo.as<i32>(), e->d_hi.as<i32>());
-        k_scan_arena<0><<<1, 256, 0, s>>>(rs, n, e->moves_arena);
-    }
-    MARK(); // 9 main dp
-    if (ON(TBA_STAGE_ASSIGN)) {
-        e->last_dp.main = true;
-        e->last_dp.lowreg = dp_lowreg(e); // (launch_dp_t's choice for the 8-cell class)
-        e->last_dp.wide = e->wide_w != 0;
-        for (int c : DpClasses::list) launch_dp(e, c, DP_MAIN);
-        launch_dp_multi(e); // narrow adaptive bands: several reads per wavefront
-        if (e->wide_w) // a static band wider than every class is possible in this batch
-            k_dp_wide<<<WIDE_BLOCKS, 64, 0, s>>>(rs, n, dp, e->d_evm.as<double>(), e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_bst.as<i64>(), e->d_moves.as<unsigned char>(), e->d_wide.as<double>(), e->wide_w);
-    }
-    MARK(); // 10 main tb
-    if (ON(TBA_STAGE_ASSIGN)) {
-        // rows of a read over several lanes (k_tb_par.h): 16 lanes per read when the reads fill the
-        // machine, a wavefront per read for small batches and for the long reads; what it leaves
-        // (static bands, failed verification) is walked by the lane-per-read kernels below
-        if (n > e->tb_wave_below) k_main_tb_par<16><<<(unsigned)((n + 3) / 4), 64, 0, s>>>(rs, n, nullptr, dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
-        else k_main_tb_par<64><<<nb, 64, 0, s>>>(rs, n, nullptr, dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
-        if (e->n_long > 0 && n > e->tb_wave_below) k_main_tb_par<64><<<(unsigned)e->n_long, 64, 0, s>>>(rs, e->n_long, e->d_long.as<i32>(), dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
+    return 0;
+}
+static int step_event_means(Run &c)
+{
+    // long events (RNA: mean_obs_per_event 15): the wide staging slice
+    (c.P.mean_obs_per_event >= 10 ? k_event_means<double, 1280> : k_event_means<double>)<<<dim3(c.gE, c.nb), 256, 0, c.s>>>(c.rs, c.dp, c.norm, c.cpts, c.evm, 0);
+    return 0;
+}
+static int step_ref_levels(Run &c)
+{
+    if (c.side) {                                                  // (computed on the side stream)
+        HIP_TRY(hipStreamWaitEvent(c.s, c.e->ev_levels, 0));
+        k_seq_status<<<c.tpr, 64, 0, c.s>>>(c.rs, c.n);
+    } else
+        k_ref_levels<<<dim3(c.gB, c.nb), 256, 0, c.s>>>(c.rs, c.dp, c.seq, c.kmeans, c.ksds, c.refm, c.refs);
+    return 0;
+}
+static void launch_start_tb(Run &c, int mode)
+{
+    k_start_tb<<<(unsigned)((c.n + TB_LANES - 1) / TB_LANES), TB_LANES, 0, c.s>>>(c.rs, c.n, c.dp, mode, c.evm, c.refm, c.refs, c.smoves, c.e->z.start_moves_stride, c.readtb, c.startvals);
+}
+// start_dp + start_tb: find_seq_start_in_events, first try then retry
+static int step_start_dp(Run &c)
+{
+    k_path0<<<c.tpr, 64, 0, c.s>>>(c.rs, c.n, c.dp);
+    launch_dp(c, cpl_class(c.P.start_bw), DP_START_TRY);
+    launch_start_tb(c, DP_START_TRY);
+    return 0;
+}
+static int step_start_tb(Run &c)
+{
+    // the retry of the few reads whose first try failed: one workgroup per read (k_dp_wg.h)
+    const int wcpl = c.P.start_n_bases <= WG_MAX_ROWS ? dp_wg_cpl(c.P.start_save_bw) : 0;
+    c.e->last_dp.start = true, c.e->last_dp.retry_wcpl = wcpl;
+    const auto wg = wcpl == 4 ? k_dp_wg<4> : wcpl == 8 ? k_dp_wg<8> : wcpl == 12 ? k_dp_wg<12> : nullptr;
+    if (wg) wg<<<c.nb, 256, 0, c.s>>>(c.rs, c.dp, c.evm, c.refm, c.refs, c.smoves, c.e->z.start_moves_stride, c.lastrow);
+    else launch_dp(c, cpl_class(c.P.start_save_bw), DP_START_RETRY);
+    launch_start_tb(c, DP_START_RETRY);
+    return 0;
+}
+static int step_prep(Run &c)
+{
+    k_prep<<<c.tpr, 64, 0, c.s>>>(c.rs, c.n, c.dp, c.bst, c.lo, c.hi);
+    k_scan_arena<0><<<1, 256, 0, c.s>>>(c.rs, c.n, c.e->z.moves_arena);
+    return 0;
+}
+static int step_main_dp(Run &c)
+{
+    const i64 wide_w = c.e->z.wide_w;
+    c.e->last_dp.main = true, c.e->last_dp.wide = wide_w != 0;
+    c.e->last_dp.lowreg = dp_lowreg(c.e); // (launch_dp_t's choice for the 8-cell class)
+    for (int cls : DpClasses::list) launch_dp(c, cls, DP_MAIN);
+    const DpMultiClass m = dp_multi_class(c.P.bandwidth); // narrow adaptive bands: several reads per wavefront
+    if (m.cpl == 4 && m.rpw == 2) launch_dp_multi_t<4, 2>(c);
+    if (wide_w) // a static band wider than every class is possible in this batch
+        k_dp_wide<<<WIDE_BLOCKS, 64, 0, c.s>>>(c.rs, c.n, c.dp, c.evm, c.refm, c.refs, c.bst, c.moves, c.wide, wide_w);
+    return 0;
+}
+static int step_main_tb(Run &c)
+{
+    const i64 n = c.n, n_long = c.e->n_long;
+    // rows of a read over several lanes (k_tb_par.h): 16 lanes per read when the reads fill the
+    // machine, a wavefront per read for small batches and for the long reads; what it leaves
+    // (static bands, failed verification) is walked by the lane-per-read kernels below
+    const bool lanes16 = n > c.e->tb_wave_below;
+    auto per_chunk = [&](auto k16, auto k64) {
+        if (lanes16) k16<<<(unsigned)((n + 3) / 4), 64, 0, c.s>>>(c.rs, n, nullptr, c.dp, c.moves, c.bst, c.readtb);
+        else k64<<<c.nb, 64, 0, c.s>>>(c.rs, n, nullptr, c.dp, c.moves, c.bst, c.readtb);
+        if (n_long > 0 && lanes16) k64<<<(unsigned)n_long, 64, 0, c.s>>>(c.rs, n_long, c.lng, c.dp, c.moves, c.bst, c.readtb);
+    };
+    per_chunk(k_main_tb_par<16>, k_main_tb_par<64>);
 #ifndef TBA_NO_TB_VERIFY
-        // behind the kernel boundary: the first block of rows under every chunk top walked again, compare
-        // only; what disagrees is the serial kernels' (counted: TBA_GET_TB_VERIFY_FAIL), the rest is trimmed
-        if (n > e->tb_wave_below) k_tb_par_verify<16><<<(unsigned)((n + 3) / 4), 64, 0, s>>>(rs, n, nullptr, dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
-        else k_tb_par_verify<64><<<nb, 64, 0, s>>>(rs, n, nullptr, dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
-        if (e->n_long > 0 && n > e->tb_wave_below) k_tb_par_verify<64><<<(unsigned)e->n_long, 64, 0, s>>>(rs, e->n_long, e->d_long.as<i32>(), dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
+    // behind the kernel boundary: the first block of rows under every chunk top walked again, compare
+    // only; what disagrees is the serial kernels' (counted: TBA_GET_TB_VERIFY_FAIL), the rest is trimmed
+    per_chunk(k_tb_par_verify<16>, k_tb_par_verify<64>);
 #endif
-        k_main_tb<<<(unsigned)((n + TB_LANES - 1) / TB_LANES), TB_LANES, 0, s>>>(rs, n, dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
-        if (e->n_long > 0) k_main_tb_long<<<(unsigned)e->n_long, 64, 0, s>>>(rs, e->d_long.as<i32>(), dp, e->d_moves.as<unsigned char>(), e->d_bst.as<i64>(), e->d_readtb.as<i64>());
-        k_tb_gather<<<dim3(gB, nb), 256, 0, s>>>(rs, e->d_cpts.as<i64>(), e->d_readtb.as<i64>(), e->d_dpsegs.as<i64>());
-    }
-    MARK(); // 11 skip resolve
-    if (ON(TBA_STAGE_SKIP)) {
-        // window queues of the wave-per-window kernels: counters + three (read, window) lists
-        const i64 qcap = n * 32 + 4096;
-        i64 *skipq = e->d_skipq.as<i64>();
-        i32 *lists = (i32 *)(skipq + 8);
-        HIP_TRY(hipMemsetAsync(skipq, 0, 64, s));
-        k_skip_plan<<<nb, 64, 0, s>>>(rs, n, dp, e->d_dpsegs.as<i64>(), e->d_segs.as<i64>(), e->d_win.as<i64>(), skipq, lists, qcap);
-        k_scan_arena<1><<<1, 256, 0, s>>>(rs, n, e->skip_arena);
-#define SKIP_WAVE_ARGS(c_) rs, dp, e->d_norm.as<double>(), e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_dpsegs.as<i64>(), e->d_segs.as<i64>(), e->d_win.as<i64>(), skipq, lists + 2 * qcap * (c_), qcap
-        if (P.raw_min_obs_per_base > 1) { // (k_skip_plan queues nothing otherwise)
-            // The three classes own disjoint windows and each is a queue drained by lone wavefronts whose time is
-            // one lane's stay recurrence: a kernel is as long as its slowest chain of windows, not as its work.
-            // With the side stream the middle class runs beside the big one instead of behind it: 5.0 -> 4.1 ms for
-            // the three on cfg4 (tools/skip_timeline.sh; before the kernels' LDS diet 7.5 -> 5.7; all three at once
-            // on three streams: 3.7-4.1, no better for the stage).  TBA_SKIP_FORK=0: one after the other, as before
-            // round 6.
-            static const bool fork_off = getenv("TBA_SKIP_FORK") != nullptr && getenv("TBA_SKIP_FORK")[0] == '0';
-            const bool fork = side && !fork_off;
-            hipStream_t sw = fork ? s2 : s;
-            if (fork) {
-                HIP_TRY(hipEventRecord(e->ev_skip0, s));
-                HIP_TRY(hipStreamWaitEvent(s2, e->ev_skip0, 0));
-            }
-            k_skip_dp_wave<SKIP_LEN_B, SKIP_BITS_B, 2><<<512, 64, 0, s>>>(SKIP_WAVE_ARGS(2));
-            k_skip_dp_wave<SKIP_LEN_M, SKIP_BITS_M, 1><<<1024, 64, 0, sw>>>(SKIP_WAVE_ARGS(1));
-            k_skip_dp_wave<SKIP_LEN_S, SKIP_BITS_S, 0><<<2048, 64, 0, s>>>(SKIP_WAVE_ARGS(0));
-            if (fork) {
-                HIP_TRY(hipEventRecord(e->ev_skip1, s2));
-                HIP_TRY(hipStreamWaitEvent(s, e->ev_skip1, 0));
-            }
+    k_main_tb<<<(unsigned)((n + TB_LANES - 1) / TB_LANES), TB_LANES, 0, c.s>>>(c.rs, n, c.dp, c.moves, c.bst, c.readtb);
+    if (n_long > 0) k_main_tb_long<<<(unsigned)n_long, 64, 0, c.s>>>(c.rs, c.lng, c.dp, c.moves, c.bst, c.readtb);
+    k_tb_gather<<<dim3(c.gB, c.nb), 256, 0, c.s>>>(c.rs, c.cpts, c.readtb, c.dpsegs);
+    return 0;
+}
+static int step_skip_resolve(Run &c)
+{
+    // window queues of the wave-per-window kernels: counters + three (read, window) lists
+    const i64 qcap = c.n * 32 + 4096;
+    i32 *lists = (i32 *)(c.skipq + 8);
+    HIP_TRY(hipMemsetAsync(c.skipq, 0, 64, c.s));
+    k_skip_plan<<<c.nb, 64, 0, c.s>>>(c.rs, c.n, c.dp, c.dpsegs, c.segs, c.win, c.skipq, lists, qcap);
+    k_scan_arena<1><<<1, 256, 0, c.s>>>(c.rs, c.n, c.e->z.skip_arena);
+    if (c.P.raw_min_obs_per_base > 1) { // (k_skip_plan queues nothing otherwise)
+        // The three classes own disjoint windows and each is a queue drained by lone wavefronts whose time is
+        // one lane's stay recurrence: a kernel is as long as its slowest chain of windows, not as its work.
+        // With the side stream the middle class runs beside the big one instead of behind it: 5.0 -> 4.1 ms for
+        // the three on cfg4 (tools/skip_timeline.sh; before the kernels' LDS diet 7.5 -> 5.7; all three at once
+        // on three streams: 3.7-4.1, no better for the stage).  TBA_SKIP_FORK=0: one after the other, as before
+        // round 6.
+        static const bool fork_off = getenv("TBA_SKIP_FORK") != nullptr && getenv("TBA_SKIP_FORK")[0] == '0';
+        const bool fork = c.side && !fork_off;
+        if (fork) {
+            HIP_TRY(hipEventRecord(c.e->ev_skip0, c.s));
+            HIP_TRY(hipStreamWaitEvent(c.s2, c.e->ev_skip0, 0));
         }
-#undef SKIP_WAVE_ARGS
-        // (raw_min_obs_per_base == 1, DNA: the small windows out of LDS -- k_tail.h)
-        (e->hp.p.raw_min_obs_per_base == 1 ? k_skip_dp<true> : k_skip_dp<false>)<<<nb, 64, 0, s>>>(rs, dp, e->d_norm.as<double>(), e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_dpsegs.as<i64>(), e->d_segs.as<i64>(), e->d_win.as<i64>(), e->d_dscr.as<double>());
+        auto wave = [&](auto k, int cls, unsigned n_blocks, hipStream_t st) { // (the class's list is the cls-th)
+            k<<<n_blocks, 64, 0, st>>>(c.rs, c.dp, c.norm, c.refm, c.refs, c.dpsegs, c.segs, c.win, c.skipq, lists + 2 * qcap * cls, qcap);
+        };
+        wave(k_skip_dp_wave<SKIP_LEN_B, SKIP_BITS_B, 2>, 2, 512, c.s);
+        wave(k_skip_dp_wave<SKIP_LEN_M, SKIP_BITS_M, 1>, 1, 1024, fork ? c.s2 : c.s);
+        wave(k_skip_dp_wave<SKIP_LEN_S, SKIP_BITS_S, 0>, 0, 2048, c.s);
+        if (fork) {
+            HIP_TRY(hipEventRecord(c.e->ev_skip1, c.s2));
+            HIP_TRY(hipStreamWaitEvent(c.s, c.e->ev_skip1, 0));
+        }
     }
-    MARK(); // 12 theil-sen
-    if (ON(TBA_STAGE_RESCALE)) {
-        k_theil_sen<<<nb, SEL_NT, 0, s>>>(rs, dp, e->d_norm.as<double>(), e->d_segs.as<i64>(), e->d_refm.as<double>(), e->have_samp || e->hp.o.device_subsample ? e->d_samp.as<i64>() : nullptr, e->d_csum.as<double>(), e->d_score.as<double>());
+    // (raw_min_obs_per_base == 1, DNA: the small windows out of LDS -- k_tail.h)
+    (c.P.raw_min_obs_per_base == 1 ? k_skip_dp<true> : k_skip_dp<false>)<<<c.nb, 64, 0, c.s>>>(c.rs, c.dp, c.norm, c.refm, c.refs, c.dpsegs, c.segs, c.win, c.dscr);
+    return 0;
+}
+static int step_theil_sen(Run &c)
+{
+    k_theil_sen<<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, c.norm, c.segs, c.refm, c.e->have_samp || c.O.device_subsample ? c.samp : nullptr, c.csum, c.score);
+    return 0;
+}
+static int step_rescale_score(Run &c)
+{
+    const bool out = !c.O.skip_norm_out;
+    (out ? k_rescale_absz<true> : k_rescale_absz<false>)<<<dim3(c.gB, c.nb), 256, 0, c.s>>>(c.rs, c.dp, c.norm, out ? c.norm_out : nullptr, c.segs, c.refm, c.refs, c.absz);
+    k_final_score<<<c.nb, 64, 0, c.s>>>(c.rs, c.n, c.absz);
+    return 0;
+}
+
+// The schedule: step i runs between the events ev[i] and ev[i + 1] of the main stream (timing slot i, named
+// here), in a run whose stage range holds its public stage.
+static const struct Step { const char *name; int stage; int (*enqueue)(Run &); } STEPS[] = {
+    {"normalize", TBA_STAGE_SEGMENT, step_normalize},
+    {"cumsum", TBA_STAGE_SEGMENT, step_cumsum},
+    {"scores", TBA_STAGE_SEGMENT, step_scores},
+    {"peaks", TBA_STAGE_SEGMENT, step_peaks},
+    {"event_means", TBA_STAGE_EVENT_MEANS, step_event_means},
+    {"ref_levels", TBA_STAGE_REF_LEVELS, step_ref_levels},
+    {"start_dp", TBA_STAGE_START, step_start_dp},
+    {"start_tb", TBA_STAGE_START, step_start_tb},
+    {"prep", TBA_STAGE_ASSIGN, step_prep},
+    {"main_dp", TBA_STAGE_ASSIGN, step_main_dp},
+    {"main_tb", TBA_STAGE_ASSIGN, step_main_tb},
+    {"skip_resolve", TBA_STAGE_SKIP, step_skip_resolve},
+    {"theil_sen", TBA_STAGE_RESCALE, step_theil_sen},
+    {"rescale_score", TBA_STAGE_RESCALE, step_rescale_score},
+};
+static_assert(sizeof(STEPS) / sizeof(STEPS[0]) == N_STEP, "one step per timing slot");
+
+// Every event is recorded in every run, whether or not its step runs: tba_batch_sync reads them all.
+static int enqueue_stages(tba_engine *e, int first, int last)
+{
+    if (!e || !e->have_batch) return set_err(TBA_E_STATE, "no batch uploaded");
+    if (first < 0 || last > TBA_STAGE_RESCALE || first > last) return set_err(TBA_E_ARG, "bad stage range");
+    if (first > 0 && !e->ran) return set_err(TBA_E_STATE, "stages before `first` have not been run or injected");
+    HIP_TRY(hipSetDevice(e->device));
+    Run c{e};
+    if (int rc = run_prelude(c, first, last)) return rc;
+    for (int i = 0; i < N_STEP; i++) {
+        HIP_TRY(hipEventRecord(e->ev[i], c.s));
+        if (STEPS[i].stage >= first && STEPS[i].stage <= last)
+            if (int rc = STEPS[i].enqueue(c)) return rc;
     }
-    MARK(); // 13 rescale + score
-    if (ON(TBA_STAGE_RESCALE)) {
-        if (e->hp.o.skip_norm_out)
-            k_rescale_absz<false><<<dim3(gB, nb), 256, 0, s>>>(rs, dp, e->d_norm.as<double>(), nullptr, e->d_segs.as<i64>(), e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_absz.as<double>());
-        else
-            k_rescale_absz<true><<<dim3(gB, nb), 256, 0, s>>>(rs, dp, e->d_norm.as<double>(), e->d_norm_out.as<double>(), e->d_segs.as<i64>(), e->d_refm.as<double>(), e->d_refs.as<double>(), e->d_absz.as<double>());
-        k_final_score<<<nb, 64, 0, s>>>(rs, n, e->d_absz.as<double>());
-    }
-    MARK(); // 14 end
-#undef MARK
-#undef ON
+    HIP_TRY(hipEventRecord(e->ev[N_STEP], c.s)); // the end of the last step
     HIP_TRY(hipGetLastError());
     e->ran = true;
     e->finished = last == TBA_STAGE_RESCALE;
@@ -883,14 +899,13 @@ extern "C" int tba_batch_wait_for(tba_engine *e, tba_engine *other)
     if (!e || !other) return set_err(TBA_E_ARG, "engine is NULL");
     if (!other->ran || e == other) return 0; // nothing enqueued there yet
     HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamWaitEvent(e->stream, other->ev[14], 0));
+    HIP_TRY(hipStreamWaitEvent(e->stream, other->ev[N_STEP], 0));
     return 0;
 }
 
 extern "C" int tba_batch_run_stages(tba_engine *e, int first_stage, int last_stage)
 {
-    int rc = enqueue_stages(e, first_stage, last_stage);
-    if (rc) return rc;
+    if (int rc = enqueue_stages(e, first_stage, last_stage)) return rc;
     return tba_batch_sync(e);
 }
 
@@ -925,16 +940,16 @@ extern "C" int tba_batch_put(tba_engine *e, int what, const void *data, int64_t 
                 if (c[k] < 0 || c[k] > rs[i].n_raw || (k > 0 && c[k] <= c[k - 1]))
                     return set_err(TBA_E_ARG, "change points must be strictly increasing inside [0, n_raw]");
         }
-        rc = put(e->d_cpts, (size_t)e->E_tot * 8);
+        rc = put(e->d_cpts, (size_t)e->z.E_tot * 8);
         for (size_t i = 0; i < N && !rc; i++) { rs[i].n_cpts = per_read[i]; rs[i].n_ev = per_read[i] - 1; }
         break;
-    case TBA_PUT_EVENT_MEANS: rc = put(e->d_evm, (size_t)e->E_tot * 8); break;
-    case TBA_PUT_NORM: rc = put(e->d_norm, (size_t)e->S_tot * 8); break;
-    case TBA_PUT_REF_MEANS: rc = put(e->d_refm, (size_t)e->B_tot * 8); break;
-    case TBA_PUT_REF_SDS: rc = put(e->d_refs, (size_t)e->B_tot * 8); break;
+    case TBA_PUT_EVENT_MEANS: rc = put(e->d_evm, (size_t)e->z.E_tot * 8); break;
+    case TBA_PUT_NORM: rc = put(e->d_norm, (size_t)e->z.S_tot * 8); break;
+    case TBA_PUT_REF_MEANS: rc = put(e->d_refm, (size_t)e->z.B_tot * 8); break;
+    case TBA_PUT_REF_SDS: rc = put(e->d_refs, (size_t)e->z.B_tot * 8); break;
     case TBA_PUT_DP_SEGS: // per_read[2i] = read_start_rel_to_raw, per_read[2i+1] = trimmed signal length
         if (!per_read) return set_err(TBA_E_ARG, "per_read (read_start, norm_len) required");
-        if ((size_t)bytes < (size_t)(e->B_tot + e->n_reads) * 8) return set_err(TBA_E_ARG, "segment array shorter than the batch");
+        if ((size_t)bytes < e->n_segs() * 8) return set_err(TBA_E_ARG, "segment array shorter than the batch");
         for (size_t i = 0; i < N; i++) { // boundaries index the signal: non-decreasing inside [0, norm_len]
             const i64 rstart = per_read[2 * i], nl = per_read[2 * i + 1];
             if (rstart < 0 || nl < 0 || rstart + nl > rs[i].n_raw) return set_err(TBA_E_ARG, "segments outside the signal");
@@ -943,7 +958,7 @@ extern "C" int tba_batch_put(tba_engine *e, int what, const void *data, int64_t 
                 if (sg[k] < 0 || sg[k] > nl || (k > 0 && sg[k] < sg[k - 1]))
                     return set_err(TBA_E_ARG, "segment boundaries must be non-decreasing inside [0, norm_len]");
         }
-        rc = put(e->d_dpsegs, (size_t)(e->B_tot + e->n_reads) * 8);
+        rc = put(e->d_dpsegs, e->n_segs() * 8);
         for (size_t i = 0; i < N && !rc; i++) {
             rs[i].read_start = rs[i].dp_read_start = per_read[2 * i];
             rs[i].norm_len = per_read[2 * i + 1];
@@ -967,19 +982,14 @@ extern "C" int tba_batch_sync(tba_engine *e)
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->ran) {
         memset(e->stage_ms, 0, sizeof(e->stage_ms));
-        for (int i = 0; i < 14; i++) (void)hipEventElapsedTime(&e->stage_ms[i], e->ev[i], e->ev[i + 1]);
-        (void)hipEventElapsedTime(&e->stage_ms[14], e->ev_st0, e->ev_st1); // stall detection (side stream: overlaps the stages above)
-        (void)hipEventElapsedTime(&e->stage_ms[15], e->ev[15], e->ev[14]);
+        for (int i = 0; i < N_STEP; i++) (void)hipEventElapsedTime(&e->stage_ms[i], e->ev[i], e->ev[i + 1]);
+        (void)hipEventElapsedTime(&e->stage_ms[SLOT_STALLS], e->ev_st0, e->ev_st1); // stall detection (side stream: overlaps the steps above)
+        (void)hipEventElapsedTime(&e->stage_ms[SLOT_TOTAL], e->ev[SLOT_TOTAL], e->ev[N_STEP]);
     }
     return 0;
 }
 
-extern "C" int tba_batch_run(tba_engine *e)
-{
-    int rc = tba_batch_enqueue(e);
-    if (rc) return rc;
-    return tba_batch_sync(e);
-}
+extern "C" int tba_batch_run(tba_engine *e) { return tba_batch_run_stages(e, TBA_STAGE_SEGMENT, TBA_STAGE_RESCALE); }
 
 extern "C" int tba_batch_download(tba_engine *e, int32_t *status, int64_t *segs,
                                   int64_t *read_start_rel_to_raw, double *norm_signal,
@@ -994,8 +1004,8 @@ extern "C" int tba_batch_download(tba_engine *e, int32_t *status, int64_t *segs,
     const size_t N = (size_t)e->n_reads;
     std::vector<ReadState> rs(N);
     HIP_TRY(hipMemcpy(rs.data(), e->d_rs.p, N * sizeof(ReadState), hipMemcpyDeviceToHost));
-    if (segs) HIP_TRY(hipMemcpy(segs, e->d_segs.p, (size_t)(e->B_tot + e->n_reads) * 8, hipMemcpyDeviceToHost));
-    if (norm_signal) HIP_TRY(hipMemcpy(norm_signal, e->d_norm_out.p, (size_t)e->S_tot * 8, hipMemcpyDeviceToHost));
+    if (segs) HIP_TRY(hipMemcpy(segs, e->d_segs.p, e->n_segs() * 8, hipMemcpyDeviceToHost));
+    if (norm_signal) HIP_TRY(hipMemcpy(norm_signal, e->d_norm_out.p, (size_t)e->z.S_tot * 8, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < N; i++) {
         const ReadState &r = rs[i];
         if (status) status[i] = r.status;
@@ -1043,20 +1053,20 @@ extern "C" int tba_batch_download_async(tba_engine *e, tba_read_result *results,
     if (!e || !e->ran) return set_err(TBA_E_STATE, "no batch has been run");
     if (norm_signal && e->hp.o.skip_norm_out)
         return set_err(TBA_E_STATE, "the batch was run with skip_norm_out: there is no normalised signal to download");
-    if (segs32 && e->max_raw > 0x7fffffffll) return set_err(TBA_E_ARG, "signal too long for int32 boundaries");
+    if (segs32 && e->z.max_raw > 0x7fffffffll) return set_err(TBA_E_ARG, "signal too long for int32 boundaries");
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     const size_t N = (size_t)e->n_reads;
-    const unsigned gB = (unsigned)std::min<i64>(std::max<i64>((e->max_B + 1 + 255) / 256, 1), 64);
+    const unsigned gB = (unsigned)std::min<i64>(std::max<i64>((e->z.max_B + 1 + 255) / 256, 1), 64);
     if (results || segs32) {
         k_pack_results<<<dim3(segs32 ? gB : 1, (unsigned)N), 256, 0, s>>>(e->d_rs.as<ReadState>(),
             e->d_segs.as<i64>(), e->d_res.as<tba_read_result>(), segs32 ? e->d_segs32.as<i32>() : nullptr);
         HIP_TRY(hipGetLastError());
     }
     if (results) HIP_TRY(hipMemcpyAsync(results, e->d_res.p, N * sizeof(tba_read_result), hipMemcpyDeviceToHost, s));
-    if (segs32) HIP_TRY(hipMemcpyAsync(segs32, e->d_segs32.p, (size_t)(e->B_tot + e->n_reads) * 4, hipMemcpyDeviceToHost, s));
-    if (segs64) HIP_TRY(hipMemcpyAsync(segs64, e->d_segs.p, (size_t)(e->B_tot + e->n_reads) * 8, hipMemcpyDeviceToHost, s));
-    if (norm_signal) HIP_TRY(hipMemcpyAsync(norm_signal, e->d_norm_out.p, (size_t)e->S_tot * 8, hipMemcpyDeviceToHost, s));
+    if (segs32) HIP_TRY(hipMemcpyAsync(segs32, e->d_segs32.p, e->n_segs() * 4, hipMemcpyDeviceToHost, s));
+    if (segs64) HIP_TRY(hipMemcpyAsync(segs64, e->d_segs.p, e->n_segs() * 8, hipMemcpyDeviceToHost, s));
+    if (norm_signal) HIP_TRY(hipMemcpyAsync(norm_signal, e->d_norm_out.p, (size_t)e->z.S_tot * 8, hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -1088,36 +1098,31 @@ extern "C" int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_byt
         HIP_TRY(hipMemcpy(out, b.p, bytes, hipMemcpyDeviceToHost));
         return 0;
     };
-    std::vector<ReadState> rs;
-    auto fetch_rs = [&]() -> int {
-        rs.resize(N);
-        HIP_TRY(hipMemcpy(rs.data(), e->d_rs.p, N * sizeof(ReadState), hipMemcpyDeviceToHost));
-        return 0;
-    };
     switch (what) {
-    case TBA_GET_VALID_CPTS: return copy(e->d_cpts, (size_t)e->E_tot * 8);
-    case TBA_GET_EVENT_MEANS: return copy(e->d_evm, (size_t)e->E_tot * 8);
-    case TBA_GET_SEG_NORM: return copy(e->d_norm, (size_t)e->S_tot * 8);
-    case TBA_GET_ED_TAKEN_POS: return copy(e->d_score, (size_t)e->S_tot * 8);
-    case TBA_GET_BAND_STARTS: return copy(e->d_bst, (size_t)e->B_tot * 8);
-    case TBA_GET_READ_TB: return copy(e->d_readtb, (size_t)(e->B_tot + e->n_reads) * 8);
-    case TBA_GET_DP_SEGS: return copy(e->d_dpsegs, (size_t)(e->B_tot + e->n_reads) * 8);
+    case TBA_GET_VALID_CPTS: return copy(e->d_cpts, (size_t)e->z.E_tot * 8);
+    case TBA_GET_EVENT_MEANS: return copy(e->d_evm, (size_t)e->z.E_tot * 8);
+    case TBA_GET_SEG_NORM: return copy(e->d_norm, (size_t)e->z.S_tot * 8);
+    case TBA_GET_ED_TAKEN_POS: return copy(e->d_score, (size_t)e->z.S_tot * 8);
+    case TBA_GET_BAND_STARTS: return copy(e->d_bst, (size_t)e->z.B_tot * 8);
+    case TBA_GET_READ_TB: return copy(e->d_readtb, e->n_segs() * 8);
+    case TBA_GET_DP_SEGS: return copy(e->d_dpsegs, e->n_segs() * 8);
     case TBA_GET_LAST_ROW: return copy(e->d_lastrow, N * TBA_MAX_BAND * 8);
-    case TBA_GET_REF_MEANS: return copy(e->d_refm, (size_t)e->B_tot * 8);
-    case TBA_GET_REF_SDS: return copy(e->d_refs, (size_t)e->B_tot * 8);
-    case TBA_GET_SEGS: return copy(e->d_segs, (size_t)(e->B_tot + e->n_reads) * 8);
+    case TBA_GET_REF_MEANS: return copy(e->d_refm, (size_t)e->z.B_tot * 8);
+    case TBA_GET_REF_SDS: return copy(e->d_refs, (size_t)e->z.B_tot * 8);
+    case TBA_GET_SEGS: return copy(e->d_segs, e->n_segs() * 8);
     case TBA_GET_SAMP_IND: return copy(e->d_samp, N * MAX_TS_POINTS * 8);
     case TBA_GET_STALL_INTS:
         if (!e->any_stall) return set_err(TBA_E_STATE, "the batch has no stall intervals");
         // (the caller sizes `out` by the intervals in use: max(STALL_OFF + N_STALL))
-        return copy(e->d_stall, std::min((size_t)e->n_stall_cap * 16, (size_t)out_bytes));
+        return copy(e->d_stall, std::min((size_t)e->z.n_stall * 16, (size_t)out_bytes));
     case TBA_GET_KERNEL_MS:
         if ((size_t)out_bytes < sizeof(e->stage_ms)) return set_err(TBA_E_ARG, "output buffer too small");
         memcpy(out, e->stage_ms, sizeof(e->stage_ms));
         return 0;
     default: break;
     }
-    if (int rc = fetch_rs()) return rc;
+    std::vector<ReadState> rs(N);
+    HIP_TRY(hipMemcpy(rs.data(), e->d_rs.p, N * sizeof(ReadState), hipMemcpyDeviceToHost));
     // the per-read selectors: one T per read, from the read's ReadState `r`
     auto per_read = [&](auto get) -> int {
         typedef decltype(get(rs[0])) T;
@@ -1153,7 +1158,7 @@ extern "C" int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_byt
     case TBA_GET_PATH: return PER_READ(I4, I4{r.path, (i32)r.n_static, (i32)r.W, r.n_start_calls});
     case TBA_GET_DEBUG_COUNTERS: return PER_READ(I8, to_array(r.dbg)); // phase cycle / sweep counters of a profiling build
     case TBA_GET_DP_FORM: {
-        // Derived: what enqueue_stages launched, and per read the kernels' own selection predicates over the
+        // Derived: what the steps of the last run launched (last_dp), and per read the kernels' own selection predicates over the
         // state the run left -- k_prep / k_scan_arena leave a path only on reads that go into the main pass,
         // and nothing after start discovery touches start_state, n_start_calls or the first try's failure.
         const tba_params &P = e->hp.p;
@@ -1190,44 +1195,44 @@ extern "C" int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_byt
 }
 
 // workgroups per read of the per-base kernels over a finished batch
-static unsigned base_blocks(const tba_engine *e) { return (unsigned)std::min<i64>(std::max<i64>((e->max_B + 255) / 256, 1), 128); }
+static unsigned base_blocks(const tba_engine *e) { return (unsigned)std::min<i64>(std::max<i64>((e->z.max_B + 255) / 256, 1), 128); }
 
 // per-base means and stds of the final signal into e->d_stat (B_tot means, then B_tot stds)
 static int launch_base_stats(tba_engine *e)
 {
-    if (e->d_stat.ensure((size_t)e->B_tot * 16)) return set_err(TBA_E_NOMEM, "hipMalloc failed");
+    if (e->d_stat.ensure((size_t)e->z.B_tot * 16)) return set_err(TBA_E_NOMEM, "hipMalloc failed");
     double *d_m = e->d_stat.as<double>();
     k_base_stats<<<dim3(base_blocks(e), (unsigned)e->n_reads), 256, 0, e->stream>>>(e->d_rs.as<ReadState>(),
         e->d_dp.as<DevParams>(), e->hp.o.skip_norm_out ? nullptr : e->d_norm_out.as<double>(),
-        e->d_norm.as<double>(), e->d_segs.as<i64>(), d_m, d_m + e->B_tot);
+        e->d_norm.as<double>(), e->d_segs.as<i64>(), d_m, d_m + e->z.B_tot);
     return 0;
 }
 
 extern "C" int tba_batch_base_stats(tba_engine *e, double *means, double *stds, int64_t n_values)
 {
     if (!e || !e->have_batch || !e->finished) return set_err(TBA_E_STATE, "no finished batch");
-    if (!means || !stds || n_values < e->B_tot) return set_err(TBA_E_ARG, "output buffers too small");
+    if (!means || !stds || n_values < e->z.B_tot) return set_err(TBA_E_ARG, "output buffers too small");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->B_tot == 0) return 0;
+    if (e->z.B_tot == 0) return 0;
     if (int rc = launch_base_stats(e)) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));
     const double *d_m = e->d_stat.as<double>();
-    HIP_TRY(hipMemcpy(means, d_m, (size_t)e->B_tot * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(stds, d_m + e->B_tot, (size_t)e->B_tot * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(means, d_m, (size_t)e->z.B_tot * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(stds, d_m + e->z.B_tot, (size_t)e->z.B_tot * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
 extern "C" int tba_batch_stats(tba_engine *e, double *algorithmic_bytes, double *dp_cells)
 {
     if (!e || !e->have_batch) return set_err(TBA_E_STATE, "no batch uploaded");
-    if (algorithmic_bytes) *algorithmic_bytes = e->algo_bytes;
-    if (dp_cells) *dp_cells = e->dp_cells;
+    if (algorithmic_bytes) *algorithmic_bytes = e->z.algo_bytes;
+    if (dp_cells) *dp_cells = e->z.cells;
     return 0;
 }
 
-extern "C" const char *tba_stage_name(int i) { return i >= 0 && i < N_STAGE ? STAGE_NAMES[i] : ""; }
+extern "C" const char *tba_stage_name(int i) { return i < 0 || i >= N_STAGE ? "" : i < N_STEP ? STEPS[i].name : i == SLOT_STALLS ? "stalls" : "total"; }
 
 // ---------------------------------------------------------------------------------------------
 // per-kernel entry points (tba_c_*): host buffers in, host buffers out, batch of one
@@ -2159,10 +2164,10 @@ extern "C" int tba_batch_de_novo_stats(tba_engine *e, int64_t fm_offset, double 
                                        double *pvals, int64_t n_values)
 {
     if (!e || !e->have_batch || !e->finished) return set_err(TBA_E_STATE, "no finished batch");
-    if (!pvals || n_values < e->B_tot || fm_offset < 0 || fm_offset > 64) return set_err(TBA_E_ARG, "bad arguments");
+    if (!pvals || n_values < e->z.B_tot || fm_offset < 0 || fm_offset > 64) return set_err(TBA_E_ARG, "bad arguments");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->B_tot == 0) return 0;
+    if (e->z.B_tot == 0) return 0;
     const size_t N = (size_t)e->n_reads;
     const i64 K = e->hp.kmer_width, cp = e->hp.central_pos, dn = K - cp - 1;
     // per-base means of the final signal (the Events table's norm_mean), on the device
@@ -2186,7 +2191,7 @@ extern "C" int tba_batch_de_novo_stats(tba_engine *e, int64_t fm_offset, double 
     double *d_pr = sc.out<double>(total);
     double *d_ps = sc.out<double>(total);
     double *d_pp = sc.out<double>(total);
-    double *d_out = sc.out<double>(e->B_tot);
+    double *d_out = sc.out<double>(e->z.B_tot);
     if (sc.rc) return sc.rc;
     if (total > 0) {
         k_denovo_pack<<<dim3(gB, (unsigned)N), 256, 0, e->stream>>>(e->d_rs.as<ReadState>(), e->n_reads,
@@ -2197,7 +2202,7 @@ extern "C" int tba_batch_de_novo_stats(tba_engine *e, int64_t fm_offset, double 
     k_denovo_unpack<<<dim3(gB, (unsigned)N), 256, 0, e->stream>>>(e->d_rs.as<ReadState>(),
         e->d_dp.as<DevParams>(), d_pk, d_pp, d_out);
     if (sc.sync(e->stream)) return sc.rc;
-    return sc.get(pvals, d_out, e->B_tot);
+    return sc.get(pvals, d_out, e->z.B_tot);
 }
 
 // the two division self-tests: out[i] from (a[i], b[i])
@@ -2585,13 +2590,7 @@ extern "C" int tba_engine_held_bytes(tba_engine *e, int64_t *bytes)
 {
     if (!e || !bytes) return set_err(TBA_E_ARG, "bad arguments");
     size_t tot = 0;
-    DevBuf *all[] = {&e->d_rs, &e->d_dp, &e->d_kmeans, &e->d_ksds, &e->d_raw, &e->d_norm, &e->d_norm_out, &e->d_csum,
-                     &e->d_score, &e->d_state, &e->d_cpts, &e->d_evm, &e->d_seq, &e->d_refm, &e->d_refs, &e->d_bst,
-                     &e->d_lo, &e->d_hi, &e->d_readtb, &e->d_dpsegs, &e->d_segs, &e->d_win, &e->d_absz,
-                     &e->d_sv_in, &e->d_samp, &e->d_stall, &e->d_lastrow, &e->d_startvals, &e->d_smoves,
-                     &e->d_moves, &e->d_dscr, &e->d_wide, &e->d_stat, &e->d_res, &e->d_segs32, &e->d_skipq,
-                     &e->d_stall_csum, &e->d_stall_bits};
-    for (DevBuf *b : all) tot += b->cap;
+    e->for_each_devbuf([&](DevBuf &b) { tot += b.cap; });
     *bytes = (int64_t)tot;
     return 0;
 }
