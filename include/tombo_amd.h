@@ -308,8 +308,9 @@ enum {
                                * kernels: the launch decisions the engine recorded when it enqueued the run, and per read
                                * the predicates by which the kernels select their reads (k_dp.h, k_dp_multi.h, k_dp_wg.h)
                                * over the state the run left (TBA_GET_PATH, TBA_GET_START_FAIL, start state) */
-    TBA_GET_DEBUG_COUNTERS = 99 /* int64[n][8]: ReadState.dbg, only filled by -DTBA_PHASE_DEBUG /
-                                   -DTBA_SWEEP_STATS profiling builds (zeros otherwise) */
+    TBA_GET_DEBUG_COUNTERS = 99 /* int64[n][8]: ReadState.dbg, only filled by the profiling builds (one of
+                                   -DTBA_PHASE_DEBUG=<id>, -DTBA_SWEEP_STATS, -DTBA_SKIP_STATS, -DTBA_SKIP_CLASS_STATS;
+                                   the slots of each: csrc/tba_phase.h), zeros otherwise */
 };
 enum {
     TBA_ED_FORM_NONE = 0,

@@ -11,8 +11,8 @@ from collections import namedtuple
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# TBA_LIB_PATH: an alternative build of the same library (profiling builds with
-# -DTBA_PHASE_DEBUG / -DTBA_SWEEP_STATS, A/B comparisons of a kernel variant)
+# TBA_LIB_PATH: an alternative build of the same library (profiling builds with one of -DTBA_PHASE_DEBUG=<id> /
+# -DTBA_SWEEP_STATS / -DTBA_SKIP_STATS / -DTBA_SKIP_CLASS_STATS, A/B comparisons of a kernel variant)
 LIB_PATH = os.environ.get('TBA_LIB_PATH') or os.path.join(_HERE, 'libtombo_amd.so')
 CSRC = os.path.join(_HERE, 'csrc')
 i64, f64, i32 = C.c_int64, C.c_double, C.c_int32
@@ -106,7 +106,9 @@ TB_FORM_NONE, TB_FORM_LANE, TB_FORM_LONG, TB_FORM_PAR16, TB_FORM_PAR64 = 0, 1, 2
 # start discovery, class of the retry kernel); derived on the host from the run's launch decisions and per-read state
 DP_FORM_NONE, DP_FORM_K_DP, DP_FORM_K_DP8_LOWREG, DP_FORM_MULTI, DP_FORM_WIDE = range(5)
 DP_START_NONE, DP_START_FIRST_TRY, DP_START_RETRY_WG, DP_START_RETRY_K_DP = range(4)
-GET_DEBUG_COUNTERS = 99  # ReadState.dbg of a -DTBA_PHASE_DEBUG / -DTBA_SWEEP_STATS profiling build
+# ReadState.dbg of a profiling build: -DTBA_PHASE_DEBUG=<id>, -DTBA_SWEEP_STATS, -DTBA_SKIP_STATS or
+# -DTBA_SKIP_CLASS_STATS (what each leaves in the eight slots: the table in csrc/tba_phase.h)
+GET_DEBUG_COUNTERS = 99
 STAGE_SEGMENT, STAGE_EVENT_MEANS, STAGE_REF_LEVELS, STAGE_START, STAGE_ASSIGN, STAGE_SKIP, \
     STAGE_RESCALE = range(7)
 PUT_VALID_CPTS, PUT_EVENT_MEANS, PUT_NORM, PUT_REF_MEANS, PUT_REF_SDS, PUT_DP_SEGS, \

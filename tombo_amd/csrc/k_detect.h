@@ -51,15 +51,6 @@ __device__ __forceinline__ u32 dt_lane_above(u32 x) // lane l <- lane l + 1 (lan
     return (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0x130, 0xf, 0xf, false);
 }
 
-// -DTBA_PHASE_DEBUG=7: cycles per role and part, summed over the steps, into dbg[] of the
-// workgroup's first read: 0 scan, 1 loader, 2 greedy (wave 2) = 3 masks + 4 rounds + 5 emission + 6 tail
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 7
-#define DT_T0() i64 dt_t_ = (i64)__builtin_readcyclecounter()
-#define DT_T(i_) do { const i64 n_ = (i64)__builtin_readcyclecounter(); if (lane == 0) dt_acc[i_] += n_ - dt_t_; dt_t_ = n_; } while (0)
-#else
-#define DT_T0() do { } while (0)
-#define DT_T(i_) do { } while (0)
-#endif
 // g <- 2 g + (|a| >= |b|): one compare into VCC, one add-with-carry (the C++ form is a compare, a
 // select and a shift-or)
 __device__ __forceinline__ u32 dt_shift_in_ge(u32 g, double a, double b)
@@ -198,12 +189,10 @@ __global__ __launch_bounds__(256, 2) void k_detect(ReadState *rs, i64 n_reads, c
     for (int d = 0; d <= R; d++) prevX[d] = 0;
     int cb = 0;
     double smin = INFINITY, smax = -INFINITY;        // range of the scores this lane emitted (k_pick's select)
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 7
-    i64 dt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+    LapClock<7, phase_on(PH_DETECT)> laps;           // cycles per role and part, summed over the steps (tba_phase.h, id 7)
 
     for (i64 i = 0; i <= n_steps + 1; i++) {
-        DT_T0();
+        laps.mark();
         if (wave == 0) {
             if (i < n_steps && lane < DT_READS) {
                 double *row = DT_TILEP(i % 3) + lane * DT_STRIDE;
@@ -216,10 +205,10 @@ __global__ __launch_bounds__(256, 2) void k_detect(ReadState *rs, i64 n_reads, c
                         if (k < left) { acc = acc + row[DT_PC(k)]; row[DT_PC(k)] = acc; }
                 }
             }
-            DT_T(0);
+            laps.lap(0);
         } else if (wave == 1) {
             if (i + 1 < n_steps) loader_step(i + 1, DT_TILEP((i + 1) % 3), i + 2 < n_steps ? i + 2 : -1);
-            DT_T(1);
+            laps.lap(1);
         } else if (i >= 1) {
             // tile j = i - 1: column t holds c[jC + 1 + t]; slot s = jC + t is the score whose window
             // ends there: position k = s + 1 - 2w, |2 c[k+w] - c[k] - c[k+2w]| (pyx:94-98) with
@@ -337,7 +326,7 @@ __global__ __launch_bounds__(256, 2) void k_detect(ReadState *rs, i64 n_reads, c
                 const u32 xb = dt_lane_below(X[d]);
                 Hm[d] = V & dt_up(X[d], h == 0 ? prevX[d] : xb, d); // the neighbour at -d outranks me
             }
-            DT_T(3);
+            laps.lap(3);
             u32 T = 0, S = 0, U = V;
             for (int round = 0; round < DT_MAX_ROUNDS; round++) {
                 const u32 ta = dt_lane_above(T), tb = dt_lane_below(T);
@@ -354,7 +343,7 @@ __global__ __launch_bounds__(256, 2) void k_detect(ReadState *rs, i64 n_reads, c
                 T |= nT; S |= nS; U &= ~(nT | nS);
                 if (__ballot((nS | nT) != 0) == 0) break;
             }
-            DT_T(4);
+            laps.lap(4);
             // words 0..3 are final now; an open position there means a chain longer than a word
             if (glane && h < 4 && U != 0) s_bad[q] = 1;
             // emission, in position order: what word 0 decided late, words 1..3, and what word 4
@@ -380,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void k_detect(ReadState *rs, i64 n_reads, c
                 pn[o] = (i32)(slot0 + t - (w2 - 1));
                 o++;
             }
-            DT_T(5);
+            laps.lap(5);
             // context of the next step: its word 0 is this step's word 4, below it word 3
             prevT = (u32)__shfl((int)T, (lane + 3) & 63, 64);
 #pragma unroll
@@ -390,18 +379,16 @@ __global__ __launch_bounds__(256, 2) void k_detect(ReadState *rs, i64 n_reads, c
             if (glane && j < n_steps)                  // (the read's five lanes share the copy)
                 for (int k = h; k < w2; k += 5) smem[ih_row + k] = trow[CS_CHUNK - w2 + k + 3]; // (last word: 3 pads)
             cb ^= 1;
-            DT_T(6);
+            laps.lap(6);
         }
         __syncthreads();
     }
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 7
     if (lane == 0 && r0 < n_reads) {
-        i64 *dbg = rs[r0].dbg;
-        if (wave == 0) dbg[0] = dt_acc[0];
-        if (wave == 1) dbg[1] = dt_acc[1];
-        if (wave == 2) { dbg[2] = dt_acc[3] + dt_acc[4] + dt_acc[5] + dt_acc[6]; dbg[3] = dt_acc[3]; dbg[4] = dt_acc[4]; dbg[5] = dt_acc[5]; dbg[6] = dt_acc[6]; dbg[7] = n_steps; }
+        if (wave < 2) laps.flush(rs[r0].dbg, wave, wave + 1);
+        if (wave == 2) laps.flush(rs[r0].dbg, 3, 7);
+        if constexpr (phase_on(PH_DETECT))
+            if (wave == 2) { rs[r0].dbg[2] = laps.get(3) + laps.get(4) + laps.get(5) + laps.get(6); rs[r0].dbg[7] = n_steps; }
     }
-#endif
     if (wave >= 2) {                                  // the read's range: over its five lanes
 #pragma unroll
         for (int dd = 1; dd < 5; dd++) {
@@ -441,7 +428,7 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_pick(ReadState *rs, const DevPara
     const i64 n_taken = r.n_taken;
     if (ns <= 0 || num_cpts <= 0) { if (tid == 0) r.status = TBA_INTERNAL; return; }
     if (n_taken < num_cpts) { if (tid == 0) r.status = TBA_FEWER_CPTS; return; }
-    TBA_PHASE_T0(8);
+    const StampClock<phase_on(PH_PICK)> stamps(r.dbg);
     // range of the taken scores: k_detect / k_detect_tt kept it
     const double mn = r.ed_min, mx = r.ed_max;
 
@@ -557,13 +544,13 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_pick(ReadState *rs, const DevPara
         if (lane == 0) { s_gt[wv] = gt; s_eq[wv] = eq; }
     }
     __syncthreads();
-    TBA_PHASE(8, 0);
+    stamps.stamp(0);
     i64 c_gt = 0, c_eq = 0, off = 0;
     for (int q = 0; q < SEL_NT / 64; q++) {
         if (q < wv) off += s_gt[q] + s_eq[q];
         c_gt += s_gt[q]; c_eq += s_eq[q];
     }
-    TBA_PHASE(8, 1);
+    stamps.stamp(1);
     const i64 need_eq = num_cpts - c_gt;              // 1 <= need_eq <= c_eq
     // The reference raises when the rank of the last pick in the argsort order, + 1, reaches
     // num_cands (_c_helper.pyx:116-118).  That rank is below ns minus the positions that score
@@ -595,8 +582,8 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_pick(ReadState *rs, const DevPara
             n_taken, load, [&](i64, SP e) { return e.v > tval || (e.v == tval && (i64)e.p >= idx_thr); },
             emit, s_w);
     }
-    TBA_PHASE(8, 2);
-    TBA_PHASE_END(8);
+    stamps.stamp(2);
+    stamps.end();
     if (tid == 0) { r.n_cpts = num_cpts; r.n_ev = num_cpts - 1; }
 }
 
@@ -710,20 +697,11 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_detect_tt(ReadState *rs, const De
 #pragma unroll
     for (int d = 0; d <= R; d++) prevX[d] = 0;
     double smin = INFINITY, smax = -INFINITY;            // range of the emitted scores (k_pick's select)
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 9
-    // cycles of the greedy wavefront / of one scorer wavefront inside their sections, and of the whole loop
-    i64 tt_acc = 0;
-    const i64 tt_t0 = (i64)__builtin_readcyclecounter();
-#define TT_T0() const i64 tt_a_ = (i64)__builtin_readcyclecounter()
-#define TT_T1() tt_acc += (i64)__builtin_readcyclecounter() - tt_a_
-#else
-#define TT_T0() do { } while (0)
-#define TT_T1() do { } while (0)
-#endif
+    LapClock<1, phase_on(PH_DETECT_TT)> laps;            // this wavefront's cycles inside its sections (tba_phase.h, id 9)
     for (int i = 0; i <= n_tiles; i++) {                 // (one more step finishes the carried word)
         const double *sb = sbuf[i & 1];
         const int P0 = i * TT_NEW;                       // first new position of the tile
-        TT_T0();
+        laps.mark();
         if (wave != 0) {
             // tile i + 1: its samples sit in rawt[(i + 1) & 1]; tile i + 2's are fetched meanwhile and
             // dropped into rawt[i & 1], which nobody reads any more (tile i was scored a step ago)
@@ -852,14 +830,14 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_detect_tt(ReadState *rs, const De
             prev_emitted = (u32)__shfl((int)T, TT_WORDS - 1, 64);
             __builtin_amdgcn_s_setprio(0);
         }
-        TT_T1();
+        laps.lap(0);
         __syncthreads();
     }
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 9
-    if (lane == 0 && wave == 0) { r.dbg[0] = tt_acc; r.dbg[2] = (i64)__builtin_readcyclecounter() - tt_t0; r.dbg[3] = n_tiles; }
-    if (lane == 0 && wave == 1) r.dbg[1] = tt_acc;
-    if (lane == 0 && wave == 7) r.dbg[4] = tt_acc;
-#endif
+    if constexpr (phase_on(PH_DETECT_TT)) {
+        if (lane == 0 && wave == 0) { r.dbg[0] = laps.get(0); r.dbg[2] = laps.since_start(); r.dbg[3] = n_tiles; }
+        if (lane == 0 && wave == 1) r.dbg[1] = laps.get(0);
+        if (lane == 0 && wave == 7) r.dbg[4] = laps.get(0);
+    }
     if (wave == 0) {
         for (int mm = 32; mm >= 1; mm >>= 1) {
             const double a = shfl_xor_f64(smin, mm), b = shfl_xor_f64(smax, mm);

@@ -446,24 +446,10 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
     };
     fetch_row(row0);
 
-#ifdef TBA_SWEEP_STATS
-    i64 sw_total = 0;
-#endif
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 5
-    // cycles of wave 0's rows by part: 0 z-scores (ring reads + arithmetic), 1 candidates, 2 first
-    // scan + sweeps, 3 cells / flags / stores / ring upkeep, 4 arg-max, 5 band placement; 6 rows
-    // dbg[7]: where the wavefront ran: HW_ID (wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13])
-    // | XCC_ID << 32
-    i64 ph[7] = {0, 0, 0, 0, 0, 0, 0};
-    i64 ph_t = (i64)__builtin_readcyclecounter();
-    u32 hw_id, xcc_id;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));
-    const i64 ph_first = (i64)hw_id | ((i64)(xcc_id & 15) << 32);
-#define DP_PH(i_) do { const i64 t_ = (i64)__builtin_readcyclecounter(); ph[i_] += t_ - ph_t; ph_t = t_; } while (0)
-#else
-#define DP_PH(i_) do { } while (0)
-#endif
+    i64 sw_total = 0;                                  // stay-chain sweeps of the read (-DTBA_SWEEP_STATS, tba_phase.h)
+    LapClock<7, phase_on(PH_DP_ROW)> laps;             // cycles of the row's parts and the rows (tba_phase.h, id 5)
+    i64 hw_id = 0;                                     // ... and where the wavefront runs
+    if constexpr (phase_on(PH_DP_ROW)) hw_id = phase_hw_id();
     // One row of the forward pass.  ADAPT: the row is past the static rows (compile-time: no
     // band-geometry loads, no masked-start test -- a wavefront on its own issues ONE instruction
     // of any kind per >= 4 cycles, so the scalar bookkeeping of the general row costs it as much
@@ -502,7 +488,7 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         }
         if (!ADAPT) fetch_row(row + 1); // next row's inputs travel while this row computes
         const int diff_i = row > 0 ? cur_start - prev_start : 0;
-        DP_PH(5);
+        laps.lap(5);
 
         // shifted half z-scores of my cells (pyx:361-372 / resquiggle.py:574-582,712-720)
         double z[CPL];
@@ -541,7 +527,7 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
                 for (int j = 0; j < CPL; j++) if (j < nvalid) job->z_out[(i64)(row - row0) * W + b0 + j] = z[j];
             }
         }
-        DP_PH(0);
+        laps.lap(0);
         // diag / skip candidates from the previous row (pyx:220-231), first cell pyx:392-401:
         // pp[j] is cell j's diagonal source and cell j-1's skip source
         double cv[CPL];
@@ -572,7 +558,7 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         // instructions per cell instead of 3) to get the lane's exit value max(v0[CPL-1], c_{CPL-1}),
         // and the cells themselves are written once, in the pass that also derives the move flags.
         // The sequence of incoming values is the same as with full sweeps, so is the sweep count.
-        DP_PH(1);
+        laps.lap(1);
         // Band cell 0 has no stay move (pyx:392-401): nothing may come into lane 0.  Instead of
         // handing lane 0 an incoming -inf with every lane shift (two v_mov per sweep to prepare the
         // DPP destination), lane 0's z[0] is -inf for the chain from here on (the candidates above were
@@ -584,9 +570,7 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         double exit0 = NEG_INF;                // sweep 1
 #pragma unroll
         for (int j = 0; j < CPL; j++) exit0 = max_f64_raw(cv[j], (exit0 - stay_pen) + z[j]);
-#ifdef TBA_SWEEP_STATS
-        i64 sw_row = 1;
-#endif
+        i64 sw_row = 1;                        // sweeps of this row (-DTBA_SWEEP_STATS only: dead otherwise)
         {
             double nin = wave_shr1_f64_zero(exit0);
             for (int it = 0; it < 66; it++) { // <= 64 sweeps by induction over lanes (NaN-proof bound)
@@ -596,19 +580,15 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
 #pragma unroll
                 for (int j = 0; j < CPL; j++) c = (c - stay_pen) + z[j];
                 nin = wave_shr1_f64_zero(max_f64_raw(exit0, c));
-#ifdef TBA_SWEEP_STATS
-                sw_row++;
-#endif
+                if constexpr (TBA_SWEEP_STATS_ON) sw_row++;
             }
         }
-#ifdef TBA_SWEEP_STATS
-        sw_total += sw_row;
-#endif
+        if constexpr (TBA_SWEEP_STATS_ON) sw_total += sw_row;
         if (!converged) { // only reachable with NaNs in the signal
             if (lane == 0) { if (DIRECT) job->status = TBA_INTERNAL; else r.status = TBA_INTERNAL; }
             return true;
         }
-        DP_PH(2);
+        laps.lap(2);
         // the cells, their move codes (0 stay, 1 skip, 2 diag; pyx:216-231) packed 2 bits per cell,
         // lane-local argmax (pyx:186-197; -inf cells never win)
         u32 mvw[(CPL + 15) / 16];
@@ -680,7 +660,7 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
                 pf_at = filled; pf = ev_load(filled + lane); pf_pending = true;
             }
         }
-        DP_PH(3);
+        laps.lap(3);
         // wave argmax, first index among equal maxima (c_argmax, pyx:186-197): first lane that
         // holds the maximum, first of its cells that equals it
         // The wave maximum is first located in float32 (conversion is monotone, so the lanes
@@ -705,10 +685,8 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         for (int j = CPL - 2; j >= 0; j--) wj = ((__ballot(v[j] == wm) >> wl) & 1ull) ? j : wj;
         am = wl * CPL + wj;
         prev_start = cur_start;
-        DP_PH(4);
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 5
-        ph[6]++;
-#endif
+        laps.lap(4);
+        laps.count(6);
         return false;
     };
     {
@@ -717,18 +695,11 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         for (; row < n_stat_rows; row++) if (row_step(row, BoolTag<false>{})) return;
         for (; row < n_rows; row++) if (row_step(row, BoolTag<true>{})) return;
     }
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 5
     if (!DIRECT && mode == DP_MAIN && lane == 0) {
-        for (int i = 0; i < 7; i++) r.dbg[i] = ph[i];
-        r.dbg[7] = ph_first;
+        laps.flush(r.dbg, 0, 7);
+        if constexpr (phase_on(PH_DP_ROW)) r.dbg[7] = hw_id;
+        if constexpr (TBA_SWEEP_STATS_ON) { r.dbg[0] = n_rows - row0; r.dbg[1] = sw_total; }
     }
-#endif
-#undef DP_PH
-#ifdef TBA_SWEEP_STATS
-    if (!DIRECT && mode == DP_MAIN && lane == 0) {
-        r.dbg[0] = n_rows - row0; r.dbg[1] = sw_total;
-    }
-#endif
     // last row + traceback start (np.argmax of the last row, resquiggle.py:728,1032)
     if constexpr (DIRECT) {
         if (lane == 0) job->top_pos = am;

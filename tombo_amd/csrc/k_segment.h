@@ -31,7 +31,7 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_normalize(ReadState *rs, const De
     ReadState &r = rs[blockIdx.x];
     if (r.status != TBA_OK) return;
     const int tid = threadIdx.x;
-    TBA_PHASE_T0(2);
+    const StampClock<phase_on(PH_NORMALIZE)> stamps(r.dbg);
     const i64 n = r.n_raw;
     const RawSamples<RT> x{raw + r.raw_off};
     double *y = norm + r.raw_off;
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_normalize(ReadState *rs, const De
         double span = smx - smn;
         span = span > 0 ? span : 1.0;
         mn = smn - span; mx = smx + span;
-        TBA_PHASE(2, 0);
+        stamps.stamp(0);
         bool have_med = false;
         if constexpr (raw_is_int<RT>::value) {
             // both medians from one counting pass (the deviations of the scale are ranked from the
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_normalize(ReadState *rs, const De
             if (what == 0) { shift = res; xlo = a_lo; xhi = a_hi; have_med = true; }
             else if (what == 1) { scale = res; dlo = a_lo; dhi = a_hi; have_dev = true; }
             else mad = res;
-            TBA_PHASE(2, 1 + what);
+            stamps.stamp(1 + what);
         }
         if (thresh) {
             lo = med - (mad * o.outlier_thresh);
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_normalize(ReadState *rs, const De
     }
     // The normalised signal is written once, at the end: the passes in between recompute
     // (x - shift) / scale on the fly (same operation, same bits).
-    TBA_PHASE(2, 3);
+    stamps.stamp(3);
     // write_norm == 2: only the reads whose normalised signal k_detect's loader (k_detect.h) will not
     // write on its way: the long ones (k_long.h takes their scan), and the reads whose scale is
     // outside the range in which the loader's reciprocal form of the division is the division bit
@@ -180,8 +180,8 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_normalize(ReadState *rs, const De
             block_map2<2>(n, x, y, [&](double xv) { return (xv - shift) / scale; });
         }
     }
-    TBA_PHASE(2, 4);
-    TBA_PHASE_END(2);
+    stamps.stamp(4);
+    stamps.end();
     if (tid == 0) {
         r.shift = shift; r.scale = scale; r.lower = lo; r.upper = hi;
         r.has_lims = have_lims ? 1 : 0;
@@ -555,17 +555,12 @@ __device__ __forceinline__ W64 w_ballot_to_lane(W64 old, u64 m, int g) // word o
 }
 // Taken scores of the core positions are appended to `dense` on the way (order is irrelevant to
 // the selection that follows): one LDS counter bump per 64 positions.
-template <int R>
+// laps: the wavefront's cycles in the three parts of a tile, its rounds and tiles (tba_phase.h, id 4)
+template <int R, class Laps>
 __device__ i64 peaks_bits(const double *s, unsigned char *st, i64 ns, double *dense, u32 *n_dense,
-                          double &mn, double &mx, i64 *tdbg = nullptr)
+                          double &mn, double &mx, Laps &laps)
 {
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 4
-    // wave 0's cycles in the three parts of a tile, rounds and tiles (sums over its tiles)
-#define TILE_T(i_) do { if (tdbg && threadIdx.x == 0) { const i64 t_ = (i64)__builtin_readcyclecounter(); tdbg[i_] += t_ - tile_t_; tile_t_ = t_; } } while (0)
-    i64 tile_t_ = (i64)__builtin_readcyclecounter();
-#else
-#define TILE_T(i_) do { } while (0)
-#endif
+    laps.mark();
     static_assert(R >= 1 && R < 32, "exclusion radius");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     i64 left = 0;
@@ -615,7 +610,7 @@ __device__ i64 peaks_bits(const double *s, unsigned char *st, i64 ns, double *de
 #pragma unroll
             for (int u = 0; u < GC; u++) cu[u] = nx[u];
         }
-        TILE_T(0);
+        laps.lap(0);
         // validity of the words just outside the tile
         const i64 after = ns - (g0 + PKB_SPAN); // positions of the signal past the tile
         const W64 v_after = after >= 64 ? ones : (after <= 0 ? zero :
@@ -648,12 +643,10 @@ __device__ i64 peaks_bits(const double *s, unsigned char *st, i64 ns, double *de
             const W64 nT = w_andn(w_andn(U, at), au);
             T = w_or(T, nT); S = w_or(S, nS);
             U = w_andn(w_andn(U, nT), nS);
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 4
-            if (tdbg && threadIdx.x == 0) tdbg[3]++;
-#endif
+            laps.count(3);
             if (__ballot((nS.lo | nS.hi | nT.lo | nT.hi) != 0) == 0) break;
         }
-        TILE_T(1);
+        laps.lap(1);
         // core lanes 1..62 -> one state byte per position, taken scores -> dense list.  The
         // slot of every taken position is known up front (prefix of the per-word counts: one
         // counter bump per tile), and the scores of four groups are fetched before they are used.
@@ -707,12 +700,9 @@ __device__ i64 peaks_bits(const double *s, unsigned char *st, i64 ns, double *de
             for (int u = 0; u < OU; u++) if (g + u < 63) out_group(g + u, v[u]);
         }
         if (lane >= 1 && lane < 63) left += __popc(U.lo) + __popc(U.hi);
-        TILE_T(2);
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 4
-        if (tdbg && threadIdx.x == 0) tdbg[4]++;
-#endif
+        laps.lap(2);
+        laps.count(4);
     }
-#undef TILE_T
     return left;
 }
 
@@ -750,14 +740,16 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_peaks(ReadState *rs, const DevPar
     // A position is only decided from neighbours that are themselves decided, so every decision
     // made here is final; positions whose dependency chain leaves the tile stay undecided (0)
     // and are finished by the global rounds below (rare: chains are a few positions long).
-    TBA_PHASE_T0(1);
+    const StampClock<phase_on(PH_PEAKS)> stamps(r.dbg);
     {
         i64 left_undecided = 0;
         if (tid == 0) s_ndense = 0;
         __syncthreads();
         if constexpr (RT > 0) {
             if (m - 1 != RT) { if (tid == 0) r.status = TBA_INTERNAL; return; } // (host dispatch)
-            left_undecided = peaks_bits<RT>(s, st, ns, dn, &s_ndense, mn, mx, r.dbg);
+            LapClock<5, phase_on(PH_PEAKS_TILES)> laps;
+            left_undecided = peaks_bits<RT>(s, st, ns, dn, &s_ndense, mn, mx, laps);
+            if (tid == 0) laps.flush_add(r.dbg, 0, 5);
             fused = true;
             __syncthreads();
         } else { // unusual min_obs_per_base: everything goes through the global rounds
@@ -767,7 +759,7 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_peaks(ReadState *rs, const DevPar
         }
         left_undecided = block_sum_i64(left_undecided, &sm.rad);
         had_leftovers = left_undecided > 0;
-        TBA_PHASE(1, 0);
+        stamps.stamp(0);
         // Phase 2: global rounds for whatever the tiles could not settle
         for (i64 round = 0; left_undecided > 0 && round <= ns; round++) {
             i64 undecided = 0;
@@ -791,7 +783,7 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_peaks(ReadState *rs, const DevPar
             left_undecided = block_sum_i64(undecided, &sm.rad);
         }
     }
-    TBA_PHASE(1, 1);
+    stamps.stamp(1);
     // taken scores -> dense array (+ their range): done by the tiles, unless some positions had
     // to be settled by the global rounds (then one ordered compaction pass redoes it)
     i64 n_taken;
@@ -819,12 +811,12 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_peaks(ReadState *rs, const DevPar
         mx = sm.redd[2 * q + 1] > mx ? sm.redd[2 * q + 1] : mx;
     }
     __syncthreads();
-    TBA_PHASE(1, 2);
+    stamps.stamp(2);
     // score of the num_cpts-th best taken position (ascending rank n_taken - num_cpts)
     const double tval = block_kth([&](i64 i) { return dn[i]; }, n_taken, n_taken - num_cpts, mn,
                                   mx, &sm);
     __syncthreads();
-    TBA_PHASE(1, 3);
+    stamps.stamp(3);
     // one pass: ordered compaction of the picks (the .sort() of tombo_helper.py:76-82), taking
     // every taken position at or above the threshold score, and on the way the counts that tell
     // whether that was right: taken above / at the threshold, all positions above / at it.
@@ -909,9 +901,9 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_peaks(ReadState *rs, const DevPar
     // the reference raises when rank + 1 >= num_cands (cand_idx is advanced past the pick before
     // the bound check, _c_helper.pyx:116-118)
     if (num_cpts > 1 && before + 1 >= num_cands) { if (tid == 0) r.status = TBA_FEWER_CPTS; return; }
-    TBA_PHASE(1, 4);
-    TBA_PHASE(1, 5);
-    TBA_PHASE_END(1);
+    stamps.stamp(4);
+    stamps.stamp(5);
+    stamps.end();
     if (tid == 0) { r.n_cpts = num_cpts; r.n_ev = num_cpts - 1; }
 }
 

@@ -295,15 +295,7 @@ struct BucketSmem {
     i64 n_le;            // number of elements <= result (valid when has_le)
     double redd[2 * (SEL_NT / 64)];
     SelectSmem rad;      // fallback
-#ifdef TBA_PHASE_DEBUG
-    i64 stamp[4];        // cycle counter after: histogram pass, bucket search, gather pass, ranking
-#endif
 };
-#ifdef TBA_PHASE_DEBUG
-#define BS_STAMP(i_) do { if (threadIdx.x == 0) sm->stamp[i_] = (i64)__builtin_readcyclecounter(); } while (0)
-#else
-#define BS_STAMP(i_) do { } while (0)
-#endif
 
 __device__ __forceinline__ int bs_bucket(double v, double lo, double scale)
 {
@@ -401,7 +393,6 @@ __device__ double block_kth_fe(FE fe, i64 n, i64 k, double lo, double hi, Bucket
             if (ok && bs_member(sm, nlev, v)) atomicAdd(&sm->hist[bs_bucket(v, lo, scale)], 1u);
         });
         __syncthreads();
-        BS_STAMP(0);
         if (tid < 64) { // wave 0: locate the bucket of rank k (BS_NB/64 bins per lane)
             const int per = BS_NB / 64;
             i64 c = 0;
@@ -429,7 +420,6 @@ __device__ double block_kth_fe(FE fe, i64 n, i64 k, double lo, double hi, Bucket
         }
         } // !small
         __syncthreads();
-        BS_STAMP(1);
         const i64 cnt = sm->cnt;
         const int nl = sm->nlev;
         if (cnt <= BS_CAP) {
@@ -440,7 +430,6 @@ __device__ double block_kth_fe(FE fe, i64 n, i64 k, double lo, double hi, Bucket
                 if (ok && bs_member(sm, nl, v)) { u32 p = atomicAdd(&sm->n_cand, 1u); if (p < BS_CAP) sm->cand[p] = v; }
             });
             __syncthreads();
-            BS_STAMP(2);
             const int m = (int)cnt;
             const i64 kk = sm->k;
             for (int a = tid; a < m; a += SEL_NT) {
@@ -464,7 +453,6 @@ __device__ double block_kth_fe(FE fe, i64 n, i64 k, double lo, double hi, Bucket
                 }
             }
             __syncthreads();
-            BS_STAMP(3);
             return sm->result;
         }
         // too many members: re-bucket them over their exact min / max

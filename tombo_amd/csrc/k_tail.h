@@ -585,23 +585,14 @@ struct SkipWaveSmem {
     double mu[256], sd[256];       // expected level / sd of the window's bases
     double sg[SIG_LDS ? LEN + 512 : 1]; // the window's signal (L = len + (n - 1) m)
 };
-#ifdef TBA_SKIP_STATS
-#define SKP(i_) do { const i64 t_ = __builtin_readcyclecounter(); if (threadIdx.x == 0) skp[i_] += t_ - tl_; tl_ = __builtin_readcyclecounter(); } while (0)
-#else
-#define SKP(i_) do { } while (0)
-#endif
-template <int LEN, int BITS, bool SIG_LDS>
+// laps 3 .. 7: the wavefront's cycles in the parts of a base (-DTBA_SKIP_STATS, tba_phase.h)
+template <int LEN, int BITS, bool SIG_LDS, class Laps>
 __device__ inline int raw_window_dp_wave(const double *sig, i64 L, const double *means,
-    const double *sds, i64 n, i64 m, bool winsor, double mh, SkipWaveSmem<LEN, BITS, SIG_LDS> &S, i64 *new_segs
-#ifdef TBA_SKIP_STATS
-    , i64 *skp
-#endif
-    )
+    const double *sds, i64 n, i64 m, bool winsor, double mh, SkipWaveSmem<LEN, BITS, SIG_LDS> &S, i64 *new_segs,
+    Laps &laps)
 {
     const int lane = threadIdx.x;
-#ifdef TBA_SKIP_STATS
-    i64 tl_ = __builtin_readcyclecounter();
-#endif
+    laps.mark();
     if (n < 2) return TBA_INTERNAL;
     const i64 len = L - (n - 1) * m;
     if (len <= m || len > LEN) return TBA_INTERNAL; // (the planner's windows always have len > 2 m)
@@ -644,10 +635,10 @@ __device__ inline int raw_window_dp_wave(const double *sig, i64 L, const double 
     for (i64 i = 1; i < n; i++) { // c_base_forward_pass, pyx:99-163
         const double *pf = S.row[(i - 1) & 1];
         double *bf = S.row[i & 1];
-        SKP(3);
+        laps.lap(3);
         zrow(i, zc);
         __syncthreads();
-        SKP(4);
+        laps.lap(4);
         // cum = np.cumsum of the previous base's scores (left by the previous row's walk)
         const i64 k_last = len - m < len - 1 ? len - m : len - 1; // pos <= pe, k = pos - b_s < len
         for (i64 k = 1 + lane; k <= k_last; k += 64) { // diagonal sources
@@ -665,7 +656,7 @@ __device__ inline int raw_window_dp_wave(const double *sig, i64 L, const double 
             bf[k] = diag;                        // (the row two bases back is dead; lane 0 reads a batch, then writes it)
         }
         __syncthreads();
-        SKP(5);
+        laps.lap(5);
         if (lane == 0) { // the stay recurrence, and on the way this base's cumulative z-scores
             double stay_run = zc[0] + pf[m - 1];
             double csum = zc[0];
@@ -709,7 +700,7 @@ __device__ inline int raw_window_dp_wave(const double *sig, i64 L, const double 
             }
         }
         if (__syncthreads_or(bad)) return TBA_INTERNAL;
-        SKP(6);
+        laps.lap(6);
         // traceback test of this base: position sp <-> j = sp - cs - 1 in this row, j + m in the
         // previous one; bit j = previous[j + m] > this[j]
         for (i64 w0 = 0; w0 < words; w0++) {
@@ -721,7 +712,7 @@ __device__ inline int raw_window_dp_wave(const double *sig, i64 L, const double 
         __syncthreads();
         short *t = pl; pl = bl; bl = t;
         double *tz = cum; cum = zc; zc = tz;     // this base's cumulative scores are the next one's `cum`
-        SKP(7);
+        laps.lap(7);
     }
     int rc = TBA_OK;
     if (lane == 0) { // raw_traceback / c_base_traceback, pyx:165-182
@@ -784,40 +775,25 @@ __global__ __launch_bounds__(64) void k_skip_dp_wave(ReadState *rs, const DevPar
         const i64 s = w3[3 * i], e = w3[3 * i + 1], n = e - s;
         const i64 sig_start = ds[s], sig_end = ds[e];
         int rc = TBA_OK;
-#ifdef TBA_SKIP_CLASS_STATS
-        const i64 tcs_ = __builtin_readcyclecounter();
-#endif
-#ifdef TBA_SKIP_STATS
-        const i64 t0_ = __builtin_readcyclecounter();
-#endif
+        LapClock<6, TBA_SKIP_CLASS_STATS_ON> cls_laps; // per read: windows and cycles of every class (tba_phase.h)
+        LapClock<8, TBA_SKIP_STATS_ON> laps;           // per read: windows, cycles, cells, parts of a base
         if (sig_start < 0 || sig_end > r.norm_len) rc = TBA_INTERNAL;
         else {
             rc = raw_window_dp_wave<LEN, BITS, SIG_LDS>(sig + sig_start, sig_end - sig_start,
                                                ref_means + r.ref_off + s, ref_sds + r.ref_off + s, n, m,
-                                               P.do_winsorize_z != 0, P.max_half_z_score, S, out + s + 1
-#ifdef TBA_SKIP_STATS
-                                               , r.dbg
-#endif
-                                               );
+                                               P.do_winsorize_z != 0, P.max_half_z_score, S, out + s + 1, laps);
             wave_mem_fence(); // (lane 0 wrote the boundaries, every lane reads them back)
             if (rc == TBA_OK)
                 for (i64 k = threadIdx.x; k < n - 1; k += 64) out[s + 1 + k] += sig_start;
         }
         // (every failure of the window DP is the same "unexpected error" status)
         if (rc != TBA_OK && threadIdx.x == 0) r.status = rc;
-#ifdef TBA_SKIP_CLASS_STATS   // per read: windows and cycles of every class (tools/stage_times.py, TBA_DBG_PHASES=1: the sums)
-        if (threadIdx.x == 0) {
-            atomicAdd((unsigned long long *)&r.dbg[CLS], 1ull);
-            atomicAdd((unsigned long long *)&r.dbg[3 + CLS], (unsigned long long)(__builtin_readcyclecounter() - tcs_));
+        cls_laps.count(CLS); cls_laps.count(3 + CLS, cls_laps.since_start());
+        laps.count(0); laps.count(1, laps.since_start()); laps.count(2, n * (sig_end - sig_start - (n - 1) * m));
+        if (threadIdx.x == 0) { // (workgroups share a read: the sums by atomicAdd; tools/stage_times.py, TBA_DBG_PHASES=1)
+            cls_laps.flush_atomic(r.dbg, CLS, CLS + 1); cls_laps.flush_atomic(r.dbg, 3 + CLS, 4 + CLS);
+            laps.flush_atomic(r.dbg, 0, 3); laps.flush_add(r.dbg, 3, 8);
         }
-#endif
-#ifdef TBA_SKIP_STATS
-        if (threadIdx.x == 0) {
-            atomicAdd((unsigned long long *)&r.dbg[0], 1ull);
-            atomicAdd((unsigned long long *)&r.dbg[1], (unsigned long long)(__builtin_readcyclecounter() - t0_));
-            atomicAdd((unsigned long long *)&r.dbg[2], (unsigned long long)(n * (sig_end - sig_start - (n - 1) * m)));
-        }
-#endif
     }
 }
 
@@ -844,12 +820,7 @@ __global__ __launch_bounds__(64) void k_skip_dp(ReadState *rs, const DevParams *
     // over global scratch, and the final checks)
     const i64 *w3 = win_scratch + 3 * r.seg_off;
     int rc = TBA_OK;
-#if TBA_PHASE_DEBUG_OR0 == 13
-    // -DTBA_PHASE_DEBUG=13: cycles of the wavefront (0 whole kernel, 1 its window loops, 2 the column phase, 3 the flat
-    // phase, 6 windows)
-    const i64 pt0 = (i64)__builtin_readcyclecounter();
-    i64 pc_lds = 0, pc_arena = 0;
-#endif
+    LapClock<4, phase_on(PH_SKIP_DP)> laps; // cycles of the wavefront: 2 the column phase, 3 the flat phase (tba_phase.h, id 13)
     if constexpr (DNA_LDS) {
         __shared__ SkipLaneSmem S_;
         const bool winsor = P.do_winsorize_z != 0;
@@ -864,9 +835,7 @@ __global__ __launch_bounds__(64) void k_skip_dp(ReadState *rs, const DevParams *
             if (rr != TBA_OK) { rc = rr; break; }
             for (i64 k = 0; k < n - 1; k++) out[s + 1 + k] += sig_start;
         }
-#if TBA_PHASE_DEBUG_OR0 == 13
-        const i64 pt_a = (i64)__builtin_readcyclecounter();
-#endif
+        laps.lap(2);
         // phase 2: the larger ones, SKL_FLAT_N at a time, each in its quarter of the same memory
         for (i64 i0 = 0; i0 < r.n_win; i0 += 64) {
             const i64 i = i0 + lane;
@@ -892,9 +861,7 @@ __global__ __launch_bounds__(64) void k_skip_dp(ReadState *rs, const DevParams *
                 }
             }
         }
-#if TBA_PHASE_DEBUG_OR0 == 13
-        pc_lds = pt_a - pt0; pc_arena = (i64)__builtin_readcyclecounter() - pt_a;
-#endif
+        laps.lap(3);
     }
     // what is left: windows over global scratch (raw_min_obs_per_base > 1: all the small ones; DNA: none in practice)
     for (i64 i = lane; i < r.n_win && rc == TBA_OK; i += 64) {
@@ -908,12 +875,8 @@ __global__ __launch_bounds__(64) void k_skip_dp(ReadState *rs, const DevParams *
         if (rr != TBA_OK) { rc = rr; break; }
         for (i64 k = 0; k < n - 1; k++) out[s + 1 + k] += sig_start;
     }
-#if TBA_PHASE_DEBUG_OR0 == 13
-    {
-        const i64 pt1 = (i64)__builtin_readcyclecounter();
-        if (lane == 0) { r.dbg[1] = pt1 - pt0; r.dbg[2] = pc_lds; r.dbg[3] = pc_arena; r.dbg[6] = r.n_win; }
-    }
-#endif
+    if constexpr (phase_on(PH_SKIP_DP))
+        if (lane == 0) { r.dbg[1] = laps.since_start(); laps.flush(r.dbg, 2, 4); r.dbg[6] = r.n_win; }
     // first failing window in window order decides the status, as in the sequential loop
     // (all window failures here are non-Tombo errors, so any of them is "unexpected")
     if (__syncthreads_or(rc != TBA_OK)) {
@@ -939,9 +902,7 @@ __global__ __launch_bounds__(64) void k_skip_dp(ReadState *rs, const DevParams *
     if (lane == 0) {
         if (out[0] < 0) r.status = TBA_NEG_START;
         else if (out[n_segs - 1] > n_norm) r.status = TBA_PAST_END;
-#if TBA_PHASE_DEBUG_OR0 == 13
-        r.dbg[0] = (i64)__builtin_readcyclecounter() - pt0;
-#endif
+        if constexpr (phase_on(PH_SKIP_DP)) r.dbg[0] = laps.since_start();
     }
 }
 
@@ -981,7 +942,7 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
     if (r.status != TBA_OK) return;
     if (dp->o.skip_seq_scaling) return;
     const int tid = threadIdx.x;
-    TBA_PHASE_T0(3);
+    const StampClock<phase_on(PH_THEIL_SEN)> stamps(r.dbg);
     const double *mu = ref_means + r.ref_off;
     const double *x = norm + r.raw_off + r.read_start;
     const i64 *sg = segs + r.seg_off;
@@ -1022,7 +983,7 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
     }
     const i64 ns = n * (n - 1) / 2;
     if (ns <= 0) { if (tid == 0) r.status = TBA_INTERNAL; return; }
-    TBA_PHASE(3, 0);
+    stamps.stamp(0);
     // all n(n-1)/2 pairs by circular distance d: (i, (i+d) mod n) for d = 1..(n-1)/2, plus
     // (i, i + n/2) for i < n/2 when n is even; slope(i,j) == slope(j,i) bitwise.  The loops have
     // workgroup-uniform trip counts (the visitor ballots).
@@ -1148,7 +1109,7 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
             }
         }
         __syncthreads();
-        TBA_PHASE(3, 1);
+        stamps.stamp(1);
         if (s_win_ok) {
             double A1, B2;
             {
@@ -1220,7 +1181,7 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
             __syncthreads();
             for (int w = 0; w < SEL_NT / 64; w++) mx = fmax(mx, sm.redd[w]);
             const float tau = (float)(0x1p-20 * mx);
-            TBA_PHASE(3, 6);
+            stamps.stamp(6);
             const int lane = tid & 63, wv = tid >> 6;
             i64 wave_lo = 0;
             for (int bk = wv; bk < (nblk + 1) / 2; bk += SEL_NT / 64) {
@@ -1303,7 +1264,7 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
             c_lo = block_sum_i64(c_lo, &sm.rad);
             __threadfence_block();
             __syncthreads();
-            TBA_PHASE(3, 2);
+            stamps.stamp(2);
             const i64 n_c = s_ncand;
             if (n_c <= cap) {
                 // exact slopes of the listed pairs; in-window ones stay (in place of their a),
@@ -1349,16 +1310,16 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
             }
         }
     }
-    TBA_PHASE(3, 3);
+    stamps.stamp(3);
     if (!fast_done) { [[clang::always_inline]] slope = block_median_fe(slopes, ns, 0.5, 1.5, &sm); } // (inlined by request, as the intercepts below)
-    TBA_PHASE(3, 4);
+    stamps.stamp(4);
     // intercepts of a normalised read sit within a unit or so of 0 (first bucket range only)
     // (inlined by request: past the kernel's present size the compiler made it a call, with the closure in scratch)
     double inter;
     [[clang::always_inline]] inter = block_median_fast([=](i64 i) { return s_md[i] - (slope * s_ev[i]); }, n, -2.0,
                                                        2.0, &sm);
-    TBA_PHASE(3, 5);
-    TBA_PHASE_END(3);
+    stamps.stamp(5);
+    stamps.end();
     if (tid == 0) {
         if (slope == 0) { r.status = TBA_RESCALE_FAIL; return; }
         double scale_corr = 1 / slope;

@@ -93,7 +93,7 @@ template <int MODE, bool IDENT = false>
 __device__ __forceinline__ void tbp_block(const unsigned char *mv, int rowb, int roww, const i64 *st,
     int Wi, int thresh, i64 r0, i64 stop, i64 &cur_ev, int &bp_guess, int &rc, i64 *tb,
     i64 &viol_lo, i64 cmp_lo, i64 &merged_row, const unsigned char *strip, int strip_s0, i64 n_static,
-    int *dbg_stores = nullptr)
+    int *dbg_stores)
 {
     constexpr bool EXT = MODE != TBP_A, VER = MODE == TBP_V;
     i64 stv[TBR];
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, 
         bool walking = mine;
         while (__any(walking)) {
             if (walking) {
-                tbp_block<TBP_A>(mv, rowb, roww, st, Wi, thresh, r0, lo, cur, guess, rcA, tb, viol_lo, 0, none, strip, strip_s0, n_stat);
+                tbp_block<TBP_A>(mv, rowb, roww, st, Wi, thresh, r0, lo, cur, guess, rcA, tb, viol_lo, 0, none, strip, strip_s0, n_stat, nullptr);
                 r0 -= TBR;
                 if (rcA != TBA_OK || r0 <= lo) walking = false;
             }
@@ -322,13 +322,10 @@ __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, 
     const i64 lo2 = c + 1 >= n_chunks - 1 || lo - L < 0 ? 0 : lo - L; // lo of chunk c + 1
     i64 merged_row = TBP_NONE;
     int rcB = TBA_OK;
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 12
-    int dbg_st = 0;
-    int *dbg_stp = &dbg_st;
-    const bool dbg_imm = ext && cur == nxt_start;
-#else
-    int *dbg_stp = nullptr;
-#endif
+    LapClock<8, phase_on(PH_TB_PAR)> counts;       // what phase B did, added up per read (tba_phase.h, id 12)
+    int dbg_st = 0;                                // rows overwritten in phase B (counted in that build only)
+    int *dbg_stp = phase_on(PH_TB_PAR) ? &dbg_st : nullptr;
+    const bool dbg_imm = phase_on(PH_TB_PAR) && ext && cur == nxt_start; // merged at once: the state is equal on entry
     {
         bool walking = ext;
         if (ext && cur == nxt_start) { merged_row = lo; walking = false; } // (entering row lo = its hi)
@@ -347,21 +344,16 @@ __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, 
     // expects the verifier to catch exactly those reads and the results to be the oracle's all the same)
     if (ext && c == 1 && lo >= 1 && ri % TBA_TB_INJECT == 3) tb[lo - 1] += 1;
 #endif
-#if defined(TBA_PHASE_DEBUG) && TBA_PHASE_DEBUG == 12
-    // per read: 0 lanes that extended, 1 merged at once (state equal on entry), 2 merged later, 3 rows
-    // overwritten in phase B, 4 chunks, 5 sum of the rows merged at relative to the chunk top, 6 lanes
-    // whose phase A died, 7 sum of phase-A start states
-    if (on) {
-        auto add = [&](int k, i64 v) { atomicAdd((unsigned long long *)&r.dbg[k], (unsigned long long)v); };
-        if (ext) add(0, 1);
-        if (dbg_imm) add(1, 1);
-        if (ext && !dbg_imm && merged_row != TBP_NONE) { add(2, 1); add(5, lo - merged_row); }
-        add(3, dbg_st);
-        if (c == 0) add(4, n_chunks);
-        if (mine && rcA != TBA_OK) add(6, 1);
-        if (mine) add(7, start_ev);
+    if constexpr (phase_on(PH_TB_PAR)) {
+        if (ext) counts.count(0);
+        if (dbg_imm) counts.count(1);
+        if (ext && !dbg_imm && merged_row != TBP_NONE) { counts.count(2); counts.count(5, lo - merged_row); }
+        counts.count(3, dbg_st);
+        if (c == 0) counts.count(4, n_chunks);
+        if (mine && rcA != TBA_OK) counts.count(6);
+        if (mine) counts.count(7, start_ev);
+        if (on) counts.flush_atomic(r.dbg, 0, 8);  // (every lane of the read)
     }
-#endif
     // ---- the chain, top down (uniform over the group: every lane runs the same loop)
     int status = TBA_OK;
     bool broken = false, from_b = false;            // from_b: the status is a phase B's
@@ -420,7 +412,7 @@ __global__ __launch_bounds__(64) void k_start_tb(ReadState *rs, i64 n_reads, con
         int guess = (int)r.top_pos;
         tb[nb] = cur + 1;
         for (i64 r0 = nb; r0 >= 1 && rc == TBA_OK; r0 -= TBR)
-            tbp_block<TBP_A, true>(mv, rowb, roww, nullptr, (int)bw, -1, r0, 0, cur, guess, rc, tb, viol, 0, none, nullptr, -1, 0);
+            tbp_block<TBP_A, true>(mv, rowb, roww, nullptr, (int)bw, -1, r0, 0, cur, guess, rc, tb, viol, 0, none, nullptr, -1, 0, nullptr);
     }
     const double *ev = event_means + r.ev_off;
     if (rc == TBA_OK && mode == DP_START_TRY && dp->o.check_start_score) {

@@ -20,23 +20,7 @@ typedef uint32_t u32;
 #define SCALE_CHANGE_THRESH 0.1   // _default_parameters.py:170
 #define MAX_TS_POINTS 1000        // _default_parameters.py:178
 
-// optional per-phase cycle stamps into ReadState.dbg: build with -DTBA_PHASE_DEBUG=<kernel>
-// (1 k_peaks, 2 k_normalize, 3 k_theil_sen: stamps cumulative from the kernel's start; 4: the
-// three parts of k_peaks' tiles, summed over wave 0's tiles; 5: the parts of a k_dp row, summed
-// over the rows of the read)
-#ifdef TBA_PHASE_DEBUG
-#define TBA_PHASE_DEBUG_OR0 TBA_PHASE_DEBUG
-#define TBA_PHASE_T0(k_) const i64 tba_t0_ = (k_) == TBA_PHASE_DEBUG ? (i64)__builtin_readcyclecounter() : 0; \
-    const i64 tba_w0_ = (k_) == TBA_PHASE_DEBUG ? (i64)__builtin_amdgcn_s_memrealtime() : 0
-// dbg[7]: the same interval on the constant 100 MHz counter (gives the shader clock of the run)
-#define TBA_PHASE_END(k_) do { if ((k_) == TBA_PHASE_DEBUG && threadIdx.x == 0) r.dbg[7] = (i64)__builtin_amdgcn_s_memrealtime() - tba_w0_; } while (0)
-#define TBA_PHASE(k_, i_) do { if ((k_) == TBA_PHASE_DEBUG && threadIdx.x == 0) r.dbg[i_] = (i64)__builtin_readcyclecounter() - tba_t0_; } while (0)
-#else
-#define TBA_PHASE_DEBUG_OR0 0
-#define TBA_PHASE_T0(k_) do { } while (0)
-#define TBA_PHASE(k_, i_) do { } while (0)
-#define TBA_PHASE_END(k_) do { } while (0)
-#endif
+#include "tba_phase.h" // profiling builds: the switches, the clocks, the meaning of ReadState.dbg
 
 enum { PATH_NONE = 0, PATH_ADAPTIVE = 1, PATH_STATIC = 2 };
 enum { ST_NONE = 0, ST_TRY = 1, ST_OK = 2, ST_RETRY = 3, ST_STATIC = 4 };
