@@ -311,3 +311,71 @@ def test_long_read_lists_are_cut_and_oversized_batches_refused():
     seqs = [np.zeros(8, np.uint8)] * 65536
     with pytest.raises(_native.EngineError):
         eng.upload(_native.make_params(params), _native.make_opts(), raws, seqs)
+
+
+def test_host_batch_path_five_ways_and_recorded_digest(monkeypatch):
+    """What the host layer hands the library, pinned: 40 reads (four of them over 1 000 bases, so their
+    rows of the subsample block matter; one that fails on the device, one without a signal, one with
+    scale values and limits, one with scale values alone) as one batch, streamed, streamed with copied
+    outputs, streamed with pooled views from the first read on and streamed without the signal -- all
+    five agree read for read, and the boundaries and scale values of the successful reads hash to the
+    value recorded on an MI355X before the host batch path was reorganised."""
+    import hashlib
+    from tombo_amd import resquiggle as rq, synth, tombo_stats as ts, tombo_helper as th
+    samp = th.seqSampleType('DNA', False)
+    model = ts.TomboModel(seq_samp_type=samp)
+    params = ts.load_resquiggle_parameters(samp)
+    rng = np.random.RandomState(29)
+    n_bases = [int(x) for x in rng.randint(150, 301, 40)]
+    for i in (3, 17, 26, 38):
+        n_bases[i] = 1200
+    mrs = [synth.synth_map_res(model, nb, 7300 + i, **synth.DNA_SYNTH) for i, nb in enumerate(n_bases)]
+    mrs[5] = mrs[5]._replace(raw_signal=mrs[5].raw_signal[:400])      # fails on the device
+    mrs[9] = mrs[9]._replace(raw_signal=None)                         # fails on the host (message 21)
+    for i, lims in ((12, True), (13, False)):
+        raw = mrs[i].raw_signal
+        shift = float(np.median(raw))
+        scale = float(np.median(np.abs(raw - shift)))
+        mrs[i] = mrs[i]._replace(scale_values=th.scaleValues(
+            shift, scale, -5.0 if lims else None, 5.0 if lims else None, None))   # (limits: normalised units)
+
+    def run(env, **kw):
+        for k in ('TBA_API_STREAM', 'TBA_API_STREAM_MIN', 'TBA_API_ZERO_COPY', 'TBA_API_ZERO_COPY_MIN', 'TBA_API_CUTS'):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        return rq.resquiggle_batch(mrs, model, params, outlier_thresh=5.0, seq_samp_type=samp,
+                                   subsample_seed=3, **kw)
+    runs = [run({'TBA_API_STREAM': '0'}),
+            run({'TBA_API_STREAM_MIN': '12'}),
+            run({'TBA_API_STREAM_MIN': '12', 'TBA_API_ZERO_COPY': '0'}),
+            run({'TBA_API_STREAM_MIN': '12', 'TBA_API_ZERO_COPY_MIN': '1'}),
+            run({'TBA_API_STREAM_MIN': '12'}, return_signal=False)]
+    one = runs[0]
+    assert all(len(r) == len(mrs) for r in runs)
+    failed = [i for i, x in enumerate(one) if isinstance(x, Exception)]
+    assert failed == [5, 9], [(i, str(one[i])) for i in failed]
+    from tombo_amd import errors
+    assert str(one[9]) == errors.MESSAGES[21]
+    for k, other in enumerate(runs[1:], 1):
+        for i, (x, y) in enumerate(zip(one, other)):
+            assert isinstance(x, Exception) == isinstance(y, Exception), (k, i)
+            if isinstance(x, Exception):
+                assert type(x) is type(y) and str(x) == str(y), (k, i)
+                continue
+            np.testing.assert_array_equal(x.segs, y.segs)
+            assert x.scale_values == y.scale_values, (k, i)
+            assert x.sig_match_score == y.sig_match_score, (k, i)
+            assert x.read_start_rel_to_raw == y.read_start_rel_to_raw and x.genome_seq == y.genome_seq, (k, i)
+            if k < 4:
+                np.testing.assert_array_equal(x.raw_signal, y.raw_signal)
+            else:
+                assert y.raw_signal is None
+    h = hashlib.sha256()
+    for x in one:
+        if not isinstance(x, Exception):
+            h.update(np.ascontiguousarray(x.segs, dtype=np.int64).tobytes())
+            sv = x.scale_values
+            h.update(np.array([np.nan if v is None else v for v in
+                               (sv.shift, sv.scale, sv.lower_lim, sv.upper_lim)], dtype=np.float64).tobytes())
+    assert h.hexdigest() == '288b6118c6a3c6016272bf8397c96fff6fae39939df8158b4b5c2e4c9471745b'

@@ -10,6 +10,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from ._default_parameters import MAX_POINTS_FOR_THEIL_SEN, SIG_MATCH_THRESH
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TBA_LIB_PATH: an alternative build of the same library (profiling builds with one of -DTBA_PHASE_DEBUG=<id> /
 # -DTBA_SWEEP_STATS / -DTBA_SKIP_STATS / -DTBA_SKIP_CLASS_STATS, A/B comparisons of a kernel variant)
@@ -118,6 +120,26 @@ ABI_VERSION = 12  # TBA_ABI_VERSION of include/tombo_amd.h
 STAGE_NAMES = ["normalize", "cumsum", "scores", "peaks", "event_means", "ref_levels",
                "start_dp", "start_tb", "prep", "main_dp", "main_tb", "skip_resolve", "theil_sen",
                "rescale_score", "stalls", "total"]
+
+# what Engine.get returns per selector: (element type, shape); a name is that count of the uploaded batch
+# (n reads, raw samples, ref bases, seg boundaries = bases + reads, ev events -- at least one element)
+_GET_SHAPES = {
+    GET_N_CPTS: (np.int64, ('n',)), GET_DP_READ_START: (np.int64, ('n',)),
+    GET_SEG_SV: (np.float64, ('n', 4)), GET_START: (np.float64, ('n', 4)),
+    GET_THEIL_SEN: (np.float64, ('n', 4)), GET_PATH: (np.int32, ('n', 4)), GET_DP_FORM: (np.int32, ('n', 4)),
+    GET_LAST_ROW: (np.float64, ('n', MAX_BAND)), GET_KERNEL_MS: (np.float32, (32,)),
+    GET_DEBUG_COUNTERS: (np.int64, ('n', 8)),
+    GET_VALID_CPTS: (np.int64, ('ev',)), GET_EVENT_MEANS: (np.float64, ('ev',)),
+    GET_SEG_NORM: (np.float64, ('raw',)),
+    GET_BAND_STARTS: (np.int64, ('ref',)), GET_REF_MEANS: (np.float64, ('ref',)), GET_REF_SDS: (np.float64, ('ref',)),
+    GET_READ_TB: (np.int64, ('seg',)), GET_DP_SEGS: (np.int64, ('seg',)), GET_SEGS: (np.int64, ('seg',)),
+    GET_STATUS: (np.int32, ('n',)), GET_START_FAIL: (np.int32, ('n',)),
+    GET_N_STALL: (np.int64, ('n',)), GET_STALL_OFF: (np.int64, ('n',)),
+    GET_SAMP_IND: (np.int64, ('n', MAX_POINTS_FOR_THEIL_SEN)),
+    GET_TB_PARALLEL: (np.int32, ('n',)), GET_ED_FUSED: (np.int32, ('n',)), GET_DP_WORKGROUP: (np.int32, ('n',)),
+    GET_ED_FORM: (np.int32, ('n',)), GET_TB_FORM: (np.int32, ('n',)), GET_TB_VERIFY_FAIL: (np.int32, ('n',)),
+    GET_ED_TAKEN_POS: (np.int32, ('raw_x2',)), GET_ED_N_TAKEN: (np.int64, ('n',)),
+}
 
 _lib = None
 
@@ -229,12 +251,16 @@ def make_params(rp):
 def make_opts(outlier_thresh=None, const_scale=None, skip_seq_scaling=False,
               sig_match_thresh=None, max_raw_cpts=200, min_event_to_seq_ratio=1.1,
               skip_norm_out=False, reverse_raw=False, stall_params=None, subsample_seed=None,
-              del_fix_window=2, max_del_fix_window=10, extra_sig_factor=1.1, subsample_first_read=0):
-    """tba_opts.  `reverse_raw` / `stall_params` (a th.stallParams of the running-window-mean
+              del_fix_window=2, max_del_fix_window=10, extra_sig_factor=1.1, subsample_first_read=0,
+              seq_samp_type=None):
+    """tba_opts.  `seq_samp_type` (a th.seqSampleType): `sig_match_thresh` is that sample type's
+    SIG_MATCH_THRESH unless given; `reverse_raw` / `stall_params` (a th.stallParams of the running-window-mean
     method): the worker's RNA preparation on the device (resquiggle.py:1506-1530);
     `subsample_seed` (int): the Theil-Sen subsample is drawn on the device;
     `del_fix_window` / `max_del_fix_window` / `extra_sig_factor`: the keyword arguments of
     resolve_skipped_bases_with_raw (resquiggle.py:405-407)."""
+    if sig_match_thresh is None and seq_samp_type is not None:
+        sig_match_thresh = SIG_MATCH_THRESH[seq_samp_type.name]
     o = Opts()
     o.del_fix_window, o.max_del_fix_window = int(del_fix_window), int(max_del_fix_window)
     o.extra_sig_factor = float(extra_sig_factor)
@@ -411,14 +437,17 @@ class Engine(object):
     def __init__(self, device=0):
         self._L = lib()
         self._h = C.c_void_p()
+        self.device = int(device)
+        self.kmer_width = None
+        self._model_key = None
+        self._keep = self._keep_out = None    # the arrays of the upload / the downloads in flight
+        self._stage = None                    # page-locked staging, made on first use (host_stage)
+        self._ne_override = None              # set_num_events: event counts forced on the next upload
+        self.skip_norm_out = False            # of the last upload's options
         rc = self._L.tba_engine_create(C.c_int(device), C.byref(self._h))
         if rc != 0:
             raise EngineError('tba_engine_create failed (%d): %s' % (
                 rc, self._L.tba_last_error().decode()))
-        self.device = int(device)
-        self.kmer_width = None
-        self._keep = None
-        self._model_key = None
 
     def _check(self, rc, what):
         if rc != 0:
@@ -426,7 +455,7 @@ class Engine(object):
                                                      self._L.tba_last_error().decode()))
 
     def close(self):
-        if getattr(self, '_stage', None) is not None:
+        if self._stage is not None:
             self._stage.close()
             self._stage = None
         if self._h:
@@ -464,17 +493,7 @@ class Engine(object):
                stall_ints=None):
         """raws: list of sample arrays (all int16, all float32, or anything else -> float64);
         seqs: list of uint8 code arrays."""
-        n = len(raws)
-        raw_off = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum([r.shape[0] for r in raws], out=raw_off[1:])
-        seq_off = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum([s.shape[0] for s in seqs], out=seq_off[1:])
-        dts = set(np.asarray(r).dtype for r in raws)
-        dt = next(iter(dts)) if len(dts) == 1 and next(iter(dts)) in RAW_DTYPES \
-            else np.dtype(np.float64)
-        raw = np.ascontiguousarray(np.concatenate(raws), dtype=dt) \
-            if n > 1 else np.ascontiguousarray(raws[0], dtype=dt)
-        seq = np.ascontiguousarray(np.concatenate(seqs), dtype=np.uint8)
+        raw, raw_off, seq, seq_off, _ = pack_code_reads(raws, seqs)
         st, sto = pack_stalls(stall_ints)
         self.upload_packed(params, opts, raw, raw_off, seq, seq_off, sv_in=sv_in,
                            sv_flags=sv_flags, samp_ind=samp_ind, stall_ints=st, stall_off=sto,
@@ -504,7 +523,7 @@ class Engine(object):
         ne = np.maximum(n_raw // int(params.mean_obs_per_event),
                         (self.B * float(opts.min_event_to_seq_ratio)).astype(np.int64))
         ne[(self.B <= 0) | (n_raw <= 0)] = 0
-        ov = getattr(self, '_ne_override', None)
+        ov = self._ne_override
         if ov is not None and ov.shape[0] == n:
             ne = np.where((ov > 0) & (self.B > 0) & (n_raw > 0), ov, ne)
         self._ne_override = None
@@ -585,10 +604,9 @@ class Engine(object):
 
     def host_stage(self):
         """this engine's reusable page-locked staging arrays (PinnedStage)"""
-        st = getattr(self, '_stage', None)
-        if st is None:
-            st = self._stage = PinnedStage()
-        return st
+        if self._stage is None:
+            self._stage = PinnedStage()
+        return self._stage
 
     def query(self):
         """True while work of this engine is still in flight (never blocks)"""
@@ -624,7 +642,7 @@ class Engine(object):
 
     def download(self, want_norm=True):
         n = self.n
-        want_norm = want_norm and not getattr(self, 'skip_norm_out', False)
+        want_norm = want_norm and not self.skip_norm_out
         status = np.zeros(n, np.int32)
         segs = np.zeros(int(self.seg_off[-1]), np.int64)
         rs = np.zeros(n, np.int64)
@@ -640,35 +658,11 @@ class Engine(object):
                     score=score, changed=changed)
 
     def get(self, what):
-        n = self.n
-        shapes = {
-            GET_N_CPTS: (np.int64, n), GET_DP_READ_START: (np.int64, n),
-            GET_SEG_SV: (np.float64, (n, 4)), GET_START: (np.float64, (n, 4)),
-            GET_THEIL_SEN: (np.float64, (n, 4)), GET_PATH: (np.int32, (n, 4)), GET_DP_FORM: (np.int32, (n, 4)),
-            GET_LAST_ROW: (np.float64, (n, MAX_BAND)), GET_KERNEL_MS: (np.float32, 32),
-            GET_DEBUG_COUNTERS: (np.int64, (n, 8)),
-            GET_SEG_NORM: (np.float64, self.n_raw_total),
-            GET_BAND_STARTS: (np.int64, int(self.ref_off[-1])),
-            GET_READ_TB: (np.int64, int(self.seg_off[-1])),
-            GET_DP_SEGS: (np.int64, int(self.seg_off[-1])),
-            GET_SEGS: (np.int64, int(self.seg_off[-1])),
-            GET_REF_MEANS: (np.float64, int(self.ref_off[-1])),
-            GET_REF_SDS: (np.float64, int(self.ref_off[-1])),
-            GET_STATUS: (np.int32, n), GET_START_FAIL: (np.int32, n),
-            GET_N_STALL: (np.int64, n), GET_STALL_OFF: (np.int64, n),
-            GET_SAMP_IND: (np.int64, (n, 1000)),
-            GET_TB_PARALLEL: (np.int32, n), GET_ED_FUSED: (np.int32, n), GET_DP_WORKGROUP: (np.int32, n),
-            GET_ED_FORM: (np.int32, n), GET_TB_FORM: (np.int32, n), GET_TB_VERIFY_FAIL: (np.int32, n),
-            GET_ED_TAKEN_POS: (np.int32, 2 * self.n_raw_total), GET_ED_N_TAKEN: (np.int64, n),
-        }
-        if what in (GET_VALID_CPTS, GET_EVENT_MEANS):
-            out = np.zeros(max(int(self.ev_off[-1]), 1),
-                           np.int64 if what == GET_VALID_CPTS else np.float64)
-            self._check(self._L.tba_batch_get(self._h, C.c_int(what), out.ctypes.data_as(C.c_void_p),
-                                              i64(out.nbytes)), 'tba_batch_get')
-            return out
-        dt, shp = shapes[what]
-        out = np.zeros(shp, dt)
+        """tba_batch_get: one intermediate of the uploaded batch (a TBA_GET_* selector) as a fresh array"""
+        dims = dict(n=self.n, raw=self.n_raw_total, raw_x2=2 * self.n_raw_total, ref=int(self.ref_off[-1]),
+                    seg=int(self.seg_off[-1]), ev=max(int(self.ev_off[-1]), 1))
+        dt, shape = _GET_SHAPES[what]
+        out = np.zeros([dims.get(d, d) for d in shape], dt)
         self._check(self._L.tba_batch_get(self._h, C.c_int(what), out.ctypes.data_as(C.c_void_p),
                                           i64(out.nbytes)), 'tba_batch_get')
         return out
@@ -958,18 +952,52 @@ def identify_stalls(eng, raw, sp):
     return out[:cnt.value]
 
 
-def pack_stalls(stall_ints):
+def _offsets(items):
+    """int64 [n + 1]: where item i starts in the concatenation of `items`"""
+    off = np.zeros(len(items) + 1, np.int64)
+    np.cumsum(list(map(len, items)), out=off[1:])
+    return off
+
+
+def pack_stalls(stall_ints, or_none=False):
     """per-read stall interval lists (None / empty allowed) -> (int64 [m, 2], int64 offsets[n + 1]),
-    or (None, None) for None"""
-    if stall_ints is None:
+    or (None, None) for None and, with `or_none`, when no read has an interval (else one zero row)"""
+    if stall_ints is None or (or_none and not any(s is not None and len(s) for s in stall_ints)):
         return None, None
-    cnt = [0 if s is None else len(s) for s in stall_ints]
-    sto = np.zeros(len(cnt) + 1, dtype=np.int64)
-    np.cumsum(cnt, out=sto[1:])
     rows = [np.array([[int(a), int(b)] for a, b in s], dtype=np.int64).reshape(-1, 2)
             for s in stall_ints if s is not None and len(s)]
     st = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((1, 2), np.int64)
-    return st, sto
+    return st, _offsets([() if s is None else s for s in stall_ints])
+
+
+def pack_scale_values(scale_values):
+    """per-read th.scaleValues (or None) -> (sv_in float64 [n, 4]: shift, scale, lower_lim, upper_lim;
+    sv_flags int32 [n]: 1 given, | 2 with both limits), or (None, None) when no read has any"""
+    if all(sv is None for sv in scale_values):
+        return None, None
+    sv_in = np.zeros((len(scale_values), 4))
+    sv_flags = np.zeros(len(scale_values), np.int32)
+    for i, sv in enumerate(scale_values):
+        if sv is None:
+            continue
+        sv_in[i, :2] = sv.shift, sv.scale
+        sv_flags[i] = 1
+        if sv.lower_lim is not None and sv.upper_lim is not None:
+            sv_in[i, 2:] = sv.lower_lim, sv.upper_lim
+            sv_flags[i] |= 2
+    return sv_in, sv_flags
+
+
+def pack_samp_inds(samp_inds, out=None):
+    """per-read Theil-Sen subsamples (MAX_POINTS_FOR_THEIL_SEN indices, or None) -> int64 [n, 1000], filled into
+    `out` (reused staging, page-locked memory) when given.  A read of more than 1000 bases needs its row; the
+    row of a read without a subsample is set to -1 whatever it held: the kernel rejects a negative index
+    (TBA_INTERNAL for that read) instead of fitting a line through an earlier batch's indices -- it cannot tell
+    a missing subsample from a given one."""
+    si = np.empty((len(samp_inds), MAX_POINTS_FOR_THEIL_SEN), np.int64) if out is None else out
+    for i, s in enumerate(samp_inds):
+        si[i] = -1 if s is None else s
+    return si
 
 
 class PinnedStage(object):
@@ -1006,6 +1034,37 @@ _str_ptr.argtypes = [C.py_object]
 _str_ptr.restype = C.c_void_p
 
 
+def sample_dtype(raws):
+    """the sample type a batch is uploaded in: the reads' own when all share one of RAW_DTYPES, else float64"""
+    dts = set(r.dtype if isinstance(r, np.ndarray) else np.asarray(r).dtype for r in raws)
+    dt = dts.pop() if len(dts) == 1 else None
+    return dt if dt in RAW_DTYPES else np.dtype(np.float64)
+
+
+def _csr_targets(raw_off, seq_off, dt, pinned=False, stage=None):
+    """(raw, seq, keep): the two big arrays of a packed batch -- views of `stage`'s reusable page-locked buffers,
+    else `pinned`: fresh page-locked memory (alive while `keep` is referenced), else plain numpy arrays"""
+    n_raw, n_seq = int(raw_off[-1]), int(seq_off[-1])
+    if stage is not None:
+        return stage.get('raw', n_raw, dt), stage.get('seq', n_seq, np.uint8), []
+    if pinned:
+        pr, ps = PinnedArray(n_raw, dt), PinnedArray(n_seq, np.uint8)
+        return pr.a, ps.a, [pr, ps]
+    return np.empty(n_raw, dt), np.empty(n_seq, np.uint8), []
+
+
+def pack_code_reads(raws, seqs, pinned=False):
+    """per-read sample arrays and sequences given as uint8 code arrays -> the five-tuple of pack_reads
+    (one concatenation each, straight into the target)"""
+    dt = sample_dtype(raws)
+    raw_off, seq_off = _offsets(raws), _offsets(seqs)
+    raw, seq, keep = _csr_targets(raw_off, seq_off, dt, pinned=pinned)
+    if len(raws):
+        np.concatenate(raws, out=raw, casting='unsafe')
+        np.concatenate(seqs, out=seq, casting='unsafe')
+    return raw, raw_off, seq, seq_off, keep
+
+
 def pack_reads(raws, seqs, reverse=False, pinned=False, n_threads=None, stage=None):
     """tba_pack_reads: per-read sample arrays (one dtype of RAW_DTYPES, else float64) and
     sequences (str / bytes of ACGT) -> (raw, raw_off, seq, seq_off, keep) CSR arrays, copied by
@@ -1014,19 +1073,15 @@ def pack_reads(raws, seqs, reverse=False, pinned=False, n_threads=None, stage=No
     through `keep`); else plain numpy arrays."""
     L = lib()
     n = len(raws)
-    dt = None
-    for r in raws:
-        if not isinstance(r, np.ndarray) or (dt is not None and r.dtype != dt) or \
-                not r.flags.c_contiguous:
-            dt = False
+    dt = raws[0].dtype if n and isinstance(raws[0], np.ndarray) else None
+    as_is = dt in RAW_DTYPES          # (one pass when the reads can be taken as they are)
+    for r in raws if as_is else ():
+        if not (isinstance(r, np.ndarray) and r.dtype == dt and r.flags.c_contiguous):
+            as_is = False
             break
-        dt = r.dtype
-    if dt is False or dt is None or dt not in RAW_DTYPES:
-        raws = [np.asarray(r) for r in raws]
-        dts = set(r.dtype for r in raws)
-        dt = next(iter(dts)) if len(dts) == 1 and next(iter(dts)) in RAW_DTYPES else np.dtype(np.float64)
-        raws = [r if r.dtype == dt and r.flags.c_contiguous else np.ascontiguousarray(r, dtype=dt)
-                for r in raws]
+    if not as_is:
+        dt = sample_dtype(raws)
+        raws = [np.ascontiguousarray(r, dtype=dt) for r in raws]
     # sequences: the UTF-8 view of a str is its own buffer for ASCII text (no copy); the strings
     # themselves stay referenced by the caller's list for the duration of the call
     seq_ptr = [_str_ptr(s) if type(s) is str else None for s in seqs]
@@ -1034,21 +1089,10 @@ def pack_reads(raws, seqs, reverse=False, pinned=False, n_threads=None, stage=No
         seqs = [s if type(s) is str else bytes(s) for s in seqs]
         seq_ptr = [_str_ptr(s) if type(s) is str else C.cast(C.c_char_p(s), C.c_void_p).value
                    for s in seqs]
-    raw_off = np.zeros(n + 1, np.int64)
-    np.cumsum([r.shape[0] for r in raws], out=raw_off[1:])
-    seq_off = np.zeros(n + 1, np.int64)
-    np.cumsum([len(s) for s in seqs], out=seq_off[1:])
+    raw_off, seq_off = _offsets(raws), _offsets(seqs)
     if any(not s.isascii() for s in seqs if type(s) is str):
         raise ValueError('sequences must be ASCII')
-    keep = []
-    if stage is not None:
-        raw, seq = stage.get('raw', raw_off[-1], dt), stage.get('seq', seq_off[-1], np.uint8)
-    elif pinned:
-        pr, ps = PinnedArray(int(raw_off[-1]), dt), PinnedArray(int(seq_off[-1]), np.uint8)
-        keep = [pr, ps]
-        raw, seq = pr.a, ps.a
-    else:
-        raw, seq = np.empty(int(raw_off[-1]), dt), np.empty(int(seq_off[-1]), np.uint8)
+    raw, seq, keep = _csr_targets(raw_off, seq_off, dt, pinned=pinned, stage=stage)
     rp = (C.c_void_p * n)(*[_addr(r) for r in raws])
     sp = (C.c_void_p * n)(*seq_ptr)
     if n_threads is None:

@@ -6,6 +6,7 @@ ABI in include/tombo_amd.h.  `resquiggle_batch` is the throughput entry point: m
 kernel sequence.  Host code here only marshals buffers.
 """
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -15,8 +16,7 @@ from . import errors
 from . import _native
 from ._default_parameters import (
     DEL_FIX_WINDOW, MAX_DEL_FIX_WINDOW, EXTRA_SIG_FACTOR,
-    MAX_RAW_CPTS, MIN_EVENT_TO_SEQ_RATIO, SIG_MATCH_THRESH, DNA_SAMP_TYPE, RNA_SAMP_TYPE,
-    MAX_POINTS_FOR_THEIL_SEN)
+    MAX_RAW_CPTS, MIN_EVENT_TO_SEQ_RATIO, DNA_SAMP_TYPE, RNA_SAMP_TYPE, MAX_POINTS_FOR_THEIL_SEN)
 from .mapping import get_read_seq, map_read   # (tombo.resquiggle's names; the glue lives there)
 
 __all__ = ['resquiggle_read', 'resquiggle_batch', 'resquiggle_batch_iters', 'adjust_map_res',
@@ -30,6 +30,7 @@ _ENGINES = {}
 
 def default_device():
     """$LOCAL_RANK (one process per GPU) modulo the visible devices, else 0"""
+    # (the launcher's variable, not a switch of this module: those are read in _api_switches)
     device = int(os.environ.get('LOCAL_RANK', '0'))
     n = _native.lib().tba_device_count()
     return device % n if n > 0 else device
@@ -50,12 +51,39 @@ def _draw_samp_ind(n_bases):
     return np.random.choice(n_bases, MAX_POINTS_FOR_THEIL_SEN, replace=False)
 
 
+# The TBA_API_* environment switches of `resquiggle_batch`, read once per call (_api_switches) and handed down:
+#   stream         TBA_API_STREAM=0: one sub-batch at a time (passing `engine=` does that too)
+#   stream_min     TBA_API_STREAM_MIN (2400; tests lower it): reads from which a list is streamed
+#   cuts           TBA_API_CUTS (measurement aid): sub-batches of a streamed list, at least 2
+#   chain          TBA_API_CHAIN=1 / 0 (measurement aid): sub-batches compute one after the other / together
+#   trace          TBA_API_TRACE: the stream's timeline on stderr
+#   zero_copy      TBA_API_ZERO_COPY=0: every result owns pageable memory
+#   zero_copy_min  TBA_API_ZERO_COPY_MIN (32): sub-batches of fewer reads always copy
+_Switches = namedtuple('_Switches', 'stream stream_min cuts chain trace zero_copy zero_copy_min')
+
+
+def _api_switches():
+    env = os.environ.get
+    return _Switches(
+        stream=env('TBA_API_STREAM', '1') != '0', stream_min=int(env('TBA_API_STREAM_MIN', '2400')),
+        cuts=int(env('TBA_API_CUTS')) if env('TBA_API_CUTS') else None,
+        chain=env('TBA_API_CHAIN') == '1' if env('TBA_API_CHAIN') else None, trace=bool(env('TBA_API_TRACE')),
+        zero_copy=env('TBA_API_ZERO_COPY', '1') != '0', zero_copy_min=int(env('TBA_API_ZERO_COPY_MIN', '32')))
+
+
+# One `resquiggle_batch` call as its sub-batches see it: the whole lists (a sub-batch takes [a, b) of them), the
+# engine's structs built once (`params`, `opts`; every other option is read off `opts`), what the results need
+# as the caller gave it, and the switches.
+_Job = namedtuple('_Job', 'map_results raws pre_err samp_inds std_ref rsqgl_params params opts outlier_thresh '
+                          'const_scale return_signal switches')
+
+
 def resquiggle_batch(map_results, std_ref, rsqgl_params, outlier_thresh=None,
                      all_raw_signals=None, max_raw_cpts=MAX_RAW_CPTS,
                      min_event_to_seq_ratio=MIN_EVENT_TO_SEQ_RATIO, const_scale=None,
                      skip_seq_scaling=False,
                      seq_samp_type=th.seqSampleType(DNA_SAMP_TYPE, False),
-                     samp_inds=None, engine=None, return_debug=False, mem_budget=None,
+                     samp_inds=None, engine=None, mem_budget=None,
                      reverse_raw=False, stall_params=None, subsample_seed=None, return_signal=True):
     """resquiggle_read over a list of `resquiggleResults` (mapping results).
 
@@ -84,14 +112,14 @@ def resquiggle_batch(map_results, std_ref, rsqgl_params, outlier_thresh=None,
 
     Marshalling is native: the per-read arrays are packed into page-locked CSR staging by
     threads (`tba_pack_reads`), transfers are DMA, and the per-read result arrays are cut out of
-    the flat downloads by threads (`tba_unpack_reads`).
+    the flat downloads by threads (`tba_unpack_reads`).  The engine's raw per-read arrays of the
+    last (sub-)batch: pass `engine=` and call `engine.download()` afterwards.
     """
     eng = get_engine() if engine is None else engine
     n = len(map_results)
     if n == 0:
         return []
     eng.ensure_model(std_ref)
-    K = std_ref.kmer_width
     raws = []
     pre_err = [None] * n
     for i, mr in enumerate(map_results):
@@ -101,66 +129,67 @@ def resquiggle_batch(map_results, std_ref, rsqgl_params, outlier_thresh=None,
             pre_err[i] = th.TomboError(errors.MESSAGES[21])
             raw = np.zeros(1)
         raws.append(raw if isinstance(raw, np.ndarray) else np.asarray(raw))
-    args = dict(std_ref=std_ref, rsqgl_params=rsqgl_params, outlier_thresh=outlier_thresh,
-                max_raw_cpts=max_raw_cpts, min_event_to_seq_ratio=min_event_to_seq_ratio,
-                const_scale=const_scale, skip_seq_scaling=skip_seq_scaling,
-                seq_samp_type=seq_samp_type, reverse_raw=reverse_raw, stall_params=stall_params,
-                return_signal=return_signal, return_debug=return_debug)
-    cuts = [(0, n)]
-    if n > 1 and not return_debug:
-        from . import planner
+    opts = _native.make_opts(
+        outlier_thresh=outlier_thresh, const_scale=const_scale, skip_seq_scaling=skip_seq_scaling,
+        seq_samp_type=seq_samp_type, max_raw_cpts=max_raw_cpts, min_event_to_seq_ratio=min_event_to_seq_ratio,
+        reverse_raw=reverse_raw, stall_params=stall_params, subsample_seed=subsample_seed,
+        skip_norm_out=not return_signal)
+    job = _Job(map_results, raws, pre_err, samp_inds, std_ref, rsqgl_params, _native.make_params(rsqgl_params), opts,
+               outlier_thresh, const_scale, return_signal, _api_switches())
+    cuts, stream_cuts = [(0, n)], 1
+    if n > 1:
         if mem_budget is None:
             # (what is free now plus what this engine already holds; no floor: on a device that
             # other engines share a floor would stop the planner from cutting, and the upload
             # would fail with TBA_E_NOMEM instead)
             held = eng.held_bytes() + sum(e.held_bytes() for e in _STREAM_ENGINES.get(eng.device, []))
             mem_budget = 0.6 * (eng.device_mem()[0] + held)
-        p_ = _native.make_params(rsqgl_params)
-        o_ = _native.make_opts(min_event_to_seq_ratio=min_event_to_seq_ratio, reverse_raw=reverse_raw,
-                               stall_params=stall_params, subsample_seed=subsample_seed,
-                               skip_norm_out=not return_signal)
-        n_raw = [r.shape[0] for r in raws]
-        seq_len = [len(mr.genome_seq) for mr in map_results]
-        # Sub-batches.  By memory (the engine's own footprint function) and by host staging, and --
-        # for a list worth it -- by the stream: with several sub-batches in flight on as many
-        # engines the packing of one, the kernels of another and the download + unpacking of a
-        # third overlap (_stream_batches); one sub-batch should still fill the machine's DP
-        # wavefront slots together with its neighbours (~1 600 reads each: 6 cuts of a 5 000-read list
-        # took 110 ms of GPU time for what one batch does in 50).
-        stream_cuts = 1
-        stream_min = int(os.environ.get('TBA_API_STREAM_MIN', '2400'))   # (tests lower it)
-        if engine is None and n >= stream_min and os.environ.get('TBA_API_STREAM', '1') != '0':
-            stream_cuts = max(3, min(12, n // max(2 * stream_min // 3, 1)))
-            if os.environ.get('TBA_API_CUTS'):     # (measurement aid)
-                stream_cuts = max(2, int(os.environ['TBA_API_CUTS']))
-        slot_budget = mem_budget if stream_cuts == 1 else mem_budget / _STREAM_SLOTS
-        host_cap = 1 << 28   # samples per sub-batch: 2 GiB of float64 each way in page-locked staging
-        target = -(-n // stream_cuts)
-        if n > planner.MAX_READS or sum(n_raw) > host_cap or stream_cuts > 1 or \
-                planner.exact_bytes(n_raw, seq_len, p_, o_, K) > slot_budget:
-            # consecutive cuts (sort=False): the Theil-Sen subsamples are drawn from the global
-            # RNG in read order, exactly as for one big batch
-            parts = planner.plan_batches(n_raw, seq_len, p_, o_, K, slot_budget, sort=False,
-                                         max_reads=min(planner.MAX_READS, max(target, 1)))
-            cuts = []
-            for idx in parts:   # ... and by host staging
-                a0, acc = int(idx[0]), 0
-                for i in idx:
-                    if acc + n_raw[i] > host_cap and i > a0:
-                        cuts.append((a0, int(i)))
-                        a0, acc = int(i), 0
-                    acc += n_raw[i]
-                cuts.append((a0, int(idx[-1]) + 1))
+        cuts, stream_cuts = _plan_cuts([r.shape[0] for r in raws], [len(mr.genome_seq) for mr in map_results],
+                                       job.params, opts, std_ref.kmer_width, mem_budget, job.switches,
+                                       may_stream=engine is None)
     if len(cuts) > 1:
-        engines = _stream_engines(eng, std_ref) if engine is None and stream_cuts > 1 else [eng]
-        return _stream_batches(engines, cuts, map_results, raws, pre_err, samp_inds, subsample_seed, args)
-    ctx = _submit_batch(eng, 0, n, map_results, raws, pre_err, samp_inds, subsample_seed, args)
-    _sync_batch(ctx)
-    _unpack_batch(ctx)
-    results = _build_results(ctx)
-    if return_debug:
-        return results, ctx['out']
-    return results
+        return _stream_batches(_stream_engines(eng, std_ref) if stream_cuts > 1 else [eng], cuts, job)
+    batch = _submit_batch(eng, 0, n, job)
+    batch.sync()
+    batch.unpack()
+    return batch.results()
+
+
+def _plan_cuts(n_raw, seq_len, params, opts, kmer_width, mem_budget, switches, may_stream=True):
+    """The consecutive sub-batches [(a, b)] of a read list (samples and sequence length per read), and for how
+    many the stream was planned (1: the list is not streamed).  By memory (the engine's own footprint
+    function; `params` / `opts`: the structs of the call, `mem_budget`: device bytes) and by host staging, and --
+    for a list worth it -- by the stream: with several sub-batches in flight on as many
+    engines the packing of one, the kernels of another and the download + unpacking of a
+    third overlap (_stream_batches); one sub-batch should still fill the machine's DP
+    wavefront slots together with its neighbours (~1 600 reads each: 6 cuts of a 5 000-read list
+    took 110 ms of GPU time for what one batch does in 50).  Host only."""
+    from . import planner
+    n = len(n_raw)
+    stream_cuts = 1
+    if may_stream and switches.stream and n >= switches.stream_min:
+        stream_cuts = max(3, min(12, n // max(2 * switches.stream_min // 3, 1)))
+        if switches.cuts is not None:
+            stream_cuts = max(2, switches.cuts)
+    slot_budget = mem_budget if stream_cuts == 1 else mem_budget / _STREAM_SLOTS
+    host_cap = 1 << 28   # samples per sub-batch: 2 GiB of float64 each way in page-locked staging
+    if not (n > planner.MAX_READS or sum(n_raw) > host_cap or stream_cuts > 1 or
+            planner.exact_bytes(n_raw, seq_len, params, opts, kmer_width) > slot_budget):
+        return [(0, n)], stream_cuts
+    # consecutive cuts (sort=False): the Theil-Sen subsamples are drawn from the global
+    # RNG in read order, exactly as for one big batch
+    parts = planner.plan_batches(n_raw, seq_len, params, opts, kmer_width, slot_budget, sort=False,
+                                 max_reads=min(planner.MAX_READS, max(-(-n // stream_cuts), 1)))
+    cuts = []
+    for idx in parts:   # ... and by host staging
+        a0, acc = int(idx[0]), 0
+        for i in idx:
+            if acc + n_raw[i] > host_cap and i > a0:
+                cuts.append((a0, int(i)))
+                a0, acc = int(i), 0
+            acc += n_raw[i]
+        cuts.append((a0, int(idx[-1]) + 1))
+    return cuts, stream_cuts
 
 
 _STREAM_SLOTS = 3
@@ -190,68 +219,63 @@ def _stream_engines(eng, std_ref):
     return engines
 
 
-def _stream_batches(engines, cuts, map_results, raws, pre_err, samp_inds, subsample_seed, args):
+def _stream_batches(engines, cuts, job):
     """Sub-batches through `engines` in rotation: while one computes, the next is packed and
     uploaded and the one before is downloaded, cut into per-read arrays (a helper thread: native
     copies, GIL released) and turned into results (this thread).  Results in input order."""
     from concurrent.futures import ThreadPoolExecutor
     import time
-    trace = [] if os.environ.get('TBA_API_TRACE') else None   # (what, sub-batch, seconds since the call)
+    trace = [] if job.switches.trace else None   # (what, sub-batch, seconds since the call)
     t_call = time.perf_counter()
 
     def mark(what, k):
         if trace is not None:
             trace.append((what, k, round(time.perf_counter() - t_call, 4)))
-    out, pending = [], []          # pending: contexts in submission order
+    out, pending = [], []          # pending: sub-batches in submission order
     S = len(engines)
-    last_ctx = [None] * S          # the context that used engine k last (its staging is reused)
+    last = [None] * S              # the sub-batch that used engine k last (its staging is reused)
     # With the signal coming back the call is bound by the download (0.74 MB per 10 kb read): the
     # sub-batches then compute one after the other (tba_batch_wait_for), so that the download of one
     # runs under the kernels of the next; without it they share the device (small batches do not
     # fill it alone) -- measured on 5 000 reads of 10 kb, three cuts: all three finished computing
     # together after 65 ms and only then 74 ms of downloads began.
-    chain = bool(args['return_signal'])
-    if os.environ.get('TBA_API_CHAIN'):            # (measurement aid)
-        chain = os.environ['TBA_API_CHAIN'] == '1'
+    chain = bool(job.return_signal) if job.switches.chain is None else job.switches.chain
     ex = ThreadPoolExecutor(1)
     try:
-        def unpack(ctx):
-            _unpack_batch(ctx)
-            mark('unpacked', ctx['k'])
+        def unpack(b):
+            b.unpack()
+            mark('unpacked', b.k)
 
         def pump():
             """retire what the device has finished (sync is immediate then; the unpacking goes to
             the helper), build the results of what the helper is done with, in order"""
             moved = False
-            for c in pending:
-                if 'unpack' not in c and not c['eng'].query():
-                    _sync_batch(c)
-                    mark('synced', c['k'])
-                    c['unpack'] = ex.submit(unpack, c)
+            for b in pending:
+                if not b.synced and not b.eng.query():
+                    b.sync()
+                    mark('synced', b.k)
+                    b.unpacking = ex.submit(unpack, b)
                     moved = True
-            while pending and 'unpack' in pending[0] and pending[0]['unpack'].done():
-                c = pending.pop(0)
-                c['unpack'].result()
-                out.extend(_build_results(c))
-                mark('built', c['k'])
+            while pending and pending[0].unpacked():
+                b = pending.pop(0)
+                b.unpacking.result()
+                out.extend(b.results())
+                mark('built', b.k)
                 moved = True
             return moved
 
         for k, (a, b) in enumerate(cuts):
             e = k % S
-            old = last_ctx[e]
-            while old is not None and not ('unpack' in old and old['unpack'].done()):
+            while last[e] is not None and not last[e].unpacked():
                 if not pump():           # its page-locked outputs must be free again
                     time.sleep(0.0002)
             mark('submit', k)
-            # (the device-side draw of a read is keyed by its index in the whole list -- _submit_batch hands
+            # (the device-side draw of a read is keyed by its index in the whole list -- the sub-batch hands
             # `a` to the engine -- so the result does not depend on how the list was cut)
-            ctx = _submit_batch(engines[e], a, b, map_results, raws, pre_err, samp_inds, subsample_seed, args,
-                                after=engines[(k - 1) % S] if chain and k > 0 else None)
-            ctx['k'] = k
+            last[e] = _submit_batch(engines[e], a, b, job, after=engines[(k - 1) % S] if chain and k > 0 else None)
+            last[e].k = k
             mark('submitted', k)
-            last_ctx[e] = ctx
-            pending.append(ctx)
+            pending.append(last[e])
             pump()
         while pending:
             if not pump():
@@ -275,180 +299,159 @@ def _stream_batches(engines, cuts, map_results, raws, pre_err, samp_inds, subsam
     return out
 
 
-def _submit_batch(eng, a, b, map_results, raws, pre_err, samp_inds, subsample_seed, args, after=None):
-    """pack reads [a, b), upload, enqueue the kernel sequence and the downloads; returns the
-    context `_sync_batch` / `_unpack_batch` / `_build_results` finish"""
-    std_ref, rsqgl_params = args['std_ref'], args['rsqgl_params']
-    return_signal, return_debug = args['return_signal'], args['return_debug']
-    mrs, rws = map_results[a:b], raws[a:b]
-    n = b - a
-    K = std_ref.kmer_width
-    stage = eng.host_stage()
-    raw, raw_off, seq, seq_off, _ = _native.pack_reads(
-        rws, [mr.genome_seq for mr in mrs], stage=stage)
-    sv_in = sv_flags = None
-    if any(mr.scale_values is not None for mr in mrs):
-        sv_in = np.zeros((n, 4))
-        sv_flags = np.zeros(n, np.int32)
-        for i, mr in enumerate(mrs):
-            sv = mr.scale_values
-            if sv is None:
-                continue
-            sv_in[i, 0], sv_in[i, 1] = sv.shift, sv.scale
-            sv_flags[i] = 1
-            if sv.lower_lim is not None and sv.upper_lim is not None:
-                sv_in[i, 2], sv_in[i, 3] = sv.lower_lim, sv.upper_lim
-                sv_flags[i] |= 2
-    st = sto = None
-    if args['stall_params'] is None:
-        stalls = [mr.stall_ints for mr in mrs]
-        if any(s is not None and len(s) for s in stalls):
-            st, sto = _native.pack_stalls(stalls)
-    nb = np.diff(seq_off) - K + 1
-    si = None
-    rng_state = np.random.get_state() if len(map_results) == 1 else None
-    if not args['skip_seq_scaling'] and subsample_seed is None and (nb > MAX_POINTS_FOR_THEIL_SEN).any():
-        si = stage.get('si', n * MAX_POINTS_FOR_THEIL_SEN, np.int64).reshape(n, MAX_POINTS_FOR_THEIL_SEN)
-        si[:] = -1   # (rows of reads that need none; the kernel rejects a negative index)
-        for i in np.flatnonzero(nb > MAX_POINTS_FOR_THEIL_SEN):
-            si[i] = _draw_samp_ind(int(nb[i])) if samp_inds is None or samp_inds[a + i] is None \
-                else samp_inds[a + i]
-    p = _native.make_params(rsqgl_params)
-    seq_samp_type = args['seq_samp_type']
-    o = _native.make_opts(
-        outlier_thresh=args['outlier_thresh'], const_scale=args['const_scale'],
-        skip_seq_scaling=args['skip_seq_scaling'],
-        sig_match_thresh=None if seq_samp_type is None else SIG_MATCH_THRESH[seq_samp_type.name],
-        max_raw_cpts=args['max_raw_cpts'], min_event_to_seq_ratio=args['min_event_to_seq_ratio'],
-        reverse_raw=args['reverse_raw'], stall_params=args['stall_params'], subsample_seed=subsample_seed,
-        subsample_first_read=a, skip_norm_out=not return_signal and not return_debug)
-    eng.upload_packed(p, o, raw, raw_off, seq, seq_off, sv_in=sv_in, sv_flags=sv_flags,
-                      samp_ind=si, stall_ints=st, stall_off=sto)
-    if after is not None:
-        eng.wait_for(after)   # this batch's kernels start when that engine's sequence has finished
-    eng.enqueue()
-    ctx = dict(eng=eng, a=a, b=b, n=n, nb=nb, raw_off=raw_off, seg_off=eng.seg_off.copy(),
-               map_results=mrs, pre_err=pre_err[a:b], rng_state=rng_state, args=args)
-    if not return_debug:
-        ctx['o_res'] = stage.get('res', n, _native.RESULT_DTYPE)
+def _submit_batch(eng, a, b, job, after=None):
+    """every sub-batch of every call starts here: reads [a, b) of `job` packed, uploaded and enqueued on `eng`"""
+    return _Batch(job, eng, a, b).submit(after)
+
+
+class _Batch(object):
+    """Reads [a, b) of a `resquiggle_batch` call in flight on one engine: submit() -> sync() -> unpack()
+    -> results(); each step fills the attributes the next one reads."""
+
+    def __init__(self, job, eng, a, b):
+        self.job, self.eng, self.a, self.b, self.n = job, eng, a, b, b - a
+        self.map_results, self.pre_err = job.map_results[a:b], job.pre_err[a:b]
+        self.k = 0                # its place in a stream
+        self.synced = False
+        self.unpacking = None     # the helper's future, once a stream has handed it over
+        # submit: bases per read, the offsets of the flat arrays, numpy's RNG state before a batch of one, the
+        # download targets, and whether the results will be views of pooled page-locked blocks (else copies out
+        # of the engine's reusable staging)
+        self.nb = self.raw_off = self.seg_off = self.rng_state = None
+        self.o_res = self.o_segs = self.o_norm = self.views = None
+        # sync: a copy of the per-read records, the indices of the successful reads, stalls found on the device
+        self.rec = self.ok = self.dev_stalls = None
+        # unpack: per successful read its boundaries and normalised signal
+        self.segs_l = self.norm_l = None
+
+    def unpacked(self):
+        return self.unpacking is not None and self.unpacking.done()
+
+    def submit(self, after=None):
+        """pack, upload, enqueue the kernel sequence (behind engine `after`'s, when given) and the downloads"""
+        job, eng, a, b, n = self.job, self.eng, self.a, self.b, self.n
+        mrs, opts = self.map_results, job.opts
+        K = job.std_ref.kmer_width
+        stage = eng.host_stage()
+        raw, raw_off, seq, seq_off, _ = _native.pack_reads(job.raws[a:b], [mr.genome_seq for mr in mrs], stage=stage)
+        sv_in, sv_flags = _native.pack_scale_values([mr.scale_values for mr in mrs])
+        st = sto = None
+        if not opts.detect_stalls:
+            st, sto = _native.pack_stalls([mr.stall_ints for mr in mrs], or_none=True)
+        self.nb = nb = np.diff(seq_off) - K + 1
+        si = None
+        self.rng_state = np.random.get_state() if len(job.map_results) == 1 else None
+        if not opts.skip_seq_scaling and not opts.device_subsample and (nb > MAX_POINTS_FOR_THEIL_SEN).any():
+            # (a row per read of more than 1000 bases: the caller's, else drawn now, in read order)
+            given = job.samp_inds[a:b] if job.samp_inds is not None else [None] * n
+            rows = [None if nb_i <= MAX_POINTS_FOR_THEIL_SEN else _draw_samp_ind(nb_i) if g is None else g
+                    for nb_i, g in zip(nb.tolist(), given)]
+            si = _native.pack_samp_inds(rows, out=stage.get(
+                'si', n * MAX_POINTS_FOR_THEIL_SEN, np.int64).reshape(n, MAX_POINTS_FOR_THEIL_SEN))
+        if opts.device_subsample:
+            # (the draw of a read is keyed by its index in the whole list; `opts` is shared by the call's
+            # sub-batches: the engine copies the struct at upload, and sub-batches are submitted by one thread)
+            opts.subsample_first_read = a
+        eng.upload_packed(job.params, opts, raw, raw_off, seq, seq_off, sv_in=sv_in, sv_flags=sv_flags,
+                          samp_ind=si, stall_ints=st, stall_off=sto)
+        if after is not None:
+            eng.wait_for(after)   # this batch's kernels start when that engine's sequence has finished
+        eng.enqueue()
+        self.raw_off, self.seg_off = raw_off, eng.seg_off.copy()
+        self.o_res = stage.get('res', n, _native.RESULT_DTYPE)
         # The boundaries and the normalised signal are downloaded into page-locked blocks leased from the
         # process-wide result pool, and the per-read arrays of the results are VIEWS of those blocks (no
         # second copy of 0.8 MB per 10 kb read; a block returns to the pool when the last result that
         # looks into it is gone).  Without a lease (pool budget spent, TBA_API_ZERO_COPY=0): the engine's
         # reusable staging + a native copy into pageable memory, as before.
         # (small batches copy: a page-locked block per handful of reads is not worth holding)
-        pool = _native.result_pool() if n >= int(os.environ.get('TBA_API_ZERO_COPY_MIN', '32')) and \
-            os.environ.get('TBA_API_ZERO_COPY', '1') != '0' else None
+        sw, want_norm = job.switches, job.return_signal
+        pool = _native.result_pool() if sw.zero_copy and n >= sw.zero_copy_min else None
         n_segs, n_norm = int(eng.seg_off[-1]), int(eng.n_raw_total)
         l_segs = pool.lease(n_segs, np.int64) if pool is not None else None
-        l_norm = pool.lease(n_norm, np.float64) if pool is not None and return_signal and l_segs is not None else None
-        ctx['views'] = l_segs is not None and (l_norm is not None or not return_signal)
-        if not ctx['views']:
-            l_segs = l_norm = None
-        ctx['o_segs'] = l_segs if ctx['views'] else stage.get('segs', n_segs, np.int64)
-        ctx['o_norm'] = (l_norm if ctx['views'] else stage.get('norm', n_norm, np.float64)) if return_signal else None
-        eng.download_async(results=ctx['o_res'], segs64=ctx['o_segs'], norm=ctx['o_norm'])
-    return ctx
+        l_norm = pool.lease(n_norm, np.float64) if want_norm and l_segs is not None else None
+        self.views = l_segs is not None and (l_norm is not None or not want_norm)
+        if not self.views:
+            l_segs = None         # (a boundaries block without its signal block goes back to the pool now)
+        self.o_segs = l_segs if self.views else stage.get('segs', n_segs, np.int64)
+        self.o_norm = (l_norm if self.views else stage.get('norm', n_norm, np.float64)) if want_norm else None
+        eng.download_async(results=self.o_res, segs64=self.o_segs, norm=self.o_norm)
+        return self
+
+    def sync(self):
+        """wait for the batch; the per-read records (a copy: the staging is reused)"""
+        self.eng.sync()
+        self.synced = True
+        self.rec = rec = self.o_res.copy()
+        if self.rng_state is not None and int(rec['status'][0]) not in (0, 19, 20):
+            # a batch of one is the reference's call: it only touches the RNG once the read reaches
+            # sequence rescaling (calc_kmer_fitted_shift_scale), so a read that failed earlier leaves
+            # the seeded stream where it was
+            np.random.set_state(self.rng_state)
+        self.ok = np.flatnonzero((rec['status'] == 0) & np.array([e is None for e in self.pre_err]))
+        self.dev_stalls = self.eng.stall_ints() if self.job.opts.detect_stalls else None
+
+    def unpack(self):
+        """the per-read boundary / signal arrays out of the flat downloads"""
+        ok, want_norm = self.ok, self.job.return_signal
+        self.norm_l = [None] * len(ok)
+        if self.views:
+            so, ro, okl = self.seg_off.tolist(), self.raw_off.tolist(), ok.tolist()
+            self.segs_l = [self.o_segs[so[i]:so[i + 1]] for i in okl]
+            if want_norm:
+                nl = self.rec['norm_len'].tolist()
+                self.norm_l = [self.o_norm[ro[i]:ro[i] + nl[i]] for i in okl]
+            self.o_segs = self.o_norm = None     # (only the results hold the blocks now)
+        else:                                    # (native threads)
+            self.segs_l = _native.unpack_reads(self.o_segs, self.seg_off[:-1][ok], self.nb[ok] + 1)
+            if want_norm:
+                self.norm_l = _native.unpack_reads(self.o_norm, self.raw_off[:-1][ok], self.rec['norm_len'][ok])
+
+    def results(self):
+        """resquiggleResults / TomboError per read of the batch"""
+        results = [None] * self.n
+        # (thousands of small tuples are born here and none of them is garbage: with the cyclic
+        # collector running, its generation passes over the caller's live objects were a quarter of the
+        # host time of a 5 000-read call)
+        import gc
+        gc_was = gc.isenabled()
+        gc.disable()
+        try:
+            _fill_results(results, self)
+        finally:
+            if gc_was:
+                gc.enable()
+        status = self.rec['status']
+        for i, err in enumerate(self.pre_err):
+            if results[i] is not None:
+                continue
+            st_i = int(status[i])
+            if err is not None:
+                results[i] = err
+            elif st_i in errors.MESSAGES:
+                results[i] = th.TomboError(errors.MESSAGES[st_i])
+            else:
+                results[i] = RuntimeError('Unexpected error in resquiggle engine (status %d)' % st_i)
+        return results
 
 
-def _sync_batch(ctx):
-    """wait for the batch; the small per-read outputs (copies: the staging is reused)"""
-    eng, args = ctx['eng'], ctx['args']
-    eng.sync()
-    if args['return_debug']:
-        out = eng.download()
-    else:
-        o_res = ctx['o_res']
-        out = dict(status=o_res['status'].copy(), read_start=o_res['read_start_rel_to_raw'].copy(),
-                   norm_len=o_res['norm_len'].copy(), score=o_res['sig_match_score'].copy(),
-                   changed=o_res['norm_params_changed'].copy(),
-                   sv=np.stack([o_res['shift'], o_res['scale'], o_res['lower_lim'],
-                                o_res['upper_lim']], axis=1))
-    ctx['out'] = out
-    status = np.asarray(out['status'])
-    if ctx['rng_state'] is not None and int(status[0]) not in (0, 19, 20):
-        # a batch of one is the reference's call: it only touches the RNG once the read reaches
-        # sequence rescaling (calc_kmer_fitted_shift_scale), so a read that failed earlier leaves
-        # the seeded stream where it was
-        np.random.set_state(ctx['rng_state'])
-    ctx['ok'] = np.flatnonzero((status == 0) & np.array([e is None for e in ctx['pre_err']]))
-    ctx['dev_stalls'] = eng.stall_ints() if args['stall_params'] is not None else None
-
-
-def _unpack_batch(ctx):
-    """the per-read boundary / signal arrays out of the flat downloads (native threads)"""
-    out, ok, nb, args = ctx['out'], ctx['ok'], ctx['nb'], ctx['args']
-    if not args['return_debug'] and ctx.get('views'):
-        so, ro = ctx['seg_off'].tolist(), ctx['raw_off'].tolist()
-        o_segs, o_norm = ctx['o_segs'], ctx['o_norm']
-        okl = ok.tolist()
-        ctx['segs_l'] = [o_segs[so[i]:so[i + 1]] for i in okl]
-        if args['return_signal']:
-            nl = out['norm_len'].tolist()
-            ctx['norm_l'] = [o_norm[ro[i]:ro[i] + nl[i]] for i in okl]
-        else:
-            ctx['norm_l'] = [None] * len(okl)
-        ctx['o_segs'] = ctx['o_norm'] = None     # (only the results hold the blocks now)
-    elif not args['return_debug']:
-        ctx['segs_l'] = _native.unpack_reads(ctx['o_segs'], ctx['seg_off'][:-1][ok], nb[ok] + 1)
-        ctx['norm_l'] = _native.unpack_reads(ctx['o_norm'], ctx['raw_off'][:-1][ok], out['norm_len'][ok]) \
-            if args['return_signal'] else [None] * len(ok)
-    else:
-        so, ro = ctx['seg_off'], ctx['raw_off']
-        ctx['segs_l'] = [out['segs'][so[i]:so[i + 1]].copy() for i in ok]
-        ctx['norm_l'] = [out['norm'][ro[i]:ro[i] + int(out['norm_len'][i])].copy() for i in ok]
-
-
-def _build_results(ctx):
-    """resquiggleResults / TomboError per read of the batch"""
-    out, ok, args, n = ctx['out'], ctx['ok'], ctx['args'], ctx['n']
-    std_ref = args['std_ref']
-    K, cp = std_ref.kmer_width, std_ref.central_pos
-    dn = K - cp - 1
-    results = [None] * n
-    status = np.asarray(out['status'])
-    # (thousands of small tuples are born here and none of them is garbage: with the cyclic
-    # collector running, its generation passes over the caller's live objects were a quarter of the
-    # host time of a 5 000-read call)
-    import gc
-    gc_was = gc.isenabled()
-    gc.disable()
-    try:
-        _fill_results(results, ok, ctx['map_results'], out['sv'], out['read_start'], out['score'],
-                      out['changed'], ctx['segs_l'], ctx['norm_l'], ctx['dev_stalls'],
-                      args['skip_seq_scaling'], args['outlier_thresh'], args['rsqgl_params'],
-                      args['const_scale'], cp, dn)
-    finally:
-        if gc_was:
-            gc.enable()
-    pre_err = ctx['pre_err']
-    for i in range(n):
-        if results[i] is not None:
-            continue
-        if pre_err[i] is not None:
-            results[i] = pre_err[i]
-            continue
-        st_i = int(status[i])
-        if st_i in errors.MESSAGES:
-            results[i] = th.TomboError(errors.MESSAGES[st_i])
-        else:
-            results[i] = RuntimeError('Unexpected error in resquiggle engine (status %d)' % st_i)
-    return results
-
-
-def _fill_results(results, ok, map_results, svs, rstart, score, changed, segs_l, norm_l, dev_stalls,
-                  skip_seq_scaling, outlier_thresh, rsqgl_params, const_scale, cp, dn):
+def _fill_results(results, batch):
     """the resquiggleResults of the successful reads of one batch (resquiggle.py:1210-1214)"""
+    job, map_results, segs_l, norm_l, dev_stalls = batch.job, batch.map_results, batch.segs_l, batch.norm_l, batch.dev_stalls
+    skip_seq_scaling, outlier_thresh, const_scale = job.opts.skip_seq_scaling, job.outlier_thresh, job.const_scale
+    cp = job.std_ref.central_pos
+    dn = job.std_ref.kmer_width - cp - 1
     # Built field by field through tuple.__new__ (namedtuple._replace walks a keyword dict per call: 3 us
     # per read, the largest item of a 5 000-read call's host time), scalars converted once per batch.
     RR, SV, new = th.resquiggleResults, th.scaleValues, tuple.__new__
     I_SEQ, I_RAW, I_START, I_SEGS, I_SV, I_SCORE, I_CH, I_STALL = (
         RR._fields.index(f) for f in ('genome_seq', 'raw_signal', 'read_start_rel_to_raw', 'segs',
                                       'scale_values', 'sig_match_score', 'norm_params_changed', 'stall_ints'))
-    okl = ok.tolist() if hasattr(ok, 'tolist') else list(ok)
-    sv_rows = np.asarray(svs)[okl][:, :4].tolist() if len(okl) else []
-    rs_l, sc_l, ch_l = (np.asarray(x)[okl].tolist() if len(okl) else [] for x in (rstart, score, changed))
-    t_test = bool(rsqgl_params.use_t_test_seg)
+    okl = batch.ok.tolist()
+    rec = batch.rec[okl]
+    sv_rows = list(zip(*(rec[f].tolist() for f in ('shift', 'scale', 'lower_lim', 'upper_lim'))))
+    rs_l, sc_l, ch_l = (rec[f].tolist() for f in ('read_start_rel_to_raw', 'sig_match_score', 'norm_params_changed'))
+    t_test = bool(job.rsqgl_params.use_t_test_seg)
     for k, i in enumerate(okl):
         mr = map_results[i]
         sh, scl, lo, hi = sv_rows[k]
@@ -537,12 +540,7 @@ def segment_signal(map_res, num_events, rsqgl_params, outlier_thresh=None, const
         _set_model(eng, _LevelsOnly)
     raw = np.ascontiguousarray(map_res.raw_signal, dtype=np.float64)
     sv = map_res.scale_values
-    sv_in = sv_flags = None
-    if sv is not None:
-        has_lims = sv.lower_lim is not None and sv.upper_lim is not None
-        sv_in = np.array([[sv.shift, sv.scale, sv.lower_lim if has_lims else 0.0,
-                           sv.upper_lim if has_lims else 0.0]])
-        sv_flags = np.array([1 | (2 if has_lims else 0)], np.int32)
+    sv_in, sv_flags = _native.pack_scale_values([sv])
     stalls = map_res.stall_ints
     K = eng.kmer_width
     eng.set_num_events([int(num_events)])
@@ -589,8 +587,7 @@ def find_adaptive_base_assignment(
                                   'off in the reference and not part of this engine')
     eng = get_engine()
     _set_model(eng, std_ref)
-    opts = _native.make_opts(
-        sig_match_thresh=None if seq_samp_type is None else SIG_MATCH_THRESH[seq_samp_type.name])
+    opts = _native.make_opts(seq_samp_type=seq_samp_type)
     _upload_events(eng, rsqgl_params, opts, valid_cpts, event_means, ts.encode_seq(genome_seq))
     eng.run_stages(_native.STAGE_REF_LEVELS, _native.STAGE_ASSIGN)
     _status_or_raise(eng)
@@ -624,8 +621,7 @@ def find_seq_start_in_events(event_means, r_ref_means, r_ref_sds, rsqgl_params, 
     eng = get_engine()
     p = rsqgl_params._replace(start_n_bases=int(num_bases), start_bw=int(num_events),
                               start_save_bw=int(num_events))
-    opts = _native.make_opts(
-        sig_match_thresh=None if seq_samp_type is None else SIG_MATCH_THRESH[seq_samp_type.name])
+    opts = _native.make_opts(seq_samp_type=seq_samp_type)
     _upload_levels(eng, p, opts, event_means, r_ref_means, r_ref_sds)
     eng.run_stages(_native.STAGE_START, _native.STAGE_START)
     _status_or_raise(eng)
@@ -693,12 +689,10 @@ def adjust_map_res(map_res, seq_samp_type):
     return map_res
 
 
-def _run_iters(map_results, idx, std_ref, params, outlier_thresh, const_scale, skip_seq_scaling,
-               seq_samp_type, max_scaling_iters, engine, n_passes, prep):
-    """run_rsqgl_iters (resquiggle.py:1492-1504) for the reads `idx`, round by round"""
-    res = dict(zip(idx, resquiggle_batch(
-        [map_results[i] for i in idx], std_ref, params, outlier_thresh, const_scale=const_scale,
-        skip_seq_scaling=skip_seq_scaling, seq_samp_type=seq_samp_type, engine=engine, **prep)))
+def _run_iters(run_pass, map_results, idx, params, max_scaling_iters, n_passes):
+    """run_rsqgl_iters (resquiggle.py:1492-1504) for the reads `idx`, round by round.  `run_pass(map_results,
+    params, first_pass, **kw)`: resquiggle_batch with the arguments that are fixed for the whole loop."""
+    res = dict(zip(idx, run_pass([map_results[i] for i in idx], params, True)))
     for i in idx:
         n_passes[i] += 1
     n_iters = 1
@@ -709,10 +703,8 @@ def _run_iters(map_results, idx, std_ref, params, outlier_thresh, const_scale, s
             break
         # the re-runs take the fitted scale values and the un-normalised signal; const_scale /
         # skip_seq_scaling are NOT forwarded (resquiggle.py:1499-1502)
-        sub = resquiggle_batch(
-            [map_results[i]._replace(scale_values=res[i].scale_values) for i in again], std_ref,
-            params, outlier_thresh, all_raw_signals=[map_results[i].raw_signal for i in again],
-            seq_samp_type=seq_samp_type, engine=engine, **prep)
+        sub = run_pass([map_results[i]._replace(scale_values=res[i].scale_values) for i in again], params, False,
+                    all_raw_signals=[map_results[i].raw_signal for i in again])
         for i, r in zip(again, sub):
             res[i] = r
             n_passes[i] += 1
@@ -765,27 +757,20 @@ def resquiggle_batch_iters(map_results, std_ref, rsqgl_params, save_params=None,
         rna = seq_samp_type is not None and seq_samp_type.name == RNA_SAMP_TYPE
         prep.update(reverse_raw=rna, stall_params=th.stallParams(**STALL_PARAMS)
                     if rna and COLLAPSE_RNA_STALLS else None)
-    if rng_order == 'read_major':
-        res = {}
-        for i in range(n):
-            res.update(_run_iters(map_results, [i], std_ref, rsqgl_params, outlier_thresh, const_scale,
-                                  skip_seq_scaling, seq_samp_type, max_scaling_iters, engine, n_passes, prep))
-            if isinstance(res[i], Exception) and save_params is not None:
-                res.update(_run_iters(map_results, [i], std_ref, save_params, outlier_thresh, const_scale,
-                                      skip_seq_scaling, seq_samp_type, max_scaling_iters, engine,
-                                      n_passes, prep))
-        out = [res[i] for i in range(n)]
-        return (out, n_passes) if return_passes else out
-    if rng_order != 'round_major':
+    if rng_order not in ('round_major', 'read_major'):
         raise ValueError("rng_order is 'round_major' or 'read_major'")
-    res = _run_iters(map_results, list(range(n)), std_ref, rsqgl_params, outlier_thresh,
-                     const_scale, skip_seq_scaling, seq_samp_type, max_scaling_iters, engine,
-                     n_passes, prep)
-    failed = [i for i in range(n) if isinstance(res[i], Exception)]
-    if failed and save_params is not None:
-        res.update(_run_iters(map_results, failed, std_ref, save_params, outlier_thresh,
-                              const_scale, skip_seq_scaling, seq_samp_type, max_scaling_iters,
-                              engine, n_passes, prep))
+
+    def run_pass(mrs, params, first_pass, **kw):
+        if first_pass:
+            kw.update(const_scale=const_scale, skip_seq_scaling=skip_seq_scaling)
+        return resquiggle_batch(mrs, std_ref, params, outlier_thresh, seq_samp_type=seq_samp_type,
+                                engine=engine, **prep, **kw)
+    res = {}
+    for group in ([[i] for i in range(n)] if rng_order == 'read_major' else [list(range(n))]):
+        res.update(_run_iters(run_pass, map_results, group, rsqgl_params, max_scaling_iters, n_passes))
+        failed = [i for i in group if isinstance(res[i], Exception)]
+        if failed and save_params is not None:
+            res.update(_run_iters(run_pass, map_results, failed, save_params, max_scaling_iters, n_passes))
     out = [res[i] for i in range(n)]
     return (out, n_passes) if return_passes else out
 

@@ -25,8 +25,7 @@ import numpy as np
 from . import _native
 from . import tombo_helper as th
 from ._default_parameters import (
-    MAX_RAW_CPTS, MIN_EVENT_TO_SEQ_RATIO, SIG_MATCH_THRESH, DNA_SAMP_TYPE,
-    MAX_POINTS_FOR_THEIL_SEN)
+    MAX_RAW_CPTS, MIN_EVENT_TO_SEQ_RATIO, DNA_SAMP_TYPE, MAX_POINTS_FOR_THEIL_SEN)
 
 __all__ = ['ReadBatch', 'BatchResults', 'StreamPipeline', 'ReadFeeder']
 
@@ -47,47 +46,15 @@ class ReadBatch(object):
     def from_lists(cls, raws, seqs, samp_inds=None, stalls=None, tag=None, pinned=False):
         """pack per-read arrays; with `pinned` the big arrays are built in page-locked memory
         (returned batch keeps the PinnedArray objects alive)"""
-        n = len(raws)
-        raw_off = np.zeros(n + 1, np.int64)
-        np.cumsum([len(r) for r in raws], out=raw_off[1:])
-        seq_off = np.zeros(n + 1, np.int64)
-        np.cumsum([len(s) for s in seqs], out=seq_off[1:])
-        dts = set(np.asarray(r).dtype for r in raws)
-        dt = next(iter(dts)) if len(dts) == 1 and next(iter(dts)) in _native.RAW_DTYPES \
-            else np.dtype(np.float64)
-        keep = []
-        if pinned:
-            pr = _native.PinnedArray(int(raw_off[-1]), dt)
-            ps = _native.PinnedArray(int(seq_off[-1]), np.uint8)
-            keep = [pr, ps]
-            raw, seq = pr.a, ps.a
-        else:
-            raw, seq = np.empty(int(raw_off[-1]), dt), np.empty(int(seq_off[-1]), np.uint8)
-        for i in range(n):
-            raw[raw_off[i]:raw_off[i + 1]] = raws[i]
-            seq[seq_off[i]:seq_off[i + 1]] = seqs[i]
+        raw, raw_off, seq, seq_off, keep = _native.pack_code_reads(raws, seqs, pinned=pinned)
         si = None
         if samp_inds is not None and any(s is not None for s in samp_inds):
-            # A read of more than 1000 bases (len(seq) - kmer_width + 1: the engine knows K, this
-            # function does not) needs its row.  Rows without one are poisoned with -1: the kernel
-            # rejects a negative index (TBA_INTERNAL for that read) instead of fitting a line
-            # through whatever the row held -- it cannot tell a missing subsample from a given one.
+            # (a read of more than 1000 bases -- len(seq) - kmer_width + 1: the engine knows K, this function
+            # does not -- needs its row)
             if pinned:
-                psi = _native.PinnedArray((n, 1000), np.int64)
-                keep.append(psi)
-                si = psi.a
-                si[:] = -1
-            else:
-                si = np.full((n, 1000), -1, np.int64)
-            for i, s in enumerate(samp_inds):
-                if s is not None:
-                    si[i] = s
-        st = sto = None
-        if stalls is not None and any(s is not None and len(s) for s in stalls):
-            sto = np.zeros(n + 1, np.int64)
-            np.cumsum([0 if s is None else len(s) for s in stalls], out=sto[1:])
-            st = np.array([[int(a), int(b)] for s in stalls if s is not None for a, b in s],
-                          dtype=np.int64).reshape(-1, 2)
+                keep.append(_native.PinnedArray((len(raws), MAX_POINTS_FOR_THEIL_SEN), np.int64))
+            si = _native.pack_samp_inds(samp_inds, out=keep[-1].a if pinned else None)
+        st, sto = _native.pack_stalls(stalls, or_none=True)
         b = cls(raw, raw_off, seq, seq_off, si, st, sto, tag)
         b._keep = keep
         return b
@@ -164,7 +131,7 @@ class StreamPipeline(object):
         self.opts = _native.make_opts(
             outlier_thresh=outlier_thresh, const_scale=const_scale,
             skip_seq_scaling=skip_seq_scaling,
-            sig_match_thresh=None if seq_samp_type is None else SIG_MATCH_THRESH[seq_samp_type.name],
+            seq_samp_type=seq_samp_type,
             max_raw_cpts=max_raw_cpts, min_event_to_seq_ratio=min_event_to_seq_ratio,
             skip_norm_out=not want_norm, reverse_raw=reverse_raw, stall_params=stall_params,
             subsample_seed=subsample_seed)
@@ -223,17 +190,16 @@ class StreamPipeline(object):
                 slot = next((s for s in self.slots if not s.eng.query()), None)
                 if slot is None:
                     time.sleep(0.0002)
-        if batch.samp_ind is None and self.subsample_seed is None and not self.opts.skip_seq_scaling and \
-                int(np.max(np.diff(batch.seq_off), initial=0)) - (slot.eng.kmer_width or 1) + 1 > MAX_POINTS_FOR_THEIL_SEN:
-            # (on the device this is the generic TBA_INTERNAL status of every long read; say it here)
-            raise ValueError('batch %r has reads longer than %d bases but no Theil-Sen subsamples: pass '
-                             'samp_inds, or subsample_seed to the pipeline' % (batch.tag, MAX_POINTS_FOR_THEIL_SEN))
-        if batch.samp_ind is not None and self.subsample_seed is None and not self.opts.skip_seq_scaling:
-            # per read, with the model's k-mer width: a read of more than 1000 bases whose row was
-            # left without a subsample (poisoned with -1 by from_lists / ReadFeeder.pack)
-            n_bases = np.diff(batch.seq_off) - (slot.eng.kmer_width or 1) + 1
-            si0 = np.asarray(batch.samp_ind).reshape(batch.n, -1)[:, 0]
-            if np.any((n_bases > MAX_POINTS_FOR_THEIL_SEN) & (si0 < 0)):
+        if self.subsample_seed is None and not self.opts.skip_seq_scaling:
+            # reads of more than 1000 bases (by the model's k-mer width) need a subsample row: on the device a
+            # missing one is the generic TBA_INTERNAL status of every such read; say it here
+            needs = np.diff(batch.seq_off) - (slot.eng.kmer_width or 1) + 1 > MAX_POINTS_FOR_THEIL_SEN
+            if batch.samp_ind is None and needs.any():
+                raise ValueError('batch %r has reads longer than %d bases but no Theil-Sen subsamples: pass '
+                                 'samp_inds, or subsample_seed to the pipeline' % (batch.tag, MAX_POINTS_FOR_THEIL_SEN))
+            # (a row left without a subsample is all -1: _native.pack_samp_inds)
+            if batch.samp_ind is not None and \
+                    (np.asarray(batch.samp_ind).reshape(batch.n, -1)[needs, 0] < 0).any():
                 raise ValueError('batch %r: no Theil-Sen subsample for a read longer than %d bases' %
                                  (batch.tag, MAX_POINTS_FOR_THEIL_SEN))
         done = self._finish(slot) if slot.pending is not None else None
@@ -343,16 +309,9 @@ class ReadFeeder(object):
             si = None
             if samp_inds is not None:
                 n = len(raws)
-                si = stage.get('si', n * MAX_POINTS_FOR_THEIL_SEN, np.int64).reshape(n, MAX_POINTS_FOR_THEIL_SEN)
-                for i, s in enumerate(samp_inds):
-                    if s is not None:
-                        si[i] = s
-                    else:
-                        # the staging buffer is reused: a row without a subsample must not keep an
-                        # earlier batch's indices (the kernel rejects -1, see ReadBatch.from_lists)
-                        si[i] = -1
-            st, sto = _native.pack_stalls(stalls) if stalls is not None and \
-                any(s is not None and len(s) for s in stalls) else (None, None)
+                si = _native.pack_samp_inds(samp_inds, out=stage.get(
+                    'si', n * MAX_POINTS_FOR_THEIL_SEN, np.int64).reshape(n, MAX_POINTS_FOR_THEIL_SEN))
+            st, sto = _native.pack_stalls(stalls, or_none=True)
         except BaseException:
             self._release_stage(k)  # (a failed pack must not leave the staging set busy for good)
             raise
