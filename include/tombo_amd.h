@@ -579,6 +579,63 @@ int tba_kmer_levels(tba_engine *e, const double *means, const uint8_t *codes,
 int tba_kde_eval(tba_engine *e, const double *levels, const int64_t *lv_off, int64_t n_seg,
     const double *x, int64_t n_x, double bandwidth, double *out_dens);
 
+/* ---- genome tracks (text_output browser_files, iter_cov_regs, get_largest_signal_differences) ---
+ * The pileup of per-base values over the reads of one (chromosome, strand):
+ * get_mean_slot_genome_centric (tombo_helper.py:1661-1676) and TomboReads._compute_coverage
+ * (:1394-1404).  The reference adds the reads to a float64 array one after the other, so a
+ * position's sum is the left-to-right sum of its values in read order; these entries keep that
+ * order (no floating-point atomics, one thread per position) and are bit-identical to it.
+ *
+ * tba_tracks_begin opens a track set over the window [win_start, win_end) of the chromosome:
+ * n_slots (1..3) float64 sum arrays at +0.0, one int64 coverage per slot and one int64 read
+ * coverage, all in device memory until the next tba_tracks_begin.  An engine holds one set.
+ * TBA_E_ARG: an empty window, one of 2^31 positions or more, n_slots outside [1, 3]. */
+#define TBA_TRK_TILE 256
+int tba_tracks_begin(tba_engine *e, int64_t win_start, int64_t win_end, int n_slots);
+/* Adds n_reads reads to the open set.  Read q lies at genomic [read_start[q], read_end[q]): that
+ * interval counts into the read coverage.  Its slot values, read-centric (5'->3' of the read),
+ * are slots[s][read_off[q] .. read_off[q + 1]) for every slot s with bit 1 + s of read_flags[q]
+ * set (a read without an Events table has none); bit 0: minus strand, value i lies at genomic
+ * read_start + len - 1 - i instead of read_start + i.  Positions outside the window are ignored.
+ * The window is cut into tiles of TBA_TRK_TILE positions, n_tiles = ceil(window / TBA_TRK_TILE);
+ * tile_reads[tile_read_off[t] .. tile_read_off[t + 1]) lists, in input order, the reads that
+ * overlap tile t (a listed read that does not overlap adds nothing; an overlapping read that is
+ * not listed is missed).  The values of a position are added in list order, continuing the sums
+ * of earlier calls: reads fed batch by batch in index order give the bits of one call.
+ * NaN and +-inf pass through ordinary IEEE addition.
+ * TBA_E_ARG: no open set, NULL pointers, offsets that do not start at 0 or decrease, n_tiles that
+ * is not the window's, a listed read outside [0, n_reads), end < start, a flag for a slot the
+ * set does not have. */
+int tba_tracks_add(tba_engine *e, int64_t n_reads, const int64_t *read_start, const int64_t *read_end,
+    const uint8_t *read_flags, const int64_t *read_off, const double *const *slots, int64_t n_tiles,
+    const int64_t *tile_read_off, const int32_t *tile_reads);
+/* The open set's results, each may be NULL: means_out[s * window + p] = sum / (double)coverage
+ * (NaN where nothing was added: 0 / 0), sums_out and slot_cov_out in the same layout,
+ * read_cov_out[window].  The set stays open: further reads may be added. */
+int tba_tracks_finish(tba_engine *e, double *means_out, double *sums_out, int64_t *slot_cov_out,
+    int64_t *read_cov_out);
+/* kernel time (hipEvents) of the open set's tba_tracks_add / tba_tracks_finish calls so far */
+int tba_tracks_kernel_ms(tba_engine *e, double *ms);
+/* Ordered compaction of n 64-bit values (flag, scan, scatter on the device; order kept).
+ * mode 0 (filter_cs_nans, _text_output_commands.py:230-233): values float64; out_pos / out_val =
+ *   the indices and values that are not NaN.
+ * mode 1 (iter_coverage_regions, tombo_helper.py:1430-1453): values int64; out_pos = 0, every i
+ *   with values[i] != values[i - 1], and n behind them (*out_count + 1 entries); out_val = the
+ *   value at each of those starts.
+ * out_pos holds n + 1 entries, out_val n; *out_count: the kept values. */
+int tba_tracks_compact(tba_engine *e, int mode, const void *values, int64_t n, int64_t *out_pos,
+    void *out_val, int64_t *out_count);
+/* out = np.nan_to_num(a - b): NaN -> 0, +-inf -> +-the largest double (get_signal_differences) */
+int tba_tracks_diff(tba_engine *e, const double *a, const double *b, int64_t n, double *out);
+/* The min(n_top, n) largest values of np.nan_to_num(np.abs(a - b)) and their positions
+ * (get_largest_signal_differences, tombo_helper.py:1714-1728), selected on the device: a radix
+ * select over the whole grid on the values' bit patterns, then compaction; only the selected
+ * pairs are copied back.  Output: first the values above the n_top-th largest in position
+ * order, then those that equal it.  Of equal values at the cut the HIGHEST positions are taken
+ * (the reference's unstable argsort leaves that choice open). */
+int tba_tracks_topn(tba_engine *e, const double *a, const double *b, int64_t n, int64_t n_top,
+    int64_t *out_pos, double *out_val, int64_t *out_count);
+
 /* The de novo statistic of every read of the finished resident batch, nothing uploaded: per-base
  * means (c_new_means over the final signal and boundaries, as tba_batch_base_stats) against the
  * batch's own expected levels, which are the canonical model's levels of the read sequence --

@@ -221,6 +221,66 @@ def _check_kde_eval_args(levels, lv_off, x, bandwidth):
     return np.ascontiguousarray(levels), off, np.ascontiguousarray(x)
 
 
+TRK_TILE = 256      # TBA_TRK_TILE of include/tombo_amd.h: positions per tile of the genome-track pileup
+TRK_MAX_SLOTS = 3
+# what tracks_finish gives back: means / sums / slot_cov float64 / int64 [n_slots, window], read_cov int64 [window]
+TrackSet = namedtuple('TrackSet', 'means sums slot_cov read_cov')
+
+
+def _check_tracks_begin_args(win_start, win_end, n_slots):
+    """the argument checks of Engine.tracks_begin (shared with the tests' stand-in engine)"""
+    if int(win_start) != win_start or int(win_end) != win_end or not 0 <= win_start < win_end:
+        raise ValueError('the window must be a non-empty integer interval at or above 0')
+    if win_end - win_start >= 2 ** 31:
+        raise ValueError('a window holds fewer than 2**31 positions')
+    if int(n_slots) != n_slots or not 1 <= n_slots <= TRK_MAX_SLOTS:
+        raise ValueError('n_slots must be an integer in [1, %d]' % TRK_MAX_SLOTS)
+
+
+def _check_tracks_add_args(window, n_slots, read_start, read_end, read_flags, read_off, slots, tile_read_off,
+                           tile_reads):
+    """the argument checks of Engine.tracks_add (shared with the tests' stand-in engine): dtypes are checked, not
+    converted -> contiguous (read_start, read_end, read_flags, read_off, slots, tile_read_off, tile_reads)"""
+    rs, re_, fl, tr = np.asarray(read_start), np.asarray(read_end), np.asarray(read_flags), np.asarray(tile_reads)
+    if rs.dtype != np.int64 or re_.dtype != np.int64 or fl.dtype != np.uint8 or tr.dtype != np.int32:
+        raise ValueError('read_start and read_end must be int64, read_flags uint8, tile_reads int32')
+    off, toff = _check_offsets(read_off, 'read_off'), _check_offsets(tile_read_off, 'tile_read_off')
+    n = off.shape[0] - 1
+    if not (rs.shape == re_.shape == fl.shape == (n,)) or tr.ndim != 1:
+        raise ValueError('per-read arrays and offsets disagree')
+    if n and ((re_ < rs).any() or (rs < 0).any()):
+        raise ValueError('a read ends before its start or starts below 0')
+    if n and (fl >> (1 + n_slots)).any():
+        raise ValueError('read_flags name a slot the track set does not have')
+    if toff.shape[0] - 1 != -(-window // TRK_TILE) or int(toff[-1]) != tr.shape[0]:
+        raise ValueError('tile_read_off must have one entry per tile of %d positions, plus one, and end at '
+                         'len(tile_reads)' % TRK_TILE)
+    if tr.shape[0] and (tr.min() < 0 or tr.max() >= n):
+        raise ValueError('tile_reads names a read outside the batch')
+    slots = [np.asarray(v) for v in slots]
+    if len(slots) != n_slots or any(v.dtype != np.float64 or v.shape != (int(off[-1]),) for v in slots):
+        raise ValueError('slots must be n_slots float64 arrays of read_off[-1] values')
+    return (np.ascontiguousarray(rs), np.ascontiguousarray(re_), np.ascontiguousarray(fl), off,
+            [np.ascontiguousarray(v) for v in slots], toff, np.ascontiguousarray(tr))
+
+
+def _check_track_pair(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    if a.dtype != np.float64 or b.dtype != np.float64 or a.ndim != 1 or a.shape != b.shape:
+        raise ValueError('a and b must be one-dimensional float64 arrays of one length')
+    return np.ascontiguousarray(a), np.ascontiguousarray(b)
+
+
+def _check_compact_args(values):
+    """-> (contiguous values, mode): float64 -> 0 (the NaN filter), int64 -> 1 (run-length form)"""
+    v = np.asarray(values)
+    if v.ndim != 1 or v.dtype not in (np.dtype(np.float64), np.dtype(np.int64)):
+        raise ValueError('values must be a one-dimensional float64 or int64 array')
+    if v.dtype == np.int64 and v.shape[0] == 0:
+        raise ValueError('the run-length form needs at least one value')
+    return np.ascontiguousarray(v), int(v.dtype == np.int64)
+
+
 # what one tba_site_fractions call gives back: the per-site arrays compacted per track at pos_off
 # (counts[t] records from pos_off[t]), per track the number of statistics, the statistics themselves
 SiteFractions = namedtuple('SiteFractions', 'pos_off frac poss cov valid damp counts n_stats per_read')
@@ -841,6 +901,76 @@ class Engine(object):
             self._h, _p(lv, f64), _p(off, i64), i64(off.shape[0] - 1), _p(x, f64), i64(x.shape[0]),
             f64(float(bandwidth)), _p(out, f64)), 'tba_kde_eval')
         return out
+
+    # ---- genome tracks (csrc/k_tracks.h) ----
+    def tracks_begin(self, win_start, win_end, n_slots):
+        """tba_tracks_begin: open a resident track set over [win_start, win_end) of one (chromosome, strand)"""
+        _check_tracks_begin_args(win_start, win_end, n_slots)
+        self._check(self._L.tba_tracks_begin(self._h, i64(int(win_start)), i64(int(win_end)), C.c_int(int(n_slots))),
+                    'tba_tracks_begin')
+        self._trk = (int(win_end) - int(win_start), int(n_slots))
+
+    def tracks_add(self, read_start, read_end, read_flags, read_off, slots, tile_read_off, tile_reads):
+        """tba_tracks_add: add reads to the open set.  read_flags: bit 0 minus strand, bit 1 + s the read has slot s;
+        slots: n_slots float64 arrays, read-centric, CSR by read_off; tile_reads / tile_read_off: per tile of
+        TRK_TILE positions the reads that overlap it, in input order"""
+        if getattr(self, '_trk', None) is None:
+            raise ValueError('no track set is open (tracks_begin)')
+        rs, re_, fl, off, sl, toff, tr = _check_tracks_add_args(
+            self._trk[0], self._trk[1], read_start, read_end, read_flags, read_off, slots, tile_read_off, tile_reads)
+        ptrs = (C.POINTER(f64) * TRK_MAX_SLOTS)(*[_p(v, f64) for v in sl])
+        self._check(self._L.tba_tracks_add(
+            self._h, i64(rs.shape[0]), _p(rs, i64), _p(re_, i64), _p(fl, C.c_uint8), _p(off, i64), ptrs,
+            i64(toff.shape[0] - 1), _p(toff, i64), _p(tr, i32)), 'tba_tracks_add')
+
+    def tracks_finish(self, want_sums=False):
+        """tba_tracks_finish -> TrackSet(means, sums or None, slot_cov, read_cov) of the open set"""
+        if getattr(self, '_trk', None) is None:
+            raise ValueError('no track set is open (tracks_begin)')
+        W, ns = self._trk
+        means, cov = np.empty((ns, W), dtype=np.float64), np.empty((ns, W), dtype=np.int64)
+        sums = np.empty((ns, W), dtype=np.float64) if want_sums else None
+        rcov = np.empty(W, dtype=np.int64)
+        self._check(self._L.tba_tracks_finish(self._h, _p(means, f64), _p(sums, f64), _p(cov, i64), _p(rcov, i64)),
+                    'tba_tracks_finish')
+        return TrackSet(means, sums, cov, rcov)
+
+    def tracks_kernel_ms(self):
+        ms = f64(0)
+        self._check(self._L.tba_tracks_kernel_ms(self._h, C.byref(ms)), 'tba_tracks_kernel_ms')
+        return ms.value
+
+    def tracks_compact(self, values):
+        """tba_tracks_compact.  float64 values -> (positions, values) that are not NaN (filter_cs_nans);
+        int64 values -> (run starts with len(values) behind them, run values) (iter_coverage_regions)"""
+        v, mode = _check_compact_args(values)
+        n = v.shape[0]
+        pos, val, cnt = np.empty(n + 1, dtype=np.int64), np.empty(n, dtype=v.dtype), i64(0)
+        self._check(self._L.tba_tracks_compact(self._h, C.c_int(mode), v.ctypes.data_as(C.c_void_p), i64(n),
+                                               _p(pos, i64), val.ctypes.data_as(C.c_void_p), C.byref(cnt)),
+                    'tba_tracks_compact')
+        return pos[:cnt.value + mode].copy(), val[:cnt.value].copy()
+
+    def tracks_diff(self, a, b):
+        """tba_tracks_diff: np.nan_to_num(a - b)"""
+        a, b = _check_track_pair(a, b)
+        out = np.empty(a.shape[0], dtype=np.float64)
+        self._check(self._L.tba_tracks_diff(self._h, _p(a, f64), _p(b, f64), i64(a.shape[0]), _p(out, f64)),
+                    'tba_tracks_diff')
+        return out
+
+    def tracks_topn(self, a, b, n_top):
+        """tba_tracks_topn: the min(n_top, len) largest np.nan_to_num(np.abs(a - b)) -> (values, positions), largest
+        first; equal values: the higher position first, at the cut as well as in the output"""
+        a, b = _check_track_pair(a, b)
+        if int(n_top) != n_top or n_top < 0:
+            raise ValueError('n_top must be a non-negative integer')
+        k = min(int(n_top), a.shape[0])
+        pos, val, cnt = np.empty(k, dtype=np.int64), np.empty(k, dtype=np.float64), i64(0)
+        self._check(self._L.tba_tracks_topn(self._h, _p(a, f64), _p(b, f64), i64(a.shape[0]), i64(k), _p(pos, i64),
+                                            _p(val, f64), C.byref(cnt)), 'tba_tracks_topn')
+        order = np.lexsort((pos[:cnt.value], val[:cnt.value]))[::-1]
+        return val[order], pos[order]
 
     def stats(self):
         a, c = f64(0), f64(0)

@@ -18,6 +18,7 @@
 #include "k_group.h"
 #include "k_site.h"
 #include "k_kde.h"
+#include "k_tracks.h"
 
 #include <algorithm>
 #include <array>
@@ -100,7 +101,8 @@ struct BatchSizes {
     X(d_res); X(d_segs32);            /* packed results of tba_batch_download_async */                                \
     X(d_skipq);                       /* window queues of k_skip_dp_wave */                                           \
     X(d_order); X(d_long);            /* read indices by decreasing length (k_dp_multi's grouping); the long reads (k_long.h) */ \
-    X(d_stall_csum); X(d_stall_bits); /* the stall detector's own scratch (it runs beside event detection) */
+    X(d_stall_csum); X(d_stall_bits); /* the stall detector's own scratch (it runs beside event detection) */ \
+    X(d_trk_sum); X(d_trk_cov); X(d_trk_rcov); /* the resident genome tracks (tba_tracks_begin .. tba_tracks_finish) */
 
 struct tba_engine {
     int device = 0;
@@ -111,7 +113,7 @@ struct tba_engine {
     // first consumer (k_remove_stalls; start discovery).  Both groups wait on memory most of their time
     // (SQ_WAIT_ANY 60-80 % of their wave cycles): together they fill what each leaves idle.
     hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_stalls = nullptr, ev_levels = nullptr, ev_st0 = nullptr, ev_st1 = nullptr, ev_skip0 = nullptr, ev_skip1 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_stalls = nullptr, ev_levels = nullptr, ev_st0 = nullptr, ev_st1 = nullptr, ev_skip0 = nullptr, ev_skip1 = nullptr, ev_trk0 = nullptr, ev_trk1 = nullptr;
     hipEvent_t ev[N_STAGE + 1] = {}; // ev[i], ev[i + 1]: around step i of the pipeline; ev[N_STEP]: its end, ev[SLOT_TOTAL]: its start
     float stage_ms[32] = {};
     bool have_model = false, have_batch = false, ran = false;
@@ -135,6 +137,10 @@ struct tba_engine {
     i64 small_batch = TBA_SMALL_BATCH, tb_wave_below = TBP_WAVE_BELOW;
     int last_c_ed_form = 0;       // tba_c_last_ed_form
     int raw_dtype = TBA_RAW_F64;
+    // the open genome-track set (k_tracks.h): window [trk_start, trk_start + trk_W), trk_slots sum arrays (0: none open)
+    i64 trk_start = 0, trk_W = 0;
+    int trk_slots = 0;
+    double trk_kernel_ms = 0;     // kernel time of the open set so far (tba_tracks_kernel_ms)
     PinBuf h_rs, h_dp;            // ReadState[n] / DevParams as uploaded (pinned)
 #define DEVBUF_MEMBER(name_) DevBuf name_
     TBA_ENGINE_DEVBUFS(DEVBUF_MEMBER)
@@ -182,7 +188,7 @@ extern "C" int tba_engine_create(int device, tba_engine **out)
     if (const char *v = getenv("TBA_TB_WAVE_BELOW")) e->tb_wave_below = std::max<i64>(atoll(v), 0);
     HIP_TRY(hipStreamCreate(&e->stream));
     if (device < TBA_MAX_DEVICES) g_live_engines[device]++;
-    for (hipEvent_t *x : {&e->ev_fork, &e->ev_stalls, &e->ev_levels, &e->ev_st0, &e->ev_st1, &e->ev_skip0, &e->ev_skip1}) HIP_TRY(hipEventCreate(x));
+    for (hipEvent_t *x : {&e->ev_fork, &e->ev_stalls, &e->ev_levels, &e->ev_st0, &e->ev_st1, &e->ev_skip0, &e->ev_skip1, &e->ev_trk0, &e->ev_trk1}) HIP_TRY(hipEventCreate(x));
     for (int i = 0; i <= N_STAGE; i++) HIP_TRY(hipEventCreate(&e->ev[i]));
     *out = e;
     return 0;
@@ -196,7 +202,7 @@ extern "C" void tba_engine_destroy(tba_engine *e)
     if (e->stream2) (void)hipStreamSynchronize(e->stream2);
     e->release_all();
     for (int i = 0; i <= N_STAGE; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
-    for (hipEvent_t x : {e->ev_fork, e->ev_stalls, e->ev_levels, e->ev_st0, e->ev_st1, e->ev_skip0, e->ev_skip1}) if (x) (void)hipEventDestroy(x);
+    for (hipEvent_t x : {e->ev_fork, e->ev_stalls, e->ev_levels, e->ev_st0, e->ev_st1, e->ev_skip0, e->ev_skip1, e->ev_trk0, e->ev_trk1}) if (x) (void)hipEventDestroy(x);
     if (e->stream2) (void)hipStreamDestroy(e->stream2);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     if (e->device < TBA_MAX_DEVICES) g_live_engines[e->device]--;
@@ -2130,6 +2136,195 @@ extern "C" int tba_kde_eval(tba_engine *e, const double *levels, const int64_t *
         n_seg, cov, has_nan, d_off, d_lv, d_x, n_x, bandwidth, d_dens);
     if (sc.sync(e->stream)) return sc.rc;
     return sc.get(out_dens, d_dens, n_seg * n_x);
+}
+
+// ---- genome tracks (k_tracks.h): pileup sums and coverages, compaction, difference, top N --------
+namespace {
+// kernel time of the launches between start() and stop(), added to the open set's total
+struct TrkTimer {
+    tba_engine *e;
+    explicit TrkTimer(tba_engine *e_) : e(e_) { (void)hipEventRecord(e->ev_trk0, e->stream); }
+    void stop(Scratch &sc)
+    {
+        float ms = 0;
+        if (sc.rc || hipEventRecord(e->ev_trk1, e->stream) != hipSuccess || hipEventSynchronize(e->ev_trk1) != hipSuccess) return;
+        if (hipEventElapsedTime(&ms, e->ev_trk0, e->ev_trk1) == hipSuccess) e->trk_kernel_ms += ms;
+    }
+};
+static unsigned trk_chunks(i64 n) { return (unsigned)((n + TRK_CHUNK - 1) / TRK_CHUNK); }
+
+// flag / scan / scatter of the n words x under `mode` (sel: the search state of the top-N modes); the kept
+// indices to d_pos (n + 1 words), the kept words of src to d_val (n words); d_total: how many were kept
+static void launch_compact(tba_engine *e, Scratch &sc, i64 n, int mode, const u64 *x, const TrkSel *sel, const u64 *src,
+                           i64 *d_pos, u64 *d_val, i64 *d_total)
+{
+    const unsigned nb = trk_chunks(n);
+    i64 *d_cnt = sc.out<i64>(nb);
+    if (sc.rc) return;
+    k_trk_count<<<nb, 256, 0, e->stream>>>(n, mode, x, sel, d_cnt);
+    k_trk_scan_blocks<<<1, 256, 0, e->stream>>>((i64)nb, d_cnt, d_total);
+    k_trk_scatter<<<nb, 256, 0, e->stream>>>(n, mode, x, sel, src, d_cnt, d_total, d_pos, d_val);
+}
+} // namespace
+
+extern "C" int tba_tracks_begin(tba_engine *e, int64_t win_start, int64_t win_end, int n_slots)
+{
+    if (!e || win_start < 0 || win_end <= win_start || win_end - win_start >= ((i64)1 << 31) ||
+        n_slots < 1 || n_slots > TRK_MAX_SLOTS)
+        return set_err(TBA_E_ARG, "bad arguments");
+    HIP_TRY(hipSetDevice(e->device));
+    const i64 W = win_end - win_start;
+    e->trk_slots = 0;
+    if (e->d_trk_sum.ensure((size_t)n_slots * W * 8) || e->d_trk_cov.ensure((size_t)n_slots * W * 8) ||
+        e->d_trk_rcov.ensure((size_t)W * 8))
+        return TBA_E_NOMEM;
+    // all bits zero: +0.0 sums, zero coverages
+    HIP_TRY(hipMemsetAsync(e->d_trk_sum.p, 0, (size_t)n_slots * W * 8, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_trk_cov.p, 0, (size_t)n_slots * W * 8, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_trk_rcov.p, 0, (size_t)W * 8, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->trk_start = win_start; e->trk_W = W; e->trk_slots = n_slots; e->trk_kernel_ms = 0;
+    return TBA_OK;
+}
+
+extern "C" int tba_tracks_add(tba_engine *e, int64_t n_reads, const int64_t *read_start, const int64_t *read_end,
+    const uint8_t *read_flags, const int64_t *read_off, const double *const *slots, int64_t n_tiles,
+    const int64_t *tile_read_off, const int32_t *tile_reads)
+{
+    if (!e || !e->trk_slots) return set_err(TBA_E_ARG, "no track set is open (tba_tracks_begin)");
+    const i64 W = e->trk_W;
+    const int ns = e->trk_slots;
+    if (n_reads < 0 || n_reads >= ((i64)1 << 31) || n_tiles != (W + TRK_TILE - 1) / TRK_TILE || !tile_read_off || !slots ||
+        (n_reads > 0 && (!read_start || !read_end || !read_flags || !read_off)))
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (const int rc = check_csr_off(tile_read_off, n_tiles)) return rc;
+    const i64 n_listed = tile_read_off[n_tiles];
+    if (n_listed > 0 && !tile_reads) return set_err(TBA_E_ARG, "bad arguments");
+    for (i64 i = 0; i < n_listed; i++)
+        if (tile_reads[i] < 0 || tile_reads[i] >= n_reads) return set_err(TBA_E_ARG, "tile list names a read outside the batch");
+    if (n_reads == 0 || n_listed == 0) return TBA_OK;
+    if (const int rc = check_csr_off(read_off, n_reads)) return rc;
+    const i64 total = read_off[n_reads];
+    for (i64 q = 0; q < n_reads; q++) {
+        if (read_end[q] < read_start[q] || read_start[q] < 0) return set_err(TBA_E_ARG, "read with end < start or start < 0");
+        if (read_flags[q] >> (1 + ns)) return set_err(TBA_E_ARG, "read flags name a slot the track set does not have");
+    }
+    for (int s = 0; s < ns; s++) if (total > 0 && !slots[s]) return set_err(TBA_E_ARG, "bad arguments");
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    TrkAdd a{};
+    a.win_start = e->trk_start; a.W = W;
+    a.read_start = sc.in(read_start, n_reads);
+    a.read_end = sc.in(read_end, n_reads);
+    a.read_off = sc.in(read_off, n_reads + 1);
+    a.read_flags = sc.in(read_flags, n_reads);
+    for (int s = 0; s < ns; s++) a.slot[s] = total > 0 ? sc.in(slots[s], total) : sc.out<double>(1);
+    a.tile_off = sc.in(tile_read_off, n_tiles + 1);
+    a.tile_reads = sc.in(tile_reads, n_listed);
+    a.sum = e->d_trk_sum.as<double>(); a.cov = e->d_trk_cov.as<i64>(); a.rcov = e->d_trk_rcov.as<i64>();
+    if (sc.rc) return sc.rc;
+    TrkTimer tm(e);
+    (ns == 1 ? k_trk_add<1> : ns == 2 ? k_trk_add<2> : k_trk_add<3>)<<<(unsigned)n_tiles, TRK_TILE, 0, e->stream>>>(a);
+    tm.stop(sc);
+    return sc.sync(e->stream);
+}
+
+extern "C" int tba_tracks_finish(tba_engine *e, double *means_out, double *sums_out, int64_t *slot_cov_out,
+    int64_t *read_cov_out)
+{
+    if (!e || !e->trk_slots) return set_err(TBA_E_ARG, "no track set is open (tba_tracks_begin)");
+    HIP_TRY(hipSetDevice(e->device));
+    const i64 W = e->trk_W, n = W * e->trk_slots;
+    Scratch sc;
+    if (means_out) {
+        double *d_mean = sc.out<double>(n);
+        if (sc.rc) return sc.rc;
+        TrkTimer tm(e);
+        k_trk_finish<<<grid_for(n), 256, 0, e->stream>>>(n, e->d_trk_sum.as<double>(), e->d_trk_cov.as<i64>(), d_mean);
+        tm.stop(sc);
+        if (sc.sync(e->stream) || sc.get(means_out, d_mean, n)) return sc.rc;
+    } else if (sc.sync(e->stream)) return sc.rc;
+    if (sums_out && sc.get(sums_out, e->d_trk_sum.as<double>(), n)) return sc.rc;
+    if (slot_cov_out && sc.get(slot_cov_out, e->d_trk_cov.as<i64>(), n)) return sc.rc;
+    if (read_cov_out && sc.get(read_cov_out, e->d_trk_rcov.as<i64>(), W)) return sc.rc;
+    return TBA_OK;
+}
+
+extern "C" int tba_tracks_kernel_ms(tba_engine *e, double *ms)
+{
+    if (!e || !ms) return set_err(TBA_E_ARG, "bad arguments");
+    *ms = e->trk_kernel_ms;
+    return TBA_OK;
+}
+
+extern "C" int tba_tracks_compact(tba_engine *e, int mode, const void *values, int64_t n, int64_t *out_pos,
+    void *out_val, int64_t *out_count)
+{
+    if (!e || (mode != TRK_KEEP_NOT_NAN && mode != TRK_KEEP_RUN_START) || n < 0 || n >= ((i64)1 << 31) || !out_count ||
+        (n > 0 && (!values || !out_pos || !out_val)))
+        return set_err(TBA_E_ARG, "bad arguments");
+    *out_count = 0;
+    if (n == 0) return TBA_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    const u64 *d_x = sc.in((const u64 *)values, n);
+    i64 *d_pos = sc.out<i64>(n + 1), *d_total = sc.out<i64>(1);
+    u64 *d_val = sc.out<u64>(n);
+    launch_compact(e, sc, n, mode, d_x, nullptr, d_x, d_pos, d_val, d_total);
+    if (sc.sync(e->stream) || sc.get(out_count, d_total, 1)) return sc.rc;
+    const i64 k = *out_count;
+    if (sc.get(out_pos, d_pos, k + (mode == TRK_KEEP_RUN_START))) return sc.rc;
+    return sc.get((u64 *)out_val, d_val, k);
+}
+
+extern "C" int tba_tracks_diff(tba_engine *e, const double *a, const double *b, int64_t n, double *out)
+{
+    if (!e || n < 0 || (n > 0 && (!a || !b || !out))) return set_err(TBA_E_ARG, "bad arguments");
+    if (n == 0) return TBA_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    const double *d_a = sc.in(a, n), *d_b = sc.in(b, n);
+    double *d_out = sc.out<double>(n);
+    if (sc.rc) return sc.rc;
+    k_trk_diff<false><<<grid_for(n), 256, 0, e->stream>>>(n, d_a, d_b, d_out, nullptr);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(out, d_out, n);
+}
+
+extern "C" int tba_tracks_topn(tba_engine *e, const double *a, const double *b, int64_t n, int64_t n_top,
+    int64_t *out_pos, double *out_val, int64_t *out_count)
+{
+    if (!e || n < 0 || n >= ((i64)1 << 31) || n_top < 0 || !out_count || (n > 0 && (!a || !b)) ||
+        (n > 0 && n_top > 0 && (!out_pos || !out_val)))
+        return set_err(TBA_E_ARG, "bad arguments");
+    const i64 N = std::min<i64>(n_top, n);
+    *out_count = 0;
+    if (N == 0) return TBA_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    const double *d_a = sc.in(a, n), *d_b = sc.in(b, n);
+    double *d_diff = sc.out<double>(n);
+    u64 *d_key = sc.out<u64>(n);
+    TrkSel hs{};
+    hs.remaining = N;
+    TrkSel *d_sel = sc.in(&hs, 1);
+    i64 *d_pos = sc.out<i64>(n + 1), *d_total = sc.out<i64>(2);
+    u64 *d_val = sc.out<u64>(n);
+    if (sc.rc) return sc.rc;
+    k_trk_diff<true><<<grid_for(n), 256, 0, e->stream>>>(n, d_a, d_b, d_diff, d_key);
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        k_trk_hist<<<grid_for(n), 256, 0, e->stream>>>(n, d_key, shift, d_sel);
+        k_trk_pick<<<1, 256, 0, e->stream>>>(shift, d_sel);
+    }
+    if (sc.sync(e->stream) || sc.get(&hs, d_sel, 1)) return sc.rc;
+    // what is above the N-th largest value, in position order, then the highest positions that equal it
+    launch_compact(e, sc, n, TRK_KEEP_ABOVE, d_key, d_sel, (const u64 *)d_diff, d_pos, d_val, d_total);
+    launch_compact(e, sc, n, TRK_KEEP_EQUAL, d_key, d_sel, (const u64 *)d_diff, d_pos + hs.n_above, d_val + hs.n_above,
+                   d_total + 1);
+    if (sc.sync(e->stream)) return sc.rc;
+    *out_count = N;
+    if (sc.get(out_pos, d_pos, N)) return sc.rc;
+    return sc.get((u64 *)out_val, d_val, N);
 }
 
 // testable slice of every read -> CSR offsets into a packed copy of (means, levels); one thread

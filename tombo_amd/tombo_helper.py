@@ -385,3 +385,313 @@ class regionData(object):
     def __init__(self, chrm, strand, start, end, reads, seq=None):
         self.chrm, self.strand, self.start, self.end = chrm, strand, int(start), int(end)
         self.reads, self.seq = reads, seq
+
+
+# ---- genome tracks: coverage, mean signal / SD / dwell per position, sample - control ---------
+# (text_output browser_files, iter_cov_regs, get_largest_signal_differences; the pileup kernels
+# are csrc/k_tracks.h).  A `reads_index` is the {(chrm, strand): [reads]} mapping `read_index`
+# returns; the reads are `resquiggledRead`s or any objects with `start`, `end`, `strand`, `means`.
+# Where the reference opens the FAST5 file of a read for an Events column, the column is taken
+# from memory: `norm_mean` defaults to `rd.means`, `norm_stdev` and `length` come from `slots`.
+TRACK_SLOTS = ('norm_mean', 'norm_stdev', 'length')
+
+
+def _tracks_engine(engine=None):
+    if engine is not None:
+        return engine
+    from . import resquiggle as rq
+    return rq.get_engine()
+
+
+def _cs_slots(slots, chrm_strand):
+    """reads_index-level `slots` ({(chrm, strand): per-list mapping}, or one mapping by read_id for all
+    reads) -> the mapping of one (chrm, strand)"""
+    if slots is None:
+        return None
+    if isinstance(slots, dict) and chrm_strand in slots:
+        return slots[chrm_strand]
+    return slots
+
+
+def _read_slot(rd, i, slot_name, slots):
+    """read-centric `slot_name` of read i of a list, or None (no Events table).  slots: a sequence by position in
+    the list, or a mapping by `read_id` or by position"""
+    if slots is None:
+        if slot_name != 'norm_mean':
+            raise ValueError('slot %s needs `slots`: only norm_mean is kept on the reads' % slot_name)
+        return getattr(rd, 'means', None)
+    if isinstance(slots, dict):
+        rid = getattr(rd, 'read_id', None)
+        return slots[rid] if rid is not None and rid in slots else slots.get(i)
+    return slots[i]
+
+
+def build_tile_lists(starts, ends, win_start, win_end, tile):
+    """Per tile of `tile` positions of the window [win_start, win_end) the reads [starts, ends) that overlap it, in
+    input order, in CSR form -> (tile_read_off int64[n_tiles + 1], tile_reads int32).  Vectorised: the (tile, read)
+    pairs read by read, then a stable sort by tile."""
+    starts, ends = np.asarray(starts, dtype=np.int64), np.asarray(ends, dtype=np.int64)
+    n_tiles = -(-(win_end - win_start) // tile)
+    lo, hi = np.clip(starts, win_start, win_end) - win_start, np.clip(ends, win_start, win_end) - win_start
+    t0 = lo // tile
+    cnt = np.where(hi > lo, (hi - 1) // tile - t0 + 1, 0)
+    first = np.cumsum(cnt) - cnt
+    total = int(cnt.sum())
+    reads = np.repeat(np.arange(starts.shape[0], dtype=np.int64), cnt)
+    tiles = np.repeat(t0 - first, cnt) + np.arange(total, dtype=np.int64)
+    order = np.argsort(tiles, kind='stable')
+    off = np.zeros(n_tiles + 1, dtype=np.int64)
+    np.cumsum(np.bincount(tiles, minlength=n_tiles), out=off[1:])
+    return off, reads[order].astype(np.int32)
+
+
+class GenomeTracks(object):
+    """Per (chromosome, strand) the per-position mean of up to three Events columns over all reads, the number of
+    reads behind each mean and the read coverage, computed on the device.
+
+        tracks = GenomeTracks(chrm_sizes, slots=('norm_mean', 'norm_stdev', 'length'))
+        tracks.add_reads(chrm, strand, reads, slots={'norm_stdev': [...], 'length': [...]})   # any number of times
+        res = tracks.finish()    # {(chrm, strand): TrackSet(means, sums, slot_cov, read_cov)}, arrays of chrm_sizes[chrm]
+
+    add_reads takes batches straight from `read_from_results`; per batch it gathers the reads' arrays (the only
+    per-read Python loop) and keeps them.  finish() feeds every (chromosome, strand) to the engine batch by batch,
+    in the order the batches came: the device sums stay resident between the batches, and the result has the bits
+    of the reference's loop over the reads in that order, however the reads were cut into batches.  A chromosome
+    longer than `max_window` is cut into windows on the host (a read that crosses a cut is given to both sides);
+    the result does not depend on where the cuts fall.
+    slots of add_reads: {slot_name: sequence by position in `reads`, or mapping by read_id / position}; norm_mean
+    defaults to `rd.means`.  A read whose column is None (no Events table) is left out of that column's sum and
+    coverage and stays in the read coverage.  All columns of a read have one length; `length` (uint32) is added as
+    float64, which is exact.  slots=() computes the read coverage alone."""
+
+    def __init__(self, chrm_sizes, slots=('norm_mean',), engine=None, max_window=1 << 26):
+        from ._native import TRK_TILE
+        slots = tuple(slots)
+        if len(slots) > 3 or any(s not in TRACK_SLOTS for s in slots) or len(set(slots)) != len(slots):
+            raise ValueError('slots: up to three different names out of %s' % (TRACK_SLOTS,))
+        if int(max_window) != max_window or max_window < 1:
+            raise ValueError('max_window must be a positive integer')
+        self.chrm_sizes, self.slots, self.engine, self.max_window = dict(chrm_sizes), slots, engine, int(max_window)
+        self.tile = TRK_TILE
+        self._batches = {}      # (chrm, strand) -> [(start, end, flags, off, [values per slot])]
+        self.timing = {'lists_s': 0.0, 'engine_s': 0.0, 'kernel_ms': 0.0}
+
+    def add_reads(self, chrm, strand, reads, slots=None):
+        if chrm not in self.chrm_sizes:
+            raise ValueError('chromosome %r is not in chrm_sizes' % (chrm,))
+        slots = slots or {}
+        n, ns = len(reads), len(self.slots)
+        start, end = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+        flags, lens = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int64)
+        cols = [[] for _ in range(ns)]
+        for i, rd in enumerate(reads):
+            start[i], end[i] = rd.start, rd.end
+            if rd.strand == '-':
+                flags[i] |= 1
+            vals = [_read_slot(rd, i, name, slots.get(name)) for name in self.slots]
+            have = [v for v in vals if v is not None]
+            if have:
+                lens[i] = len(have[0])
+                if any(len(v) != lens[i] for v in have):
+                    raise ValueError('read %d: its slots differ in length' % i)
+            for s, v in enumerate(vals):
+                if v is None:
+                    cols[s].append(None)
+                else:
+                    flags[i] |= 2 << s
+                    cols[s].append(np.asarray(v, dtype=np.float64))
+        if n and ((end < start).any() or (start < 0).any() or (end > self.chrm_sizes[chrm]).any() or
+                  (start + lens > self.chrm_sizes[chrm]).any()):
+            raise ValueError('a read lies outside [0, chrm_sizes[%r])' % (chrm,))
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        values = []
+        for s in range(ns):
+            v = np.zeros(int(off[-1]), dtype=np.float64)    # (a read without this slot keeps zeros nobody reads)
+            for i, c in enumerate(cols[s]):
+                if c is not None:
+                    v[off[i]:off[i + 1]] = c
+            values.append(v)
+        self._batches.setdefault((chrm, strand), []).append((start, end, flags, off, values))
+        return self
+
+    def _window(self, eng, batches, ws, we, want_sums):
+        import time
+        eng.tracks_begin(ws, we, max(len(self.slots), 1))
+        for start, end, flags, off, values in batches:
+            t0 = time.perf_counter()
+            reach = np.maximum(end, start + np.diff(off))
+            sel = np.flatnonzero((reach > ws) & (start < we))
+            if sel.shape[0] < start.shape[0]:       # the reads of this window only, repacked
+                ln = np.diff(off)[sel]
+                noff = np.zeros(sel.shape[0] + 1, dtype=np.int64)
+                np.cumsum(ln, out=noff[1:])
+                idx = np.repeat(off[sel] - noff[:-1], ln) + np.arange(int(noff[-1]), dtype=np.int64)
+                start, end, flags, off, values = start[sel], end[sel], flags[sel], noff, [v[idx] for v in values]
+                reach = reach[sel]
+            toff, treads = build_tile_lists(start, reach, ws, we, self.tile)
+            t1 = time.perf_counter()
+            eng.tracks_add(start, end, flags, off, values or [np.zeros(int(off[-1]))], toff, treads)
+            self.timing['lists_s'] += t1 - t0
+            self.timing['engine_s'] += time.perf_counter() - t1
+        t1 = time.perf_counter()
+        res = eng.tracks_finish(want_sums=want_sums)
+        self.timing['engine_s'] += time.perf_counter() - t1
+        if hasattr(eng, 'tracks_kernel_ms'):
+            self.timing['kernel_ms'] += eng.tracks_kernel_ms()
+        return res
+
+    def finish(self, want_sums=False):
+        """-> {(chrm, strand): TrackSet}: means / sums (None unless want_sums) / slot_cov [len(slots), chrm size],
+        read_cov [chrm size]"""
+        from ._native import TrackSet
+        eng, out, ns = _tracks_engine(self.engine), {}, len(self.slots)
+        for (chrm, strand), batches in self._batches.items():
+            size = int(self.chrm_sizes[chrm])
+            parts = [self._window(eng, batches, ws, min(ws + self.max_window, size), want_sums)
+                     for ws in range(0, size, self.max_window)]
+            if not parts:
+                z = np.zeros((ns, 0))
+                parts = [TrackSet(z, z if want_sums else None, z.astype(np.int64), np.zeros(0, dtype=np.int64))]
+            cat = (lambda xs: xs[0] if len(xs) == 1 else np.concatenate(xs, axis=-1))
+            out[(chrm, strand)] = TrackSet(
+                cat([p.means for p in parts])[:ns], cat([p.sums for p in parts])[:ns] if want_sums else None,
+                cat([p.slot_cov for p in parts])[:ns], cat([p.read_cov for p in parts]))
+        return out
+
+
+def _iter_index(reads_index):
+    return reads_index.items() if hasattr(reads_index, 'items') else iter(reads_index)
+
+
+def get_chrm_sizes(reads_index, ctrl_reads_index=None):
+    """{chrm: the largest read end over both strands (and both indices)} (tombo_helper.py:396-421)"""
+    sizes = {}
+    for index in (reads_index, ctrl_reads_index):
+        if index is None:
+            continue
+        for (chrm, _), cs_reads in _iter_index(index):
+            if len(cs_reads):
+                sizes[chrm] = max(sizes.get(chrm, 0), max(rd.end for rd in cs_reads))
+    return sizes
+
+
+def compute_coverage(reads_index, engine=None, max_window=1 << 26):
+    """{(chrm, strand): int64 read coverage up to the largest read end of that strand}
+    (TomboReads._compute_coverage, tombo_helper.py:1394-1404): every read counts over [start, end), with or
+    without an Events table."""
+    ends = dict((cs, max(rd.end for rd in rds)) for cs, rds in _iter_index(reads_index) if len(rds))
+    tracks = GenomeTracks(get_chrm_sizes(reads_index), slots=(), engine=engine, max_window=max_window)
+    for (chrm, strand), cs_reads in _iter_index(reads_index):
+        if len(cs_reads):
+            tracks.add_reads(chrm, strand, cs_reads)
+    res = tracks.finish()
+    return dict((cs, res[cs].read_cov[:ends[cs]].copy()) for cs in ends)
+
+
+def _add_coverages(cov, ctrl_cov):
+    """TomboReads._add_coverages (tombo_helper.py:1406-1428): per (chrm, strand) OF THE CONTROL the longer array
+    plus the shorter one; what only the sample covers is left out, as in the reference"""
+    merged = {}
+    for cs, c in ctrl_cov.items():
+        if cs in cov:
+            a, b = (cov[cs], c) if cov[cs].shape[0] > c.shape[0] else (c, cov[cs])
+            m = a.copy()
+            m[:b.shape[0]] += b
+        else:
+            m = c.copy()
+        merged[cs] = m
+    return merged
+
+
+def iter_coverage_regions(reads_index, ctrl_reads_index=None, engine=None):
+    """Yields (chrm, strand, cs_cov, cs_cov_starts): the read coverage in run-length form
+    (TomboReads.iter_coverage_regions, tombo_helper.py:1430-1453): cs_cov_starts holds 0, every position where
+    the coverage changes and the length; cs_cov the coverage of each run.  With a control index the coverages are
+    added, over the (chrm, strand) of the control only (the reference's behaviour)."""
+    eng = _tracks_engine(engine)
+    cov = compute_coverage(reads_index, engine=eng)
+    if ctrl_reads_index is not None:
+        cov = _add_coverages(cov, compute_coverage(ctrl_reads_index, engine=eng))
+    for (chrm, strand), cs_cov in cov.items():
+        starts, vals = eng.tracks_compact(cs_cov)
+        yield chrm, strand, vals, starts
+
+
+def iter_cov_regs(reads_index, cov_thresh, region_size=None, ctrl_reads_index=None, engine=None):
+    """Regions with coverage >= cov_thresh (TomboReads.iter_cov_regs, tombo_helper.py:1457-1485): without
+    region_size (chrm, strand, start, end), with it (chrm, strand, start) for starts on multiples of region_size.
+    Two habits of the reference are kept:
+      * the threshold crossings are paired (1st, 2nd), (2nd, 3rd), ...: the stretch BETWEEN two qualifying runs is
+        yielded too, like the runs themselves;
+      * with region_size a start is skipped only when it equals the one yielded just before it."""
+    for chrm, strand, cov, starts in iter_coverage_regions(reads_index, ctrl_reads_index, engine=engine):
+        curr_reg_start = -1
+        valid_cov = np.flatnonzero(np.diff(np.concatenate([[False], cov >= cov_thresh, [False]])))
+        for i, j in zip(valid_cov[:-1], valid_cov[1:]):
+            cov_start, cov_end = starts[i], starts[j]
+            if region_size is None:
+                yield chrm, strand, cov_start, cov_end
+                continue
+            first = int(region_size * np.floor(cov_start / float(region_size)))
+            last = int(region_size * np.ceil(cov_end / float(region_size)))
+            for reg_start in range(first, last, region_size):
+                if reg_start != curr_reg_start:
+                    yield chrm, strand, reg_start
+                    curr_reg_start = reg_start
+
+
+def get_mean_slot_genome_centric(cs_reads, chrm_len, slot_name, slots=None, engine=None, max_window=1 << 26):
+    """float64[chrm_len]: the mean of `slot_name` over the reads of one (chrm, strand) at every position, NaN where
+    no read has a value (tombo_helper.py:1661-1676; bit-identical, the reads are added in list order).  slots: the
+    column per read, a sequence by position in cs_reads or a mapping by read_id / position (norm_mean: defaults to
+    rd.means); None for a read without an Events table."""
+    tracks = GenomeTracks({'': chrm_len}, slots=(slot_name,), engine=engine, max_window=max_window)
+    tracks.add_reads('', '+', cs_reads, {slot_name: slots})   # (each read's own strand decides the flip)
+    return tracks.finish()[('', '+')].means[0]
+
+
+def iter_mean_slot_values(reads_index, chrm_sizes, slot_name, ctrl_reads_index=None, slots=None, ctrl_slots=None,
+                          engine=None):
+    """Yields (chrm, strand, cs_mean_values, ctrl_cs_mean_values) over the sorted chromosomes and '+', '-'
+    (tombo_helper.py:1678-1712); without a control the fourth value is None, with one a side without reads on that
+    (chrm, strand) is None.  slots / ctrl_slots: {(chrm, strand): per-list column mapping}, or one mapping by
+    read_id."""
+    for chrm, strand in [(c, s) for c in sorted(chrm_sizes) for s in ('+', '-')]:
+        cs, vals = (chrm, strand), []
+        for index, sl in ((reads_index, slots), (ctrl_reads_index, ctrl_slots)):
+            vals.append(None if index is None or cs not in index else get_mean_slot_genome_centric(
+                index[cs], chrm_sizes[chrm], slot_name, _cs_slots(sl, cs), engine=engine))
+        if ctrl_reads_index is None:
+            if vals[0] is not None:
+                yield chrm, strand, vals[0], None
+        elif vals[0] is not None or vals[1] is not None:
+            yield chrm, strand, vals[0], vals[1]
+
+
+def get_signal_differences(reads_index, ctrl_reads_index, engine=None):
+    """{(chrm, strand): nan_to_num(sample mean - control mean)} where both have reads (tombo_helper.py:1730-1742)"""
+    eng = _tracks_engine(engine)
+    chrm_sizes = get_chrm_sizes(reads_index, ctrl_reads_index)
+    return dict(((chrm, strand), eng.tracks_diff(a, b))
+                for chrm, strand, a, b in iter_mean_slot_values(reads_index, chrm_sizes, 'norm_mean',
+                                                                ctrl_reads_index, engine=eng)
+                if a is not None and b is not None)
+
+
+def get_largest_signal_differences(reads_index, ctrl_reads_index, num_regions, num_bases, engine=None):
+    """The num_regions positions with the largest |sample mean - control mean| as (difference,
+    max(pos - int(num_bases / 2), 0), chrm, strand), largest first (tombo_helper.py:1714-1728).  The candidates of a
+    (chrm, strand) are selected on the device; the difference track is not copied back.
+    Ties: the reference takes its candidates from an unstable argsort, so which of several EQUAL differences at the
+    cut it keeps is not defined; here the higher position is taken first."""
+    eng = _tracks_engine(engine)
+    chrm_sizes = get_chrm_sizes(reads_index, ctrl_reads_index)
+    found = []
+    for chrm, strand, a, b in iter_mean_slot_values(reads_index, chrm_sizes, 'norm_mean', ctrl_reads_index,
+                                                    engine=eng):
+        if a is None or b is None:
+            continue
+        vals, poss = eng.tracks_topn(a, b, num_regions)
+        found.extend((v, max(int(p) - int(num_bases / 2.0), 0), chrm, strand) for v, p in zip(vals, poss))
+    return sorted(found, reverse=True)[:num_regions]
