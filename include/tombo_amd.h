@@ -636,6 +636,30 @@ int tba_tracks_diff(tba_engine *e, const double *a, const double *b, int64_t n, 
 int tba_tracks_topn(tba_engine *e, const double *a, const double *b, int64_t n, int64_t n_top,
     int64_t *out_pos, double *out_val, int64_t *out_count);
 
+/* ---- estimate_kmer_model / estimate_motif_alt_model (csrc/k_kmer_est.h) ----
+ * get_region_kmer_levels (tombo_stats.py:1242-1359) for a batch of regions, the arithmetic only:
+ * the host has done the region sequences, the coverage intervals, the motif search and the keys.
+ *   reads      read_start, read_minus (1: minus strand, its levels are reversed to genome order),
+ *              means CSR by read_off[n_reads + 1]; a read is uploaded once per call
+ *   regions    reg_reads CSR by reg_read_off[n_regions + 1]: indices of the region's reads in the
+ *              region's read order (the order the levels of a position are taken in)
+ *   positions  pos_reg / pos_g [n_pos]: region and genomic position of every wanted position
+ *   entries    ent_pos / ent_key [n_ent]: a position index and a key in [0, n_keys), n_keys <= 2^24
+ * Per position the levels of the region's reads that cover it, NaN levels included, give the pair
+ * (np.median, np.std), or with est_mean the pair of c_mean_std (left-to-right sums).  The entries
+ * are then stably partitioned by key: out_counts[n_keys], out_off[n_keys + 1], and out_levels /
+ * out_sds [n_ent] hold per key its entries' pairs in entry order.  No floating-point atomics:
+ * the same call gives the same bits. */
+int tba_region_key_levels(tba_engine *e, int est_mean, int64_t n_reads, const int64_t *read_start,
+    const uint8_t *read_minus, const int64_t *read_off, const double *means, int64_t n_regions,
+    const int64_t *reg_read_off, const int64_t *reg_reads, int64_t n_pos, const int64_t *pos_reg,
+    const int64_t *pos_g, int64_t n_ent, const int64_t *ent_pos, const int64_t *ent_key, int64_t n_keys,
+    int64_t *out_counts, int64_t *out_off, double *out_levels, double *out_sds);
+/* np.median of every segment of values (CSR by off[n_seg + 1]): the mean of the two middle values
+ * for an even count, NaN for an empty segment or one that holds a NaN.  values is not modified. */
+int tba_segment_medians(tba_engine *e, const double *values, const int64_t *off, int64_t n_seg,
+    double *out_medians);
+
 /* The de novo statistic of every read of the finished resident batch, nothing uploaded: per-base
  * means (c_new_means over the final signal and boundaries, as tba_batch_base_stats) against the
  * batch's own expected levels, which are the canonical model's levels of the read sequence --

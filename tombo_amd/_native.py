@@ -221,6 +221,50 @@ def _check_kde_eval_args(levels, lv_off, x, bandwidth):
     return np.ascontiguousarray(levels), off, np.ascontiguousarray(x)
 
 
+KEST_MAX_KEYS = 1 << 24    # the key limit of tba_region_key_levels
+
+
+def _check_region_key_levels_args(read_start, read_minus, read_off, means, reg_read_off, reg_reads, pos_reg, pos_g,
+                                  ent_pos, ent_key, n_keys):
+    """the argument checks of Engine.region_key_levels (shared with the tests' stand-in engine): dtypes are checked,
+    not converted; every index is checked against the array it points into -> the contiguous arrays, in order"""
+    rs, rm, m = np.asarray(read_start), np.asarray(read_minus), np.asarray(means)
+    rr, pr, pg, ep, ek = (np.asarray(v) for v in (reg_reads, pos_reg, pos_g, ent_pos, ent_key))
+    if rs.dtype != np.int64 or rm.dtype != np.uint8 or m.dtype != np.float64:
+        raise ValueError('read_start must be int64, read_minus uint8, means float64')
+    if any(v.dtype != np.int64 or v.ndim != 1 for v in (rr, pr, pg, ep, ek)):
+        raise ValueError('reg_reads, pos_reg, pos_g, ent_pos and ent_key must be one-dimensional int64 arrays')
+    off, roff = _check_offsets(read_off, 'read_off'), _check_offsets(reg_read_off, 'reg_read_off')
+    n_reads, n_regions = off.shape[0] - 1, roff.shape[0] - 1
+    if rs.shape != (n_reads,) or rm.shape != (n_reads,) or m.shape != (int(off[-1]),):
+        raise ValueError('per-read arrays, levels and offsets disagree')
+    if n_reads >= 2 ** 31 or ep.shape[0] >= 2 ** 31:
+        raise ValueError('a call holds fewer than 2**31 reads and entries')
+    if rr.shape[0] != int(roff[-1]) or (rr.shape[0] and (rr.min() < 0 or rr.max() >= n_reads)):
+        raise ValueError('reg_reads must hold reg_read_off[-1] indices of reads of the batch')
+    if pr.shape != pg.shape or (pr.shape[0] and (pr.min() < 0 or pr.max() >= n_regions)):
+        raise ValueError('pos_reg and pos_g must have one entry per position, pos_reg naming a region of the batch')
+    if int(n_keys) != n_keys or not 1 <= n_keys <= KEST_MAX_KEYS:
+        raise ValueError('n_keys must be an integer in [1, %d]' % KEST_MAX_KEYS)
+    if ep.shape != ek.shape or (ep.shape[0] and (ep.min() < 0 or ep.max() >= pr.shape[0] or ek.min() < 0 or
+                                                 ek.max() >= n_keys)):
+        raise ValueError('ent_pos and ent_key must have one entry per entry, naming a position and a key of the batch')
+    return tuple(np.ascontiguousarray(v) for v in (rs, rm, off, m, roff, rr, pr, pg, ep, ek))
+
+
+def _check_segment_medians_args(values, off):
+    """the argument checks of Engine.segment_medians -> contiguous (values, off)"""
+    values = np.asarray(values)
+    if values.dtype != np.float64 or values.ndim != 1:
+        raise ValueError('values must be a one-dimensional float64 array')
+    off = _check_offsets(off, 'off')
+    if values.shape[0] != int(off[-1]):
+        raise ValueError('values and offsets disagree')
+    if off.shape[0] > 1 and np.diff(off).max() >= 2 ** 31:
+        raise ValueError('a segment holds fewer than 2**31 values')
+    return np.ascontiguousarray(values), off
+
+
 TRK_TILE = 256      # TBA_TRK_TILE of include/tombo_amd.h: positions per tile of the genome-track pileup
 TRK_MAX_SLOTS = 3
 # what tracks_finish gives back: means / sums / slot_cov float64 / int64 [n_slots, window], read_cov int64 [window]
@@ -900,6 +944,35 @@ class Engine(object):
         self._check(self._L.tba_kde_eval(
             self._h, _p(lv, f64), _p(off, i64), i64(off.shape[0] - 1), _p(x, f64), i64(x.shape[0]),
             f64(float(bandwidth)), _p(out, f64)), 'tba_kde_eval')
+        return out
+
+    # ---- k-mer model estimation (csrc/k_kmer_est.h) ----
+    def region_key_levels(self, est_mean, read_start, read_minus, read_off, means, reg_read_off, reg_reads, pos_reg,
+                          pos_g, ent_pos, ent_key, n_keys):
+        """tba_region_key_levels: get_region_kmer_levels for a batch of regions.  Reads (start, minus-strand flag,
+        levels CSR by read_off) are given once; region r uses the reads reg_reads[reg_read_off[r]:reg_read_off[r + 1]]
+        in that order; position p is (pos_reg[p], pos_g[p]); entry i files the pair of position ent_pos[i] under key
+        ent_key[i].  -> (counts int64[n_keys], off int64[n_keys + 1], levels, sds float64[n_ent]): per key the
+        (np.median, np.std) pairs -- est_mean: the c_mean_std pairs -- of its entries, in entry order"""
+        rs, rm, off, m, roff, rr, pr, pg, ep, ek = _check_region_key_levels_args(
+            read_start, read_minus, read_off, means, reg_read_off, reg_reads, pos_reg, pos_g, ent_pos, ent_key, n_keys)
+        n_keys, n_ent = int(n_keys), ep.shape[0]
+        counts, koff = np.empty(n_keys, dtype=np.int64), np.empty(n_keys + 1, dtype=np.int64)
+        levels, sds = np.empty(n_ent, dtype=np.float64), np.empty(n_ent, dtype=np.float64)
+        self._check(self._L.tba_region_key_levels(
+            self._h, C.c_int(1 if est_mean else 0), i64(rs.shape[0]), _p(rs, i64), _p(rm, C.c_uint8), _p(off, i64),
+            _p(m, f64), i64(roff.shape[0] - 1), _p(roff, i64), _p(rr, i64), i64(pr.shape[0]), _p(pr, i64), _p(pg, i64),
+            i64(n_ent), _p(ep, i64), _p(ek, i64), i64(n_keys), _p(counts, i64), _p(koff, i64), _p(levels, f64),
+            _p(sds, f64)), 'tba_region_key_levels')
+        return counts, koff, levels, sds
+
+    def segment_medians(self, values, off):
+        """tba_segment_medians: np.median of every segment of `values` (CSR by off) -> float64[n_seg]; NaN for an
+        empty segment or one that holds a NaN.  `values` is not modified"""
+        v, off = _check_segment_medians_args(values, off)
+        out = np.empty(off.shape[0] - 1, dtype=np.float64)
+        self._check(self._L.tba_segment_medians(self._h, _p(v, f64), _p(off, i64), i64(off.shape[0] - 1), _p(out, f64)),
+                    'tba_segment_medians')
         return out
 
     # ---- genome tracks (csrc/k_tracks.h) ----

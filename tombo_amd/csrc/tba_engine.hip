@@ -19,6 +19,7 @@
 #include "k_site.h"
 #include "k_kde.h"
 #include "k_tracks.h"
+#include "k_kmer_est.h"
 
 #include <algorithm>
 #include <array>
@@ -2106,6 +2107,24 @@ extern "C" int tba_kmer_levels(tba_engine *e, const double *means, const uint8_t
     return sc.get(out_levels, d_lv, n_lv);
 }
 
+namespace {
+// the segments of d_lv (n_seg, CSR by d_off) with more than one level and no NaN sorted ascending in place (shared by
+// tba_kde_eval, tba_region_key_levels and tba_segment_medians) -> has_nan per segment; *cov_out: the sizes
+static i32 *sort_segments(tba_engine *e, Scratch &sc, i64 n_seg, const i64 *d_off, double *d_lv, i32 **cov_out = nullptr)
+{
+    i32 *cov = sc.out<i32>(n_seg), *has_nan = sc.out<i32>(n_seg);
+    if (cov_out) *cov_out = cov;
+    i64 *lists = sc.out<i64>(3 * n_seg);
+    u32 *cls = sc.out<u32>(3);
+    if (sc.rc || sc.hip(hipMemsetAsync(cls, 0, 3 * sizeof(u32), e->stream), "hipMemsetAsync")) return nullptr;
+    k_kde_classify<<<grid_for(64 * n_seg), 256, 0, e->stream>>>(n_seg, d_off, d_lv, cov, has_nan, lists, cls);
+    k_grp_sort_wave<<<1024, 256, 0, e->stream>>>(lists, cls, cov, d_off, d_lv);
+    k_grp_sort_wg<<<1024, 256, 0, e->stream>>>(lists + n_seg, cls + 1, cov, d_off, d_lv, 0);
+    k_grp_sort_wg<<<256, 256, 0, e->stream>>>(lists + 2 * n_seg, cls + 2, cov, d_off, d_lv, 1);
+    return has_nan;
+}
+} // namespace
+
 extern "C" int tba_kde_eval(tba_engine *e, const double *levels, const int64_t *lv_off, int64_t n_seg,
     const double *x, int64_t n_x, double bandwidth, double *out_dens)
 {
@@ -2123,15 +2142,10 @@ extern "C" int tba_kde_eval(tba_engine *e, const double *levels, const int64_t *
     double *d_lv = n_lv > 0 ? sc.in(levels, n_lv) : sc.out<double>(1);
     const i64 *d_off = sc.in(lv_off, n_seg + 1);
     const double *d_x = sc.in(x, n_x);
-    i32 *cov = sc.out<i32>(n_seg), *has_nan = sc.out<i32>(n_seg);
-    i64 *lists = sc.out<i64>(3 * n_seg);
-    u32 *cls = sc.out<u32>(3);
     double *d_dens = sc.out<double>(n_seg * n_x);
-    if (sc.rc || sc.hip(hipMemsetAsync(cls, 0, 3 * sizeof(u32), e->stream), "hipMemsetAsync")) return sc.rc;
-    k_kde_classify<<<grid_for(64 * n_seg), 256, 0, e->stream>>>(n_seg, d_off, d_lv, cov, has_nan, lists, cls);
-    k_grp_sort_wave<<<1024, 256, 0, e->stream>>>(lists, cls, cov, d_off, d_lv);
-    k_grp_sort_wg<<<1024, 256, 0, e->stream>>>(lists + n_seg, cls + 1, cov, d_off, d_lv, 0);
-    k_grp_sort_wg<<<256, 256, 0, e->stream>>>(lists + 2 * n_seg, cls + 2, cov, d_off, d_lv, 1);
+    i32 *cov = nullptr;
+    const i32 *has_nan = sort_segments(e, sc, n_seg, d_off, d_lv, &cov);
+    if (sc.rc) return sc.rc;
     k_kde_eval<<<dim3((unsigned)std::min<i64>(n_seg, 65535), (unsigned)((n_x + 255) / 256)), 256, 0, e->stream>>>(
         n_seg, cov, has_nan, d_off, d_lv, d_x, n_x, bandwidth, d_dens);
     if (sc.sync(e->stream)) return sc.rc;
@@ -2325,6 +2339,110 @@ extern "C" int tba_tracks_topn(tba_engine *e, const double *a, const double *b, 
     *out_count = N;
     if (sc.get(out_pos, d_pos, N)) return sc.rc;
     return sc.get((u64 *)out_val, d_val, N);
+}
+
+// ---- estimate_kmer_model / estimate_motif_alt_model (k_kmer_est.h) ------------------------------
+extern "C" int tba_region_key_levels(tba_engine *e, int est_mean, int64_t n_reads, const int64_t *read_start,
+    const uint8_t *read_minus, const int64_t *read_off, const double *means, int64_t n_regions,
+    const int64_t *reg_read_off, const int64_t *reg_reads, int64_t n_pos, const int64_t *pos_reg,
+    const int64_t *pos_g, int64_t n_ent, const int64_t *ent_pos, const int64_t *ent_key, int64_t n_keys,
+    int64_t *out_counts, int64_t *out_off, double *out_levels, double *out_sds)
+{
+    if (!e || n_reads < 0 || n_reads >= ((i64)1 << 31) || n_regions < 0 || n_pos < 0 || n_ent < 0 ||
+        n_ent >= ((i64)1 << 31) || n_keys < 1 || n_keys > ((i64)1 << 24) || !read_off || !reg_read_off ||
+        !out_counts || !out_off || (n_reads > 0 && (!read_start || !read_minus)) ||
+        (n_pos > 0 && (!pos_reg || !pos_g)) || (n_ent > 0 && (!ent_pos || !ent_key || !out_levels || !out_sds)))
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (const int rc = check_csr_off(read_off, n_reads)) return rc;
+    if (const int rc = check_csr_off(reg_read_off, n_regions)) return rc;
+    const i64 total = n_reads > 0 ? read_off[n_reads] : 0, n_rr = n_regions > 0 ? reg_read_off[n_regions] : 0;
+    if ((total > 0 && !means) || (n_rr > 0 && !reg_reads)) return set_err(TBA_E_ARG, "bad arguments");
+    for (i64 q = 0; q < n_rr; q++)
+        if (reg_reads[q] < 0 || reg_reads[q] >= n_reads) return set_err(TBA_E_ARG, "a region names a read outside the batch");
+    for (i64 p = 0; p < n_pos; p++)
+        if (pos_reg[p] < 0 || pos_reg[p] >= n_regions) return set_err(TBA_E_ARG, "a position names a region outside the batch");
+    for (i64 i = 0; i < n_ent; i++)
+        if (ent_pos[i] < 0 || ent_pos[i] >= n_pos || ent_key[i] < 0 || ent_key[i] >= n_keys)
+            return set_err(TBA_E_ARG, "an entry names a position or a key outside the batch");
+    if (n_ent == 0) {
+        for (i64 q = 0; q < n_keys; q++) out_counts[q] = 0;
+        for (i64 q = 0; q <= n_keys; q++) out_off[q] = 0;
+        return TBA_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    KestArgs a{};
+    a.n_pos = n_pos;
+    a.pos_reg = sc.in(pos_reg, n_pos);
+    a.pos_g = sc.in(pos_g, n_pos);
+    a.reg_read_off = sc.in(reg_read_off, n_regions + 1);
+    a.reg_reads = n_rr > 0 ? sc.in(reg_reads, n_rr) : sc.out<i64>(1);
+    a.read_start = n_reads > 0 ? sc.in(read_start, n_reads) : sc.out<i64>(1);
+    a.read_minus = n_reads > 0 ? sc.in(read_minus, n_reads) : sc.out<uint8_t>(1);
+    a.read_off = sc.in(read_off, n_reads + 1);
+    a.means = total > 0 ? sc.in(means, total) : sc.out<double>(1);
+    i32 *cov = sc.out<i32>(n_pos);
+    i64 *lv_off = sc.out<i64>(n_pos + 1);
+    double *d_level = sc.out<double>(n_pos), *d_sd = sc.out<double>(n_pos);
+    if (sc.rc) return sc.rc;
+    k_kest_pileup<false><<<grid_for(n_pos), 256, 0, e->stream>>>(a, cov, nullptr, nullptr);
+    k_kest_offsets<<<1, 256, 0, e->stream>>>(n_pos, cov, lv_off);
+    i64 n_lv = 0;
+    if (sc.sync(e->stream) || sc.get(&n_lv, lv_off + n_pos, 1)) return sc.rc;
+    double *d_lv = sc.out<double>(n_lv);
+    if (sc.rc) return sc.rc;
+    k_kest_pileup<true><<<grid_for(n_pos), 256, 0, e->stream>>>(a, nullptr, lv_off, d_lv);
+    k_kest_moments<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, est_mean, lv_off, d_lv, d_level, d_sd);
+    if (!est_mean) {
+        const i32 *has_nan = sort_segments(e, sc, n_pos, lv_off, d_lv);
+        if (sc.rc) return sc.rc;
+        k_kest_median<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, has_nan, lv_off, d_lv, d_level);
+    }
+    // the entries by key: at most 1024 chunks and at most 2^24 counters, a chunk a multiple of 64 entries
+    int key_bits = 0;
+    while (((i64)1 << key_bits) < n_keys) key_bits++;
+    const i64 max_chunks = std::max<i64>(1, std::min<i64>(1024, ((i64)1 << 24) / n_keys));
+    const i64 chunk = std::max<i64>(4096, ((n_ent + max_chunks - 1) / max_chunks + 63) / 64 * 64);
+    const i64 n_chunks = (n_ent + chunk - 1) / chunk;
+    const i64 *d_ep = sc.in(ent_pos, n_ent), *d_ek = sc.in(ent_key, n_ent);
+    u32 *rows = sc.out<u32>(n_chunks * n_keys);
+    i64 *d_counts = sc.out<i64>(n_keys), *d_koff = sc.out<i64>(n_keys + 1);
+    double *d_ol = sc.out<double>(n_ent), *d_os = sc.out<double>(n_ent);
+    if (sc.rc || sc.hip(hipMemsetAsync(rows, 0, n_chunks * n_keys * sizeof(u32), e->stream), "hipMemsetAsync"))
+        return sc.rc;
+    k_kest_partition<false><<<(unsigned)n_chunks, 64, 0, e->stream>>>(n_ent, chunk, n_keys, key_bits, d_ep, d_ek, rows,
+        nullptr, nullptr, nullptr, nullptr, nullptr);
+    k_kmer_colscan<<<grid_for(n_keys), 256, 0, e->stream>>>(n_keys, n_chunks, rows, d_counts);
+    k_kmer_offsets<<<1, 64, 0, e->stream>>>(n_keys, d_counts, d_koff);
+    k_kest_partition<true><<<(unsigned)n_chunks, 64, 0, e->stream>>>(n_ent, chunk, n_keys, key_bits, d_ep, d_ek, rows,
+        d_koff, d_level, d_sd, d_ol, d_os);
+    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.get(out_counts, d_counts, n_keys) || sc.get(out_off, d_koff, n_keys + 1) ||
+        sc.get(out_levels, d_ol, n_ent))
+        return sc.rc;
+    return sc.get(out_sds, d_os, n_ent);
+}
+
+extern "C" int tba_segment_medians(tba_engine *e, const double *values, const int64_t *off, int64_t n_seg,
+    double *out_medians)
+{
+    if (!e || !off || n_seg < 0 || (n_seg > 0 && !out_medians)) return set_err(TBA_E_ARG, "bad arguments");
+    if (n_seg == 0) return TBA_OK;
+    if (const int rc = check_csr_off(off, n_seg)) return rc;
+    for (i64 s = 0; s < n_seg; s++)
+        if (off[s + 1] - off[s] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "segment of more than 2^31 - 1 values");
+    const i64 n = off[n_seg];
+    if (n > 0 && !values) return set_err(TBA_E_ARG, "bad arguments");
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    double *d_v = n > 0 ? sc.in(values, n) : sc.out<double>(1);
+    const i64 *d_off = sc.in(off, n_seg + 1);
+    double *d_out = sc.out<double>(n_seg);
+    const i32 *has_nan = sort_segments(e, sc, n_seg, d_off, d_v);
+    if (sc.rc) return sc.rc;
+    k_kest_median<<<grid_for(n_seg), 256, 0, e->stream>>>(n_seg, has_nan, d_off, d_v, d_out);
+    if (sc.sync(e->stream)) return sc.rc;
+    return sc.get(out_medians, d_out, n_seg);
 }
 
 // testable slice of every read -> CSR offsets into a packed copy of (means, levels); one thread

@@ -175,21 +175,63 @@ SINGLE_LETTER_CODE = {
 
 
 class TomboMotif(object):
-    """Sequence motif with the (1-based) modified position (tombo_helper.py:542-626): the part
-    the alternative-model statistic uses -- `motif_pat`, `motif_len`, `mod_pos`, `mod_base`."""
+    """Sequence motif with the (1-based) modified position (tombo_helper.py:542-707): `motif_pat`,
+    `rev_comp_pat`, `is_palindrome`, `motif_len`, `mod_pos`, `mod_base`; with a modified position
+    also `find_mod_poss` and `matches_seq`, which count partial matches at either end of a
+    sequence as long as they hold the modified position."""
+
+    @staticmethod
+    def _parse_motif(raw_motif, rev_comp_motif=False):
+        conv = ''.join(SINGLE_LETTER_CODE[c] for c in raw_motif)
+        if rev_comp_motif:   # reverse complement, then the group brackets the right way round again
+            conv = rev_comp(conv).translate({ord('['): ']', ord(']'): '['})
+        return re.compile(conv)
 
     def __init__(self, raw_motif, mod_pos=None):
-        import re
         bad = [c for c in raw_motif if c not in SINGLE_LETTER_CODE]
         if bad:
             raise ValueError('Invalid characters in motif: ' + ', '.join(bad))
         self.raw_motif = raw_motif
         self.motif_len = len(raw_motif)
-        self.motif_pat = re.compile(''.join(SINGLE_LETTER_CODE[c] for c in raw_motif))
+        self.motif_pat = self._parse_motif(raw_motif)
+        self.rev_comp_pat = self._parse_motif(raw_motif, True)
+        self.is_palindrome = self.motif_pat == self.rev_comp_pat
         self.mod_pos = mod_pos
         self.mod_base = None if mod_pos is None else raw_motif[mod_pos - 1]
         if mod_pos is not None:
             assert 0 < mod_pos <= self.motif_len
+            # partial patterns that still hold mod_pos: by length, (pattern, mod_pos inside it) for a
+            # sequence start, a sequence end, and (a list) for a sequence shorter than the motif
+            L, mp = self.motif_len, mod_pos
+            self._partial_pats = {
+                'start': dict((L - o - 1, (self._parse_motif(raw_motif[o + 1:]), mp - o - 1)) for o in range(mp - 1)),
+                'end': dict((L - o - 1, (self._parse_motif(raw_motif[:-(o + 1)]), mp)) for o in range(L - mp)),
+                'short': dict((n, [(self._parse_motif(raw_motif[o:o + n]), mp - o)
+                                   for o in range(max(0, mp - n), min(L - n + 1, mp))]) for n in range(1, L))}
+
+    def _iter_partial(self, seq):
+        """(where, matched length, mod_pos in the pattern, match start) of every full or partial match"""
+        for n in range(1, min(len(seq) + 1, self.motif_len)):
+            if n in self._partial_pats['start'] and self._partial_pats['start'][n][0].match(seq[:n]):
+                yield self._partial_pats['start'][n][1]
+        if len(seq) < self.motif_len:
+            for pat, mp in self._partial_pats['short'].get(len(seq), ()):
+                if pat.match(seq):
+                    yield mp
+        else:
+            for m in self.motif_pat.finditer(seq):
+                yield m.start() + self.mod_pos
+        for n in range(1, min(len(seq) + 1, self.motif_len)):
+            if n in self._partial_pats['end'] and self._partial_pats['end'][n][0].match(seq[-n:]):
+                yield len(seq) - n + self._partial_pats['end'][n][1]
+
+    def find_mod_poss(self, seq):
+        """sorted 1-based positions of the modified base in `seq` (tombo_helper.py:672-707)"""
+        return sorted(set(self._iter_partial(seq)))
+
+    def matches_seq(self, seq):
+        """does the motif match `seq` with the modified position inside it? (tombo_helper.py:637-670)"""
+        return next(self._iter_partial(seq), None) is not None
 
 
 def read_from_results(rsqgl_res, norm_means, fn=None, corr_group='RawGenomeCorrected_000',
@@ -385,6 +427,64 @@ class regionData(object):
     def __init__(self, chrm, strand, start, end, reads, seq=None):
         self.chrm, self.strand, self.start, self.end = chrm, strand, int(start), int(end)
         self.reads, self.seq = reads, seq
+
+
+def _region_seq_add_read(rd, start, end, bases):
+    """one read's bases into the interval's list (intervalData._update_seq, tombo_helper.py:1891-1926) ->
+    (bases, covered-so-far).  The slices are the reference's, taken as Python takes them: a read that lies
+    outside the interval moves or resizes the list exactly as it does there."""
+    if rd.seq is None:
+        return bases, max(0, rd.start - start)
+    r_seq = rev_comp(rd.seq) if rd.strand == '-' else rd.seq
+    if rd.start <= start:
+        overlap = rd.end - start
+        if rd.end > end:    # the read covers the interval: its slice IS the sequence
+            bases = r_seq[-overlap:-(rd.end - end)]
+            return bases, len(bases)
+        bases[:overlap] = r_seq[-overlap:]
+        return bases, overlap
+    if rd.end > end:
+        overlap = end - rd.start
+        bases[-overlap:] = r_seq[:overlap]
+        return bases, len(bases)
+    r_len, at = rd.end - rd.start, rd.start - start
+    bases[at:at + r_len] = r_seq
+    return bases, at + r_len
+
+
+def get_region_seq(reads, start, end):
+    """The forward-strand sequence of [start, end) from the reads alone: the reads-only branch of
+    intervalData.add_seq (tombo_helper.py:1928-1975).
+
+    The reads are sorted on (start, end).  The first one gives its bases.  Then the reads are walked in
+    order, keeping as candidate the one that ends furthest; each time a read's start is at or past the
+    covered count, the candidate gives its bases and that read becomes the candidate.  The last candidate
+    gives its bases at the end.  A later read writes over an earlier one where they overlap.
+
+    The reference compares the read's GENOMIC start with the covered count, which is relative to the
+    interval; that comparison is kept as it is.  Positions no read fills stay '-', so an uncovered flank
+    reads '-'.  A minus-strand read gives the reverse complement of its `seq`.  The reads are those of the
+    whole region; one that misses the interval is handled as the reference handles it (see
+    _region_seq_add_read)."""
+    bases = ['-'] * (end - start)
+    if reads is None or len(reads) == 0:
+        return ''.join(bases)
+    rest = sorted(reads, key=lambda r: (r.start, r.end))
+    bases, covered = _region_seq_add_read(rest.pop(0), start, end, bases)
+    if len(rest) == 0 or covered >= end - start:
+        return ''.join(bases)
+    curr = rest.pop(0)
+    for nxt in rest:
+        if nxt.start >= covered:
+            bases, covered = _region_seq_add_read(curr, start, end, bases)
+            curr = nxt
+            if covered >= end - start:
+                return ''.join(bases)
+            continue
+        if nxt.end > curr.end:
+            curr = nxt
+    bases, _ = _region_seq_add_read(curr, start, end, bases)
+    return ''.join(bases)
 
 
 # ---- genome tracks: coverage, mean signal / SD / dwell per position, sample - control ---------

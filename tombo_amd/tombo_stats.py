@@ -117,6 +117,27 @@ class TomboModel(object):
             idx = idx[::-1]
         return self.level_means[idx], self.level_sds[idx]
 
+    def _center_model(self, shift_corr_factor, scale_corr_factor):
+        """tombo_stats.py:587-595: every level times the scale factor, plus the shift factor"""
+        self.level_means = (self.level_means * scale_corr_factor) + shift_corr_factor
+        self._dicts = None
+
+    def _make_constant_sd(self):
+        """tombo_stats.py:597-600: every spread becomes the median spread"""
+        self.level_sds = np.full(self.level_sds.shape[0], np.median(self.level_sds))
+        self._dicts = None
+
+    def write_model(self, ref_fp):
+        """tombo_stats.py:602-621 into `ref_fp`, any object with the h5py group interface (an open
+        h5py.File): the record array `model` (kmer, mean, sd) in lexicographic k-mer order and the
+        attributes central_pos and model_name"""
+        kmers = _all_kmers(self.kmer_width)
+        tab = np.array(list(zip(kmers, self.level_means.tolist(), self.level_sds.tolist())),
+                       dtype=[(str('kmer'), 'S%d' % self.kmer_width), (str('mean'), 'f8'), (str('sd'), 'f8')])
+        ref_fp.create_dataset('model', data=tab, compression='gzip')
+        ref_fp.attrs['central_pos'] = self.central_pos
+        ref_fp.attrs['model_name'] = STANDARD_MODEL_NAME
+
     def get_exp_levels_from_seq_with_gaps(self, reg_seq, rev_strand):
         """tombo_stats.py:886-915: levels of every k-mer of reg_seq, NaN for k-mers that touch a
         non-ACGT run"""
@@ -248,6 +269,11 @@ class AltModel(object):
         nan = float('nan')
         return (np.array([self.means.get((k, p), nan) for k, p in zip(seq_kmers, pos_range)]),
                 np.array([self.sds.get((k, p), nan) for k, p in zip(seq_kmers, pos_range)]))
+
+    def _make_constant_sd(self):
+        """tombo_stats.py:955-958: every spread becomes the median spread"""
+        med_sd = np.median(list(self.sds.values()))
+        self.sds = dict((key, med_sd) for key in self.sds)
 
     def write_model(self, ref_fp):
         """tombo_stats.py:929-953 into `ref_fp`, any object with the h5py group interface (an open
@@ -1191,3 +1217,374 @@ def estimate_alt_model(reads, ctrl_reads, std_ref, alt_base, alt_frac_pctl, kmer
     else:
         alt_dens, std_dens, std_ref, save_x = load_kmer_densities(alt_dens_fn, std_dens_fn, std_ref)
     return isolate_alt_density(alt_dens, std_dens, alt_base, alt_frac_pctl, std_ref, save_x)
+
+
+# ---------------------------------------------------------------------------------------------
+# Canonical and motif k-mer model estimation: `tombo build_model estimate_reference` /
+# `estimate_motif_alt_reference` (tombo_stats.py:1242-1501, :1716-1740, :2108-2189).  The reference
+# loops over the covered positions of every region in worker processes; here the host does what
+# the reference does with strings (region sequence, motif search, k-mer codes, the key of each
+# entry) and the coverage intervals, and a batch of regions is ONE `Engine.region_key_levels` call
+# that does all arithmetic over levels (kernels in csrc/k_kmer_est.h).  The tabulation is one
+# `Engine.segment_medians` call per column.
+NUM_READS_TO_ADJUST_MODEL = 5000     # _default_parameters.py:174
+STANDARD_MODEL_NAME = 'standard'     # tombo_stats.py:87
+KMER_EST_MAX_LEVELS = 1 << 24        # levels piled up per engine call (128 MB of float64)
+
+# keys: k-mers in lexicographic order, or (k-mer, offset) in the order of tabulate_mod_kmer_levels;
+# levels[off[k]:off[k + 1]] / sds[...]: the (level, spread) pairs of key k in region order, then
+# position order; n_regions: the regions that got as far as a coverage interval
+KmerLevelTable = namedtuple('KmerLevelTable', 'keys off levels sds n_regions')
+
+
+def motif_kmer_keys(kmer_width, motif):
+    """[(kmer, offset)] in the order tabulate_mod_kmer_levels walks them (tombo_stats.py:2116-2118)"""
+    return [(kmer, p - 1) for kmer in _all_kmers(kmer_width) for p in motif.find_mod_poss(kmer)]
+
+
+def _window_codes(int_seq, kmer_width, minus):
+    """the k-mer index of every window of int_seq (the reverse complement's on the minus strand); -1 for a
+    window with anything but ACGT"""
+    codes = encode_seq(int_seq).astype(np.int64)
+    n = codes.shape[0] - kmer_width + 1
+    if n <= 0:
+        return np.empty(0, dtype=np.int64)
+    idx, bad = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=bool)
+    for j in range(kmer_width):
+        c = codes[kmer_width - 1 - j:kmer_width - 1 - j + n] if minus else codes[j:j + n]
+        bad |= c > 3
+        idx = idx * 4 + ((3 - c) if minus else c)
+    idx[bad] = -1
+    return idx
+
+
+def _subsample_region_reads(reads, reg_start, reg_end, region_size, cs_cov_thresh):
+    """tombo_stats.py:1247-1260: shuffle, then keep the reads before the first one at which the running sum of
+    max(r.end, reg.end) - min(r.start, reg.start) reaches region_size * cs_cov_thresh (all, if it never does)"""
+    np.random.shuffle(reads)
+    csum = np.cumsum([max(rd.end, reg_end) - min(rd.start, reg_start) for rd in reads])
+    hit = np.flatnonzero(csum >= region_size * cs_cov_thresh)
+    return reads[:int(hit[0])] if hit.shape[0] else reads
+
+
+def _region_entries(chrm, strand, reg_start, region_size, reads, lv_reads, cov_thresh, upstrm_bases, dnstrm_bases,
+                    motif, valid_poss, key_of):
+    """get_region_kmer_levels after the subsampling, up to the arithmetic: (genomic position, key) of every
+    entry of the region in the reference's order, or None when the region has no coverage interval.
+    reads: the region's reads (they give the sequence); lv_reads: those whose levels count."""
+    K = upstrm_bases + dnstrm_bases + 1
+    diff = np.zeros(region_size + 1, dtype=np.int64)
+    for rd in lv_reads:
+        a, b = max(rd.start, reg_start) - reg_start, min(rd.end, reg_start + region_size) - reg_start
+        if b > a:
+            diff[a] += 1
+            diff[b] -= 1
+    reg_cov = np.cumsum(diff[:-1])
+    edges = np.flatnonzero(np.diff(np.concatenate([[False], reg_cov > cov_thresh])))
+    if reg_cov[-1] > cov_thresh:
+        edges = np.concatenate([edges, [region_size]])
+    if edges.shape[0] <= 1:
+        return None
+    minus = strand == '-'
+    bb, ab = (dnstrm_bases, upstrm_bases) if minus else (upstrm_bases, dnstrm_bases)
+    ent_g, ent_key = [], []
+    for cov_start, cov_end in edges.reshape(-1, 2).tolist():
+        int_len = cov_end - cov_start
+        int_seq = th.get_region_seq(reads, reg_start + cov_start - bb, reg_start + cov_end + ab)
+        win = _window_codes(int_seq, K, minus)
+        if valid_poss is None and motif is None:
+            poss, keys = np.arange(min(int_len, win.shape[0]), dtype=np.int64), win[:int_len]
+        else:
+            if valid_poss is not None:
+                if (chrm, strand) not in valid_poss:
+                    continue
+                mod_poss = np.asarray(valid_poss[(chrm, strand)], dtype=np.int64) - reg_start - cov_start
+                mod_poss = mod_poss[(mod_poss >= 0) & (mod_poss < int_len)].tolist()
+            elif not minus:
+                mod_poss = [m.start() + motif.mod_pos - 1 - bb for m in motif.motif_pat.finditer(int_seq)]
+            else:
+                mod_poss = [m.start() + motif.motif_len - motif.mod_pos - bb
+                            for m in motif.rev_comp_pat.finditer(int_seq)]
+            pairs = [(mp - i + bb, K - i - 1 if minus else i) for mp in mod_poss if 0 <= mp < int_len
+                     for i in range(K) if 0 <= mp - i + bb < min(int_len, win.shape[0])]
+            poss = np.array([p for p, _ in pairs], dtype=np.int64)
+            offs = np.array([o for _, o in pairs], dtype=np.int64)
+            keys = np.where(win[poss] >= 0, key_of[np.maximum(win[poss], 0) * K + offs], -1) if pairs else poss
+        # (a position no read of the region has a level at: the reference's KeyError, skipped)
+        keep = (keys >= 0) & (reg_cov[poss + cov_start] > 0)
+        ent_g.append(poss[keep] + reg_start + cov_start)
+        ent_key.append(keys[keep])
+    cat = (lambda xs: np.concatenate(xs) if xs else np.empty(0, dtype=np.int64))
+    return cat(ent_g), cat(ent_key), reg_cov
+
+
+class _KmerEstBatch(object):
+    """the regions of one `region_key_levels` call: reads once, regions by read index, positions once"""
+
+    def __init__(self):
+        self.read_idx, self.reads, self.reg_reads, self.reg_read_off = {}, [], [], [0]
+        self.pos_reg, self.pos_g, self.ent_pos, self.ent_key, self.n_pos, self.n_levels = [], [], [], [], 0, 0
+
+    def add(self, lv_reads, ent_g, ent_key, reg_start, reg_cov):
+        for rd in lv_reads:
+            if id(rd) not in self.read_idx:
+                self.read_idx[id(rd)] = len(self.reads)
+                self.reads.append(rd)
+            self.reg_reads.append(self.read_idx[id(rd)])
+        self.reg_read_off.append(len(self.reg_reads))
+        uniq, inv = np.unique(ent_g, return_inverse=True)
+        self.pos_reg.append(np.full(uniq.shape[0], len(self.reg_read_off) - 2, dtype=np.int64))
+        self.pos_g.append(uniq)
+        self.ent_pos.append(inv.astype(np.int64).reshape(-1) + self.n_pos)
+        self.ent_key.append(ent_key)
+        self.n_pos += uniq.shape[0]
+        self.n_levels += int(reg_cov[uniq - reg_start].sum())
+
+    def run(self, engine, est_mean, n_keys):
+        cat = (lambda xs: np.ascontiguousarray(np.concatenate(xs), dtype=np.int64))
+        means = [np.asarray(rd.means, dtype=np.float64) for rd in self.reads]
+        return engine.region_key_levels(
+            est_mean, np.array([rd.start for rd in self.reads], dtype=np.int64),
+            np.array([rd.strand == '-' for rd in self.reads], dtype=np.uint8),
+            _csr_offsets([m.shape[0] for m in means]), _concat_f64(means),
+            np.array(self.reg_read_off, dtype=np.int64), np.array(self.reg_reads, dtype=np.int64),
+            cat(self.pos_reg), cat(self.pos_g), cat(self.ent_pos), cat(self.ent_key), n_keys)
+
+
+def extract_kmer_levels(reads_index, region_size, cov_thresh, upstrm_bases, dnstrm_bases, cs_cov_thresh,
+                        est_mean=False, motif=None, valid_poss=None, engine=None,
+                        max_levels=KMER_EST_MAX_LEVELS):
+    """tombo_stats.py:1398-1452 with get_region_kmer_levels (:1242-1359) -> one KmerLevelTable for the run.
+    reads_index: {(chrm, strand): [th.resquiggledRead]}.  Regions come from th.iter_cov_regs; a region's reads
+    are those that overlap it (intervalData.add_reads).  With cs_cov_thresh the region's reads are shuffled
+    with np.random.shuffle and cut as the reference cuts them.  A read without levels, or whose number of
+    levels differs from end - start, gives no levels but still counts in the subsampling and in the sequence.
+    A position is used when more than cov_thresh reads have a level there (NaN levels count, and make that
+    position's pair NaN).  valid_poss: {(chrm, strand): int array} of modified positions, replacing the motif
+    search.  Regions are cut into engine calls of at most max_levels piled-up levels (a single region may
+    exceed it); the result does not depend on the cut.  Raises th.TomboError where the reference exits."""
+    region_size = int(region_size)
+    if region_size < 1 or int(max_levels) < 1:
+        raise ValueError('region_size and max_levels must be positive')
+    if upstrm_bases < 0 or dnstrm_bases < 0:
+        raise ValueError('upstrm_bases and dnstrm_bases must not be negative')
+    if valid_poss is not None and motif is None:
+        raise ValueError('valid_poss needs the motif')
+    eng = _engine(engine)
+    K = upstrm_bases + dnstrm_bases + 1
+    key_of = None
+    if motif is None:
+        keys = _all_kmers(K)
+    else:
+        keys = motif_kmer_keys(K, motif)
+        key_of = np.full(4 ** K * K, -1, dtype=np.int64)
+        for i, (kmer, offset) in enumerate(keys):
+            key_of[TomboModel._kmer_code(kmer) * K + offset] = i
+    n_keys, results, n_regions = len(keys), [], 0
+    batch, spans = _KmerEstBatch(), {}
+    for chrm, strand, reg_start in th.iter_cov_regs(reads_index, cov_thresh, region_size, engine=eng):
+        reg_start, reg_end = int(reg_start), int(reg_start) + region_size
+        if (chrm, strand) not in spans:     # (start, end of the strand's reads once: the overlap test is one numpy line)
+            cs_reads = reads_index.get((chrm, strand), ())
+            spans[(chrm, strand)] = (cs_reads, np.array([rd.start for rd in cs_reads], dtype=np.int64),
+                                     np.array([rd.end for rd in cs_reads], dtype=np.int64))
+        cs_reads, cs_start, cs_end = spans[(chrm, strand)]
+        reads = [cs_reads[i] for i in np.flatnonzero((cs_start < reg_end) & (cs_end > reg_start)).tolist()]
+        if len(reads) == 0:
+            continue
+        if cs_cov_thresh is not None:
+            reads = _subsample_region_reads(reads, reg_start, reg_end, region_size, cs_cov_thresh)
+        lv_reads = [rd for rd in reads if rd.means is not None and len(rd.means) == rd.end - rd.start]
+        if len(lv_reads) == 0:
+            continue
+        ent = _region_entries(chrm, strand, reg_start, region_size, reads, lv_reads, cov_thresh, upstrm_bases,
+                              dnstrm_bases, motif, valid_poss, key_of)
+        if ent is None:
+            continue
+        n_regions += 1
+        if ent[0].shape[0] == 0:
+            continue
+        batch.add(lv_reads, ent[0], ent[1], reg_start, ent[2])
+        if batch.n_levels >= max_levels:
+            results.append(batch.run(eng, est_mean, n_keys))
+            batch = _KmerEstBatch()
+    if batch.n_pos:
+        results.append(batch.run(eng, est_mean, n_keys))
+    if n_regions == 0:
+        raise th.TomboError('No genomic positions contain --minimum-test-reads. Consider ' +
+                            'setting this option to a lower value.')
+    # the one concatenation per key: batch b's pairs of key k follow those of the earlier batches
+    totals = np.zeros(n_keys, dtype=np.int64)
+    for counts, _, _, _ in results:
+        totals += counts
+    out_off = _csr_offsets(totals)
+    levels, sds = np.empty(int(out_off[-1]), dtype=np.float64), np.empty(int(out_off[-1]), dtype=np.float64)
+    before = np.zeros(n_keys, dtype=np.int64)
+    for counts, koff, lv, sd in results:
+        at = np.repeat(out_off[:-1] + before - koff[:-1], counts) + np.arange(lv.shape[0])
+        levels[at], sds[at] = lv, sd
+        before += counts
+    return KmerLevelTable(keys, out_off, levels, sds, n_regions)
+
+
+_NO_OBS_MSG = ('At least one %sk-mer is not covered at any poitions by --minimum-test-reads.\n\t\tConsider fitting '
+               'to a smaller k-mer via the --upstream-bases and --downstream-bases, or lowering '
+               '--minimum-test-reads.\n\t\tNote that this may result in a lower quality model.')
+_FEW_OBS_MSG = ('K-mers represeneted in fewer observations than requested in the provided reads. Consider a '
+                'shorter k-mer or providing more reads.\n\t%d observations found in least common kmer.')
+
+
+def _tabulate(table, min_kmer_obs, engine, what):
+    counts = np.diff(table.off)
+    short = np.flatnonzero((counts == 0) | (counts < min_kmer_obs))
+    if short.shape[0]:     # the reference meets the keys in order: the first one that falls short decides
+        if counts[short[0]] == 0:
+            raise th.TomboError(_NO_OBS_MSG % what)
+        raise th.TomboError(_FEW_OBS_MSG % int(counts.min()))
+    eng = _engine(engine)
+    return eng.segment_medians(table.levels, table.off), eng.segment_medians(table.sds, table.off)
+
+
+def tabulate_kmer_levels(table, min_kmer_obs, engine=None):
+    """tombo_stats.py:1454-1501: [(kmer, median level, median sd)] in lexicographic k-mer order.  Where the
+    reference names an undefined `motif` in its too-few-observations branch (and dies with NameError), the
+    message it meant is raised."""
+    lv, sd = _tabulate(table, min_kmer_obs, engine, '')
+    return [(kmer, lv[i], sd[i]) for i, kmer in enumerate(table.keys)]
+
+
+def tabulate_mod_kmer_levels(table, min_kmer_obs, motif, engine=None):
+    """tombo_stats.py:2108-2158: [(kmer, offset, median level, median sd)] in the order of motif_kmer_keys"""
+    if list(table.keys) != motif_kmer_keys(len(table.keys[0][0]) if table.keys else 1, motif):
+        raise ValueError('the table was not extracted with this motif')
+    lv, sd = _tabulate(table, min_kmer_obs, engine, 'modified ')
+    return [(kmer, offset, lv[i], sd[i]) for i, (kmer, offset) in enumerate(table.keys)]
+
+
+# what center_model_to_median_norm takes per read, in memory: the raw signal, the `start` column of the read's
+# Events table, its bases (read-centric, one per event) and read_start_rel_to_raw
+CenterRead = namedtuple('CenterRead', 'raw_signal event_starts seq read_start_rel_to_raw rna')
+CenterRead.__new__.__defaults__ = (False,)
+_NO_CENTER_READS_MSG = 'No reads succcessfully processed for sequence-based normalization parameter re-fitting.'
+_FEW_CENTER_READS_MSG = ('Fewer reads succcessfully processed for sequence-based normalization parameter '
+                         're-fitting than requested.')
+
+
+def _read_corr_factors(eng, rd, init_ref, params, opts, min_raw):
+    """get_read_corr_factors (tombo_stats.py:1624-1667) of one DNA read -> (shift_corr_factor, scale_corr_factor).
+    Two slices of the resident pipeline: the median normalisation of the whole raw signal, then the read's own
+    boundaries over that signal against init_ref's levels of its sequence through the Theil-Sen stage.  Raises
+    th.TomboError where the reference's read raises (and is skipped)."""
+    from . import errors
+    K, up = init_ref.kmer_width, init_ref.central_pos
+    dn = K - up - 1
+    if dn < 1:
+        raise th.TomboError('Must have at least one upstream and downstream base for a Tombo model.')
+    raw = np.ascontiguousarray(rd.raw_signal, dtype=np.float64)
+    starts = np.asarray(rd.event_starts).astype(np.int64)
+    codes = encode_seq(rd.seq)
+    if (codes > 3).any():
+        raise th.TomboError(errors.MESSAGES[22])
+    if starts.shape[0] != codes.shape[0] or codes.shape[0] < K + 1:
+        raise th.TomboError('Read events and sequence differ in number, or the read is shorter than two k-mers.')
+    rsrtr = int(rd.read_start_rel_to_raw) + int(starts[up])
+    starts = starts[up:-(dn - 1)] if dn > 1 else starts[up:]
+    starts = starts - starts[0]
+    norm_len = int(starts[-1])
+    if rsrtr < 0 or rsrtr + norm_len > raw.shape[0] or (np.diff(starts) <= 0).any() or raw.shape[0] < min_raw:
+        raise th.TomboError('Read events do not fit the raw signal.')
+    # (the draw comes after everything that can fail on the host, as in the reference: tombo_stats.py:411-414)
+    n_points = starts.shape[0] - 1
+    samp = None
+    if n_points > _native.MAX_POINTS_FOR_THEIL_SEN:
+        samp = _native.pack_samp_inds([np.random.choice(n_points, _native.MAX_POINTS_FOR_THEIL_SEN, replace=False)])
+    # slice 1: normalize_raw_signal(all_raw_signal) -- the segmentation that shares the stage is not used
+    eng.set_num_events([2])
+    eng.upload(params, opts, [raw], [codes])
+    eng.run_stages(_native.STAGE_SEGMENT, _native.STAGE_SEGMENT)
+    st = int(eng.get(_native.GET_STATUS)[0])
+    if st not in (0, 2):     # (2: the two change points asked for were not found; the signal is normalised before)
+        errors.raise_for_status(st)
+    norm = eng.get(_native.GET_SEG_NORM)[:raw.shape[0]].copy()
+    # slice 2: expected levels of the sequence, base means over the given boundaries, Theil-Sen
+    eng.set_num_events([2])
+    eng.upload(params, opts, [norm], [codes], samp_ind=samp)
+    eng.put(_native.PUT_NORM, norm)
+    eng.put(_native.PUT_DP_SEGS, starts, per_read=[rsrtr, norm_len])
+    eng.run_stages(_native.STAGE_REF_LEVELS, _native.STAGE_REF_LEVELS)
+    eng.run_stages(_native.STAGE_SKIP, _native.STAGE_RESCALE)
+    errors.raise_for_status(int(eng.get(_native.GET_STATUS)[0]))
+    fit = eng.get(_native.GET_THEIL_SEN)[0]
+    return fit[2], fit[3]     # -inter / slope, 1 / slope
+
+
+def center_model_to_median_norm(reads, init_ref, max_reads=NUM_READS_TO_ADJUST_MODEL, engine=None):
+    """tombo_stats.py:1599-1705: shift and scale init_ref (in place; it is returned) so that median-normalised
+    reads fit it.  reads: CenterRead-like objects (raw_signal, event_starts, seq, read_start_rel_to_raw, rna).
+    They are shuffled with np.random.shuffle; then read by read the raw signal is median-normalised, the event
+    starts clipped to the model's k-mer flanks, and the Theil-Sen line of init_ref's levels over the base means
+    gives shift_corr_factor = -inter / slope and scale_corr_factor = 1 / slope (a read of more than
+    MAX_POINTS_FOR_THEIL_SEN points is drawn with np.random.choice, in read order).  A read that fails is skipped;
+    the first max_reads successes count; the medians of their factors go to init_ref._center_model.  Raises
+    th.TomboError without a success, warns with fewer than max_reads.  RNA reads are refused.  A read with fewer
+    raw samples than the engine's segmentation needs (4 * running_stat_width + 2) counts as failed."""
+    reads = list(reads)
+    if any(getattr(rd, 'rna', False) for rd in reads):
+        raise NotImplementedError('center_model_to_median_norm: RNA reads (signal reversal, event-based scale '
+                                  'values) are not built')
+    eng = _engine(engine)
+    rsqgl_params = load_resquiggle_parameters(th.seqSampleType(DNA_SAMP_TYPE, False))
+    params, opts = _native.make_params(rsqgl_params), _native.make_opts()
+    min_raw = 4 * int(rsqgl_params.running_stat_width) + 2
+    eng.ensure_model(init_ref)      # (Engine.set_model, and the engine knows which table it holds)
+    np.random.shuffle(reads)
+    shifts, scales = [], []
+    for rd in reads:
+        try:
+            shift_corr, scale_corr = _read_corr_factors(eng, rd, init_ref, params, opts, min_raw)
+        except th.TomboError:
+            continue
+        shifts.append(shift_corr)
+        scales.append(scale_corr)
+        if len(shifts) >= max_reads:
+            break
+    if len(shifts) < max_reads:
+        if len(shifts) == 0:
+            raise th.TomboError(_NO_CENTER_READS_MSG)
+        warnings.warn(_FEW_CENTER_READS_MSG)
+    init_ref._center_model(np.median(shifts), np.median(scales))
+    return init_ref
+
+
+def estimate_kmer_model(reads_index, cov_thresh, upstrm_bases, dnstrm_bases, min_kmer_obs, kmer_specific_sd,
+                        cs_cov_thresh, est_mean, region_size, center_reads=None, engine=None):
+    """The canonical k-mer model of the reads; WITHOUT center_reads it is left uncentred, which the reference never
+    returns (a warning says so).  tombo_stats.py:1716-1740 after the file access.  center_reads: the reads
+    center_model_to_median_norm takes; the reference centres on reads of the same index."""
+    table = extract_kmer_levels(reads_index, region_size, cov_thresh, upstrm_bases, dnstrm_bases, cs_cov_thresh,
+                                est_mean, engine=engine)
+    ref = TomboModel(kmer_ref=tabulate_kmer_levels(table, min_kmer_obs, engine=engine), central_pos=upstrm_bases)
+    if center_reads is not None:
+        ref = center_model_to_median_norm(center_reads, ref, engine=engine)
+    else:
+        warnings.warn('estimate_kmer_model: no center_reads given, the model is not centred to median normalisation')
+    if not kmer_specific_sd:
+        ref._make_constant_sd()
+    return ref
+
+
+def estimate_motif_alt_model(reads_index, motif_desc, upstrm_bases, dnstrm_bases, valid_poss, min_kmer_obs,
+                             cov_thresh, cs_cov_thresh, region_size, engine=None):
+    """tombo_stats.py:2160-2189 after the file access: a motif-centred alternate-base model, constant sd.
+    motif_desc: 'MOTIF:mod_pos' (1-based); valid_poss: None or {(chrm, strand): int array}."""
+    try:
+        raw_motif, mod_pos = motif_desc.split(':')
+    except Exception:
+        raise th.TomboError('Invalid motif decription format.')
+    motif = th.TomboMotif(raw_motif, int(mod_pos))
+    table = extract_kmer_levels(reads_index, region_size, cov_thresh, upstrm_bases, dnstrm_bases, cs_cov_thresh,
+                                False, motif, valid_poss, engine=engine)
+    alt_ref = AltModel(kmer_ref=tabulate_mod_kmer_levels(table, min_kmer_obs, motif, engine=engine),
+                       central_pos=upstrm_bases, alt_base=motif.mod_base, motif=motif)
+    alt_ref._make_constant_sd()
+    return alt_ref
