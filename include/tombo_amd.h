@@ -549,6 +549,27 @@ int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, const int64_t 
     int64_t *out_valid_cov, double *out_damp_frac, int64_t *out_counts, int64_t *out_n_stats,
     double *out_per_read);
 
+/* The same per-site outputs from STORED per-read statistics (aggregate_per_read_stats,
+ * tombo_stats.py:4699-4777): n_blocks blocks of a per-read statistics file, block t covering
+ * genomic [blk_start[t], blk_end[t]) and owning records rec_off[t] .. rec_off[t + 1] of `records`,
+ * which holds the blocks' records concatenated in the layout they are stored in: numpy's packed
+ * [('pos','u4'),('stat','f8'),('read_id','u4')], 16 bytes per record with the float64 at byte
+ * offset 4 (no repack on the host; the read id is not used).  Any order inside a block.
+ * Validity as above: lower_thresh given; else form 1 (model_compare): |stat| >= single_read_thresh;
+ * else (form 0) every statistic.  NaN statistics are dropped.  Outputs as tba_site_fractions, a
+ * block being a track: block t owns entries from P_t = sum of the earlier blocks' lengths, a block
+ * without records gives out_counts[t] = 0.  Only the outputs are copied back.  out_kernel_ms (may
+ * be NULL): device time of the call's kernels (hipEvents).
+ * TBA_E_ARG: NULL pointers, offsets that do not start at 0 or decrease, a block with
+ * end <= start, 2^31 positions or more in one call (nothing is launched for any of these); a
+ * record whose position lies outside its block (found on the device: such a record is counted
+ * and otherwise ignored, no output is written). */
+int tba_site_aggregate(tba_engine *e, int64_t n_blocks, const int64_t *blk_start,
+    const int64_t *blk_end, const int64_t *rec_off, const void *records, double single_read_thresh,
+    const double *lower_thresh, int form, const double *damp_counts, double *out_frac,
+    int64_t *out_pos, int64_t *out_cov, int64_t *out_valid_cov, double *out_damp_frac,
+    int64_t *out_counts, int64_t *out_n_stats, double *out_kernel_ms);
+
 /* ---- alternate-base model estimation (estimate_alt_model, tombo_stats.py:1747-2098) -----------
  * The base levels of a batch of reads gathered by k-mer (_parse_base_levels_worker, :1747-1776).
  * means / codes: read-centric levels and base codes (0..3 = ACGT, anything else: not a base) of

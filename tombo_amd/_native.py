@@ -330,6 +330,28 @@ def _check_compact_args(values):
 SiteFractions = namedtuple('SiteFractions', 'pos_off frac poss cov valid damp counts n_stats per_read')
 
 
+# a stored per-read record (PerReadStats block_stats): numpy's packed layout, 16 bytes, the float64 at offset 4
+PER_READ_DTYPE = np.dtype([('pos', 'u4'), ('stat', 'f8'), ('read_id', 'u4')])
+
+
+def _check_site_aggregate_args(blk_start, blk_end, rec_off, records):
+    """-> contiguous (blk_start, blk_end, rec_off, records) of site_aggregate, or ValueError"""
+    bs, be, off = (np.ascontiguousarray(np.asarray(v, dtype=np.int64)) for v in (blk_start, blk_end, rec_off))
+    rec = np.asarray(records)
+    if bs.ndim != 1 or be.shape != bs.shape or off.shape != (bs.shape[0] + 1,):
+        raise ValueError('blk_start, blk_end must have one entry per block and rec_off one more')
+    if rec.dtype != PER_READ_DTYPE or rec.ndim != 1:
+        raise ValueError("records must be a one-dimensional array of the stored per-read layout "
+                         "[('pos', 'u4'), ('stat', 'f8'), ('read_id', 'u4')] (packed, 16 bytes)")
+    if off[0] != 0 or np.any(np.diff(off) < 0) or int(off[-1]) != rec.shape[0]:
+        raise ValueError('rec_off must start at 0, not decrease and end at len(records)')
+    if np.any(be <= bs):
+        raise ValueError('a block must have end > start')
+    if int((be - bs).sum()) >= 2 ** 31:
+        raise ValueError('2^31 positions or more in one call')
+    return bs, be, off, np.ascontiguousarray(rec)
+
+
 def _site_other_form(form):
     """typed nulls and zeros for the arguments of tba_site_fractions that the form in use leaves out"""
     nd, ni = C.cast(None, C.POINTER(f64)), C.cast(None, C.POINTER(i64))
@@ -920,6 +942,29 @@ class Engine(object):
         return self._site_fractions(1, trk_start, trk_end, (_p(m, f64), _p(r, f64)) + _site_other_form(1),
                                     win_args, st.shape[0], single_read_thresh, lower_thresh, damp_counts,
                                     return_per_read)
+
+    def site_aggregate(self, blk_start, blk_end, rec_off, records, single_read_thresh, lower_thresh=None,
+                       abs_rule=False, damp_counts=None):
+        """tba_site_aggregate: the per-site fractions of stored per-read blocks (aggregate_per_read_stats).  Block t
+        covers [blk_start[t], blk_end[t]) and owns records[rec_off[t]:rec_off[t + 1]] (PER_READ_DTYPE, uploaded as
+        stored) -> SiteFractions (per_read None).  abs_rule: model_compare's |stat| >= single_read_thresh validity
+        when no lower threshold is given.  `last_site_aggregate_kernel_ms`: device time of the call's kernels."""
+        bs, be, off, rec = _check_site_aggregate_args(blk_start, blk_end, rec_off, records)
+        pos_off = np.concatenate([[0], np.cumsum(be - bs)]).astype(np.int64)
+        n_blk, n_pos = bs.shape[0], int(pos_off[-1])
+        frac = np.empty(n_pos, dtype=np.float64)
+        poss, cov, valid = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
+        counts, n_stats = np.zeros(n_blk, dtype=np.int64), np.zeros(n_blk, dtype=np.int64)
+        damp = None if damp_counts is None else np.empty(n_pos, dtype=np.float64)
+        ms = f64(0.0)
+        self._check(self._L.tba_site_aggregate(
+            self._h, i64(n_blk), _p(bs, i64), _p(be, i64), _p(off, i64), C.c_void_p(rec.ctypes.data),
+            f64(float(single_read_thresh)), None if lower_thresh is None else (f64 * 1)(float(lower_thresh)),
+            C.c_int(int(bool(abs_rule))), None if damp_counts is None else (f64 * 2)(*damp_counts), _p(frac, f64),
+            _p(poss, i64), _p(cov, i64), _p(valid, i64), _p(damp, f64), _p(counts, i64), _p(n_stats, i64),
+            C.byref(ms)), 'tba_site_aggregate')
+        self.last_site_aggregate_kernel_ms = ms.value
+        return SiteFractions(pos_off, frac, poss, cov, valid, damp, counts, n_stats, None)
 
     def kmer_levels(self, means, codes, read_off, kmer_width, central_pos, completed):
         """tba_kmer_levels: the levels of a batch of reads (means / codes CSR by read_off) gathered by k-mer

@@ -11,6 +11,8 @@
 //                           atomic adds on the counters (cov, valid, ge) of its (track, position)
 //   k_site_stat             the same scatter from statistics k_read_pvals left on the device
 //                           (Fisher's method, fm_offset > 0)
+//   k_site_rec              the same scatter from STORED per-read records (a per-read statistics
+//                           file: aggregate_per_read_stats), a track being one stored block
 //   k_site_finish           one wavefront per track: positions with cov > 0 compacted in ascending
 //                           order, fraction / coverage / dampened fraction written out
 // The counters are integers, so the sums do not depend on the order the atomics land in.
@@ -67,6 +69,26 @@ __global__ void k_site_stat(SiteArgs a, const double *stats, const i64 *off, i64
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (i64)gridDim.x * blockDim.x) {
         const i64 r = dev_csr_row(off, n_reads, i);
         site_accumulate(a, read_track[r], read_pos[r] + (i - off[r]), stats[i]);
+    }
+}
+
+// stored-record form (aggregate_per_read_stats, tombo_stats.py:4699-4725): recs are the blocks'
+// records in the layout they are stored in, numpy's packed [('pos','u4'),('stat','f8'),
+// ('read_id','u4')]: 16 bytes, the float64 at byte offset 4, so a record is read as one uint4 and
+// the double rebuilt from its two dwords (x: pos, y / z: low / high half of stat, w: read id, not
+// used: the compiler narrows the load to three dwords).  Track t (a block) owns records rec_off[t] .. rec_off[t + 1].  The position comes from
+// the file, not from the host's own bookkeeping, so it is tested against [trk_start, trk_end) of
+// its block BEFORE any counter address is formed: a record outside counts into n_bad and touches
+// nothing else (the entry then fails the call).
+__global__ void k_site_rec(SiteArgs a, const uint4 *recs, const i64 *rec_off, i64 n_recs,
+    const i64 *trk_end, i32 *n_bad)
+{
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n_recs; i += (i64)gridDim.x * blockDim.x) {
+        const uint4 q = recs[i];
+        const i64 t = dev_csr_row(rec_off, a.n_tracks, i);
+        const i64 g = q.x;
+        if (g < a.trk_start[t] || g >= trk_end[t]) { atomicAdd(n_bad, 1); continue; }
+        site_accumulate(a, t, g, __hiloint2double((int)q.z, (int)q.y));
     }
 }
 

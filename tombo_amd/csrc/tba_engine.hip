@@ -2055,6 +2055,78 @@ extern "C" int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, con
     return TBA_OK;
 }
 
+// ---- per-site fractions from stored per-read records: aggregate_per_read_stats -----------------
+extern "C" int tba_site_aggregate(tba_engine *e, int64_t n_blocks, const int64_t *blk_start,
+    const int64_t *blk_end, const int64_t *rec_off, const void *records, double single_read_thresh,
+    const double *lower_thresh, int form, const double *damp_counts, double *out_frac,
+    int64_t *out_pos, int64_t *out_cov, int64_t *out_valid_cov, double *out_damp_frac,
+    int64_t *out_counts, int64_t *out_n_stats, double *out_kernel_ms)
+{
+    if (!e || (form != 0 && form != 1) || n_blocks < 0 || !blk_start || !blk_end || !rec_off ||
+        !out_frac || !out_pos || !out_cov || !out_valid_cov || !out_counts || !out_n_stats ||
+        (!damp_counts) != (!out_damp_frac))
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (n_blocks == 0) return TBA_OK;
+    if (const int rc = check_csr_off(rec_off, n_blocks)) return rc;
+    const i64 n_recs = rec_off[n_blocks];
+    if (n_recs > 0 && !records) return set_err(TBA_E_ARG, "bad arguments");
+    std::vector<i64> pos_off(n_blocks + 1, 0);
+    for (i64 t = 0; t < n_blocks; t++) {
+        if (blk_end[t] <= blk_start[t] || blk_end[t] - blk_start[t] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "bad block");
+        pos_off[t + 1] = pos_off[t] + (blk_end[t] - blk_start[t]);
+        if (pos_off[t + 1] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "2^31 positions or more in one call");
+    }
+    const i64 n_pos = pos_off[n_blocks];
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    SiteArgs a{};
+    a.n_tracks = n_blocks;
+    a.trk_start = sc.in(blk_start, n_blocks);
+    a.pos_off = sc.in(pos_off.data(), n_blocks + 1);
+    a.valid_mode = lower_thresh ? 0 : form == 1 ? 1 : 2;
+    a.single = single_read_thresh;
+    a.lower = lower_thresh ? *lower_thresh : 0.0;
+    a.cnt = sc.out<i32>(3 * n_pos);
+    const i64 *d_end = sc.in(blk_end, n_blocks);
+    const i64 *d_off = sc.in(rec_off, n_blocks + 1);
+    const uint4 *d_rec = n_recs > 0 ? sc.in((const uint4 *)records, n_recs) : nullptr;
+    double *d_frac = sc.out<double>(n_pos), *d_damp = damp_counts ? sc.out<double>(n_pos) : nullptr;
+    i64 *d_pos = sc.out<i64>(n_pos), *d_cov = sc.out<i64>(n_pos), *d_valid = sc.out<i64>(n_pos);
+    i64 *d_counts = sc.out<i64>(n_blocks), *d_ns = sc.out<i64>(n_blocks);
+    i32 *d_bad = sc.status(e->stream);
+    if (sc.rc) return sc.rc;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (out_kernel_ms && (sc.hip(hipEventCreate(&ev0), "hipEventCreate") || sc.hip(hipEventCreate(&ev1), "hipEventCreate"))) {
+        if (ev0) (void)hipEventDestroy(ev0);
+        return sc.rc;
+    }
+    if (ev0) sc.hip(hipEventRecord(ev0, e->stream), "hipEventRecord");
+    sc.hip(hipMemsetAsync(a.cnt, 0, 3 * n_pos * sizeof(i32), e->stream), "hipMemsetAsync");
+    if (n_recs > 0 && !sc.rc)
+        k_site_rec<<<grid_for(n_recs), 256, 0, e->stream>>>(a, d_rec, d_off, n_recs, d_end, d_bad);
+    if (!sc.rc)
+        k_site_finish<<<(unsigned)n_blocks, 64, 0, e->stream>>>(a, damp_counts ? damp_counts[0] : 0.0,
+            damp_counts ? damp_counts[0] + damp_counts[1] : 0.0, d_frac, d_pos, d_cov, d_valid, d_damp,
+            d_counts, d_ns);
+    if (ev1) sc.hip(hipEventRecord(ev1, e->stream), "hipEventRecord");
+    const int n_bad = sc.sync(e->stream, d_bad);
+    if (ev0) {
+        float ms = 0;
+        if (!sc.rc && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *out_kernel_ms = ms;
+        (void)hipEventDestroy(ev0);
+        (void)hipEventDestroy(ev1);
+    }
+    if (sc.rc) return sc.rc;
+    if (n_bad) return set_err(TBA_E_ARG, "record position outside its block");
+    if (sc.get(out_counts, d_counts, n_blocks) || sc.get(out_n_stats, d_ns, n_blocks) ||
+        sc.get(out_frac, d_frac, n_pos) || sc.get(out_pos, d_pos, n_pos) ||
+        sc.get(out_cov, d_cov, n_pos) || sc.get(out_valid_cov, d_valid, n_pos))
+        return sc.rc;
+    if (d_damp) return sc.get(out_damp_frac, d_damp, n_pos);
+    return TBA_OK;
+}
+
 // ---- estimate_alt_model (k_kde.h): levels gathered by k-mer, kernel densities ----------------
 extern "C" int tba_kmer_levels(tba_engine *e, const double *means, const uint8_t *codes,
     const int64_t *read_off, int64_t n_reads, int64_t kmer_width, int64_t central_pos,

@@ -18,8 +18,12 @@ GROUP_NAME, CTRL_NAME = 'sample', 'control'
 COV_WIG_TYPE, SIG_WIG_TYPE, DIFF_WIG_TYPE, SD_WIG_TYPE, DWELL_WIG_TYPE = (
     'coverage', 'signal', 'difference', 'signal_sd', 'dwell')
 SIG_SLOT, SD_SLOT, DWELL_SLOT = 'norm_mean', 'norm_stdev', 'length'
-# these read a statistics file: not part of this module
-STATS_WIG_TYPES = ('fraction', 'dampened_fraction', 'statistic', 'valid_coverage')
+# these read a statistics file (write_frac_wigs)
+FRAC_WIG_TYPE, DFRAC_WIG_TYPE, STAT_WIG_TYPE, VCOV_WIG_TYPE = (
+    'fraction', 'dampened_fraction', 'statistic', 'valid_coverage')
+STATS_WIG_TYPES = (FRAC_WIG_TYPE, DFRAC_WIG_TYPE, STAT_WIG_TYPE, VCOV_WIG_TYPE)
+FRAC_WIG_NAME, DFRAC_WIG_NAME, STAT_WIG_NAME, VCOV_WIG_NAME = (
+    'fraction_modified_reads', 'dampened_fraction_modified_reads', 'statistic', 'valid_coverage')
 
 
 def open_browser_files(wig_base, group_text, type_name, out_type=WIG_TYPE):
@@ -37,6 +41,44 @@ def open_browser_files(wig_base, group_text, type_name, out_type=WIG_TYPE):
 def _write_cs_data(wig_fp, chrm, cs_poss, cs_vals):
     wig_fp.write('variableStep chrom={} span=1\n'.format(chrm))
     wig_fp.write('\n'.join('{:d} {:.4f}'.format(p + 1, v) for p, v in zip(cs_poss.tolist(), cs_vals.tolist())) + '\n')
+
+
+def _write_cs_int_data(wig_fp, chrm, cs_poss, cs_vals):
+    wig_fp.write('variableStep chrom={} span=1\n'.format(chrm))
+    wig_fp.write('\n'.join('{:d} {:d}'.format(p + 1, v) for p, v in zip(cs_poss.tolist(), cs_vals.tolist())) + '\n')
+
+
+def write_frac_wigs(all_stats, wig_base, do_frac, do_damp, do_stats, do_vcov, fasta_fn=None, motif_descs=None):
+    """_text_output_commands.py:95-228: the fraction / dampened fraction / statistic / valid coverage wiggles of a
+    statistics container (tombo_stats.ModelStats / LevelStats), block after block in the container's own order,
+    one variableStep section per run of blocks of one (chrm, strand)."""
+    if fasta_fn is not None and motif_descs is not None:
+        raise NotImplementedError('motif filtering of the statistics wiggles needs the genome index: not built')
+    slots = [(FRAC_WIG_NAME, lambda b: 1 - b['frac'], _write_cs_data), (DFRAC_WIG_NAME, lambda b: 1 - b['damp_frac'],
+             _write_cs_data), (STAT_WIG_NAME, all_stats._stat_transform, _write_cs_data),
+             (VCOV_WIG_NAME, lambda b: b['valid_cov'], _write_cs_int_data)]
+    slots = [s + (open_browser_files(wig_base, '', s[0]),)
+             for s, do in zip(slots, (do_frac, do_damp, do_stats, do_vcov)) if do]
+
+    def write_cs_stats(chrm, strand, poss, vals):
+        poss = np.concatenate(poss)
+        for (_, _, write, fps), v in zip(slots, vals):
+            write(fps[0 if strand == '+' else 1], chrm, poss, np.concatenate(v))
+
+    curr_cs, curr_poss, curr_vals = None, [], [[] for _ in slots]
+    for chrm, strand, _, _, block_stats in all_stats:
+        if (chrm, strand) != curr_cs:
+            if len(curr_poss) > 0:
+                write_cs_stats(*curr_cs, curr_poss, curr_vals)
+            curr_cs, curr_poss, curr_vals = (chrm, strand), [], [[] for _ in slots]
+        curr_poss.append(block_stats['pos'])
+        for (_, value, _, _), v in zip(slots, curr_vals):
+            v.append(value(block_stats))
+    if len(curr_poss) > 0:
+        write_cs_stats(*curr_cs, curr_poss, curr_vals)
+    for _, _, _, fps in slots:
+        for fp in fps:
+            fp.close()
 
 
 def write_cov_wig(reads_index, out_base, group_text, engine=None):
@@ -91,17 +133,35 @@ def write_signal_and_diff_wigs(reads_index, ctrl_reads_index, chrm_sizes, wig_ba
         fp.close()
 
 
+def _write_stats_files(all_stats, wig_base, wig_types):
+    """the tail of write_all_browser_files (:369-386), the container given instead of a file name"""
+    if not all_stats.is_model_stats and any(t in wig_types for t in (FRAC_WIG_TYPE, DFRAC_WIG_TYPE, VCOV_WIG_TYPE)):
+        raise th.TomboError('Cannot output --file-type fraction, dampened_fraction or valid_coverage for level '
+                            'sample compare statistics.')
+    if all_stats.is_model_stats and STAT_WIG_TYPE in wig_types:
+        raise th.TomboError('Cannot output `--file-type statistics` for aggregated per-read statistics.')
+    write_frac_wigs(all_stats, wig_base, FRAC_WIG_TYPE in wig_types, DFRAC_WIG_TYPE in wig_types,
+                    STAT_WIG_TYPE in wig_types, VCOV_WIG_TYPE in wig_types)
+
+
 def write_all_browser_files(reads_index, ctrl_reads_index, wig_base, wig_types, slots=None, ctrl_slots=None,
-                            engine=None):
-    """The files of `tombo text_output browser_files --file-types ...` for coverage, signal, signal_sd, dwell and
-    difference (write_all_browser_files, _text_output_commands.py:322-388; the order of the calls is the
-    reference's).  With a control index the sample's files carry `sample` in their names, the control's `control`."""
+                            engine=None, all_stats=None):
+    """The files of `tombo text_output browser_files --file-types ...` (write_all_browser_files,
+    _text_output_commands.py:322-388; the order of the calls is the reference's).  With a control index the sample's
+    files carry `sample` in their names, the control's `control`.  all_stats: an open statistics container
+    (tombo_stats.TomboStats(...)), which fraction, dampened_fraction, valid_coverage (ModelStats) and statistic
+    (LevelStats) are read from; without it these four types are refused.  reads_index may be None when only those
+    are asked for."""
     wig_types = list(wig_types)
     for t in wig_types:
-        if t in STATS_WIG_TYPES:
+        if t in STATS_WIG_TYPES and all_stats is None:
             raise NotImplementedError('file type %r reads a statistics file: not written by this module' % t)
-        if t not in (COV_WIG_TYPE, SIG_WIG_TYPE, DIFF_WIG_TYPE, SD_WIG_TYPE, DWELL_WIG_TYPE):
+        if t not in (COV_WIG_TYPE, SIG_WIG_TYPE, DIFF_WIG_TYPE, SD_WIG_TYPE, DWELL_WIG_TYPE) + STATS_WIG_TYPES:
             raise ValueError('unknown file type %r' % (t,))
+    if reads_index is None:
+        if any(t not in STATS_WIG_TYPES for t in wig_types):
+            raise ValueError('file types other than the statistics types need reads')
+        return _write_stats_files(all_stats, wig_base, wig_types)
     eng = th._tracks_engine(engine)
     slots, ctrl_slots = slots or {}, ctrl_slots or {}
     sig = dict(slots=slots.get(SIG_SLOT), ctrl_slots=ctrl_slots.get(SIG_SLOT), engine=eng)
@@ -128,3 +188,5 @@ def write_all_browser_files(reads_index, ctrl_reads_index, wig_base, wig_types, 
         if wig_type in wig_types:
             write_slot_mean_wig(reads_index, chrm_sizes, wig_base, group_name, wig_type, slot,
                                 slots=slots.get(slot), engine=eng)
+    if any(t in STATS_WIG_TYPES for t in wig_types):
+        _write_stats_files(all_stats, wig_base, wig_types)

@@ -980,11 +980,14 @@ def calc_damp_fraction(cov_damp_counts, fracs, valid_cov):
     return (np.round(fracs * valid_cov) + unmod) / (valid_cov + total)
 
 
-def region_stats_block(reg_stats, cov_damp_counts):
+def region_stats_block(reg_stats, cov_damp_counts, damp_frac=None):
     """the record array ModelStats._write_stat_block builds from a regionStats (:2752-2764): rows
     with a NaN dampened fraction dropped; control_cov is reg_stats.ctrl_cov zipped against the
-    per-site arrays, i.e. truncated to their length"""
-    damp = calc_damp_fraction(cov_damp_counts, reg_stats.reg_frac_standard_base, reg_stats.valid_cov)
+    per-site arrays, i.e. truncated to their length.  damp_frac: the dampened fractions where the
+    device has computed them already, else calc_damp_fraction"""
+    with np.errstate(invalid='ignore'):
+        damp = calc_damp_fraction(cov_damp_counts, reg_stats.reg_frac_standard_base, reg_stats.valid_cov) \
+            if damp_frac is None else np.asarray(damp_frac)
     n = min(damp.shape[0], len(reg_stats.ctrl_cov))
     keep = np.flatnonzero(~np.isnan(damp[:n]))
     block = np.empty(keep.shape[0], dtype=[('damp_frac', 'f8'), ('frac', 'f8'), ('pos', 'u4'),
@@ -996,6 +999,478 @@ def region_stats_block(reg_stats, cov_damp_counts):
     block['control_cov'] = np.asarray(reg_stats.ctrl_cov[:n], dtype=np.int64)[keep]
     block['valid_cov'] = np.asarray(reg_stats.valid_cov)[keep]
     return block
+
+
+# ---------------------------------------------------------------------------------------------
+# Statistics files: ModelStats (:2554-3061), LevelStats (:3063-3224), TomboStats (:3226-3237),
+# PerReadStats (:3239-3565) and aggregate_per_read_stats (:4664-4777).  The constructor
+# signatures, attribute names, HDF5 layout and error strings are the reference's.  The first
+# argument is a file name (opened with h5py, which must then be installed) or any object with the
+# h5py group interface (`attrs`, `create_group`, `create_dataset`, `items`, `__getitem__`,
+# `close`, `flush`), as `tombo_helper.write_new_fast5_group` takes one.  Differences, all stated
+# in DESIGN.md section 3g: the most significant sites are sorted once at `close` (same array,
+# see `_close_write`); `get_reg_stats` concatenates overlapping blocks; where the reference
+# prints a message and exits the process a th.TomboError with that message is raised, where it
+# prints a warning `warnings.warn` is called.
+STAT_BLOCKS_H5_NAME = 'Statistic_Blocks'
+MOST_SIGNIF_H5_NAME = 'Most_Significant_Stats'
+COV_DAMP_COUNTS_H5_NAME = 'Cov_Damp_Counts'
+COV_THRESH_H5_NAME = 'Cov_Threshold'
+MOST_SIGNIF_NUM_BATCHES_DEFAULT = 10
+PER_READ_STATS = (SAMP_COMP_TXT, DE_NOVO_TXT, ALT_MODEL_TXT)
+LEVEL_STATS_TXTS = (KS_TEST_TXT, U_TEST_TXT, T_TEST_TXT, KS_STAT_TEST_TXT, U_STAT_TEST_TXT, T_STAT_TEST_TXT)
+_MODEL_BLOCK_DTYPE = [('damp_frac', 'f8'), ('frac', 'f8'), ('pos', 'u4'), ('cov', 'u4'), ('control_cov', 'u4'),
+                      ('valid_cov', 'u4')]
+_LEVEL_BLOCK_DTYPE = [('stat', 'f8'), ('pos', 'u4'), ('cov', 'u4'), ('control_cov', 'u4')]
+_SITE_ID_DTYPE = [('chrm', 'u4'), ('strand', 'S1')]
+_INVALID_STATS_MSG = ('Invalid statistics file provided. Try running tombo/scripts/convert_stats.py if this '
+                      'stats file was created before Tombo v1.3.1')
+_NO_SITES_MSG = 'No genomic positions contain --minimum-test-reads.'
+
+
+def _open_store(store, mode):
+    """a file name -> h5py.File (ImportError without h5py); anything else is used as the group it is"""
+    if isinstance(store, (str, bytes, os.PathLike)):
+        import h5py
+        return h5py.File(store, mode)
+    return store
+
+
+def _text(v):
+    return v.decode() if isinstance(v, bytes) else v
+
+
+def _blocks_index(blocks):
+    """{(chrm, strand): {start: block name}} in stored order, number of blocks"""
+    index, n = {}, 0
+    for name, block in blocks.items():
+        cs = (_text(block.attrs.get('chrm')), _text(block.attrs.get('strand')))
+        index.setdefault(cs, {})[block.attrs.get('start')] = name
+        n += 1
+    return index, n
+
+
+def _neg_log10(self, pos_stat):
+    with np.errstate(divide='ignore'):
+        return -np.log10(pos_stat[self._stat_slot])
+
+
+class _BlockStore(object):
+    """what the three containers share: the block iterator and get_reg_stats"""
+    _sort_keys = False
+
+    def _new_block(self, chrm, strand, start):
+        block = self._blocks.create_group('Block_' + str(self.curr_block_num))
+        self.curr_block_num += 1
+        block.attrs['chrm'], block.attrs['strand'], block.attrs['start'] = chrm, strand, start
+        return block
+
+    def __iter__(self):
+        """(chrm, strand, start, end, block_stats) of every block: the blocks of the first (chrm, strand) in
+        stored order, those of the later ones sorted by start (:2984-3014, :3505-3530)"""
+        self.iter_all_cs = iter(sorted(self.blocks_index) if self._sort_keys else list(self.blocks_index))
+        try:
+            self.iter_curr_cs = next(self.iter_all_cs)
+        except StopIteration:   # (a file without blocks: nothing to iterate, for PerReadStats too)
+            self.iter_curr_cs, self.iter_curr_cs_blocks = None, iter([])
+        else:
+            self.iter_curr_cs_blocks = iter(self.blocks_index[self.iter_curr_cs].items())
+        return self
+
+    def __next__(self):
+        try:
+            next_start, next_block_name = next(self.iter_curr_cs_blocks)
+        except StopIteration:
+            self.iter_curr_cs = next(self.iter_all_cs)   # (the second StopIteration ends the iteration)
+            self.iter_curr_cs_blocks = iter(sorted(self.blocks_index[self.iter_curr_cs].items()))
+            next_start, next_block_name = next(self.iter_curr_cs_blocks)
+        chrm, strand = self.iter_curr_cs
+        return (chrm, strand, next_start, next_start + self.region_size,
+                self._blocks[next_block_name]['block_stats'][:])
+
+    next = __next__
+
+    def get_reg_stats(self, chrm, strand, start, end):
+        """the records with start <= pos < end, blocks in order of their start; None without an overlapping
+        block.  Several overlapping blocks are concatenated (the reference's np.vstack needs them to be of one
+        length)."""
+        if (chrm, strand) not in self.blocks_index:
+            return
+        reg_stats = []
+        for reg_start, block_name in sorted(self.blocks_index[(chrm, strand)].items()):
+            if reg_start < end and reg_start + self.region_size > start:
+                block = self._blocks[block_name]['block_stats'][:]
+                reg_stats.append(block[(block['pos'] >= start) & (block['pos'] < end)])
+        if len(reg_stats) == 0:
+            return
+        return reg_stats[0] if len(reg_stats) == 1 else np.concatenate(reg_stats)
+
+
+class ModelStats(_BlockStore):
+    """A standard (per genomic base) statistics file of the model-based tests: all of stat_type, region_size,
+    cov_damp_counts, cov_thresh and num_most_signif given opens a fresh file for writing, else `stats_fn` is
+    parsed."""
+    _sort_keys = True
+    _block_dtype = _MODEL_BLOCK_DTYPE
+    _blocks = property(lambda self: self.stat_blocks)
+
+    def _parse_stats(self):
+        self.stat_type = _text(self._fp.attrs.get('stat_type'))
+        self.region_size = self._fp.attrs.get('block_size')
+        self.stat_blocks = self._fp[STAT_BLOCKS_H5_NAME]
+        self.blocks_index, self.num_blocks = _blocks_index(self.stat_blocks)
+        self.cov_thresh = self._fp.attrs.get(COV_THRESH_H5_NAME)
+        most_signif_grp = self._fp[MOST_SIGNIF_H5_NAME]
+        self.most_signif_stats = most_signif_grp[MOST_SIGNIF_H5_NAME][:]
+        self.most_signif_chrm_map = dict((v, k) for k, v in most_signif_grp['chrm_ids'].attrs.items())
+        try:   # (LevelStats has no damp counts)
+            self.cov_damp_counts = dict(self._fp[COV_DAMP_COUNTS_H5_NAME].attrs.items())
+        except Exception:
+            self.cov_damp_counts = None
+
+    def _create_new_stats_file(self):
+        self._fp = _open_store(self.stats_fn, 'w')
+        self._fp.attrs['stat_type'] = self.stat_type
+        self._fp.attrs['block_size'] = self.region_size
+        self.stat_blocks = self._fp.create_group(STAT_BLOCKS_H5_NAME)
+        self._fp.attrs[COV_THRESH_H5_NAME] = self.cov_thresh
+        if self.cov_damp_counts is not None:
+            self.cov_damp_counts_grp = self._fp.create_group(COV_DAMP_COUNTS_H5_NAME)
+            self.cov_damp_counts_grp.attrs['unmod'] = self.cov_damp_counts['unmod']
+            self.cov_damp_counts_grp.attrs['mod'] = self.cov_damp_counts['mod']
+        self.most_signif_sites = self._fp.create_group(MOST_SIGNIF_H5_NAME)
+        self.queued_stat_batches = []
+        self.curr_chrm_id = 0
+        self.chrm_names = {}
+        self.chrm_id_grp = self.most_signif_sites.create_group('chrm_ids')
+        self.is_empty = True
+
+    def _open(self, stats_fn, write_args, stat_type, region_size, cov_thresh, num_most_signif,
+              most_signif_num_batches):
+        self.stats_fn = stats_fn
+        self.open_for_writing = not any(arg is None for arg in write_args)
+        if self.open_for_writing:
+            self.stat_type, self.region_size, self.curr_block_num = stat_type, region_size, 0
+            self.cov_thresh, self.num_most_signif = cov_thresh, num_most_signif
+            self.most_signif_num_batches = most_signif_num_batches
+            self._create_new_stats_file()
+        else:
+            if isinstance(stats_fn, (str, bytes, os.PathLike)) and not os.path.isfile(stats_fn):
+                raise th.TomboError('Statistics file not provided or provided file does not exist.')
+            self._fp = _open_store(stats_fn, 'r')
+            try:
+                self._parse_stats()
+            except Exception:
+                raise th.TomboError(_INVALID_STATS_MSG)
+
+    def __init__(self, stats_fn, stat_type=None, region_size=None, cov_damp_counts=None, cov_thresh=None,
+                 num_most_signif=None, most_signif_num_batches=MOST_SIGNIF_NUM_BATCHES_DEFAULT):
+        if cov_damp_counts is not None:
+            self.cov_damp_counts = dict(zip(('unmod', 'mod'), cov_damp_counts))
+        self._open(stats_fn, (stat_type, region_size, cov_damp_counts, cov_thresh, num_most_signif), stat_type,
+                   region_size, cov_thresh, num_most_signif, most_signif_num_batches)
+        if self.stat_type not in PER_READ_STATS:
+            if self.stat_type in LEVEL_STATS_TXTS:
+                raise th.TomboError('This appears to be a group-comparison stats file. Open with '
+                                    'tombo_stats.LevelStats.')
+            raise th.TomboError('This file is not a valid ModelStats file. `stat_type` listed as "' +
+                                str(self.stat_type) + '".')
+        self.is_model_stats = True
+        self._stat_slot = 'damp_frac'
+        self._stat_text = 'Est. Frac. Alternate: {0:.2g}'
+        self._stat_transform = lambda pos_stat: 1 - pos_stat[self._stat_slot]
+
+    def _add_block(self, chrm, strand, start, block):
+        try:
+            block_data = self._new_block(chrm, strand, start)
+        except Exception:
+            warnings.warn('Statistics file not opened for writing.')
+            return
+        block_data.create_dataset('block_stats', data=block, compression='gzip')
+        if chrm not in self.chrm_names:
+            self.chrm_names[chrm] = self.curr_chrm_id
+            self.curr_chrm_id += 1
+        sites = np.empty(block.shape[0], dtype=self._block_dtype + _SITE_ID_DTYPE)
+        for name in block.dtype.names:
+            sites[name] = block[name]
+        sites['chrm'], sites['strand'] = self.chrm_names[chrm], strand
+        self.queued_stat_batches.append(sites)
+        self.is_empty = False
+
+    def _write_stat_block(self, reg_stats, damp_frac=None):
+        """one th.regionStats as a block (:2737-2773).  damp_frac: the dampened fractions under THIS file's
+        pseudo-counts where the device has computed them already (aggregate_per_read_stats), else
+        calc_damp_fraction"""
+        self._add_block(reg_stats.chrm, reg_stats.strand, reg_stats.start,
+                        region_stats_block(reg_stats, self.cov_damp_counts, damp_frac))
+
+    def _close_write(self):
+        # The reference keeps a running array of num_most_signif rows (NaN at first), merges the queued blocks
+        # into it every most_signif_num_batches blocks with `sort(order=<statistic>)` and cuts it again, then trims
+        # it at its first NaN.  numpy breaks ties of the named field by the remaining fields in dtype order, so that
+        # sort is a total order on the records (equal records are equal bytes) and a row that is cut has
+        # num_most_signif rows in front of it for good: the result is the sort of all sites, cut and trimmed --
+        # computed here once, whatever most_signif_num_batches is.
+        sites = np.concatenate([np.empty(0, dtype=self._block_dtype + _SITE_ID_DTYPE)] + self.queued_stat_batches)
+        sites.sort(kind='mergesort', order=self._stat_slot)
+        sites = sites[:self.num_most_signif]
+        nans = np.flatnonzero(np.isnan(sites[self._stat_slot]))
+        self.running_most_signif_sites = sites[:nans[0]] if nans.shape[0] else sites
+        self.queued_stat_batches = []
+        self.most_signif_sites.create_dataset(MOST_SIGNIF_H5_NAME, data=self.running_most_signif_sites,
+                                              compression='gzip')
+        for chrm_name, chrm_id in self.chrm_names.items():
+            self.chrm_id_grp.attrs[chrm_name] = chrm_id
+
+    def close(self):
+        """writes the most significant sites if open for writing, then closes the file"""
+        if self.open_for_writing:
+            self._close_write()
+        self._fp.close()
+
+    def _get_chrm_name(self, pos_stat):
+        return self.most_signif_chrm_map[pos_stat['chrm']]
+
+    def iter_most_signif_sites(self):
+        """(chrm, strand, pos, transformed statistic) of the stored most significant sites.  (:2850-2859 applies
+        the transform to the statistic's value instead of the record, which raises there; the record is passed)"""
+        for pos_stat in self.most_signif_stats:
+            yield (self._get_chrm_name(pos_stat), pos_stat['strand'].decode(), pos_stat['pos'],
+                   self._stat_transform(pos_stat))
+
+    def get_most_signif_regions(self, num_bases, num_regions, unique_pos=True, prepend_loc_to_text=False):
+        """:2861-2913 -> [(chrm, start, end, strand, reg_id, reg_text), ...] (the fields the reference gives its
+        intervalData)"""
+        selected_regs, used_intervals = [], {}
+        for i, pos_stat in enumerate(self.most_signif_stats):
+            pos = int(pos_stat['pos'])
+            int_start = max(0, pos - int(num_bases / 2.0))
+            chrm, strand = self._get_chrm_name(pos_stat), pos_stat['strand'].decode()
+            used = used_intervals.setdefault((chrm, strand), set())
+            if not unique_pos or pos not in used:
+                used.update(range(int_start, int_start + num_bases))
+                int_text = self._stat_text.format(self._stat_transform(pos_stat))
+                if prepend_loc_to_text:
+                    int_text = '{0}:{1:d}:{2}'.format(chrm, pos + 1, strand) + ' ' + int_text
+                selected_regs.append((chrm, int_start, int_start + num_bases, strand, '{:03d}'.format(i), int_text))
+                if len(selected_regs) >= num_regions:
+                    break
+        if len(selected_regs) == 0:
+            raise th.TomboError('No locations identified. Most likely an empty statistics file.')
+        if len(selected_regs) < num_regions:
+            warnings.warn('Fewer unique significant locations more than [--num-bases]/2 apart were identified. '
+                          'Continuing with ' + str(len(selected_regs)) + ' unique locations. Must raise '
+                          '--num-most-significant-stored in order to see more most significant stats.')
+        return selected_regs
+
+    def get_pos_stat(self, chrm, strand, pos, missing_value=None):
+        try:
+            pos_block_start = np.floor_divide(pos, self.region_size) * self.region_size
+            block_data = self.stat_blocks[self.blocks_index[(chrm, strand)][pos_block_start]]['block_stats'][:]
+            pos_index = np.where(block_data['pos'] == pos)[0]
+            if len(pos_index) != 1:
+                raise KeyError
+            return self._stat_transform(block_data[pos_index[0]])
+        except KeyError:
+            return missing_value
+
+
+class LevelStats(ModelStats):
+    """A statistics file of the level sample comparison (ks / u / t tests)"""
+    _block_dtype = _LEVEL_BLOCK_DTYPE
+    cov_damp_counts = None
+
+    def __init__(self, stats_fn, stat_type=None, region_size=None, cov_thresh=None, num_most_signif=None,
+                 most_signif_num_batches=MOST_SIGNIF_NUM_BATCHES_DEFAULT):
+        self._open(stats_fn, (stat_type, region_size, cov_thresh, num_most_signif), stat_type, region_size,
+                   cov_thresh, num_most_signif, most_signif_num_batches)
+        if self.stat_type not in LEVEL_STATS_TXTS:
+            if self.stat_type in PER_READ_STATS:
+                raise th.TomboError('This appears to be a model-based comparison stats file. Open with '
+                                    'tombo_stats.ModelStats.')
+            raise th.TomboError('This file is not a valid LevelStats file. `stat_type` listed as "' +
+                                str(self.stat_type) + '".')
+        self.is_model_stats = False
+        self._stat_slot = 'stat'
+        if self.stat_type in (KS_TEST_TXT, U_TEST_TXT, T_TEST_TXT):
+            self._stat_text = '-log10(p-value): {0:.2g}'
+            self._stat_transform = lambda pos_stat: _neg_log10(self, pos_stat)
+        elif self.stat_type == KS_STAT_TEST_TXT:
+            self._stat_text = 'D Statistic: {0:.2g}'
+            self._stat_transform = lambda pos_stat: 1 - pos_stat[self._stat_slot]
+        else:
+            self._stat_text = ('Common Language Marginal Effect: {0:.2g}' if self.stat_type == U_STAT_TEST_TXT
+                               else "Cohen's D: {0:.2g}")
+            self._stat_transform = lambda pos_stat: -pos_stat[self._stat_slot]
+
+    def _write_stat_block(self, grp_stats):
+        """one th.groupStats as a block (:3194-3224): rows with a NaN statistic dropped"""
+        rows = [r for r in zip(grp_stats.reg_stats, grp_stats.reg_poss, grp_stats.reg_cov, grp_stats.ctrl_cov)
+                if not np.isnan(r[0])]
+        self._add_block(grp_stats.chrm, grp_stats.strand, grp_stats.start, np.array(rows, dtype=_LEVEL_BLOCK_DTYPE))
+
+
+def TomboStats(stat_fn):
+    """ModelStats or LevelStats, whichever the file is (read only)"""
+    try:
+        return ModelStats(stat_fn)
+    except th.TomboError:
+        return LevelStats(stat_fn)
+
+
+class PerReadStats(_BlockStore):
+    """A per-read statistics file: stat_type and region_size given opens a fresh file for writing, else
+    `per_read_stats_fn` is parsed.  A block holds (pos, stat, read_id) records (`_native.PER_READ_DTYPE`)."""
+    _blocks = property(lambda self: self.per_read_blocks)
+
+    def __init__(self, per_read_stats_fn, stat_type=None, region_size=None):
+        self.per_read_stats_fn = per_read_stats_fn
+        if stat_type is None or region_size is None:
+            self._fp = _open_store(per_read_stats_fn, 'r')
+            try:
+                self.stat_type = _text(self._fp.attrs.get('stat_type'))
+                self.region_size = self._fp.attrs.get('block_size')
+                self.per_read_blocks = self._fp[STAT_BLOCKS_H5_NAME]
+                self.blocks_index, self.num_blocks = _blocks_index(self.per_read_blocks)
+            except Exception:
+                raise th.TomboError('Non-existent or invalid per-read statistics file provided.')
+        else:
+            self.stat_type, self.region_size = stat_type, region_size
+            self._fp = _open_store(per_read_stats_fn, 'w')
+            self.curr_block_num = 0
+            self._fp.attrs['stat_type'] = self.stat_type
+            self._fp.attrs['block_size'] = self.region_size
+            self.per_read_blocks = self._fp.create_group(STAT_BLOCKS_H5_NAME)
+        self.are_pvals = self.stat_type != ALT_MODEL_TXT
+        self._stat_slot = 'stat'
+        self._stat_text = '-log10(p-value): {0:.2g}'
+        self._stat_transform = lambda pos_stat: _neg_log10(self, pos_stat)
+
+    def _write_per_read_block(self, per_read_block, read_id_lookup, chrm, strand, start):
+        """:3335-3366: the records, and the lookup from their read_id numbers back to the ids as the two datasets
+        read_ids (variable-length strings) and read_id_vals"""
+        try:
+            block_data = self._new_block(chrm, strand, start)
+        except Exception:
+            warnings.warn('Per-read statistics file not opened for writing.')
+            return
+        block_data.create_dataset('block_stats', data=per_read_block, compression='gzip')
+        try:
+            import h5py
+            dt = h5py.special_dtype(vlen=str)
+        except ImportError:   # (a stand-in group: objects)
+            dt = object
+        read_ids = np.array(list(read_id_lookup.keys()), dtype=dt)
+        read_ids_ds = block_data.create_dataset('read_ids', read_ids.shape, dtype=dt, compression='gzip')
+        read_ids_ds[...] = read_ids
+        block_data.create_dataset('read_id_vals', data=np.array(list(read_id_lookup.values())), compression='gzip')
+        self._fp.flush()
+
+    def get_region_per_read_stats(self, interval_data):
+        """:3368-3434 without the num_reads sampling: (pos, stat, read id string) records of the interval
+        (`chrm`, `strand`, `start`, `end` attributes), None for an unknown (chrm, strand) or no block"""
+        try:
+            cs_blocks = self.blocks_index[(interval_data.chrm, interval_data.strand)]
+        except KeyError:
+            return
+        int_block_stats = []
+        for block_start, block_name in cs_blocks.items():
+            if interval_data.end < block_start or interval_data.start > block_start + self.region_size:
+                continue
+            block = self.per_read_blocks[block_name]
+            block_stats = block['block_stats'][:]
+            lookup = dict((val, _text(rid)) for rid, val in zip(block['read_ids'][()], block['read_id_vals'][()]))
+            rows = np.empty(block_stats.shape[0], dtype=[('pos', 'u4'), ('stat', 'f8'), ('read_id', object)])
+            rows['pos'], rows['stat'] = block_stats['pos'], block_stats[self._stat_slot]
+            rows['read_id'] = [lookup[r_id] for r_id in block_stats['read_id']]
+            int_block_stats.append(rows)
+        if len(int_block_stats) == 0:
+            return
+        stats = np.concatenate(int_block_stats)
+        return stats[(stats['pos'] >= interval_data.start) & (stats['pos'] < interval_data.end)]
+
+    def close(self):
+        self._fp.close()
+
+
+# aggregate_per_read_stats (:4699-4777): the reference sorts every stored block by position, splits it per
+# site and thresholds the pieces in worker processes.  Here consecutive blocks go to the device as they are
+# stored, one `Engine.site_aggregate` call (kernel k_site_rec, csrc/k_site.h) per group of blocks.
+_AGG_BYTES_PER_RECORD = 16      # a stored record, uploaded as it is
+_AGG_BYTES_PER_POSITION = 60    # three i32 counters, frac / pos / cov / valid_cov / damp_frac, per block position
+_AGG_MEM_FRACTION = 0.5         # of the device's free memory, for one call
+
+
+def _default_max_records(engine):
+    """records per site_aggregate call that fit into half of the engine's free memory (`_agg_groups` counts a
+    block as at least one record per position); a stand-in engine without `device_mem`: 2^24"""
+    if not hasattr(engine, 'device_mem'):
+        return 1 << 24
+    free = engine.device_mem()[0]
+    return max(1, int(free * _AGG_MEM_FRACTION) // (_AGG_BYTES_PER_RECORD + _AGG_BYTES_PER_POSITION))
+
+
+def _agg_groups(pr_stats, max_records, max_positions=2 ** 31 - 1):
+    """consecutive blocks of the per-read file, in its own order, grouped into calls of at most max_records
+    records (a larger block stands alone) and fewer than 2^31 positions.  The device holds per-position arrays
+    too, so a block counts as at least region_size records."""
+    group, n_rec = [], 0
+    for block in pr_stats:
+        n = max(block[4].shape[0], int(pr_stats.region_size))
+        if group and (n_rec + n > max_records or (len(group) + 1) * pr_stats.region_size > max_positions):
+            yield group
+            group, n_rec = [], 0
+        group.append(block)
+        n_rec += n
+    if group:
+        yield group
+
+
+def aggregate_per_read_stats(pr_stats, single_read_thresh, lower_thresh, stats, cov_damp_counts, min_test_reads,
+                             num_most_signif, engine=None, max_records=None):
+    """:4736-4777: the per-site statistics of a per-read statistics file under new thresholds, written to
+    `stats` (pr_stats / stats: file names or group objects).  Every stored block becomes one block of the new
+    file, control coverage 0 (_agg_stats_worker)."""
+    pr_stats = PerReadStats(pr_stats)
+    eng = _engine(engine)
+    if max_records is None:
+        max_records = _default_max_records(eng)
+    cd = cov_damp_counts
+    all_stats = ModelStats(stats, stat_type=pr_stats.stat_type, region_size=pr_stats.region_size,
+                           cov_damp_counts=(cd['unmod'], cd['mod']) if isinstance(cd, dict) else cd,
+                           cov_thresh=min_test_reads, num_most_signif=num_most_signif)
+    damp = _damp_pair(cov_damp_counts)
+    for group in _agg_groups(pr_stats, int(max_records)):
+        starts = np.array([b[2] for b in group], dtype=np.int64)
+        ends = np.array([b[3] for b in group], dtype=np.int64)
+        rec_off = _csr_offsets([b[4].shape[0] for b in group])
+        records = np.concatenate([np.asarray(b[4], dtype=_native.PER_READ_DTYPE) for b in group])
+        res = eng.site_aggregate(starts, ends, rec_off, records, single_read_thresh, lower_thresh,
+                                 pr_stats.stat_type == ALT_MODEL_TXT, damp)
+        for t, (chrm, strand, start, _, _) in enumerate(group):
+            a = int(res.pos_off[t])
+            b = a + int(res.counts[t])
+            rs = th.regionStats(res.frac[a:b], res.poss[a:b], chrm, strand, start, res.cov[a:b], [0] * (b - a),
+                                res.valid[a:b])
+            all_stats._write_stat_block(rs, res.damp[a:b])
+    pr_stats.close()
+    all_stats.close()
+    if all_stats.is_empty:
+        raise th.TomboError(_NO_SITES_MSG)
+
+
+def write_stats_from_regions(results, per_read, stats, pr_stats=None):
+    """Stores what `compute_reg_stats_batch(..., return_per_read=True)` returned: every regionStats of
+    `results` (regions that failed are skipped) through `stats._write_stat_block`, every per-read block of
+    `per_read` through `pr_stats._write_per_read_block` (stats: an open ModelStats; pr_stats: an open
+    PerReadStats or None).  The containers stay open."""
+    for reg_res, reg_blocks in zip(results, per_read):
+        if pr_stats is not None:
+            for _, block in reg_blocks:
+                pr_stats._write_per_read_block(*block)
+        if not isinstance(reg_res, Exception):
+            for _, reg_stats in reg_res:
+                stats._write_stat_block(reg_stats)
 
 
 # ---------------------------------------------------------------------------------------------
