@@ -570,6 +570,53 @@ int tba_site_aggregate(tba_engine *e, int64_t n_blocks, const int64_t *blk_start
     int64_t *out_pos, int64_t *out_cov, int64_t *out_valid_cov, double *out_damp_frac,
     int64_t *out_counts, int64_t *out_n_stats, double *out_kernel_ms);
 
+/* ---- ROC / precision-recall from stored statistics (tombo_stats.py:2377-2535) -----------------
+ * Records are (rec_pos, rec_stat) pairs, CSR by block: block t owns rec_off[t] .. rec_off[t + 1].
+ *
+ * tba_roc_motif_labels: compute_motif_stats (mode 0) / compute_ctrl_motif_stats (mode 1).  Block t
+ * lies on the minus strand when blk_minus[t] != 0 and carries the base codes seq[seq_off[t] ..
+ * seq_off[t + 1]) (0..3 = ACGT, anything else: not a base) of the genome from coordinate
+ * blk_seq_start[t] on; a minus-strand block is read as the complement, backwards.  Motif k is
+ * motifs[3k .. 3k + 2] = (length, 1-based modified position, base code of the modified position or
+ * a value above 3 for a letter that is not a base) and `length` 4-bit base sets (bit c: code c
+ * allowed) in motif_sets, all motifs concatenated.  A motif matches at a record when all of its
+ * positions, the modified one on the record, lie inside the block's sequence and hold an allowed
+ * base.  mode 0: a (record, motif) pair is kept when the base under the record, in strand
+ * orientation, is the motif's modified base; its label is whether the motif matches.  mode 1: a
+ * pair is kept when the motif matches; its label is `label`.
+ * Outputs: the kept pairs of motif 0 in record order, then those of motif 1, ...: out_stats,
+ * out_has_mod (0 / 1) and, unless NULL, out_index (the record) -- capacity n_motifs * n_records
+ * each; out_counts[n_motifs].  out_kernel_ms (may be NULL): device time of the kernels.
+ *
+ * tba_roc_loc_labels: compute_ground_truth_stats.  Block t owns mod_locs[blk_loc[4t] ..
+ * blk_loc[4t + 1]) and unmod_locs[blk_loc[4t + 2] .. blk_loc[4t + 3]), each slice ascending.  A
+ * record is kept when its position is in either slice; its label is whether it is in the first.
+ * Outputs as above with one motif (capacity n_records).
+ *
+ * tba_roc_rank_counts: out_tp_at[j] = entries with has_mod != 0 among the ranks[j] + 1 first
+ * entries in ascending (statistic, has_mod) order (-0.0 equals 0.0; of equal statistics the
+ * unmodified come first); out_tp_total: all of them; out_n_nan: NaN statistics (the counts mean
+ * nothing when there is one).  n < 2^31; ranks non-decreasing inside [0, n).  out_kernel_ms (may be
+ * NULL): two values, the device time of the keys and the sort, and of the label scan and the gather.
+ * tba_roc_sort_tile: entries per workgroup and pass of that call's sort.
+ *
+ * TBA_E_ARG: NULL pointers, offsets that do not start at 0 or decrease, 2^31 records or more, no
+ * motif or more than 64, a motif with length outside [1, 1024] or its modified position outside
+ * it, a location slice outside its list, bad ranks.  Nothing is launched for any of these. */
+int tba_roc_motif_labels(tba_engine *e, int64_t n_blocks, const uint8_t *blk_minus,
+    const int64_t *blk_seq_start, const int64_t *seq_off, const uint8_t *seq, const int64_t *rec_off,
+    const int64_t *rec_pos, const double *rec_stat, int64_t n_motifs, const int32_t *motifs,
+    const uint8_t *motif_sets, int mode, int label, double *out_stats, uint8_t *out_has_mod,
+    int64_t *out_index, int64_t *out_counts, double *out_kernel_ms);
+int tba_roc_loc_labels(tba_engine *e, int64_t n_blocks, const int64_t *blk_loc, const int64_t *mod_locs,
+    int64_t n_mod, const int64_t *unmod_locs, int64_t n_unmod, const int64_t *rec_off, const int64_t *rec_pos,
+    const double *rec_stat, double *out_stats, uint8_t *out_has_mod, int64_t *out_index, int64_t *out_count,
+    double *out_kernel_ms);
+int tba_roc_rank_counts(tba_engine *e, int64_t n, const double *stats, const uint8_t *has_mod,
+    int64_t n_ranks, const int64_t *ranks, int64_t *out_tp_at, int64_t *out_tp_total, int64_t *out_n_nan,
+    double *out_kernel_ms);
+int64_t tba_roc_sort_tile(void);
+
 /* ---- alternate-base model estimation (estimate_alt_model, tombo_stats.py:1747-2098) -----------
  * The base levels of a batch of reads gathered by k-mer (_parse_base_levels_worker, :1747-1776).
  * means / codes: read-centric levels and base codes (0..3 = ACGT, anything else: not a base) of

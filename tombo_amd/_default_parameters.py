@@ -69,3 +69,6 @@ KERNEL_DENSITY_RANGE = (-5, 5)
 ALT_EST_PCTL = 5
 NUM_DENS_POINTS = 500
 KERNEL_DENSITY_BW = 0.05
+
+# points along the ROC and precision-recall curves (_default_parameters.py:181)
+ROC_PLOT_POINTS = 1000

@@ -352,6 +352,86 @@ def _check_site_aggregate_args(blk_start, blk_end, rec_off, records):
     return bs, be, off, np.ascontiguousarray(rec)
 
 
+ROC_SORT_TILE = 4096   # ROC_SORT_TILE of csrc/k_roc.h (tba_roc_sort_tile): entries per workgroup and pass of the sort
+ROC_MAX_MOTIFS = 64
+
+
+def _check_roc_recs(rec_off, rec_pos, rec_stat, n_blocks):
+    off, pos, stat = np.asarray(rec_off), np.asarray(rec_pos), np.asarray(rec_stat)
+    if off.dtype != np.int64 or pos.dtype != np.int64 or stat.dtype != np.float64:
+        raise ValueError('rec_off and rec_pos must be int64, rec_stat float64')
+    if off.ndim != 1 or off.shape[0] != n_blocks + 1 or pos.ndim != 1 or stat.shape != pos.shape:
+        raise ValueError('rec_off must have one entry per block and one more, rec_pos and rec_stat one per record')
+    if off[0] != 0 or np.any(np.diff(off) < 0) or int(off[-1]) != pos.shape[0]:
+        raise ValueError('rec_off must start at 0, not decrease and end at len(rec_pos)')
+    if pos.shape[0] >= 2 ** 31:
+        raise ValueError('2^31 records or more in one call')
+    return tuple(np.ascontiguousarray(v) for v in (off, pos, stat))
+
+
+def _check_roc_motif_args(blk_minus, blk_seq_start, seq_off, seq_codes, rec_off, rec_pos, rec_stat, motifs):
+    """the argument checks of Engine.roc_motif_labels (shared with the tests' stand-in engine): dtypes are checked,
+    not converted -> contiguous (blk_minus, blk_seq_start, seq_off, seq_codes, rec_off, rec_pos, rec_stat, motif table
+    int32[n][3], concatenated sets uint8)"""
+    minus, ss, s_off, seq = (np.asarray(v) for v in (blk_minus, blk_seq_start, seq_off, seq_codes))
+    if minus.dtype != np.uint8 or seq.dtype != np.uint8 or ss.dtype != np.int64 or s_off.dtype != np.int64:
+        raise ValueError('blk_minus and seq_codes must be uint8, blk_seq_start and seq_off int64')
+    n_blk = minus.shape[0]
+    if minus.ndim != 1 or ss.shape != (n_blk,) or s_off.shape != (n_blk + 1,) or seq.ndim != 1:
+        raise ValueError('blk_minus, blk_seq_start must have one entry per block and seq_off one more')
+    if s_off[0] != 0 or np.any(np.diff(s_off) < 0) or int(s_off[-1]) != seq.shape[0]:
+        raise ValueError('seq_off must start at 0, not decrease and end at len(seq_codes)')
+    off, pos, stat = _check_roc_recs(rec_off, rec_pos, rec_stat, n_blk)
+    if not 1 <= len(motifs) <= ROC_MAX_MOTIFS:
+        raise ValueError('between 1 and %d motifs' % ROC_MAX_MOTIFS)
+    table, sets = np.empty((len(motifs), 3), dtype=np.int32), []
+    for k, (length, mod_pos, mod_base, base_sets) in enumerate(motifs):
+        base_sets = np.asarray(base_sets)
+        if base_sets.dtype != np.uint8 or base_sets.shape != (length,) or not 1 <= length <= 1024 or \
+                np.any(base_sets > 15):
+            raise ValueError('a motif needs one 4-bit base set (uint8) per position, 1 to 1024 positions')
+        if not 1 <= mod_pos <= length:
+            raise ValueError('mod_pos outside the motif')
+        table[k] = length, mod_pos, mod_base if 0 <= mod_base <= 3 else 255
+        sets.append(base_sets)
+    return tuple(np.ascontiguousarray(v) for v in (minus, ss, s_off, seq)) + (off, pos, stat, table,
+                                                                              np.ascontiguousarray(np.concatenate(sets)))
+
+
+def _check_roc_loc_args(blk_loc, mod_locs, unmod_locs, rec_off, rec_pos, rec_stat):
+    """-> contiguous (blk_loc int64[n][4], mod_locs, unmod_locs, rec_off, rec_pos, rec_stat) of roc_loc_labels"""
+    loc, mod, unmod = np.asarray(blk_loc), np.asarray(mod_locs), np.asarray(unmod_locs)
+    if loc.dtype != np.int64 or mod.dtype != np.int64 or unmod.dtype != np.int64:
+        raise ValueError('blk_loc, mod_locs and unmod_locs must be int64')
+    if loc.ndim != 2 or loc.shape[1] != 4 or mod.ndim != 1 or unmod.ndim != 1:
+        raise ValueError('blk_loc must be [n_blocks][4]: mod lo, hi, unmod lo, hi')
+    if np.any(loc < 0) or np.any(loc[:, 1] < loc[:, 0]) or np.any(loc[:, 3] < loc[:, 2]) or \
+            np.any(loc[:, 1] > mod.shape[0]) or np.any(loc[:, 3] > unmod.shape[0]):
+        raise ValueError('location slice outside its list')
+    for v, lo, hi in ((mod, loc[:, 0], loc[:, 1]), (unmod, loc[:, 2], loc[:, 3])):
+        drops = np.concatenate([[0], np.cumsum(np.diff(v) < 0)])   # drops[i]: descents before element i
+        last = v.shape[0] - 1
+        if v.shape[0] and np.any(drops[np.minimum(np.maximum(hi - 1, lo), last)] - drops[np.minimum(lo, last)] > 0):
+            raise ValueError('a location slice must be ascending')
+    off, pos, stat = _check_roc_recs(rec_off, rec_pos, rec_stat, loc.shape[0])
+    return (np.ascontiguousarray(loc), np.ascontiguousarray(mod), np.ascontiguousarray(unmod), off, pos, stat)
+
+
+def _check_roc_rank_args(stats, has_mod, ranks):
+    """-> contiguous (stats float64, has_mod as uint8, ranks int64) of roc_rank_counts"""
+    st, hm, rk = np.asarray(stats), np.asarray(has_mod), np.asarray(ranks)
+    if st.dtype != np.float64 or hm.dtype != np.bool_ or rk.dtype != np.int64:
+        raise ValueError('stats must be float64, has_mod bool, ranks int64')
+    if st.ndim != 1 or hm.shape != st.shape or rk.ndim != 1:
+        raise ValueError('stats and has_mod must be one-dimensional and of one length, ranks one-dimensional')
+    n = st.shape[0]
+    if n >= 2 ** 31:
+        raise ValueError('2^31 entries or more in one call')
+    if rk.shape[0] and (rk[0] < 0 or rk[-1] >= n or np.any(np.diff(rk) < 0)):
+        raise ValueError('ranks must be non-decreasing and inside [0, n)')
+    return np.ascontiguousarray(st), np.ascontiguousarray(hm).view(np.uint8), np.ascontiguousarray(rk)
+
+
 def _site_other_form(form):
     """typed nulls and zeros for the arguments of tba_site_fractions that the form in use leaves out"""
     nd, ni = C.cast(None, C.POINTER(f64)), C.cast(None, C.POINTER(i64))
@@ -965,6 +1045,68 @@ class Engine(object):
             C.byref(ms)), 'tba_site_aggregate')
         self.last_site_aggregate_kernel_ms = ms.value
         return SiteFractions(pos_off, frac, poss, cov, valid, damp, counts, n_stats, None)
+
+    # ---- ROC / precision-recall (csrc/k_roc.h) ----
+    def _roc_split(self, stats, labels, index, counts, return_index):
+        out, a = [], 0
+        for c in counts.tolist():
+            item = (stats[a:a + c].copy(), labels[a:a + c].astype(np.bool_))
+            out.append(item + (index[a:a + c].copy(),) if return_index else item)
+            a += c
+        return out
+
+    def roc_motif_labels(self, blk_minus, blk_seq_start, seq_off, seq_codes, rec_off, rec_pos, rec_stat, motifs,
+                         ctrl_label=None, return_index=False):
+        """tba_roc_motif_labels: records (rec_pos, rec_stat; CSR by block through rec_off) against motifs, each
+        (length, mod_pos, mod_base code, uint8 base sets).  Block t: minus strand flag, the genome coordinate of the
+        first of its base codes seq_codes[seq_off[t]:seq_off[t + 1]] (0-3 = ACGT, else 4).  ctrl_label None: the rule
+        of compute_motif_stats (kept: the record's base is mod_base; label: the motif matches); else that of
+        compute_ctrl_motif_stats (kept: the motif matches; label: ctrl_label).  -> per motif (stats float64, has_mod
+        bool[, record index int64]) of the kept records in record order.  `last_roc_kernel_ms`: kernel time."""
+        minus, ss, s_off, seq, off, pos, stat, table, sets = _check_roc_motif_args(
+            blk_minus, blk_seq_start, seq_off, seq_codes, rec_off, rec_pos, rec_stat, motifs)
+        n_mot, cap = table.shape[0], table.shape[0] * pos.shape[0]
+        o_stat, o_lab = np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.uint8)
+        o_idx = np.empty(cap, dtype=np.int64) if return_index else None
+        counts, ms = np.zeros(n_mot, dtype=np.int64), f64(0.0)
+        self._check(self._L.tba_roc_motif_labels(
+            self._h, i64(minus.shape[0]), _p(minus, C.c_uint8), _p(ss, i64), _p(s_off, i64), _p(seq, C.c_uint8),
+            _p(off, i64), _p(pos, i64), _p(stat, f64), i64(n_mot), _p(table, i32), _p(sets, C.c_uint8),
+            C.c_int(0 if ctrl_label is None else 1), C.c_int(int(bool(ctrl_label))), _p(o_stat, f64),
+            _p(o_lab, C.c_uint8), _p(o_idx, i64), _p(counts, i64), C.byref(ms)), 'tba_roc_motif_labels')
+        self.last_roc_kernel_ms = ms.value
+        return self._roc_split(o_stat, o_lab, o_idx, counts, return_index)
+
+    def roc_loc_labels(self, blk_loc, mod_locs, unmod_locs, rec_off, rec_pos, rec_stat, return_index=False):
+        """tba_roc_loc_labels: block t owns the ascending slices mod_locs[blk_loc[t, 0]:blk_loc[t, 1]] and
+        unmod_locs[blk_loc[t, 2]:blk_loc[t, 3]]; a record is kept when its position is in either, its label is
+        whether it is in the first -> (stats, has_mod[, record index]) in record order"""
+        loc, mod, unmod, off, pos, stat = _check_roc_loc_args(blk_loc, mod_locs, unmod_locs, rec_off, rec_pos, rec_stat)
+        cap = pos.shape[0]
+        o_stat, o_lab = np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.uint8)
+        o_idx = np.empty(cap, dtype=np.int64) if return_index else None
+        counts, ms = np.zeros(1, dtype=np.int64), f64(0.0)
+        self._check(self._L.tba_roc_loc_labels(
+            self._h, i64(loc.shape[0]), _p(loc, i64), _p(mod, i64), i64(mod.shape[0]), _p(unmod, i64),
+            i64(unmod.shape[0]), _p(off, i64), _p(pos, i64), _p(stat, f64), _p(o_stat, f64), _p(o_lab, C.c_uint8),
+            _p(o_idx, i64), _p(counts, i64), C.byref(ms)), 'tba_roc_loc_labels')
+        self.last_roc_kernel_ms = ms.value
+        return self._roc_split(o_stat, o_lab, o_idx, counts, return_index)[0]
+
+    def roc_rank_counts(self, stats, has_mod, ranks):
+        """tba_roc_rank_counts -> (tp_at int64[len(ranks)], tp_total, n_nan): tp_at[j] = True labels among the
+        ranks[j] + 1 first entries in ascending (stat, has_mod) order; -0.0 ties with 0.0.  With NaN statistics
+        (n_nan > 0) the counts mean nothing.  `last_roc_sort_ms` / `last_roc_gather_ms`: kernel time of the keys and
+        the sort / of the label scan and the gather."""
+        st, hm, rk = _check_roc_rank_args(stats, has_mod, ranks)
+        tp_at = np.zeros(rk.shape[0], dtype=np.int64)
+        total, n_nan, ms = i64(0), i64(0), (f64 * 2)()
+        self._check(self._L.tba_roc_rank_counts(
+            self._h, i64(st.shape[0]), _p(st, f64), _p(hm, C.c_uint8), i64(rk.shape[0]), _p(rk, i64), _p(tp_at, i64),
+            C.byref(total), C.byref(n_nan), ms), 'tba_roc_rank_counts')
+        self.last_roc_sort_ms, self.last_roc_gather_ms = ms[0], ms[1]
+        self.last_roc_kernel_ms = ms[0] + ms[1]
+        return tp_at, total.value, n_nan.value
 
     def kmer_levels(self, means, codes, read_off, kmer_width, central_pos, completed):
         """tba_kmer_levels: the levels of a batch of reads (means / codes CSR by read_off) gathered by k-mer

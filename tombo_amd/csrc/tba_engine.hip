@@ -20,6 +20,7 @@
 #include "k_kde.h"
 #include "k_tracks.h"
 #include "k_kmer_est.h"
+#include "k_roc.h"
 
 #include <algorithm>
 #include <array>
@@ -2978,4 +2979,214 @@ extern "C" int tba_engine_held_bytes(tba_engine *e, int64_t *bytes)
     e->for_each_devbuf([&](DevBuf &b) { tot += b.cap; });
     *bytes = (int64_t)tot;
     return 0;
+}
+
+// ---- ROC / precision-recall (k_roc.h): labels of stored statistics, sorted cumulative counts ------
+namespace {
+// kernel time of the launches between construction and stop(), through hipEvents on the engine's stream
+struct RocTimer {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipStream_t s;
+    RocTimer(Scratch &sc, hipStream_t s_, bool on) : s(s_)
+    {
+        if (!on || sc.rc) return;
+        if (sc.hip(hipEventCreate(&ev0), "hipEventCreate") || sc.hip(hipEventCreate(&ev1), "hipEventCreate")) return;
+        sc.hip(hipEventRecord(ev0, s), "hipEventRecord");
+    }
+    void mark(Scratch &sc) { if (ev1 && !sc.rc) sc.hip(hipEventRecord(ev1, s), "hipEventRecord"); }
+    // after the stream was synchronised
+    void read(Scratch &sc, double *out_ms)
+    {
+        float ms = 0;
+        if (ev1 && !sc.rc && out_ms && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *out_ms += ms;
+    }
+    ~RocTimer() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+};
+
+static int check_roc_recs(int64_t n_blocks, const int64_t *rec_off, const int64_t *rec_pos, const double *rec_stat)
+{
+    if (n_blocks < 0 || !rec_off) return set_err(TBA_E_ARG, "bad arguments");
+    if (const int rc = check_csr_off(rec_off, n_blocks)) return rc;
+    const i64 n_rec = n_blocks > 0 ? rec_off[n_blocks] : 0;
+    if (n_rec >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "2^31 records or more in one call");
+    if (n_rec > 0 && (!rec_pos || !rec_stat)) return set_err(TBA_E_ARG, "bad arguments");
+    return TBA_OK;
+}
+
+// count / scan / scatter of the kept (record, motif) pairs under f; everything after the uploads.  f's own arrays
+// are on the device already.  out_counts[n_motifs]; the pairs of all motifs back to back in the outputs.
+template <class F>
+static int roc_compact(tba_engine *e, Scratch &sc, F f, RocRecs R, i64 n_motifs, double *out_stats,
+    uint8_t *out_has_mod, int64_t *out_index, int64_t *out_counts, double *out_kernel_ms)
+{
+    const unsigned nb = trk_chunks(R.n_rec);
+    const i64 m = (i64)nb * n_motifs;
+    i64 *d_cnt = sc.out<i64>(m + 1);
+    double *d_stat = sc.out<double>(R.n_rec * n_motifs);
+    uint8_t *d_lab = sc.out<uint8_t>(R.n_rec * n_motifs);
+    i64 *d_idx = out_index ? sc.out<i64>(R.n_rec * n_motifs) : nullptr;
+    if (sc.rc) return sc.rc;
+    RocTimer tm(sc, e->stream, out_kernel_ms != nullptr);
+    if (!sc.rc) {
+        const dim3 grid(nb, (unsigned)n_motifs);
+        k_roc_count<<<grid, 256, 0, e->stream>>>(f, R, d_cnt);
+        k_trk_scan_blocks<<<1, 256, 0, e->stream>>>(m, d_cnt, d_cnt + m);
+        k_roc_scatter<<<grid, 256, 0, e->stream>>>(f, R, d_cnt, d_stat, d_lab, d_idx);
+    }
+    tm.mark(sc);
+    if (sc.sync(e->stream)) return sc.rc;
+    tm.read(sc, out_kernel_ms);
+    std::vector<i64> base(m + 1);
+    if (sc.get(base.data(), d_cnt, m + 1)) return sc.rc;
+    for (i64 k = 0; k < n_motifs; k++) out_counts[k] = base[(k + 1) * nb] - base[k * nb];
+    const i64 total = base[m];
+    if (total == 0) return TBA_OK;
+    if (sc.get(out_stats, d_stat, total) || sc.get(out_has_mod, d_lab, total)) return sc.rc;
+    if (out_index) return sc.get(out_index, d_idx, total);
+    return TBA_OK;
+}
+} // namespace
+
+extern "C" int tba_roc_motif_labels(tba_engine *e, int64_t n_blocks, const uint8_t *blk_minus,
+    const int64_t *blk_seq_start, const int64_t *seq_off, const uint8_t *seq, const int64_t *rec_off,
+    const int64_t *rec_pos, const double *rec_stat, int64_t n_motifs, const int32_t *motifs,
+    const uint8_t *motif_sets, int mode, int label, double *out_stats, uint8_t *out_has_mod,
+    int64_t *out_index, int64_t *out_counts, double *out_kernel_ms)
+{
+    if (!e || !blk_minus || !blk_seq_start || !seq_off || n_motifs < 1 || n_motifs > ROC_MAX_MOTIFS || !motifs ||
+        !motif_sets || (mode != 0 && mode != 1) || !out_stats || !out_has_mod || !out_counts)
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (const int rc = check_roc_recs(n_blocks, rec_off, rec_pos, rec_stat)) return rc;
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    for (i64 k = 0; k < n_motifs; k++) out_counts[k] = 0;
+    const i64 n_rec = n_blocks > 0 ? rec_off[n_blocks] : 0;
+    if (const int rc = check_csr_off(seq_off, n_blocks)) return rc;
+    const i64 n_seq = seq_off[n_blocks];
+    if (n_seq > 0 && !seq) return set_err(TBA_E_ARG, "bad arguments");
+    // the motif table of the device: length, mod_pos, mod_base, first set
+    std::vector<i32> mot(4 * n_motifs);
+    i64 n_sets = 0;
+    for (i64 k = 0; k < n_motifs; k++) {
+        const i32 len = motifs[3 * k], mp = motifs[3 * k + 1];
+        if (len < 1 || len > 1024 || mp < 1 || mp > len) return set_err(TBA_E_ARG, "bad motif");
+        mot[4 * k] = len; mot[4 * k + 1] = mp; mot[4 * k + 2] = motifs[3 * k + 2]; mot[4 * k + 3] = (i32)n_sets;
+        n_sets += len;
+    }
+    if (n_rec == 0) return TBA_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    RocMotifLabel f{};
+    f.blk_minus = sc.in(blk_minus, n_blocks);
+    f.blk_seq_start = sc.in(blk_seq_start, n_blocks);
+    f.seq_off = sc.in(seq_off, n_blocks + 1);
+    f.seq = n_seq > 0 ? sc.in(seq, n_seq) : sc.out<uint8_t>(1);
+    f.mot = sc.in(mot.data(), mot.size());
+    f.sets = sc.in(motif_sets, n_sets);
+    f.mode = mode; f.label = label ? 1 : 0;
+    RocRecs R{n_blocks, n_rec, sc.in(rec_off, n_blocks + 1), sc.in(rec_pos, n_rec), sc.in(rec_stat, n_rec)};
+    return roc_compact(e, sc, f, R, n_motifs, out_stats, out_has_mod, out_index, out_counts, out_kernel_ms);
+}
+
+extern "C" int tba_roc_loc_labels(tba_engine *e, int64_t n_blocks, const int64_t *blk_loc, const int64_t *mod_locs,
+    int64_t n_mod, const int64_t *unmod_locs, int64_t n_unmod, const int64_t *rec_off, const int64_t *rec_pos,
+    const double *rec_stat, double *out_stats, uint8_t *out_has_mod, int64_t *out_index, int64_t *out_count,
+    double *out_kernel_ms)
+{
+    if (!e || !blk_loc || n_mod < 0 || n_unmod < 0 || (n_mod > 0 && !mod_locs) || (n_unmod > 0 && !unmod_locs) ||
+        !out_stats || !out_has_mod || !out_count)
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (const int rc = check_roc_recs(n_blocks, rec_off, rec_pos, rec_stat)) return rc;
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    *out_count = 0;
+    const i64 n_rec = n_blocks > 0 ? rec_off[n_blocks] : 0;
+    for (i64 b = 0; b < n_blocks; b++) {
+        const i64 *s = blk_loc + 4 * b;
+        if (s[0] < 0 || s[1] < s[0] || s[1] > n_mod || s[2] < 0 || s[3] < s[2] || s[3] > n_unmod)
+            return set_err(TBA_E_ARG, "location slice outside its list");
+    }
+    if (n_rec == 0) return TBA_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    RocLocLabel f{};
+    f.blk_loc = sc.in(blk_loc, 4 * n_blocks);
+    f.mod = n_mod > 0 ? sc.in(mod_locs, n_mod) : sc.out<i64>(1);
+    f.unmod = n_unmod > 0 ? sc.in(unmod_locs, n_unmod) : sc.out<i64>(1);
+    RocRecs R{n_blocks, n_rec, sc.in(rec_off, n_blocks + 1), sc.in(rec_pos, n_rec), sc.in(rec_stat, n_rec)};
+    return roc_compact(e, sc, f, R, 1, out_stats, out_has_mod, out_index, out_count, out_kernel_ms);
+}
+
+extern "C" int64_t tba_roc_sort_tile(void) { return ROC_SORT_TILE; }
+
+extern "C" int tba_roc_rank_counts(tba_engine *e, int64_t n, const double *stats, const uint8_t *has_mod,
+    int64_t n_ranks, const int64_t *ranks, int64_t *out_tp_at, int64_t *out_tp_total, int64_t *out_n_nan,
+    double *out_kernel_ms)
+{
+    if (!e || n < 0 || n >= ((i64)1 << 31) || n_ranks < 0 || (n > 0 && (!stats || !has_mod)) ||
+        (n_ranks > 0 && (!ranks || !out_tp_at)) || !out_tp_total || !out_n_nan)
+        return set_err(TBA_E_ARG, "bad arguments");
+    for (i64 j = 0; j < n_ranks; j++)
+        if (ranks[j] < 0 || ranks[j] >= n || (j > 0 && ranks[j] < ranks[j - 1]))
+            return set_err(TBA_E_ARG, "ranks must be non-decreasing and inside [0, n)");
+    if (out_kernel_ms) out_kernel_ms[0] = out_kernel_ms[1] = 0.0;
+    *out_tp_total = 0; *out_n_nan = 0;
+    if (n == 0) return TBA_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    Scratch sc;
+    const double *d_stat = sc.in(stats, n);
+    uint8_t *lab[2] = {sc.in(has_mod, n), sc.out<uint8_t>(n)};
+    u64 *key[2] = {sc.out<u64>(n), sc.out<u64>(n)};
+    const i64 *d_ranks = n_ranks > 0 ? sc.in(ranks, n_ranks) : nullptr;
+    i64 *d_tp = sc.out<i64>(n_ranks);
+    unsigned long long *d_hist = sc.out<unsigned long long>(ROC_HIST_BINS + 1);
+    const unsigned n_tiles = (unsigned)((n + ROC_SORT_TILE - 1) / ROC_SORT_TILE);
+    u32 *d_table = sc.out<u32>((i64)ROC_MAX_DIGITS * n_tiles);
+    const unsigned n_tab_chunks = trk_chunks((i64)ROC_MAX_DIGITS * n_tiles), n_lab_chunks = trk_chunks(n);
+    i64 *d_tab_cnt = sc.out<i64>(n_tab_chunks + 1), *d_lab_cnt = sc.out<i64>(n_lab_chunks + 1);
+    i32 *d_bad = sc.status(e->stream);
+    if (sc.rc || sc.hip(hipMemsetAsync(d_hist, 0, (ROC_HIST_BINS + 1) * 8, e->stream), "hipMemsetAsync")) return sc.rc;
+    std::vector<unsigned long long> hist(ROC_HIST_BINS + 1);
+    {
+        RocTimer tm(sc, e->stream, out_kernel_ms != nullptr);
+        if (!sc.rc) k_roc_keys<<<grid_for(n), 256, 0, e->stream>>>(n, d_stat, lab[0], key[0], d_hist);
+        tm.mark(sc);
+        if (sc.sync(e->stream)) return sc.rc;
+        tm.read(sc, out_kernel_ms);
+        if (sc.get(hist.data(), d_hist, hist.size())) return sc.rc;
+    }
+    *out_n_nan = (int64_t)hist[ROC_HIST_BINS];
+    double sort_ms = 0.0, rank_ms = 0.0;
+    RocTimer tm(sc, e->stream, out_kernel_ms != nullptr);
+    int cur = 0;
+    for (int pass = 0; pass < 8 && !sc.rc; pass++) {
+        const int nd = pass == 0 ? 512 : 256;
+        bool one_digit = false;   // a digit that holds every entry: the pass would change nothing
+        for (int d = 0; d < nd; d++) one_digit |= hist[roc_hist_base(pass) + d] == (unsigned long long)n;
+        if (one_digit) continue;
+        const i64 m = (i64)nd * n_tiles;
+        const unsigned nc = trk_chunks(m);
+        k_roc_hist<<<n_tiles, 256, 0, e->stream>>>(n, pass, nd, key[cur], lab[cur], d_table);
+        k_roc_tab_count<<<nc, 256, 0, e->stream>>>(m, d_table, d_tab_cnt);
+        k_trk_scan_blocks<<<1, 256, 0, e->stream>>>((i64)nc, d_tab_cnt, d_tab_cnt + n_tab_chunks);
+        k_roc_tab_apply<<<nc, 256, 0, e->stream>>>(m, d_table, d_tab_cnt);
+        k_roc_scatter_pass<<<n_tiles, 256, 0, e->stream>>>(n, pass, nd, key[cur], lab[cur], d_table, key[cur ^ 1],
+            lab[cur ^ 1]);
+        cur ^= 1;
+    }
+    tm.mark(sc);
+    RocTimer tm_rank(sc, e->stream, out_kernel_ms != nullptr);
+    if (!sc.rc) {
+        k_roc_label_count<<<n_lab_chunks, 256, 0, e->stream>>>(n, lab[cur], d_lab_cnt);
+        k_trk_scan_blocks<<<1, 256, 0, e->stream>>>((i64)n_lab_chunks, d_lab_cnt, d_lab_cnt + n_lab_chunks);
+        if (n_ranks > 0)
+            k_roc_gather<<<grid_for(n_ranks), 256, 0, e->stream>>>(n, n_ranks, d_ranks, lab[cur], d_lab_cnt, d_tp, d_bad);
+    }
+    tm_rank.mark(sc);
+    const int bad = sc.sync(e->stream, d_bad);
+    if (sc.rc) return sc.rc;
+    tm.read(sc, &sort_ms);
+    tm_rank.read(sc, &rank_ms);
+    if (out_kernel_ms) { out_kernel_ms[0] += sort_ms; out_kernel_ms[1] = rank_ms; }
+    if (bad) return set_err(TBA_E_ARG, "rank outside [0, n)");
+    if (sc.get(out_tp_total, d_lab_cnt + n_lab_chunks, 1)) return sc.rc;
+    return n_ranks > 0 ? sc.get(out_tp_at, d_tp, n_ranks) : TBA_OK;
 }

@@ -15,8 +15,12 @@ can switch packages without touching its code:
   rev_transcribe / get_mean_q_score          tombo_helper.py:370-394
   get_raw_read_slot tombo_helper.py:1071     get_channel_info  tombo_helper.py:2071
 """
+import io
+import os
 import re
+import warnings
 from collections import namedtuple
+from itertools import islice
 
 import numpy as np
 
@@ -232,6 +236,100 @@ class TomboMotif(object):
     def matches_seq(self, seq):
         """does the motif match `seq` with the modified position inside it? (tombo_helper.py:637-670)"""
         return next(self._iter_partial(seq), None) is not None
+
+
+_MOTIF_DESCS_MSG = ('Invalid motif decriptions format. Format descriptions as: '
+                    '"motif:mod_pos:name[::motif2:mod_pos2:name2...]".')
+
+
+def parse_motif_descs(stat_motif_descs):
+    """`--motif-descriptions` text -> [(TomboMotif, name), ...] (tombo_helper.py:710-730); the reference's
+    message, which it prints before exiting, is raised as a TomboError"""
+    parsed_motif_descs = []
+    try:
+        for motif_desc in stat_motif_descs.split('::'):
+            raw_motif, mod_pos, mod_name = motif_desc.split(':')
+            parsed_motif_descs.append((TomboMotif(raw_motif, int(mod_pos)), mod_name))
+    except Exception:
+        raise TomboError(_MOTIF_DESCS_MSG)
+    return parsed_motif_descs
+
+
+def parse_locs_file(locs_fn):
+    """BED file of single-base locations -> {(chrm, strand): sorted positions} (tombo_helper.py:475-506: the
+    0-based start column is the position, the end column is ignored, repeated lines count once)"""
+    n_added, n_failed = 0, 0
+    raw_locs = {}
+    with open(locs_fn) as locs_fp:
+        for line in locs_fp:
+            try:
+                chrm, pos, _, _, _, strand = line.split()[:6]
+                pos = int(pos)
+            except ValueError:
+                n_failed += 1
+                continue
+            raw_locs.setdefault((chrm, strand), set()).add(pos)
+            n_added += 1
+    if n_failed > 0:
+        if n_added > 0:
+            warnings.warn(('Some provided locations ({}) were incorrectly formatted. ' +
+                           'Ensure that provided file ({}) is in BED format.').format(n_failed, locs_fn))
+        else:
+            warnings.warn(('All provided locations from {} were incorrectly formatted. ' +
+                           'Ensure that provided file is in BED format.').format(locs_fn))
+    return dict((cs, np.array(sorted(cs_poss))) for cs, cs_poss in raw_locs.items())
+
+
+class Fasta(object):
+    """A FASTA file held in memory (tombo_helper.py:744-865, the branch without pyfaidx; `force_in_mem` is
+    accepted for the reference's call sites and changes nothing).  Sequence is upper-cased and, when the first
+    records hold uridines, converted to the DNA alphabet."""
+
+    def _load_in_mem(self):
+        genome_index, curr_id, curr_seq = {}, None, []
+        with io.open(self.fasta_fn) as fasta_fp:
+            for line in fasta_fp:
+                if line.startswith('>'):
+                    if curr_id is not None:
+                        genome_index[curr_id] = ''.join(curr_seq)
+                    curr_seq = []
+                    curr_id = line.replace('>', '').split()[0]
+                else:
+                    curr_seq.append(line.strip())
+            if curr_id is not None:
+                genome_index[curr_id] = ''.join(curr_seq)
+        return genome_index
+
+    def _index_contains_uridines(self, n_chrms=10, n_bases=1000):
+        return any(re.search('U', self.get_seq(chrm, 1, n_bases, error_end=False))
+                   for chrm in islice(self.index.keys(), n_chrms))
+
+    def __init__(self, fasta_fn, dry_run=False, force_in_mem=True, assume_dna_base=False):
+        self.fasta_fn = os.path.realpath(os.path.expanduser(fasta_fn))
+        self.has_rna_bases = False
+        self.has_pyfaidx = False
+        if not dry_run:
+            self.index = self._load_in_mem()
+            # (the reference's expression, :810-811)
+            self.has_rna_bases = assume_dna_base or self._index_contains_uridines()
+
+    def get_seq(self, chrm, start=None, end=None, error_end=True):
+        """bases [start, end) of `chrm`, 0-based; a start outside the chromosome, or with error_end an end outside
+        it, raises TomboError"""
+        if (start is not None and (start < 0 or start > len(self.index[chrm]))) or (
+                error_end and end is not None and (end < 0 or end > len(self.index[chrm]))):
+            raise TomboError('Encountered invalid genome sequence request.')
+        r_seq = self.index[chrm][start:end].upper()
+        if self.has_rna_bases:
+            r_seq = rev_transcribe(r_seq)
+        return r_seq
+
+    def iter_chrms(self):
+        for chrm in self.index:
+            yield chrm
+
+    def __contains__(self, chrm):
+        return chrm in self.index
 
 
 def read_from_results(rsqgl_res, norm_means, fn=None, corr_group='RawGenomeCorrected_000',

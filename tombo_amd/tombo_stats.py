@@ -25,7 +25,7 @@ from ._default_parameters import (
     HALF_NORM_EXPECTED_VAL, MIN_EVENT_TO_SEQ_RATIO, STALL_PARAMS, SMALLEST_PVAL, FM_OFFSET_DEFAULT,
     SAMP_COMP_TXT, DE_NOVO_TXT, ALT_MODEL_TXT, CONST_SD_MODEL, OCLLHR_SCALE, OCLLHR_HEIGHT,
     OCLLHR_POWER, MEAN_PRIOR_CONST, SD_PRIOR_CONST, ALT_EST_BATCH, MAX_KMER_OBS, MIN_KMER_OBS_TO_EST,
-    KERNEL_DENSITY_RANGE, NUM_DENS_POINTS)
+    KERNEL_DENSITY_RANGE, NUM_DENS_POINTS, ROC_PLOT_POINTS)
 
 _MODEL_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tombo_models')
 _BASE_CODE = np.full(256, 255, dtype=np.uint8)
@@ -1105,6 +1105,19 @@ class _BlockStore(object):
             return
         return reg_stats[0] if len(reg_stats) == 1 else np.concatenate(reg_stats)
 
+    # the (statistic, has_mod) pairs behind `tombo plot roc` (:2406-2535): see the module functions of these names
+    def compute_motif_stats(self, motif_descs, genome_index, stats_per_block=None, total_stats_limit=None,
+                            engine=None):
+        return compute_motif_stats(self, motif_descs, genome_index, stats_per_block, total_stats_limit, engine)
+
+    def compute_ground_truth_stats(self, ground_truth_locs, engine=None):
+        return compute_ground_truth_stats(self, ground_truth_locs, engine)
+
+    def compute_ctrl_motif_stats(self, ctrl_stats, motif_descs, genome_index, stats_per_block=None,
+                                 total_stats_limit=None, engine=None):
+        return compute_ctrl_motif_stats(self, ctrl_stats, motif_descs, genome_index, stats_per_block,
+                                        total_stats_limit, engine)
+
 
 class ModelStats(_BlockStore):
     """A standard (per genomic base) statistics file of the model-based tests: all of stat_type, region_size,
@@ -1471,6 +1484,404 @@ def write_stats_from_regions(results, per_read, stats, pr_stats=None):
         if not isinstance(reg_res, Exception):
             for _, reg_stats in reg_res:
                 stats._write_stat_block(reg_stats)
+
+
+# ---------------------------------------------------------------------------------------------
+# ROC and precision-recall from statistics files: the numbers behind `tombo plot roc`, `per_read_roc`,
+# `sample_compare_roc` and `sample_compare_per_read_roc` (tombo_stats.py:2377-2535, _plot_commands.py:60-82).
+# The reference labels every record in a Python loop and sorts a list of tuples; here the records of many blocks
+# are labelled and compacted in one call (`Engine.roc_motif_labels` / `roc_loc_labels`) and the sorted
+# cumulative counts come from `Engine.roc_rank_counts` (kernels in csrc/k_roc.h).  Every output is an integer
+# count or one float64 division of two integers.
+#
+# Deviations from the reference, all at places where it fails or reads the wrong bases:
+#   * a motif whose window around a record leaves the fetched sequence does not match; the test of the
+#     record's own base still applies.  At a chromosome start the reference slices with a negative offset
+#     (an empty or shifted window: IndexError or wrong bases), and for a minus-strand record within
+#     before_bases of a chromosome end its reverse-complemented window is shifted.  Everywhere else, the end of
+#     a plus-strand chromosome included, the two agree.
+#   * a genome letter that is not A, C, G or T never equals mod_base (the reference compares letters, so an `N`
+#     in the genome under a motif whose modified position is `N` is emitted there, always with label False).
+#   * prep_accuracy_rates raises ValueError for a name without entries (the reference fails inside zip(); its
+#     callers drop empty names first) and for a NaN statistic (sorted() is order-dependent there).
+# (record, motif) pairs per labelling call: the engine holds an output slot of up to 17 bytes for each, on the host
+# and on the device, before compaction
+_ROC_MAX_PAIRS = 1 << 26
+# with a total_stats_limit the control form sends at most as many records per call as entries are still missing
+# (what a call emits is known only when it returns), but not fewer than this
+_ROC_LIMIT_MIN_RECORDS = 1 << 16
+_SEQ_CODE = np.full(256, 4, dtype=np.uint8)
+for _i, _b in enumerate(b'ACGT'):
+    _SEQ_CODE[_b] = _i
+_EMPTY_I64 = np.zeros(0, dtype=np.int64)
+
+
+class MotifStats(object):
+    """The (statistic, has_mod) pairs of one modification name: `stats` float64 and `has_mod` bool, in the
+    reference's order.  len() and iteration (tuples) stand in for the reference's list of tuples."""
+
+    def __init__(self, stats=(), has_mod=()):
+        self.stats = np.ascontiguousarray(stats, dtype=np.float64)
+        self.has_mod = np.ascontiguousarray(has_mod, dtype=np.bool_)
+        if self.stats.ndim != 1 or self.stats.shape != self.has_mod.shape:
+            raise ValueError('stats and has_mod must be one-dimensional and of one length')
+
+    def __len__(self):
+        return self.stats.shape[0]
+
+    def __iter__(self):
+        return iter(zip(self.stats.tolist(), self.has_mod.tolist()))
+
+    @classmethod
+    def concat(cls, parts):
+        parts = list(parts)
+        if not parts:
+            return cls()
+        return cls(np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]))
+
+
+def _as_motif_stats(mod_stats):
+    if isinstance(mod_stats, MotifStats):
+        return mod_stats
+    pairs = list(mod_stats)
+    return MotifStats([p[0] for p in pairs], [bool(p[1]) for p in pairs])
+
+
+def motif_base_sets(motif):
+    """(length, mod_pos, code of mod_base or 255, uint8 base sets: bit c set when code c is allowed)"""
+    sets = np.array([sum(1 << 'ACGT'.index(b) for b in th.SINGLE_LETTER_CODE[c].strip('[]')) for c in motif.raw_motif],
+                    dtype=np.uint8)
+    code = 'ACGT'.find(motif.mod_base)
+    return motif.motif_len, motif.mod_pos, code if code >= 0 else 255, sets
+
+
+def motif_can_overlap_itself(motif):
+    """can two matches of the motif overlap?  (Only then does re.finditer, leftmost and non-overlapping, differ
+    from `matches at this position`.)"""
+    sets = motif_base_sets(motif)[3]
+    return any(np.all(sets[shift:] & sets[:len(sets) - shift]) for shift in range(1, len(sets)))
+
+
+def _check_motif_descs(motif_descs):
+    motif_descs = list(motif_descs)
+    if not motif_descs:
+        raise ValueError('motif_descs needs at least one motif')
+    motifs = [motif for motif, _ in motif_descs]
+    before_bases = max(m.mod_pos for m in motifs) - 1
+    after_bases = max(m.motif_len - m.mod_pos for m in motifs)
+    return motifs, [name for _, name in motif_descs], before_bases, after_bases
+
+
+def _by_name(names, parts):
+    """{name: MotifStats} from the pieces of every motif.  parts[k]: one (stats, has_mod, order key) per call, in call
+    order.  Motifs that share a name share a list, as in the reference: within a call the entries are ordered by the
+    key (the record in the motif form, the block in the control form), then by the motif's place in motif_descs."""
+    out = {}
+    for name in names:
+        if name in out:
+            continue
+        ks = [k for k, n in enumerate(names) if n == name]
+        pieces = []
+        for call in range(len(parts[ks[0]])):
+            st, hm = (np.concatenate([parts[k][call][j] for k in ks]) for j in (0, 1))
+            if len(ks) > 1:
+                order = np.argsort(np.concatenate([parts[k][call][2] for k in ks]), kind='stable')
+                st, hm = st[order], hm[order]
+            pieces.append((st, hm))
+        out[name] = MotifStats.concat(pieces)
+    return out
+
+
+class _RocBlocks(object):
+    """the blocks of one labelling call: sequences and records, concatenated"""
+
+    def __init__(self):
+        self.minus, self.seq_start, self.seqs, self.recs = [], [], [], []
+        self.n_rec = 0
+
+    def add(self, strand, seq_start, reg_seq, rec_pos, rec_stat):
+        self.minus.append(strand == '-')
+        self.seq_start.append(seq_start)
+        self.seqs.append(reg_seq)
+        self.recs.append((np.asarray(rec_pos, dtype=np.int64), np.asarray(rec_stat, dtype=np.float64)))
+        self.n_rec += self.recs[-1][0].shape[0]
+
+    def __len__(self):
+        return len(self.minus)
+
+    def rec_arrays(self):
+        off = _csr_offsets([p.shape[0] for p, _ in self.recs])
+        pos = np.concatenate([p for p, _ in self.recs]) if self.recs else _EMPTY_I64
+        return off, pos, _concat_f64([s for _, s in self.recs])
+
+    def seq_arrays(self):
+        codes = _SEQ_CODE[np.frombuffer(''.join(self.seqs).encode('latin-1', 'replace'), dtype=np.uint8)]
+        return (np.array(self.minus, dtype=np.uint8), np.array(self.seq_start, dtype=np.int64),
+                _csr_offsets([len(s) for s in self.seqs]), codes)
+
+
+def _block_seq(genome_index, chrm, strand, start, end, before_bases, after_bases):
+    """(seq_start, reg_seq) of a block as the reference fetches it (:2417-2425)"""
+    if strand == '+':
+        seq_start, seq_end = max(start - before_bases, 0), end + after_bases
+    else:
+        seq_start, seq_end = max(start - after_bases, 0), end + before_bases
+    return seq_start, genome_index.get_seq(chrm, seq_start, seq_end, error_end=False)
+
+
+def compute_motif_stats(stats, motif_descs, genome_index, stats_per_block=None, total_stats_limit=None,
+                        engine=None):
+    """:2406-2456: for every record of `stats` (a ModelStats, LevelStats or PerReadStats; blocks in the order of
+    its iterator) and every motif whose mod_base is the base under the record, the pair (statistic, does the
+    motif match with its modified position on the record) -> {mod_name: MotifStats}.  stats_per_block: blocks
+    with more records are sub-sampled with np.random.choice (global state, one draw per such block, in block
+    order); total_stats_limit: no further block is read once that many rows were seen.  Blocks go to the engine
+    in groups of at most _ROC_MAX_PAIRS (record, motif) pairs."""
+    motifs, names, before_bases, after_bases = _check_motif_descs(motif_descs)
+    eng = _engine(engine)
+    descs = [motif_base_sets(m) for m in motifs]
+    max_records = max(1, _ROC_MAX_PAIRS // len(motifs))
+    shared_names = len(set(names)) < len(names)
+    parts = [[] for _ in motifs]
+
+    def flush(group):
+        if group.n_rec:
+            res = eng.roc_motif_labels(*(group.seq_arrays() + group.rec_arrays() + (descs,)), return_index=shared_names)
+            for k, r in enumerate(res):
+                parts[k].append(r)
+
+    group, total_num_stats = _RocBlocks(), 0
+    for chrm, strand, start, end, block_stats in stats:
+        seq_start, reg_seq = _block_seq(genome_index, chrm, strand, start, end, before_bases, after_bases)
+        if stats_per_block is not None and block_stats.shape[0] > stats_per_block:
+            block_stats = block_stats[np.random.choice(block_stats.shape[0], stats_per_block, replace=False)]
+        total_num_stats += block_stats.shape[0]
+        if group.n_rec and group.n_rec + block_stats.shape[0] > max_records:
+            flush(group)
+            group = _RocBlocks()
+        group.add(strand, seq_start, reg_seq, block_stats['pos'], block_stats[stats._stat_slot])
+        if total_stats_limit is not None and total_num_stats >= total_stats_limit:
+            break
+    flush(group)
+    return _by_name(names, parts)
+
+
+def _truth_group(eng, mod_locs, unmod_locs, slot, blocks):
+    """the kept (stats, has_mod) of a group of blocks against the position lists of their (chrm, strand) keys"""
+    lists, where, sizes = ([], []), ({}, {}), [0, 0]   # per list: pieces, key -> (sorted positions, first index)
+
+    def cs_slice(which, locs, cs, start, end):
+        if cs not in where[which]:
+            v = np.unique(np.asarray(locs.get(cs, ()), dtype=np.int64))
+            where[which][cs] = (v, sizes[which])
+            lists[which].append(v)
+            sizes[which] += v.shape[0]
+        v, base = where[which][cs]
+        return base + int(np.searchsorted(v, start)), base + int(np.searchsorted(v, end))
+
+    blk_loc, recs = [], _RocBlocks()
+    for chrm, strand, start, end, block_stats in blocks:
+        blk_loc.append(cs_slice(0, mod_locs, (chrm, strand), start, end) +
+                       cs_slice(1, unmod_locs, (chrm, strand), start, end))
+        recs.add(strand, 0, '', block_stats['pos'], block_stats[slot])
+    return eng.roc_loc_labels(np.array(blk_loc, dtype=np.int64).reshape(-1, 4), np.concatenate(lists[0]),
+                              np.concatenate(lists[1]), *recs.rec_arrays())
+
+
+def compute_ground_truth_stats(stats, ground_truth_locs, engine=None):
+    """:2458-2483: ground_truth_locs = (mod_locs, unmod_locs, mod_name), the first two {(chrm, strand):
+    positions} as parse_locs_file returns them.  A record whose position is in either list of its block's
+    (chrm, strand) is kept; it counts as modified when the position is in mod_locs -> {mod_name: MotifStats}.
+    Blocks go to the engine in groups of at most _ROC_MAX_PAIRS records."""
+    mod_locs, unmod_locs, mod_name = ground_truth_locs
+    eng = _engine(engine)
+    pieces, group, n_rec = [], [], 0
+    for block in stats:
+        n = block[4].shape[0]
+        if n == 0:
+            continue
+        if group and n_rec + n > _ROC_MAX_PAIRS:
+            pieces.append(_truth_group(eng, mod_locs, unmod_locs, stats._stat_slot, group))
+            group, n_rec = [], 0
+        group.append(block)
+        n_rec += n
+    if group:
+        pieces.append(_truth_group(eng, mod_locs, unmod_locs, stats._stat_slot, group))
+    return {mod_name: MotifStats.concat(pieces)}
+
+
+def _interleave_by_block(samp, ctrl, samp_off, ctrl_off):
+    """per block the kept sample entries, then the kept control entries.  samp / ctrl: (stats, has_mod, record
+    index) in record order; *_off: the blocks' record offsets -> (stats, has_mod, block of every entry)"""
+    n_blk = samp_off.shape[0] - 1
+    s_blk = np.searchsorted(samp_off, samp[2], side='right') - 1
+    c_blk = np.searchsorted(ctrl_off, ctrl[2], side='right') - 1
+    s_cnt, c_cnt = np.bincount(s_blk, minlength=n_blk), np.bincount(c_blk, minlength=n_blk)
+    s_first, c_first = np.concatenate([[0], np.cumsum(s_cnt)]), np.concatenate([[0], np.cumsum(c_cnt)])
+    n = samp[0].shape[0] + ctrl[0].shape[0]
+    st, hm, blk = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.bool_), np.empty(n, dtype=np.int64)
+    s_dest = np.arange(samp[0].shape[0]) + c_first[s_blk]          # the control entries of earlier blocks go before
+    c_dest = np.arange(ctrl[0].shape[0]) + s_first[c_blk + 1]      # the sample entries up to this block go before
+    st[s_dest], hm[s_dest], blk[s_dest] = samp[0], samp[1], s_blk
+    st[c_dest], hm[c_dest], blk[c_dest] = ctrl[0], ctrl[1], c_blk
+    return st, hm, blk
+
+
+_NO_PAIRS = (np.zeros(0), np.zeros(0, dtype=np.bool_), _EMPTY_I64)
+
+
+def _ctrl_group(eng, motifs, on_device, samp, ctrl):
+    """the control form for a group of blocks (samp / ctrl: _RocBlocks with the same blocks and sequences) -> per
+    motif (stats, has_mod, block of every entry): per block the sample's kept records, then the control's"""
+    n_blk = len(samp)
+    seq_args, samp_recs, ctrl_recs = samp.seq_arrays(), samp.rec_arrays(), ctrl.rec_arrays()
+    kept = {}                 # motif -> [(stats, has_mod, index) of the sample, of the control]
+    if on_device:
+        descs = [motif_base_sets(motifs[k]) for k in on_device]
+        for which, recs in enumerate((samp_recs, ctrl_recs)):
+            res = eng.roc_motif_labels(*(seq_args + recs + (descs,)), ctrl_label=which == 0, return_index=True) \
+                if recs[1].shape[0] else [_NO_PAIRS] * len(descs)
+            for k, r in zip(on_device, res):
+                kept.setdefault(k, []).append(r)
+    for k, motif in enumerate(motifs):
+        if k in kept:
+            continue
+        # a motif that can overlap itself: the reference's own scan, block by block (:2507-2515)
+        sites, blk_loc, n_sites = [], np.zeros((n_blk, 4), dtype=np.int64), 0
+        for t in range(n_blk):
+            if samp.minus[t]:
+                poss = [m.start() + motif.motif_len - motif.mod_pos for m in motif.rev_comp_pat.finditer(samp.seqs[t])]
+            else:
+                poss = [m.start() + motif.mod_pos - 1 for m in motif.motif_pat.finditer(samp.seqs[t])]
+            sites.append(np.array(poss, dtype=np.int64) + samp.seq_start[t])
+            blk_loc[t] = n_sites, n_sites + len(poss), 0, 0
+            n_sites += len(poss)
+        sites = np.concatenate(sites)
+        kept[k] = [
+            eng.roc_loc_labels(blk_loc, sites, _EMPTY_I64, *samp_recs, return_index=True)
+            if samp_recs[1].shape[0] else _NO_PAIRS,
+            eng.roc_loc_labels(blk_loc[:, [2, 3, 0, 1]], _EMPTY_I64, sites, *ctrl_recs, return_index=True)
+            if ctrl_recs[1].shape[0] else _NO_PAIRS]
+    return [_interleave_by_block(kept[k][0], kept[k][1], samp_recs[0], ctrl_recs[0]) for k in range(len(motifs))]
+
+
+def compute_ctrl_motif_stats(stats, ctrl_stats, motif_descs, genome_index, stats_per_block=None,
+                             total_stats_limit=None, engine=None):
+    """:2485-2535: the records of `stats` at motif sites count as modified, those of `ctrl_stats` at the same sites
+    of the same block as unmodified -> {mod_name: MotifStats}, per block and motif the sample entries, then the
+    control entries.  The sites of a block are those of re.finditer over the block's fetched sequence: for a
+    motif that cannot overlap itself that is every position where it matches (found on the device); for one that
+    can, the positions come from the regular expression here and the device tests membership.  stats_per_block
+    is accepted and unused, as in the reference.  total_stats_limit counts emitted entries and ends the output
+    after the block that reaches it.  Blocks are sent in groups of at most _ROC_MAX_PAIRS (record,
+    motif) pairs; with a limit a group holds at most as many records as entries are still missing (at least
+    _ROC_LIMIT_MIN_RECORDS, a larger block stands alone), and nothing is read or sent after the group that reaches
+    it."""
+    motifs, names, before_bases, after_bases = _check_motif_descs(motif_descs)
+    eng = _engine(engine)
+    on_device = [k for k, m in enumerate(motifs) if not motif_can_overlap_itself(m)]
+    max_records = max(1, _ROC_MAX_PAIRS // len(motifs))
+    parts = [[] for _ in motifs]
+    total_num_stats = 0
+
+    def flush(samp, ctrl):
+        """-> the limit was reached"""
+        nonlocal total_num_stats
+        if len(samp) == 0:
+            return False
+        merged = _ctrl_group(eng, motifs, on_device, samp, ctrl)
+        emitted = total_num_stats + np.cumsum(sum(np.bincount(blk, minlength=len(samp)) for _, _, blk in merged))
+        total_num_stats = int(emitted[-1])
+        reached = np.flatnonzero(emitted >= total_stats_limit) if total_stats_limit is not None else _EMPTY_I64
+        for k, (st, hm, blk) in enumerate(merged):
+            if reached.shape[0]:
+                keep = blk <= reached[0]
+                st, hm, blk = st[keep], hm[keep], blk[keep]
+            parts[k].append((st, hm, blk))
+        return reached.shape[0] > 0
+
+    samp, ctrl, done = _RocBlocks(), _RocBlocks(), False
+    for chrm, strand, start, end, block_stats in stats:
+        ctrl_block = ctrl_stats.get_reg_stats(chrm, strand, start, end)
+        n = max(block_stats.shape[0], 0 if ctrl_block is None else ctrl_block.shape[0])
+        budget = max_records if total_stats_limit is None else \
+            min(max_records, max(total_stats_limit - total_num_stats, _ROC_LIMIT_MIN_RECORDS))
+        if len(samp) and max(samp.n_rec, ctrl.n_rec) + n > budget:
+            done = flush(samp, ctrl)
+            if done:
+                break
+            samp, ctrl = _RocBlocks(), _RocBlocks()
+        seq_start, reg_seq = _block_seq(genome_index, chrm, strand, start, end, before_bases, after_bases)
+        samp.add(strand, seq_start, reg_seq, block_stats['pos'], block_stats[stats._stat_slot])
+        if ctrl_block is None:
+            ctrl.add(strand, seq_start, reg_seq, _EMPTY_I64, np.zeros(0))
+        else:
+            ctrl.add(strand, seq_start, reg_seq, ctrl_block['pos'], ctrl_block[stats._stat_slot])
+    if not done:
+        flush(samp, ctrl)
+    return _by_name(names, parts)
+
+
+def compute_auc(tp_rate, fp_rate):
+    return np.sum(tp_rate[:-1] * (fp_rate[1:] - fp_rate[:-1]))
+
+
+def compute_mean_avg_precison(tp_rate, precision):
+    return np.sum(np.diff(np.concatenate([[0, ], tp_rate, [1, ]]), ) *
+                  np.concatenate([[0, ], precision, [1, ]])[:-1])
+
+
+def compute_accuracy_rates(stat_has_mod, num_plot_points=ROC_PLOT_POINTS):
+    """:2384-2404, on the host: num_plot_points evenly spaced values of the true positive rate, the false
+    positive rate and the precision along an ordered sequence of True / False"""
+    with np.errstate(invalid='ignore', divide='ignore'):
+        tp_cumsum = np.cumsum(stat_has_mod)
+        tp_rate = tp_cumsum / tp_cumsum[-1]
+        fp_cumsum = np.cumsum(np.logical_not(stat_has_mod))
+        fp_rate = fp_cumsum / fp_cumsum[-1]
+        precision = tp_cumsum / np.arange(1, len(stat_has_mod) + 1, dtype=float)
+    tp_rate = tp_rate[np.linspace(0, tp_rate.shape[0] - 1, num_plot_points).astype(np.int64)]
+    fp_rate = fp_rate[np.linspace(0, fp_rate.shape[0] - 1, num_plot_points).astype(np.int64)]
+    precision = precision[np.linspace(0, precision.shape[0] - 1, num_plot_points + 1).astype(np.int64)][1:]
+    return tp_rate, fp_rate, precision
+
+
+def sampled_accuracy_rates(mod_stats, num_plot_points=ROC_PLOT_POINTS, engine=None, mod_name=None):
+    """compute_accuracy_rates of the entries ordered by (statistic, has_mod), the ordering and the cumulative counts
+    on the device: only the counts at the sampled ranks come back, the divisions are the reference's"""
+    mod_stats = _as_motif_stats(mod_stats)
+    n = len(mod_stats)
+    if n == 0:
+        raise ValueError('No statistics for modification %s' % (mod_name,))
+    rate_idx = np.linspace(0, n - 1, num_plot_points).astype(np.int64)
+    prec_idx = np.linspace(0, n - 1, num_plot_points + 1).astype(np.int64)[1:]
+    ranks = np.union1d(rate_idx, prec_idx)
+    tp_at, tp_total, n_nan = _engine(engine).roc_rank_counts(mod_stats.stats, mod_stats.has_mod, ranks)
+    if n_nan:
+        raise ValueError('NaN statistic')
+    tp_rate_at, tp_prec_at = tp_at[np.searchsorted(ranks, rate_idx)], tp_at[np.searchsorted(ranks, prec_idx)]
+    with np.errstate(invalid='ignore', divide='ignore'):
+        tp_rate = tp_rate_at / np.int64(tp_total)
+        fp_rate = (rate_idx + 1 - tp_rate_at) / np.int64(n - tp_total)
+        precision = tp_prec_at / (prec_idx + 1).astype(float)
+    return tp_rate, fp_rate, precision
+
+
+def prep_accuracy_rates(all_motif_stats, engine=None, summary=None):
+    """_plot_commands.py:60-82: the flat lists (tp rates, fp rates, precisions, names) that go into the ROC and
+    precision-recall plots, ROC_PLOT_POINTS per name.  summary (a dict): receives name -> (AUC, mean average
+    precision).  ValueError for a name without entries and for a NaN statistic."""
+    tp_rates, fp_rates, precisions, mod_names_for_r = [], [], [], []
+    for mod_name, mod_stats in all_motif_stats.items():
+        mod_tp_rate, mod_fp_rate, mod_precision = sampled_accuracy_rates(mod_stats, engine=engine, mod_name=mod_name)
+        if summary is not None:
+            summary[mod_name] = (compute_auc(mod_tp_rate, mod_fp_rate),
+                                 compute_mean_avg_precison(mod_tp_rate, mod_precision))
+        tp_rates.extend(mod_tp_rate)
+        fp_rates.extend(mod_fp_rate)
+        precisions.extend(mod_precision)
+        mod_names_for_r.extend([mod_name] * len(mod_tp_rate))
+    return tp_rates, fp_rates, precisions, mod_names_for_r
 
 
 # ---------------------------------------------------------------------------------------------
