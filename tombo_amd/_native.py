@@ -432,6 +432,24 @@ def _check_roc_rank_args(stats, has_mod, ranks):
     return np.ascontiguousarray(st), np.ascontiguousarray(hm).view(np.uint8), np.ascontiguousarray(rk)
 
 
+def _site_outputs(starts, ends, damp_counts):
+    """both site entries, tracks [starts[t], ends[t]) -> (pos_off, SiteFractions' frac .. n_stats, their C pointers)"""
+    pos_off = np.concatenate([[0], np.cumsum(ends - starts)]).astype(np.int64)
+    n_trk, n_pos = starts.shape[0], int(pos_off[-1])
+    frac = np.empty(n_pos, dtype=np.float64)
+    poss, cov, valid = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
+    damp = None if damp_counts is None else np.empty(n_pos, dtype=np.float64)
+    outs = (frac, poss, cov, valid, damp, np.zeros(n_trk, dtype=np.int64), np.zeros(n_trk, dtype=np.int64))
+    return pos_off, outs, tuple(_p(a, f64 if a is frac or a is damp else i64) for a in outs)
+
+
+def _roc_label_outputs(cap, n_counts, return_index):
+    """-> (stats, labels, record index or None, counts) of a ROC label entry and their pointers"""
+    outs = (np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.uint8),
+            np.empty(cap, dtype=np.int64) if return_index else None, np.zeros(n_counts, dtype=np.int64))
+    return outs, tuple(_p(a, t) for a, t in zip(outs, (f64, C.c_uint8, i64, i64)))
+
+
 def _site_other_form(form):
     """typed nulls and zeros for the arguments of tba_site_fractions that the form in use leaves out"""
     nd, ni = C.cast(None, C.POINTER(f64)), C.cast(None, C.POINTER(i64))
@@ -976,20 +994,14 @@ class Engine(object):
     def _site_fractions(self, form, trk_start, trk_end, z_args, win_args, n_stats, single_read_thresh,
                         lower_thresh, damp_counts, return_per_read):
         trk_start, trk_end = _i64(trk_start), _i64(trk_end)
-        pos_off = np.concatenate([[0], np.cumsum(trk_end - trk_start)]).astype(np.int64)
-        n_trk, n_pos = trk_start.shape[0], int(pos_off[-1])
-        frac = np.empty(n_pos, dtype=np.float64)
-        poss, cov, valid = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
-        counts, trk_stats = np.empty(n_trk, dtype=np.int64), np.empty(n_trk, dtype=np.int64)
-        damp = None if damp_counts is None else np.empty(n_pos, dtype=np.float64)
+        pos_off, outs, out_ptrs = _site_outputs(trk_start, trk_end, damp_counts)
         per_read = np.empty(n_stats, dtype=np.float64) if return_per_read else None
         self._check(self._L.tba_site_fractions(
-            self._h, C.c_int(form), i64(n_trk), _p(trk_start, i64), _p(trk_end, i64), *z_args, *win_args,
+            self._h, C.c_int(form), i64(trk_start.shape[0]), _p(trk_start, i64), _p(trk_end, i64), *z_args, *win_args,
             f64(float(single_read_thresh)), None if lower_thresh is None else (f64 * 1)(float(lower_thresh)),
-            None if damp_counts is None else (f64 * 2)(*damp_counts), _p(frac, f64), _p(poss, i64), _p(cov, i64),
-            _p(valid, i64), _p(damp, f64), _p(counts, i64), _p(trk_stats, i64), _p(per_read, f64)),
+            None if damp_counts is None else (f64 * 2)(*damp_counts), *out_ptrs, _p(per_read, f64)),
             'tba_site_fractions')
-        return SiteFractions(pos_off, frac, poss, cov, valid, damp, counts, trk_stats, per_read)
+        return SiteFractions(pos_off, *outs, per_read)
 
     def site_fractions_z(self, trk_start, trk_end, means, ref_means, ref_sds, off, read_track, read_pos,
                          fm_offset, floor_out, smallest_pval, single_read_thresh, lower_thresh=None,
@@ -1030,21 +1042,14 @@ class Engine(object):
         stored) -> SiteFractions (per_read None).  abs_rule: model_compare's |stat| >= single_read_thresh validity
         when no lower threshold is given.  `last_site_aggregate_kernel_ms`: device time of the call's kernels."""
         bs, be, off, rec = _check_site_aggregate_args(blk_start, blk_end, rec_off, records)
-        pos_off = np.concatenate([[0], np.cumsum(be - bs)]).astype(np.int64)
-        n_blk, n_pos = bs.shape[0], int(pos_off[-1])
-        frac = np.empty(n_pos, dtype=np.float64)
-        poss, cov, valid = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
-        counts, n_stats = np.zeros(n_blk, dtype=np.int64), np.zeros(n_blk, dtype=np.int64)
-        damp = None if damp_counts is None else np.empty(n_pos, dtype=np.float64)
-        ms = f64(0.0)
+        (pos_off, outs, out_ptrs), ms = _site_outputs(bs, be, damp_counts), f64(0.0)
         self._check(self._L.tba_site_aggregate(
-            self._h, i64(n_blk), _p(bs, i64), _p(be, i64), _p(off, i64), C.c_void_p(rec.ctypes.data),
+            self._h, i64(bs.shape[0]), _p(bs, i64), _p(be, i64), _p(off, i64), C.c_void_p(rec.ctypes.data),
             f64(float(single_read_thresh)), None if lower_thresh is None else (f64 * 1)(float(lower_thresh)),
-            C.c_int(int(bool(abs_rule))), None if damp_counts is None else (f64 * 2)(*damp_counts), _p(frac, f64),
-            _p(poss, i64), _p(cov, i64), _p(valid, i64), _p(damp, f64), _p(counts, i64), _p(n_stats, i64),
+            C.c_int(int(bool(abs_rule))), None if damp_counts is None else (f64 * 2)(*damp_counts), *out_ptrs,
             C.byref(ms)), 'tba_site_aggregate')
         self.last_site_aggregate_kernel_ms = ms.value
-        return SiteFractions(pos_off, frac, poss, cov, valid, damp, counts, n_stats, None)
+        return SiteFractions(pos_off, *outs, None)
 
     # ---- ROC / precision-recall (csrc/k_roc.h) ----
     def _roc_split(self, stats, labels, index, counts, return_index):
@@ -1065,33 +1070,28 @@ class Engine(object):
         bool[, record index int64]) of the kept records in record order.  `last_roc_kernel_ms`: kernel time."""
         minus, ss, s_off, seq, off, pos, stat, table, sets = _check_roc_motif_args(
             blk_minus, blk_seq_start, seq_off, seq_codes, rec_off, rec_pos, rec_stat, motifs)
-        n_mot, cap = table.shape[0], table.shape[0] * pos.shape[0]
-        o_stat, o_lab = np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.uint8)
-        o_idx = np.empty(cap, dtype=np.int64) if return_index else None
-        counts, ms = np.zeros(n_mot, dtype=np.int64), f64(0.0)
+        n_mot, ms = table.shape[0], f64(0.0)
+        outs, out_ptrs = _roc_label_outputs(n_mot * pos.shape[0], n_mot, return_index)
         self._check(self._L.tba_roc_motif_labels(
             self._h, i64(minus.shape[0]), _p(minus, C.c_uint8), _p(ss, i64), _p(s_off, i64), _p(seq, C.c_uint8),
             _p(off, i64), _p(pos, i64), _p(stat, f64), i64(n_mot), _p(table, i32), _p(sets, C.c_uint8),
-            C.c_int(0 if ctrl_label is None else 1), C.c_int(int(bool(ctrl_label))), _p(o_stat, f64),
-            _p(o_lab, C.c_uint8), _p(o_idx, i64), _p(counts, i64), C.byref(ms)), 'tba_roc_motif_labels')
+            C.c_int(0 if ctrl_label is None else 1), C.c_int(int(bool(ctrl_label))), *out_ptrs, C.byref(ms)),
+            'tba_roc_motif_labels')
         self.last_roc_kernel_ms = ms.value
-        return self._roc_split(o_stat, o_lab, o_idx, counts, return_index)
+        return self._roc_split(*outs, return_index)
 
     def roc_loc_labels(self, blk_loc, mod_locs, unmod_locs, rec_off, rec_pos, rec_stat, return_index=False):
         """tba_roc_loc_labels: block t owns the ascending slices mod_locs[blk_loc[t, 0]:blk_loc[t, 1]] and
         unmod_locs[blk_loc[t, 2]:blk_loc[t, 3]]; a record is kept when its position is in either, its label is
         whether it is in the first -> (stats, has_mod[, record index]) in record order"""
         loc, mod, unmod, off, pos, stat = _check_roc_loc_args(blk_loc, mod_locs, unmod_locs, rec_off, rec_pos, rec_stat)
-        cap = pos.shape[0]
-        o_stat, o_lab = np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.uint8)
-        o_idx = np.empty(cap, dtype=np.int64) if return_index else None
-        counts, ms = np.zeros(1, dtype=np.int64), f64(0.0)
+        (outs, out_ptrs), ms = _roc_label_outputs(pos.shape[0], 1, return_index), f64(0.0)
         self._check(self._L.tba_roc_loc_labels(
             self._h, i64(loc.shape[0]), _p(loc, i64), _p(mod, i64), i64(mod.shape[0]), _p(unmod, i64),
-            i64(unmod.shape[0]), _p(off, i64), _p(pos, i64), _p(stat, f64), _p(o_stat, f64), _p(o_lab, C.c_uint8),
-            _p(o_idx, i64), _p(counts, i64), C.byref(ms)), 'tba_roc_loc_labels')
+            i64(unmod.shape[0]), _p(off, i64), _p(pos, i64), _p(stat, f64), *out_ptrs, C.byref(ms)),
+            'tba_roc_loc_labels')
         self.last_roc_kernel_ms = ms.value
-        return self._roc_split(o_stat, o_lab, o_idx, counts, return_index)[0]
+        return self._roc_split(*outs, return_index)[0]
 
     def roc_rank_counts(self, stats, has_mod, ranks):
         """tba_roc_rank_counts -> (tp_at int64[len(ranks)], tp_total, n_nan): tp_at[j] = True labels among the

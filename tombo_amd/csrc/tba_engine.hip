@@ -115,7 +115,7 @@ struct tba_engine {
     // first consumer (k_remove_stalls; start discovery).  Both groups wait on memory most of their time
     // (SQ_WAIT_ANY 60-80 % of their wave cycles): together they fill what each leaves idle.
     hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_stalls = nullptr, ev_levels = nullptr, ev_st0 = nullptr, ev_st1 = nullptr, ev_skip0 = nullptr, ev_skip1 = nullptr, ev_trk0 = nullptr, ev_trk1 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_stalls = nullptr, ev_levels = nullptr, ev_st0 = nullptr, ev_st1 = nullptr, ev_skip0 = nullptr, ev_skip1 = nullptr;
     hipEvent_t ev[N_STAGE + 1] = {}; // ev[i], ev[i + 1]: around step i of the pipeline; ev[N_STEP]: its end, ev[SLOT_TOTAL]: its start
     float stage_ms[32] = {};
     bool have_model = false, have_batch = false, ran = false;
@@ -190,7 +190,7 @@ extern "C" int tba_engine_create(int device, tba_engine **out)
     if (const char *v = getenv("TBA_TB_WAVE_BELOW")) e->tb_wave_below = std::max<i64>(atoll(v), 0);
     HIP_TRY(hipStreamCreate(&e->stream));
     if (device < TBA_MAX_DEVICES) g_live_engines[device]++;
-    for (hipEvent_t *x : {&e->ev_fork, &e->ev_stalls, &e->ev_levels, &e->ev_st0, &e->ev_st1, &e->ev_skip0, &e->ev_skip1, &e->ev_trk0, &e->ev_trk1}) HIP_TRY(hipEventCreate(x));
+    for (hipEvent_t *x : {&e->ev_fork, &e->ev_stalls, &e->ev_levels, &e->ev_st0, &e->ev_st1, &e->ev_skip0, &e->ev_skip1}) HIP_TRY(hipEventCreate(x));
     for (int i = 0; i <= N_STAGE; i++) HIP_TRY(hipEventCreate(&e->ev[i]));
     *out = e;
     return 0;
@@ -204,7 +204,7 @@ extern "C" void tba_engine_destroy(tba_engine *e)
     if (e->stream2) (void)hipStreamSynchronize(e->stream2);
     e->release_all();
     for (int i = 0; i <= N_STAGE; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
-    for (hipEvent_t x : {e->ev_fork, e->ev_stalls, e->ev_levels, e->ev_st0, e->ev_st1, e->ev_skip0, e->ev_skip1, e->ev_trk0, e->ev_trk1}) if (x) (void)hipEventDestroy(x);
+    for (hipEvent_t x : {e->ev_fork, e->ev_stalls, e->ev_levels, e->ev_st0, e->ev_st1, e->ev_skip0, e->ev_skip1}) if (x) (void)hipEventDestroy(x);
     if (e->stream2) (void)hipStreamDestroy(e->stream2);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     if (e->device < TBA_MAX_DEVICES) g_live_engines[e->device]--;
@@ -1245,13 +1245,15 @@ extern "C" const char *tba_stage_name(int i) { return i < 0 || i >= N_STAGE ? ""
 // ---------------------------------------------------------------------------------------------
 // per-kernel entry points (tba_c_*): host buffers in, host buffers out, batch of one
 namespace {
-// The device scratch of one call, freed on return.  The first failure is kept (its code in `rc`,
-// its message through set_err) and turns every later step into a no-op, so an entry checks `rc`
-// once, after its buffers.  Copies block: inputs are on the device before the launches that read
-// them, outputs are read back after sync().
+// The device scratch of one call on its engine's device and stream, freed on return.  The first
+// failure is kept (its code in `rc`, its message through set_err) and turns every later step into
+// a no-op, so an entry checks `rc` once, after its buffers.  Copies block: inputs are on the device
+// before the launches that read them, outputs are read back after sync().
 struct Scratch {
     int rc = 0;
+    hipStream_t stream;
     std::vector<void *> bufs;
+    explicit Scratch(tba_engine *e) : stream(e->stream) { hip(hipSetDevice(e->device), "hipSetDevice(e->device)"); }
     ~Scratch() { for (void *p : bufs) (void)hipFree(p); }
     int hip(hipError_t err, const char *what)
     {
@@ -1270,26 +1272,31 @@ struct Scratch {
         bufs.push_back(p);
         return (T *)p;
     }
-    // n elements copied in from the host, followed by `pad` zeroed bytes
+    // n elements copied in from the host, followed by `pad` zeroed bytes; n == 0 never touches `host`
     template <class T> T *in(const T *host, size_t n, size_t pad = 0)
     {
         char *p = out<char>(n * sizeof(T) + pad);
         if (p && pad) hip(hipMemset(p + n * sizeof(T), 0, pad), "hipMemset");
-        if (p && !rc) hip(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
+        if (p && n && !rc) hip(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
         return rc ? nullptr : (T *)p;
     }
+    // `bytes` of p zeroed on the stream, before the launches that follow; returns rc
+    int zero(void *p, size_t bytes)
+    {
+        return rc || !p ? rc : hip(hipMemsetAsync(p, 0, bytes, stream), "hipMemsetAsync");
+    }
     // a zeroed status word for a kernel of k_cabi.h that reports one (read back by sync)
-    i32 *status(hipStream_t s)
+    i32 *status()
     {
         i32 *p = out<i32>(1);
-        if (p) hip(hipMemsetAsync(p, 0, 4, s), "hipMemsetAsync");
+        zero(p, 4);
         return p;
     }
     // after the launches: their errors, then the stream.  Returns rc after a failure, else the
     // status word (0 without one).
-    int sync(hipStream_t s, const i32 *d_status = nullptr)
+    int sync(const i32 *d_status = nullptr)
     {
-        if (rc || hip(hipGetLastError(), "hipGetLastError") || hip(hipStreamSynchronize(s), "hipStreamSynchronize")) return rc;
+        if (rc || hip(hipGetLastError(), "hipGetLastError") || hip(hipStreamSynchronize(stream), "hipStreamSynchronize")) return rc;
         i32 st = 0;
         if (d_status && get(&st, d_status, 1)) return rc;
         return st;
@@ -1298,6 +1305,29 @@ struct Scratch {
     template <class T> int get(T *host, const T *dev, size_t n)
     {
         return rc ? rc : hip(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost), "hipMemcpy");
+    }
+};
+
+// Kernel time of one span of launches on the call's stream: from construction to stop(), through
+// two events made for the call and destroyed with it.  Switched off, or after a failure in `sc`,
+// every step is a no-op and ms() is 0.
+struct KernelTimer {
+    Scratch &sc;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool stopped = false;
+    explicit KernelTimer(Scratch &sc_, bool on = true) : sc(sc_)
+    {
+        if (!on || sc.rc || sc.hip(hipEventCreate(&ev0), "hipEventCreate") || sc.hip(hipEventCreate(&ev1), "hipEventCreate")) return;
+        sc.hip(hipEventRecord(ev0, sc.stream), "hipEventRecord");
+    }
+    ~KernelTimer() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+    void stop() { stopped = ev1 && !sc.rc && !sc.hip(hipEventRecord(ev1, sc.stream), "hipEventRecord"); }
+    // the span's time; waits for its end, so it is safe before sc.sync() too (and costs nothing after it)
+    double ms()
+    {
+        float t = 0;
+        if (!stopped || sc.rc || hipEventSynchronize(ev1) != hipSuccess || hipEventElapsedTime(&t, ev0, ev1) != hipSuccess) return 0.0;
+        return t;
     }
 };
 static unsigned grid_for(i64 n) { return (unsigned)std::min<i64>(std::max<i64>((n + 255) / 256, 1), 4096); }
@@ -1317,7 +1347,7 @@ static int run_direct_dp(tba_engine *e, DpJob hj, int cpl, i64 n_rows, i64 W, i6
 {
     const i64 stride = (i64)cpl * 64;            // forward rows
     const i64 mstride = mv_class_rowb(cpl);      // packed 2-bit move rows
-    Scratch sc;
+    Scratch sc(e);
     double *d_fwd = sc.out<double>((size_t)(n_rows + 1) * stride);
     unsigned char *d_mv = sc.out<unsigned char>((size_t)(n_rows + 1) * mstride);
     hj.fwd_out = d_fwd;
@@ -1328,7 +1358,7 @@ static int run_direct_dp(tba_engine *e, DpJob hj, int cpl, i64 n_rows, i64 W, i6
     // the kernel needs *some* ReadState / DevParams to bind its references to
     if (e->d_rs.ensure(sizeof(ReadState)) || e->d_dp.ensure(sizeof(DevParams))) return TBA_E_NOMEM;
     launch_direct(e, cpl, d_job);
-    if (sc.sync(e->stream) || sc.get(&hj, d_job, 1)) return sc.rc;
+    if (sc.sync() || sc.get(&hj, d_job, 1)) return sc.rc;
     if (hj.status != TBA_OK) return hj.status;
     std::vector<unsigned char> mv((size_t)(n_rows + 1) * mstride);
     std::vector<double> fw((size_t)(n_rows + 1) * stride);
@@ -1370,11 +1400,10 @@ extern "C" int tba_c_adaptive_banded_forward_pass_z(tba_engine *e, double *fwd_p
     for (i64 i = 0; i < start_seq_pos; i++) // the given (static) rows' band starts index the events
         if (event_starts[i] < 0 || event_starts[i] >= n_events || (i > 0 && event_starts[i] < event_starts[i - 1]))
             return set_err(TBA_E_ARG, "event_starts must be non-decreasing inside [0, n_events)");
-    HIP_TRY(hipSetDevice(e->device));
     const size_t n_z = (size_t)(n_bases - start_seq_pos) * (size_t)bandwidth;
     DpJob j;
     memset(&j, 0, sizeof(j));
-    Scratch sc;
+    Scratch sc(e);
     j.z_out = z_scores && n_z ? sc.out<double>(n_z) : nullptr;
     j.ev = sc.in(event_means, n_events);
     j.mu = sc.in(r_ref_means, n_bases);
@@ -1416,10 +1445,9 @@ extern "C" int tba_c_banded_forward_pass(tba_engine *e, const double *shifted_z_
     for (i64 i = 0; i < n_bases; i++)
         if (event_starts[i] < 0 || (i > 0 && event_starts[i] < event_starts[i - 1]))
             return set_err(TBA_E_ARG, "event_starts must be non-negative and non-decreasing");
-    HIP_TRY(hipSetDevice(e->device));
     DpJob j;
     memset(&j, 0, sizeof(j));
-    Scratch sc;
+    Scratch sc(e);
     j.zmat = sc.in(shifted_z_scores, (size_t)n_bases * bandwidth);
     j.starts = sc.in(event_starts, n_bases);
     if (sc.rc) return sc.rc;
@@ -1439,19 +1467,18 @@ extern "C" int tba_c_banded_traceback(tba_engine *e, const int64_t *fwd_pass_tb,
     if (!e || !fwd_pass_tb || !event_starts || !seq_poss || n_bases < 1 || bandwidth < 1 ||
         band_pos < 0 || band_pos >= bandwidth)
         return set_err(TBA_E_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(e->device));
     const size_t cells = (size_t)(n_bases + 1) * bandwidth;
     std::vector<unsigned char> mv(cells);
     for (size_t i = 0; i < cells; i++) mv[i] = (unsigned char)fwd_pass_tb[i];
-    Scratch sc;
+    Scratch sc(e);
     const unsigned char *d_mv = sc.in(mv.data(), cells);
     const i64 *d_st = sc.in(event_starts, n_bases);
     i64 *d_out = sc.out<i64>(n_bases + 1);
-    i32 *d_status = sc.status(e->stream);
+    i32 *d_status = sc.status();
     if (sc.rc) return sc.rc;
     k_c_traceback<<<1, 64, 0, e->stream>>>(d_mv, bandwidth, n_bases, bandwidth, d_st, band_pos,
                                            band_boundary_thresh, d_out, d_status);
-    const int st = sc.sync(e->stream, d_status);
+    const int st = sc.sync(d_status);
     if (st == TBA_OK) return sc.get(seq_poss, d_out, n_bases + 1);
     return st;
 }
@@ -1461,14 +1488,13 @@ extern "C" int tba_c_base_z_scores(tba_engine *e, const double *b_sig, int64_t n
 {
     if (!e || !b_sig || !out || n < 0) return set_err(TBA_E_ARG, "bad arguments");
     if (n == 0) return TBA_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_in = sc.in(b_sig, n);
     double *d_out = sc.out<double>(n);
     if (sc.rc) return sc.rc;
     k_c_base_z_scores<<<grid_for(n), 256, 0, e->stream>>>(d_in, n, ref_mean, ref_sd,
                                                           do_winsorize_z, max_half_z_score, d_out);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(out, d_out, n);
 }
 
@@ -1479,7 +1505,6 @@ extern "C" int tba_c_new_means(tba_engine *e, const double *norm_signal, int64_t
         return set_err(TBA_E_ARG, "bad arguments");
     if (n_segs == 0) return TBA_OK;
     if (int rc = check_segs(new_segs, n_segs, n_sig)) return rc;
-    HIP_TRY(hipSetDevice(e->device));
     // the batch pipeline's own kernel on a one-read batch (k_event_means: wave-cooperative, software-
     // pipelined segment sums, k_select.h) -- the slice size picked as the batch pipeline picks it,
     // by the mean segment length (+ 64 bytes: a 16-byte access may touch the element past an odd end)
@@ -1488,7 +1513,7 @@ extern "C" int tba_c_new_means(tba_engine *e, const double *norm_signal, int64_t
     r.n_raw = n_sig; r.n_cpts = n_segs + 1; r.status = TBA_OK;
     DevParams dp;
     memset(&dp, 0, sizeof(dp));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_sig = sc.in(norm_signal, n_sig, 64);
     const i64 *d_segs = sc.in(new_segs, n_segs + 1);
     double *d_out = sc.out<double>(n_segs);
@@ -1500,7 +1525,7 @@ extern "C" int tba_c_new_means(tba_engine *e, const double *norm_signal, int64_t
         k_event_means<double, 1280><<<dim3(g, 1), 256, 0, e->stream>>>(d_rs, d_dp, d_sig, d_segs, d_out, 0);
     else
         k_event_means<double><<<dim3(g, 1), 256, 0, e->stream>>>(d_rs, d_dp, d_sig, d_segs, d_out, 0);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(means, d_out, n_segs);
 }
 
@@ -1509,13 +1534,12 @@ extern "C" int tba_c_apply_outlier_thresh(tba_engine *e, const double *sig, int6
 {
     if (!e || !sig || !out || n < 0) return set_err(TBA_E_ARG, "bad arguments");
     if (n == 0) return TBA_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_in = sc.in(sig, n);
     double *d_out = sc.out<double>(n);
     if (sc.rc) return sc.rc;
     k_c_clip<<<grid_for(n), 256, 0, e->stream>>>(d_in, n, lower_lim, upper_lim, d_out);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(out, d_out, n);
 }
 
@@ -1526,7 +1550,6 @@ static int c_valid_cpts(tba_engine *e, const double *sig, int64_t n, int64_t min
     if (!e || !sig || !cpts || n < 1 || min_base_obs < 1 || width < 1 || num_cpts < 1)
         return set_err(TBA_E_ARG, "bad arguments");
     if ((ttest ? n - 2 * width : n + 1 - 2 * width) <= 0) return TBA_INTERNAL;
-    HIP_TRY(hipSetDevice(e->device));
     // The score-free kernels of the batch pipeline (k_detect.h) when the engine's dispatch sends a
     // batch of one read through the throughput form (tba_engine_set_dispatch(0, ...): the parity tests
     // of this entry in both forms) and for the t-test scores at RNA's defaults; the kernels that keep
@@ -1543,7 +1566,7 @@ static int c_valid_cpts(tba_engine *e, const double *sig, int64_t n, int64_t min
     DevParams dp;
     memset(&dp, 0, sizeof(dp));
     dp.p.running_stat_width = width; dp.p.min_obs_per_base = min_base_obs;
-    Scratch sc;
+    Scratch sc(e);
     const double *d_sig = sc.in(sig, n);
     double *d_csum = sc.out<double>(n + 1);
     double *d_score = sc.out<double>(n);
@@ -1555,12 +1578,12 @@ static int c_valid_cpts(tba_engine *e, const double *sig, int64_t n, int64_t min
     hipStream_t s = e->stream;
     const unsigned g = grid_for(n) > 128 ? 128 : grid_for(n);
     if (detect) {
-        Scratch norm; // (released at the end of this scope, before the launches below)
+        Scratch norm(e); // (released at the end of this scope, before the launches below)
         double *d_norm = norm.out<double>(n + 2 + 8); // (+ 64 bytes past the n + 2 values)
         if (norm.rc) return norm.rc;
         k_detect<2, double><<<1, 256, 0, s>>>(d_rs, 1, d_dp, d_sig, d_norm, d_csum, d_score, n);
         k_pick<<<1, SEL_NT, 0, s>>>(d_rs, d_dp, d_csum, d_score, d_cpts, 0);
-        if (norm.sync(s)) return norm.rc;
+        if (norm.sync()) return norm.rc;
     } else if (detect_tt) {
         if (width == 12) k_detect_tt<5, 12, double><<<1, SEL_NT, 0, s>>>(d_rs, d_dp, d_sig, d_csum, d_score);
         else k_detect_tt<5, 0, double><<<1, SEL_NT, 0, s>>>(d_rs, d_dp, d_sig, d_csum, d_score);
@@ -1577,7 +1600,7 @@ static int c_valid_cpts(tba_engine *e, const double *sig, int64_t n, int64_t min
     }
     launch_peaks(min_base_obs, 1, s, d_rs, d_dp, d_score, d_state, d_csum, d_cpts, ttest, only_flagged,
                  ttest ? TBA_ED_FORM_TTEST_PEAKS : TBA_ED_FORM_SCORES_PEAKS);
-    if (sc.sync(s) || sc.get(&r, d_rs, 1)) return sc.rc;
+    if (sc.sync() || sc.get(&r, d_rs, 1)) return sc.rc;
     if (r.status == TBA_OK && sc.get(cpts, d_cpts, num_cpts)) return sc.rc;
     e->last_c_ed_form = r.ed_form;
     return r.status;
@@ -1605,15 +1628,14 @@ extern "C" int tba_c_new_mean_stds(tba_engine *e, const double *norm_signal, int
         return set_err(TBA_E_ARG, "bad arguments");
     if (n_segs == 0) return TBA_OK;
     if (int rc = check_segs(new_segs, n_segs, n_sig)) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_sig = sc.in(norm_signal, n_sig);
     const i64 *d_segs = sc.in(new_segs, n_segs + 1);
     double *d_m = sc.out<double>(n_segs);
     double *d_s = sc.out<double>(n_segs);
     if (sc.rc) return sc.rc;
     k_c_new_mean_stds<<<grid_for(n_segs), 256, 0, e->stream>>>(d_sig, d_segs, n_segs, d_m, d_s);
-    if (sc.sync(e->stream) || sc.get(means, d_m, n_segs)) return sc.rc;
+    if (sc.sync() || sc.get(means, d_m, n_segs)) return sc.rc;
     return sc.get(stds, d_s, n_segs);
 }
 
@@ -1625,14 +1647,13 @@ extern "C" int tba_c_compute_slopes(tba_engine *e, const double *r_event_means,
     if (n < 2) return TBA_OK;
     if (n > 65535) return set_err(TBA_E_ARG, "too many points");
     const size_t ns = (size_t)n * (size_t)(n - 1) / 2;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_ev = sc.in(r_event_means, n);
     const double *d_md = sc.in(r_model_means, n);
     double *d_out = sc.out<double>(ns);
     if (sc.rc) return sc.rc;
     k_c_compute_slopes<<<dim3((unsigned)(n - 1)), 256, 0, e->stream>>>(d_ev, d_md, n, max_slope, d_out);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(slopes, d_out, ns);
 }
 
@@ -1649,8 +1670,7 @@ extern "C" int tba_c_reg_z_scores(tba_engine *e, const double *r_sig, int64_t n_
     if (reg_start < 0 || reg_len <= 0 || reg_end > n_bases || reg_end >= n_b_starts ||
         max_base_shift < 0)
         return set_err(TBA_E_ARG, "region outside the bases / base starts");
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_sig = sc.in(r_sig, n_sig);
     const double *d_mu = sc.in(r_ref_means, n_bases);
     const double *d_sd = sc.in(r_ref_sds, n_bases);
@@ -1659,14 +1679,14 @@ extern "C" int tba_c_reg_z_scores(tba_engine *e, const double *r_sig, int64_t n_
     i64 *d_se = sc.out<i64>(reg_len);
     i64 *d_off = sc.out<i64>(reg_len + 1);
     double *d_z = sc.out<double>(z_cap);
-    i32 *d_st = sc.status(e->stream);
+    i32 *d_st = sc.status();
     if (sc.rc) return sc.rc;
     k_c_reg_bounds<<<1, 64, 0, e->stream>>>(d_bs, reg_start, reg_end, max_base_shift,
         min_obs_per_base, d_ss, d_se, d_off);
     k_c_reg_z<<<dim3((unsigned)reg_len), 64, 0, e->stream>>>(d_sig, n_sig, d_mu, d_sd, reg_start,
         d_ss, d_se, d_off, z_cap, do_winsorize_z, max_half_z_score, d_z, d_st);
     std::vector<i64> ss(reg_len), se(reg_len);
-    const int st = sc.sync(e->stream, d_st);
+    const int st = sc.sync(d_st);
     if (sc.rc || sc.get(ss.data(), d_ss, reg_len) || sc.get(se.data(), d_se, reg_len) ||
         sc.get(z_off, d_off, reg_len + 1))
         return sc.rc;
@@ -1688,8 +1708,7 @@ extern "C" int tba_c_base_forward_pass(tba_engine *e, const double *b_data, int6
         return set_err(TBA_E_ARG, "bad arguments");
     const i64 b_len = b_end - b_start, plen = prev_b_end - prev_b_start;
     if (b_len <= 0 || plen <= 0) return set_err(TBA_E_ARG, "empty base interval");
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_b = sc.in(b_data, b_len);
     const double *d_pb = sc.in(prev_b_data, plen);
     const double *d_pf = sc.in(prev_b_fwd_data, plen);
@@ -1697,11 +1716,11 @@ extern "C" int tba_c_base_forward_pass(tba_engine *e, const double *b_data, int6
     double *d_cum = sc.out<double>(plen);
     double *d_f = sc.out<double>(b_len);
     i64 *d_l = sc.out<i64>(b_len);
-    i32 *d_st = sc.status(e->stream);
+    i32 *d_st = sc.status();
     if (sc.rc) return sc.rc;
     k_c_base_forward_pass<<<1, 64, 0, e->stream>>>(d_b, b_start, b_end, d_pb, prev_b_start, prev_b_end,
         d_pf, d_pl, min_obs_per_base, d_cum, d_f, d_l, d_st);
-    if (int st = sc.sync(e->stream, d_st)) return st;
+    if (int st = sc.sync(d_st)) return st;
     if (sc.get(b_fwd_data, d_f, b_len)) return sc.rc;
     return sc.get(b_last_diag, d_l, b_len);
 }
@@ -1712,16 +1731,15 @@ extern "C" int tba_c_base_traceback(tba_engine *e, const double *curr_b_data, in
 {
     if (!e || !curr_b_data || !next_b_data || !sig_pos || curr_len <= 0 || next_len <= 0)
         return set_err(TBA_E_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_c = sc.in(curr_b_data, curr_len);
     const double *d_n = sc.in(next_b_data, next_len);
     i64 *d_out = sc.out<i64>(1);
-    i32 *d_st = sc.status(e->stream);
+    i32 *d_st = sc.status();
     if (sc.rc) return sc.rc;
     k_c_base_traceback<<<1, 64, 0, e->stream>>>(d_c, curr_len, curr_start, d_n, next_len, next_start,
         next_end, sig_start, min_obs_per_base, d_out, d_st);
-    if (int st = sc.sync(e->stream, d_st)) return st;
+    if (int st = sc.sync(d_st)) return st;
     return sc.get(sig_pos, d_out, 1);
 }
 
@@ -1751,8 +1769,7 @@ extern "C" int tba_llh_ratio_windows(tba_engine *e, int kind, const double *mean
         return set_err(TBA_E_ARG, "bad arguments");
     if (n_windows == 0) return TBA_OK;
     if (const int rc = check_windows(kind, starts, n_windows, width, n_values)) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_m = sc.in(means, n_values);
     const double *d_r = sc.in(ref_means, n_values);
     const double *d_a = sc.in(alt_means, n_values);
@@ -1763,7 +1780,7 @@ extern "C" int tba_llh_ratio_windows(tba_engine *e, int kind, const double *mean
     if (sc.rc) return sc.rc;
     k_c_llh_windows<<<grid_for(n_windows), 256, 0, e->stream>>>(kind, d_m, d_r, d_a, d_rv, d_av, width,
         d_s, n_windows, par ? par[0] : 0.0, par ? par[1] : 0.0, par ? par[2] : 0.0, d_o);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(out, d_o, n_windows);
 }
 
@@ -1778,8 +1795,7 @@ extern "C" int tba_read_pvals(tba_engine *e, const double *means, const double *
     if (const int rc = check_csr_off(off, n_reads)) return rc;
     const i64 total = off[n_reads];
     if (total == 0) return TBA_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_m = sc.in(means, total);
     const double *d_r = sc.in(ref_means, total);
     const double *d_s = sc.in(ref_sds, total);
@@ -1788,7 +1804,7 @@ extern "C" int tba_read_pvals(tba_engine *e, const double *means, const double *
     if (sc.rc) return sc.rc;
     k_read_pvals<<<grid_for(total), 256, 0, e->stream>>>(d_m, d_r, d_s, d_off, n_reads, total, fm_offset,
         floor_out, smallest_pval, d_o);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(pvals, d_o, total);
 }
 
@@ -1805,19 +1821,27 @@ struct Pileup {
     double *levels = nullptr;
 };
 
-// the levels of every position sorted in place, one kernel per class of pileup size (a failure stays in sc.rc)
-static void grp_sort_levels(tba_engine *e, Scratch &sc, const Pileup &P)
+// Segments of `levels` (sizes cov, starts lv_off) sorted in place, one kernel per size class.  The classify
+// kernel in front has filled the three lists of segments (`stride` apart) and their three lengths cls.
+static void launch_sort_classes(hipStream_t s, const i64 *lists, i64 stride, const u32 *cls, const i32 *cov,
+                                const i64 *lv_off, double *levels)
+{
+    k_grp_sort_wave<<<1024, 256, 0, s>>>(lists, cls, cov, lv_off, levels);
+    k_grp_sort_wg<<<1024, 256, 0, s>>>(lists + stride, cls + 1, cov, lv_off, levels, 0);
+    k_grp_sort_wg<<<256, 256, 0, s>>>(lists + 2 * stride, cls + 2, cov, lv_off, levels, 1);
+}
+
+// the levels of every position sorted in place (a failure stays in sc.rc)
+static void grp_sort_levels(Scratch &sc, const Pileup &P)
 {
     i64 *lists = sc.out<i64>(6 * P.a.n_pos);
     u32 *cls = sc.out<u32>(3);
-    if (sc.rc || sc.hip(hipMemsetAsync(cls, 0, 3 * sizeof(u32), e->stream), "hipMemsetAsync")) return;
-    k_grp_classify<<<grid_for(2 * P.a.n_pos), 256, 0, e->stream>>>(P.a.n_pos, P.cov, P.out_idx, lists, cls);
-    k_grp_sort_wave<<<1024, 256, 0, e->stream>>>(lists, cls, P.cov, P.lv_off, P.levels);
-    k_grp_sort_wg<<<1024, 256, 0, e->stream>>>(lists + 2 * P.a.n_pos, cls + 1, P.cov, P.lv_off, P.levels, 0);
-    k_grp_sort_wg<<<256, 256, 0, e->stream>>>(lists + 4 * P.a.n_pos, cls + 2, P.cov, P.lv_off, P.levels, 1);
+    if (sc.zero(cls, 3 * sizeof(u32))) return;
+    k_grp_classify<<<grid_for(2 * P.a.n_pos), 256, 0, sc.stream>>>(P.a.n_pos, P.cov, P.out_idx, lists, cls);
+    launch_sort_classes(sc.stream, lists, 2 * P.a.n_pos, cls, P.cov, P.lv_off, P.levels);
 }
 
-static int grp_pileup(tba_engine *e, Scratch &sc, Pileup &P, i64 fm, i64 min_reads, int two_groups,
+static int grp_pileup(Scratch &sc, Pileup &P, i64 fm, i64 min_reads, int two_groups,
     i64 min_run, bool sort, i64 n_regions, const int64_t *reg_start, const int64_t *reg_end,
     const int8_t *reg_strand, const int64_t *reg_read_off, i64 n_reads, const int64_t *read_start,
     const int8_t *read_strand, const int8_t *read_ctrl, const int64_t *read_off, const double *means)
@@ -1855,7 +1879,7 @@ static int grp_pileup(tba_engine *e, Scratch &sc, Pileup &P, i64 fm, i64 min_rea
     a.read_off = sc.in(read_off, n_reads + 1);
     a.read_strand = sc.in(read_strand, n_reads);
     a.read_ctrl = read_ctrl ? sc.in(read_ctrl, n_reads) : nullptr;
-    if (!read_ctrl) { int8_t *z = sc.out<int8_t>(n_reads); if (z) sc.hip(hipMemsetAsync(z, 0, n_reads, e->stream), "hipMemsetAsync"); a.read_ctrl = z; }
+    if (!read_ctrl) { int8_t *z = sc.out<int8_t>(n_reads); sc.zero(z, n_reads); a.read_ctrl = z; }
     a.means = sc.in(means, n_means);
     P.cov = sc.out<i32>(2 * n_pos);
     P.run_a = sc.out<i32>(n_pos);
@@ -1865,11 +1889,11 @@ static int grp_pileup(tba_engine *e, Scratch &sc, Pileup &P, i64 fm, i64 min_rea
     P.counts = sc.out<i64>(n_regions);
     P.levels = sc.out<double>(n_lv);
     if (sc.rc) return sc.rc;
-    k_grp_pileup<false><<<grid_for(n_pos), 256, 0, e->stream>>>(a, P.cov, nullptr, nullptr);
-    k_grp_scan<<<(unsigned)n_regions, 64, 0, e->stream>>>(a, P.cov, min_reads, two_groups, min_run,
+    k_grp_pileup<false><<<grid_for(n_pos), 256, 0, sc.stream>>>(a, P.cov, nullptr, nullptr);
+    k_grp_scan<<<(unsigned)n_regions, 64, 0, sc.stream>>>(a, P.cov, min_reads, two_groups, min_run,
         P.lv_off, P.run_a, P.run_b, P.out_idx, P.counts);
-    k_grp_pileup<true><<<grid_for(n_pos), 256, 0, e->stream>>>(a, P.cov, P.lv_off, P.levels);
-    if (sort) grp_sort_levels(e, sc, P);
+    k_grp_pileup<true><<<grid_for(n_pos), 256, 0, sc.stream>>>(a, P.cov, P.lv_off, P.levels);
+    if (sort) grp_sort_levels(sc, P);
     return sc.hip(hipGetLastError(), "launch");
 }
 }  // namespace
@@ -1887,10 +1911,9 @@ extern "C" int tba_group_level_stats(tba_engine *e, int stat_kind, int return_p,
         !out_cov || !out_ctrl_cov || !out_counts)
         return set_err(TBA_E_ARG, "bad arguments");
     if (n_regions == 0) return TBA_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     Pileup P;
-    if (const int rc = grp_pileup(e, sc, P, fm_offset, min_test_reads, 1, 2 * fm_offset + 1, true,
+    if (const int rc = grp_pileup(sc, P, fm_offset, min_test_reads, 1, 2 * fm_offset + 1, true,
             n_regions, reg_start, reg_end, reg_strand, reg_read_off, n_reads, read_start, read_strand,
             read_ctrl, read_off, means))
         return rc;
@@ -1902,7 +1925,7 @@ extern "C" int tba_group_level_stats(tba_engine *e, int stat_kind, int return_p,
         P.out_idx, P.levels, raw);
     k_grp_window<<<grid_for(n_pos), 256, 0, e->stream>>>(P.a, return_p, smallest_pval, P.cov, P.run_a,
         P.run_b, P.out_idx, raw, d_stats, d_poss, d_cov, d_ccov);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     // the compacted outputs of region r start at its first extended position (unused tails are
     // left as they are)
     if (sc.get(out_counts, P.counts, n_regions) || sc.get(out_stats, d_stats, n_pos) ||
@@ -1923,10 +1946,9 @@ extern "C" int tba_reads_ref_levels(tba_engine *e, int est_mean, int64_t fm_offs
         !means || !out_means || !out_sds || !out_cov || (!prior_means) != (!prior_sds))
         return set_err(TBA_E_ARG, "bad arguments");
     if (n_regions == 0) return TBA_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     Pileup P;
-    if (const int rc = grp_pileup(e, sc, P, fm_offset, min_test_reads, 0, 1, false, n_regions, reg_start,
+    if (const int rc = grp_pileup(sc, P, fm_offset, min_test_reads, 0, 1, false, n_regions, reg_start,
             reg_end, reg_strand, reg_read_off, n_reads, read_start, read_strand, nullptr, read_off, means))
         return rc;
     const i64 n_pos = P.a.n_pos;
@@ -1937,15 +1959,62 @@ extern "C" int tba_reads_ref_levels(tba_engine *e, int est_mean, int64_t fm_offs
     if (sc.rc) return sc.rc;
     // moments in read order first, then the sort for the median
     k_ref_moments<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, P.cov, P.lv_off, P.out_idx, P.levels, mean, sd);
-    if (!est_mean) grp_sort_levels(e, sc, P);
+    if (!est_mean) grp_sort_levels(sc, P);
     k_ref_finish<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, est_mean, P.cov, P.lv_off, P.out_idx,
         P.levels, mean, sd, d_pm, d_ps, prior_w_mean, prior_w_sd, d_m, d_s, d_c);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     if (sc.get(out_means, d_m, n_pos) || sc.get(out_sds, d_s, n_pos)) return sc.rc;
     return sc.get(out_cov, d_c, n_pos);
 }
 
 // ---- per-site modified fractions (k_site.h): compute_reg_stats for a batch of tracks -----------
+namespace {
+// The collation both site entries share: the tracks and their counters on the device, the per-site outputs,
+// k_site_finish over them and the read-back.  An entry zeroes the counters, runs its own kernels that fill
+// them, then finish(); a failure stays in sc.rc.
+struct SiteCollate {
+    Scratch &sc;
+    SiteArgs a{};
+    i64 n_pos;
+    double damp_num = 0.0, damp_den = 0.0;
+    double *d_frac, *d_damp = nullptr;
+    i64 *d_pos, *d_cov, *d_valid, *d_counts, *d_ns;
+    SiteCollate(Scratch &sc_, i64 n_tracks, const int64_t *starts, const std::vector<i64> &pos_off, double single_read_thresh,
+                const double *lower_thresh, int form, const double *damp_counts) : sc(sc_), n_pos(pos_off[n_tracks])
+    {
+        a.n_tracks = n_tracks;
+        a.trk_start = sc.in(starts, n_tracks);
+        a.pos_off = sc.in(pos_off.data(), n_tracks + 1);
+        a.valid_mode = lower_thresh ? 0 : form == 1 ? 1 : 2;
+        a.single = single_read_thresh;
+        a.lower = lower_thresh ? *lower_thresh : 0.0;
+        a.cnt = sc.out<i32>(3 * n_pos);
+        d_frac = sc.out<double>(n_pos);
+        if (damp_counts) { d_damp = sc.out<double>(n_pos); damp_num = damp_counts[0]; damp_den = damp_counts[0] + damp_counts[1]; }
+        d_pos = sc.out<i64>(n_pos); d_cov = sc.out<i64>(n_pos); d_valid = sc.out<i64>(n_pos);
+        d_counts = sc.out<i64>(n_tracks); d_ns = sc.out<i64>(n_tracks);
+    }
+    int zero_counters() { return sc.zero(a.cnt, 3 * n_pos * sizeof(i32)); }
+    void finish()
+    {
+        if (sc.rc) return;
+        k_site_finish<<<(unsigned)a.n_tracks, 64, 0, sc.stream>>>(a, damp_num, damp_den, d_frac, d_pos, d_cov, d_valid,
+            d_damp, d_counts, d_ns);
+    }
+    // after sc.sync(): the compacted outputs of track t start at its first position (unused tails are left
+    // as they are); returns rc
+    int read_back(double *out_frac, int64_t *out_pos, int64_t *out_cov, int64_t *out_valid_cov, double *out_damp_frac,
+                  int64_t *out_counts, int64_t *out_n_stats)
+    {
+        if (sc.get(out_counts, d_counts, a.n_tracks) || sc.get(out_n_stats, d_ns, a.n_tracks) ||
+            sc.get(out_frac, d_frac, n_pos) || sc.get(out_pos, d_pos, n_pos) ||
+            sc.get(out_cov, d_cov, n_pos) || sc.get(out_valid_cov, d_valid, n_pos))
+            return sc.rc;
+        return d_damp ? sc.get(out_damp_frac, d_damp, n_pos) : sc.rc;
+    }
+};
+} // namespace
+
 extern "C" int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, const int64_t *trk_start,
     const int64_t *trk_end, const double *means, const double *ref_means, const double *ref_sds,
     const int64_t *off, int64_t n_reads, const int64_t *read_track, const int64_t *read_pos,
@@ -1974,7 +2043,6 @@ extern "C" int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, con
         if (trk_end[t] < trk_start[t]) return set_err(TBA_E_ARG, "bad track");
         pos_off[t + 1] = pos_off[t] + (trk_end[t] - trk_start[t]);
     }
-    const i64 n_pos = pos_off[n_tracks];
     const i64 total = form == 0 && n_reads > 0 ? off[n_reads] : 0;
     if (form == 0) {
         if (const int rc = check_csr_off(off, n_reads)) return rc;
@@ -1993,17 +2061,10 @@ extern "C" int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, con
                 return set_err(TBA_E_ARG, "statistic position outside its track");
         }
     }
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
-    SiteArgs a{};
-    a.n_tracks = n_tracks;
-    a.trk_start = sc.in(trk_start, n_tracks);
-    a.pos_off = sc.in(pos_off.data(), n_tracks + 1);
-    a.valid_mode = lower_thresh ? 0 : form == 1 ? 1 : 2;
-    a.single = single_read_thresh;
-    a.lower = lower_thresh ? *lower_thresh : 0.0;
-    a.cnt = sc.out<i32>(3 * n_pos);
-    if (a.cnt) sc.hip(hipMemsetAsync(a.cnt, 0, 3 * n_pos * sizeof(i32), e->stream), "hipMemsetAsync");
+    Scratch sc(e);
+    SiteCollate S(sc, n_tracks, trk_start, pos_off, single_read_thresh, lower_thresh, form, damp_counts);
+    const SiteArgs &a = S.a;
+    S.zero_counters();
     double *d_pr = nullptr;
     const i64 n_stats = form == 0 ? total : n_windows;
     if (form == 0 && total > 0) {
@@ -2037,21 +2098,9 @@ extern "C" int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, con
         k_site_win<<<grid_for(n_windows), 256, 0, e->stream>>>(a, kind, d_m, d_r, d_a, d_rv, d_av, width,
             d_st, n_windows, par ? par[0] : 0.0, par ? par[1] : 0.0, par ? par[2] : 0.0, d_wt, d_wp, d_pr);
     }
-    double *d_frac = sc.out<double>(n_pos), *d_damp = damp_counts ? sc.out<double>(n_pos) : nullptr;
-    i64 *d_pos = sc.out<i64>(n_pos), *d_cov = sc.out<i64>(n_pos), *d_valid = sc.out<i64>(n_pos);
-    i64 *d_counts = sc.out<i64>(n_tracks), *d_ns = sc.out<i64>(n_tracks);
-    if (sc.rc) return sc.rc;
-    k_site_finish<<<(unsigned)n_tracks, 64, 0, e->stream>>>(a, damp_counts ? damp_counts[0] : 0.0,
-        damp_counts ? damp_counts[0] + damp_counts[1] : 0.0, d_frac, d_pos, d_cov, d_valid, d_damp,
-        d_counts, d_ns);
-    if (sc.sync(e->stream)) return sc.rc;
-    // the compacted outputs of track t start at its first position (unused tails are left as
-    // they are)
-    if (sc.get(out_counts, d_counts, n_tracks) || sc.get(out_n_stats, d_ns, n_tracks) ||
-        sc.get(out_frac, d_frac, n_pos) || sc.get(out_pos, d_pos, n_pos) ||
-        sc.get(out_cov, d_cov, n_pos) || sc.get(out_valid_cov, d_valid, n_pos))
+    S.finish();
+    if (sc.sync() || S.read_back(out_frac, out_pos, out_cov, out_valid_cov, out_damp_frac, out_counts, out_n_stats))
         return sc.rc;
-    if (d_damp && sc.get(out_damp_frac, d_damp, n_pos)) return sc.rc;
     if (out_per_read && d_pr) return sc.get(out_per_read, d_pr, n_stats);
     return TBA_OK;
 }
@@ -2078,57 +2127,55 @@ extern "C" int tba_site_aggregate(tba_engine *e, int64_t n_blocks, const int64_t
         pos_off[t + 1] = pos_off[t] + (blk_end[t] - blk_start[t]);
         if (pos_off[t + 1] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "2^31 positions or more in one call");
     }
-    const i64 n_pos = pos_off[n_blocks];
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
-    SiteArgs a{};
-    a.n_tracks = n_blocks;
-    a.trk_start = sc.in(blk_start, n_blocks);
-    a.pos_off = sc.in(pos_off.data(), n_blocks + 1);
-    a.valid_mode = lower_thresh ? 0 : form == 1 ? 1 : 2;
-    a.single = single_read_thresh;
-    a.lower = lower_thresh ? *lower_thresh : 0.0;
-    a.cnt = sc.out<i32>(3 * n_pos);
+    Scratch sc(e);
+    SiteCollate S(sc, n_blocks, blk_start, pos_off, single_read_thresh, lower_thresh, form, damp_counts);
     const i64 *d_end = sc.in(blk_end, n_blocks);
     const i64 *d_off = sc.in(rec_off, n_blocks + 1);
-    const uint4 *d_rec = n_recs > 0 ? sc.in((const uint4 *)records, n_recs) : nullptr;
-    double *d_frac = sc.out<double>(n_pos), *d_damp = damp_counts ? sc.out<double>(n_pos) : nullptr;
-    i64 *d_pos = sc.out<i64>(n_pos), *d_cov = sc.out<i64>(n_pos), *d_valid = sc.out<i64>(n_pos);
-    i64 *d_counts = sc.out<i64>(n_blocks), *d_ns = sc.out<i64>(n_blocks);
-    i32 *d_bad = sc.status(e->stream);
+    const uint4 *d_rec = sc.in((const uint4 *)records, n_recs);
+    i32 *d_bad = sc.status();
     if (sc.rc) return sc.rc;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (out_kernel_ms && (sc.hip(hipEventCreate(&ev0), "hipEventCreate") || sc.hip(hipEventCreate(&ev1), "hipEventCreate"))) {
-        if (ev0) (void)hipEventDestroy(ev0);
-        return sc.rc;
-    }
-    if (ev0) sc.hip(hipEventRecord(ev0, e->stream), "hipEventRecord");
-    sc.hip(hipMemsetAsync(a.cnt, 0, 3 * n_pos * sizeof(i32), e->stream), "hipMemsetAsync");
-    if (n_recs > 0 && !sc.rc)
-        k_site_rec<<<grid_for(n_recs), 256, 0, e->stream>>>(a, d_rec, d_off, n_recs, d_end, d_bad);
-    if (!sc.rc)
-        k_site_finish<<<(unsigned)n_blocks, 64, 0, e->stream>>>(a, damp_counts ? damp_counts[0] : 0.0,
-            damp_counts ? damp_counts[0] + damp_counts[1] : 0.0, d_frac, d_pos, d_cov, d_valid, d_damp,
-            d_counts, d_ns);
-    if (ev1) sc.hip(hipEventRecord(ev1, e->stream), "hipEventRecord");
-    const int n_bad = sc.sync(e->stream, d_bad);
-    if (ev0) {
-        float ms = 0;
-        if (!sc.rc && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *out_kernel_ms = ms;
-        (void)hipEventDestroy(ev0);
-        (void)hipEventDestroy(ev1);
-    }
+    KernelTimer tm(sc, out_kernel_ms != nullptr);
+    if (!S.zero_counters() && n_recs > 0)
+        k_site_rec<<<grid_for(n_recs), 256, 0, sc.stream>>>(S.a, d_rec, d_off, n_recs, d_end, d_bad);
+    S.finish();
+    tm.stop();
+    const int n_bad = sc.sync(d_bad);
+    if (out_kernel_ms) *out_kernel_ms = tm.ms();
     if (sc.rc) return sc.rc;
     if (n_bad) return set_err(TBA_E_ARG, "record position outside its block");
-    if (sc.get(out_counts, d_counts, n_blocks) || sc.get(out_n_stats, d_ns, n_blocks) ||
-        sc.get(out_frac, d_frac, n_pos) || sc.get(out_pos, d_pos, n_pos) ||
-        sc.get(out_cov, d_cov, n_pos) || sc.get(out_valid_cov, d_valid, n_pos))
-        return sc.rc;
-    if (d_damp) return sc.get(out_damp_frac, d_damp, n_pos);
-    return TBA_OK;
+    return S.read_back(out_frac, out_pos, out_cov, out_valid_cov, out_damp_frac, out_counts, out_n_stats);
 }
 
 // ---- estimate_alt_model (k_kde.h): levels gathered by k-mer, kernel densities ----------------
+namespace {
+// n items partitioned by one of n_keys keys, in chunks: a row of per-key counters per chunk (at most 1024
+// chunks and at most 2^24 counters; a chunk is a multiple of 64 items and at least 4096).  count() runs the
+// caller's counting pass over zeroed rows and leaves the per-key counts and their offsets on the device;
+// the caller's filling pass then reads rows and off.
+struct KeyPartition {
+    Scratch &sc;
+    i64 n_keys, chunk, n_chunks;
+    u32 *rows;
+    i64 *counts, *off;
+    KeyPartition(Scratch &sc_, i64 n, i64 n_keys_) : sc(sc_), n_keys(n_keys_)
+    {
+        const i64 max_chunks = std::max<i64>(1, std::min<i64>(1024, ((i64)1 << 24) / n_keys));
+        chunk = std::max<i64>(4096, ((n + max_chunks - 1) / max_chunks + 63) / 64 * 64);
+        n_chunks = (n + chunk - 1) / chunk;
+        rows = sc.out<u32>(n_chunks * n_keys);
+        counts = sc.out<i64>(n_keys);
+        off = sc.out<i64>(n_keys + 1);
+    }
+    template <class F> void count(F launch_count_pass)
+    {
+        if (sc.zero(rows, n_chunks * n_keys * sizeof(u32))) return;
+        launch_count_pass();
+        k_kmer_colscan<<<grid_for(n_keys), 256, 0, sc.stream>>>(n_keys, n_chunks, rows, counts);
+        k_kmer_offsets<<<1, 64, 0, sc.stream>>>(n_keys, counts, off);
+    }
+};
+} // namespace
+
 extern "C" int tba_kmer_levels(tba_engine *e, const double *means, const uint8_t *codes,
     const int64_t *read_off, int64_t n_reads, int64_t kmer_width, int64_t central_pos,
     const uint8_t *completed, int64_t *out_counts, int64_t *out_lv_off, double *out_levels,
@@ -2147,53 +2194,43 @@ extern "C" int tba_kmer_levels(tba_engine *e, const double *means, const uint8_t
         if (out_lv_off) for (i64 q = 0; q <= n_kmers; q++) out_lv_off[q] = 0;
         return TBA_OK;
     }
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
+    KeyPartition part(sc, total, n_kmers);
+    const unsigned n_chunks = (unsigned)part.n_chunks;
     KmerArgs a{};
-    // at most 1024 chunks and at most 2^24 counters: a chunk is a multiple of 64 positions
-    const i64 max_chunks = std::max<i64>(1, std::min<i64>(1024, ((i64)1 << 24) / n_kmers));
-    a.chunk = std::max<i64>(4096, ((total + max_chunks - 1) / max_chunks + 63) / 64 * 64);
-    const i64 n_chunks = (total + a.chunk - 1) / a.chunk;
+    a.chunk = part.chunk;
     a.n_reads = n_reads; a.total = total; a.K = (int)kmer_width; a.cp = (int)central_pos;
     a.read_off = sc.in(read_off, n_reads + 1);
     a.codes = sc.in(codes, total);
     a.completed = sc.in(completed, n_kmers);
     a.means = sc.in(means, total);
-    u32 *rows = sc.out<u32>(n_chunks * n_kmers);
-    i64 *d_counts = sc.out<i64>(n_kmers), *d_off = sc.out<i64>(n_kmers + 1);
-    if (sc.rc || sc.hip(hipMemsetAsync(rows, 0, n_chunks * n_kmers * sizeof(u32), e->stream), "hipMemsetAsync"))
-        return sc.rc;
-    k_kmer_gather<false><<<(unsigned)n_chunks, 64, 0, e->stream>>>(a, rows, nullptr, nullptr);
-    k_kmer_colscan<<<grid_for(n_kmers), 256, 0, e->stream>>>(n_kmers, n_chunks, rows, d_counts);
-    k_kmer_offsets<<<1, 64, 0, e->stream>>>(n_kmers, d_counts, d_off);
-    if (sc.sync(e->stream)) return sc.rc;
-    if (sc.get(out_counts, d_counts, n_kmers)) return sc.rc;
-    if (out_lv_off && sc.get(out_lv_off, d_off, n_kmers + 1)) return sc.rc;
+    part.count([&] { k_kmer_gather<false><<<n_chunks, 64, 0, sc.stream>>>(a, part.rows, nullptr, nullptr); });
+    if (sc.sync()) return sc.rc;
+    if (sc.get(out_counts, part.counts, n_kmers)) return sc.rc;
+    if (out_lv_off && sc.get(out_lv_off, part.off, n_kmers + 1)) return sc.rc;
     if (!out_levels) return TBA_OK;
     const i64 n_lv = out_lv_off[n_kmers];
     if (n_lv > levels_cap) return set_err(TBA_E_ARG, "levels_cap is smaller than the number of gathered levels");
     if (n_lv == 0) return TBA_OK;
     double *d_lv = sc.out<double>(n_lv);
     if (sc.rc) return sc.rc;
-    k_kmer_gather<true><<<(unsigned)n_chunks, 64, 0, e->stream>>>(a, rows, d_off, d_lv);
-    if (sc.sync(e->stream)) return sc.rc;
+    k_kmer_gather<true><<<n_chunks, 64, 0, sc.stream>>>(a, part.rows, part.off, d_lv);
+    if (sc.sync()) return sc.rc;
     return sc.get(out_levels, d_lv, n_lv);
 }
 
 namespace {
 // the segments of d_lv (n_seg, CSR by d_off) with more than one level and no NaN sorted ascending in place (shared by
 // tba_kde_eval, tba_region_key_levels and tba_segment_medians) -> has_nan per segment; *cov_out: the sizes
-static i32 *sort_segments(tba_engine *e, Scratch &sc, i64 n_seg, const i64 *d_off, double *d_lv, i32 **cov_out = nullptr)
+static i32 *sort_segments(Scratch &sc, i64 n_seg, const i64 *d_off, double *d_lv, i32 **cov_out = nullptr)
 {
     i32 *cov = sc.out<i32>(n_seg), *has_nan = sc.out<i32>(n_seg);
     if (cov_out) *cov_out = cov;
     i64 *lists = sc.out<i64>(3 * n_seg);
     u32 *cls = sc.out<u32>(3);
-    if (sc.rc || sc.hip(hipMemsetAsync(cls, 0, 3 * sizeof(u32), e->stream), "hipMemsetAsync")) return nullptr;
-    k_kde_classify<<<grid_for(64 * n_seg), 256, 0, e->stream>>>(n_seg, d_off, d_lv, cov, has_nan, lists, cls);
-    k_grp_sort_wave<<<1024, 256, 0, e->stream>>>(lists, cls, cov, d_off, d_lv);
-    k_grp_sort_wg<<<1024, 256, 0, e->stream>>>(lists + n_seg, cls + 1, cov, d_off, d_lv, 0);
-    k_grp_sort_wg<<<256, 256, 0, e->stream>>>(lists + 2 * n_seg, cls + 2, cov, d_off, d_lv, 1);
+    if (sc.zero(cls, 3 * sizeof(u32))) return nullptr;
+    k_kde_classify<<<grid_for(64 * n_seg), 256, 0, sc.stream>>>(n_seg, d_off, d_lv, cov, has_nan, lists, cls);
+    launch_sort_classes(sc.stream, lists, n_seg, cls, cov, d_off, d_lv);
     return has_nan;
 }
 } // namespace
@@ -2210,47 +2247,35 @@ extern "C" int tba_kde_eval(tba_engine *e, const double *levels, const int64_t *
         if (lv_off[s + 1] - lv_off[s] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "segment of more than 2^31 - 1 levels");
     const i64 n_lv = lv_off[n_seg];
     if (n_lv > 0 && !levels) return set_err(TBA_E_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
-    double *d_lv = n_lv > 0 ? sc.in(levels, n_lv) : sc.out<double>(1);
+    Scratch sc(e);
+    double *d_lv = sc.in(levels, n_lv);
     const i64 *d_off = sc.in(lv_off, n_seg + 1);
     const double *d_x = sc.in(x, n_x);
     double *d_dens = sc.out<double>(n_seg * n_x);
     i32 *cov = nullptr;
-    const i32 *has_nan = sort_segments(e, sc, n_seg, d_off, d_lv, &cov);
+    const i32 *has_nan = sort_segments(sc, n_seg, d_off, d_lv, &cov);
     if (sc.rc) return sc.rc;
     k_kde_eval<<<dim3((unsigned)std::min<i64>(n_seg, 65535), (unsigned)((n_x + 255) / 256)), 256, 0, e->stream>>>(
         n_seg, cov, has_nan, d_off, d_lv, d_x, n_x, bandwidth, d_dens);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(out_dens, d_dens, n_seg * n_x);
 }
 
 // ---- genome tracks (k_tracks.h): pileup sums and coverages, compaction, difference, top N --------
 namespace {
-// kernel time of the launches between start() and stop(), added to the open set's total
-struct TrkTimer {
-    tba_engine *e;
-    explicit TrkTimer(tba_engine *e_) : e(e_) { (void)hipEventRecord(e->ev_trk0, e->stream); }
-    void stop(Scratch &sc)
-    {
-        float ms = 0;
-        if (sc.rc || hipEventRecord(e->ev_trk1, e->stream) != hipSuccess || hipEventSynchronize(e->ev_trk1) != hipSuccess) return;
-        if (hipEventElapsedTime(&ms, e->ev_trk0, e->ev_trk1) == hipSuccess) e->trk_kernel_ms += ms;
-    }
-};
 static unsigned trk_chunks(i64 n) { return (unsigned)((n + TRK_CHUNK - 1) / TRK_CHUNK); }
 
 // flag / scan / scatter of the n words x under `mode` (sel: the search state of the top-N modes); the kept
 // indices to d_pos (n + 1 words), the kept words of src to d_val (n words); d_total: how many were kept
-static void launch_compact(tba_engine *e, Scratch &sc, i64 n, int mode, const u64 *x, const TrkSel *sel, const u64 *src,
+static void launch_compact(Scratch &sc, i64 n, int mode, const u64 *x, const TrkSel *sel, const u64 *src,
                            i64 *d_pos, u64 *d_val, i64 *d_total)
 {
     const unsigned nb = trk_chunks(n);
     i64 *d_cnt = sc.out<i64>(nb);
     if (sc.rc) return;
-    k_trk_count<<<nb, 256, 0, e->stream>>>(n, mode, x, sel, d_cnt);
-    k_trk_scan_blocks<<<1, 256, 0, e->stream>>>((i64)nb, d_cnt, d_total);
-    k_trk_scatter<<<nb, 256, 0, e->stream>>>(n, mode, x, sel, src, d_cnt, d_total, d_pos, d_val);
+    k_trk_count<<<nb, 256, 0, sc.stream>>>(n, mode, x, sel, d_cnt);
+    k_trk_scan_blocks<<<1, 256, 0, sc.stream>>>((i64)nb, d_cnt, d_total);
+    k_trk_scatter<<<nb, 256, 0, sc.stream>>>(n, mode, x, sel, src, d_cnt, d_total, d_pos, d_val);
 }
 } // namespace
 
@@ -2297,40 +2322,41 @@ extern "C" int tba_tracks_add(tba_engine *e, int64_t n_reads, const int64_t *rea
         if (read_flags[q] >> (1 + ns)) return set_err(TBA_E_ARG, "read flags name a slot the track set does not have");
     }
     for (int s = 0; s < ns; s++) if (total > 0 && !slots[s]) return set_err(TBA_E_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     TrkAdd a{};
     a.win_start = e->trk_start; a.W = W;
     a.read_start = sc.in(read_start, n_reads);
     a.read_end = sc.in(read_end, n_reads);
     a.read_off = sc.in(read_off, n_reads + 1);
     a.read_flags = sc.in(read_flags, n_reads);
-    for (int s = 0; s < ns; s++) a.slot[s] = total > 0 ? sc.in(slots[s], total) : sc.out<double>(1);
+    for (int s = 0; s < ns; s++) a.slot[s] = sc.in(slots[s], total);
     a.tile_off = sc.in(tile_read_off, n_tiles + 1);
     a.tile_reads = sc.in(tile_reads, n_listed);
     a.sum = e->d_trk_sum.as<double>(); a.cov = e->d_trk_cov.as<i64>(); a.rcov = e->d_trk_rcov.as<i64>();
     if (sc.rc) return sc.rc;
-    TrkTimer tm(e);
+    KernelTimer tm(sc);
     (ns == 1 ? k_trk_add<1> : ns == 2 ? k_trk_add<2> : k_trk_add<3>)<<<(unsigned)n_tiles, TRK_TILE, 0, e->stream>>>(a);
-    tm.stop(sc);
-    return sc.sync(e->stream);
+    tm.stop();
+    const int rc = sc.sync();
+    e->trk_kernel_ms += tm.ms();
+    return rc;
 }
 
 extern "C" int tba_tracks_finish(tba_engine *e, double *means_out, double *sums_out, int64_t *slot_cov_out,
     int64_t *read_cov_out)
 {
     if (!e || !e->trk_slots) return set_err(TBA_E_ARG, "no track set is open (tba_tracks_begin)");
-    HIP_TRY(hipSetDevice(e->device));
     const i64 W = e->trk_W, n = W * e->trk_slots;
-    Scratch sc;
+    Scratch sc(e);
     if (means_out) {
         double *d_mean = sc.out<double>(n);
         if (sc.rc) return sc.rc;
-        TrkTimer tm(e);
+        KernelTimer tm(sc);
         k_trk_finish<<<grid_for(n), 256, 0, e->stream>>>(n, e->d_trk_sum.as<double>(), e->d_trk_cov.as<i64>(), d_mean);
-        tm.stop(sc);
-        if (sc.sync(e->stream) || sc.get(means_out, d_mean, n)) return sc.rc;
-    } else if (sc.sync(e->stream)) return sc.rc;
+        tm.stop();
+        e->trk_kernel_ms += tm.ms();
+        if (sc.sync() || sc.get(means_out, d_mean, n)) return sc.rc;
+    } else if (sc.sync()) return sc.rc;
     if (sums_out && sc.get(sums_out, e->d_trk_sum.as<double>(), n)) return sc.rc;
     if (slot_cov_out && sc.get(slot_cov_out, e->d_trk_cov.as<i64>(), n)) return sc.rc;
     if (read_cov_out && sc.get(read_cov_out, e->d_trk_rcov.as<i64>(), W)) return sc.rc;
@@ -2352,13 +2378,12 @@ extern "C" int tba_tracks_compact(tba_engine *e, int mode, const void *values, i
         return set_err(TBA_E_ARG, "bad arguments");
     *out_count = 0;
     if (n == 0) return TBA_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const u64 *d_x = sc.in((const u64 *)values, n);
     i64 *d_pos = sc.out<i64>(n + 1), *d_total = sc.out<i64>(1);
     u64 *d_val = sc.out<u64>(n);
-    launch_compact(e, sc, n, mode, d_x, nullptr, d_x, d_pos, d_val, d_total);
-    if (sc.sync(e->stream) || sc.get(out_count, d_total, 1)) return sc.rc;
+    launch_compact(sc, n, mode, d_x, nullptr, d_x, d_pos, d_val, d_total);
+    if (sc.sync() || sc.get(out_count, d_total, 1)) return sc.rc;
     const i64 k = *out_count;
     if (sc.get(out_pos, d_pos, k + (mode == TRK_KEEP_RUN_START))) return sc.rc;
     return sc.get((u64 *)out_val, d_val, k);
@@ -2368,13 +2393,12 @@ extern "C" int tba_tracks_diff(tba_engine *e, const double *a, const double *b, 
 {
     if (!e || n < 0 || (n > 0 && (!a || !b || !out))) return set_err(TBA_E_ARG, "bad arguments");
     if (n == 0) return TBA_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_a = sc.in(a, n), *d_b = sc.in(b, n);
     double *d_out = sc.out<double>(n);
     if (sc.rc) return sc.rc;
     k_trk_diff<false><<<grid_for(n), 256, 0, e->stream>>>(n, d_a, d_b, d_out, nullptr);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(out, d_out, n);
 }
 
@@ -2387,8 +2411,7 @@ extern "C" int tba_tracks_topn(tba_engine *e, const double *a, const double *b, 
     const i64 N = std::min<i64>(n_top, n);
     *out_count = 0;
     if (N == 0) return TBA_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_a = sc.in(a, n), *d_b = sc.in(b, n);
     double *d_diff = sc.out<double>(n);
     u64 *d_key = sc.out<u64>(n);
@@ -2403,12 +2426,12 @@ extern "C" int tba_tracks_topn(tba_engine *e, const double *a, const double *b, 
         k_trk_hist<<<grid_for(n), 256, 0, e->stream>>>(n, d_key, shift, d_sel);
         k_trk_pick<<<1, 256, 0, e->stream>>>(shift, d_sel);
     }
-    if (sc.sync(e->stream) || sc.get(&hs, d_sel, 1)) return sc.rc;
+    if (sc.sync() || sc.get(&hs, d_sel, 1)) return sc.rc;
     // what is above the N-th largest value, in position order, then the highest positions that equal it
-    launch_compact(e, sc, n, TRK_KEEP_ABOVE, d_key, d_sel, (const u64 *)d_diff, d_pos, d_val, d_total);
-    launch_compact(e, sc, n, TRK_KEEP_EQUAL, d_key, d_sel, (const u64 *)d_diff, d_pos + hs.n_above, d_val + hs.n_above,
+    launch_compact(sc, n, TRK_KEEP_ABOVE, d_key, d_sel, (const u64 *)d_diff, d_pos, d_val, d_total);
+    launch_compact(sc, n, TRK_KEEP_EQUAL, d_key, d_sel, (const u64 *)d_diff, d_pos + hs.n_above, d_val + hs.n_above,
                    d_total + 1);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     *out_count = N;
     if (sc.get(out_pos, d_pos, N)) return sc.rc;
     return sc.get((u64 *)out_val, d_val, N);
@@ -2442,18 +2465,17 @@ extern "C" int tba_region_key_levels(tba_engine *e, int est_mean, int64_t n_read
         for (i64 q = 0; q <= n_keys; q++) out_off[q] = 0;
         return TBA_OK;
     }
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     KestArgs a{};
     a.n_pos = n_pos;
     a.pos_reg = sc.in(pos_reg, n_pos);
     a.pos_g = sc.in(pos_g, n_pos);
     a.reg_read_off = sc.in(reg_read_off, n_regions + 1);
-    a.reg_reads = n_rr > 0 ? sc.in(reg_reads, n_rr) : sc.out<i64>(1);
-    a.read_start = n_reads > 0 ? sc.in(read_start, n_reads) : sc.out<i64>(1);
-    a.read_minus = n_reads > 0 ? sc.in(read_minus, n_reads) : sc.out<uint8_t>(1);
+    a.reg_reads = sc.in(reg_reads, n_rr);
+    a.read_start = sc.in(read_start, n_reads);
+    a.read_minus = sc.in(read_minus, n_reads);
     a.read_off = sc.in(read_off, n_reads + 1);
-    a.means = total > 0 ? sc.in(means, total) : sc.out<double>(1);
+    a.means = sc.in(means, total);
     i32 *cov = sc.out<i32>(n_pos);
     i64 *lv_off = sc.out<i64>(n_pos + 1);
     double *d_level = sc.out<double>(n_pos), *d_sd = sc.out<double>(n_pos);
@@ -2461,36 +2483,32 @@ extern "C" int tba_region_key_levels(tba_engine *e, int est_mean, int64_t n_read
     k_kest_pileup<false><<<grid_for(n_pos), 256, 0, e->stream>>>(a, cov, nullptr, nullptr);
     k_kest_offsets<<<1, 256, 0, e->stream>>>(n_pos, cov, lv_off);
     i64 n_lv = 0;
-    if (sc.sync(e->stream) || sc.get(&n_lv, lv_off + n_pos, 1)) return sc.rc;
+    if (sc.sync() || sc.get(&n_lv, lv_off + n_pos, 1)) return sc.rc;
     double *d_lv = sc.out<double>(n_lv);
     if (sc.rc) return sc.rc;
     k_kest_pileup<true><<<grid_for(n_pos), 256, 0, e->stream>>>(a, nullptr, lv_off, d_lv);
     k_kest_moments<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, est_mean, lv_off, d_lv, d_level, d_sd);
     if (!est_mean) {
-        const i32 *has_nan = sort_segments(e, sc, n_pos, lv_off, d_lv);
+        const i32 *has_nan = sort_segments(sc, n_pos, lv_off, d_lv);
         if (sc.rc) return sc.rc;
         k_kest_median<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, has_nan, lv_off, d_lv, d_level);
     }
-    // the entries by key: at most 1024 chunks and at most 2^24 counters, a chunk a multiple of 64 entries
+    // the entries by key
     int key_bits = 0;
     while (((i64)1 << key_bits) < n_keys) key_bits++;
-    const i64 max_chunks = std::max<i64>(1, std::min<i64>(1024, ((i64)1 << 24) / n_keys));
-    const i64 chunk = std::max<i64>(4096, ((n_ent + max_chunks - 1) / max_chunks + 63) / 64 * 64);
-    const i64 n_chunks = (n_ent + chunk - 1) / chunk;
     const i64 *d_ep = sc.in(ent_pos, n_ent), *d_ek = sc.in(ent_key, n_ent);
-    u32 *rows = sc.out<u32>(n_chunks * n_keys);
-    i64 *d_counts = sc.out<i64>(n_keys), *d_koff = sc.out<i64>(n_keys + 1);
+    KeyPartition part(sc, n_ent, n_keys);
+    const unsigned n_chunks = (unsigned)part.n_chunks;
     double *d_ol = sc.out<double>(n_ent), *d_os = sc.out<double>(n_ent);
-    if (sc.rc || sc.hip(hipMemsetAsync(rows, 0, n_chunks * n_keys * sizeof(u32), e->stream), "hipMemsetAsync"))
-        return sc.rc;
-    k_kest_partition<false><<<(unsigned)n_chunks, 64, 0, e->stream>>>(n_ent, chunk, n_keys, key_bits, d_ep, d_ek, rows,
-        nullptr, nullptr, nullptr, nullptr, nullptr);
-    k_kmer_colscan<<<grid_for(n_keys), 256, 0, e->stream>>>(n_keys, n_chunks, rows, d_counts);
-    k_kmer_offsets<<<1, 64, 0, e->stream>>>(n_keys, d_counts, d_koff);
-    k_kest_partition<true><<<(unsigned)n_chunks, 64, 0, e->stream>>>(n_ent, chunk, n_keys, key_bits, d_ep, d_ek, rows,
-        d_koff, d_level, d_sd, d_ol, d_os);
-    if (sc.sync(e->stream)) return sc.rc;
-    if (sc.get(out_counts, d_counts, n_keys) || sc.get(out_off, d_koff, n_keys + 1) ||
+    part.count([&] {
+        k_kest_partition<false><<<n_chunks, 64, 0, sc.stream>>>(n_ent, part.chunk, n_keys, key_bits, d_ep, d_ek, part.rows,
+            nullptr, nullptr, nullptr, nullptr, nullptr);
+    });
+    if (sc.rc) return sc.rc;
+    k_kest_partition<true><<<n_chunks, 64, 0, sc.stream>>>(n_ent, part.chunk, n_keys, key_bits, d_ep, d_ek, part.rows,
+        part.off, d_level, d_sd, d_ol, d_os);
+    if (sc.sync()) return sc.rc;
+    if (sc.get(out_counts, part.counts, n_keys) || sc.get(out_off, part.off, n_keys + 1) ||
         sc.get(out_levels, d_ol, n_ent))
         return sc.rc;
     return sc.get(out_sds, d_os, n_ent);
@@ -2506,15 +2524,14 @@ extern "C" int tba_segment_medians(tba_engine *e, const double *values, const in
         if (off[s + 1] - off[s] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "segment of more than 2^31 - 1 values");
     const i64 n = off[n_seg];
     if (n > 0 && !values) return set_err(TBA_E_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
-    double *d_v = n > 0 ? sc.in(values, n) : sc.out<double>(1);
+    Scratch sc(e);
+    double *d_v = sc.in(values, n);
     const i64 *d_off = sc.in(off, n_seg + 1);
     double *d_out = sc.out<double>(n_seg);
-    const i32 *has_nan = sort_segments(e, sc, n_seg, d_off, d_v);
+    const i32 *has_nan = sort_segments(sc, n_seg, d_off, d_v);
     if (sc.rc) return sc.rc;
     k_kest_median<<<grid_for(n_seg), 256, 0, e->stream>>>(n_seg, has_nan, d_off, d_v, d_out);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(out_medians, d_out, n_seg);
 }
 
@@ -2571,7 +2588,7 @@ extern "C" int tba_batch_de_novo_stats(tba_engine *e, int64_t fm_offset, double 
         pk[i + 1] = pk[i] + cnt;
     }
     const i64 total = pk[N];
-    Scratch sc;
+    Scratch sc(e);
     const i64 *d_pk = sc.in(pk.data(), N + 1);
     double *d_pm = sc.out<double>(total);
     double *d_pr = sc.out<double>(total);
@@ -2587,7 +2604,7 @@ extern "C" int tba_batch_de_novo_stats(tba_engine *e, int64_t fm_offset, double 
     }
     k_denovo_unpack<<<dim3(gB, (unsigned)N), 256, 0, e->stream>>>(e->d_rs.as<ReadState>(),
         e->d_dp.as<DevParams>(), d_pk, d_pp, d_out);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(pvals, d_out, e->z.B_tot);
 }
 
@@ -2596,14 +2613,13 @@ static int c_div_selftest(tba_engine *e, void (*kernel)(const double *, const do
                           const double *a, const double *b, int64_t n, double *out)
 {
     if (!e || !a || !b || !out || n < 1) return set_err(TBA_E_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_a = sc.in(a, n);
     const double *d_b = sc.in(b, n);
     double *d_o = sc.out<double>(n);
     if (sc.rc) return sc.rc;
     kernel<<<grid_for(n), 256, 0, e->stream>>>(d_a, d_b, n, d_o);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(out, d_o, n);
 }
 
@@ -2644,7 +2660,7 @@ extern "C" int tba_identify_stalls(tba_engine *e, const void *raw, int raw_dtype
     hp.o.stall_mini_window_size = mini_window_size; hp.o.stall_threshold = threshold;
     hp.o.stall_min_consecutive_obs = min_consecutive_obs; hp.o.stall_edge_buffer = edge_buffer;
     const i64 dev_cap = n / (min_consecutive_obs + 1) + 2;
-    Scratch sc;
+    Scratch sc(e);
     ReadState *rs = sc.in(&r, 1);
     const DevParams *dp = sc.in(&hp, 1);
     char *d_raw = sc.in((const char *)raw, (size_t)n * raw_elem_bytes(raw_dtype));
@@ -2665,7 +2681,7 @@ extern "C" int tba_identify_stalls(tba_engine *e, const void *raw, int raw_dtype
     }
     k_stall_runs<<<dim3(grid_for(n / 64 + 1), 1), 256, 0, s>>>(rs, dp, d_bits, d_ints);
     k_stall_merge<<<1, 64, 0, s>>>(rs, 1, dp, d_ints);
-    if (sc.sync(s) || sc.get(&r, rs, 1)) return sc.rc;
+    if (sc.sync() || sc.get(&r, rs, 1)) return sc.rc;
     if (r.status != TBA_OK) return r.status;
     *n_ints = r.n_stall;
     if (r.n_stall > cap) return set_err(TBA_E_ARG, "interval buffer too small (n_ints holds the count)");
@@ -2685,12 +2701,11 @@ extern "C" int tba_selftest_subsample(tba_engine *e, int64_t n, uint64_t seed, i
                                       int64_t count, int64_t *out)
 {
     if (!e || !out || n < 1 || count < 1 || count > n) return set_err(TBA_E_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     i64 *d_o = sc.out<i64>(count);
     if (sc.rc) return sc.rc;
     k_c_perm_check<<<grid_for(count), 256, 0, e->stream>>>(n, seed, read_index, count, d_o);
-    if (sc.sync(e->stream)) return sc.rc;
+    if (sc.sync()) return sc.rc;
     return sc.get(out, d_o, count);
 }
 
@@ -2983,26 +2998,6 @@ extern "C" int tba_engine_held_bytes(tba_engine *e, int64_t *bytes)
 
 // ---- ROC / precision-recall (k_roc.h): labels of stored statistics, sorted cumulative counts ------
 namespace {
-// kernel time of the launches between construction and stop(), through hipEvents on the engine's stream
-struct RocTimer {
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipStream_t s;
-    RocTimer(Scratch &sc, hipStream_t s_, bool on) : s(s_)
-    {
-        if (!on || sc.rc) return;
-        if (sc.hip(hipEventCreate(&ev0), "hipEventCreate") || sc.hip(hipEventCreate(&ev1), "hipEventCreate")) return;
-        sc.hip(hipEventRecord(ev0, s), "hipEventRecord");
-    }
-    void mark(Scratch &sc) { if (ev1 && !sc.rc) sc.hip(hipEventRecord(ev1, s), "hipEventRecord"); }
-    // after the stream was synchronised
-    void read(Scratch &sc, double *out_ms)
-    {
-        float ms = 0;
-        if (ev1 && !sc.rc && out_ms && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *out_ms += ms;
-    }
-    ~RocTimer() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
-};
-
 static int check_roc_recs(int64_t n_blocks, const int64_t *rec_off, const int64_t *rec_pos, const double *rec_stat)
 {
     if (n_blocks < 0 || !rec_off) return set_err(TBA_E_ARG, "bad arguments");
@@ -3016,7 +3011,7 @@ static int check_roc_recs(int64_t n_blocks, const int64_t *rec_off, const int64_
 // count / scan / scatter of the kept (record, motif) pairs under f; everything after the uploads.  f's own arrays
 // are on the device already.  out_counts[n_motifs]; the pairs of all motifs back to back in the outputs.
 template <class F>
-static int roc_compact(tba_engine *e, Scratch &sc, F f, RocRecs R, i64 n_motifs, double *out_stats,
+static int roc_compact(Scratch &sc, F f, RocRecs R, i64 n_motifs, double *out_stats,
     uint8_t *out_has_mod, int64_t *out_index, int64_t *out_counts, double *out_kernel_ms)
 {
     const unsigned nb = trk_chunks(R.n_rec);
@@ -3026,16 +3021,16 @@ static int roc_compact(tba_engine *e, Scratch &sc, F f, RocRecs R, i64 n_motifs,
     uint8_t *d_lab = sc.out<uint8_t>(R.n_rec * n_motifs);
     i64 *d_idx = out_index ? sc.out<i64>(R.n_rec * n_motifs) : nullptr;
     if (sc.rc) return sc.rc;
-    RocTimer tm(sc, e->stream, out_kernel_ms != nullptr);
+    KernelTimer tm(sc, out_kernel_ms != nullptr);
     if (!sc.rc) {
         const dim3 grid(nb, (unsigned)n_motifs);
-        k_roc_count<<<grid, 256, 0, e->stream>>>(f, R, d_cnt);
-        k_trk_scan_blocks<<<1, 256, 0, e->stream>>>(m, d_cnt, d_cnt + m);
-        k_roc_scatter<<<grid, 256, 0, e->stream>>>(f, R, d_cnt, d_stat, d_lab, d_idx);
+        k_roc_count<<<grid, 256, 0, sc.stream>>>(f, R, d_cnt);
+        k_trk_scan_blocks<<<1, 256, 0, sc.stream>>>(m, d_cnt, d_cnt + m);
+        k_roc_scatter<<<grid, 256, 0, sc.stream>>>(f, R, d_cnt, d_stat, d_lab, d_idx);
     }
-    tm.mark(sc);
-    if (sc.sync(e->stream)) return sc.rc;
-    tm.read(sc, out_kernel_ms);
+    tm.stop();
+    if (sc.sync()) return sc.rc;
+    if (out_kernel_ms) *out_kernel_ms = tm.ms();
     std::vector<i64> base(m + 1);
     if (sc.get(base.data(), d_cnt, m + 1)) return sc.rc;
     for (i64 k = 0; k < n_motifs; k++) out_counts[k] = base[(k + 1) * nb] - base[k * nb];
@@ -3073,18 +3068,17 @@ extern "C" int tba_roc_motif_labels(tba_engine *e, int64_t n_blocks, const uint8
         n_sets += len;
     }
     if (n_rec == 0) return TBA_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     RocMotifLabel f{};
     f.blk_minus = sc.in(blk_minus, n_blocks);
     f.blk_seq_start = sc.in(blk_seq_start, n_blocks);
     f.seq_off = sc.in(seq_off, n_blocks + 1);
-    f.seq = n_seq > 0 ? sc.in(seq, n_seq) : sc.out<uint8_t>(1);
+    f.seq = sc.in(seq, n_seq);
     f.mot = sc.in(mot.data(), mot.size());
     f.sets = sc.in(motif_sets, n_sets);
     f.mode = mode; f.label = label ? 1 : 0;
     RocRecs R{n_blocks, n_rec, sc.in(rec_off, n_blocks + 1), sc.in(rec_pos, n_rec), sc.in(rec_stat, n_rec)};
-    return roc_compact(e, sc, f, R, n_motifs, out_stats, out_has_mod, out_index, out_counts, out_kernel_ms);
+    return roc_compact(sc, f, R, n_motifs, out_stats, out_has_mod, out_index, out_counts, out_kernel_ms);
 }
 
 extern "C" int tba_roc_loc_labels(tba_engine *e, int64_t n_blocks, const int64_t *blk_loc, const int64_t *mod_locs,
@@ -3105,14 +3099,13 @@ extern "C" int tba_roc_loc_labels(tba_engine *e, int64_t n_blocks, const int64_t
             return set_err(TBA_E_ARG, "location slice outside its list");
     }
     if (n_rec == 0) return TBA_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     RocLocLabel f{};
     f.blk_loc = sc.in(blk_loc, 4 * n_blocks);
-    f.mod = n_mod > 0 ? sc.in(mod_locs, n_mod) : sc.out<i64>(1);
-    f.unmod = n_unmod > 0 ? sc.in(unmod_locs, n_unmod) : sc.out<i64>(1);
+    f.mod = sc.in(mod_locs, n_mod);
+    f.unmod = sc.in(unmod_locs, n_unmod);
     RocRecs R{n_blocks, n_rec, sc.in(rec_off, n_blocks + 1), sc.in(rec_pos, n_rec), sc.in(rec_stat, n_rec)};
-    return roc_compact(e, sc, f, R, 1, out_stats, out_has_mod, out_index, out_count, out_kernel_ms);
+    return roc_compact(sc, f, R, 1, out_stats, out_has_mod, out_index, out_count, out_kernel_ms);
 }
 
 extern "C" int64_t tba_roc_sort_tile(void) { return ROC_SORT_TILE; }
@@ -3130,8 +3123,7 @@ extern "C" int tba_roc_rank_counts(tba_engine *e, int64_t n, const double *stats
     if (out_kernel_ms) out_kernel_ms[0] = out_kernel_ms[1] = 0.0;
     *out_tp_total = 0; *out_n_nan = 0;
     if (n == 0) return TBA_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    Scratch sc;
+    Scratch sc(e);
     const double *d_stat = sc.in(stats, n);
     uint8_t *lab[2] = {sc.in(has_mod, n), sc.out<uint8_t>(n)};
     u64 *key[2] = {sc.out<u64>(n), sc.out<u64>(n)};
@@ -3142,20 +3134,17 @@ extern "C" int tba_roc_rank_counts(tba_engine *e, int64_t n, const double *stats
     u32 *d_table = sc.out<u32>((i64)ROC_MAX_DIGITS * n_tiles);
     const unsigned n_tab_chunks = trk_chunks((i64)ROC_MAX_DIGITS * n_tiles), n_lab_chunks = trk_chunks(n);
     i64 *d_tab_cnt = sc.out<i64>(n_tab_chunks + 1), *d_lab_cnt = sc.out<i64>(n_lab_chunks + 1);
-    i32 *d_bad = sc.status(e->stream);
-    if (sc.rc || sc.hip(hipMemsetAsync(d_hist, 0, (ROC_HIST_BINS + 1) * 8, e->stream), "hipMemsetAsync")) return sc.rc;
+    i32 *d_bad = sc.status();
+    if (sc.zero(d_hist, (ROC_HIST_BINS + 1) * 8)) return sc.rc;
+    // keys first: the sort's passes are chosen from their histogram, on the host
+    const bool timed = out_kernel_ms != nullptr;
     std::vector<unsigned long long> hist(ROC_HIST_BINS + 1);
-    {
-        RocTimer tm(sc, e->stream, out_kernel_ms != nullptr);
-        if (!sc.rc) k_roc_keys<<<grid_for(n), 256, 0, e->stream>>>(n, d_stat, lab[0], key[0], d_hist);
-        tm.mark(sc);
-        if (sc.sync(e->stream)) return sc.rc;
-        tm.read(sc, out_kernel_ms);
-        if (sc.get(hist.data(), d_hist, hist.size())) return sc.rc;
-    }
+    KernelTimer tm_keys(sc, timed);
+    if (!sc.rc) k_roc_keys<<<grid_for(n), 256, 0, e->stream>>>(n, d_stat, lab[0], key[0], d_hist);
+    tm_keys.stop();
+    if (sc.sync() || sc.get(hist.data(), d_hist, hist.size())) return sc.rc;
     *out_n_nan = (int64_t)hist[ROC_HIST_BINS];
-    double sort_ms = 0.0, rank_ms = 0.0;
-    RocTimer tm(sc, e->stream, out_kernel_ms != nullptr);
+    KernelTimer tm_sort(sc, timed);
     int cur = 0;
     for (int pass = 0; pass < 8 && !sc.rc; pass++) {
         const int nd = pass == 0 ? 512 : 256;
@@ -3172,20 +3161,18 @@ extern "C" int tba_roc_rank_counts(tba_engine *e, int64_t n, const double *stats
             lab[cur ^ 1]);
         cur ^= 1;
     }
-    tm.mark(sc);
-    RocTimer tm_rank(sc, e->stream, out_kernel_ms != nullptr);
+    tm_sort.stop();
+    KernelTimer tm_rank(sc, timed);
     if (!sc.rc) {
         k_roc_label_count<<<n_lab_chunks, 256, 0, e->stream>>>(n, lab[cur], d_lab_cnt);
         k_trk_scan_blocks<<<1, 256, 0, e->stream>>>((i64)n_lab_chunks, d_lab_cnt, d_lab_cnt + n_lab_chunks);
         if (n_ranks > 0)
             k_roc_gather<<<grid_for(n_ranks), 256, 0, e->stream>>>(n, n_ranks, d_ranks, lab[cur], d_lab_cnt, d_tp, d_bad);
     }
-    tm_rank.mark(sc);
-    const int bad = sc.sync(e->stream, d_bad);
+    tm_rank.stop();
+    const int bad = sc.sync(d_bad);
     if (sc.rc) return sc.rc;
-    tm.read(sc, &sort_ms);
-    tm_rank.read(sc, &rank_ms);
-    if (out_kernel_ms) { out_kernel_ms[0] += sort_ms; out_kernel_ms[1] = rank_ms; }
+    if (timed) { out_kernel_ms[0] = tm_keys.ms() + tm_sort.ms(); out_kernel_ms[1] = tm_rank.ms(); }
     if (bad) return set_err(TBA_E_ARG, "rank outside [0, n)");
     if (sc.get(out_tp_total, d_lab_cnt + n_lab_chunks, 1)) return sc.rc;
     return n_ranks > 0 ? sc.get(out_tp_at, d_tp, n_ranks) : TBA_OK;
