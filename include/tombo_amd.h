@@ -617,6 +617,34 @@ int tba_roc_rank_counts(tba_engine *e, int64_t n, const double *stats, const uin
     double *out_kernel_ms);
 int64_t tba_roc_sort_tile(void);
 
+/* ---- pairwise distances between the rows of a matrix (tombo_stats.py:142-196) ------------------
+ * rows: dense row-major float64[n_rows][row_len].  Every sum is numpy's float64 add.reduce of a
+ * contiguous vector, so the outputs equal numpy's bit for bit.
+ *
+ * tba_pairwise_window_dists: get_pairwise_dists.  out[n_rows][n_rows]; for j <= i
+ *   out[i][j] = sqrt(min over i1, i2 in [0, 2 slide_span] of
+ *                    sum((rows[i][i1 : i1 + nb] - rows[j][i2 : i2 + nb])^2)),  nb = row_len - 2 slide_span
+ * (Python's min over i1 outer, i2 inner: a NaN sum stays only when it is the first), and 0 for
+ * j > i.  slide_span 0 is euclidian_dist.
+ *
+ * tba_pairwise_nanmean_dists: the metric of order_reads, np.nanmean(np.sqrt((u - v)**2)), for
+ * every i < j in scipy's condensed pdist order (k = n i - i (i + 1) / 2 + j - i - 1):
+ * out_condensed[n_rows (n_rows - 1) / 2]; NaN for a pair without a position where both rows hold a
+ * number.  n_rows == 1 writes nothing (out_condensed may then be NULL).
+ *
+ * out_kernel_ms (may be NULL): device time of the call's kernel.
+ * tba_pdist_tile: rows per side of the tile of pairs one workgroup owns; tba_pdist_lds_row_max:
+ * the longest row the workgroup keeps in LDS (longer rows are read from global memory).
+ * Limits of one call: n_rows <= 16384 (a 2 GiB matrix out) and n_rows * row_len <= 2^28 (2 GiB in).
+ * TBA_E_ARG: NULL pointers, n_rows < 1, row_len < 1, slide_span < 0, row_len - 2 slide_span < 1,
+ * a size above the limits.  Nothing is launched for any of these. */
+int tba_pairwise_window_dists(tba_engine *e, int64_t n_rows, int64_t row_len, int64_t slide_span,
+    const double *rows, double *out, double *out_kernel_ms);
+int tba_pairwise_nanmean_dists(tba_engine *e, int64_t n_rows, int64_t row_len, const double *rows,
+    double *out_condensed, double *out_kernel_ms);
+int64_t tba_pdist_tile(void);
+int64_t tba_pdist_lds_row_max(void);
+
 /* ---- alternate-base model estimation (estimate_alt_model, tombo_stats.py:1747-2098) -----------
  * The base levels of a batch of reads gathered by k-mer (_parse_base_levels_worker, :1747-1776).
  * means / codes: read-centric levels and base codes (0..3 = ACGT, anything else: not a base) of

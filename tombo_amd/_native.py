@@ -432,6 +432,26 @@ def _check_roc_rank_args(stats, has_mod, ranks):
     return np.ascontiguousarray(st), np.ascontiguousarray(hm).view(np.uint8), np.ascontiguousarray(rk)
 
 
+PDIST_TILE = 16           # PDIST_TILE of csrc/k_pdist.h (tba_pdist_tile): rows per side of a workgroup's tile of pairs
+PDIST_LDS_ROW_MAX = 255   # PDIST_LDS_ROW_MAX (tba_pdist_lds_row_max): longer rows are read from global memory
+PDIST_MAX_ROWS, PDIST_MAX_ELEMS = 16384, 2 ** 28
+
+
+def _check_pdist_rows(rows, slide_span=0):
+    """the argument checks of Engine.pairwise_window_dists / pairwise_nanmean_dists (shared with the tests' stand-in
+    engine): the dtype and the layout are checked, not converted -> rows"""
+    rows = np.asarray(rows)
+    if rows.dtype != np.float64 or rows.ndim != 2 or not rows.flags.c_contiguous:
+        raise ValueError('rows must be a C-contiguous two-dimensional float64 array')
+    if rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise ValueError('rows must have at least one row and one column')
+    if rows.shape[0] > PDIST_MAX_ROWS or rows.size > PDIST_MAX_ELEMS:
+        raise ValueError('at most %d rows and 2^28 values in one call' % PDIST_MAX_ROWS)
+    if int(slide_span) != slide_span or slide_span < 0 or rows.shape[1] - 2 * int(slide_span) < 1:
+        raise ValueError('slide_span must be an integer >= 0 that leaves a window of at least one value')
+    return rows
+
+
 def _site_outputs(starts, ends, damp_counts):
     """both site entries, tracks [starts[t], ends[t]) -> (pos_off, SiteFractions' frac .. n_stats, their C pointers)"""
     pos_off = np.concatenate([[0], np.cumsum(ends - starts)]).astype(np.int64)
@@ -1107,6 +1127,32 @@ class Engine(object):
         self.last_roc_sort_ms, self.last_roc_gather_ms = ms[0], ms[1]
         self.last_roc_kernel_ms = ms[0] + ms[1]
         return tp_at, total.value, n_nan.value
+
+    # ---- pairwise distances between rows (csrc/k_pdist.h) ----
+    def pairwise_window_dists(self, rows, slide_span=0):
+        """tba_pairwise_window_dists: rows float64[R, L] -> float64[R, R], [i, j] for j <= i the sqrt of the smallest
+        sum of squared differences between a window of row i and one of row j (windows of L - 2 slide_span values at
+        the starts 0 .. 2 slide_span), 0 above the diagonal.  `last_pdist_kernel_ms`: kernel time."""
+        rows = _check_pdist_rows(rows, slide_span)
+        n, ms = rows.shape[0], f64(0.0)
+        out = np.empty((n, n), dtype=np.float64)
+        self._check(self._L.tba_pairwise_window_dists(
+            self._h, i64(n), i64(rows.shape[1]), i64(int(slide_span)), _p(rows, f64), _p(out, f64), C.byref(ms)),
+            'tba_pairwise_window_dists')
+        self.last_pdist_kernel_ms = ms.value
+        return out
+
+    def pairwise_nanmean_dists(self, rows):
+        """tba_pairwise_nanmean_dists: rows float64[R, L] -> float64[R (R - 1) / 2], np.nanmean(np.sqrt((u - v)**2)) of
+        every pair of rows in scipy's condensed pdist order; NaN where two rows share no number"""
+        rows = _check_pdist_rows(rows)
+        n, ms = rows.shape[0], f64(0.0)
+        out = np.empty(n * (n - 1) // 2, dtype=np.float64)
+        self._check(self._L.tba_pairwise_nanmean_dists(
+            self._h, i64(n), i64(rows.shape[1]), _p(rows, f64), _p(out, f64), C.byref(ms)),
+            'tba_pairwise_nanmean_dists')
+        self.last_pdist_kernel_ms = ms.value
+        return out
 
     def kmer_levels(self, means, codes, read_off, kmer_width, central_pos, completed):
         """tba_kmer_levels: the levels of a batch of reads (means / codes CSR by read_off) gathered by k-mer

@@ -21,6 +21,7 @@
 #include "k_tracks.h"
 #include "k_kmer_est.h"
 #include "k_roc.h"
+#include "k_pdist.h"
 
 #include <algorithm>
 #include <array>
@@ -3176,4 +3177,77 @@ extern "C" int tba_roc_rank_counts(tba_engine *e, int64_t n, const double *stats
     if (bad) return set_err(TBA_E_ARG, "rank outside [0, n)");
     if (sc.get(out_tp_total, d_lab_cnt + n_lab_chunks, 1)) return sc.rc;
     return n_ranks > 0 ? sc.get(out_tp_at, d_tp, n_ranks) : TBA_OK;
+}
+
+// ---- pairwise distances between rows (k_pdist.h): get_pairwise_dists, order_reads' pdist -----------
+namespace {
+static int check_pdist(tba_engine *e, int64_t n_rows, int64_t row_len, const double *rows)
+{
+    if (!e || !rows || n_rows < 1 || row_len < 1) return set_err(TBA_E_ARG, "bad arguments");
+    if (n_rows > PDIST_MAX_ROWS) return set_err(TBA_E_ARG, "more than 16384 rows in one call");
+    if (row_len > PDIST_MAX_ELEMS / n_rows) return set_err(TBA_E_ARG, "more than 2^28 values in one call");
+    return TBA_OK;
+}
+// the launch shape both modes share: one workgroup per tile of the triangle, the two row sets in LDS when they fit
+struct PdistLaunch {
+    unsigned blocks;
+    int use_lds;
+    size_t lds_bytes;
+    PdistLaunch(i64 n_rows, i64 row_len)
+    {
+        const i64 nt = (n_rows + PDIST_TILE - 1) / PDIST_TILE;
+        blocks = (unsigned)(nt * (nt + 1) / 2);
+        use_lds = row_len <= PDIST_LDS_ROW_MAX;
+        lds_bytes = use_lds ? (size_t)2 * PDIST_TILE * (row_len | 1) * sizeof(double) : 0;
+    }
+};
+} // namespace
+
+extern "C" int64_t tba_pdist_tile(void) { return PDIST_TILE; }
+extern "C" int64_t tba_pdist_lds_row_max(void) { return PDIST_LDS_ROW_MAX; }
+
+extern "C" int tba_pairwise_window_dists(tba_engine *e, int64_t n_rows, int64_t row_len, int64_t slide_span,
+    const double *rows, double *out, double *out_kernel_ms)
+{
+    if (!out) return set_err(TBA_E_ARG, "bad arguments");
+    if (const int rc = check_pdist(e, n_rows, row_len, rows)) return rc;
+    if (slide_span < 0 || slide_span > row_len || row_len - 2 * slide_span < 1)
+        return set_err(TBA_E_ARG, "slide_span must be >= 0 and leave a window of at least one value");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    Scratch sc(e);
+    const double *d_rows = sc.in(rows, (size_t)(n_rows * row_len));
+    double *d_out = sc.out<double>((size_t)(n_rows * n_rows));
+    if (sc.rc) return sc.rc;
+    const PdistLaunch L(n_rows, row_len);
+    KernelTimer tm(sc, out_kernel_ms != nullptr);
+    if (!sc.rc)
+        k_pdist_window<<<L.blocks, PDIST_TILE * PDIST_TILE, L.lds_bytes, sc.stream>>>(n_rows, row_len, slide_span,
+            L.use_lds, d_rows, d_out);
+    tm.stop();
+    if (sc.sync()) return sc.rc;
+    if (out_kernel_ms) *out_kernel_ms = tm.ms();
+    return sc.get(out, d_out, (size_t)(n_rows * n_rows));
+}
+
+extern "C" int tba_pairwise_nanmean_dists(tba_engine *e, int64_t n_rows, int64_t row_len, const double *rows,
+    double *out_condensed, double *out_kernel_ms)
+{
+    if (const int rc = check_pdist(e, n_rows, row_len, rows)) return rc;
+    if (n_rows > 1 && !out_condensed) return set_err(TBA_E_ARG, "bad arguments");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (n_rows == 1) return TBA_OK;
+    const size_t n_pairs = (size_t)(n_rows * (n_rows - 1) / 2);
+    Scratch sc(e);
+    const double *d_rows = sc.in(rows, (size_t)(n_rows * row_len));
+    double *d_out = sc.out<double>(n_pairs);
+    if (sc.rc) return sc.rc;
+    const PdistLaunch L(n_rows, row_len);
+    KernelTimer tm(sc, out_kernel_ms != nullptr);
+    if (!sc.rc)
+        k_pdist_nanmean<<<L.blocks, PDIST_TILE * PDIST_TILE, L.lds_bytes, sc.stream>>>(n_rows, row_len, L.use_lds,
+            d_rows, d_out);
+    tm.stop();
+    if (sc.sync()) return sc.rc;
+    if (out_kernel_ms) *out_kernel_ms = tm.ms();
+    return sc.get(out_condensed, d_out, n_pairs);
 }

@@ -1,6 +1,7 @@
 """`tombo text_output browser_files` for reads held in memory: coverage (bedGraph), mean signal, signal SD, dwell
 and the sample - control difference (wiggle) per position and strand -- the file names, headers and number
-formats of the reference's writers (tombo/_text_output_commands.py:64-93, 230-388).  The per-position numbers come
+formats of the reference's writers (tombo/_text_output_commands.py:64-93, 230-388) -- and the FASTA of
+`tombo text_output signif_sequence_context` (write_most_signif, :395-420).  The per-position numbers come
 from the device (tombo_helper.GenomeTracks, csrc/k_tracks.h); the formatting stays in Python.
 
 A `reads_index` is {(chrm, strand): [reads]}.  `slots` / `ctrl_slots`: {slot name: {(chrm, strand): per-list
@@ -190,3 +191,22 @@ def write_all_browser_files(reads_index, ctrl_reads_index, wig_base, wig_types, 
                                 slots=slots.get(slot), engine=eng)
     if any(t in STATS_WIG_TYPES for t in wig_types):
         _write_stats_files(all_stats, wig_base, wig_types)
+
+
+def write_most_signif(stats, seqs_fp, num_regions, num_bases, reads_index=None, genome_index=None):
+    """`tombo text_output signif_sequence_context` (_text_output_commands.py:395-420): one FASTA record
+    `>{chrm}:{pos + 1}:{strand} {statistic text}` per most significant region of num_bases bases, the sequence in the
+    region's strand orientation.  stats: an open statistics container; seqs_fp: a text file open for writing.  The
+    sequence comes from genome_index (a th.Fasta; a region that runs past the chromosome end is cut there, one that
+    starts outside raises th.TomboError) or, without one, from the reads of reads_index that overlap the region
+    (th.get_region_seq: '-' where no read lies)."""
+    if genome_index is None and reads_index is None:
+        raise th.TomboError('Must provide either reads or a genome FASTA to output sequences.')
+    for chrm, start, end, strand, _, reg_text in stats.get_most_signif_regions(
+            num_bases, num_regions, prepend_loc_to_text=True):
+        if genome_index is not None:
+            seq = genome_index.get_seq(chrm, start, end, error_end=False)
+        else:
+            seq = th.get_region_seq([rd for rd in reads_index.get((chrm, strand), ())
+                                     if not (rd.start >= end or rd.end <= start)], start, end)
+        seqs_fp.write('>{0}\n{1}\n'.format(reg_text, seq if strand == '+' else th.rev_comp(seq)))

@@ -585,6 +585,25 @@ def get_region_seq(reads, start, end):
     return ''.join(bases)
 
 
+def get_unique_intervals(plot_intervals, covered_poss=None, num_regions=None):
+    """The regions, in order, that do not start inside a region kept before them and, with covered_poss
+    ({(chrm, strand): container of positions}), lie on covered positions only; at most num_regions
+    (tombo_helper.py:2045-2064).  Regions are the (chrm, start, end, strand, ...) tuples of
+    ModelStats.get_most_signif_regions."""
+    uniq_p_intervals, used_intervals = [], {}
+    for reg_data in plot_intervals:
+        chrm, start, end, strand = reg_data[:4]
+        interval_poss = list(range(start, end))
+        used = used_intervals.setdefault((chrm, strand), set())
+        if start not in used and (covered_poss is None or all(
+                pos in covered_poss[(chrm, strand)] for pos in interval_poss)):
+            uniq_p_intervals.append(reg_data)
+            used.update(interval_poss)
+        if num_regions is not None and len(uniq_p_intervals) >= num_regions:
+            break
+    return uniq_p_intervals
+
+
 # ---- genome tracks: coverage, mean signal / SD / dwell per position, sample - control ---------
 # (text_output browser_files, iter_cov_regs, get_largest_signal_differences; the pileup kernels
 # are csrc/k_tracks.h).  A `reads_index` is the {(chrm, strand): [reads]} mapping `read_index`

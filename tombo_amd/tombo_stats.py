@@ -164,6 +164,127 @@ def _engine(engine=None):
     return rq.get_engine()
 
 
+# ---- pair-wise distance and clustering (tombo_stats.py:126-196; the kernels are csrc/k_pdist.h) ----
+def transform_and_trim_stats(reg_stats, are_pvals, trim_value):
+    """:130-140, statement for statement: p-values become -log10 in a new array, likelihood ratios are trimmed in
+    the array that was passed"""
+    if are_pvals:
+        with np.errstate(divide='ignore'):
+            reg_stats = -np.log10(reg_stats)
+        nan_r_stats = np.nan_to_num(reg_stats)
+        reg_stats[nan_r_stats > trim_value] = trim_value
+    else:
+        nan_r_stats = np.nan_to_num(reg_stats)
+        reg_stats[nan_r_stats > trim_value] = trim_value
+        reg_stats[nan_r_stats < -trim_value] = -trim_value
+    return reg_stats
+
+
+def order_reads(reg_stats, engine=None):
+    """The order of the reads (rows) of a per-read statistics matrix in the per-read plots (:142-156): single
+    linkage over the NaN-aware mean absolute difference of every pair of rows, leaves in dendrogram order.  The
+    distances come from the device (Engine.pairwise_nanmean_dists); a pair of reads that share no position gets the
+    largest distance + 1, as in the reference."""
+    reg_stats = np.asarray(reg_stats)
+    if reg_stats.shape[0] == 1:
+        return [0]
+    try:
+        from scipy.cluster.hierarchy import single, leaves_list
+    except ImportError:
+        raise th.TomboError('order_reads needs scipy (scipy.cluster.hierarchy), which is not installed.')
+    r_dists = _engine(engine).pairwise_nanmean_dists(np.ascontiguousarray(reg_stats, dtype=np.float64))
+    with warnings.catch_warnings():   # (all pairs NaN: nanmax warns and gives NaN, as in the reference)
+        warnings.simplefilter('ignore', category=RuntimeWarning)
+        r_dists[np.isnan(r_dists)] = np.nanmax(r_dists) + 1
+    return leaves_list(single(r_dists))
+
+
+def sliding_window_dist(sig_diffs1, sig_diffs2, slide_span, num_bases):
+    """one pair of get_pairwise_dists with slide_span > 0, in numpy (:158-164)"""
+    return np.sqrt(min(np.sum(np.square(sig_diffs1[i1:i1 + num_bases] - sig_diffs2[i2:i2 + num_bases]))
+                       for i1 in range((slide_span * 2) + 1) for i2 in range((slide_span * 2) + 1)))
+
+
+def euclidian_dist(sig_diffs1, sig_diffs2):
+    """one pair of get_pairwise_dists with slide_span 0, in numpy (:166-169)"""
+    return np.sqrt(np.sum(np.square(sig_diffs1 - sig_diffs2)))
+
+
+def get_pairwise_dists(reg_sig_diffs, slide_span=0, engine=None):
+    """The distances between the signal-shift profiles of regions (:171-196) -> float64[R, R], row i holding the
+    distances to the regions j <= i and 0 beyond: the rows the reference's workers put on their queue, all from one
+    engine call.  slide_span None counts as 0.  Profiles of unequal length (a region cut by a chromosome end) raise
+    th.TomboError; the reference fails there with a broadcast error."""
+    slide_span = int(slide_span) if slide_span else 0
+    profiles = [np.asarray(v, dtype=np.float64) for v in reg_sig_diffs]
+    if len(profiles) == 0:
+        raise th.TomboError('No regions to compute distances between.')
+    row_len = profiles[0].shape[0]
+    for i, v in enumerate(profiles):
+        if v.ndim != 1 or v.shape[0] != row_len:
+            raise th.TomboError('Region %d holds %s signal differences where the first region holds %d: a region cut '
+                                'by the end of its chromosome cannot be compared.' % (
+                                    i, 'x'.join(str(d) for d in v.shape), row_len))
+    if slide_span < 0 or row_len - 2 * slide_span < 1:
+        raise th.TomboError('Regions of %d bases leave no window with a slide span of %d.' % (row_len, slide_span))
+    return _engine(engine).pairwise_window_dists(np.ascontiguousarray(np.stack(profiles)), slide_span)
+
+
+class _CoveredPositions(object):
+    """`pos in covered` over a boolean track, where the reference builds a set of every covered position"""
+    def __init__(self, covered=None):
+        self.covered = np.zeros(0, dtype=np.bool_) if covered is None else covered
+
+    def __contains__(self, pos):
+        return 0 <= pos < self.covered.shape[0] and bool(self.covered[pos])
+
+
+class _CoveredByBoth(dict):
+    """{(chrm, strand): _CoveredPositions}; a (chrm, strand) that one of the two indices lacks covers nothing (the
+    reference's plain dict raises KeyError for a significant region there)"""
+    def __missing__(self, key):
+        return _CoveredPositions()
+
+
+def cluster_most_signif_dists(stats, reads_index, ctrl_reads_index, num_regions, num_bases, slide_span=0,
+                              genome_index=None, with_seqs=False, engine=None):
+    """The data half of `tombo plot cluster_most_significant` (_plot_commands.py:2122-2214) -> (dists float64[R, R],
+    intervals, column names or None): the most significant regions of num_bases + 2 slide_span bases, those kept
+    that are covered by both sets of reads at every position and do not start inside an earlier one, the pairwise
+    distances of their sample - control signal differences.  with_seqs: the reference's column names
+    `seq::chrm::strand::start + 1`, the sequence over the region widened by two bases on either side, from
+    genome_index or else from the sample's reads (each listed twice, as the reference merges the region with
+    itself).  As in the reference, the genome index refuses (th.TomboError) the widened form of a region that starts
+    within two bases of its chromosome's start or ends within two of its end."""
+    eng = _engine(engine)
+    slide_span = int(slide_span) if slide_span else 0
+    width = num_bases + 2 * slide_span
+    plot_intervals = stats.get_most_signif_regions(width, num_regions)
+    cov, ctrl_cov = th.compute_coverage(reads_index, engine=eng), th.compute_coverage(ctrl_reads_index, engine=eng)
+    covered_poss = _CoveredByBoth()
+    for cs in set(cov).intersection(ctrl_cov):
+        n = min(cov[cs].shape[0], ctrl_cov[cs].shape[0])
+        covered_poss[cs] = _CoveredPositions((cov[cs][:n] > 0) & (ctrl_cov[cs][:n] > 0))
+    plot_intervals = th.get_unique_intervals(plot_intervals, covered_poss)
+    if len(plot_intervals) == 0:
+        raise th.TomboError('No significant region is covered by both sets of reads.')
+    col_names = None
+    if with_seqs:
+        col_names = []
+        for chrm, start, _, strand, _, _ in plot_intervals:
+            seq_start, seq_end = start - 2, start + 2 + width
+            if genome_index is not None:
+                seq = genome_index.get_seq(chrm, seq_start, seq_end)
+            else:
+                reads = [rd for rd in reads_index.get((chrm, strand), ())
+                         if not (rd.start >= seq_end or rd.end <= seq_start)]
+                seq = th.get_region_seq(reads + reads, seq_start, seq_end)
+            col_names.append('::'.join((seq, chrm, strand, str(start + 1))))
+    signal_diffs = th.get_signal_differences(reads_index, ctrl_reads_index, engine=eng)
+    reg_sig_diffs = [signal_diffs[(chrm, strand)][start:start + width] for chrm, start, _, strand, _, _ in plot_intervals]
+    return get_pairwise_dists(reg_sig_diffs, slide_span, engine=eng), plot_intervals, col_names
+
+
 def get_dynamic_prog_params(match_evalue):
     return HALF_NORM_EXPECTED_VAL + match_evalue, match_evalue
 
@@ -1243,6 +1364,24 @@ class ModelStats(_BlockStore):
 
     def _get_chrm_name(self, pos_stat):
         return self.most_signif_chrm_map[pos_stat['chrm']]
+
+    def iter_stat_seqs(self, genome_index, before_bases, after_bases, include_pos=True):
+        """the genome sequence around every stored most significant site, in strand orientation (:2811-2848):
+        (seq, chrm, strand, start, end), or seq alone without include_pos.  A site whose window the genome index
+        refuses (th.TomboError: it leaves the chromosome) is skipped."""
+        for pos_stat in self.most_signif_stats:
+            chrm, strand, pos = self._get_chrm_name(pos_stat), pos_stat['strand'].decode(), int(pos_stat['pos'])
+            if strand == '+':
+                start, end = pos - before_bases, pos + after_bases + 1
+            else:
+                start, end = pos - after_bases, pos + before_bases + 1
+            try:
+                stat_seq = genome_index.get_seq(chrm, start, end)
+            except th.TomboError:
+                continue
+            if strand != '+':
+                stat_seq = th.rev_comp(stat_seq)
+            yield (stat_seq, chrm, strand, start, end) if include_pos else stat_seq
 
     def iter_most_signif_sites(self):
         """(chrm, strand, pos, transformed statistic) of the stored most significant sites.  (:2850-2859 applies
