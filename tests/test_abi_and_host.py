@@ -505,3 +505,110 @@ def test_pinned_pool_budget_counts_what_it_allocates_and_divides_by_the_node_ran
     assert _native.PinnedPool().budget >= one and one <= (16 << 30)
     host = os.sysconf('SC_PHYS_PAGES') * os.sysconf('SC_PAGE_SIZE')
     assert one == min(host // 4 // 8, 16 << 30)
+
+
+def _header_declarations():
+    """[(return type, name, [parameter text])] of every `ret tba_name(args);` of include/tombo_amd.h"""
+    hdr = open(os.path.join(ROOT, 'include', 'tombo_amd.h')).read()
+    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    decls = re.findall(r'^[ \t]*((?:const[ \t]+)?\w+[ \t]*\*?)[ \t]*(tba_[a-z0-9_]+)[ \t]*\(([^)]*)\)[ \t]*;', hdr, flags=re.M)
+    return [(' '.join(ret.replace('*', ' * ').split()), name,
+             [] if args.strip() == 'void' else [' '.join(a.split()) for a in args.split(',')])
+            for ret, name, args in decls], hdr
+
+
+def test_prototype_table_matches_the_header():
+    """_native.PROTOTYPES against include/tombo_amd.h, declaration by declaration: the same entries, the same number
+    of parameters, scalars and return types by width, handles / void * / pointers to pointers as c_void_p, struct
+    pointers as POINTER of their mirror, typed data pointers by element type and const-ness"""
+    import ctypes as C
+    from tombo_amd import _native
+    decls, hdr = _header_declarations()
+    names = [d[1] for d in decls]
+    assert len(decls) >= 84 and len(set(names)) == len(names)
+    assert set(names) == set(re.findall(r'\b(tba_[a-z0-9_]+)\s*\(', hdr))   # (test_library_exports_every_declared_symbol)
+    assert set(_native.PROTOTYPES) == set(names)
+    assert list(_native.PROTOTYPES) == names                                # the header's order
+    scalars = {'int': C.c_int, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64, 'double': C.c_double}
+    returns = {'int': C.c_int, 'int64_t': C.c_int64, 'void': None, 'const char *': C.c_char_p}
+    structs = {'tba_params': _native.Params, 'tba_opts': _native.Opts, 'tba_read_result': _native.ReadResult,
+               'tba_synth_params': _native.SynthParams}
+    elems = {'double': np.float64, 'int64_t': np.int64, 'int32_t': np.int32, 'uint32_t': np.uint32,
+             'uint8_t': np.uint8, 'int8_t': np.int8}
+    n_typed = 0
+    for ret, name, params in decls:
+        restype, argtypes = _native.PROTOTYPES[name]
+        assert restype is returns[ret], name
+        assert len(argtypes) == len(params), name
+        for k, (text, got) in enumerate(zip(params, argtypes)):
+            toks = re.findall(r'\w+|\*', text)[:-1]          # (the last word is the parameter's name)
+            base = [t for t in toks if t not in ('const', '*')]
+            assert len(base) == 1, (name, text)
+            where = '%s, parameter %d: %s' % (name, k, text)
+            if toks.count('*') == 0:
+                assert got is scalars[base[0]], where
+            elif toks.count('*') == 2 or base[0] in ('void', 'tba_engine', 'tba_synth'):
+                assert got is C.c_void_p, where
+            elif base[0] in structs:
+                assert got is C.POINTER(structs[base[0]]), where
+            else:
+                n_typed += 1
+                assert isinstance(got, _native._Ptr), where
+                assert got.dtype == np.dtype(elems[base[0]]), where
+                assert got.const == (toks[0] == 'const'), where
+    assert n_typed > 250
+    lib = _native.lib()
+    for name, (restype, argtypes) in _native.PROTOTYPES.items():            # ... and lib() has installed it
+        assert getattr(lib, name).restype is restype and list(getattr(lib, name).argtypes) == list(argtypes), name
+
+
+def test_pointer_parameters_take_arrays_and_refuse_what_was_reinterpreted():
+    """the typed pointer parameters: a right array, None, a ctypes array and byref pass; another dtype, a strided
+    array, a read-only output, a bare integer -- and a float for an int64_t -- are ctypes.ArgumentError before the call"""
+    import ctypes as C
+    from tombo_amd import _native, planner, tombo_stats as ts, tombo_helper as th
+    lib = _native.lib()
+    p = _native.make_params(ts.load_resquiggle_parameters(th.seqSampleType('DNA', False)))
+    o = _native.make_opts(outlier_thresh=5.0)
+    # host-only entries: arrays as they are, ctypes arrays, byref, None
+    want = planner.exact_bytes([3000, 9000], [300, 900], p, o, 6)
+    out = C.c_double(0)
+    assert lib.tba_batch_footprint(p, C.byref(o), 6, 0, 2, (C.c_int64 * 2)(3000, 9000), np.array([300, 900]),
+                                   C.byref(out)) == 0 and out.value == want > 0
+    sp = _native.make_synth_params()
+    thr, c = _native.synth_tables(sp)
+    thr2, c2 = (C.c_uint32 * 256)(), np.zeros(1)
+    assert lib.tba_synth_dwell_thresholds(sp, thr2, 256, c2) == 0 and list(thr2) == thr.tolist() and c2[0] == c
+    assert lib.tba_synth_dwell_thresholds(C.byref(sp), thr2, 256, None) == 0
+    assert lib.tba_abi_sizes(None, 4) == -1
+    for bad in (np.zeros(256, np.int32), np.zeros(512, np.uint32)[::2], 256, 256.0, [0] * 256):
+        with pytest.raises(C.ArgumentError):
+            lib.tba_synth_dwell_thresholds(sp, bad, 256, None)
+    ro = np.zeros(256, np.uint32)
+    ro.flags.writeable = False
+    with pytest.raises(C.ArgumentError):
+        lib.tba_synth_dwell_thresholds(sp, ro, 256, None)
+    with pytest.raises(C.ArgumentError):
+        lib.tba_batch_footprint(p, o, 6, 0, 2, np.array([3000, 9000], np.int32), np.array([300, 900]), C.byref(out))
+    # an engine entry: the conversion fails before the call (no engine, no GPU)
+    i8, s8, f8 = (lambda n: np.zeros(n, np.int64)), (lambda n: np.zeros(n, np.int8)), (lambda n: np.zeros(n))
+    good = [None, 0, 1, 0, 1, 1, i8(1), i8(1), s8(1), i8(2), 1, i8(1), s8(1), s8(1), i8(2), f8(8), 1e-10,
+            f8(1), i8(1), i8(1), i8(1), i8(1)]
+    assert lib.tba_group_level_stats(*good) == -1          # (a NULL engine is TBA_E_ARG: every argument converted)
+    ro = np.zeros(1)
+    ro.flags.writeable = False
+    for k, bad in ((15, np.zeros(8, np.float32)), (15, np.arange(8.0)[::2]), (17, ro), (6, 12345), (3, 0.0),
+                   (8, np.zeros(1, np.uint8)), (18, np.zeros(1, np.int32)), (15, [0.0] * 8)):
+        with pytest.raises(C.ArgumentError):
+            lib.tba_group_level_stats(*(good[:k] + [bad] + good[k + 1:]))
+
+
+def test_int64_scalars_arrive_whole():
+    """a count above 2^31 (and above 2^32) reaches the library as it is: the footprint of one read of 2^33 samples"""
+    from tombo_amd import planner, _native, tombo_stats as ts, tombo_helper as th
+    p = _native.make_params(ts.load_resquiggle_parameters(th.seqSampleType('DNA', False)))
+    o = _native.make_opts(outlier_thresh=5.0)
+    assert planner.exact_bytes([2 ** 33], [1000], p, o, 6) > 2 ** 33
+    eng = object.__new__(_native.Engine)                   # (footprint needs the engine's k-mer width only)
+    eng.kmer_width = 6
+    assert eng.footprint(p, o, [2 ** 33], [1000]) == planner.exact_bytes([2 ** 33], [1000], p, o, 6)

@@ -108,7 +108,8 @@ def test_c_entry_refuses_indices_outside_the_batch():
     ent_pos, ent_key out of range and offsets that do not start at 0 give TBA_E_ARG before anything reaches the
     device"""
     import ctypes as C
-    from tombo_amd._native import _p, i64, f64
+    from tombo_amd._native import i64, f64
+    _p = lambda a, t: a.ctypes.data_as(C.POINTER(t))   # noqa: E731
     eng = rq.get_engine()
     good = [np.ascontiguousarray(a) for a in random_call(np.random.default_rng(4), 20, 2, 8, 30, 40, False)[1:11]]
     rs, rm, off, m, roff, rr, pr, pg, ep, ek = good

@@ -31,8 +31,6 @@ def eng():
 
 
 def test_tile_constants_of_the_library(eng):
-    eng._L.tba_pdist_tile.restype = _native.i64
-    eng._L.tba_pdist_lds_row_max.restype = _native.i64
     assert eng._L.tba_pdist_tile() == T and eng._L.tba_pdist_lds_row_max() == LDS_MAX
 
 
@@ -157,15 +155,14 @@ def test_host_functions_on_the_device(eng):
 def _c_window(eng, n_rows, row_len, slide_span, rows, out, e=True):
     ms = _native.f64(-1.0)
     rc = eng._L.tba_pairwise_window_dists(eng._h if e else None, _native.i64(n_rows), _native.i64(row_len),
-                                          _native.i64(slide_span), _native._p(rows, _native.f64),
-                                          _native._p(out, _native.f64), C.byref(ms))
+                                          _native.i64(slide_span), rows, out, C.byref(ms))
     return rc, ms.value
 
 
 def _c_nanmean(eng, n_rows, row_len, rows, out, e=True):
     ms = _native.f64(-1.0)
     rc = eng._L.tba_pairwise_nanmean_dists(eng._h if e else None, _native.i64(n_rows), _native.i64(row_len),
-                                           _native._p(rows, _native.f64), _native._p(out, _native.f64), C.byref(ms))
+                                           rows, out, C.byref(ms))
     return rc, ms.value
 
 

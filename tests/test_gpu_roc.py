@@ -65,7 +65,6 @@ def check_rank_counts(eng, stats, has_mod, ranks):
 
 
 def test_sort_tile_of_the_library(eng):
-    eng._L.tba_roc_sort_tile.restype = _native.i64
     assert eng._L.tba_roc_sort_tile() == T
 
 
@@ -123,9 +122,7 @@ def test_rank_counts_empty_and_bad_ranks(eng):
     st, hm, rk = np.zeros(3), np.zeros(3, dtype=np.uint8), np.array([2, 1], dtype=np.int64)
     out, tot, nn = np.zeros(2, dtype=np.int64), _native.i64(0), _native.i64(0)
     import ctypes as C
-    rc_ = eng._L.tba_roc_rank_counts(eng._h, _native.i64(3), _native._p(st, _native.f64), _native._p(hm, C.c_uint8),
-                                     _native.i64(2), _native._p(rk, _native.i64), _native._p(out, _native.i64),
-                                     C.byref(tot), C.byref(nn), None)
+    rc_ = eng._L.tba_roc_rank_counts(eng._h, _native.i64(3), st, hm, _native.i64(2), rk, out, C.byref(tot), C.byref(nn), None)
     assert rc_ == -1 and b'ranks' in eng._L.tba_last_error()
 
 
@@ -216,7 +213,7 @@ def test_location_in_both_lists(eng):
 def test_c_entries_validate_before_the_empty_return(eng):
     """no record: nothing is launched, but a bad motif, bad sequence offsets or a bad location slice are still refused"""
     import ctypes as C
-    i64, f64, p = _native.i64, _native.f64, _native._p
+    i64, f64, p = _native.i64, _native.f64, lambda a, t: a.ctypes.data_as(C.POINTER(t))
     minus, ss, rec_off = np.zeros(1, np.uint8), np.zeros(1, np.int64), np.zeros(2, np.int64)
     seq, sets = np.zeros(4, np.uint8), np.array([2, 4], dtype=np.uint8)
     out_s, out_l, counts = np.zeros(1), np.zeros(1, np.uint8), np.zeros(1, np.int64)

@@ -17,9 +17,6 @@ import numpy as np
 
 from . import _native, errors
 
-_pd, _pi = C.POINTER(C.c_double), C.POINTER(C.c_int64)
-
-
 def _engine():
     from .resquiggle import get_engine
     return get_engine()
@@ -56,9 +53,7 @@ def c_base_z_scores(b_sig, ref_mean, ref_sd, do_winsorize_z=False, max_half_z_sc
     out = np.empty(b_sig.shape[0], dtype=np.float64)
     eng = _engine()
     _raise(eng._L.tba_c_base_z_scores(
-        eng._h, b_sig.ctypes.data_as(_pd), C.c_int64(b_sig.shape[0]), C.c_double(ref_mean),
-        C.c_double(ref_sd), C.c_int(bool(do_winsorize_z)), C.c_double(max_half_z_score),
-        out.ctypes.data_as(_pd)), eng)
+        eng._h, b_sig, b_sig.shape[0], ref_mean, ref_sd, bool(do_winsorize_z), max_half_z_score, out), eng)
     return out
 
 
@@ -69,10 +64,7 @@ def c_banded_forward_pass(shifted_z_scores, event_starts, skip_pen, stay_pen):
     fwd = np.empty((n_bases + 1, bw), dtype=np.float64)
     tb = np.empty((n_bases + 1, bw), dtype=np.int64)
     eng = _engine()
-    _raise(eng._L.tba_c_banded_forward_pass(
-        eng._h, z.ctypes.data_as(_pd), C.c_int64(n_bases), C.c_int64(bw), es.ctypes.data_as(_pi),
-        C.c_double(skip_pen), C.c_double(stay_pen), fwd.ctypes.data_as(_pd),
-        tb.ctypes.data_as(_pi)), eng)
+    _raise(eng._L.tba_c_banded_forward_pass(eng._h, z, n_bases, bw, es, skip_pen, stay_pen, fwd, tb), eng)
     return fwd, tb
 
 
@@ -83,9 +75,7 @@ def c_banded_traceback(fwd_pass_tb, event_starts, band_pos, band_boundary_thresh
     out = np.empty(n_bases + 1, dtype=np.int64)
     eng = _engine()
     _raise(eng._L.tba_c_banded_traceback(
-        eng._h, tb.ctypes.data_as(_pi), C.c_int64(n_bases), C.c_int64(bw), es.ctypes.data_as(_pi),
-        C.c_int64(int(band_pos)), C.c_int64(int(band_boundary_thresh)), out.ctypes.data_as(_pi)),
-        eng)
+        eng._h, tb, n_bases, bw, es, int(band_pos), int(band_boundary_thresh), out), eng)
     return out
 
 
@@ -104,13 +94,8 @@ def c_adaptive_banded_forward_pass(
     # return_z_scores (pyx:339,387-388,409-410): the shifted z-scores of the rows the pass computed
     z = np.empty((n_bases - int(start_seq_pos), bw), dtype=np.float64) if return_z_scores else None
     _raise(eng._L.tba_c_adaptive_banded_forward_pass_z(
-        eng._h, fwd_pass.ctypes.data_as(_pd), fwd_pass_tb.ctypes.data_as(_pi), C.c_int64(n_bases),
-        C.c_int64(bw), event_starts.ctypes.data_as(_pi), ev.ctypes.data_as(_pd),
-        C.c_int64(ev.shape[0]), mu.ctypes.data_as(_pd), sd.ctypes.data_as(_pd),
-        C.c_double(z_shift), C.c_double(skip_pen), C.c_double(stay_pen),
-        C.c_int64(int(start_seq_pos)), C.c_double(mask_fill_z_score),
-        C.c_int(bool(do_winsorize_z)), C.c_double(max_half_z_score),
-        None if z is None else z.ctypes.data_as(_pd)), eng)
+        eng._h, fwd_pass, fwd_pass_tb, n_bases, bw, event_starts, ev, ev.shape[0], mu, sd, z_shift, skip_pen,
+        stay_pen, int(start_seq_pos), mask_fill_z_score, bool(do_winsorize_z), max_half_z_score, z), eng)
     return z
 
 
@@ -137,14 +122,9 @@ def c_reg_z_scores(r_sig, r_ref_means, r_ref_sds, r_b_starts, reg_start, reg_end
     z = np.empty(cap, np.float64)
     eng = _engine()
     _raise_index(eng._L.tba_c_reg_z_scores(
-        eng._h, r_sig.ctypes.data_as(_pd), C.c_int64(r_sig.shape[0]), mu.ctypes.data_as(_pd),
-        sd.ctypes.data_as(_pd), C.c_int64(min(mu.shape[0], sd.shape[0])),
-        starts.ctypes.data_as(_pi), C.c_int64(starts.shape[0]), C.c_int64(reg_start),
-        C.c_int64(reg_end), C.c_int64(int(max_base_shift)), C.c_int64(int(min_obs_per_base)),
-        C.c_int(max_half_z_score is not None),
-        C.c_double(0.0 if max_half_z_score is None else max_half_z_score),
-        bounds.ctypes.data_as(_pi), off.ctypes.data_as(_pi), z.ctypes.data_as(_pd),
-        C.c_int64(cap)), eng)
+        eng._h, r_sig, r_sig.shape[0], mu, sd, min(mu.shape[0], sd.shape[0]), starts, starts.shape[0], reg_start,
+        reg_end, int(max_base_shift), int(min_obs_per_base), max_half_z_score is not None,
+        0.0 if max_half_z_score is None else max_half_z_score, bounds, off, z, cap), eng)
     return [(z[off[i]:off[i + 1]].copy(), (int(bounds[i, 0]), int(bounds[i, 1])))
             for i in range(n)]
 
@@ -163,10 +143,7 @@ def c_base_forward_pass(b_data, b_start, b_end, prev_b_data, prev_b_start, prev_
     fwd, ld = np.empty(b_len, np.float64), np.empty(b_len, np.int64)
     eng = _engine()
     _raise_index(eng._L.tba_c_base_forward_pass(
-        eng._h, b.ctypes.data_as(_pd), C.c_int64(b_start), C.c_int64(b_end),
-        pb.ctypes.data_as(_pd), C.c_int64(prev_b_start), C.c_int64(prev_b_end),
-        pf.ctypes.data_as(_pd), pl.ctypes.data_as(_pi), C.c_int64(int(min_obs_per_base)),
-        fwd.ctypes.data_as(_pd), ld.ctypes.data_as(_pi)), eng)
+        eng._h, b, b_start, b_end, pb, prev_b_start, prev_b_end, pf, pl, int(min_obs_per_base), fwd, ld), eng)
     return fwd, ld
 
 
@@ -177,8 +154,6 @@ def c_base_traceback(curr_b_data, curr_start, next_b_data, next_start, next_end,
     out = C.c_int64(-1)
     eng = _engine()
     _raise_index(eng._L.tba_c_base_traceback(
-        eng._h, cur.ctypes.data_as(_pd), C.c_int64(cur.shape[0]), C.c_int64(int(curr_start)),
-        nxt.ctypes.data_as(_pd), C.c_int64(nxt.shape[0]), C.c_int64(int(next_start)),
-        C.c_int64(int(next_end)), C.c_int64(int(sig_start)), C.c_int64(int(min_obs_per_base)),
-        C.byref(out)), eng)
+        eng._h, cur, cur.shape[0], int(curr_start), nxt, nxt.shape[0], int(next_start), int(next_end),
+        int(sig_start), int(min_obs_per_base), C.byref(out)), eng)
     return None if out.value < 0 else int(out.value)

@@ -12,11 +12,9 @@ the per-kernel C ABI (tba_c_*):
   c_calc_llh_ratio, c_calc_llh_ratio_const_var, c_calc_scaled_llh_ratio_const_var  :277-358
                              (row N4: plus llh_ratio_windows, many windows per call)
 """
-import ctypes as C
-
 import numpy as np
 
-from ._c_dynamic_programming import _engine, _f8, _i8, _raise, _pd, _pi
+from ._c_dynamic_programming import _engine, _f8, _i8, _raise
 
 
 def c_new_means(norm_signal, new_segs):
@@ -24,9 +22,7 @@ def c_new_means(norm_signal, new_segs):
     n = segs.shape[0] - 1
     out = np.empty(n, dtype=np.float64)
     eng = _engine()
-    _raise(eng._L.tba_c_new_means(eng._h, sig.ctypes.data_as(_pd), C.c_int64(sig.shape[0]),
-                                  segs.ctypes.data_as(_pi), C.c_int64(n),
-                                  out.ctypes.data_as(_pd)), eng)
+    _raise(eng._L.tba_c_new_means(eng._h, sig, sig.shape[0], segs, n, out), eng)
     return out
 
 
@@ -34,9 +30,7 @@ def c_apply_outlier_thresh(raw_signal, lower_lim, upper_lim):
     sig = _f8(raw_signal, 'raw_signal')
     out = np.empty(sig.shape[0], dtype=np.float64)
     eng = _engine()
-    _raise(eng._L.tba_c_apply_outlier_thresh(
-        eng._h, sig.ctypes.data_as(_pd), C.c_int64(sig.shape[0]), C.c_double(lower_lim),
-        C.c_double(upper_lim), out.ctypes.data_as(_pd)), eng)
+    _raise(eng._L.tba_c_apply_outlier_thresh(eng._h, sig, sig.shape[0], lower_lim, upper_lim, out), eng)
     return out
 
 
@@ -45,9 +39,7 @@ def _cpts(fn, raw_signal, min_base_obs, running_stat_width, num_cpts):
     out = np.empty(int(num_cpts), dtype=np.int64)
     eng = _engine()
     _raise(getattr(eng._L, fn)(
-        eng._h, sig.ctypes.data_as(_pd), C.c_int64(sig.shape[0]), C.c_int64(int(min_base_obs)),
-        C.c_int64(int(running_stat_width)), C.c_int64(int(num_cpts)), out.ctypes.data_as(_pi)),
-        eng)
+        eng._h, sig, sig.shape[0], int(min_base_obs), int(running_stat_width), int(num_cpts), out), eng)
     return out
 
 
@@ -73,9 +65,7 @@ def c_new_mean_stds(norm_signal, new_segs):
     n = segs.shape[0] - 1
     means, stds = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
     eng = _engine()
-    _raise(eng._L.tba_c_new_mean_stds(
-        eng._h, sig.ctypes.data_as(_pd), C.c_int64(sig.shape[0]), segs.ctypes.data_as(_pi),
-        C.c_int64(n), means.ctypes.data_as(_pd), stds.ctypes.data_as(_pd)), eng)
+    _raise(eng._L.tba_c_new_mean_stds(eng._h, sig, sig.shape[0], segs, n, means, stds), eng)
     return means, stds
 
 
@@ -86,9 +76,7 @@ def c_compute_slopes(r_event_means, r_model_means, max_slope=1000.0):
     assert md.shape[0] == n
     out = np.empty(n * (n - 1) // 2, dtype=np.float64)
     eng = _engine()
-    _raise(eng._L.tba_c_compute_slopes(
-        eng._h, ev.ctypes.data_as(_pd), md.ctypes.data_as(_pd), C.c_int64(n),
-        C.c_double(max_slope), out.ctypes.data_as(_pd)), eng)
+    _raise(eng._L.tba_c_compute_slopes(eng._h, ev, md, n, max_slope, out), eng)
     return out
 
 

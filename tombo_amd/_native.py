@@ -82,6 +82,12 @@ class ReadResult(C.Structure):
                 ('sig_match_score', f64)]
 
 
+class SynthParams(C.Structure):
+    _fields_ = [('mean_dwell', i64), ('min_dwell', i64), ('n_lead', i64), ('n_trail', i64),
+                ('scale', f64), ('offset', f64), ('noise_sd', f64), ('dac_per_pa', f64), ('dac_offset', f64),
+                ('reverse', i32), ('pad', i32)]
+
+
 RESULT_DTYPE = np.dtype([
     ('status', np.int32), ('norm_params_changed', np.int32),
     ('read_start_rel_to_raw', np.int64), ('norm_len', np.int64),
@@ -141,6 +147,144 @@ _GET_SHAPES = {
     GET_ED_TAKEN_POS: (np.int32, ('raw_x2',)), GET_ED_N_TAKEN: (np.int64, ('n',)),
 }
 
+class _Ptr(object):
+    """argtypes entry of a typed data pointer (`const double *`, `int64_t *`, ...).  Takes None (NULL), a C-contiguous
+    numpy array of exactly that element type (writeable unless the header says const), a DeviceArray of that type,
+    and any ctypes object as it is (byref, arrays, pointers); ctypes reports anything else as ArgumentError"""
+    _CTYPES = (C.c_int.__mro__[-2], type(C.byref(C.c_int())))   # (_ctypes._CData, and what byref makes)
+
+    def __init__(self, dtype, const):
+        self.dtype, self.const = np.dtype(dtype), const
+
+    def from_param(self, a):
+        if a is None or isinstance(a, self._CTYPES):
+            return a
+        if isinstance(a, np.ndarray):
+            if a.dtype == self.dtype and a.flags.c_contiguous and (self.const or a.flags.writeable):
+                return C.c_void_p(a.ctypes.data)
+        elif isinstance(a, DeviceArray) and a.dtype == self.dtype:
+            return C.c_void_p(a.ptr)
+        raise TypeError('expected None, a C-contiguous %s%s array or a ctypes object, got %s' % (
+            '' if self.const else 'writeable ', self.dtype, getattr(a, 'dtype', type(a).__name__)))
+
+
+def _prototypes():
+    """entry name -> (restype, argtypes) of every declaration of include/tombo_amd.h, in its order (checked against
+    the header by tests/test_abi_and_host.py).  n / q / u / d: int, int64_t, uint64_t, double; v: handles, void * and
+    pointers to pointers; D Q I B, with c in front when the header says const: double, int64_t, int32_t, uint8_t *"""
+    n, q, u, d, v = C.c_int, i64, C.c_uint64, f64, C.c_void_p
+    D, Q, I, B = (_Ptr(t, False) for t in (np.float64, np.int64, np.int32, np.uint8))
+    cD, cQ, cI, cB, cS = (_Ptr(t, True) for t in (np.float64, np.int64, np.int32, np.uint8, np.int8))
+    P, O, R, SP = (C.POINTER(t) for t in (Params, Opts, ReadResult, SynthParams))
+    pileup = [q, cQ, cQ, cS, cQ, q, cQ, cS]     # n_regions .. reg_read_off, n_reads, read_start, read_strand
+    site_outs = [D, Q, Q, Q, D, Q, Q]           # out_frac .. out_n_stats
+    fwd_pass = [v, D, Q, q, q, Q, cD, q, cD, cD, d, d, d, q, d, n, d]
+    return {
+        # ---- engine ----
+        'tba_engine_create': (n, [n, v]),
+        'tba_engine_destroy': (None, [v]),
+        'tba_last_error': (C.c_char_p, []),
+        'tba_device_count': (n, []),
+        'tba_device_mem': (n, [v, Q, Q]),
+        'tba_engine_held_bytes': (n, [v, Q]),
+        'tba_engine_set_sharing': (n, [v, n]),
+        'tba_engine_set_dispatch': (n, [v, q, q]),
+        'tba_engine_get_dispatch': (n, [v, Q, Q]),
+        'tba_engine_set_side_stream': (n, [v, n]),
+        'tba_engine_last_side_stream': (n, [v]),
+        'tba_engine_last_dp_lowreg': (n, [v]),
+        'tba_c_last_ed_form': (n, [v]),
+        'tba_set_model': (n, [v, cD, cD, q, q]),
+        # ---- host memory for streaming ----
+        'tba_pinned_alloc': (n, [q, v]),
+        'tba_pinned_free': (n, [v]),
+        # ---- batch pipeline ----
+        'tba_batch_upload': (n, [v, P, O, q, cD, cQ, cB, cQ, cD, cI, cQ, cQ, cQ]),
+        'tba_batch_upload_async': (n, [v, P, O, q, v, n, cQ, cB, cQ, cD, cI, cQ, cQ, cQ]),
+        'tba_batch_footprint': (n, [P, O, q, n, q, cQ, cQ, D]),
+        'tba_batch_run': (n, [v]),
+        'tba_batch_enqueue': (n, [v]),
+        'tba_batch_sync': (n, [v]),
+        'tba_batch_wait_for': (n, [v, v]),
+        'tba_batch_query': (n, [v]),
+        'tba_batch_download': (n, [v, I, Q, Q, D, Q, D, D, I]),
+        'tba_batch_download_async': (n, [v, R, I, Q, D]),
+        'tba_batch_get': (n, [v, n, v, q]),
+        # ---- stepwise execution ----
+        'tba_batch_run_stages': (n, [v, n, n]),
+        'tba_batch_put': (n, [v, n, v, q, cQ]),
+        'tba_set_num_events': (n, [v, cQ, q]),
+        'tba_batch_base_stats': (n, [v, D, D, q]),
+        'tba_batch_stats': (n, [v, D, D]),
+        # ---- per-kernel entry points ----
+        'tba_c_adaptive_banded_forward_pass': (n, fwd_pass),
+        'tba_c_adaptive_banded_forward_pass_z': (n, fwd_pass + [D]),
+        'tba_c_banded_forward_pass': (n, [v, cD, q, q, cQ, d, d, D, Q]),
+        'tba_c_banded_traceback': (n, [v, cQ, q, q, cQ, q, q, Q]),
+        'tba_c_base_z_scores': (n, [v, cD, q, d, d, n, d, D]),
+        'tba_c_new_means': (n, [v, cD, q, cQ, q, D]),
+        'tba_c_apply_outlier_thresh': (n, [v, cD, q, d, d, D]),
+        'tba_c_valid_cpts_w_cap': (n, [v, cD, q, q, q, q, Q]),
+        'tba_c_valid_cpts_w_cap_t_test': (n, [v, cD, q, q, q, q, Q]),
+        'tba_c_new_mean_stds': (n, [v, cD, q, cQ, q, D, D]),
+        'tba_c_compute_slopes': (n, [v, cD, cD, q, d, D]),
+        'tba_c_reg_z_scores': (n, [v, cD, q, cD, cD, q, cQ, q, q, q, q, q, n, d, Q, Q, D, q]),
+        'tba_c_base_forward_pass': (n, [v, cD, q, q, cD, q, q, cD, cQ, q, D, Q]),
+        'tba_c_base_traceback': (n, [v, cD, q, q, cD, q, q, q, q, q, Q]),
+        # ---- row N4: log-likelihood ratios; per-read p-values ----
+        'tba_llh_ratio_windows': (n, [v, n, cD, cD, cD, cD, cD, q, q, cQ, q, cD, D]),
+        'tba_read_pvals': (n, [v, cD, cD, cD, cQ, q, q, n, d, D]),
+        # ---- level pileups across reads ----
+        'tba_group_level_stats': (n, [v, n, n, q, q] + pileup + [cS, cQ, cD, d, D, Q, Q, Q, Q]),
+        'tba_reads_ref_levels': (n, [v, n, q, q] + pileup + [cQ, cD, cD, cD, d, d, D, D, Q]),
+        # ---- per-site modified fractions ----
+        'tba_site_fractions': (n, [v, n, q, cQ, cQ, cD, cD, cD, cQ, q, cQ, cQ, q, n, d,
+                                   n, cD, cD, cD, q, q, cQ, q, cD, cQ, cQ, d, cD, cD] + site_outs + [D]),
+        'tba_site_aggregate': (n, [v, q, cQ, cQ, cQ, v, d, cD, n, cD] + site_outs + [D]),
+        # ---- ROC / precision-recall ----
+        'tba_roc_motif_labels': (n, [v, q, cB, cQ, cQ, cB, cQ, cQ, cD, q, cI, cB, n, n, D, B, Q, Q, D]),
+        'tba_roc_loc_labels': (n, [v, q, cQ, cQ, q, cQ, q, cQ, cQ, cD, D, B, Q, Q, D]),
+        'tba_roc_rank_counts': (n, [v, q, cD, cB, q, cQ, Q, Q, Q, D]),
+        'tba_roc_sort_tile': (q, []),
+        # ---- pairwise distances ----
+        'tba_pairwise_window_dists': (n, [v, q, q, q, cD, D, D]),
+        'tba_pairwise_nanmean_dists': (n, [v, q, q, cD, D, D]),
+        'tba_pdist_tile': (q, []),
+        'tba_pdist_lds_row_max': (q, []),
+        # ---- alternate-base model estimation ----
+        'tba_kmer_levels': (n, [v, cD, cB, cQ, q, q, q, cB, Q, Q, D, q]),
+        'tba_kde_eval': (n, [v, cD, cQ, q, cD, q, d, D]),
+        # ---- genome tracks ----
+        'tba_tracks_begin': (n, [v, q, q, n]),
+        'tba_tracks_add': (n, [v, q, cQ, cQ, cB, cQ, v, q, cQ, cI]),
+        'tba_tracks_finish': (n, [v, D, D, Q, Q]),
+        'tba_tracks_kernel_ms': (n, [v, D]),
+        'tba_tracks_compact': (n, [v, n, v, q, Q, v, Q]),
+        'tba_tracks_diff': (n, [v, cD, cD, q, D]),
+        'tba_tracks_topn': (n, [v, cD, cD, q, q, Q, D, Q]),
+        # ---- estimate_kmer_model / estimate_motif_alt_model ----
+        'tba_region_key_levels': (n, [v, n, q, cQ, cB, cQ, cD, q, cQ, cQ, q, cQ, cQ, q, cQ, cQ, q, Q, Q, D, D]),
+        'tba_segment_medians': (n, [v, cD, cQ, q, D]),
+        'tba_batch_de_novo_stats': (n, [v, q, d, D, q]),
+        # ---- the worker's per-read preparation; host-side packing ----
+        'tba_identify_stalls': (n, [v, v, n, q, q, q, q, d, q, q, Q, q, Q]),
+        'tba_pack_reads': (n, [q, v, n, n, cQ, v, v, cQ, B, n]),
+        'tba_unpack_reads': (n, [q, v, q, cQ, cQ, v, n]),
+        # ---- synthetic reads made on the device ----
+        'tba_synth_create': (n, [n, cD, q, v]),
+        'tba_synth_destroy': (None, [v]),
+        'tba_synth_generate': (n, [v, SP, u, q, q, cQ, n, Q, Q, v, v]),
+        'tba_synth_download': (n, [v, v, B]),
+        'tba_synth_dwell_thresholds': (n, [SP, _Ptr(np.uint32, False), q, D]),
+        # ---- ABI check, self-tests ----
+        'tba_abi_sizes': (n, [Q, q]),
+        'tba_selftest_subsample': (n, [v, q, u, q, q, Q]),
+        'tba_selftest_division': (n, [v, cD, cD, q, D]),
+        'tba_selftest_approx_quotient': (n, [v, cD, cD, q, D]),
+    }
+
+
+PROTOTYPES = _prototypes()
 _lib = None
 
 
@@ -152,12 +296,14 @@ def lib():
                 'libtombo_amd.so is not built (run `python -c "import __graft_entry__ as g; '
                 'g.build()"`); the resquiggle engine has no CPU fallback')
         L = C.CDLL(LIB_PATH)
-        L.tba_last_error.restype = C.c_char_p
         # a stale build (the .so is not tracked by git) must not be driven through newer struct
         # mirrors: the engine would read past tba_opts, or miss fields, without any error
         try:
+            for name, (restype, argtypes) in PROTOTYPES.items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
             out = (i64 * 4)()
-            ok = L.tba_abi_sizes(out, i64(4)) == 0 and list(out) == [
+            ok = L.tba_abi_sizes(out, 4) == 0 and list(out) == [
                 C.sizeof(Params), C.sizeof(Opts), C.sizeof(ReadResult), ABI_VERSION]
         except AttributeError:
             ok = False
@@ -169,8 +315,11 @@ def lib():
     return _lib
 
 
-def _p(a, t):
-    return None if a is None else a.ctypes.data_as(C.POINTER(t))
+def _call(L, name, *args):
+    """L.name(*args); a return code other than 0 is raised as EngineError with the library's message"""
+    rc = getattr(L, name)(*args)
+    if rc != 0:
+        raise EngineError('%s failed (%d): %s' % (name, rc, L.tba_last_error().decode()))
 
 
 def _f64(a):
@@ -453,29 +602,19 @@ def _check_pdist_rows(rows, slide_span=0):
 
 
 def _site_outputs(starts, ends, damp_counts):
-    """both site entries, tracks [starts[t], ends[t]) -> (pos_off, SiteFractions' frac .. n_stats, their C pointers)"""
+    """both site entries, tracks [starts[t], ends[t]) -> (pos_off, SiteFractions' frac .. n_stats)"""
     pos_off = np.concatenate([[0], np.cumsum(ends - starts)]).astype(np.int64)
     n_trk, n_pos = starts.shape[0], int(pos_off[-1])
     frac = np.empty(n_pos, dtype=np.float64)
     poss, cov, valid = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
     damp = None if damp_counts is None else np.empty(n_pos, dtype=np.float64)
-    outs = (frac, poss, cov, valid, damp, np.zeros(n_trk, dtype=np.int64), np.zeros(n_trk, dtype=np.int64))
-    return pos_off, outs, tuple(_p(a, f64 if a is frac or a is damp else i64) for a in outs)
+    return pos_off, (frac, poss, cov, valid, damp, np.zeros(n_trk, dtype=np.int64), np.zeros(n_trk, dtype=np.int64))
 
 
 def _roc_label_outputs(cap, n_counts, return_index):
-    """-> (stats, labels, record index or None, counts) of a ROC label entry and their pointers"""
-    outs = (np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.uint8),
+    """-> (stats, labels, record index or None, counts) of a ROC label entry"""
+    return (np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.uint8),
             np.empty(cap, dtype=np.int64) if return_index else None, np.zeros(n_counts, dtype=np.int64))
-    return outs, tuple(_p(a, t) for a, t in zip(outs, (f64, C.c_uint8, i64, i64)))
-
-
-def _site_other_form(form):
-    """typed nulls and zeros for the arguments of tba_site_fractions that the form in use leaves out"""
-    nd, ni = C.cast(None, C.POINTER(f64)), C.cast(None, C.POINTER(i64))
-    if form == 1:
-        return (nd, ni, i64(0), ni, ni, i64(0), C.c_int(0), f64(0.0))
-    return (C.c_int(0), nd, nd, nd, i64(0), i64(0), ni, i64(0), nd, ni, ni)
 
 
 def make_params(rp):
@@ -546,12 +685,9 @@ class PinnedArray(object):
         dtype = np.dtype(dtype)
         n = int(np.prod(shape)) if not np.isscalar(shape) else int(shape)
         self.nbytes = max(n * dtype.itemsize, 1)
-        ptr = C.c_void_p()
-        rc = self._L.tba_pinned_alloc(i64(self.nbytes), C.byref(ptr))
-        if rc != 0:
-            raise EngineError('tba_pinned_alloc failed (%d): %s' % (rc, self._L.tba_last_error().decode()))
-        self._ptr = ptr
-        buf = (C.c_char * self.nbytes).from_address(ptr.value)
+        self._ptr = C.c_void_p()
+        _call(self._L, 'tba_pinned_alloc', self.nbytes, C.byref(self._ptr))
+        buf = (C.c_char * self.nbytes).from_address(self._ptr.value)
         self.a = np.frombuffer(buf, dtype=dtype, count=n).reshape(shape)
 
     def close(self):
@@ -688,15 +824,10 @@ class Engine(object):
         self._stage = None                    # page-locked staging, made on first use (host_stage)
         self._ne_override = None              # set_num_events: event counts forced on the next upload
         self.skip_norm_out = False            # of the last upload's options
-        rc = self._L.tba_engine_create(C.c_int(device), C.byref(self._h))
-        if rc != 0:
-            raise EngineError('tba_engine_create failed (%d): %s' % (
-                rc, self._L.tba_last_error().decode()))
+        _call(self._L, 'tba_engine_create', self.device, C.byref(self._h))
 
-    def _check(self, rc, what):
-        if rc != 0:
-            raise EngineError('%s failed (%d): %s' % (what, rc,
-                                                     self._L.tba_last_error().decode()))
+    def _call(self, name, *args):
+        _call(self._L, name, self._h, *args)
 
     def close(self):
         if self._stage is not None:
@@ -716,8 +847,7 @@ class Engine(object):
         m = np.ascontiguousarray(level_means, dtype=np.float64)
         s = np.ascontiguousarray(level_sds, dtype=np.float64)
         assert m.shape[0] == 4 ** kmer_width == s.shape[0]
-        self._check(self._L.tba_set_model(self._h, _p(m, f64), _p(s, f64), i64(kmer_width),
-                                          i64(central_pos)), 'tba_set_model')
+        self._call('tba_set_model', m, s, kmer_width, central_pos)
         self.kmer_width = int(kmer_width)
         self._model_key = None
 
@@ -753,8 +883,7 @@ class Engine(object):
         seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
         n = raw_off.shape[0] - 1
         self.n = n
-        on_device = isinstance(raw, DeviceArray)   # (a Synth batch: copied device to device)
-        if not on_device:
+        if not isinstance(raw, DeviceArray):       # (else a Synth batch: copied device to device)
             if raw.dtype not in RAW_DTYPES or not raw.flags.c_contiguous:
                 raw = np.ascontiguousarray(raw, dtype=np.float64)
             seq = np.ascontiguousarray(seq, dtype=np.uint8)
@@ -780,59 +909,54 @@ class Engine(object):
         sto = None if stall_off is None else np.ascontiguousarray(stall_off, dtype=np.int64)
         self._keep = (raw, seq, raw_off, seq_off, svi, svf, si, st, sto)
         self.skip_norm_out = bool(opts.skip_norm_out)
-        self._check(self._L.tba_batch_upload_async(
-            self._h, C.byref(params), C.byref(opts), i64(n),
-            C.c_void_p(raw.ptr) if on_device else raw.ctypes.data_as(C.c_void_p),
-            C.c_int(RAW_DTYPES[raw.dtype]), _p(raw_off, i64),
-            C.cast(C.c_void_p(seq.ptr), C.POINTER(C.c_uint8)) if on_device else _p(seq, C.c_uint8), _p(seq_off, i64), _p(svi, f64), _p(svf, i32), _p(si, i64),
-            _p(st, i64), _p(sto, i64)), 'tba_batch_upload_async')
+        self._call('tba_batch_upload_async', params, opts, n, raw.ctypes, RAW_DTYPES[raw.dtype], raw_off, seq, seq_off,
+                   svi, svf, si, st, sto)
         self.n_raw_total = int(raw_off[-1])
         if wait:
             self.sync()
 
     def run(self):
-        self._check(self._L.tba_batch_run(self._h), 'tba_batch_run')
+        self._call('tba_batch_run')
 
     def enqueue(self):
-        self._check(self._L.tba_batch_enqueue(self._h), 'tba_batch_enqueue')
+        self._call('tba_batch_enqueue')
 
     def sync(self):
         # (the targets of the finished downloads belong to the caller alone from here on: a block of
         # the result pool must not stay leased because this engine still points at it)
-        self._check(self._L.tba_batch_sync(self._h), 'tba_batch_sync')
+        self._call('tba_batch_sync')
         self._keep_out = None
 
     def wait_for(self, other):
         """kernels enqueued next on this engine start after `other`'s last enqueued sequence"""
-        self._check(self._L.tba_batch_wait_for(self._h, other._h), 'tba_batch_wait_for')
+        self._call('tba_batch_wait_for', other._h)
 
     def device_mem(self):
         """(free, total) bytes of this engine's device"""
         a, b = i64(0), i64(0)
-        self._check(self._L.tba_device_mem(self._h, C.byref(a), C.byref(b)), 'tba_device_mem')
+        self._call('tba_device_mem', C.byref(a), C.byref(b))
         return a.value, b.value
 
     def held_bytes(self):
         """device bytes of this engine's grow-only batch buffers"""
         a = i64(0)
-        self._check(self._L.tba_engine_held_bytes(self._h, C.byref(a)), 'tba_engine_held_bytes')
+        self._call('tba_engine_held_bytes', C.byref(a))
         return a.value
 
     def set_sharing(self, n_engines):
         """scheduling hint: `n_engines` engines are fed concurrently on this device (tba_engine_set_sharing)"""
-        self._check(self._L.tba_engine_set_sharing(self._h, int(n_engines)), 'tba_engine_set_sharing')
+        self._call('tba_engine_set_sharing', int(n_engines))
 
     def set_dispatch(self, small_batch_reads=-1, tb_wave_below=-1):
         """read-count thresholds between the latency and the throughput forms of DNA event detection
         and of the main traceback (tba_engine_set_dispatch; identical results; default 1 024 each;
         0: every batch takes the throughput form; negative: unchanged); from the next run"""
-        self._check(self._L.tba_engine_set_dispatch(self._h, i64(int(small_batch_reads)), i64(int(tb_wave_below))),
-                    'tba_engine_set_dispatch')
+        self._call('tba_engine_set_dispatch', int(small_batch_reads), int(tb_wave_below))
 
     def set_side_stream(self, mode=-1):
         """stall detection and expected levels beside normalisation / event detection on a second stream
         (tba_engine_set_side_stream): -1 while at most two engines are alive on the device, 0 never, 1 always"""
-        self._check(self._L.tba_engine_set_side_stream(self._h, int(mode)), 'tba_engine_set_side_stream')
+        self._call('tba_engine_set_side_stream', int(mode))
 
     def last_side_stream(self):
         return bool(self._L.tba_engine_last_side_stream(self._h))
@@ -843,7 +967,7 @@ class Engine(object):
 
     def get_dispatch(self):
         a, b = i64(0), i64(0)
-        self._check(self._L.tba_engine_get_dispatch(self._h, C.byref(a), C.byref(b)), 'tba_engine_get_dispatch')
+        self._call('tba_engine_get_dispatch', C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
     def host_stage(self):
@@ -856,7 +980,7 @@ class Engine(object):
         """True while work of this engine is still in flight (never blocks)"""
         rc = self._L.tba_batch_query(self._h)
         if rc < 0:
-            self._check(rc, 'tba_batch_query')
+            raise EngineError('tba_batch_query failed (%d): %s' % (rc, self._L.tba_last_error().decode()))
         return rc == 1
 
     def download_async(self, results=None, segs32=None, segs64=None, norm=None):
@@ -868,21 +992,14 @@ class Engine(object):
                            (norm, np.float64, self.n_raw_total)):
             if a is not None and (a.dtype != dt or a.size < cnt or not a.flags.c_contiguous):
                 raise ValueError('output array has the wrong dtype / size')
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         self._keep_out = (results, segs32, segs64, norm)
-        self._check(self._L.tba_batch_download_async(
-            self._h, vp(results), vp(segs32), vp(segs64), vp(norm)), 'tba_batch_download_async')
+        self._call('tba_batch_download_async', None if results is None else (ReadResult * self.n).from_buffer(results),
+                   segs32, segs64, norm)
 
     def footprint(self, params, opts, n_raw, seq_len, raw_dtype=np.float64):
         """device bytes a batch of reads with these lengths would occupy"""
-        nr = np.ascontiguousarray(n_raw, dtype=np.int64)
-        sl = np.ascontiguousarray(seq_len, dtype=np.int64)
-        out = f64(0)
-        self._check(self._L.tba_batch_footprint(
-            C.byref(params), C.byref(opts), i64(self.kmer_width),
-            C.c_int(RAW_DTYPES[np.dtype(raw_dtype)]), i64(nr.shape[0]), _p(nr, i64), _p(sl, i64),
-            C.byref(out)), 'tba_batch_footprint')
-        return out.value
+        from .planner import exact_bytes
+        return exact_bytes(n_raw, seq_len, params, opts, self.kmer_width, raw_dtype)
 
     def download(self, want_norm=True):
         n = self.n
@@ -895,9 +1012,7 @@ class Engine(object):
         sv = np.zeros((n, 4))
         score = np.zeros(n)
         changed = np.zeros(n, np.int32)
-        self._check(self._L.tba_batch_download(
-            self._h, _p(status, i32), _p(segs, i64), _p(rs, i64), _p(norm, f64), _p(nl, i64),
-            _p(sv, f64), _p(score, f64), _p(changed, i32)), 'tba_batch_download')
+        self._call('tba_batch_download', status, segs, rs, norm, nl, sv, score, changed)
         return dict(status=status, segs=segs, read_start=rs, norm=norm, norm_len=nl, sv=sv,
                     score=score, changed=changed)
 
@@ -907,8 +1022,7 @@ class Engine(object):
                     seg=int(self.seg_off[-1]), ev=max(int(self.ev_off[-1]), 1))
         dt, shape = _GET_SHAPES[what]
         out = np.zeros([dims.get(d, d) for d in shape], dt)
-        self._check(self._L.tba_batch_get(self._h, C.c_int(what), out.ctypes.data_as(C.c_void_p),
-                                          i64(out.nbytes)), 'tba_batch_get')
+        self._call('tba_batch_get', what, out.ctypes, out.nbytes)
         return out
 
     def stall_ints(self):
@@ -917,34 +1031,27 @@ class Engine(object):
         if not cnt.any():
             return [np.zeros((0, 2), np.int64) for _ in range(self.n)]
         flat = np.zeros((int((off + cnt).max()), 2), np.int64)
-        self._check(self._L.tba_batch_get(self._h, C.c_int(GET_STALL_INTS),
-                                          flat.ctypes.data_as(C.c_void_p), i64(flat.nbytes)),
-                    'tba_batch_get')
+        self._call('tba_batch_get', GET_STALL_INTS, flat.ctypes, flat.nbytes)
         return [flat[int(o):int(o) + int(c)].copy() for o, c in zip(off, cnt)]
 
     def run_stages(self, first, last):
-        self._check(self._L.tba_batch_run_stages(self._h, C.c_int(first), C.c_int(last)),
-                    'tba_batch_run_stages')
+        self._call('tba_batch_run_stages', first, last)
 
     def put(self, what, data, per_read=None):
         data = np.ascontiguousarray(data)
         pr = None if per_read is None else np.ascontiguousarray(per_read, dtype=np.int64)
-        self._check(self._L.tba_batch_put(
-            self._h, C.c_int(what), data.ctypes.data_as(C.c_void_p), i64(data.nbytes),
-            _p(pr, i64)), 'tba_batch_put')
+        self._call('tba_batch_put', what, data.ctypes, data.nbytes, pr)
 
     def set_num_events(self, num_events):
         ne = None if num_events is None else np.ascontiguousarray(num_events, dtype=np.int64)
-        self._check(self._L.tba_set_num_events(
-            self._h, _p(ne, i64), i64(0 if ne is None else ne.shape[0])), 'tba_set_num_events')
+        self._call('tba_set_num_events', ne, 0 if ne is None else ne.shape[0])
         self._ne_override = ne
 
     def base_stats(self):
         """(means, stds) of every base of the finished batch, concatenated by ref_off"""
         nb = int(self.ref_off[-1])
         m, s = np.zeros(nb), np.zeros(nb)
-        self._check(self._L.tba_batch_base_stats(self._h, _p(m, f64), _p(s, f64), i64(nb)),
-                    'tba_batch_base_stats')
+        self._call('tba_batch_base_stats', m, s, nb)
         return m, s
 
     def de_novo_stats(self, fm_offset, smallest_pval):
@@ -952,9 +1059,7 @@ class Engine(object):
         NaN outside the testable part of a read and for failed reads)"""
         nb = int(self.ref_off[-1])
         out = np.full(max(nb, 1), np.nan)
-        self._check(self._L.tba_batch_de_novo_stats(
-            self._h, i64(int(fm_offset)), f64(float(smallest_pval)), _p(out, f64), i64(nb)),
-            'tba_batch_de_novo_stats')
+        self._call('tba_batch_de_novo_stats', int(fm_offset), float(smallest_pval), out, nb)
         return out[:nb]
 
     # ---- statistics over host arrays (numpy in, numpy out; pileup: the CSR bundle of tombo_stats) ----
@@ -964,9 +1069,7 @@ class Engine(object):
         if not (m.shape[0] == r.shape[0] == s.shape[0] == int(off[-1])):
             raise ValueError('per-base arrays and offsets disagree')
         out = np.empty(m.shape[0], dtype=np.float64)
-        self._check(self._L.tba_read_pvals(
-            self._h, _p(m, f64), _p(r, f64), _p(s, f64), _p(off, i64), i64(off.shape[0] - 1),
-            i64(int(fm_offset)), C.c_int(int(floor_out)), f64(smallest_pval), _p(out, f64)), 'tba_read_pvals')
+        self._call('tba_read_pvals', m, r, s, off, off.shape[0] - 1, int(fm_offset), int(floor_out), smallest_pval, out)
         return out
 
     def llh_ratio_windows(self, kind, means, ref_means, alt_means, ref_vars, starts, width, alt_vars, par):
@@ -975,17 +1078,13 @@ class Engine(object):
         if min(x.shape[0] for x in (r, a, rv, av) if x is not None) < m.shape[0]:
             raise ValueError('window arrays disagree')
         out = np.empty(st.shape[0], dtype=np.float64)
-        self._check(self._L.tba_llh_ratio_windows(
-            self._h, C.c_int(int(kind)), _p(m, f64), _p(r, f64), _p(a, f64), _p(rv, f64), _p(av, f64),
-            i64(m.shape[0]), i64(int(width)), _p(st, i64), i64(st.shape[0]), (f64 * 3)(*par), _p(out, f64)),
-            'tba_llh_ratio_windows')
+        self._call('tba_llh_ratio_windows', int(kind), m, r, a, rv, av, m.shape[0], int(width), st, st.shape[0],
+                   (f64 * 3)(*par), out)
         return out
 
     def _pileup_args(self, pl, with_ctrl):
-        return (i64(pl.reg_start.shape[0]), _p(pl.reg_start, i64), _p(pl.reg_end, i64), _p(pl.reg_strand, C.c_int8),
-                _p(pl.reg_read_off, i64), i64(pl.read_start.shape[0]), _p(pl.read_start, i64),
-                _p(pl.read_strand, C.c_int8)) + ((_p(pl.read_ctrl, C.c_int8),) if with_ctrl else ()) + \
-            (_p(pl.read_off, i64), _p(pl.means, f64))
+        return (pl.reg_start.shape[0], pl.reg_start, pl.reg_end, pl.reg_strand, pl.reg_read_off, pl.read_start.shape[0],
+                pl.read_start, pl.read_strand) + ((pl.read_ctrl,) if with_ctrl else ()) + (pl.read_off, pl.means)
 
     def group_level_stats(self, kind, return_p, fm_offset, min_test_reads, pileup, smallest_pval):
         """-> (stats, positions, coverage, control coverage, counts): counts[r] records from pileup.pos_off[r]"""
@@ -993,10 +1092,8 @@ class Engine(object):
         stats = np.empty(n_pos, dtype=np.float64)
         poss, cov, ccov = (np.empty(n_pos, dtype=np.int64) for _ in range(3))
         counts = np.empty(pileup.reg_start.shape[0], dtype=np.int64)
-        self._check(self._L.tba_group_level_stats(
-            self._h, C.c_int(kind), C.c_int(return_p), i64(fm_offset), i64(min_test_reads),
-            *self._pileup_args(pileup, True), f64(smallest_pval), _p(stats, f64), _p(poss, i64), _p(cov, i64),
-            _p(ccov, i64), _p(counts, i64)), 'tba_group_level_stats')
+        self._call('tba_group_level_stats', kind, return_p, fm_offset, min_test_reads, *self._pileup_args(pileup, True),
+                   smallest_pval, stats, poss, cov, ccov, counts)
         return stats, poss, cov, ccov, counts
 
     def reads_ref_levels(self, est_mean, fm_offset, min_test_reads, pileup, prior_means, prior_sds, w_mean, w_sd):
@@ -1005,22 +1102,22 @@ class Engine(object):
         pm, ps = _f64(prior_means), _f64(prior_sds)
         lm, ls = np.empty(n_pos, dtype=np.float64), np.empty(n_pos, dtype=np.float64)
         cov = np.empty(n_pos, dtype=np.int64)
-        self._check(self._L.tba_reads_ref_levels(
-            self._h, C.c_int(int(bool(est_mean))), i64(fm_offset), i64(min_test_reads),
-            *self._pileup_args(pileup, False), _p(pm, f64), _p(ps, f64), f64(w_mean), f64(w_sd), _p(lm, f64),
-            _p(ls, f64), _p(cov, i64)), 'tba_reads_ref_levels')
+        self._call('tba_reads_ref_levels', bool(est_mean), fm_offset, min_test_reads, *self._pileup_args(pileup, False),
+                   pm, ps, w_mean, w_sd, lm, ls, cov)
         return lm, ls, cov
+
+    # tba_site_fractions' arguments of the form a call leaves out: ref_sds .. smallest_pval / kind .. win_pos
+    _NO_Z_FORM = (None, None, 0, None, None, 0, 0, 0.0)
+    _NO_WINDOW_FORM = (0, None, None, None, 0, 0, None, 0, None, None, None)
 
     def _site_fractions(self, form, trk_start, trk_end, z_args, win_args, n_stats, single_read_thresh,
                         lower_thresh, damp_counts, return_per_read):
         trk_start, trk_end = _i64(trk_start), _i64(trk_end)
-        pos_off, outs, out_ptrs = _site_outputs(trk_start, trk_end, damp_counts)
+        pos_off, outs = _site_outputs(trk_start, trk_end, damp_counts)
         per_read = np.empty(n_stats, dtype=np.float64) if return_per_read else None
-        self._check(self._L.tba_site_fractions(
-            self._h, C.c_int(form), i64(trk_start.shape[0]), _p(trk_start, i64), _p(trk_end, i64), *z_args, *win_args,
-            f64(float(single_read_thresh)), None if lower_thresh is None else (f64 * 1)(float(lower_thresh)),
-            None if damp_counts is None else (f64 * 2)(*damp_counts), *out_ptrs, _p(per_read, f64)),
-            'tba_site_fractions')
+        self._call('tba_site_fractions', form, trk_start.shape[0], trk_start, trk_end, *z_args, *win_args,
+                   float(single_read_thresh), None if lower_thresh is None else (f64 * 1)(float(lower_thresh)),
+                   None if damp_counts is None else (f64 * 2)(*damp_counts), *outs, per_read)
         return SiteFractions(pos_off, *outs, per_read)
 
     def site_fractions_z(self, trk_start, trk_end, means, ref_means, ref_sds, off, read_track, read_pos,
@@ -1033,9 +1130,8 @@ class Engine(object):
         if not (m.shape[0] == r.shape[0] == s.shape[0] == int(off[-1])) or \
                 not (off.shape[0] - 1 == r_trk.shape[0] == r_pos.shape[0]):
             raise ValueError('per-base arrays, offsets and per-read arrays disagree')
-        z_args = (_p(m, f64), _p(r, f64), _p(s, f64), _p(off, i64), i64(r_trk.shape[0]), _p(r_trk, i64),
-                  _p(r_pos, i64), i64(int(fm_offset)), C.c_int(int(floor_out)), f64(smallest_pval))
-        return self._site_fractions(0, trk_start, trk_end, z_args, _site_other_form(0), m.shape[0],
+        z_args = (m, r, s, off, r_trk.shape[0], r_trk, r_pos, int(fm_offset), int(floor_out), smallest_pval)
+        return self._site_fractions(0, trk_start, trk_end, z_args, self._NO_WINDOW_FORM, m.shape[0],
                                     single_read_thresh, lower_thresh, damp_counts, return_per_read)
 
     def site_fractions_windows(self, trk_start, trk_end, kind, means, ref_means, alt_means, ref_vars, alt_vars,
@@ -1049,11 +1145,9 @@ class Engine(object):
         if not (r.shape[0] == a.shape[0] == rv.shape[0] == n) or (av is not None and av.shape[0] != n) or \
                 not (st.shape[0] == w_trk.shape[0] == w_pos.shape[0]):
             raise ValueError('window arrays disagree')
-        win_args = (C.c_int(int(kind)), _p(a, f64), _p(rv, f64), _p(av, f64), i64(n), i64(int(width)),
-                    _p(st, i64), i64(st.shape[0]), (f64 * 3)(*par), _p(w_trk, i64), _p(w_pos, i64))
-        return self._site_fractions(1, trk_start, trk_end, (_p(m, f64), _p(r, f64)) + _site_other_form(1),
-                                    win_args, st.shape[0], single_read_thresh, lower_thresh, damp_counts,
-                                    return_per_read)
+        win_args = (int(kind), a, rv, av, n, int(width), st, st.shape[0], (f64 * 3)(*par), w_trk, w_pos)
+        return self._site_fractions(1, trk_start, trk_end, (m, r) + self._NO_Z_FORM, win_args, st.shape[0],
+                                    single_read_thresh, lower_thresh, damp_counts, return_per_read)
 
     def site_aggregate(self, blk_start, blk_end, rec_off, records, single_read_thresh, lower_thresh=None,
                        abs_rule=False, damp_counts=None):
@@ -1062,12 +1156,10 @@ class Engine(object):
         stored) -> SiteFractions (per_read None).  abs_rule: model_compare's |stat| >= single_read_thresh validity
         when no lower threshold is given.  `last_site_aggregate_kernel_ms`: device time of the call's kernels."""
         bs, be, off, rec = _check_site_aggregate_args(blk_start, blk_end, rec_off, records)
-        (pos_off, outs, out_ptrs), ms = _site_outputs(bs, be, damp_counts), f64(0.0)
-        self._check(self._L.tba_site_aggregate(
-            self._h, i64(bs.shape[0]), _p(bs, i64), _p(be, i64), _p(off, i64), C.c_void_p(rec.ctypes.data),
-            f64(float(single_read_thresh)), None if lower_thresh is None else (f64 * 1)(float(lower_thresh)),
-            C.c_int(int(bool(abs_rule))), None if damp_counts is None else (f64 * 2)(*damp_counts), *out_ptrs,
-            C.byref(ms)), 'tba_site_aggregate')
+        (pos_off, outs), ms = _site_outputs(bs, be, damp_counts), f64(0.0)
+        self._call('tba_site_aggregate', bs.shape[0], bs, be, off, rec.ctypes, float(single_read_thresh),
+                   None if lower_thresh is None else (f64 * 1)(float(lower_thresh)), bool(abs_rule),
+                   None if damp_counts is None else (f64 * 2)(*damp_counts), *outs, C.byref(ms))
         self.last_site_aggregate_kernel_ms = ms.value
         return SiteFractions(pos_off, *outs, None)
 
@@ -1091,12 +1183,9 @@ class Engine(object):
         minus, ss, s_off, seq, off, pos, stat, table, sets = _check_roc_motif_args(
             blk_minus, blk_seq_start, seq_off, seq_codes, rec_off, rec_pos, rec_stat, motifs)
         n_mot, ms = table.shape[0], f64(0.0)
-        outs, out_ptrs = _roc_label_outputs(n_mot * pos.shape[0], n_mot, return_index)
-        self._check(self._L.tba_roc_motif_labels(
-            self._h, i64(minus.shape[0]), _p(minus, C.c_uint8), _p(ss, i64), _p(s_off, i64), _p(seq, C.c_uint8),
-            _p(off, i64), _p(pos, i64), _p(stat, f64), i64(n_mot), _p(table, i32), _p(sets, C.c_uint8),
-            C.c_int(0 if ctrl_label is None else 1), C.c_int(int(bool(ctrl_label))), *out_ptrs, C.byref(ms)),
-            'tba_roc_motif_labels')
+        outs = _roc_label_outputs(n_mot * pos.shape[0], n_mot, return_index)
+        self._call('tba_roc_motif_labels', minus.shape[0], minus, ss, s_off, seq, off, pos, stat, n_mot, table, sets,
+                   0 if ctrl_label is None else 1, bool(ctrl_label), *outs, C.byref(ms))
         self.last_roc_kernel_ms = ms.value
         return self._roc_split(*outs, return_index)
 
@@ -1105,11 +1194,9 @@ class Engine(object):
         unmod_locs[blk_loc[t, 2]:blk_loc[t, 3]]; a record is kept when its position is in either, its label is
         whether it is in the first -> (stats, has_mod[, record index]) in record order"""
         loc, mod, unmod, off, pos, stat = _check_roc_loc_args(blk_loc, mod_locs, unmod_locs, rec_off, rec_pos, rec_stat)
-        (outs, out_ptrs), ms = _roc_label_outputs(pos.shape[0], 1, return_index), f64(0.0)
-        self._check(self._L.tba_roc_loc_labels(
-            self._h, i64(loc.shape[0]), _p(loc, i64), _p(mod, i64), i64(mod.shape[0]), _p(unmod, i64),
-            i64(unmod.shape[0]), _p(off, i64), _p(pos, i64), _p(stat, f64), *out_ptrs, C.byref(ms)),
-            'tba_roc_loc_labels')
+        outs, ms = _roc_label_outputs(pos.shape[0], 1, return_index), f64(0.0)
+        self._call('tba_roc_loc_labels', loc.shape[0], loc, mod, mod.shape[0], unmod, unmod.shape[0], off, pos, stat,
+                   *outs, C.byref(ms))
         self.last_roc_kernel_ms = ms.value
         return self._roc_split(*outs, return_index)[0]
 
@@ -1121,9 +1208,8 @@ class Engine(object):
         st, hm, rk = _check_roc_rank_args(stats, has_mod, ranks)
         tp_at = np.zeros(rk.shape[0], dtype=np.int64)
         total, n_nan, ms = i64(0), i64(0), (f64 * 2)()
-        self._check(self._L.tba_roc_rank_counts(
-            self._h, i64(st.shape[0]), _p(st, f64), _p(hm, C.c_uint8), i64(rk.shape[0]), _p(rk, i64), _p(tp_at, i64),
-            C.byref(total), C.byref(n_nan), ms), 'tba_roc_rank_counts')
+        self._call('tba_roc_rank_counts', st.shape[0], st, hm, rk.shape[0], rk, tp_at, C.byref(total), C.byref(n_nan),
+                   ms)
         self.last_roc_sort_ms, self.last_roc_gather_ms = ms[0], ms[1]
         self.last_roc_kernel_ms = ms[0] + ms[1]
         return tp_at, total.value, n_nan.value
@@ -1136,9 +1222,7 @@ class Engine(object):
         rows = _check_pdist_rows(rows, slide_span)
         n, ms = rows.shape[0], f64(0.0)
         out = np.empty((n, n), dtype=np.float64)
-        self._check(self._L.tba_pairwise_window_dists(
-            self._h, i64(n), i64(rows.shape[1]), i64(int(slide_span)), _p(rows, f64), _p(out, f64), C.byref(ms)),
-            'tba_pairwise_window_dists')
+        self._call('tba_pairwise_window_dists', n, rows.shape[1], int(slide_span), rows, out, C.byref(ms))
         self.last_pdist_kernel_ms = ms.value
         return out
 
@@ -1148,9 +1232,7 @@ class Engine(object):
         rows = _check_pdist_rows(rows)
         n, ms = rows.shape[0], f64(0.0)
         out = np.empty(n * (n - 1) // 2, dtype=np.float64)
-        self._check(self._L.tba_pairwise_nanmean_dists(
-            self._h, i64(n), i64(rows.shape[1]), _p(rows, f64), _p(out, f64), C.byref(ms)),
-            'tba_pairwise_nanmean_dists')
+        self._call('tba_pairwise_nanmean_dists', n, rows.shape[1], rows, out, C.byref(ms))
         self.last_pdist_kernel_ms = ms.value
         return out
 
@@ -1163,10 +1245,8 @@ class Engine(object):
         counts, lv_off = np.empty(n_kmers, dtype=np.int64), np.empty(n_kmers + 1, dtype=np.int64)
         cap = int(np.maximum(np.diff(off) - (int(kmer_width) - 1), 0).sum())   # every window of the batch
         levels = np.empty(cap, dtype=np.float64)
-        self._check(self._L.tba_kmer_levels(
-            self._h, _p(m, f64), _p(codes, C.c_uint8), _p(off, i64), i64(off.shape[0] - 1), i64(int(kmer_width)),
-            i64(int(central_pos)), _p(done, C.c_uint8), _p(counts, i64), _p(lv_off, i64), _p(levels, f64), i64(cap)),
-            'tba_kmer_levels')
+        self._call('tba_kmer_levels', m, codes, off, off.shape[0] - 1, int(kmer_width), int(central_pos), done, counts,
+                   lv_off, levels, cap)
         return counts, levels[:int(lv_off[-1])].copy(), lv_off
 
     def kde_eval(self, levels, lv_off, x, bandwidth):
@@ -1174,9 +1254,7 @@ class Engine(object):
         -> float64[n_seg, G]; NaN rows for segments of fewer than two levels or with a NaN level"""
         lv, off, x = _check_kde_eval_args(levels, lv_off, x, bandwidth)
         out = np.empty((off.shape[0] - 1, x.shape[0]), dtype=np.float64)
-        self._check(self._L.tba_kde_eval(
-            self._h, _p(lv, f64), _p(off, i64), i64(off.shape[0] - 1), _p(x, f64), i64(x.shape[0]),
-            f64(float(bandwidth)), _p(out, f64)), 'tba_kde_eval')
+        self._call('tba_kde_eval', lv, off, off.shape[0] - 1, x, x.shape[0], float(bandwidth), out)
         return out
 
     # ---- k-mer model estimation (csrc/k_kmer_est.h) ----
@@ -1192,11 +1270,8 @@ class Engine(object):
         n_keys, n_ent = int(n_keys), ep.shape[0]
         counts, koff = np.empty(n_keys, dtype=np.int64), np.empty(n_keys + 1, dtype=np.int64)
         levels, sds = np.empty(n_ent, dtype=np.float64), np.empty(n_ent, dtype=np.float64)
-        self._check(self._L.tba_region_key_levels(
-            self._h, C.c_int(1 if est_mean else 0), i64(rs.shape[0]), _p(rs, i64), _p(rm, C.c_uint8), _p(off, i64),
-            _p(m, f64), i64(roff.shape[0] - 1), _p(roff, i64), _p(rr, i64), i64(pr.shape[0]), _p(pr, i64), _p(pg, i64),
-            i64(n_ent), _p(ep, i64), _p(ek, i64), i64(n_keys), _p(counts, i64), _p(koff, i64), _p(levels, f64),
-            _p(sds, f64)), 'tba_region_key_levels')
+        self._call('tba_region_key_levels', bool(est_mean), rs.shape[0], rs, rm, off, m, roff.shape[0] - 1, roff, rr,
+                   pr.shape[0], pr, pg, n_ent, ep, ek, n_keys, counts, koff, levels, sds)
         return counts, koff, levels, sds
 
     def segment_medians(self, values, off):
@@ -1204,16 +1279,14 @@ class Engine(object):
         empty segment or one that holds a NaN.  `values` is not modified"""
         v, off = _check_segment_medians_args(values, off)
         out = np.empty(off.shape[0] - 1, dtype=np.float64)
-        self._check(self._L.tba_segment_medians(self._h, _p(v, f64), _p(off, i64), i64(off.shape[0] - 1), _p(out, f64)),
-                    'tba_segment_medians')
+        self._call('tba_segment_medians', v, off, off.shape[0] - 1, out)
         return out
 
     # ---- genome tracks (csrc/k_tracks.h) ----
     def tracks_begin(self, win_start, win_end, n_slots):
         """tba_tracks_begin: open a resident track set over [win_start, win_end) of one (chromosome, strand)"""
         _check_tracks_begin_args(win_start, win_end, n_slots)
-        self._check(self._L.tba_tracks_begin(self._h, i64(int(win_start)), i64(int(win_end)), C.c_int(int(n_slots))),
-                    'tba_tracks_begin')
+        self._call('tba_tracks_begin', int(win_start), int(win_end), int(n_slots))
         self._trk = (int(win_end) - int(win_start), int(n_slots))
 
     def tracks_add(self, read_start, read_end, read_flags, read_off, slots, tile_read_off, tile_reads):
@@ -1224,10 +1297,8 @@ class Engine(object):
             raise ValueError('no track set is open (tracks_begin)')
         rs, re_, fl, off, sl, toff, tr = _check_tracks_add_args(
             self._trk[0], self._trk[1], read_start, read_end, read_flags, read_off, slots, tile_read_off, tile_reads)
-        ptrs = (C.POINTER(f64) * TRK_MAX_SLOTS)(*[_p(v, f64) for v in sl])
-        self._check(self._L.tba_tracks_add(
-            self._h, i64(rs.shape[0]), _p(rs, i64), _p(re_, i64), _p(fl, C.c_uint8), _p(off, i64), ptrs,
-            i64(toff.shape[0] - 1), _p(toff, i64), _p(tr, i32)), 'tba_tracks_add')
+        ptrs = (C.c_void_p * TRK_MAX_SLOTS)(*[v.ctypes.data for v in sl])
+        self._call('tba_tracks_add', rs.shape[0], rs, re_, fl, off, ptrs, toff.shape[0] - 1, toff, tr)
 
     def tracks_finish(self, want_sums=False):
         """tba_tracks_finish -> TrackSet(means, sums or None, slot_cov, read_cov) of the open set"""
@@ -1237,13 +1308,12 @@ class Engine(object):
         means, cov = np.empty((ns, W), dtype=np.float64), np.empty((ns, W), dtype=np.int64)
         sums = np.empty((ns, W), dtype=np.float64) if want_sums else None
         rcov = np.empty(W, dtype=np.int64)
-        self._check(self._L.tba_tracks_finish(self._h, _p(means, f64), _p(sums, f64), _p(cov, i64), _p(rcov, i64)),
-                    'tba_tracks_finish')
+        self._call('tba_tracks_finish', means, sums, cov, rcov)
         return TrackSet(means, sums, cov, rcov)
 
     def tracks_kernel_ms(self):
         ms = f64(0)
-        self._check(self._L.tba_tracks_kernel_ms(self._h, C.byref(ms)), 'tba_tracks_kernel_ms')
+        self._call('tba_tracks_kernel_ms', C.byref(ms))
         return ms.value
 
     def tracks_compact(self, values):
@@ -1252,17 +1322,14 @@ class Engine(object):
         v, mode = _check_compact_args(values)
         n = v.shape[0]
         pos, val, cnt = np.empty(n + 1, dtype=np.int64), np.empty(n, dtype=v.dtype), i64(0)
-        self._check(self._L.tba_tracks_compact(self._h, C.c_int(mode), v.ctypes.data_as(C.c_void_p), i64(n),
-                                               _p(pos, i64), val.ctypes.data_as(C.c_void_p), C.byref(cnt)),
-                    'tba_tracks_compact')
+        self._call('tba_tracks_compact', mode, v.ctypes, n, pos, val.ctypes, C.byref(cnt))
         return pos[:cnt.value + mode].copy(), val[:cnt.value].copy()
 
     def tracks_diff(self, a, b):
         """tba_tracks_diff: np.nan_to_num(a - b)"""
         a, b = _check_track_pair(a, b)
         out = np.empty(a.shape[0], dtype=np.float64)
-        self._check(self._L.tba_tracks_diff(self._h, _p(a, f64), _p(b, f64), i64(a.shape[0]), _p(out, f64)),
-                    'tba_tracks_diff')
+        self._call('tba_tracks_diff', a, b, a.shape[0], out)
         return out
 
     def tracks_topn(self, a, b, n_top):
@@ -1273,14 +1340,13 @@ class Engine(object):
             raise ValueError('n_top must be a non-negative integer')
         k = min(int(n_top), a.shape[0])
         pos, val, cnt = np.empty(k, dtype=np.int64), np.empty(k, dtype=np.float64), i64(0)
-        self._check(self._L.tba_tracks_topn(self._h, _p(a, f64), _p(b, f64), i64(a.shape[0]), i64(k), _p(pos, i64),
-                                            _p(val, f64), C.byref(cnt)), 'tba_tracks_topn')
+        self._call('tba_tracks_topn', a, b, a.shape[0], k, pos, val, C.byref(cnt))
         order = np.lexsort((pos[:cnt.value], val[:cnt.value]))[::-1]
         return val[order], pos[order]
 
     def stats(self):
         a, c = f64(0), f64(0)
-        self._check(self._L.tba_batch_stats(self._h, C.byref(a), C.byref(c)), 'tba_batch_stats')
+        self._call('tba_batch_stats', C.byref(a), C.byref(c))
         return a.value, c.value
 
 
@@ -1292,12 +1358,7 @@ class DeviceArray(object):
         self.ptr, self.dtype, self.size, self.owner = int(ptr or 0), np.dtype(dtype), int(size), owner
         self.nbytes = self.size * self.dtype.itemsize
         self.shape = (self.size,)
-
-
-class SynthParams(C.Structure):
-    _fields_ = [('mean_dwell', i64), ('min_dwell', i64), ('n_lead', i64), ('n_trail', i64),
-                ('scale', f64), ('offset', f64), ('noise_sd', f64), ('dac_per_pa', f64), ('dac_offset', f64),
-                ('reverse', i32), ('pad', i32)]
+        self.ctypes = C.c_void_p(self.ptr)     # (what a void * parameter takes, as numpy's .ctypes)
 
 
 def make_synth_params(mean_dwell=9, min_dwell=2, scale=12.0, offset=90.0, noise_sd=0.25, n_lead=200,
@@ -1311,9 +1372,7 @@ def synth_tables(sp):
     """(dwell thresholds uint32[256], noise constant) of the device generator under `sp` (host only)"""
     thr = np.zeros(256, np.uint32)
     c = f64(0.0)
-    rc = lib().tba_synth_dwell_thresholds(C.byref(sp), _p(thr, C.c_uint32), i64(256), C.byref(c))
-    if rc != 0:
-        raise EngineError('tba_synth_dwell_thresholds failed (%d): %s' % (rc, lib().tba_last_error().decode()))
+    _call(lib(), 'tba_synth_dwell_thresholds', sp, thr, 256, C.byref(c))
     return thr, float(c.value)
 
 
@@ -1325,10 +1384,8 @@ class Synth(object):
         self._L = lib()
         self._h = C.c_void_p()
         km = np.ascontiguousarray(std_ref.level_means, dtype=np.float64)
-        rc = self._L.tba_synth_create(C.c_int(device), _p(km, f64), i64(int(std_ref.kmer_width)), C.byref(self._h))
-        if rc != 0:
-            raise EngineError('tba_synth_create failed (%d): %s' % (rc, self._L.tba_last_error().decode()))
         self.device = int(device)
+        _call(self._L, 'tba_synth_create', self.device, km, int(std_ref.kmer_width), C.byref(self._h))
 
     def generate(self, sp, seed, n_bases, raw_dtype=np.int16, first_read=0):
         """-> (raw DeviceArray, raw_off int64[n+1], seq DeviceArray, seq_off int64[n+1]); the device
@@ -1337,12 +1394,8 @@ class Synth(object):
         n = nb.shape[0]
         raw_off, seq_off = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
         d_raw, d_seq = C.c_void_p(), C.c_void_p()
-        rc = self._L.tba_synth_generate(
-            self._h, C.byref(sp), C.c_uint64(int(seed) & 0xffffffffffffffff), i64(int(first_read)), i64(n),
-            _p(nb, i64), C.c_int(RAW_DTYPES[np.dtype(raw_dtype)]), _p(raw_off, i64), _p(seq_off, i64),
-            C.byref(d_raw), C.byref(d_seq))
-        if rc != 0:
-            raise EngineError('tba_synth_generate failed (%d): %s' % (rc, self._L.tba_last_error().decode()))
+        _call(self._L, 'tba_synth_generate', self._h, sp, int(seed) & 0xffffffffffffffff, int(first_read), n, nb,
+              RAW_DTYPES[np.dtype(raw_dtype)], raw_off, seq_off, C.byref(d_raw), C.byref(d_seq))
         self._last = (np.dtype(raw_dtype), int(raw_off[-1]), int(seq_off[-1]))
         return (DeviceArray(d_raw.value, raw_dtype, raw_off[-1], self), raw_off,
                 DeviceArray(d_seq.value, np.uint8, seq_off[-1], self), seq_off)
@@ -1351,9 +1404,7 @@ class Synth(object):
         """the last batch as host arrays (raw, seq codes)"""
         dt, n_raw, n_seq = self._last
         raw, seq = np.empty(n_raw, dt), np.empty(n_seq, np.uint8)
-        rc = self._L.tba_synth_download(self._h, raw.ctypes.data_as(C.c_void_p), _p(seq, C.c_uint8))
-        if rc != 0:
-            raise EngineError('tba_synth_download failed (%d): %s' % (rc, self._L.tba_last_error().decode()))
+        _call(self._L, 'tba_synth_download', self._h, raw.ctypes, seq)
         return raw, seq
 
     def close(self):
@@ -1380,11 +1431,9 @@ def identify_stalls(eng, raw, sp):
     cnt = i64(0)
     if n == 0:
         return out[:0]
-    eng._check(eng._L.tba_identify_stalls(
-        eng._h, raw.ctypes.data_as(C.c_void_p), C.c_int(RAW_DTYPES[raw.dtype]), i64(n),
-        i64(int(sp.window_size)), i64(int(sp.n_windows)), i64(int(sp.mini_window_size)),
-        f64(float(sp.threshold)), i64(int(sp.min_consecutive_obs)), i64(int(sp.edge_buffer)),
-        _p(out, i64), i64(cap), C.byref(cnt)), 'tba_identify_stalls')
+    eng._call('tba_identify_stalls', raw.ctypes, RAW_DTYPES[raw.dtype], n, int(sp.window_size), int(sp.n_windows),
+              int(sp.mini_window_size), float(sp.threshold), int(sp.min_consecutive_obs), int(sp.edge_buffer), out, cap,
+              C.byref(cnt))
     return out[:cnt.value]
 
 
@@ -1507,7 +1556,6 @@ def pack_reads(raws, seqs, reverse=False, pinned=False, n_threads=None, stage=No
     native threads with the GIL released.  `stage` (a PinnedStage): the big arrays are views of its
     reusable page-locked buffers; else `pinned`: fresh page-locked memory (keep it referenced
     through `keep`); else plain numpy arrays."""
-    L = lib()
     n = len(raws)
     dt = raws[0].dtype if n and isinstance(raws[0], np.ndarray) else None
     as_is = dt in RAW_DTYPES          # (one pass when the reads can be taken as they are)
@@ -1533,11 +1581,8 @@ def pack_reads(raws, seqs, reverse=False, pinned=False, n_threads=None, stage=No
     sp = (C.c_void_p * n)(*seq_ptr)
     if n_threads is None:
         n_threads = min(int(os.environ.get('TBA_PACK_THREADS', '16')), os.cpu_count() or 1)
-    rc = L.tba_pack_reads(i64(n), rp, C.c_int(RAW_DTYPES[dt]), C.c_int(int(bool(reverse))),
-                          _p(raw_off, i64), C.c_void_p(_addr(raw)), sp, _p(seq_off, i64),
-                          C.cast(C.c_void_p(_addr(seq)), C.POINTER(C.c_uint8)), C.c_int(int(n_threads)))
-    if rc != 0:
-        raise EngineError('tba_pack_reads failed (%d): %s' % (rc, L.tba_last_error().decode()))
+    _call(lib(), 'tba_pack_reads', n, rp, RAW_DTYPES[dt], bool(reverse), raw_off, raw.ctypes, sp, seq_off, seq,
+          int(n_threads))
     return raw, raw_off, seq, seq_off, keep
 
 
@@ -1546,7 +1591,6 @@ def unpack_reads(src, src_off, count, dtype=None, n_threads=None):
     by native threads.  The per-read arrays are views of ONE fresh allocation (a single large
     mapping takes huge pages where the kernel offers them: first-touch page faults, not the copy,
     bound this step with one malloc per read), so they keep each other's memory alive."""
-    L = lib()
     n = len(count)
     dt = src.dtype if dtype is None else np.dtype(dtype)
     cnt = np.ascontiguousarray(count, dtype=np.int64)
@@ -1559,8 +1603,5 @@ def unpack_reads(src, src_off, count, dtype=None, n_threads=None):
     dp = (np.uint64(_addr(arena)) + off[:-1].astype(np.uint64) * np.uint64(dt.itemsize)).astype(np.uint64)
     if n_threads is None:
         n_threads = min(32, os.cpu_count() or 1)
-    rc = L.tba_unpack_reads(i64(n), C.c_void_p(_addr(src)), i64(dt.itemsize), _p(so, i64),
-                            _p(cnt, i64), dp.ctypes.data_as(C.POINTER(C.c_void_p)), C.c_int(int(n_threads)))
-    if rc != 0:
-        raise EngineError('tba_unpack_reads failed (%d): %s' % (rc, L.tba_last_error().decode()))
+    _call(lib(), 'tba_unpack_reads', n, src.ctypes, dt.itemsize, so, cnt, dp.ctypes, int(n_threads))
     return np.split(arena, off[1:-1])

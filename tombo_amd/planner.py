@@ -60,14 +60,8 @@ def exact_bytes(n_raw, seq_len, params, opts, kmer_width, raw_dtype=np.float64):
     nr = np.ascontiguousarray(n_raw, dtype=np.int64)
     sl = np.ascontiguousarray(seq_len, dtype=np.int64)
     out = C.c_double(0)
-    L = _native.lib()
-    rc = L.tba_batch_footprint(C.byref(params), C.byref(opts), C.c_int64(int(kmer_width)),
-                               C.c_int(_native.RAW_DTYPES[np.dtype(raw_dtype)]),
-                               C.c_int64(nr.shape[0]), nr.ctypes.data_as(C.POINTER(C.c_int64)),
-                               sl.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(out))
-    if rc != 0:
-        raise _native.EngineError('tba_batch_footprint failed (%d): %s' % (
-            rc, L.tba_last_error().decode()))
+    _native._call(_native.lib(), 'tba_batch_footprint', params, opts, int(kmer_width),
+                  _native.RAW_DTYPES[np.dtype(raw_dtype)], nr.shape[0], nr, sl, C.byref(out))
     return out.value
 
 
