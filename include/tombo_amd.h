@@ -323,7 +323,8 @@ enum {
 };
 enum {
     TBA_TB_FORM_NONE = 0,
-    TBA_TB_FORM_LANE = 1,           /* k_main_tb: a lane per read (static bands, broken chains) */
+    TBA_TB_FORM_LANE = 1,           /* k_main_tb: a lane per read, the serial walk on the chunk kernels' row-block walker
+                                     * (static bands, reads the chunk kernels or their verifier handed back) */
     TBA_TB_FORM_LONG = 2,           /* k_main_tb_long */
     TBA_TB_FORM_PAR16 = 16,         /* k_main_tb_par<16>: throughput form */
     TBA_TB_FORM_PAR64 = 64          /* k_main_tb_par<64>: latency form, and the long reads of any batch */

@@ -776,6 +776,27 @@ def test_wide_static_band_matches_oracle():
     assert sum(o['status'] == 0 for o in oracles) >= 4
 
 
+def test_static_reads_around_the_row_block_on_gpu(dispatch_form):
+    """static-band reads whose row count straddles the traceback's block of 16 rows: the serial walk (k_main_tb)
+    runs on the row-block walker of the chunk kernels -- a first block that lies mostly below row 1, a last partial
+    block, the pair store across an odd and an even row count, window clamping in rows narrower than two windows"""
+    from tombo_amd import _native as N, synth, tombo_stats as ts, tombo_helper as th
+    samp = th.seqSampleType('DNA', False)
+    model = ts.TomboModel(seq_samp_type=samp)
+    params = ts.load_resquiggle_parameters(samp)
+    reads = []
+    for nb in (15, 16, 17, 18, 31, 32, 33, 34, 47, 48, 49, 50, 64, 65):
+        seq, raw, _ = synth.synth_read(model, nb, 100 + nb)
+        reads.append((raw, seq, None, None))
+    eng, out, oracles = run_batch(model, params, 'DNA', reads)
+    bad = compare_batch(eng, oracles, out, 'static rows')
+    assert not bad, '\n'.join(bad[:40])
+    assert all(o['status'] == 0 for o in oracles), [o['status'] for o in oracles]
+    assert np.all(eng.get(N.GET_PATH)[:, 0] == 2)
+    assert np.all(eng.get(N.GET_TB_FORM) == N.TB_FORM_LANE)
+    assert not eng.get(N.GET_TB_VERIFY_FAIL).any()
+
+
 def test_resquiggle_batch_without_signal():
     """return_signal=False: same boundaries, scale values and scores, raw_signal None, nothing
     materialised for it on the device"""

@@ -830,10 +830,8 @@ __global__ __launch_bounds__(64) void k_dp_wide(ReadState *rs, i64 n_reads, cons
 }
 
 // one 2-bit move code out of the packed rows written by k_dp
-__device__ __forceinline__ int mv_get(const unsigned char *mv, i64 row, int cpl, int bpl, i64 b)
+__device__ __forceinline__ int mv_get(const unsigned char *mv, i64 row, int cpl, i64 b)
 {
-    (void)cpl;
-    (void)bpl;
     return (mv[row * (i64)mv_class_rowb(cpl) + (b >> 2)] >> (2 * (b & 3))) & 3;
 }
 
@@ -844,9 +842,8 @@ __device__ inline int dev_banded_traceback(const unsigned char *mv, i64 stride, 
     i64 n_bases, i64 bw, const i64 *starts, bool identity, i64 band_pos, i64 thresh,
     i64 *seq_poss)
 {
-    const int bpl = cpl ? mv_bpl(cpl) : 0;
 #define ST_AT(r_) (identity ? (i64)(r_) : starts[(r_)])
-#define MV_AT(r_, b_) (cpl ? mv_get(mv, (r_), cpl, bpl, (b_) < 0 ? (b_) + bw : (b_)) \
+#define MV_AT(r_, b_) (cpl ? mv_get(mv, (r_), cpl, (b_) < 0 ? (b_) + bw : (b_)) \
                            : (int)mv[(r_) * stride + ((b_) < 0 ? (b_) + bw : (b_))])
     i64 cur_ev = band_pos + ST_AT(n_bases - 1);
     seq_poss[n_bases] = cur_ev + 1;
@@ -871,7 +868,8 @@ __device__ inline int dev_banded_traceback(const unsigned char *mv, i64 stride, 
     return TBA_OK;
 }
 
-// (k_start_tb, the start discovery's epilogue, lives in k_tb_par.h: it walks with that file's row blocks)
+// (the traceback kernels of the batch -- k_start_tb, the start discovery's epilogue, and the main traceback,
+// k_main_tb, k_main_tb_par and its verifier -- live in k_tb_par.h: one row-block walker serves them all)
 
 // the branch of find_adaptive_base_assignment before start discovery (resquiggle.py:984-989)
 __global__ __launch_bounds__(64) void k_path0(ReadState *rs, i64 n_reads, const DevParams *dp)
@@ -1013,145 +1011,6 @@ __global__ __launch_bounds__(256) void k_scan_arena(ReadState *rs, i64 n_reads, 
         if (sz == 0) off = 0;
         if (WHICH == 0) r.moves_off = off; else r.skip_off = off;
     }
-}
-
-// main traceback (c_banded_traceback, pyx:281-310) + _trim_traceback (resquiggle.py:754-764).
-// One LANE per read; launched with only TB_LANES reads per wavefront: the walk is a chain of
-// dependent memory round trips, so what counts is the number of wavefronts in flight, not
-// the lanes in use.  The pointer chase is made
-// latency-tolerant by prefetching: the path stays near the same band position from row to row
-// (the band follows it), so for the next TBR rows a 64-cell window of packed moves around the
-// current band position (one 16-byte load per row) and the band starts are fetched together,
-// then the rows are walked out of registers; a position outside its window falls back to
-// direct loads.  A run of stays is resolved with clz on the 2-bit fields.
-#ifndef TBR
-#define TBR 16
-#endif
-__device__ __forceinline__ int mv_find_le(u64 x, int top) // highest non-zero 2-bit field <= top, or -1
-{
-    const u64 m = top >= 31 ? x : (x & ((1ull << (2 * top + 2)) - 1ull));
-    const u64 nz = (m | (m >> 1)) & 0x5555555555555555ull;
-    return nz ? (63 - __clzll((long long)nz)) >> 1 : -1;
-}
-__global__ __launch_bounds__(64) void k_main_tb(ReadState *rs, i64 n_reads, const DevParams *dp,
-    const unsigned char *moves, const i64 *band_starts, i64 *read_tb)
-{
-    const i64 ri = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (ri >= n_reads) return;
-    ReadState &r = rs[ri];
-    if (r.status != TBA_OK) return;
-    if (r.path == PATH_NONE) { r.status = TBA_INTERNAL; return; }
-    if (r.tb_done) return;                              // walked chunk-parallel (k_tb_par.h)
-    if (r.is_long && r.path == PATH_ADAPTIVE && r.W <= 1024) return; // k_main_tb_long (k_long.h)
-    r.tb_form = TBA_TB_FORM_LANE;
-    const i64 B = r.B;
-    const int Wi = (int)r.W;
-    const int rowb = (int)mv_row_bytes(r.W);            // bytes per packed row (multiple of 64)
-    const int roww = rowb / 4;                          // dwords per row
-    const unsigned char *mv = moves + r.moves_off;
-    const i64 *st = band_starts + r.ref_off;
-    i64 *tb = read_tb + r.seg_off;
-    const bool adaptive = r.path == PATH_ADAPTIVE;
-    const int thresh = adaptive ? (int)dp->p.band_bound_thresh : -1;
-    i64 cur_ev = r.top_pos + st[B - 1];
-    tb[B] = cur_ev + 1;
-    int rc = TBA_OK;
-    int bp_guess = (int)r.top_pos;
-    for (i64 r0 = B; r0 >= 1 && rc == TBA_OK; r0 -= TBR) {
-        // fetch: band starts and a 4-dword window of row r0-k around the expected position
-        i64 stv[TBR];
-        uint4 win[TBR];
-        int wb = (bp_guess >> 4) - 2;                   // first dword of the window
-        wb = wb < 0 ? 0 : (wb > roww - 4 ? roww - 4 : wb);
-#pragma unroll
-        for (int k = 0; k < TBR; k++) {
-            const i64 rr = r0 - k;
-            const i64 rc_ = rr >= 1 ? rr : 1;
-            stv[k] = st[rc_ - 1];
-            win[k] = *(const uint4 *)(mv + rc_ * rowb + 4 * wb);
-        }
-        // Per row, off the dependent chain (it only needs the fetched window): one bit per cell
-        // for "not a stay" and "is a diagonal move" in the two 32-cell halves, and the answer for
-        // "everything at or below the position in the upper half was a stay" (the highest
-        // non-stay cell of the lower half).
-        u64 nzl[TBR], nzh[TBR], d2l[TBR], d2h[TBR];
-        int fl_full[TBR], m2_full[TBR];
-#pragma unroll
-        for (int k = 0; k < TBR; k++) {
-            const u64 lo = ((u64)win[k].y << 32) | win[k].x, hi = ((u64)win[k].w << 32) | win[k].z;
-            const u64 E = 0x5555555555555555ull;
-            nzl[k] = (lo | (lo >> 1)) & E; nzh[k] = (hi | (hi >> 1)) & E;
-            d2l[k] = (lo >> 1) & ~lo & E;  d2h[k] = (hi >> 1) & ~hi & E;
-            const int cf = __clzll((long long)(nzl[k] | 1ull)); // (| 1: defined for an empty half)
-            fl_full[k] = nzl[k] ? 31 - (cf >> 1) : -1;
-            m2_full[k] = (int)((d2l[k] >> (2 * (fl_full[k] & 31))) & 1ull);
-        }
-#pragma unroll
-        for (int k = 0; k < TBR; k++) {
-            const i64 rr = r0 - k;
-            const bool act = rr >= 1 && rc == TBA_OK;
-            // Fast form, branch-free on the dependent chain (a wavefront of 16 lanes on its own
-            // SIMD pays ~10 cycles per dependent instruction and much more per exec-mask
-            // branch): the position lies in the 64-cell window; the highest non-stay move at or
-            // below it is one shift + count-leading-zeros in its 32-cell half, else the
-            // precomputed answer of the lower half.
-            const i64 bp64 = cur_ev - stv[k];
-            int bp = (int)bp64;
-            const int lc = bp - 16 * wb;                // position inside the window
-            const bool in_win = bp64 < Wi && bp64 >= 0 && (unsigned)lc < 64u;
-            const bool up = (lc & 32) != 0;
-            const int amt = 62 - 2 * (lc & 31);
-            const u64 sn = (up ? nzh[k] : nzl[k]) << amt, s2 = (up ? d2h[k] : d2l[k]) << amt;
-            const bool hit = sn != 0;
-            const int c = __clzll((long long)(sn | 1ull)); // 1 + 2 (lc - f); 63 without a hit
-            const bool low = !hit && up && fl_full[k] >= 0;
-            const int m2_hit = (int)((s2 >> (63 - c)) & 1ull);
-            const int f = hit ? lc - (c >> 1) : fl_full[k];
-            const int m2 = hit ? m2_hit : m2_full[k];
-            const bool fast = in_win && (hit || low);
-            int m = m2 ? 2 : 1;
-            if (fast) bp = 16 * wb + f;
-            if (__builtin_expect(act && !fast, 0)) {
-                // outside the window, or nothing but stays down to its start: the reference's
-                // cell-by-cell walk with direct loads (python wrap-around of a negative index kept)
-                if (bp64 >= Wi || bp64 < -Wi) { rc = TBA_INTERNAL; continue; }
-                if (in_win) bp = wb > 0 ? 16 * wb - 1 : -1; // everything in the window was a stay
-                const unsigned char *row = mv + rr * rowb;
-#define MVG(b_) ({ int bb_ = (b_) < 0 ? (b_) + Wi : (b_); (int)((row[bb_ >> 2] >> (2 * (bb_ & 3))) & 3); })
-                m = MVG(bp);
-                while (m == 0) {
-                    bp--;
-                    if (bp < -Wi) { rc = TBA_INTERNAL; break; }
-                    m = MVG(bp);
-                }
-#undef MVG
-                if (rc != TBA_OK) continue;
-            }
-            if (m == 2) bp--;
-            const int edge = bp < Wi - bp - 1 ? bp : Wi - bp - 1;
-            const bool beyond = thresh >= 0 && edge < thresh;
-            if (act) {
-                if (beyond) rc = TBA_BEYOND_BANDWIDTH;
-                else {
-                    cur_ev = stv[k] + bp;
-                    tb[rr - 1] = cur_ev + 1;
-                    bp_guess = bp;
-                }
-            }
-        }
-    }
-    if (rc != TBA_OK) { r.status = rc; return; }
-    const i64 n_ev = r.n_ev - r.clip;
-    if (adaptive) { // _trim_traceback
-        i64 i = 0;
-        while (tb[i] < 0) { tb[i] = 0; i++; if (i > B) { r.status = TBA_INTERNAL; return; } }
-        i64 j = 1;
-        while (tb[B + 1 - j] > n_ev) { tb[B + 1 - j] = n_ev; j++; if (j > B + 1) { r.status = TBA_INTERNAL; return; } }
-    }
-    i64 t0 = tb[0];
-    if (!adaptive && (t0 < -(n_ev + 1) || t0 > n_ev)) { r.status = TBA_INTERNAL; return; }
-    if (t0 < 0) t0 += n_ev + 1;
-    r.top_pos = t0; // index of the first base's change point, consumed by k_tb_gather
 }
 
 // get_rel_raw_coords (resquiggle.py:858-864): segs[i] = valid_cpts[clip:][read_tb[i]] - first.

@@ -1,10 +1,15 @@
-// k_tb_par.h -- the main traceback (c_banded_traceback, pyx:281-310), rows of one read walked by
-// several lanes at once.
+// k_tb_par.h -- the traceback of the batch (c_banded_traceback, pyx:281-310): one walker of row blocks
+// (tbp_block), one view of a read (TbRead), one trim (tbp_trim), and the kernels built on them --
+//   k_main_tb_par<LPR>    the main traceback, rows of one read walked by several lanes at once (below);
+//   k_tb_par_verify<LPR>  walks again what k_main_tb_par's lanes handed to each other (same chunks: tbp_chunks);
+//   k_main_tb             the serial walk, a lane per read: what those two do not take or hand back;
+//   k_start_tb            the serial walk over the start band, and start discovery's epilogue.
+// A rule of the walk is written once, in tbp_block; the kernels differ in what they do with a row's value.
 //
 // The walk is a pointer chase: the state entering row rr is the event position cur_ev, and what it
 // is on leaving depends on the move codes of that row only.  k_main_tb walks the B rows of a read
 // on one lane (10 000 dependent steps: 4.8 ms for a batch of 10 kb reads however few reads there
-// are; 49 ms for a 200 kb read).  Here a read is cut into chunks of rows with a lane each:
+// are; 49 ms for a 200 kb read).  In k_main_tb_par a read is cut into chunks of rows with a lane each:
 //   phase A: the lane of chunk c walks the rows of its chunk, top to bottom, writing read_tb.
 //     Chunk 0 starts from the end of the forward pass (the true walk); a chunk c >= 1 starts at
 //     the MIDDLE of its top row's band (cell W / 2): the adaptive band is placed so that the best
@@ -57,6 +62,7 @@
 #pragma once
 #include "k_dp.h"
 
+#define TBR 16              // rows of a block: their move windows and band starts are fetched together
 #define TBP_NONE ((i64)0x3fffffffffffffffll)
 #define TBP_WAVE_BELOW 1024 // batches up to this many reads: a wavefront per read (latency form)
 #define TBP_MIN_CHUNK 64    // rows; the overlap (phase B) is a block of 16 or two
@@ -65,37 +71,83 @@
 // tba_common.h, and why __threadfence_block() is not the fence for that)
 #define tbp_fence wave_mem_fence
 
-// A kernel of this file must not be allocated exactly 224 VGPRs (see above): naming v231 as clobbered
-// makes the compiler report 232.  -DTBA_TB_ALLOC224 takes it away (the build the determinism test is
-// shown failing on, profiles/r06_traceback_determinism_alloc224.txt).
+// A chunk kernel must not be allocated exactly 224 VGPRs (see above): naming v231 as clobbered makes the
+// compiler report 232.  -DTBA_TB_ALLOC224 takes it away (the build the determinism test is shown failing
+// on, profiles/r06_traceback_determinism_alloc224.txt).  k_main_tb and k_start_tb are far below that
+// allocation and stay as the compiler makes them; tests/test_kernel_resources.py holds them to it too.
 #ifdef TBA_TB_ALLOC224
 #define TBP_NOT_224_VGPRS() ((void)0)
 #else
 #define TBP_NOT_224_VGPRS() asm volatile("" ::: "v231")
 #endif
-enum { TBP_A = 0, TBP_B = 1, TBP_V = 2 };
 
-// One block of TBR rows of one walker: rows r0, r0 - 1, ... > stop, with the reference's rules
-// (negative band positions wrap like Python indices).  The fetch / bit-mask / clz scheme is
-// k_main_tb's (k_dp.h).
-//   TBP_A (phase A): every row writes tb; a band-edge violation is recorded (viol_lo = its
-//     row; rows descend, so the last one recorded is the lowest) and the walk goes on; leaving the
-//     band ends it (rc).
-//   TBP_B (phase B): before a row's value is written it is compared with what tb holds
-//     (rows >= cmp_lo only: below that the lane underneath wrote nothing); equal -> merged_row = that
-//     row, the walk ends; a violation ends it as well (rc), as in the serial walk.
-//   TBP_V (the verifier): nothing is written; every row is compared with what tb holds and the
-//     rows that differ are counted in *dbg_stores (a band-edge violation is not its business: phase B
-//     has seen the same row).
+// What a walk needs of its read and never changes while it walks.
+struct TbRead {
+    const unsigned char *mv;    // packed move rows (k_dp.h), rowb bytes = roww dwords each
+    const unsigned char *strip; // the centre strip behind them (valid when strip_s0 >= 0)
+    const i64 *st;              // band starts
+    i64 *tb;                    // read_tb of the read
+    i64 B, n_static;            // rows; those of the static bands at the read's start (no strip there)
+    int rowb, roww, Wi;
+    int thresh;                 // band_bound_thresh, -1: no band-edge test
+    int strip_s0;               // first band cell of the strip, -1: none
+};
+// ... of a read of the batch.  !on (a lane group without a read to walk): a two-row read at the start of every
+// array, so that the group kernels compute their geometry without a branch; they walk nothing of it.
+__device__ __forceinline__ TbRead tbp_read(const ReadState *r, bool on, const DevParams *dp,
+    const unsigned char *moves, const i64 *band_starts, i64 *read_tb)
+{
+    TbRead v;
+    v.B = on ? r->B : 2;
+    v.Wi = on ? (int)r->W : 64;
+    v.rowb = (int)mv_row_bytes(v.Wi), v.roww = v.rowb / 4;
+    v.mv = moves + (on ? r->moves_off : 0);
+    v.st = band_starts + (on ? r->ref_off : 0);
+    v.tb = read_tb + (on ? r->seg_off : 0);
+    v.thresh = (int)dp->p.band_bound_thresh;
+    v.strip_s0 = on ? r->strip_s0 : -1;
+    v.strip = v.mv + (v.B + 1) * (i64)v.rowb;
+    v.n_static = on ? r->n_static : 0;
+    return v;
+}
+
+struct TbWalk { i64 cur_ev; int guess, rc; };  // a walker: event position, its band position (a guess for the next
+                                               // block's windows), TBA status
+
+// What a block does with the value of a row (the entry of read_tb under it) is its mode; a mode's extras travel
+// in its struct:
+enum { TBP_SERIAL, TBP_A, TBP_B, TBP_V };
+// the serial walk: every row writes tb; a band-edge violation ends the walk (rc)
+struct TbpSerial { static constexpr int mode = TBP_SERIAL; };
+// phase A: every row writes tb; a violation is recorded (viol_lo = its row; rows descend, so the last one
+// recorded is the lowest) and the walk goes on
+struct TbpA { static constexpr int mode = TBP_A; i64 viol_lo = TBP_NONE; };
+// phase B: before a row's value is written it is compared with what tb holds (rows >= cmp_lo only: below that the
+// lane underneath wrote nothing); equal -> merged_row = that row, the walk ends; a violation ends it as well (rc),
+// as in the serial walk.  stores, if given, counts the rows overwritten.
+struct TbpB { static constexpr int mode = TBP_B; i64 cmp_lo; int *stores; i64 merged_row = TBP_NONE; };
+// the verifier: nothing is written; every row is compared with what tb holds and the rows that differ are counted
+// (a band-edge violation is not its business: phase B has seen the same row)
+struct TbpV { static constexpr int mode = TBP_V; int n_diff = 0; };
+
+// One block of TBR rows of one walker: rows r0, r0 - 1, ... > stop, with the reference's rules (negative band
+// positions wrap like Python indices); leaving the band ends the walk (rc) in every mode.  The path stays near the
+// same band position from row to row (the band follows it), so a 64-cell window of packed moves around the position
+// guess (one 16-byte load per row) and the band starts of all rows are fetched together, then the rows are walked out
+// of registers; a position outside its window takes the slow path of its row.
 //   IDENT: the band of row r starts at event r - 1 (the static band of start discovery, resquiggle.py:710-716):
 //     no band-start array to read.
-template <int MODE, bool IDENT = false>
-__device__ __forceinline__ void tbp_block(const unsigned char *mv, int rowb, int roww, const i64 *st,
-    int Wi, int thresh, i64 r0, i64 stop, i64 &cur_ev, int &bp_guess, int &rc, i64 *tb,
-    i64 &viol_lo, i64 cmp_lo, i64 &merged_row, const unsigned char *strip, int strip_s0, i64 n_static,
-    int *dbg_stores)
+template <bool IDENT = false, class X>
+__device__ __forceinline__ void tbp_block(const TbRead &v, TbWalk &w, i64 r0, i64 stop, X &x)
 {
-    constexpr bool EXT = MODE != TBP_A, VER = MODE == TBP_V;
+    constexpr bool SER = X::mode == TBP_SERIAL, PHA = X::mode == TBP_A, PHB = X::mode == TBP_B, VER = X::mode == TBP_V;
+    constexpr bool EXT = PHB || VER;                // compares with what tb holds
+    const unsigned char *const mv = v.mv;
+    const i64 *const st = v.st;
+    i64 *const tb = v.tb;
+    const int rowb = v.rowb, roww = v.roww, Wi = v.Wi, thresh = v.thresh, strip_s0 = v.strip_s0;
+    i64 &cur_ev = w.cur_ev;
+    int &bp_guess = w.guess, &rc = w.rc;
     i64 stv[TBR];
     uint4 win[TBR];
     i64 oldv[TBR];
@@ -106,7 +158,7 @@ __device__ __forceinline__ void tbp_block(const unsigned char *mv, int rowb, int
     // there, eight rows to a cache line instead of one.  Same bits as the window of the full row at
     // dword strip_s0 / 16, so everything below is unchanged; a position outside takes the slow path of
     // its row (full row) and the next block looks again.
-    const bool use_strip = strip_s0 >= 0 && r0 - (TBR - 1) > n_static && bp_guess >= strip_s0 + 24 &&
+    const bool use_strip = strip_s0 >= 0 && r0 - (TBR - 1) > v.n_static && bp_guess >= strip_s0 + 24 &&
                            bp_guess < strip_s0 + 60;
     if (use_strip) wb = strip_s0 >> 4;
     // band starts (and, phase B / verifier, the recorded path) of two rows per 16-byte access: the lanes of a wavefront
@@ -131,8 +183,11 @@ __device__ __forceinline__ void tbp_block(const unsigned char *mv, int rowb, int
     for (int k = 0; k < TBR; k++) {
         const i64 rr = r0 - k;
         const i64 rc_ = rr >= 1 ? rr : 1;
-        win[k] = use_strip ? *(const uint4 *)(strip + rc_ * MV_STRIP_BYTES) : *(const uint4 *)(mv + rc_ * rowb + 4 * wb);
+        win[k] = use_strip ? *(const uint4 *)(v.strip + rc_ * MV_STRIP_BYTES) : *(const uint4 *)(mv + rc_ * rowb + 4 * wb);
     }
+    // Per row, off the dependent chain (it only needs the fetched window): one bit per cell for "not a stay" and "is a
+    // diagonal move" in the two 32-cell halves, and the answer for "everything at or below the position in the upper
+    // half was a stay" (the highest non-stay cell of the lower half).
     u64 nzl[TBR], nzh[TBR], d2l[TBR], d2h[TBR];
     int fl_full[TBR], m2_full[TBR];
 #pragma unroll
@@ -141,20 +196,25 @@ __device__ __forceinline__ void tbp_block(const unsigned char *mv, int rowb, int
         const u64 E = 0x5555555555555555ull;
         nzl[k] = (lo | (lo >> 1)) & E; nzh[k] = (hi | (hi >> 1)) & E;
         d2l[k] = (lo >> 1) & ~lo & E;  d2h[k] = (hi >> 1) & ~hi & E;
-        const int cf = __clzll((long long)(nzl[k] | 1ull));
+        const int cf = __clzll((long long)(nzl[k] | 1ull)); // (| 1: defined for an empty half)
         fl_full[k] = nzl[k] ? 31 - (cf >> 1) : -1;
         m2_full[k] = (int)((d2l[k] >> (2 * (fl_full[k] & 31))) & 1ull);
     }
     static_assert(TBR % 2 == 0, "rows are loaded and stored in pairs");
-    bool pend_a = false;                            // (phase A: the even row's value, waiting for its pair)
+    bool pend_a = false;                            // (writing modes: the even row's value, waiting for its pair)
     i64 pend_v = 0;
 #pragma unroll
     for (int k = 0; k < TBR; k++) {
         const i64 rr = r0 - k;
-        bool sa = false;                            // phase A: this row has a value to record (sv), stored with its pair row
+        bool sa = false;                            // writing modes: this row has a value to record (sv), stored with its pair row
         i64 sv = 0;
         {
-        const bool act = rr > stop && rr >= 1 && rc == TBA_OK && (!EXT || VER || merged_row == TBP_NONE);
+        bool act = rr > stop && rr >= 1 && rc == TBA_OK;
+        if constexpr (PHB) act = act && x.merged_row == TBP_NONE;
+        // Fast form, branch-free on the dependent chain (a wavefront of few busy lanes pays ~10 cycles per dependent
+        // instruction and much more per exec-mask branch): the position lies in the 64-cell window; the highest
+        // non-stay move at or below it is one shift + count-leading-zeros in its 32-cell half, else the precomputed
+        // answer of the lower half.
         const i64 bp64 = cur_ev - stv[k];
         int bp = (int)bp64;
         const int lc = bp - 16 * wb;                // position inside the window
@@ -208,22 +268,24 @@ __device__ __forceinline__ void tbp_block(const unsigned char *mv, int rowb, int
         const int edge = bp < Wi - bp - 1 ? bp : Wi - bp - 1;
         const bool beyond = thresh >= 0 && edge < thresh;
         if (act) {
-            if (EXT && !VER && beyond) rc = TBA_BEYOND_BANDWIDTH;
+            if ((SER || PHB) && beyond) rc = TBA_BEYOND_BANDWIDTH;
             else {
-                if (!EXT && beyond) viol_lo = rr;
+                if constexpr (PHA) { if (beyond) x.viol_lo = rr; }
                 cur_ev = stv[k] + bp;
                 bp_guess = bp;
-                if (VER) { if (oldv[k] != cur_ev + 1) ++*dbg_stores; }
-                else if (EXT && rr - 1 >= cmp_lo && oldv[k] == cur_ev + 1) merged_row = rr - 1;
-                else {
-                    if (EXT) tb[rr - 1] = cur_ev + 1; else { sa = true; sv = cur_ev + 1; }
-                    if (EXT && dbg_stores) ++*dbg_stores;
-                }
+                if constexpr (VER) { if (oldv[k] != cur_ev + 1) ++x.n_diff; }
+                else if constexpr (PHB) {
+                    if (rr - 1 >= x.cmp_lo && oldv[k] == cur_ev + 1) x.merged_row = rr - 1;
+                    else {
+                        tb[rr - 1] = cur_ev + 1;
+                        if (x.stores) ++*x.stores;
+                    }
+                } else { sa = true; sv = cur_ev + 1; }
             }
         }
         }
 row_end:
-        if (MODE == TBP_A) {
+        if (!EXT) {
             // rows r0 - k (even k) and r0 - k - 1 are neighbours in read_tb: one 16-byte store for the pair
             if ((k & 1) == 0) { pend_a = sa; pend_v = sv; }
             else if (pend_a && sa) {
@@ -238,79 +300,100 @@ row_end:
     }
 }
 
-// _trim_traceback (resquiggle.py:754-764) and the first base's change point, as k_main_tb (one lane)
-__device__ __forceinline__ void tbp_trim(ReadState &r, i64 *tb, i64 B)
+// After a finished walk (one lane): _trim_traceback (resquiggle.py:754-764) on the adaptive path, on the static one
+// the range check of the first entry; top_pos = the index of the first base's change point, consumed by k_tb_gather.
+// (volatile: after the chunk kernels the entries come from other lanes, through memory)
+__device__ __forceinline__ void tbp_trim(ReadState &r, i64 *tb, i64 B, bool adaptive)
 {
     const i64 n_ev = r.n_ev - r.clip;
     volatile i64 *vtb = tb;
-    {
+    if (adaptive) {
         i64 i = 0;
         while (vtb[i] < 0) { vtb[i] = 0; i++; if (i > B) { r.status = TBA_INTERNAL; return; } }
         i64 j = 1;
         while (vtb[B + 1 - j] > n_ev) { vtb[B + 1 - j] = n_ev; j++; if (j > B + 1) { r.status = TBA_INTERNAL; return; } }
     }
     i64 t0 = vtb[0];
+    if (!adaptive && (t0 < -(n_ev + 1) || t0 > n_ev)) { r.status = TBA_INTERNAL; return; }
     if (t0 < 0) t0 += n_ev + 1;
     r.top_pos = t0;
 }
 
-// LPR lanes per read (a power of two <= 64), 64 / LPR reads per wavefront.  idx != nullptr: the
-// reads are idx[0 .. n_reads) (the long reads: one wavefront each).  Reads this kernel finishes
-// are marked (ReadState.tb_done) and skipped by k_main_tb / k_main_tb_long.
+// The group kernels (k_main_tb_par, k_tb_par_verify): LPR lanes per read (a power of two <= 64), 64 / LPR reads per
+// wavefront.  idx != nullptr: the reads are idx[0 .. n_reads) (the long reads: one wavefront each).
+// -> the read of this lane's group; !have: the group is past the end of the batch (read 0 stands in, not walked)
+template <int LPR>
+__device__ __forceinline__ i64 tbp_group_read(i64 n_reads, const i32 *idx, bool &have)
+{
+    const i64 slot = (i64)blockIdx.x * (64 / LPR) + threadIdx.x / LPR;
+    have = slot < n_reads;
+    return have ? (idx ? (i64)idx[slot] : slot) : 0;
+}
+
+// The chunks of a read, and lane c's.  Chunk c: rows (lo, hi], hi = B - c L; fewer chunks than lanes for short reads.
+// The rows of the static bands at the start of the read (masked start, resquiggle.py:607-683: the path is anywhere
+// in those bands, not near their middle) all belong to the lowest chunk.  The verifier is worth something only
+// while it looks under exactly the chunk tops phase B wrote below: this is the one definition both use.
+struct TbChunks {
+    i64 L;          // rows per chunk
+    int n_chunks;
+    i64 hi, lo;     // lane c's chunk
+    i64 lo2;        // lo of chunk c + 1: where phase B (and the verifier) of lane c must stop
+};
+template <int LPR>
+__device__ __forceinline__ TbChunks tbp_chunks(const TbRead &v, int c)
+{
+    TbChunks g;
+    i64 top_rows = v.B - (v.n_static + 16);
+    top_rows = top_rows < 1 ? 1 : top_rows;
+    g.L = (top_rows + LPR - 1) / LPR;
+    g.L = g.L < TBP_MIN_CHUNK ? TBP_MIN_CHUNK : g.L;
+    g.n_chunks = (int)((top_rows + g.L - 1) / g.L);
+    g.hi = v.B - (i64)c * g.L;
+    g.lo = c >= g.n_chunks - 1 || g.hi - g.L < 0 ? 0 : g.hi - g.L;
+    g.lo2 = c + 1 >= g.n_chunks - 1 || g.lo - g.L < 0 ? 0 : g.lo - g.L;
+    return g;
+}
+
+// Reads this kernel finishes are marked (ReadState.tb_done) and skipped by k_main_tb / k_main_tb_long.
 template <int LPR>
 __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, const i32 *idx,
     const DevParams *dp, const unsigned char *moves, const i64 *band_starts, i64 *read_tb)
 {
-    constexpr int RPW = 64 / LPR;
-    const int lane = threadIdx.x, g = lane / LPR, c = lane % LPR, gbase = g * LPR;
+    const int lane = threadIdx.x, c = lane % LPR, gbase = lane - c;
     TBP_NOT_224_VGPRS();
-    const i64 slot = (i64)blockIdx.x * RPW + g;
-    const bool have = slot < n_reads;
-    const i64 ri = have ? (idx ? (i64)idx[slot] : slot) : 0;
+    bool have;
+    const i64 ri = tbp_group_read<LPR>(n_reads, idx, have);
     ReadState &r = rs[ri];
     // every lane of the group takes the same decision here (same read)
     const bool on = have && r.status == TBA_OK && r.path == PATH_ADAPTIVE && r.tb_done == 0 &&
                     (idx != nullptr || !r.is_long) && r.B >= 2 && cpl_class(r.W) != 0;
-    const i64 B = on ? r.B : 2;
-    const int Wi = on ? (int)r.W : 64;
-    const int rowb = (int)mv_row_bytes(Wi), roww = rowb / 4;
-    const unsigned char *mv = moves + (on ? r.moves_off : 0);
-    const i64 *st = band_starts + (on ? r.ref_off : 0);
-    i64 *tb = read_tb + (on ? r.seg_off : 0);
-    const int thresh = (int)dp->p.band_bound_thresh;
-    const int strip_s0 = on ? r.strip_s0 : -1;
-    const unsigned char *strip = mv + (B + 1) * (i64)rowb;   // (behind the move rows; valid when strip_s0 >= 0)
-    const i64 n_stat = on ? r.n_static : 0;
-
-    // chunk c: rows (lo, hi], hi = B - c L; fewer chunks than lanes for short reads.  The rows of
-    // the static bands at the start of the read (masked start, resquiggle.py:607-683: the path is
-    // anywhere in those bands, not near their middle) all belong to the lowest chunk.
-    i64 top_rows = B - ((on ? r.n_static : 0) + 16);
-    top_rows = top_rows < 1 ? 1 : top_rows;
-    i64 L = (top_rows + LPR - 1) / LPR;
-    L = L < TBP_MIN_CHUNK ? TBP_MIN_CHUNK : L;
-    const int n_chunks = (int)((top_rows + L - 1) / L);
-    const i64 hi = B - (i64)c * L, lo = c >= n_chunks - 1 || hi - L < 0 ? 0 : hi - L;
+    const TbRead v = tbp_read(&r, on, dp, moves, band_starts, read_tb);
+    const TbChunks g = tbp_chunks<LPR>(v, c);
+    const i64 B = v.B, hi = g.hi, lo = g.lo;
+    const int n_chunks = g.n_chunks;
+    i64 *const tb = v.tb;
     const bool mine = on && c < n_chunks;
     // ---- phase A
-    i64 cur = 0, viol_lo = TBP_NONE, none = TBP_NONE;
-    int guess = Wi / 2, rcA = TBA_OK;
+    TbWalk w = { 0, v.Wi / 2, TBA_OK };
     if (mine) {
-        if (c == 0) { guess = (int)r.top_pos; cur = r.top_pos + st[B - 1]; tb[B] = cur + 1; }
-        else cur = st[hi - 1] + Wi / 2;
+        if (c == 0) { w.guess = (int)r.top_pos; w.cur_ev = r.top_pos + v.st[B - 1]; tb[B] = w.cur_ev + 1; }
+        else w.cur_ev = v.st[hi - 1] + v.Wi / 2;
     }
-    const i64 start_ev = cur;                       // my state entering row hi
+    const i64 start_ev = w.cur_ev;                  // my state entering row hi
+    TbpA pa;
     {
         i64 r0 = hi;
         bool walking = mine;
         while (__any(walking)) {
             if (walking) {
-                tbp_block<TBP_A>(mv, rowb, roww, st, Wi, thresh, r0, lo, cur, guess, rcA, tb, viol_lo, 0, none, strip, strip_s0, n_stat, nullptr);
+                tbp_block(v, w, r0, lo, pa);
                 r0 -= TBR;
-                if (rcA != TBA_OK || r0 <= lo) walking = false;
+                if (w.rc != TBA_OK || r0 <= lo) walking = false;
             }
         }
     }
+    const int rcA = w.rc;
     // the lowest tb index this lane wrote a value into: rows are written top-down and a walk that
     // dies (rcA) stops writing, so without a death it is lo; after one, nothing below is known --
     // the lane above then compares nothing in this chunk (cmp_lo above every row of it)
@@ -319,25 +402,25 @@ __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, 
     // ---- phase B: into chunk c + 1
     const bool ext = mine && c + 1 < n_chunks && rcA == TBA_OK;
     const i64 nxt_start = shfl_i64(start_ev, (lane + 1) & 63), nxt_wrote_lo = shfl_i64(wrote_lo, (lane + 1) & 63);
-    const i64 lo2 = c + 1 >= n_chunks - 1 || lo - L < 0 ? 0 : lo - L; // lo of chunk c + 1
-    i64 merged_row = TBP_NONE;
-    int rcB = TBA_OK;
     LapClock<8, phase_on(PH_TB_PAR)> counts;       // what phase B did, added up per read (tba_phase.h, id 12)
     int dbg_st = 0;                                // rows overwritten in phase B (counted in that build only)
-    int *dbg_stp = phase_on(PH_TB_PAR) ? &dbg_st : nullptr;
-    const bool dbg_imm = phase_on(PH_TB_PAR) && ext && cur == nxt_start; // merged at once: the state is equal on entry
+    TbpB pb = { nxt_wrote_lo, phase_on(PH_TB_PAR) ? &dbg_st : nullptr };
+    w.rc = TBA_OK;
+    const bool dbg_imm = phase_on(PH_TB_PAR) && ext && w.cur_ev == nxt_start; // merged at once: the state is equal on entry
     {
         bool walking = ext;
-        if (ext && cur == nxt_start) { merged_row = lo; walking = false; } // (entering row lo = its hi)
+        if (ext && w.cur_ev == nxt_start) { pb.merged_row = lo; walking = false; } // (entering row lo = its hi)
         i64 r0 = lo;
         while (__any(walking)) {
             if (walking) {
-                tbp_block<TBP_B>(mv, rowb, roww, st, Wi, thresh, r0, lo2, cur, guess, rcB, tb, viol_lo, nxt_wrote_lo, merged_row, strip, strip_s0, n_stat, dbg_stp);
+                tbp_block(v, w, r0, g.lo2, pb);
                 r0 -= TBR;
-                if (rcB != TBA_OK || merged_row != TBP_NONE || r0 <= lo2) walking = false;
+                if (w.rc != TBA_OK || pb.merged_row != TBP_NONE || r0 <= g.lo2) walking = false;
             }
         }
     }
+    const int rcB = w.rc;
+    const i64 merged_row = pb.merged_row;
 #ifdef TBA_TB_INJECT
     // (test build, libtombo_amd_inject.so: the round-5 fault made deterministic -- the first row under the second
     // chunk top of every TBA_TB_INJECT-th read comes out one event too high; tests/test_gpu_determinism.py
@@ -359,7 +442,7 @@ __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, 
     bool broken = false, from_b = false;            // from_b: the status is a phase B's
     i64 true_from = B + 1;                          // chunk 0: all of phase A is the true walk
     for (int j = 0; j < LPR; j++) {
-        const i64 vj = shfl_i64(viol_lo, gbase + j), mj = shfl_i64(merged_row, gbase + j);
+        const i64 vj = shfl_i64(pa.viol_lo, gbase + j), mj = shfl_i64(merged_row, gbase + j);
         const int aj = __shfl(rcA, gbase + j, 64), bj = __shfl(rcB, gbase + j, 64);
         if (j >= n_chunks || status != TBA_OK || broken) continue;
         if (vj != TBP_NONE && vj <= true_from) { status = TBA_BEYOND_BANDWIDTH; continue; }
@@ -381,8 +464,83 @@ __global__ __launch_bounds__(64) void k_main_tb_par(ReadState *rs, i64 n_reads, 
 #else
     tbp_fence(); // the lanes' read_tb entries, before lane 0 of the group reads them back
     r.tb_done = 1;
-    tbp_trim(r, tb, B);
+    tbp_trim(r, tb, B, true);
 #endif
+}
+
+// The verifier, behind the kernel boundary (what the result rests on: top of this file).  Same lanes,
+// same chunks (tbp_chunks) as k_main_tb_par<LPR>, over the reads it finished (tb_done == 2): the lane of
+// boundary c takes the state entering the top row of chunk c + 1 from the entry above it -- the bottom
+// of chunk c, true by the chain -- walks TBR rows down without writing and counts the rows where
+// read_tb holds something else.  Phase B merged within two rows at nearly every boundary and its
+// faults of round 5 sat in its first row, so this covers what phase B wrote; rows it walked beyond
+// the first block (one boundary in ~300) rest on phase B alone.  A read with any disagreement goes
+// back to the serial kernels (tb_done = 0, its count in tb_verify_fail); the others are trimmed here.
+template <int LPR>
+__global__ __launch_bounds__(64) void k_tb_par_verify(ReadState *rs, i64 n_reads, const i32 *idx,
+    const DevParams *dp, const unsigned char *moves, const i64 *band_starts, i64 *read_tb)
+{
+    const int lane = threadIdx.x, c = lane % LPR, gbase = lane - c;
+    TBP_NOT_224_VGPRS();
+    bool have;
+    const i64 ri = tbp_group_read<LPR>(n_reads, idx, have);
+    ReadState &r = rs[ri];
+    const bool on = have && r.status == TBA_OK && r.path == PATH_ADAPTIVE && r.tb_done == 2 && r.tb_form == LPR &&
+                    (idx != nullptr || !r.is_long);
+    const TbRead v = tbp_read(&r, on, dp, moves, band_starts, read_tb);
+    const TbChunks g = tbp_chunks<LPR>(v, c);
+    const i64 lo = g.lo;
+    const bool ext = on && c + 1 < g.n_chunks && lo >= 1;
+    // recorded after row lo + 1: the state entering row lo, + 1
+    TbWalk w = { ext ? v.tb[lo] - 1 : 0, v.Wi / 2, TBA_OK };
+    if (ext) {
+        const i64 g0 = w.cur_ev - v.st[lo - 1];
+        w.guess = g0 < 0 ? 0 : (g0 >= v.Wi ? v.Wi - 1 : (int)g0);
+    }
+    TbpV pv;
+    if (ext) tbp_block(v, w, lo, g.lo2, pv);
+    if (ext && w.rc != TBA_OK) pv.n_diff++;         // (a walk that died where phase B's did not)
+    int total = 0;
+    for (int j = 0; j < LPR; j++) total += __shfl(pv.n_diff, gbase + j, 64);
+    if (!on || c != 0) return;
+    if (total != 0) {                               // the serial kernels walk this read from top_pos, untouched so far
+        r.tb_verify_fail = total;
+        r.tb_done = 0;
+        r.tb_form = TBA_TB_FORM_NONE;
+        return;
+    }
+    r.tb_done = 1;
+    tbp_trim(r, v.tb, v.B, true);
+}
+
+// The serial main traceback: one LANE per read, for what the kernels above do not take or hand back -- static
+// bands, bands wider than every class, reads of a single base, reads whose chain broke or whose status rested on a
+// phase B, reads the verifier disagreed with.  Launched with only TB_LANES reads per wavefront: the walk is a chain
+// of dependent steps, so what counts is the number of wavefronts in flight, not the lanes in use.  Its windows
+// always come from the full rows: static rows have no strip, and nothing is measured for the few adaptive reads here.
+// (The pair of band starts a single-base read loads ends 8 bytes past its own entry: the next read's, or the slack
+// every device buffer of the engine is allocated with.)
+__global__ __launch_bounds__(64) void k_main_tb(ReadState *rs, i64 n_reads, const DevParams *dp,
+    const unsigned char *moves, const i64 *band_starts, i64 *read_tb)
+{
+    const i64 ri = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ri >= n_reads) return;
+    ReadState &r = rs[ri];
+    if (r.status != TBA_OK) return;
+    if (r.path == PATH_NONE) { r.status = TBA_INTERNAL; return; }
+    if (r.tb_done) return;                              // walked chunk-parallel
+    if (r.is_long && r.path == PATH_ADAPTIVE && r.W <= 1024) return; // k_main_tb_long (k_long.h)
+    r.tb_form = TBA_TB_FORM_LANE;
+    TbRead v = tbp_read(&r, true, dp, moves, band_starts, read_tb);
+    const bool adaptive = r.path == PATH_ADAPTIVE;
+    v.strip_s0 = -1;
+    if (!adaptive) v.thresh = -1;
+    TbWalk w = { r.top_pos + v.st[v.B - 1], (int)r.top_pos, TBA_OK };
+    v.tb[v.B] = w.cur_ev + 1;
+    TbpSerial ps;
+    for (i64 r0 = v.B; r0 >= 1 && w.rc == TBA_OK; r0 -= TBR) tbp_block(v, w, r0, 0, ps);
+    if (w.rc != TBA_OK) { r.status = w.rc; return; }
+    tbp_trim(r, v.tb, v.B, adaptive);
 }
 
 // start discovery epilogue: traceback, score_valid_bases (tombo_stats.py:2340-2362), events per
@@ -401,19 +559,21 @@ __global__ __launch_bounds__(64) void k_start_tb(ReadState *rs, i64 n_reads, con
     const i64 nb = P.start_n_bases;
     const i64 bw = mode == DP_START_TRY ? P.start_bw : P.start_save_bw;
     i64 *tb = read_tb + r.seg_off;
-    // c_banded_traceback over the start band (identity band starts, no band-edge test) in blocks of TBR rows: their
-    // 64-cell windows fetched together (tbp_block; a cell-by-cell walk is a dependent memory round trip per cell --
-    // 0.5 ms per launch for 250 rows, whatever the batch)
-    int rc = TBA_OK;
-    {
-        const unsigned char *mv = moves + ri * start_moves_stride;
-        const int rowb = (int)mv_row_bytes(bw), roww = rowb / 4;
-        i64 cur = r.top_pos + (nb - 1), viol = TBP_NONE, none = TBP_NONE;
-        int guess = (int)r.top_pos;
-        tb[nb] = cur + 1;
-        for (i64 r0 = nb; r0 >= 1 && rc == TBA_OK; r0 -= TBR)
-            tbp_block<TBP_A, true>(mv, rowb, roww, nullptr, (int)bw, -1, r0, 0, cur, guess, rc, tb, viol, 0, none, nullptr, -1, 0, nullptr);
-    }
+    // c_banded_traceback over the start band (identity band starts, no strip, no band-edge test) in blocks of TBR
+    // rows (a cell-by-cell walk is a dependent memory round trip per cell -- 0.5 ms per launch for 250 rows, whatever
+    // the batch)
+    TbRead v = {};
+    v.mv = moves + ri * start_moves_stride;
+    v.tb = tb;
+    v.B = nb;
+    v.Wi = (int)bw;
+    v.rowb = (int)mv_row_bytes(bw), v.roww = v.rowb / 4;
+    v.thresh = v.strip_s0 = -1;
+    TbWalk w = { r.top_pos + (nb - 1), (int)r.top_pos, TBA_OK };
+    tb[nb] = w.cur_ev + 1;
+    TbpSerial ps;
+    for (i64 r0 = nb; r0 >= 1 && w.rc == TBA_OK; r0 -= TBR) tbp_block<true>(v, w, r0, 0, ps);
+    int rc = w.rc;
     const double *ev = event_means + r.ev_off;
     if (rc == TBA_OK && mode == DP_START_TRY && dp->o.check_start_score) {
         const double *mu = ref_means + r.ref_off, *sd = ref_sds + r.ref_off;
@@ -441,64 +601,4 @@ __global__ __launch_bounds__(64) void k_start_tb(ReadState *rs, i64 n_reads, con
     } else {
         r.status = rc;
     }
-}
-
-// The verifier, behind the kernel boundary (what the result rests on: top of this file).  Same lanes,
-// same chunk geometry as k_main_tb_par<LPR>, over the reads it finished (tb_done == 2): the lane of
-// boundary c takes the state entering the top row of chunk c + 1 from the entry above it -- the bottom
-// of chunk c, true by the chain -- walks TBR rows down without writing and counts the rows where
-// read_tb holds something else.  Phase B merged within two rows at nearly every boundary and its
-// faults of round 5 sat in its first row, so this covers what phase B wrote; rows it walked beyond
-// the first block (one boundary in ~300) rest on phase B alone.  A read with any disagreement goes
-// back to the serial kernels (tb_done = 0, its count in tb_verify_fail); the others are trimmed here.
-template <int LPR>
-__global__ __launch_bounds__(64) void k_tb_par_verify(ReadState *rs, i64 n_reads, const i32 *idx,
-    const DevParams *dp, const unsigned char *moves, const i64 *band_starts, i64 *read_tb)
-{
-    constexpr int RPW = 64 / LPR;
-    const int lane = threadIdx.x, g = lane / LPR, c = lane % LPR, gbase = g * LPR;
-    TBP_NOT_224_VGPRS();
-    const i64 slot = (i64)blockIdx.x * RPW + g;
-    const bool have = slot < n_reads;
-    const i64 ri = have ? (idx ? (i64)idx[slot] : slot) : 0;
-    ReadState &r = rs[ri];
-    const bool on = have && r.status == TBA_OK && r.path == PATH_ADAPTIVE && r.tb_done == 2 && r.tb_form == LPR &&
-                    (idx != nullptr || !r.is_long);
-    const i64 B = on ? r.B : 2;
-    const int Wi = on ? (int)r.W : 64;
-    const int rowb = (int)mv_row_bytes(Wi), roww = rowb / 4;
-    const unsigned char *mv = moves + (on ? r.moves_off : 0);
-    const i64 *st = band_starts + (on ? r.ref_off : 0);
-    i64 *tb = read_tb + (on ? r.seg_off : 0);
-    const int strip_s0 = on ? r.strip_s0 : -1;
-    const unsigned char *strip = mv + (B + 1) * (i64)rowb;
-    const i64 n_stat = on ? r.n_static : 0;
-    i64 top_rows = B - ((on ? r.n_static : 0) + 16);   // (the chunk geometry of k_main_tb_par)
-    top_rows = top_rows < 1 ? 1 : top_rows;
-    i64 L = (top_rows + LPR - 1) / LPR;
-    L = L < TBP_MIN_CHUNK ? TBP_MIN_CHUNK : L;
-    const int n_chunks = (int)((top_rows + L - 1) / L);
-    const i64 hi = B - (i64)c * L, lo = c >= n_chunks - 1 || hi - L < 0 ? 0 : hi - L;
-    const i64 lo2 = c + 1 >= n_chunks - 1 || lo - L < 0 ? 0 : lo - L;
-    const bool ext = on && c + 1 < n_chunks && lo >= 1;
-    i64 cur = ext ? tb[lo] - 1 : 0;                 // recorded after row lo + 1: the state entering row lo, + 1
-    int guess = Wi / 2, rc = TBA_OK, n_diff = 0;
-    if (ext) {
-        const i64 g0 = cur - st[lo - 1];
-        guess = g0 < 0 ? 0 : (g0 >= Wi ? Wi - 1 : (int)g0);
-    }
-    i64 none = TBP_NONE, viol = TBP_NONE;
-    if (ext) tbp_block<TBP_V>(mv, rowb, roww, st, Wi, -1, lo, lo2, cur, guess, rc, tb, viol, 0, none, strip, strip_s0, n_stat, &n_diff);
-    if (ext && rc != TBA_OK) n_diff++;              // (a walk that died where phase B's did not)
-    int total = 0;
-    for (int j = 0; j < LPR; j++) total += __shfl(n_diff, gbase + j, 64);
-    if (!on || c != 0) return;
-    if (total != 0) {                               // the serial kernels walk this read from top_pos, untouched so far
-        r.tb_verify_fail = total;
-        r.tb_done = 0;
-        r.tb_form = TBA_TB_FORM_NONE;
-        return;
-    }
-    r.tb_done = 1;
-    tbp_trim(r, tb, B);
 }
