@@ -141,3 +141,52 @@ def test_the_verifier_catches_an_injected_fault_and_the_read_is_walked_again():
     env = dict(os.environ, TBA_LIB_PATH=_native.INJECT_LIB_PATH)
     p = subprocess.run([sys.executable, '-c', _INJECT_CHILD % dict(root=ROOT)], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and 'INJECT_OK' in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]
+
+
+_HAND_BACK_CHILD = r'''
+import sys, time, numpy as np
+sys.path.insert(0, %(root)r); sys.path.insert(0, %(root)r + '/tests')
+from tombo_amd import _native as N, resquiggle as rq
+import tb_cases as T
+from test_gpu_parity import run_batch, compare_batch
+model, params = T.dna()
+runs = [c for _, c in T.INJECT] + [dict(T.LONG)['plain'], dict(T.LONG)['run >= 66']]
+n = 5 * len(runs)
+cases = [runs[i // 5] if i %% 5 == 3 else T.Case(500, 2000, 700 + i, None, 0) for i in range(n)]
+injected = np.arange(n) %% 5 == 3
+is_long = np.array([c.nb > 24576 for c in cases])
+assert is_long.sum() == 2 and np.all(injected[is_long])
+t0 = time.perf_counter()
+rq.get_engine(0).set_dispatch(0, 0)       # the throughput form: k_main_tb_par<16>, the long reads through <64> and the index list
+eng, out, oracles = run_batch(model, params[500], 'DNA', [T.make_read(model, c) for c in cases])
+assert all(o['status'] == 0 for o in oracles), [o['status'] for o in oracles]
+bad = compare_batch(eng, oracles, out, 'hand-back')
+assert not bad, '\n'.join(bad[:40])
+vf, form, path = eng.get(N.GET_TB_VERIFY_FAIL), eng.get(N.GET_TB_FORM), eng.get(N.GET_PATH)
+assert np.all(path[:, 0] == 1)
+assert np.array_equal(vf != 0, injected), (np.flatnonzero(vf).tolist(), vf[vf != 0].tolist())
+assert np.all(form[injected & ~is_long] == N.TB_FORM_LANE) and np.all(form[is_long] == N.TB_FORM_LONG), form[injected].tolist()
+assert np.all(form[~injected] == N.TB_FORM_PAR16), form.tolist()
+# the runs are where the table says, in the geometry the engine walked with: the perturbed entry is the run's own row
+for i in np.flatnonzero(injected & ~is_long):
+    off = T.INJECT[i // 5][0]
+    assert T.longest_run(oracles[i])[0] - T.chunk_tops(2000, int(path[i, 1]), 16)[1][2] == off, i
+    assert T.longest_run(oracles[i])[1] >= 66
+assert T.longest_run(oracles[n - 2])[1] >= 33
+print('HAND_BACK_OK %%d reads handed back, verify_fail %%s, %%.2f s' %% (injected.sum(), vf[injected].tolist(), time.perf_counter() - t0))
+'''
+
+
+def test_handed_back_reads_with_long_runs_are_walked_by_the_serial_kernels():
+    """the inject build again, throughput form, a host-built batch: the injected reads (index = 3 mod 5) are 2 kb reads
+    with a run of >= 66 events in the very row under the chunk top hi_2 whose entry the build perturbs, or a few rows
+    under it, and two reads of 24 800 bases, one with such a run.  The verifier names exactly those; k_main_tb's
+    serial mode walks the 2 kb reads -- adaptive, band-edge threshold active, tbp_block's slow path in them -- and
+    k_main_tb_long the long ones, inside a batch of the throughput form; every result is the oracle's."""
+    from tombo_amd import _native
+    if not os.path.exists(_native.INJECT_LIB_PATH):
+        pytest.fail('%s is missing: run `python -c "import __graft_entry__ as g; g.build()"`' % _native.INJECT_LIB_PATH)
+    env = dict(os.environ, TBA_LIB_PATH=_native.INJECT_LIB_PATH)
+    p = subprocess.run([sys.executable, '-c', _HAND_BACK_CHILD % dict(root=ROOT)], env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and 'HAND_BACK_OK' in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]
+    print(p.stdout.strip().splitlines()[-1])
