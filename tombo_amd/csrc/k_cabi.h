@@ -3,17 +3,14 @@
 #pragma once
 #include "tba_common.h"
 #include "k_dp.h"
+#include "k_base_dp.h" // base_z, base_forward_row, base_traceback: one copy, shared with the batch pipeline (k_tail.h)
 
 // c_base_z_scores, _c_dynamic_programming.pyx:17-32
 __global__ void k_c_base_z_scores(const double *sig, i64 n, double mean, double sd, int winsor,
                                   double mh, double *out)
 {
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
-        double z = (sig[i] - mean) / sd;
-        if (z > 0) z = -z;
-        if (winsor && z < -mh) z = -mh;
-        out[i] = z;
-    }
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x)
+        out[i] = base_z((sig[i] - mean) / sd, winsor != 0, mh);
 }
 
 // (c_new_means, _c_helper.pyx:59-71: tba_c_new_means runs the batch pipeline's k_event_means, k_segment.h)
@@ -133,85 +130,30 @@ __global__ void k_c_reg_z(const double *r_sig, i64 n_sig, const double *means, c
     if (s < 0 || e > n_sig || z_off[b] + (e - s) > z_cap) { if (threadIdx.x == 0) *status = TBA_INTERNAL; return; }
     const double mu = means[reg_start + b], sd = sds[reg_start + b];
     double *out = z + z_off[b];
-    for (i64 k = threadIdx.x; k < e - s; k += blockDim.x) {
-        double v = (r_sig[s + k] - mu) / sd;
-        if (v > 0) v = -v;
-        if (winsor && v < -mh) v = -mh;
-        out[k] = v;
-    }
+    for (i64 k = threadIdx.x; k < e - s; k += blockDim.x) out[k] = base_z((r_sig[s + k] - mu) / sd, winsor != 0, mh);
 }
 
-// c_base_forward_pass, _c_dynamic_programming.pyx:99-163 (one serial chain; one thread).
-// Negative indices wrap like the Cython buffer accesses, other out-of-range accesses are the
-// reference's IndexError (TBA_INTERNAL).
+// c_base_forward_pass, _c_dynamic_programming.pyx:99-163 (one serial chain; one thread): base_forward_row, k_base_dp.h
 __global__ void k_c_base_forward_pass(const double *b_data, i64 b_start, i64 b_end,
     const double *prev_b_data, i64 prev_b_start, i64 prev_b_end, const double *prev_fwd,
     const i64 *prev_last_diag, i64 m, double *cum, double *b_fwd, i64 *b_last_diag, i32 *status)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const i64 b_len = b_end - b_start, plen = prev_b_end - prev_b_start;
-    { double acc = 0; for (i64 k = 0; k < plen; k++) { acc = k == 0 ? prev_b_data[k] : acc + prev_b_data[k]; cum[k] = acc; } }
-    i64 i0 = b_start - prev_b_start - 1;
-    if (i0 < 0) i0 += plen;
-    if (i0 < 0 || i0 >= plen) { *status = TBA_INTERNAL; return; }
-    b_fwd[0] = b_data[0] + prev_fwd[i0];
-    b_last_diag[0] = 1;
-    for (i64 pos = b_start + 1; pos < prev_b_end + 1; pos++) {
-        if (pos - b_start >= b_len) { *status = TBA_INTERNAL; return; }
-        i64 lag = 1;
-        for (;;) {
-            i64 idx = pos - prev_b_start - lag;
-            if (idx < 0) idx += plen;
-            if (idx < 0 || idx >= plen) { *status = TBA_INTERNAL; return; }
-            if (prev_last_diag[idx] + lag <= m) lag++;
-            else break;
-        }
-        i64 di = pos - prev_b_start - lag;
-        if (di < 0) di += plen;
-        double diag = prev_fwd[di];
-        if (lag > 1) diag += cum[pos - prev_b_start - 1] - cum[di];
-        const double stay = b_fwd[pos - b_start - 1];
-        double best;
-        i64 dv;
-        if (diag > stay) { best = diag; dv = 1; }
-        else { best = stay; dv = b_last_diag[pos - b_start - 1] + 1; }
-        b_fwd[pos - b_start] = b_data[pos - b_start] + best;
-        b_last_diag[pos - b_start] = dv;
-    }
-    if (b_end > prev_b_end + 1) {
-        i64 at = prev_b_end - b_start;
-        if (at < 0) at += b_len;
-        if (at < 0 || at >= b_len) { *status = TBA_INTERNAL; return; }
-        double fv = b_fwd[at];
-        i64 cl = b_last_diag[at];
-        for (i64 k = 0; k < b_end - prev_b_end - 1; k++) {
-            fv += b_data[k + prev_b_end - b_start + 1];
-            cl += 1;
-            b_fwd[k + prev_b_end - b_start + 1] = fv;
-            b_last_diag[k + prev_b_end - b_start + 1] = cl;
-        }
-    }
+    const int rc = base_forward_row(b_data, b_start, b_end, prev_b_data, prev_b_start, prev_b_end, prev_fwd,
+                                    prev_last_diag, m, cum, b_fwd, b_last_diag);
+    if (rc != TBA_OK) *status = rc;
 }
 
-// c_base_traceback, _c_dynamic_programming.pyx:165-182; *out = -1 where the reference runs off
-// the loop (returns None)
+// c_base_traceback, _c_dynamic_programming.pyx:165-182 (base_traceback, k_base_dp.h); *out = -1 where the reference runs
+// off the loop (returns None)
 __global__ void k_c_base_traceback(const double *curr, i64 curr_len, i64 curr_start,
     const double *next, i64 next_len, i64 next_start, i64 next_end, i64 sig_start, i64 m,
     i64 *out, i32 *status)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    i64 cnt = 1;
-    *out = -1;
-    for (i64 sp = sig_start; sp >= 0; sp--) {
-        cnt += 1;
-        if (cnt <= m || sp - 1 >= next_end) continue;
-        if (sp <= curr_start) { *out = sp; return; }
-        i64 ni = sp - next_start - 1, ci = sp - curr_start - 1;
-        if (ni < 0) ni += next_len;
-        if (ci < 0) ci += curr_len;
-        if (ni < 0 || ni >= next_len || ci < 0 || ci >= curr_len) { *status = TBA_INTERNAL; return; }
-        if (next[ni] > curr[ci]) { *out = sp; return; }
-    }
+    const i64 found = base_traceback<true>(curr, curr_len, curr_start, next, next_len, next_start, next_end, sig_start, m);
+    *out = found < 0 ? -1 : found;
+    if (found == -2) *status = TBA_INTERNAL;
 }
 
 // Row N4: the per-position log-likelihood ratio kernels of the model-comparison

@@ -2,13 +2,21 @@
 // rescale, final score (resquiggle.py:402-540, 1176-1214; tombo_stats.py:401-450, 2327-2338).
 #pragma once
 #include "k_select.h"
+#include "k_base_dp.h"
 
 // ---------------------------------------------------------------------------------------------
 // rq.resolve_skipped_bases_with_raw (resquiggle.py:402-540): deletion windows, then per window
 // c_reg_z_scores (pyx:34-97, reg_start=0, reg_end=n, max_base_shift=n) -> raw_forward_pass
 // (resquiggle.py:345-380, c_base_forward_pass pyx:99-163) -> raw_traceback (:382-400,
-// c_base_traceback pyx:165-182).  One thread per read; per-read scratch arenas:
-//   win[2*(B+1)] i64, fw/z[cap] f64, ld[cap]... (cap elements each, see engine)
+// c_base_traceback pyx:165-182).  Three kernels:
+//   k_skip_plan        a wavefront per read: the windows, their checks, what resolves each (skip_plan_windows, written
+//                      once, over LDS or over the read's slice of win_scratch: 3 * (B + 1) words)
+//   k_skip_dp_wave<>   RNA's large windows, queued per LDS class: a wavefront per window (raw_window_dp_wave)
+//   k_skip_dp<>        a wavefront per read, a lane per window: DNA out of LDS (raw_window_dp_lane_lds, column and flat
+//                      layout), whatever is left over the global scratch arena (raw_window_dp); the final checks
+// The pieces of the DP exist once each: base_z (the z-score), base_forward_row (the serial row) and base_traceback (the
+// walk) in k_base_dp.h, which the C entries of k_cabi.h share; flag_traceback (the walk's closed form over flag bits)
+// and SkipWindow (window i of a read's plan) here.
 struct Win { i64 s, e; };
 
 __device__ inline i64 merge_windows(Win *w, i64 n)
@@ -42,12 +50,21 @@ __device__ __forceinline__ i64 raw_window_need(i64 n, i64 len) { return n * len 
 __device__ inline void base_z_row(const double *x, i64 len, double mu, double sd, bool winsor,
                                   double mh, double *z)
 {
-    for (i64 k = 0; k < len; k++) { // c_base_z_scores, pyx:17-32
-        double v = (x[k] - mu) / sd;
-        if (v > 0) v = -v;
-        if (winsor && v < -mh) v = -mh;
-        z[k] = v;
+    for (i64 k = 0; k < len; k++) z[k] = base_z((x[k] - mu) / sd, winsor, mh);
+}
+
+// raw_traceback (resquiggle.py:382-400) over the n forward rows fw[b * len ..] of a window
+__device__ __forceinline__ int raw_window_walk(const double *fw, i64 n, i64 len, i64 m, i64 *new_segs)
+{
+    i64 sig_start = (n - 1) * m + len - 1;
+    for (i64 b = n - 1; b >= 1; b--) {
+        const i64 found = base_traceback<false>(fw + b * len, len, b * m, fw + (b - 1) * len, len, (b - 1) * m,
+                                                (b - 1) * m + len, sig_start, m);
+        if (found < 0) return TBA_INTERNAL;
+        new_segs[b - 1] = found;
+        sig_start = found - 1;
     }
+    return TBA_OK;
 }
 
 __device__ inline int raw_window_dp(const double *sig, i64 L, const double *means,
@@ -66,9 +83,7 @@ __device__ inline int raw_window_dp(const double *sig, i64 L, const double *mean
             const double mu = means[0], sd = sds[0];
             double acc = 0;
             for (i64 k = 0; k < len; k++) {
-                double zv = (sig[k] - mu) / sd;
-                if (zv > 0) zv = -zv;
-                if (winsor && zv < -mh) zv = -mh;
+                const double zv = base_z((sig[k] - mu) / sd, winsor, mh);
                 acc = k == 0 ? zv : acc + zv;
                 fwr[k] = acc;
             }
@@ -92,9 +107,7 @@ __device__ inline int raw_window_dp(const double *sig, i64 L, const double *mean
                 for (int u = 0; u < 8; u++) {
                     const i64 k = k0 + u;
                     if (k < len) {
-                        double zv = (xv[u] - mu) / sd;
-                        if (zv > 0) zv = -zv;
-                        if (winsor && zv < -mh) zv = -mh;
+                        const double zv = base_z((xv[u] - mu) / sd, winsor, mh);
                         const double best = (k == 0 || dg[u] > stay) ? dg[u] : stay;
                         stay = zv + best;
                         bf[k] = stay;
@@ -102,22 +115,7 @@ __device__ inline int raw_window_dp(const double *sig, i64 L, const double *mean
                 }
             }
         }
-        i64 sig_start = (n - 1) + len - 1; // raw_traceback / c_base_traceback, pyx:165-182
-        for (i64 b = n - 1; b >= 1; b--) {
-            const double *cf = fwr + b * len, *nf = fwr + (b - 1) * len;
-            const i64 cs = b, ns = b - 1, ne = ns + len;
-            i64 cnt = 1, found = -1;
-            for (i64 sp = sig_start; sp >= 0; sp--) {
-                cnt += 1;
-                if (cnt <= 1 || sp - 1 >= ne) continue;
-                if (sp <= cs) { found = sp; break; }
-                if (nf[sp - ns - 1] > cf[sp - cs - 1]) { found = sp; break; }
-            }
-            if (found < 0) return TBA_INTERNAL;
-            new_segs[b - 1] = found;
-            sig_start = found - 1;
-        }
-        return TBA_OK;
+        return raw_window_walk(fwr, n, len, 1, new_segs);
     }
     double *fw = scratch, *zp = fw + n * len, *zc = zp + len, *cum = zc + len;
     i64 *pl = (i64 *)(cum + len), *bl = pl + len;
@@ -126,66 +124,44 @@ __device__ inline int raw_window_dp(const double *sig, i64 L, const double *mean
         double acc = 0;
         for (i64 k = 0; k < len; k++) { acc = k == 0 ? zp[k] : acc + zp[k]; fw[k] = acc; pl[k] = m; }
     }
-    for (i64 i = 1; i < n; i++) { // c_base_forward_pass, pyx:99-163
+    for (i64 i = 1; i < n; i++) {
         base_z_row(sig + i * m, len, means[i], sds[i], winsor, mh, zc);
-        const double *pf = fw + (i - 1) * len;
-        double *bf = fw + i * len;
-        const i64 ps = (i - 1) * m, pe = ps + len, b_s = i * m, b_e = b_s + len;
-        { double acc = 0; for (i64 k = 0; k < len; k++) { acc = k == 0 ? zp[k] : acc + zp[k]; cum[k] = acc; } }
-        if (b_s - ps - 1 < 0 || b_s - ps - 1 >= len) return TBA_INTERNAL;
-        bf[0] = zc[0] + pf[b_s - ps - 1];
-        bl[0] = 1;
-        double stay_run = bf[0]; // bf / bl of the previous position, carried in registers
-        i64 bl_run = 1;
-        for (i64 pos = b_s + 1; pos < pe + 1; pos++) {
-            if (pos - b_s >= len) break;
-            i64 lag = 1;
-            for (;;) {
-                i64 idx = pos - ps - lag;
-                if (idx < 0) idx += len;
-                if (idx < 0 || idx >= len) return TBA_INTERNAL;
-                if (pl[idx] + lag <= m) lag++;
-                else break;
-            }
-            i64 di = pos - ps - lag;
-            if (di < 0) di += len;
-            double diag = pf[di];
-            if (lag > 1) diag += cum[pos - ps - 1] - cum[di];
-            const double stay = stay_run;
-            double best;
-            i64 dv;
-            if (diag > stay) { best = diag; dv = 1; }
-            else { best = stay; dv = bl_run + 1; }
-            stay_run = zc[pos - b_s] + best;
-            bl_run = dv;
-            bf[pos - b_s] = stay_run;
-            bl[pos - b_s] = dv;
-        }
-        if (b_e > pe + 1) {
-            double fv = bf[pe - b_s];
-            i64 cl = bl[pe - b_s];
-            for (i64 k = 0; k < b_e - pe - 1; k++) {
-                fv += zc[k + pe - b_s + 1];
-                cl += 1;
-                bf[k + pe - b_s + 1] = fv;
-                bl[k + pe - b_s + 1] = cl;
-            }
-        }
+        const int rc = base_forward_row(zc, i * m, i * m + len, zp, (i - 1) * m, (i - 1) * m + len, fw + (i - 1) * len,
+                                        pl, m, cum, fw + i * len, bl);
+        if (rc != TBA_OK) return rc;
         i64 *t = pl; pl = bl; bl = t;
         double *tz = zp; zp = zc; zc = tz;
     }
-    i64 sig_start = (n - 1) * m + len - 1; // raw_traceback / c_base_traceback, pyx:165-182
+    return raw_window_walk(fw, n, len, m, new_segs);
+}
+
+// raw_traceback / c_base_traceback (pyx:165-182) without the walk, for the forms that keep the traceback's test
+// "previous base's score > this base's score" as one bit per (base, position) while the rows are made: bit j of base
+// b's flags = fwd[b - 1][j + m] > fwd[b][j]; word(b, w0) loads flag word w0 of base b.  The reference walks sp down from
+// sig_start: the first m - 1 positions and those with sp - 1 >= next_end are passed over, then the first position
+// with sp <= curr_start or with the flag set is returned.  Same result without the walk: start at
+// min(sig_start - (m - 1), next_end); at or below curr_start -> that position; else the highest set flag at or
+// below it (word-wise), else curr_start.
+template <class Word>
+__device__ __forceinline__ int flag_traceback(i64 n, i64 len, i64 m, Word word, i64 *new_segs)
+{
+    i64 sig_start = (n - 1) * m + len - 1;
     for (i64 b = n - 1; b >= 1; b--) {
-        const double *cf = fw + b * len, *nf = fw + (b - 1) * len;
-        const i64 cs = b * m, ns = (b - 1) * m, ne = ns + len;
-        i64 cnt = 1, found = -1;
-        for (i64 sp = sig_start; sp >= 0; sp--) {
-            cnt += 1;
-            if (cnt <= m || sp - 1 >= ne) continue;
-            if (sp <= cs) { found = sp; break; }
-            if (nf[sp - ns - 1] > cf[sp - cs - 1]) { found = sp; break; }
+        const i64 cs = b * m, ne = (b - 1) * m + len;
+        i64 st = sig_start - (m - 1);
+        st = st < ne ? st : ne;
+        i64 found;
+        if (st < 0) return TBA_INTERNAL;
+        if (st <= cs) found = st;
+        else {
+            found = cs;
+            const i64 j = st - cs - 1;                // highest candidate flag (j <= len - 2)
+            for (i64 w0 = j >> 6; w0 >= 0; w0--) {
+                u64 v = word(b, w0);
+                if (w0 == (j >> 6) && (j & 63) != 63) v &= (1ull << ((j & 63) + 1)) - 1ull;
+                if (v) { found = cs + 1 + w0 * 64 + (63 - __clzll((long long)v)); break; }
+            }
         }
-        if (found < 0) return TBA_INTERNAL;
         new_segs[b - 1] = found;
         sig_start = found - 1;
     }
@@ -222,12 +198,6 @@ struct SkipLaneSmem {
 __device__ __forceinline__ int raw_window_dp_lane_lds(const double *sig, int len, const double *means,
     const double *sds, int n, bool winsor, double mh, double *rp, int rs, u64 *fp, int fs, int words, i64 *new_segs)
 {
-    auto zscore = [&](double x, double mu, double sd, double y) { // c_base_z_scores, pyx:17-32
-        double zv = div_by_recip(x - mu, sd, y);
-        if (zv > 0) zv = -zv;
-        if (winsor && zv < -mh) zv = -mh;
-        return zv;
-    };
     // Eight positions at a time, the samples of the NEXT eight already on their way: a lane's window lies anywhere
     // in the read, so a sample load is a 64-line memory instruction with a round trip of a few thousand cycles at
     // this kernel's occupancy (four wavefronts per CU) -- a step-by-step loop paid it per position (820 cycles per
@@ -250,7 +220,7 @@ __device__ __forceinline__ int raw_window_dp_lane_lds(const double *sig, int len
             for (int u = 0; u < 8; u++) xv[u] = xn[u];
             if (k0 + 8 < len) fetch8(sig, k0 + 8, xn); else if (n > 1) fetch8(sig + 1, 0, xn);
 #pragma unroll
-            for (int u = 0; u < 8; u++) xv[u] = zscore(xv[u], mu, sd, y);
+            for (int u = 0; u < 8; u++) xv[u] = base_z(div_by_recip(xv[u] - mu, sd, y), winsor, mh);
 #pragma unroll
             for (int u = 0; u < 8; u++) {
                 acc = k0 + u == 0 ? xv[u] : acc + xv[u];
@@ -270,7 +240,7 @@ __device__ __forceinline__ int raw_window_dp_lane_lds(const double *sig, int len
             for (int u = 0; u < 8; u++) { xv[u] = xn[u]; dg[u] = rp[(k0 + u) * rs]; }
             if (k0 + 8 < len) fetch8(x, k0 + 8, xn); else if (i + 1 < n) fetch8(x + 1, 0, xn);
 #pragma unroll
-            for (int u = 0; u < 8; u++) xv[u] = zscore(xv[u], mu, sd, y);
+            for (int u = 0; u < 8; u++) xv[u] = base_z(div_by_recip(xv[u] - mu, sd, y), winsor, mh);
 #pragma unroll
             for (int u = 0; u < 8; u++) {
                 const int k = k0 + u;
@@ -284,43 +254,21 @@ __device__ __forceinline__ int raw_window_dp_lane_lds(const double *sig, int len
         }
         if (len >= 2 && ((len - 2) >> 6) > w_done) fp[(i * words + ((len - 2) >> 6)) * fs] = bits;
     }
-    // raw_traceback / c_base_traceback (pyx:165-182) in the closed form of raw_window_dp_wave
-    i64 sig_start = (n - 1) + len - 1;
-    for (int b = n - 1; b >= 1; b--) {
-        const i64 cs = b, ne = (b - 1) + len;
-        const i64 st = sig_start < ne ? sig_start : ne;
-        i64 found;
-        if (st < 0) return TBA_INTERNAL;
-        if (st <= cs) found = st;
-        else {
-            found = cs;
-            const i64 j = st - cs - 1;                // highest candidate flag (j <= len - 2)
-            for (i64 w0 = j >> 6; w0 >= 0; w0--) {
-                u64 v = fp[(b * words + w0) * fs];
-                if (w0 == (j >> 6) && (j & 63) != 63) v &= (1ull << ((j & 63) + 1)) - 1ull;
-                if (v) { found = cs + 1 + w0 * 64 + (63 - __clzll((long long)v)); break; }
-            }
-        }
-        new_segs[b - 1] = found;
-        sig_start = found - 1;
-    }
-    return TBA_OK;
+    return flag_traceback(n, len, 1, [&](i64 b, i64 w0) { return fp[(b * words + w0) * fs]; }, new_segs);
 }
 
-// get_deletion_windows (resquiggle.py:462-498) + per-window scratch sizing; one thread per read.
-// win[3*k..] = (start, end, scratch offset inside the read's slice); r.n_win, r.skip_off (need,
-// turned into an arena offset by k_scan_skip).
-// Windows of at least SKIP_WAVE_MIN positions (bases x admissible interval) whose interval is at
-// most SKIP_WAVE_LEN samples are resolved by a whole wavefront out of LDS (k_skip_dp_wave): the
-// kernel time of the lane-per-window form is the serial walk of its LARGEST window (RNA: mean 3.5 k
-// positions per read, but 28 k in the largest window of a 10 k-read batch).  win[3k+2] = -1 marks
-// them; the rest keep their offset inside the read's slice of the global scratch arena.
-// Three LDS classes (interval length, flag words); windows of a class are queued in a global list
-// (skipq: [c] = entries of the list of class c, [4 + c] = next entry to hand out) that a fixed
-// grid of wavefronts drains, so no workgroup is launched per read.
-// smallest window (positions) handed to the wave form.  Only used for raw_min_obs_per_base > 1
-// (RNA): the lane form's DNA fast path (recurrence in a register, windows of a few hundred
-// positions, ~55 per read) is faster than queueing (3.4 vs 3.9 ms per 10 k reads)
+// ---- the plan of a read: get_deletion_windows (resquiggle.py:462-498), the checks behind it, and for every window
+// what resolves it.  One wavefront per read (k_skip_plan).  win[3k..] = (start, end, code) of window k of the read;
+// r.n_win; r.skip_off = the read's need of scratch arena (turned into its arena offset by k_scan_arena).  The code:
+//   SKW_COLUMN / SKW_FLAT  raw_min_obs_per_base == 1 (DNA): k_skip_dp<true> out of LDS (SkipLaneSmem above);
+//   SKW_QUEUED  raw_min_obs_per_base > 1 (RNA), at least SKIP_WAVE_MIN positions (bases x admissible interval): a whole
+//     wavefront out of LDS (k_skip_dp_wave) -- the kernel time of the lane-per-window form is the serial walk of its
+//     LARGEST window (RNA: mean 3.5 k positions per read, but 28 k in the largest window of a 10 k-read batch).
+//     Three LDS classes (interval length, flag words); the windows of a class are queued in a global list (skipq:
+//     [c] = entries of the list of class c, [4 + c] = next entry to hand out) that a fixed grid of wavefronts drains,
+//     so no workgroup is launched per read.  DNA never queues: the lane form's fast path (recurrence in a register,
+//     windows of a few hundred positions, ~55 per read) is faster than queueing (3.4 vs 3.9 ms per 10 k reads);
+//   >= 0  everything else: raw_window_dp by a lane of k_skip_dp, at this offset inside the read's slice of the arena.
 #define SKIP_WAVE_MIN 256
 #define SKIP_LEN_S 320
 #define SKIP_BITS_S 128
@@ -328,6 +276,129 @@ __device__ __forceinline__ int raw_window_dp_lane_lds(const double *sig, int len
 #define SKIP_BITS_M 384
 #define SKIP_LEN_B 1792
 #define SKIP_BITS_B 1024 // u64 words of traceback flags (n * ceil(len / 64))
+enum : i64 { SKW_QUEUED = -1, SKW_COLUMN = -2, SKW_FLAT = -3, SKW_WAVE = -4 };
+
+// the code of a window of n bases over an admissible interval of len samples, before queueing: SKW_WAVE - c asks for
+// the queue of class c (a full list leaves the window to the arena); >= 0: raw_window_need
+__device__ __forceinline__ i64 skip_window_code(i64 n, i64 len, i64 m)
+{
+    const i64 fw = n * ((len + 63) / 64);
+    if (m == 1 && len <= SKL_LEN && n <= SKL_N) return SKW_COLUMN;
+    if (m == 1 && len <= SKL_FLAT_LEN && fw <= SKL_FLAT_WORDS) return SKW_FLAT;
+    // (L = len + (n - 1) m must fit the staged signal, n the staged levels)
+    if (m > 1 && n * len >= SKIP_WAVE_MIN && (n - 1) * m <= 512 && n <= 256) {
+        if (len <= SKIP_LEN_S && fw <= SKIP_BITS_S) return SKW_WAVE;
+        if (len <= SKIP_LEN_M && fw <= SKIP_BITS_M) return SKW_WAVE - 1;
+        if (len <= SKIP_LEN_B && fw <= SKIP_BITS_B) return SKW_WAVE - 2;
+    }
+    return raw_window_need(n, len);
+}
+
+// The plan, by all lanes of the read's wavefront, over storage the caller picks (inlined at both call sites, each
+// keeps its address space): w[] room for one window per skipped base; aux[] the n_del skipped bases in order on entry,
+// later each window's code.  Lane 0 alone builds and merges (serial by nature); the per-window checks run on all
+// lanes, and the first failing window in window order decides the status, checks in the reference's order, as in
+// its serial loops.  A read that fails queues nothing and leaves r.n_win = 0.
+// w3 is the read's slice of win_scratch, 3 * (B + 1) words, and may BE the storage: w in front (two words per
+// window), aux behind 2 * (B + 1).  Hence the triples go out last, back to front, a batch of 64 through registers:
+// triple i lies on pairs >= i only, and below aux altogether (the windows are disjoint and of two bases at least
+// by then, so there are fewer than (B + 1) / 2 of them).
+__device__ __forceinline__ void skip_plan_windows(Win *w, i64 *aux, i64 n_del, ReadState &r, const DevParams *dp,
+    const i64 *ds, i64 *w3, i64 *skipq, i32 *lists, i64 list_cap)
+{
+    __shared__ i64 s_nw;
+    const int lane = threadIdx.x;
+    const i64 m = dp->p.raw_min_obs_per_base, n_segs = r.B + 1;
+    // del_fix_window / max_del_fix_window / extra_sig_factor of resolve_skipped_bases_with_raw
+    // (resquiggle.py:405-407; defaults _default_parameters.py:67,72,73)
+    const i64 dfw = dp->o.del_fix_window, mdfw = dp->o.max_del_fix_window;
+    const double esf = dp->o.extra_sig_factor;
+    if (lane == 0) {
+        i64 nw = 0;
+        for (i64 q = 0; q < n_del; q++) {
+            const i64 d = aux[q];
+            if (nw > 0 && d < w[nw - 1].e + dfw) w[nw - 1].e = d + dfw + 1;
+            else { w[nw].s = d - dfw; w[nw].e = d + dfw + 1; nw++; }
+        }
+        if (nw > 0) { nw = merge_windows(w, nw); trim_windows(w, nw, n_segs); }
+        s_nw = nw;
+    }
+    __syncthreads();
+    if (s_nw == 0) return;
+    // first failing window of a parallel check (code 0: fine), in window order
+    auto first_code = [&](auto code_of) -> int {
+        int res = 0;
+        for (i64 i0 = 0; i0 < s_nw && res == 0; i0 += 64) {
+            const i64 i = i0 + lane;
+            const int c = i < s_nw ? code_of(i) : 0;
+            const u64 mk = __ballot(c != 0);
+            if (mk) res = __shfl(c, __ffsll((unsigned long long)mk) - 1, 64);
+        }
+        return res;
+    };
+    auto fail = [&](int err) { if (err && lane == 0) r.status = err; return err != 0; };
+    bool expanded = false;
+    for (i64 it = 0; it < mdfw - dfw; it++) {
+        bool any = false;
+        if (fail(first_code([&](i64 i) {
+                const int ts = window_too_small(ds, n_segs, w[i], m, esf);
+                if (ts > 0) any = true;
+                return ts < 0 ? (int)TBA_INTERNAL : 0;
+            }))) return;
+        expanded = __ballot(any) != 0;
+        if (!expanded) break;
+        __syncthreads();
+        for (i64 i = lane; i < s_nw; i += 64)       // (every lane re-derives its windows' verdicts: cheap, from cache)
+            if (window_too_small(ds, n_segs, w[i], m, esf) > 0) { w[i].s -= 1; w[i].e += 1; }
+        __syncthreads();
+        if (lane == 0) { const i64 nw = merge_windows(w, s_nw); trim_windows(w, nw, n_segs); s_nw = nw; }
+        __syncthreads();
+    }
+    if (expanded && fail(first_code([&](i64 i) {
+            const int ts = window_too_small(ds, n_segs, w[i], m, esf);
+            return ts < 0 ? (int)TBA_INTERNAL : (ts ? (int)TBA_NOT_ENOUGH_DEL_SIGNAL : 0);
+        }))) return;
+    if (dp->o.max_raw_cpts >= 0 &&
+        fail(first_code([&](i64 i) { return w[i].e - w[i].s > dp->o.max_raw_cpts ? (int)TBA_TOO_MANY_DELS : 0; }))) return;
+    if (fail(first_code([&](i64 i) {
+            const i64 s = w[i].s, e = w[i].e, n = e - s;
+            if (s < 0 || e >= n_segs) return (int)TBA_INTERNAL;
+            const i64 len = ds[e] - ds[s] - (n - 1) * m;
+            if (len <= 0 || n < 2) return (int)TBA_INTERNAL;
+            aux[i] = skip_window_code(n, len, m);
+            return 0;
+        }))) return;
+    const i64 nw = s_nw;
+    if (m > 1)                                     // queue for k_skip_dp_wave (each lane the windows it has just coded)
+        for (i64 i = lane; i < nw; i += 64) {
+            if (aux[i] > SKW_WAVE) continue;
+            const i64 cls = SKW_WAVE - aux[i], n = w[i].e - w[i].s;
+            const i64 pos = (i64)atomicAdd((unsigned long long *)&skipq[cls], 1ull);
+            if (pos < list_cap) {
+                i32 *lst = lists + 2 * list_cap * cls;
+                lst[2 * pos] = (i32)blockIdx.x; lst[2 * pos + 1] = (i32)i;
+                aux[i] = SKW_QUEUED;
+            } else aux[i] = raw_window_need(n, ds[w[i].e] - ds[w[i].s] - (n - 1) * m);
+        }
+    __syncthreads();
+    if (lane == 0) { // arena offsets in window order
+        i64 acc = 0;
+        for (i64 i = 0; i < nw; i++) {
+            const i64 c = aux[i];
+            if (c >= 0) { aux[i] = acc; acc += c; }
+        }
+        r.n_win = nw;
+        r.skip_off = acc;
+    }
+    __syncthreads();
+    for (i64 i0 = (nw - 1) / 64 * 64; i0 >= 0; i0 -= 64) {
+        const i64 i = i0 + lane < nw ? i0 + lane : nw - 1;
+        const Win wi = w[i];
+        const i64 code = aux[i];
+        __syncthreads();                            // (the batch is in registers before a triple lands on its pairs)
+        if (i0 + lane < nw) { w3[3 * i] = wi.s; w3[3 * i + 1] = wi.e; w3[3 * i + 2] = code; }
+    }
+}
 
 #define SKP_LDS_DELS 256   // (6 KB of LDS: the scan of the boundaries wants many wavefronts per CU)
 __global__ __launch_bounds__(64) void k_skip_plan(ReadState *rs, i64 n_reads, const DevParams *dp,
@@ -338,13 +409,12 @@ __global__ __launch_bounds__(64) void k_skip_plan(ReadState *rs, i64 n_reads, co
     const int lane = threadIdx.x;
     if (lane == 0) { r.n_win = 0; r.skip_off = 0; }
     if (r.status != TBA_OK) return;
-    const i64 m = dp->p.raw_min_obs_per_base;
     const i64 n_segs = r.B + 1;
     const i64 *ds = dp_segs + r.seg_off;
     // the resolved boundaries start as a copy; the window kernels overwrite their interiors.  The same pass finds the
     // skipped bases (diff(segs) == 0), kept in order behind the window area.  Eight strides of loads in flight: one
     // wavefront per read, and a load -> use loop of 157 steps pays 157 memory round trips (half of this kernel).
-    i64 *dels = win_scratch + 3 * r.seg_off + 2 * n_segs;
+    i64 *w3 = win_scratch + 3 * r.seg_off, *dels = w3 + 2 * n_segs;
     i64 n_del = 0;
     for (i64 base = 0; base < n_segs; base += 64 * 8) {
         i64 a8[8], b8[8];
@@ -365,202 +435,31 @@ __global__ __launch_bounds__(64) void k_skip_plan(ReadState *rs, i64 n_reads, co
         }
     }
     __syncthreads();
-    // ---- the usual case (at most SKP_LDS_DELS skipped bases): windows in LDS, per-window work on all lanes.
-    // Lane 0 alone over global memory (the form below, kept for reads with more deletions) paid a memory round
-    // trip for every window it touched -- ~350 of them, 0.5 of the kernel's 0.84 ms.  Same windows, same statuses:
-    // the first failing window in window order decides, as in the serial loops.
+    // The usual read (at most SKP_LDS_DELS skipped bases) is planned out of LDS: over global memory every window a
+    // lane touches is a memory round trip -- ~350 of them per read when one lane did it all, 0.5 of the kernel's
+    // 0.84 ms.  A read with more is planned in place, in its slice of win_scratch.
     if (n_del <= SKP_LDS_DELS) {
-        __shared__ i64 s_aux[SKP_LDS_DELS];              // the deletions, later each window's scratch need / class
+        __shared__ i64 s_aux[SKP_LDS_DELS];
         __shared__ Win s_w[SKP_LDS_DELS];
-        __shared__ i64 s_nw;
-        __shared__ int s_st;
-        const i64 dfw = dp->o.del_fix_window, mdfw = dp->o.max_del_fix_window;
-        const double esf = dp->o.extra_sig_factor;
         for (i64 q = lane; q < n_del; q += 64) s_aux[q] = dels[q];
-        if (lane == 0) s_st = TBA_OK;
         __syncthreads();
-        if (lane == 0) {
-            i64 nw = 0;
-            for (i64 q = 0; q < n_del; q++) {
-                const i64 d = s_aux[q];
-                if (nw > 0 && d < s_w[nw - 1].e + dfw) s_w[nw - 1].e = d + dfw + 1;
-                else { s_w[nw].s = d - dfw; s_w[nw].e = d + dfw + 1; nw++; }
-            }
-            if (nw > 0) { nw = merge_windows(s_w, nw); trim_windows(s_w, nw, n_segs); }
-            s_nw = nw;
-        }
-        __syncthreads();
-        if (s_nw == 0) return;
-        // first failing window of a parallel check (code 0: fine), in window order
-        auto first_code = [&](auto code_of) -> int {
-            int res = 0;
-            for (i64 i0 = 0; i0 < s_nw && res == 0; i0 += 64) {
-                const i64 i = i0 + lane;
-                const int c = i < s_nw ? code_of(i) : 0;
-                const u64 mk = __ballot(c != 0);
-                if (mk) res = __shfl(c, __ffsll((unsigned long long)mk) - 1, 64);
-            }
-            return res;
-        };
-        bool expanded = false;
-        for (i64 it = 0; it < mdfw - dfw; it++) {
-            bool any = false;
-            const int err = first_code([&](i64 i) {
-                const int ts = window_too_small(ds, n_segs, s_w[i], m, esf);
-                if (ts > 0) any = true;
-                return ts < 0 ? (int)TBA_INTERNAL : 0;
-            });
-            if (err) { if (lane == 0) r.status = err; return; }
-            expanded = __ballot(any) != 0;
-            if (!expanded) break;
-            __syncthreads();
-            for (i64 i = lane; i < s_nw; i += 64)       // (every lane re-derives its windows' verdicts: cheap, from cache)
-                if (window_too_small(ds, n_segs, s_w[i], m, esf) > 0) { s_w[i].s -= 1; s_w[i].e += 1; }
-            __syncthreads();
-            if (lane == 0) { const i64 nw = merge_windows(s_w, s_nw); trim_windows(s_w, nw, n_segs); s_nw = nw; }
-            __syncthreads();
-        }
-        if (expanded) {
-            const int err = first_code([&](i64 i) {
-                const int ts = window_too_small(ds, n_segs, s_w[i], m, esf);
-                return ts < 0 ? (int)TBA_INTERNAL : (ts ? (int)TBA_NOT_ENOUGH_DEL_SIGNAL : 0);
-            });
-            if (err) { if (lane == 0) r.status = err; return; }
-        }
-        if (dp->o.max_raw_cpts >= 0) {
-            const int err = first_code([&](i64 i) { return s_w[i].e - s_w[i].s > dp->o.max_raw_cpts ? (int)TBA_TOO_MANY_DELS : 0; });
-            if (err) { if (lane == 0) r.status = err; return; }
-        }
-        // per window: class / scratch need (s_aux[i]: -1 wave form, -2 LDS column, -3 LDS flat, >= 0 arena doubles)
-        i64 *w3 = win_scratch + 3 * r.seg_off;
-        {
-            const int err = first_code([&](i64 i) {
-                const i64 s = s_w[i].s, e = s_w[i].e, n = e - s;
-                if (s < 0 || e >= n_segs) return (int)TBA_INTERNAL;
-                const i64 L = ds[e] - ds[s];
-                const i64 len = L - (n - 1) * m;
-                if (len <= 0 || n < 2) return (int)TBA_INTERNAL;
-                w3[3 * i] = s; w3[3 * i + 1] = e;
-                const i64 fw = n * ((len + 63) / 64);
-                i64 code;
-                if (m == 1 && len <= SKL_LEN && n <= SKL_N) code = -2;
-                else if (m == 1 && len <= SKL_FLAT_LEN && fw <= SKL_FLAT_WORDS) code = -3;
-                else {
-                    code = raw_window_need(n, len);
-                    if (m > 1 && n * len >= SKIP_WAVE_MIN) {
-                        const bool fits = (n - 1) * m <= 512 && n <= 256;
-                        int cls = -1;
-                        if (fits && len <= SKIP_LEN_S && fw <= SKIP_BITS_S) cls = 0;
-                        else if (fits && len <= SKIP_LEN_M && fw <= SKIP_BITS_M) cls = 1;
-                        else if (fits && len <= SKIP_LEN_B && fw <= SKIP_BITS_B) cls = 2;
-                        if (cls >= 0) { // queue for k_skip_dp_wave (a full list leaves the window to the lane form)
-                            const i64 pos = (i64)atomicAdd((unsigned long long *)&skipq[cls], 1ull);
-                            if (pos < list_cap) {
-                                i32 *lst = lists + 2 * list_cap * cls;
-                                lst[2 * pos] = (i32)blockIdx.x; lst[2 * pos + 1] = (i32)i;
-                                code = -1;
-                            }
-                        }
-                    }
-                }
-                s_aux[i] = code;
-                return 0;
-            });
-            if (err) { if (lane == 0) r.status = err; return; }
-        }
-        __syncthreads();
-        if (lane == 0) { // arena offsets in window order
-            i64 acc = 0;
-            for (i64 i = 0; i < s_nw; i++) {
-                const i64 c = s_aux[i];
-                if (c >= 0) { s_aux[i] = acc; acc += c; }
-            }
-            r.n_win = s_nw;
-            r.skip_off = acc;
-        }
-        __syncthreads();
-        for (i64 i = lane; i < s_nw; i += 64) w3[3 * i + 2] = s_aux[i];
-        return;
-    }
-    if (lane != 0) return;
-    // windows are built in place as (s, e) pairs, then widened to (s, e, off) triples back to
-    // front; capacity 3 * (B + 1) entries per read
-    Win *w = (Win *)(win_scratch + 3 * r.seg_off);
-    // del_fix_window / max_del_fix_window / extra_sig_factor of resolve_skipped_bases_with_raw
-    // (resquiggle.py:405-407; defaults _default_parameters.py:67,72,73)
-    const i64 dfw = dp->o.del_fix_window, mdfw = dp->o.max_del_fix_window;
-    const double esf = dp->o.extra_sig_factor;
-    i64 nw = 0;
-    for (i64 q = 0; q < n_del; q++) {
-        const i64 d = dels[q];
-        if (nw > 0 && d < w[nw - 1].e + dfw) w[nw - 1].e = d + dfw + 1;
-        else { w[nw].s = d - dfw; w[nw].e = d + dfw + 1; nw++; }
-    }
-    if (nw == 0) return;
-    bool expanded = false;
-    nw = merge_windows(w, nw);
-    trim_windows(w, nw, n_segs);
-    for (i64 it = 0; it < mdfw - dfw; it++) {
-        expanded = false;
-        for (i64 i = 0; i < nw; i++) {
-            int ts = window_too_small(ds, n_segs, w[i], m, esf);
-            if (ts < 0) { r.status = TBA_INTERNAL; return; }
-            if (ts) { expanded = true; w[i].s -= 1; w[i].e += 1; }
-        }
-        if (!expanded) break;
-        nw = merge_windows(w, nw);
-        trim_windows(w, nw, n_segs);
-    }
-    if (expanded) {
-        for (i64 i = 0; i < nw; i++) {
-            int ts = window_too_small(ds, n_segs, w[i], m, esf);
-            if (ts < 0) { r.status = TBA_INTERNAL; return; }
-            if (ts) { r.status = TBA_NOT_ENOUGH_DEL_SIGNAL; return; }
-        }
-    }
-    if (dp->o.max_raw_cpts >= 0) {
-        i64 mx = 0;
-        for (i64 i = 0; i < nw; i++) mx = w[i].e - w[i].s > mx ? w[i].e - w[i].s : mx;
-        if (mx > dp->o.max_raw_cpts) { r.status = TBA_TOO_MANY_DELS; return; }
-    }
-    i64 *w3 = win_scratch + 3 * r.seg_off;
-    for (i64 i = nw - 1; i >= 0; i--) { // widen pairs to triples, back to front
-        const i64 s = w[i].s, e = w[i].e;
-        w3[3 * i] = s; w3[3 * i + 1] = e; w3[3 * i + 2] = 0;
-    }
-    i64 acc = 0;
-    for (i64 i = 0; i < nw; i++) {
-        const i64 s = w3[3 * i], e = w3[3 * i + 1], n = e - s;
-        if (s < 0 || e >= n_segs) { r.status = TBA_INTERNAL; return; }
-        const i64 L = ds[e] - ds[s];
-        const i64 len = L - (n - 1) * m;
-        if (len <= 0 || n < 2) { r.status = TBA_INTERNAL; return; }
-        const i64 fw = n * ((len + 63) / 64);
-        int cls = -1;
-        if (m == 1 && len <= SKL_LEN && n <= SKL_N) { w3[3 * i + 2] = -2; continue; } // k_skip_dp out of LDS: column
-        if (m == 1 && len <= SKL_FLAT_LEN && n * ((len + 63) / 64) <= SKL_FLAT_WORDS) { w3[3 * i + 2] = -3; continue; } // flat
-        if (m > 1 && n * len >= SKIP_WAVE_MIN) {
-            // (L = len + (n - 1) m must fit the staged signal, n the staged levels)
-            const bool fits = (n - 1) * m <= 512 && n <= 256;
-            if (fits && len <= SKIP_LEN_S && fw <= SKIP_BITS_S) cls = 0;
-            else if (fits && len <= SKIP_LEN_M && fw <= SKIP_BITS_M) cls = 1;
-            else if (fits && len <= SKIP_LEN_B && fw <= SKIP_BITS_B) cls = 2;
-        }
-        if (cls >= 0) { // queue for k_skip_dp_wave (a full list leaves the window to the lane form)
-            const i64 pos = (i64)atomicAdd((unsigned long long *)&skipq[cls], 1ull);
-            if (pos < list_cap) {
-                i32 *lst = lists + 2 * list_cap * cls;
-                lst[2 * pos] = (i32)blockIdx.x; lst[2 * pos + 1] = (i32)i;
-                w3[3 * i + 2] = -1;
-                continue;
-            }
-        }
-        w3[3 * i + 2] = acc;
-        acc += raw_window_need(n, len);
-    }
-    r.n_win = nw;
-    r.skip_off = acc;
+        skip_plan_windows(s_w, s_aux, n_del, r, dp, ds, w3, skipq, lists, list_cap);
+    } else skip_plan_windows((Win *)w3, dels, n_del, r, dp, ds, w3, skipq, lists, list_cap);
 }
+
+// window i of a read's plan as the DP forms take it: the bases [s, s + n) over the samples [sig_start, sig_start + L)
+// of the read's signal.  The DP gives the n - 1 inner boundaries relative to the window's first sample.
+struct SkipWindow {
+    i64 s, n, sig_start, L, code;
+    __device__ __forceinline__ SkipWindow(const i64 *w3, const i64 *ds, i64 i)
+        : s(w3[3 * i]), n(w3[3 * i + 1] - s), sig_start(ds[s]), L(ds[s + n] - sig_start), code(w3[3 * i + 2]) {}
+    __device__ __forceinline__ bool inside(i64 n_norm) const { return sig_start >= 0 && sig_start + L <= n_norm; }
+    // out[]: the read's boundaries, the DP's results at out[s + 1 ..]; lanes first, first + step, ... of them
+    __device__ __forceinline__ void to_read_positions(i64 *out, i64 first = 0, i64 step = 1) const
+    {
+        for (i64 k = first; k < n - 1; k += step) out[s + 1 + k] += sig_start;
+    }
+};
 
 // raw-signal DP of one (large) window by one WAVEFRONT out of LDS.  Same arithmetic, in the same
 // order, as raw_window_dp (c_reg_z_scores -> raw_forward_pass / c_base_forward_pass ->
@@ -610,12 +509,7 @@ __device__ inline int raw_window_dp_wave(const double *sig, i64 L, const double 
     auto zrow = [&](i64 base, double *z) { // c_base_z_scores, pyx:17-32
         const double *x = (SIG_LDS ? S.sg : sig) + base * m;
         const double mu = S.mu[base], sd = S.sd[base];
-        for (i64 k = lane; k < len; k += 64) {
-            double v = (x[k] - mu) / sd;
-            if (v > 0) v = -v;
-            if (winsor && v < -mh) v = -mh;
-            z[k] = v;
-        }
+        for (i64 k = lane; k < len; k += 64) z[k] = base_z((x[k] - mu) / sd, winsor, mh);
     };
     zrow(0, cum);
     __syncthreads();
@@ -715,34 +609,7 @@ __device__ inline int raw_window_dp_wave(const double *sig, i64 L, const double 
         laps.lap(7);
     }
     int rc = TBA_OK;
-    if (lane == 0) { // raw_traceback / c_base_traceback, pyx:165-182
-        // The reference walks sp down from sig_start: the first m - 1 positions and those with
-        // sp - 1 >= next_end are passed over, then the first position with sp <= curr_start or
-        // with the flag set is returned.  Same result without the walk: start at
-        // min(sig_start - (m - 1), next_end); at or below curr_start -> that position; else the
-        // highest set flag at or below it (word-wise), else curr_start.
-        i64 sig_start = (n - 1) * m + len - 1;
-        for (i64 b = n - 1; b >= 1; b--) {
-            const i64 cs = b * m, ne = (b - 1) * m + len;
-            i64 st = sig_start - (m - 1);
-            st = st < ne ? st : ne;
-            i64 found;
-            if (st < 0) { rc = TBA_INTERNAL; break; }
-            if (st <= cs) found = st;
-            else {
-                found = cs;
-                const u64 *bw = S.bits + b * words;
-                i64 j = st - cs - 1; // highest candidate flag
-                for (i64 w0 = j >> 6; w0 >= 0; w0--) {
-                    u64 v = bw[w0];
-                    if (w0 == (j >> 6) && (j & 63) != 63) v &= (1ull << ((j & 63) + 1)) - 1ull;
-                    if (v) { found = cs + 1 + w0 * 64 + (63 - __clzll((long long)v)); break; }
-                }
-            }
-            new_segs[b - 1] = found;
-            sig_start = found - 1;
-        }
-    }
+    if (lane == 0) rc = flag_traceback(n, len, m, [&](i64 b, i64 w0) { return S.bits[b * words + w0]; }, new_segs);
     return __syncthreads_or(rc != TBA_OK) ? TBA_INTERNAL : TBA_OK;
 }
 
@@ -767,29 +634,24 @@ __global__ __launch_bounds__(64) void k_skip_dp_wave(ReadState *rs, const DevPar
         const i64 id = s_id;
         if (id >= total) break;
         ReadState &r = rs[list[2 * id]];
-        const i64 i = list[2 * id + 1];
         const i64 *ds = dp_segs + r.seg_off;
         i64 *out = segs + r.seg_off;
         const double *sig = norm + r.raw_off + r.read_start;
-        const i64 *w3 = win_scratch + 3 * r.seg_off;
-        const i64 s = w3[3 * i], e = w3[3 * i + 1], n = e - s;
-        const i64 sig_start = ds[s], sig_end = ds[e];
-        int rc = TBA_OK;
+        const SkipWindow v(win_scratch + 3 * r.seg_off, ds, list[2 * id + 1]);
+        int rc = TBA_INTERNAL;
         LapClock<6, TBA_SKIP_CLASS_STATS_ON> cls_laps; // per read: windows and cycles of every class (tba_phase.h)
         LapClock<8, TBA_SKIP_STATS_ON> laps;           // per read: windows, cycles, cells, parts of a base
-        if (sig_start < 0 || sig_end > r.norm_len) rc = TBA_INTERNAL;
-        else {
-            rc = raw_window_dp_wave<LEN, BITS, SIG_LDS>(sig + sig_start, sig_end - sig_start,
-                                               ref_means + r.ref_off + s, ref_sds + r.ref_off + s, n, m,
-                                               P.do_winsorize_z != 0, P.max_half_z_score, S, out + s + 1, laps);
+        if (v.inside(r.norm_len)) {
+            rc = raw_window_dp_wave<LEN, BITS, SIG_LDS>(sig + v.sig_start, v.L, ref_means + r.ref_off + v.s,
+                                                        ref_sds + r.ref_off + v.s, v.n, m, P.do_winsorize_z != 0,
+                                                        P.max_half_z_score, S, out + v.s + 1, laps);
             wave_mem_fence(); // (lane 0 wrote the boundaries, every lane reads them back)
-            if (rc == TBA_OK)
-                for (i64 k = threadIdx.x; k < n - 1; k += 64) out[s + 1 + k] += sig_start;
+            if (rc == TBA_OK) v.to_read_positions(out, threadIdx.x, 64);
         }
         // (every failure of the window DP is the same "unexpected error" status)
         if (rc != TBA_OK && threadIdx.x == 0) r.status = rc;
         cls_laps.count(CLS); cls_laps.count(3 + CLS, cls_laps.since_start());
-        laps.count(0); laps.count(1, laps.since_start()); laps.count(2, n * (sig_end - sig_start - (n - 1) * m));
+        laps.count(0); laps.count(1, laps.since_start()); laps.count(2, v.n * (v.L - (v.n - 1) * m));
         if (threadIdx.x == 0) { // (workgroups share a read: the sums by atomicAdd; tools/stage_times.py, TBA_DBG_PHASES=1)
             cls_laps.flush_atomic(r.dbg, CLS, CLS + 1); cls_laps.flush_atomic(r.dbg, 3 + CLS, 4 + CLS);
             laps.flush_atomic(r.dbg, 0, 3); laps.flush_add(r.dbg, 3, 8);
@@ -799,7 +661,10 @@ __global__ __launch_bounds__(64) void k_skip_dp_wave(ReadState *rs, const DevPar
 
 // rq.resolve_skipped_bases_with_raw window loop + final checks (resquiggle.py:500-538).
 // One wavefront per read, one window per lane at a time (windows own disjoint boundary ranges).
-template <bool DNA_LDS> // raw_min_obs_per_base == 1: the windows k_skip_plan marked -2 run out of LDS
+// (Registers: k_skip_dp<false> stands at 121 VGPRs, allocated 128 -- the last granule of four wavefronts per SIMD and
+// the budget of tests/test_kernel_resources.py.  raw_window_dp and base_forward_row are inlined here: a few more live
+// values in either cross the step.)
+template <bool DNA_LDS> // raw_min_obs_per_base == 1: the windows k_skip_plan coded SKW_COLUMN / SKW_FLAT run out of LDS
 __global__ __launch_bounds__(64) void k_skip_dp(ReadState *rs, const DevParams *dp,
     const double *norm, const double *ref_means, const double *ref_sds, const i64 *dp_segs,
     i64 *segs, const i64 *win_scratch, double *arena)
@@ -826,20 +691,19 @@ __global__ __launch_bounds__(64) void k_skip_dp(ReadState *rs, const DevParams *
         const bool winsor = P.do_winsorize_z != 0;
         // phase 1: the small windows, every lane in its column
         for (i64 i = lane; i < r.n_win && rc == TBA_OK; i += 64) {
-            if (w3[3 * i + 2] != -2) continue;
-            const i64 s = w3[3 * i], e = w3[3 * i + 1], n = e - s;
-            const i64 sig_start = ds[s], sig_end = ds[e];
-            if (sig_start < 0 || sig_end > n_norm) { rc = TBA_INTERNAL; break; }
-            const int rr = raw_window_dp_lane_lds(sig + sig_start, (int)(sig_end - sig_start - (n - 1)), mu + s, sd + s, (int)n,
-                                                  winsor, P.max_half_z_score, &S_.row[0][lane], 64, &S_.flag[0][lane], 64, 1, out + s + 1);
-            if (rr != TBA_OK) { rc = rr; break; }
-            for (i64 k = 0; k < n - 1; k++) out[s + 1 + k] += sig_start;
+            if (w3[3 * i + 2] != SKW_COLUMN) continue;
+            const SkipWindow v(w3, ds, i);
+            if (v.inside(n_norm))
+                rc = raw_window_dp_lane_lds(sig + v.sig_start, (int)(v.L - (v.n - 1)), mu + v.s, sd + v.s, (int)v.n, winsor,
+                                            P.max_half_z_score, &S_.row[0][lane], 64, &S_.flag[0][lane], 64, 1, out + v.s + 1);
+            else rc = TBA_INTERNAL;
+            if (rc == TBA_OK) v.to_read_positions(out);
         }
         laps.lap(2);
         // phase 2: the larger ones, SKL_FLAT_N at a time, each in its quarter of the same memory
         for (i64 i0 = 0; i0 < r.n_win; i0 += 64) {
             const i64 i = i0 + lane;
-            bool todo = i < r.n_win && w3[3 * i + 2] == -3 && rc == TBA_OK;
+            bool todo = i < r.n_win && w3[3 * i + 2] == SKW_FLAT && rc == TBA_OK;
             for (;;) {
                 const u64 mk = __ballot(todo);
                 if (mk == 0) break;
@@ -847,17 +711,14 @@ __global__ __launch_bounds__(64) void k_skip_dp(ReadState *rs, const DevParams *
                 __syncthreads();                                  // (the previous round's rows are done with)
                 if (todo && rank < SKL_FLAT_N) {
                     todo = false;
-                    const i64 s = w3[3 * i], e = w3[3 * i + 1], n = e - s;
-                    const i64 sig_start = ds[s], sig_end = ds[e];
-                    int rr = TBA_INTERNAL;
-                    if (sig_start >= 0 && sig_end <= n_norm) {
-                        const int len = (int)(sig_end - sig_start - (n - 1));
-                        rr = raw_window_dp_lane_lds(sig + sig_start, len, mu + s, sd + s, (int)n, winsor, P.max_half_z_score,
+                    const SkipWindow v(w3, ds, i);
+                    const int len = (int)(v.L - (v.n - 1));
+                    if (v.inside(n_norm))
+                        rc = raw_window_dp_lane_lds(sig + v.sig_start, len, mu + v.s, sd + v.s, (int)v.n, winsor, P.max_half_z_score,
                                                     &S_.row[0][0] + rank * (SKL_FLAT_LEN + 8), 1,
-                                                    &S_.flag[0][0] + rank * SKL_FLAT_WORDS, 1, (len + 63) >> 6, out + s + 1);
-                    }
-                    if (rr != TBA_OK) rc = rr;
-                    else for (i64 k = 0; k < n - 1; k++) out[s + 1 + k] += sig_start;
+                                                    &S_.flag[0][0] + rank * SKL_FLAT_WORDS, 1, (len + 63) >> 6, out + v.s + 1);
+                    else rc = TBA_INTERNAL;
+                    if (rc == TBA_OK) v.to_read_positions(out);
                 }
             }
         }
@@ -866,14 +727,12 @@ __global__ __launch_bounds__(64) void k_skip_dp(ReadState *rs, const DevParams *
     // what is left: windows over global scratch (raw_min_obs_per_base > 1: all the small ones; DNA: none in practice)
     for (i64 i = lane; i < r.n_win && rc == TBA_OK; i += 64) {
         if (w3[3 * i + 2] < 0) continue;                      // k_skip_dp_wave's, or done above
-        const i64 s = w3[3 * i], e = w3[3 * i + 1], n = e - s;
-        const i64 sig_start = ds[s], sig_end = ds[e];
-        if (sig_start < 0 || sig_end > n_norm) { rc = TBA_INTERNAL; break; }
-        const int rr = raw_window_dp(sig + sig_start, sig_end - sig_start, mu + s, sd + s, n, m,
-                                     P.do_winsorize_z != 0, P.max_half_z_score,
-                                     arena + r.skip_off + w3[3 * i + 2], out + s + 1);
-        if (rr != TBA_OK) { rc = rr; break; }
-        for (i64 k = 0; k < n - 1; k++) out[s + 1 + k] += sig_start;
+        const SkipWindow v(w3, ds, i);
+        if (v.inside(n_norm))
+            rc = raw_window_dp(sig + v.sig_start, v.L, mu + v.s, sd + v.s, v.n, m, P.do_winsorize_z != 0,
+                               P.max_half_z_score, arena + r.skip_off + v.code, out + v.s + 1);
+        else rc = TBA_INTERNAL;
+        if (rc == TBA_OK) v.to_read_positions(out);
     }
     if constexpr (phase_on(PH_SKIP_DP))
         if (lane == 0) { r.dbg[1] = laps.since_start(); laps.flush(r.dbg, 2, 4); r.dbg[6] = r.n_win; }
