@@ -757,6 +757,63 @@ int tba_region_key_levels(tba_engine *e, int est_mean, int64_t n_reads, const in
 int tba_segment_medians(tba_engine *e, const double *values, const int64_t *off, int64_t n_seg,
     double *out_medians);
 
+/* ---- region plot data (csrc/k_plot.h): the numbers behind the frames of tombo/_plot_commands.py:784-984 ----
+ * Level piles of a batch of plot regions: get_r_boxplot_data, get_r_quant_data and get_r_event_data over
+ * intervalData.get_base_levels (tombo_helper.py:1976-2032).  Reads as in tba_region_key_levels (read_start,
+ * read_minus, means CSR by read_off[n_reads + 1]); region r is [reg_start[r], reg_end[r]) with the reads
+ * reg_reads[reg_read_off[r] .. reg_read_off[r + 1]) in that order.  Positions run region-major, then in
+ * genomic order: n_pos = sum(reg_end - reg_start).  The pile of a position holds, in the region's read
+ * order, the levels of the reads that cover it; a NaN level is DROPPED (the frames remove NaN; the k-mer
+ * estimation above keeps it).
+ *   out_off[n_pos + 1]      the piles' offsets
+ *   out_levels              NULL, or the piles themselves (levels_cap values of room; the reads' overlaps
+ *                           with their regions always suffice)
+ *   out_lin[n_pos * n_ql]   np.percentile(pile, 100 q_linear[j]), the default linear form
+ *   out_near[n_pos * n_qn]  np.percentile(pile, 100 q_nearest[j], interpolation='nearest')
+ * q_linear / q_nearest are the fractions numpy divides out (np.true_divide(q, 100)), in [0, 1].  On the
+ * pile sorted ascending, v of n values: nearest is v[rint((n - 1) q)] (round half to even); linear is
+ * numpy's _lerp of a = v[floor(vi)], b = v[min(floor(vi) + 1, n - 1)], t = vi - floor(vi), vi = (n - 1) q:
+ * a + (b - a) t, and b - (b - a) (1 - t) where t >= 0.5, no operation fused.  An empty pile: NaN.
+ * No floating-point atomics: the same call gives the same bits.  out_kernel_ms (may be NULL): kernel time.
+ * TBA_E_ARG: NULL pointers, offsets that do not start at 0 or decrease, a region that names a read outside
+ * the batch, reg_end <= reg_start, a coordinate outside (-2^62, 2^62), a fraction outside [0, 1], a region
+ * with 2^31 reads or more (a pile of 2^31 levels), 2^31 positions or more, levels_cap too small.  Zero
+ * regions write out_off[0] = 0 and launch nothing. */
+int tba_region_level_piles(tba_engine *e, int64_t n_reads, const int64_t *read_start,
+    const uint8_t *read_minus, const int64_t *read_off, const double *means, int64_t n_regions,
+    const int64_t *reg_read_off, const int64_t *reg_reads, const int64_t *reg_start, const int64_t *reg_end,
+    int64_t n_ql, const double *q_linear, int64_t n_qn, const double *q_nearest, int64_t *out_off,
+    double *out_levels, int64_t levels_cap, double *out_lin, double *out_near, double *out_kernel_ms);
+/* The two percentile forms alone, of every segment of values (CSR by off[n_seg + 1]; values is not
+ * modified): out_lin[n_seg * n_ql], out_near[n_seg * n_qn].  An empty segment and one that holds a NaN give
+ * NaN, as np.percentile does.  Zero segments or zero fractions launch nothing. */
+int tba_segment_percentiles(tba_engine *e, const double *values, const int64_t *off, int64_t n_seg,
+    int64_t n_ql, const double *q_linear, int64_t n_qn, const double *q_nearest, double *out_lin, double *out_near,
+    double *out_kernel_ms);
+/* The raw-signal frame: th.get_raw_signal (tombo_helper.py:2090-2137), normalize_raw_signal with the read's
+ * stored scale values and the per-base position spread of get_r_raw_signal_data (_plot_commands.py:946-966)
+ * for n_pair (read, region) pairs.
+ *   reads  raw: the stored DAC values, int16_t (raw_bytes 2) or int32_t (raw_bytes 4), CSR by raw_off;
+ *          segs: the Events start column and the end, CSR by segs_off (bases + 1 entries a read);
+ *          read_start (genomic), rsrtr (read_start_rel_to_raw), minus, rna, shift, scale, lower_lim,
+ *          upper_lim (a NaN limit: no clip)
+ *   pairs  pair_read, and the region [pair_start, pair_end), which the read must overlap
+ * Per pair: the overlap slice of the segments (reversed for '-' as segs[-1] - segs[::-1]), its window of
+ * the signal (the whole signal reversed first for RNA, the window reversed for '-'), (raw - shift) / scale,
+ * the clip of c_apply_outlier_thresh; genome_centric == 0 applies the minus-strand flip of :946-952.  Then
+ * for sample i of n of overlap base b: Position = (pair_start + b + start_offset) + i * (1.0 / n).
+ *   out_sig_off[n_pair + 1]; out_position, out_signal, out_base_i [samples_cap]: pair-major, sample order
+ * TBA_E_ARG: NULL pointers, bad offsets, raw_bytes not 2 or 4, a read with fewer than two segment entries,
+ * with decreasing or negative segments, a negative rsrtr or segments that end past its signal, a pair that
+ * names no read of the batch, pair_end <= pair_start, no overlap, samples_cap too small.  Zero pairs write
+ * out_sig_off[0] = 0 and launch nothing. */
+int tba_region_raw_signal(tba_engine *e, int64_t n_reads, const void *raw, int raw_bytes,
+    const int64_t *raw_off, const int64_t *segs, const int64_t *segs_off, const int64_t *read_start,
+    const int64_t *rsrtr, const uint8_t *minus, const uint8_t *rna, const double *shift, const double *scale,
+    const double *lower_lim, const double *upper_lim, int64_t n_pair, const int64_t *pair_read,
+    const int64_t *pair_start, const int64_t *pair_end, int genome_centric, int64_t *out_sig_off,
+    double *out_position, double *out_signal, int64_t *out_base_i, int64_t samples_cap, double *out_kernel_ms);
+
 /* The de novo statistic of every read of the finished resident batch, nothing uploaded: per-base
  * means (c_new_means over the final signal and boundaries, as tba_batch_base_stats) against the
  * batch's own expected levels, which are the canonical model's levels of the read sequence --

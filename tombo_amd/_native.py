@@ -265,6 +265,11 @@ def _prototypes():
         # ---- estimate_kmer_model / estimate_motif_alt_model ----
         'tba_region_key_levels': (n, [v, n, q, cQ, cB, cQ, cD, q, cQ, cQ, q, cQ, cQ, q, cQ, cQ, q, Q, Q, D, D]),
         'tba_segment_medians': (n, [v, cD, cQ, q, D]),
+        # ---- region plot data ----
+        'tba_region_level_piles': (n, [v, q, cQ, cB, cQ, cD, q, cQ, cQ, cQ, cQ, q, cD, q, cD, Q, D, q, D, D, D]),
+        'tba_segment_percentiles': (n, [v, cD, cQ, q, q, cD, q, cD, D, D, D]),
+        'tba_region_raw_signal': (n, [v, q, v, n, cQ, cQ, cQ, cQ, cQ, cB, cB, cD, cD, cD, cD, q, cQ, cQ, cQ, n, Q, D, D, Q,
+                                      q, D]),
         'tba_batch_de_novo_stats': (n, [v, q, d, D, q]),
         # ---- the worker's per-read preparation; host-side packing ----
         'tba_identify_stalls': (n, [v, v, n, q, q, q, q, d, q, q, Q, q, Q]),
@@ -412,6 +417,121 @@ def _check_segment_medians_args(values, off):
     if off.shape[0] > 1 and np.diff(off).max() >= 2 ** 31:
         raise ValueError('a segment holds fewer than 2**31 values')
     return np.ascontiguousarray(values), off
+
+
+def _check_fractions(q, what):
+    """quantile fractions (what np.true_divide(q, 100) gives) -> contiguous float64[n]; None: none"""
+    if q is None:
+        return np.empty(0, dtype=np.float64)
+    q = np.asarray(q)
+    if q.dtype != np.float64 or q.ndim != 1:
+        raise ValueError('%s must be a one-dimensional float64 array of fractions' % what)
+    if q.shape[0] and not ((q >= 0.0) & (q <= 1.0)).all():
+        raise ValueError('%s must lie in [0, 1]' % what)
+    return np.ascontiguousarray(q)
+
+
+PLOT_COORD_MAX = 1 << 62    # genomic coordinates of the plot entries lie inside (-2**62, 2**62)
+
+
+def _check_region_level_piles_args(read_start, read_minus, read_off, means, reg_read_off, reg_reads, reg_start, reg_end,
+                                   q_linear, q_nearest):
+    """the argument checks of Engine.region_level_piles (shared with the tests' stand-in engine): dtypes are checked,
+    not converted; every index is checked against the array it points into -> the contiguous arrays, in order, and
+    the capacity the levels need (the reads' overlaps with their regions)"""
+    rs, rm, m = np.asarray(read_start), np.asarray(read_minus), np.asarray(means)
+    rr, st, en = np.asarray(reg_reads), np.asarray(reg_start), np.asarray(reg_end)
+    if rs.dtype != np.int64 or rm.dtype != np.uint8 or m.dtype != np.float64:
+        raise ValueError('read_start must be int64, read_minus uint8, means float64')
+    if any(v.dtype != np.int64 or v.ndim != 1 for v in (rr, st, en)):
+        raise ValueError('reg_reads, reg_start and reg_end must be one-dimensional int64 arrays')
+    ql, qn = _check_fractions(q_linear, 'q_linear'), _check_fractions(q_nearest, 'q_nearest')
+    off, roff = _check_offsets(read_off, 'read_off'), _check_offsets(reg_read_off, 'reg_read_off')
+    n_reads, n_regions = off.shape[0] - 1, roff.shape[0] - 1
+    if rs.shape != (n_reads,) or rm.shape != (n_reads,) or m.shape != (int(off[-1]),):
+        raise ValueError('per-read arrays, levels and offsets disagree')
+    if n_reads >= 2 ** 31:
+        raise ValueError('a call holds fewer than 2**31 reads')
+    if rr.shape[0] != int(roff[-1]) or (rr.shape[0] and (rr.min() < 0 or rr.max() >= n_reads)):
+        raise ValueError('reg_reads must hold reg_read_off[-1] indices of reads of the batch')
+    if st.shape != (n_regions,) or en.shape != (n_regions,):
+        raise ValueError('reg_start and reg_end must have one entry per region')
+    if any(v.shape[0] and (v.min() <= -PLOT_COORD_MAX or v.max() >= PLOT_COORD_MAX) for v in (rs, st, en)):
+        raise ValueError('coordinates must lie inside (-2**62, 2**62)')
+    if n_regions and (en <= st).any():
+        raise ValueError('every region needs reg_start < reg_end')
+    if n_regions and (np.diff(roff).max() >= 2 ** 31 or int((en - st).sum()) >= 2 ** 31):
+        raise ValueError('a pile holds fewer than 2**31 levels and a call fewer than 2**31 positions')
+    rep = np.repeat(np.arange(n_regions), np.diff(roff))
+    cap = int(np.maximum(np.minimum(rs[rr] + np.diff(off)[rr], en[rep]) - np.maximum(rs[rr], st[rep]), 0).sum())
+    return tuple(np.ascontiguousarray(v) for v in (rs, rm, off, m, roff, rr, st, en, ql, qn)) + (cap,)
+
+
+def _check_segment_percentiles_args(values, off, q_linear, q_nearest):
+    """the argument checks of Engine.segment_percentiles -> contiguous (values, off, q_linear, q_nearest)"""
+    v, off = _check_segment_medians_args(values, off)
+    if off.shape[0] - 1 >= 2 ** 31:
+        raise ValueError('a call holds fewer than 2**31 segments')
+    return v, off, _check_fractions(q_linear, 'q_linear'), _check_fractions(q_nearest, 'q_nearest')
+
+
+def raw_signal_fits(segs, read_start_rel_to_raw, n_raw):
+    """whether a read's segments (the Events start column and the end) address its raw signal of n_raw samples
+    whichever bases are taken: at least one base, non-decreasing from 0 or above, read_start_rel_to_raw >= 0, the
+    last end inside the signal.  A read that fails is left out of a region_raw_signal call (the host's form of the
+    reference's try / except round th.get_raw_signal)"""
+    segs = np.asarray(segs)
+    return bool(segs.ndim == 1 and segs.shape[0] >= 2 and segs[0] >= 0 and (np.diff(segs) >= 0).all() and
+                0 <= read_start_rel_to_raw and read_start_rel_to_raw + int(segs[-1]) <= n_raw and
+                int(segs[-1]) - int(segs[0]) < 2 ** 31)
+
+
+def _check_region_raw_signal_args(raw, raw_off, segs, segs_off, read_start, rsrtr, minus, rna, shift, scale, lower_lim,
+                                  upper_lim, pair_read, pair_start, pair_end):
+    """the argument checks of Engine.region_raw_signal (shared with the tests' stand-in engine): dtypes are checked,
+    not converted (raw: int16 or int32 as stored); every index and offset is checked against the array it points
+    into -> the contiguous arrays, in order, and the samples of every pair"""
+    raw, segs = np.asarray(raw), np.asarray(segs)
+    if raw.dtype not in (np.dtype(np.int16), np.dtype(np.int32)) or raw.ndim != 1:
+        raise ValueError('raw must be a one-dimensional int16 or int32 array')
+    i8 = [np.asarray(v) for v in (segs, read_start, rsrtr, pair_read, pair_start, pair_end)]
+    u1 = [np.asarray(v) for v in (minus, rna)]
+    f8 = [np.asarray(v) for v in (shift, scale, lower_lim, upper_lim)]
+    if any(v.dtype != np.int64 or v.ndim != 1 for v in i8) or any(v.dtype != np.uint8 or v.ndim != 1 for v in u1) or \
+            any(v.dtype != np.float64 or v.ndim != 1 for v in f8):
+        raise ValueError('segs, read_start, rsrtr and the pair arrays must be int64, minus and rna uint8, shift, scale '
+                         'and the limits float64, all one-dimensional')
+    roff, soff = _check_offsets(raw_off, 'raw_off'), _check_offsets(segs_off, 'segs_off')
+    n_reads = roff.shape[0] - 1
+    segs, rs, rsr, pr, ps, pe = i8
+    if soff.shape[0] != n_reads + 1 or raw.shape[0] != int(roff[-1]) or segs.shape[0] != int(soff[-1]) or \
+            any(v.shape != (n_reads,) for v in [rs, rsr] + u1 + f8):
+        raise ValueError('per-read arrays, raw signal, segments and offsets disagree')
+    if n_reads >= 2 ** 31 or pr.shape[0] >= 2 ** 31:
+        raise ValueError('a call holds fewer than 2**31 reads and pairs')
+    # raw_signal_fits for every read at once
+    if n_reads:
+        if np.diff(soff).min() < 2:
+            raise ValueError('the segments of a read do not fit its raw signal: a read needs two entries or more')
+        inside = np.ones(max(segs.shape[0] - 1, 0), dtype=bool)
+        inside[soff[1:-1] - 1] = False                       # the steps from one read's end to the next read's start
+        first, last = segs[soff[:-1]], segs[soff[1:] - 1]
+        if (np.diff(segs)[inside] < 0).any() or (first < 0).any() or (rsr < 0).any() or \
+                (last > np.diff(roff) - rsr).any() or (last - first >= 2 ** 31).any():
+            raise ValueError('the segments of a read do not fit its raw signal')
+    if pr.shape != ps.shape or pr.shape != pe.shape or (pr.shape[0] and (pr.min() < 0 or pr.max() >= n_reads)):
+        raise ValueError('pair_read, pair_start and pair_end must have one entry per pair, pair_read naming a read of '
+                         'the batch')
+    if any(v.shape[0] and (v.min() <= -PLOT_COORD_MAX or v.max() >= PLOT_COORD_MAX) for v in (rs, ps, pe)):
+        raise ValueError('coordinates must lie inside (-2**62, 2**62)')
+    nb = np.diff(soff)[pr] - 1
+    if pr.shape[0] and ((pe <= ps) | (ps >= rs[pr] + nb) | (pe <= rs[pr])).any():
+        raise ValueError('every pair needs pair_start < pair_end and a read that overlaps the region')
+    lo, hi = np.maximum(ps - rs[pr], 0), np.minimum(pe - rs[pr] + 1, nb + 1)
+    mn = np.asarray(u1[0], dtype=bool)[pr]
+    a, b = np.where(mn, nb - hi + 1, lo) + soff[pr], np.where(mn, nb - lo, hi - 1) + soff[pr]
+    n_obs = (segs[b] - segs[a]) if pr.shape[0] else np.zeros(0, dtype=np.int64)
+    return tuple(np.ascontiguousarray(v) for v in [raw, roff, segs, soff, rs, rsr] + u1 + f8 + [pr, ps, pe]) + (n_obs,)
 
 
 TRK_TILE = 256      # TBA_TRK_TILE of include/tombo_amd.h: positions per tile of the genome-track pileup
@@ -1281,6 +1401,59 @@ class Engine(object):
         out = np.empty(off.shape[0] - 1, dtype=np.float64)
         self._call('tba_segment_medians', v, off, off.shape[0] - 1, out)
         return out
+
+    # ---- region plot data (csrc/k_plot.h) ----
+    def region_level_piles(self, read_start, read_minus, read_off, means, reg_read_off, reg_reads, reg_start, reg_end,
+                           q_linear=None, q_nearest=None, want_levels=True):
+        """tba_region_level_piles: the level piles of a batch of plot regions.  Reads as in region_key_levels; region
+        r is [reg_start[r], reg_end[r]) with the reads reg_reads[reg_read_off[r]:reg_read_off[r + 1]] in that order.
+        Positions run region-major, then in genomic order; a pile holds the levels of the covering reads in read
+        order, NaN dropped.  q_linear / q_nearest: fractions (np.true_divide(q, 100)).
+        -> (off int64[n_pos + 1], levels float64 | None, lin float64[n_pos, n_ql] | None, near float64[n_pos, n_qn] |
+        None): np.percentile of every pile, linear and interpolation='nearest'; NaN for an empty pile.
+        `last_plot_kernel_ms`: kernel time."""
+        rs, rm, off, m, roff, rr, st, en, ql, qn, cap = _check_region_level_piles_args(
+            read_start, read_minus, read_off, means, reg_read_off, reg_reads, reg_start, reg_end, q_linear, q_nearest)
+        n_pos, ms = int((en - st).sum()), f64(0.0)
+        out_off = np.zeros(n_pos + 1, dtype=np.int64)
+        levels = np.empty(cap, dtype=np.float64) if want_levels else None
+        lin, near = np.empty((n_pos, ql.shape[0]), dtype=np.float64), np.empty((n_pos, qn.shape[0]), dtype=np.float64)
+        self._call('tba_region_level_piles', rs.shape[0], rs, rm, off, m, st.shape[0], roff, rr, st, en, ql.shape[0], ql,
+                   qn.shape[0], qn, out_off, levels, cap, lin, near, C.byref(ms))
+        self.last_plot_kernel_ms = ms.value
+        return (out_off, levels[:int(out_off[-1])].copy() if want_levels else None,
+                None if q_linear is None else lin, None if q_nearest is None else near)
+
+    def segment_percentiles(self, values, off, q_linear, q_nearest):
+        """tba_segment_percentiles: np.percentile of every segment of `values` (CSR by off) at the fractions q_linear
+        (linear form) and q_nearest (interpolation='nearest') -> (lin float64[n_seg, n_ql], near float64[n_seg, n_qn]);
+        NaN rows for an empty segment or one that holds a NaN.  `values` is not modified"""
+        v, off, ql, qn = _check_segment_percentiles_args(values, off, q_linear, q_nearest)
+        n_seg, ms = off.shape[0] - 1, f64(0.0)
+        lin, near = np.empty((n_seg, ql.shape[0]), dtype=np.float64), np.empty((n_seg, qn.shape[0]), dtype=np.float64)
+        self._call('tba_segment_percentiles', v, off, n_seg, ql.shape[0], ql, qn.shape[0], qn, lin, near, C.byref(ms))
+        self.last_plot_kernel_ms = ms.value
+        return lin, near
+
+    def region_raw_signal(self, raw, raw_off, segs, segs_off, read_start, rsrtr, minus, rna, shift, scale, lower_lim,
+                          upper_lim, pair_read, pair_start, pair_end, genome_centric=True):
+        """tba_region_raw_signal: th.get_raw_signal, the stored normalisation and the per-base position spread of
+        get_r_raw_signal_data for (read, region) pairs.  Reads: raw (int16 or int32, CSR by raw_off), segs (Events
+        start column and the end, CSR by segs_off), genomic read_start, rsrtr (read_start_rel_to_raw), minus, rna,
+        shift, scale, lower_lim, upper_lim (NaN: no clip).  Pair p: read pair_read[p] over [pair_start[p], pair_end[p]).
+        -> (sig_off int64[n_pair + 1], position float64, signal float64, base_i int64), pair-major, sample order.
+        `last_plot_kernel_ms`: kernel time."""
+        args = _check_region_raw_signal_args(raw, raw_off, segs, segs_off, read_start, rsrtr, minus, rna, shift, scale,
+                                             lower_lim, upper_lim, pair_read, pair_start, pair_end)
+        (raw, roff, segs, soff, rs, rsr, mn, rn, sh, sc, lo, hi, pr, ps, pe), n_obs = args[:-1], args[-1]
+        n_pair, cap, ms = pr.shape[0], int(n_obs.sum()), f64(0.0)
+        sig_off = np.zeros(n_pair + 1, dtype=np.int64)
+        pos, sig, base = (np.empty(cap, dtype=t) for t in (np.float64, np.float64, np.int64))
+        self._call('tba_region_raw_signal', rs.shape[0], C.c_void_p(raw.ctypes.data), raw.dtype.itemsize, roff, segs,
+                   soff, rs, rsr, mn, rn, sh, sc, lo, hi, n_pair, pr, ps, pe, bool(genome_centric), sig_off, pos, sig, base,
+                   cap, C.byref(ms))
+        self.last_plot_kernel_ms = ms.value
+        return sig_off, pos, sig, base
 
     # ---- genome tracks (csrc/k_tracks.h) ----
     def tracks_begin(self, win_start, win_end, n_slots):

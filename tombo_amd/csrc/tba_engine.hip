@@ -22,6 +22,7 @@
 #include "k_kmer_est.h"
 #include "k_roc.h"
 #include "k_pdist.h"
+#include "k_plot.h"
 
 #include <algorithm>
 #include <array>
@@ -2534,6 +2535,217 @@ extern "C" int tba_segment_medians(tba_engine *e, const double *values, const in
     k_kest_median<<<grid_for(n_seg), 256, 0, e->stream>>>(n_seg, has_nan, d_off, d_v, d_out);
     if (sc.sync()) return sc.rc;
     return sc.get(out_medians, d_out, n_seg);
+}
+
+// ---- region plot data (k_plot.h): the numbers of the box, quantile, density and raw-signal frames ----
+namespace {
+static int check_fractions(const double *q, i64 n)
+{
+    for (i64 i = 0; i < n; i++)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return set_err(TBA_E_ARG, "a quantile fraction outside [0, 1]");
+    return TBA_OK;
+}
+static bool plot_coord_ok(i64 v) { return v > -((i64)1 << 62) && v < ((i64)1 << 62); }
+
+// the two percentile forms of every segment of d_v (sorted in place here) enqueued; a failure stays in sc.rc
+static void launch_percentiles(Scratch &sc, i64 n_seg, const i64 *d_off, double *d_v, i64 n_ql, const double *q_linear,
+                               i64 n_qn, const double *q_nearest, double *d_lin, double *d_near)
+{
+    const double *d_ql = sc.in(q_linear, n_ql), *d_qn = sc.in(q_nearest, n_qn);
+    const i32 *has_nan = sort_segments(sc, n_seg, d_off, d_v);
+    if (sc.rc) return;
+    k_plot_percentiles<<<grid_for(n_seg * (n_ql + n_qn)), 256, 0, sc.stream>>>(n_seg, has_nan, d_off, d_v, n_ql, d_ql,
+        n_qn, d_qn, d_lin, d_near);
+}
+} // namespace
+
+extern "C" int tba_region_level_piles(tba_engine *e, int64_t n_reads, const int64_t *read_start,
+    const uint8_t *read_minus, const int64_t *read_off, const double *means, int64_t n_regions,
+    const int64_t *reg_read_off, const int64_t *reg_reads, const int64_t *reg_start, const int64_t *reg_end,
+    int64_t n_ql, const double *q_linear, int64_t n_qn, const double *q_nearest, int64_t *out_off,
+    double *out_levels, int64_t levels_cap, double *out_lin, double *out_near, double *out_kernel_ms)
+{
+    if (!e || n_reads < 0 || n_reads >= ((i64)1 << 31) || n_regions < 0 || n_ql < 0 || n_qn < 0 || levels_cap < 0 ||
+        !read_off || !reg_read_off || !out_off || (n_reads > 0 && (!read_start || !read_minus)) ||
+        (n_regions > 0 && (!reg_start || !reg_end)) || (n_ql > 0 && !q_linear) || (n_qn > 0 && !q_nearest))
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (const int rc = check_csr_off(read_off, n_reads)) return rc;
+    if (const int rc = check_csr_off(reg_read_off, n_regions)) return rc;
+    if (const int rc = check_fractions(q_linear, n_ql)) return rc;
+    if (const int rc = check_fractions(q_nearest, n_qn)) return rc;
+    const i64 total = n_reads > 0 ? read_off[n_reads] : 0, n_rr = n_regions > 0 ? reg_read_off[n_regions] : 0;
+    if ((total > 0 && !means) || (n_rr > 0 && !reg_reads)) return set_err(TBA_E_ARG, "bad arguments");
+    for (i64 q = 0; q < n_rr; q++)
+        if (reg_reads[q] < 0 || reg_reads[q] >= n_reads) return set_err(TBA_E_ARG, "a region names a read outside the batch");
+    for (i64 q = 0; q < n_reads; q++)
+        if (!plot_coord_ok(read_start[q])) return set_err(TBA_E_ARG, "a read start outside (-2^62, 2^62)");
+    std::vector<i64> pos_off((size_t)n_regions + 1, 0);
+    for (i64 r = 0; r < n_regions; r++) {
+        if (!plot_coord_ok(reg_start[r]) || !plot_coord_ok(reg_end[r]) || reg_end[r] <= reg_start[r])
+            return set_err(TBA_E_ARG, "a region must have start < end, both inside (-2^62, 2^62)");
+        if (reg_read_off[r + 1] - reg_read_off[r] >= ((i64)1 << 31))
+            return set_err(TBA_E_ARG, "a pile of 2^31 levels or more");
+        pos_off[r + 1] = pos_off[r] + (reg_end[r] - reg_start[r]);
+        if (pos_off[r + 1] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "2^31 positions or more in one call");
+    }
+    const i64 n_pos = pos_off[n_regions], nq = n_ql + n_qn;
+    out_off[0] = 0;
+    if (n_pos == 0) return TBA_OK;
+    if ((n_ql > 0 && !out_lin) || (n_qn > 0 && !out_near)) return set_err(TBA_E_ARG, "bad arguments");
+    Scratch sc(e);
+    PlotPileArgs a{};
+    a.n_regions = n_regions; a.n_pos = n_pos;
+    a.reg_pos_off = sc.in(pos_off.data(), n_regions + 1);
+    a.reg_start = sc.in(reg_start, n_regions);
+    a.reg_read_off = sc.in(reg_read_off, n_regions + 1);
+    a.reg_reads = sc.in(reg_reads, n_rr);
+    a.read_start = sc.in(read_start, n_reads);
+    a.read_minus = sc.in(read_minus, n_reads);
+    a.read_off = sc.in(read_off, n_reads + 1);
+    a.means = sc.in(means, total);
+    i32 *cov = sc.out<i32>(n_pos);
+    i64 *lv_off = sc.out<i64>(n_pos + 1);
+    if (sc.rc) return sc.rc;
+    KernelTimer tm_count(sc, out_kernel_ms != nullptr);
+    k_plot_pileup<false><<<grid_for(n_pos), 256, 0, sc.stream>>>(a, cov, nullptr, nullptr);
+    k_kest_offsets<<<1, 256, 0, sc.stream>>>(n_pos, cov, lv_off);
+    tm_count.stop();
+    i64 n_lv = 0;
+    if (sc.sync() || sc.get(&n_lv, lv_off + n_pos, 1) || sc.get(out_off, lv_off, n_pos + 1)) return sc.rc;
+    if (out_levels && n_lv > levels_cap) return set_err(TBA_E_ARG, "levels_cap is smaller than the levels of the call");
+    double *d_lv = sc.out<double>(n_lv), *d_sorted = d_lv;
+    double *d_lin = sc.out<double>(n_pos * n_ql), *d_near = sc.out<double>(n_pos * n_qn);
+    if (out_levels && nq > 0) d_sorted = sc.out<double>(n_lv);   // the frames want read order and the sorters work in place
+    if (sc.rc) return sc.rc;
+    KernelTimer tm_fill(sc, out_kernel_ms != nullptr);
+    if (n_lv > 0) k_plot_pileup<true><<<grid_for(n_pos), 256, 0, sc.stream>>>(a, nullptr, lv_off, d_lv);
+    if (nq > 0) {
+        if (d_sorted != d_lv && n_lv > 0)
+            sc.hip(hipMemcpyAsync(d_sorted, d_lv, (size_t)n_lv * sizeof(double), hipMemcpyDeviceToDevice, sc.stream), "hipMemcpyAsync");
+        launch_percentiles(sc, n_pos, lv_off, d_sorted, n_ql, q_linear, n_qn, q_nearest, d_lin, d_near);
+    }
+    tm_fill.stop();
+    if (sc.sync()) return sc.rc;
+    if (out_kernel_ms) *out_kernel_ms = tm_count.ms() + tm_fill.ms();
+    if (out_levels && n_lv > 0 && sc.get(out_levels, d_lv, n_lv)) return sc.rc;
+    if (n_ql > 0 && sc.get(out_lin, d_lin, n_pos * n_ql)) return sc.rc;
+    return n_qn > 0 ? sc.get(out_near, d_near, n_pos * n_qn) : TBA_OK;
+}
+
+extern "C" int tba_segment_percentiles(tba_engine *e, const double *values, const int64_t *off, int64_t n_seg,
+    int64_t n_ql, const double *q_linear, int64_t n_qn, const double *q_nearest, double *out_lin, double *out_near,
+    double *out_kernel_ms)
+{
+    if (!e || !off || n_seg < 0 || n_ql < 0 || n_qn < 0 || (n_ql > 0 && !q_linear) || (n_qn > 0 && !q_nearest) ||
+        (n_seg > 0 && ((n_ql > 0 && !out_lin) || (n_qn > 0 && !out_near))))
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (const int rc = check_fractions(q_linear, n_ql)) return rc;
+    if (const int rc = check_fractions(q_nearest, n_qn)) return rc;
+    if (n_seg == 0 || n_ql + n_qn == 0) return TBA_OK;
+    if (n_seg >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "2^31 segments or more in one call");
+    if (const int rc = check_csr_off(off, n_seg)) return rc;
+    for (i64 s = 0; s < n_seg; s++)
+        if (off[s + 1] - off[s] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "a pile of 2^31 levels or more");
+    const i64 n = off[n_seg];
+    if (n > 0 && !values) return set_err(TBA_E_ARG, "bad arguments");
+    Scratch sc(e);
+    double *d_v = sc.in(values, n);
+    const i64 *d_off = sc.in(off, n_seg + 1);
+    double *d_lin = sc.out<double>(n_seg * n_ql), *d_near = sc.out<double>(n_seg * n_qn);
+    KernelTimer tm(sc, out_kernel_ms != nullptr);
+    launch_percentiles(sc, n_seg, d_off, d_v, n_ql, q_linear, n_qn, q_nearest, d_lin, d_near);
+    tm.stop();
+    if (sc.sync()) return sc.rc;
+    if (out_kernel_ms) *out_kernel_ms = tm.ms();
+    if (n_ql > 0 && sc.get(out_lin, d_lin, n_seg * n_ql)) return sc.rc;
+    return n_qn > 0 ? sc.get(out_near, d_near, n_seg * n_qn) : TBA_OK;
+}
+
+extern "C" int tba_region_raw_signal(tba_engine *e, int64_t n_reads, const void *raw, int raw_bytes,
+    const int64_t *raw_off, const int64_t *segs, const int64_t *segs_off, const int64_t *read_start,
+    const int64_t *rsrtr, const uint8_t *minus, const uint8_t *rna, const double *shift, const double *scale,
+    const double *lower_lim, const double *upper_lim, int64_t n_pair, const int64_t *pair_read,
+    const int64_t *pair_start, const int64_t *pair_end, int genome_centric, int64_t *out_sig_off,
+    double *out_position, double *out_signal, int64_t *out_base_i, int64_t samples_cap, double *out_kernel_ms)
+{
+    if (!e || n_reads < 0 || n_reads >= ((i64)1 << 31) || n_pair < 0 || n_pair >= ((i64)1 << 31) || samples_cap < 0 ||
+        (raw_bytes != 2 && raw_bytes != 4) || !raw_off || !segs_off || !out_sig_off ||
+        (n_reads > 0 && (!read_start || !rsrtr || !minus || !rna || !shift || !scale || !lower_lim || !upper_lim)) ||
+        (n_pair > 0 && (!pair_read || !pair_start || !pair_end)))
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (const int rc = check_csr_off(raw_off, n_reads)) return rc;
+    if (const int rc = check_csr_off(segs_off, n_reads)) return rc;
+    const i64 n_raw = n_reads > 0 ? raw_off[n_reads] : 0, n_segs = n_reads > 0 ? segs_off[n_reads] : 0;
+    if ((n_raw > 0 && !raw) || (n_segs > 0 && !segs)) return set_err(TBA_E_ARG, "bad arguments");
+    // every read's window lies inside its signal, whichever bases a pair takes: segments non-decreasing from
+    // 0 or above, read_start_rel_to_raw >= 0, the last segment end inside the signal
+    for (i64 q = 0; q < n_reads; q++) {
+        const i64 *S = segs + segs_off[q];
+        const i64 nb = segs_off[q + 1] - segs_off[q] - 1, len = raw_off[q + 1] - raw_off[q];
+        if (nb < 1) return set_err(TBA_E_ARG, "a read needs at least one base (two segment entries)");
+        if (!plot_coord_ok(read_start[q])) return set_err(TBA_E_ARG, "a read start outside (-2^62, 2^62)");
+        if (S[0] < 0 || rsrtr[q] < 0 || rsrtr[q] > len || S[nb] > len - rsrtr[q] || S[nb] - S[0] >= ((i64)1 << 31))
+            return set_err(TBA_E_ARG, "a read's segments do not fit its raw signal");
+        for (i64 k = 0; k < nb; k++)
+            if (S[k + 1] < S[k]) return set_err(TBA_E_ARG, "a read's segments must be non-decreasing");
+    }
+    for (i64 p = 0; p < n_pair; p++) {
+        const i64 q = pair_read[p];
+        if (q < 0 || q >= n_reads) return set_err(TBA_E_ARG, "a pair names a read outside the batch");
+        if (!plot_coord_ok(pair_start[p]) || !plot_coord_ok(pair_end[p]) || pair_end[p] <= pair_start[p])
+            return set_err(TBA_E_ARG, "a pair's region must have start < end, both inside (-2^62, 2^62)");
+        const i64 nb = segs_off[q + 1] - segs_off[q] - 1;
+        if (pair_start[p] >= read_start[q] + nb || pair_end[p] <= read_start[q])
+            return set_err(TBA_E_ARG, "a pair's read does not overlap its region");
+    }
+    out_sig_off[0] = 0;
+    if (n_pair == 0) return TBA_OK;
+    Scratch sc(e);
+    PlotSigArgs a{};
+    a.n_pair = n_pair; a.genome_centric = genome_centric != 0; a.raw_i32 = raw_bytes == 4;
+    a.raw = sc.in((const char *)raw, (size_t)n_raw * raw_bytes);
+    a.raw_off = sc.in(raw_off, n_reads + 1);
+    a.segs = sc.in(segs, n_segs);
+    a.segs_off = sc.in(segs_off, n_reads + 1);
+    a.read_start = sc.in(read_start, n_reads);
+    a.rsrtr = sc.in(rsrtr, n_reads);
+    a.minus = sc.in(minus, n_reads);
+    a.rna = sc.in(rna, n_reads);
+    a.shift = sc.in(shift, n_reads);
+    a.scale = sc.in(scale, n_reads);
+    a.lower = sc.in(lower_lim, n_reads);
+    a.upper = sc.in(upper_lim, n_reads);
+    a.pair_read = sc.in(pair_read, n_pair);
+    a.pair_start = sc.in(pair_start, n_pair);
+    a.pair_end = sc.in(pair_end, n_pair);
+    PlotSigGeom *geom = sc.out<PlotSigGeom>(n_pair);
+    i32 *cov = sc.out<i32>(n_pair), *d_st = sc.status();
+    i64 *sig_off = sc.out<i64>(n_pair + 1);
+    if (sc.rc) return sc.rc;
+    KernelTimer tm_sizes(sc, out_kernel_ms != nullptr);
+    k_plot_sig_sizes<<<grid_for(n_pair), 256, 0, sc.stream>>>(a, geom, cov, d_st);
+    k_kest_offsets<<<1, 256, 0, sc.stream>>>(n_pair, cov, sig_off);
+    tm_sizes.stop();
+    if (const int st = sc.sync(d_st)) return sc.rc ? sc.rc : set_err(st, "a pair failed the device's checks");
+    if (sc.get(out_sig_off, sig_off, n_pair + 1)) return sc.rc;
+    const i64 total = out_sig_off[n_pair];
+    if (out_kernel_ms) *out_kernel_ms = tm_sizes.ms();
+    if (total == 0) return TBA_OK;
+    if (total > samples_cap || !out_position || !out_signal || !out_base_i)
+        return set_err(TBA_E_ARG, "samples_cap is smaller than the samples of the call");
+    double *d_pos = sc.out<double>(total), *d_sig = sc.out<double>(total);
+    i64 *d_base = sc.out<i64>(total);
+    if (sc.rc) return sc.rc;
+    KernelTimer tm_fill(sc, out_kernel_ms != nullptr);
+    k_plot_sig_fill<<<grid_for(total), 256, 0, sc.stream>>>(a, geom, sig_off, total, d_pos, d_sig, d_base);
+    tm_fill.stop();
+    if (sc.sync()) return sc.rc;
+    if (out_kernel_ms) *out_kernel_ms += tm_fill.ms();
+    if (sc.get(out_position, d_pos, total) || sc.get(out_signal, d_sig, total)) return sc.rc;
+    return sc.get(out_base_i, d_base, total);
 }
 
 // testable slice of every read -> CSR offsets into a packed copy of (means, levels); one thread

@@ -604,6 +604,120 @@ def get_unique_intervals(plot_intervals, covered_poss=None, num_regions=None):
     return uniq_p_intervals
 
 
+class intervalData(object):
+    """A genome / transcriptome interval with its reads and sequence (tombo_helper.py:1749-2032): the regions the
+    plot data frames of tombo_amd/plot_commands.py are made from.  Every method returns the object, so calls chain
+    (`int_data.add_reads(reads_index).add_seq()`).  Reads are in-memory objects with `start`, `end`, `strand`,
+    read-centric `means` and, for add_seq without a genome, `seq`."""
+
+    def __setattr__(self, name, value):
+        if name == 'chrm':
+            if not isinstance(value, str):
+                raise TypeError(name + ' must be a string')
+        elif name in ('start', 'end'):
+            if not isinstance(value, (int, np.integer)):
+                raise TypeError(name + ' must be an int')
+        elif name == 'strand':
+            if value not in (None, '+', '-'):
+                raise TypeError('strand must be either None, "+", or "-"')
+        elif name in ('reg_id', 'reg_text', 'seq'):
+            if value is not None and not isinstance(value, str):
+                raise TypeError(name + ' must be a string')
+        elif name == 'reads':
+            if value is not None and not isinstance(value, list):
+                raise TypeError('reads must be a list')
+        else:
+            raise ValueError(name + ' is an invalid attribute for intervalData')
+        super(intervalData, self).__setattr__(name, value)
+
+    def __init__(self, chrm, start, end, strand=None, reg_id=None, reg_text='', reads=None, seq=None):
+        self.chrm = str(chrm)
+        self.start = start
+        self.end = end
+        self.strand = str(strand) if strand is not None else None
+        self.reg_id = str(reg_id) if reg_id is not None else None
+        self.reg_text = str(reg_text)
+        self.reads = reads
+        self.seq = seq
+
+    def update(self, **kwargs):
+        for k, v in kwargs.items():
+            self.__setattr__(k, v)
+        return self
+
+    def copy(self, include_reads=True):
+        return type(self)(self.chrm, self.start, self.end, self.strand, self.reg_id, self.reg_text,
+                          self.reads if include_reads else None, self.seq)
+
+    def merge(self, other_reg):
+        """a copy with the reads of this interval followed by those of other_reg; all else is this interval's"""
+        return self.copy().update(reads=(self.reads if self.reads is not None else []) +
+                                  (other_reg.reads if other_reg.reads is not None else []))
+
+    def expand_interval(self, expand_width):
+        """start and end only; not seq or reads"""
+        return self.update(start=self.start - expand_width, end=self.end + expand_width)
+
+    def add_reads(self, reads_index, require_full_span=False):
+        """the reads of reads_index ({(chrm, strand): [reads]}) that overlap the interval, or with require_full_span
+        span it (:1860-1889); without a strand the plus reads, then the minus reads"""
+        def get_c_s_data(strand):
+            if require_full_span:
+                return [rd for rd in reads_index.get((self.chrm, strand), [])
+                        if rd.start <= self.start and rd.end >= self.end]
+            return [rd for rd in reads_index.get((self.chrm, strand), [])
+                    if not (rd.start >= self.end or rd.end <= self.start)]
+        if self.strand is not None:
+            return self.update(reads=get_c_s_data(self.strand))
+        return self.update(reads=get_c_s_data('+') + get_c_s_data('-'))
+
+    def add_seq(self, genome_index=None, error_end=True):
+        """the forward-strand sequence from genome_index (a Fasta), else from the reads (get_region_seq)"""
+        if genome_index is not None:
+            return self.update(seq=genome_index.get_seq(self.chrm, self.start, self.end, error_end=error_end))
+        return self.update(seq=get_region_seq(self.reads, self.start, self.end))
+
+    def get_base_levels(self, read_rows=False, num_reads=None, engine=None):
+        """float64[end - start, reads] (read_rows: transposed) of genome-centric levels, NaN where a read does not
+        cover a position (:1976-2032).  With num_reads, `self.reads` is shuffled in place (np.random.shuffle) and the
+        first num_reads usable reads are taken.  Reads of the other strand and reads without levels are skipped.
+        The reference's four overlap branches place, for every read that overlaps the interval, the read's levels at
+        the positions it covers; that is what is built here.  The matrix is a copy of slices without arithmetic, so
+        it is made on the host; `engine` is accepted so that every plot-data call takes one, and is not used."""
+        if self.reads is None or len(self.reads) == 0:
+            raise TomboError('Must annotate region with reads (see `TomboInterval.add_reads`) to extract base levels.')
+        if num_reads is not None:
+            np.random.shuffle(self.reads)
+        reg_events = []
+        for rd in self.level_reads():
+            r_means = np.asarray(rd.means, dtype=np.float64)
+            if rd.strand == '-':
+                r_means = r_means[::-1]
+            r_reg_means = np.full(self.end - self.start, np.nan)
+            lo, hi = max(rd.start, self.start), min(rd.end, self.end)
+            if lo < hi:
+                r_reg_means[lo - self.start:hi - self.start] = r_means[lo - rd.start:hi - rd.start]
+            reg_events.append(r_reg_means)
+            if num_reads is not None and len(reg_events) >= num_reads:
+                break
+        return np.vstack(reg_events) if read_rows else np.column_stack(reg_events)
+
+    def level_reads(self):
+        """the reads get_base_levels takes columns from, in order: the interval's strand, with levels"""
+        return [rd for rd in self.reads if (self.strand is None or rd.strand == self.strand) and rd.means is not None]
+
+
+def filter_empty_regions(plot_intervals):
+    """the intervals that have reads (tombo_helper.py:2035-2043); none left is the reference's exit, raised here"""
+    num_filt = sum(len(p_int.reads) == 0 for p_int in plot_intervals)
+    plot_intervals = [p_int for p_int in plot_intervals if len(p_int.reads) > 0]
+    if len(plot_intervals) == 0:
+        raise TomboError('No reads in any selected regions.')
+    if num_filt > 0:
+        warnings.warn('Some selected regions contain no reads.')
+    return plot_intervals
+
+
 # ---- genome tracks: coverage, mean signal / SD / dwell per position, sample - control ---------
 # (text_output browser_files, iter_cov_regs, get_largest_signal_differences; the pileup kernels
 # are csrc/k_tracks.h).  A `reads_index` is the {(chrm, strand): [reads]} mapping `read_index`
