@@ -308,6 +308,7 @@ enum {
                                * kernels: the launch decisions the engine recorded when it enqueued the run, and per read
                                * the predicates by which the kernels select their reads (k_dp.h, k_dp_multi.h, k_dp_wg.h)
                                * over the state the run left (TBA_GET_PATH, TBA_GET_START_FAIL, start state) */
+    TBA_GET_NORM_FORM = 33,   /* int32[n]: TBA_NORM_FORM_*: the code that found the medians of the read's normalisation */
     TBA_GET_DEBUG_COUNTERS = 99 /* int64[n][8]: ReadState.dbg, only filled by the profiling builds (one of
                                    -DTBA_PHASE_DEBUG=<id>, -DTBA_SWEEP_STATS, -DTBA_SKIP_STATS, -DTBA_SKIP_CLASS_STATS;
                                    the slots of each: csrc/tba_phase.h), zeros otherwise */
@@ -320,6 +321,12 @@ enum {
                                      * k_detect / k_pick flagged, parameter sets outside their limits */
     TBA_ED_FORM_DETECT_TT_PICK = 4, /* RNA: k_detect_tt + k_pick */
     TBA_ED_FORM_TTEST_PEAKS = 5     /* RNA: k_scores_ttest + k_peaks */
+};
+enum {
+    TBA_NORM_FORM_NONE = 0,         /* no medians: scale values given or taken from the events (RNA), or the read had failed */
+    TBA_NORM_FORM_SELECT = 1,       /* k_normalize: one pass per median through a sampled window, or the generic bucket select */
+    TBA_NORM_FORM_INT_COUNT = 2,    /* k_normalize, int16 samples: both medians from one counting pass */
+    TBA_NORM_FORM_HIST = 3          /* k_normalize_hist, float samples: all medians from one histogram pass and one list pass */
 };
 enum {
     TBA_TB_FORM_NONE = 0,

@@ -105,10 +105,12 @@ GET_VALID_CPTS, GET_N_CPTS, GET_EVENT_MEANS, GET_SEG_NORM, GET_SEG_SV, GET_START
     GET_BAND_STARTS, GET_READ_TB, GET_DP_SEGS, GET_THEIL_SEN, GET_PATH, GET_LAST_ROW, \
     GET_DP_READ_START, GET_KERNEL_MS, GET_REF_MEANS, GET_REF_SDS, GET_SEGS, GET_STATUS, GET_START_FAIL, \
     GET_STALL_INTS, GET_N_STALL, GET_STALL_OFF, GET_SAMP_IND, GET_TB_PARALLEL, GET_ED_FUSED, GET_ED_TAKEN_POS, GET_ED_N_TAKEN, \
-    GET_DP_WORKGROUP, GET_ED_FORM, GET_TB_FORM, GET_TB_VERIFY_FAIL, GET_DP_FORM = range(1, 33)
+    GET_DP_WORKGROUP, GET_ED_FORM, GET_TB_FORM, GET_TB_VERIFY_FAIL, GET_DP_FORM, GET_NORM_FORM = range(1, 34)
 # TBA_ED_FORM_* / TBA_TB_FORM_*: which kernels produced a read's change points / main traceback
 ED_FORM_NONE, ED_FORM_WG_SCAN_PEAKS, ED_FORM_DETECT_PICK, ED_FORM_SCORES_PEAKS, ED_FORM_DETECT_TT_PICK, \
     ED_FORM_TTEST_PEAKS = range(6)
+# TBA_NORM_FORM_*: which code found the medians of a read's normalisation
+NORM_FORM_NONE, NORM_FORM_SELECT, NORM_FORM_INT_COUNT, NORM_FORM_HIST = range(4)
 TB_FORM_NONE, TB_FORM_LANE, TB_FORM_LONG, TB_FORM_PAR16, TB_FORM_PAR64 = 0, 1, 2, 16, 64
 # TBA_GET_DP_FORM, int32[n][4]: (TBA_DP_FORM_* of the main forward pass, its cells-per-lane class, TBA_DP_START_* of
 # start discovery, class of the retry kernel); derived on the host from the run's launch decisions and per-read state
@@ -143,7 +145,7 @@ _GET_SHAPES = {
     GET_N_STALL: (np.int64, ('n',)), GET_STALL_OFF: (np.int64, ('n',)),
     GET_SAMP_IND: (np.int64, ('n', MAX_POINTS_FOR_THEIL_SEN)),
     GET_TB_PARALLEL: (np.int32, ('n',)), GET_ED_FUSED: (np.int32, ('n',)), GET_DP_WORKGROUP: (np.int32, ('n',)),
-    GET_ED_FORM: (np.int32, ('n',)), GET_TB_FORM: (np.int32, ('n',)), GET_TB_VERIFY_FAIL: (np.int32, ('n',)),
+    GET_NORM_FORM: (np.int32, ('n',)), GET_ED_FORM: (np.int32, ('n',)), GET_TB_FORM: (np.int32, ('n',)), GET_TB_VERIFY_FAIL: (np.int32, ('n',)),
     GET_ED_TAKEN_POS: (np.int32, ('raw_x2',)), GET_ED_N_TAKEN: (np.int64, ('n',)),
 }
 

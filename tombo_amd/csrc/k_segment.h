@@ -12,12 +12,87 @@
 // reference sees after its own int16 -> float64 promotion.
 // The read's `norm` slice serves as scratch (window lists) until the final pass writes the signal;
 // write_norm == 0: only the scale values are produced; 2: see below.
-// Medians: int16 input -> one counting pass (block_int_medians); float input -> one pass per
-// median through a sampled window (block_median_window); short reads and every failure of the
-// fast forms -> the generic bucket select (two passes per median).
+// Medians: int16 input -> one counting pass (block_int_medians); float input of NORM_WINDOW_MIN
+// samples or more -> k_normalize_hist below, launched ahead of this kernel: all medians from one
+// histogram pass and one list pass (block_hist_medians), the scale values and ReadState.norm_form =
+// TBA_NORM_FORM_HIST left for this kernel, which then goes straight to its tail.  Every read that
+// kernel declines: one pass per median through a sampled window (block_median_window); short
+// reads and every failure of the fast forms -> the generic bucket select (two passes per median).
+// ReadState.norm_form (TBA_GET_NORM_FORM) records which of them produced the read's medians.
 template <class RT> struct raw_is_int { static constexpr bool value = false; };
 template <> struct raw_is_int<int16_t> { static constexpr bool value = true; };
 #define NORM_WINDOW_MIN 16384 // below this the generic select is cheap anyway
+
+// The reads whose medians k_normalize finds itself: the conditions of the first two branches of k_normalize below,
+// restated for k_normalize_hist -- the two must be kept in step by hand (a read taken here that k_normalize would give
+// its scale values another way gets the wrong ones; tests/test_normalize_hist_gpu.py holds both sides).
+// batch_has_medians (host): the batch-wide part of the same test, by which the engine skips the launch altogether.
+__host__ __device__ __forceinline__ bool batch_has_medians(const tba_opts &o, int mode)
+{
+    return !o.has_const_scale && !(mode == 1 && o.use_rna_event_scale);
+}
+__device__ __forceinline__ bool norm_needs_medians(const ReadState &r, const tba_opts &o, int mode)
+{
+    return !(r.sv_flags & 1) && !(mode == 1 && !o.has_const_scale && o.use_rna_event_scale);
+}
+// range of the strided sample of a read, WS_PER values per thread (all threads get it).  (k_normalize keeps its own
+// lines for the same sample: it sits on its register step, and sharing a function moves its allocation)
+template <class X>
+__device__ __forceinline__ void norm_sample_range(X x, i64 n, BucketSmem *sm, double *smn_out, double *smx_out)
+{
+    const int tid = threadIdx.x;
+    double smn = INFINITY, smx = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < WS_PER; q++) {
+        const i64 si = (n * (i64)(q * SEL_NT + tid)) / (SEL_NT * WS_PER);
+        const double v = x[si];
+        smn = v < smn ? v : smn; smx = v > smx ? v : smx;
+    }
+    for (int mm = 32; mm >= 1; mm >>= 1) {
+        double a = shfl_xor_f64(smn, mm), b2 = shfl_xor_f64(smx, mm);
+        smn = a < smn ? a : smn; smx = b2 > smx ? b2 : smx;
+    }
+    if ((tid & 63) == 0) { sm->redd[2 * (tid >> 6)] = smn; sm->redd[2 * (tid >> 6) + 1] = smx; }
+    __syncthreads();
+    smn = sm->redd[0]; smx = sm->redd[1];
+    for (int w = 1; w < SEL_NT / 64; w++) {
+        smn = sm->redd[2 * w] < smn ? sm->redd[2 * w] : smn;
+        smx = sm->redd[2 * w + 1] > smx ? sm->redd[2 * w + 1] : smx;
+    }
+    __syncthreads();
+    *smn_out = smn; *smx_out = smx;
+}
+
+// Float input: shift, scale and the outlier limits of a read from two passes over its samples
+// (block_hist_medians, k_select.h), one workgroup per read, launched ahead of k_normalize.  A kernel of
+// its own: k_normalize sits on its register step (128 VGPRs, two workgroups per CU) and has no room
+// for another select.  Takes the reads whose medians k_normalize would find by its window passes
+// (no scale values given, no const scale, n_raw >= NORM_WINDOW_MIN) and leaves every other read, and
+// every read on which a check of block_hist_medians fails, untouched: k_normalize's own code.
+template <class RT>
+__global__ __launch_bounds__(SEL_NT, 4) void k_normalize_hist(ReadState *rs, const DevParams *dp,
+    const RT *raw, double *norm, int mode)
+{
+    __shared__ BucketSmem sm;
+    ReadState &r = rs[blockIdx.x];
+    if (r.status != TBA_OK) return;
+    const tba_opts &o = dp->o;
+    const i64 n = r.n_raw;
+    if (!batch_has_medians(o, mode) || !norm_needs_medians(r, o, mode) || n < NORM_WINDOW_MIN) return;
+    const RawSamples<RT> x{raw + r.raw_off};
+    double smn, smx;
+    norm_sample_range(x, n, &sm, &smn, &smx);
+    const bool thresh = o.has_outlier_thresh && mode != 1; // (k_normalize's `thresh` without a const scale)
+    HistMedians hm;
+    if (!block_hist_medians(x, n, smn, smx, thresh, norm + r.raw_off, &sm, &hm)) return;
+    if (threadIdx.x == 0) {
+        r.shift = hm.shift; r.scale = hm.scale;
+        r.lower = thresh ? hm.med - (hm.mad * o.outlier_thresh) : 0.0;
+        r.upper = thresh ? hm.med + (hm.mad * o.outlier_thresh) : 0.0;
+        r.has_lims = thresh ? 1 : 0;
+        r.norm_form = TBA_NORM_FORM_HIST;
+    }
+}
 
 template <class RT>
 // (second launch bound = wavefronts per SIMD the register allocation must leave room for: these
@@ -40,6 +115,8 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_normalize(ReadState *rs, const De
     double xlo = 0, xhi = 0, mn = 0, mx = 0; // middle order statistics / range of the raw signal
     bool have_lims = false, have_dev = false;
     double dlo = 0, dhi = 0; // middle order statistics of |x - shift|
+    // (the conditions of the first two branches are restated in norm_needs_medians above, for k_normalize_hist:
+    // change them there too)
     if (r.sv_flags & 1) {
         shift = sv_in[4 * blockIdx.x + 0];
         scale = sv_in[4 * blockIdx.x + 1];
@@ -47,6 +124,9 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_normalize(ReadState *rs, const De
     } else if (mode == 1 && !o.has_const_scale && o.use_rna_event_scale) {
         // get_scale_values_from_events result, tombo_stats.py:217-233
         shift = r.shift; scale = r.scale; have_lims = true; lo = r.lower; hi = r.upper;
+    } else if (r.norm_form == TBA_NORM_FORM_HIST) {
+        // k_normalize_hist found the medians (and left the limits as they are computed below)
+        shift = r.shift; scale = r.scale; have_lims = r.has_lims != 0; lo = r.lower; hi = r.upper;
     } else {
         // strided sample, kept in registers: range guess for the selects and window steering
         double samp[WS_PER];
@@ -84,6 +164,7 @@ __global__ __launch_bounds__(SEL_NT, 4) void k_normalize(ReadState *rs, const De
             }
             __syncthreads();
         }
+        if (tid == 0) r.norm_form = have_med ? TBA_NORM_FORM_INT_COUNT : TBA_NORM_FORM_SELECT;
         // Up to three medians over the signal, one call site (a loop the compiler must not unroll:
         // three inlined copies of the selects cost 40 VGPRs and a workgroup per CU):
         //   what 0: np.median(x) -> shift;   what 1: np.median(|x - shift|) -> scale (mad);

@@ -809,6 +809,259 @@ __device__ bool block_int_medians(XS x, i64 n, int vmin_s, int vmax_s, BucketSme
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------
+// All the medians of the float normalisation -- np.median(x), np.median(|x - shift|) and, for the
+// outlier limits, np.median(|norm - np.median(norm)|) -- from TWO passes over the samples: the float
+// analogue of block_int_medians.
+//   Pass A counts the samples in BS_NB uniform buckets over [smn, smx] (bs_bucket: monotone; values
+//   outside fall into the edge buckets); one LDS atomic per sample, no ballots, no list.
+//   Bracket (counts only).  The buckets bl <= bh of the two middle ranks of x are known exactly, so
+//   the centre of every deviation lies in them (the third median's centre is shift + med * scale,
+//   med a few 1e-16).  With U(s) = samples in buckets bl - s .. bh + s, the half width s* of the
+//   value window that holds the middle-ranked deviation obeys s1 - 1 < s* <= s1' + 1 (in bucket
+//   widths), s1 / s1' the smallest s with U(s) >= (n - 1) / 2 + 1 and >= n / 2 + 1: the window's
+//   edges lie in the buckets [bl - s1' - 1, bh - s1 + 1] and [bl + s1 - 1, bh + s1' + 1].
+//   Pass B appends the members of those two brackets and of bl .. bh to `list` (NH_CAP doubles of
+//   global scratch; wave-aggregated appends): a fraction of a percent of a nanopore read.
+//   Resolve (no signal access): the middle order statistics of x are selected among the listed
+//   members of bl .. bh, ranks offset by the count below; the middle-ranked values of a deviation
+//   d = |g(x)|, g non-decreasing, among the listed bracket members, ranks offset by the count of
+//   the buckets strictly between the brackets.  That is right iff every sample between the brackets
+//   deviates at most as much as the selected values and every sample outside them at least as much,
+//   and g's monotonicity reduces both to the listed extremes: with mL / mR the innermost and oL / oR
+//   the outermost listed bracket members, g(mL) <= 0 <= g(mR) (zero crossing inside), d(mL), d(mR) <=
+//   the lower middle value, d(oL), d(oR) >= the upper one.  The bucket arithmetic only proposes;
+//   these comparisons of values the reference itself computes decide.
+// Returns false -- the caller runs the generic selects -- when any of it does not hold: a NaN, middle
+// ranks more than a bucket apart, brackets that touch the middle buckets (massive ties) or leave the
+// histogram, an empty bracket, a list beyond NH_CAP, a rank outside the listed set, a failed value
+// check, a scale that is not positive.  All threads call; the result is uniform.
+#define NH_CAP 4096
+struct HistMedians { double shift, scale, med, mad; };
+struct NhPlan {
+    int bl, bh, la, lb, ra, rb, ok;
+    i64 c_below, c_inner, c_outl, c_outr, n_brk, n_list;
+};
+__device__ __forceinline__ bool nh_in(int b, int lo, int hi) { return (u32)(b - lo) <= (u32)(hi - lo); }
+
+// the two order statistics k_lo <= k_hi <= k_lo + 1 of { val(i) : i < m } (all threads call)
+template <class F>
+__device__ __forceinline__ void nh_two_kth(F val, i64 m, i64 k_lo, i64 k_hi, double lo, double hi, BucketSmem *sm,
+                                           double *a_out, double *b_out)
+{
+    const double a = block_kth(val, m, k_lo, lo, hi, sm);
+    const int found = sm->found;
+    const double nxt = sm->next;
+    __syncthreads();
+    double b = a;
+    if (k_hi != k_lo) {
+        if (found & 2) b = nxt;
+        else { b = block_kth(val, m, k_hi, lo, hi, sm); __syncthreads(); }
+    }
+    *a_out = a; *b_out = b;
+}
+
+template <class X>
+__device__ bool block_hist_medians(X x, i64 n, double smn, double smx, bool want_mad, double *list,
+                                   BucketSmem *sm, HistMedians *out)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    __shared__ NhPlan s_p;
+    __shared__ int s_b[4];
+    __shared__ u32 s_nl;
+    __shared__ double s_ext[4 * (SEL_NT / 64)];
+    if (!(smx > smn) || n > 0x7fffffff) return false;
+    const double hsc = (double)BS_NB / (smx - smn);
+    if (!(hsc < 1e300) || !(hsc > 0.0)) return false;
+    for (int b = tid; b < BS_NB; b += SEL_NT) sm->hist[b] = 0;
+    if (tid == 0) { s_nl = 0; s_p.ok = 1; }
+    __syncthreads();
+    // pass A: count
+    bool bad = false;
+    block_stream2<4>(n, x, [&](i64, double v) {
+        bad |= v != v;
+        atomicAdd(&sm->hist[bs_bucket(v, smn, hsc)], 1u);
+    });
+    if (bad) s_p.ok = 0;
+    __syncthreads();
+    // inclusive prefix of the counts, in place (n < 2^31): 8 bins per thread + wave / block scan
+    {
+        constexpr int per = BS_NB / SEL_NT;
+        u32 loc[per], c = 0;
+#pragma unroll
+        for (int q = 0; q < per; q++) { c += sm->hist[tid * per + q]; loc[q] = c; }
+        u32 inc = c;
+        for (int d = 1; d < 64; d <<= 1) {
+            const u32 t = (u32)__shfl_up((int)inc, d, 64);
+            if (lane >= d) inc += t;
+        }
+        if (lane == 63) sm->rad.red[tid >> 6] = inc;
+        __syncthreads();
+        u32 off = 0;
+        for (int w = 0; w < (tid >> 6); w++) off += (u32)sm->rad.red[w];
+        const u32 exc = off + inc - c;
+#pragma unroll
+        for (int q = 0; q < per; q++) sm->hist[tid * per + q] = exc + loc[q];
+    }
+    __syncthreads();
+    auto P = [&](int b) -> i64 { return b < 0 ? 0 : (i64)sm->hist[b < BS_NB - 1 ? b : BS_NB - 1]; };
+    const i64 k_lo = (n - 1) / 2, k_hi = n / 2;
+    for (int b = tid; b < BS_NB; b += SEL_NT) { // the buckets of the two middle ranks
+        const i64 lo_c = P(b - 1), hi_c = P(b);
+        if (lo_c <= k_lo && k_lo < hi_c) s_b[0] = b;
+        if (lo_c <= k_hi && k_hi < hi_c) s_b[1] = b;
+    }
+    __syncthreads();
+    {
+        const int bl = s_b[0], bh = s_b[1];
+        for (int s = tid; s < BS_NB; s += SEL_NT) { // s1, s1': U is non-decreasing in s, U(BS_NB - 1) = n
+            const i64 u = P(bh + s) - P(bl - s - 1), up = s ? P(bh + s - 1) - P(bl - s) : 0;
+            if (up < k_lo + 1 && u >= k_lo + 1) s_b[2] = s;
+            if (up < k_hi + 1 && u >= k_hi + 1) s_b[3] = s;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int bl = s_b[0], bh = s_b[1], s1 = s_b[2], s1p = s_b[3];
+        int la = bl - s1p - 1, rb = bh + s1p + 1;
+        const int lb = bh - s1 + 1, ra = bl + s1 - 1;
+        bool ok = s_p.ok && bh - bl <= 1 && lb < bl && ra > bh && lb >= 0 && ra <= BS_NB - 1;
+        la = la > 0 ? la : 0; rb = rb < BS_NB - 1 ? rb : BS_NB - 1;
+        if (ok) {
+            const i64 n_l = P(lb) - P(la - 1), n_m = P(bh) - P(bl - 1), n_r = P(rb) - P(ra - 1);
+            ok = n_l > 0 && n_r > 0 && n_l + n_m + n_r <= NH_CAP;
+            s_p.bl = bl; s_p.bh = bh; s_p.la = la; s_p.lb = lb; s_p.ra = ra; s_p.rb = rb;
+            s_p.c_below = P(bl - 1); s_p.c_inner = P(ra - 1) - P(lb);
+            s_p.c_outl = P(la - 1); s_p.c_outr = n - P(rb);
+            s_p.n_brk = n_l + n_r; s_p.n_list = n_l + n_m + n_r;
+        }
+        s_p.ok = ok;
+    }
+    __syncthreads();
+    if (!s_p.ok) return false;
+    const int bl = s_p.bl, bh = s_p.bh, la = s_p.la, lb = s_p.lb, ra = s_p.ra, rb = s_p.rb;
+    const i64 m = s_p.n_list;
+    // pass B: list the members of the middle buckets and of the two brackets
+    {
+        constexpr int WU = 4; // pair loads in flight per thread
+        const i64 np = (n + 1) >> 1;
+        for (i64 base = 0; base < np; base += (i64)WU * SEL_NT) {
+            double v[2 * WU];
+            bool okv[2 * WU];
+#pragma unroll
+            for (int u = 0; u < WU; u++) {
+                const i64 i = 2 * (base + (i64)u * SEL_NT + tid);
+                okv[2 * u] = i < n; okv[2 * u + 1] = i + 1 < n;
+                if (i + 1 < n) sig_pair(x, i, v[2 * u], v[2 * u + 1]);
+                else { v[2 * u] = x[i < n ? i : n - 1]; v[2 * u + 1] = v[2 * u]; }
+            }
+            u64 mk[2 * WU];
+            u32 tot = 0;
+#pragma unroll
+            for (int u = 0; u < 2 * WU; u++) {
+                const int b = bs_bucket(v[u], smn, hsc);
+                mk[u] = __ballot(okv[u] && (nh_in(b, la, lb) || nh_in(b, bl, bh) || nh_in(b, ra, rb)));
+                tot += (u32)__popcll(mk[u]);
+            }
+            if (tot) {
+                u32 b0 = 0;
+                if (lane == 0) b0 = atomicAdd(&s_nl, tot);
+                b0 = __shfl(b0, 0, 64);
+#pragma unroll
+                for (int u = 0; u < 2 * WU; u++) {
+                    const u32 pos = b0 + (u32)__popcll(mk[u] & ((1ull << lane) - 1ull));
+                    if (((mk[u] >> lane) & 1ull) && pos < NH_CAP) list[pos] = v[u];
+                    b0 += (u32)__popcll(mk[u]);
+                }
+            }
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    if ((i64)s_nl != m) return false; // (the same map over the same samples: cannot happen)
+    // the listed extremes of the two brackets
+    {
+        double o_l = INFINITY, m_l = -INFINITY, m_r = INFINITY, o_r = -INFINITY;
+        for (i64 i = tid; i < m; i += SEL_NT) {
+            const double v = list[i];
+            const int b = bs_bucket(v, smn, hsc);
+            if (nh_in(b, la, lb)) { o_l = v < o_l ? v : o_l; m_l = v > m_l ? v : m_l; }
+            else if (nh_in(b, ra, rb)) { m_r = v < m_r ? v : m_r; o_r = v > o_r ? v : o_r; }
+        }
+        for (int mm = 32; mm >= 1; mm >>= 1) {
+            const double a = shfl_xor_f64(o_l, mm), b2 = shfl_xor_f64(m_l, mm), c2 = shfl_xor_f64(m_r, mm),
+                         d2 = shfl_xor_f64(o_r, mm);
+            o_l = a < o_l ? a : o_l; m_l = b2 > m_l ? b2 : m_l; m_r = c2 < m_r ? c2 : m_r; o_r = d2 > o_r ? d2 : o_r;
+        }
+        if (lane == 0) {
+            double *e = s_ext + 4 * (tid >> 6);
+            e[0] = o_l; e[1] = m_l; e[2] = m_r; e[3] = o_r;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) { // (the values every thread needs below stay in LDS until they are used: registers)
+        double o_l = s_ext[0], m_l = s_ext[1], m_r = s_ext[2], o_r = s_ext[3];
+        for (int w = 1; w < SEL_NT / 64; w++) {
+            const double *e = s_ext + 4 * w;
+            o_l = e[0] < o_l ? e[0] : o_l; m_l = e[1] > m_l ? e[1] : m_l;
+            m_r = e[2] < m_r ? e[2] : m_r; o_r = e[3] > o_r ? e[3] : o_r;
+        }
+        s_ext[0] = o_l; s_ext[1] = m_l; s_ext[2] = m_r; s_ext[3] = o_r;
+    }
+    if (k_lo - s_p.c_inner < 0 || k_hi - s_p.c_inner >= s_p.n_brk) return false;
+    __syncthreads();
+    // Up to three selections among the listed values, one call site (a loop the compiler must not unroll):
+    //   what 0: the middle order statistics of x, among the members of the middle buckets;
+    //   what 1 / 2: those of |g(x)|, g = x - shift / (x - shift) / scale - med, among the bracket members,
+    //   followed by the value checks.
+    double xlo = 0, xhi = 0, shift = 0, dlo = 0, dhi = 0, scale = 1, med = 0, mad = 0;
+#pragma nounroll
+    for (int what = 0; what < 3; what++) {
+        if (what == 2) {
+            if (!want_mad) break;
+            // np.median(norm): the images of the middle samples (x -> (x - shift) / scale is monotone)
+            const double ylo = (xlo - shift) / scale, yhi = (xhi - shift) / scale;
+            med = (n & 1) ? ylo : (ylo + yhi) / 2.0;
+            if (med == 0.0) { // |norm - 0| is a monotone image of the deviations just ranked
+                const double m_lo = dlo / scale, m_hi = dhi / scale;
+                mad = (n & 1) ? m_lo : (m_lo + m_hi) / 2.0;
+                break;
+            }
+        }
+        auto g = [&](double v) { return what == 1 ? v - shift : (v - shift) / scale - med; };
+        auto val = [&](i64 i) {
+            const double v = list[i];
+            const int b = bs_bucket(v, smn, hsc);
+            if (what == 0) return nh_in(b, bl, bh) ? v : INFINITY;
+            return nh_in(b, la, lb) || nh_in(b, ra, rb) ? fabs(g(v)) : INFINITY;
+        };
+        const i64 c_off = what == 0 ? s_p.c_below : s_p.c_inner;
+        // bucket range for the select: the middle buckets / the brackets' distance from them (any range is right)
+        const double w_lo = (double)(s_b[2] > 2 ? s_b[2] - 2 : 0) / hsc, w_hi = (double)(s_b[3] + 3) / hsc;
+        const double r_lo = what == 0 ? smn + (double)bl / hsc : (what == 1 ? w_lo : w_lo / scale);
+        const double r_hi = what == 0 ? smn + (double)(bh + 1) / hsc : (what == 1 ? w_hi : w_hi / scale);
+        double a_lo, a_hi;
+        nh_two_kth(val, m, k_lo - c_off, k_hi - c_off, r_lo, r_hi, sm, &a_lo, &a_hi);
+        if (what == 0) {
+            xlo = a_lo; xhi = a_hi;
+            shift = (n & 1) ? xlo : (xlo + xhi) / 2.0;
+            continue;
+        }
+        const double g_l = g(s_ext[1]), g_r = g(s_ext[2]);
+        bool ok = g_l <= 0.0 && g_r >= 0.0 && fabs(g_l) <= a_lo && fabs(g_r) <= a_lo;
+        if (s_p.c_outl > 0) ok = ok && fabs(g(s_ext[0])) >= a_hi;
+        if (s_p.c_outr > 0) ok = ok && fabs(g(s_ext[3])) >= a_hi;
+        if (!ok) return false;
+        const double res = (n & 1) ? a_lo : (a_lo + a_hi) / 2.0;
+        if (what == 1) {
+            dlo = a_lo; dhi = a_hi; scale = res;
+            if (!(scale > 0.0)) return false;
+        } else mad = res;
+    }
+    out->shift = shift; out->scale = scale; out->med = med; out->mad = mad;
+    return true;
+}
+
 
 // sum of p[j0 .. j1) in index order (c_new_means adds sample by sample), the LDS loads issued eight
 // at a time: the adds are the only dependent chain (a plain loop waits one LDS round trip per

@@ -44,7 +44,8 @@ struct ReadState {
     i32 ed_form, tb_form;     // which kernels produced this read's change points / main traceback
     i32 strip_s0;             // first band cell of the centre strip k_dp keeps beside the move rows (-1: none; k_dp.h)
     i32 bad_seq;              // k_ref_levels on the side stream found a base outside ACGT (applied in stage order: k_seq_status)
-    i32 tb_verify_fail, pad1; // rows where k_tb_par_verify disagreed with the chunk-parallel traceback (k_tb_par.h; 0 expected)
+    i32 tb_verify_fail;       // rows where k_tb_par_verify disagreed with the chunk-parallel traceback (k_tb_par.h; 0 expected)
+    i32 norm_form;            // which code found this read's normalisation medians (TBA_NORM_FORM_*: TBA_GET_NORM_FORM)
                               // (TBA_ED_FORM_* / TBA_TB_FORM_*, include/tombo_amd.h: TBA_GET_ED_FORM / TBA_GET_TB_FORM)
     i64 n_taken;              // entries of the taken (score, position) list k_detect left
     double ed_min, ed_max;    // ... and the range of its scores

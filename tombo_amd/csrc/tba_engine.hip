@@ -675,12 +675,24 @@ static int run_prelude(Run &c, int first, int last)
     return 0;
 }
 
+// ts.normalize_raw_signal: float samples go through k_normalize_hist first (the medians of the reads it takes,
+// two passes over the signal), then k_normalize (every other read's medians, and the normalised signal).  A batch
+// with a const scale, or RNA with its scale values from the events, has no medians for the first kernel: not launched.
+static void launch_normalize(Run &c, int mode, int write_norm)
+{
+    if (batch_has_medians(c.O, mode)) {
+        if (c.rdt == TBA_RAW_F32) k_normalize_hist<float><<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, (float *)c.raw, c.norm, mode);
+        else if (c.rdt != TBA_RAW_I16) k_normalize_hist<double><<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, (double *)c.raw, c.norm, mode);
+    }
+    RAW_DISPATCH(c.rdt, (k_normalize<RT><<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, (RT *)c.raw, c.norm, c.sv_in, mode, write_norm)));
+}
+
 // The steps: what runs between the timing events ev[i] and ev[i + 1], in the order of STEPS below.
 static int step_normalize(Run &c)
 {
     // (with k_detect on the way its loader writes the normalised signal: k_normalize only finds the
     // scale values then, and normalises the long reads, which k_detect leaves to k_long.h)
-    if (!c.rna) RAW_DISPATCH(c.rdt, (k_normalize<RT><<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, (RT *)c.raw, c.norm, c.sv_in, 0, c.fused_detect && !c.wg_scan ? 2 : 1)));
+    if (!c.rna) launch_normalize(c, 0, c.fused_detect && !c.wg_scan ? 2 : 1);
     return 0;
 }
 static int step_cumsum(Run &c)
@@ -726,7 +738,7 @@ static int step_peaks(Run &c)
     if (c.rna) { // RNA normalises after event detection (segment_signal, resquiggle.py:1073-1098)
         RAW_DISPATCH(c.rdt, (k_event_means<RT, 1280><<<dim3(c.gE, c.nb), 256, 0, c.s>>>(c.rs, c.dp, (RT *)c.raw, c.cpts, c.evm, 1)));
         k_rna_event_scale<<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, c.evm);
-        RAW_DISPATCH(c.rdt, (k_normalize<RT><<<c.nb, SEL_NT, 0, c.s>>>(c.rs, c.dp, (RT *)c.raw, c.norm, c.sv_in, 1, 1)));
+        launch_normalize(c, 1, 1);
     }
     return 0;
 }
@@ -1155,6 +1167,7 @@ extern "C" int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_byt
     case TBA_GET_TB_PARALLEL: return PER_READ(i32, r.tb_done);
     case TBA_GET_ED_FORM: return PER_READ(i32, r.ed_form);
     case TBA_GET_TB_FORM: return PER_READ(i32, r.tb_form);
+    case TBA_GET_NORM_FORM: return PER_READ(i32, r.norm_form);
     case TBA_GET_TB_VERIFY_FAIL: return PER_READ(i32, r.tb_verify_fail);
     case TBA_GET_DP_WORKGROUP: return PER_READ(i32, r.dp_wg);
     case TBA_GET_ED_N_TAKEN: return PER_READ(i64, r.n_taken);

@@ -30,6 +30,8 @@ int main()
 {
     report("k_normalize<double>", k_normalize<double>, SEL_NT);
     report("k_normalize<int16_t>", k_normalize<int16_t>, SEL_NT);
+    report("k_normalize_hist<double>", k_normalize_hist<double>, SEL_NT);
+    report("k_normalize_hist<float>", k_normalize_hist<float>, SEL_NT);
     report("k_cumsum_scores<20>", k_cumsum_scores<20>, 256);
     report("k_cumsum_scores<32>", k_cumsum_scores<32>, 256);
     report("k_scores_ttest<double>", k_scores_ttest<double>, 256);
