@@ -167,6 +167,20 @@ int  tba_engine_last_side_stream(tba_engine *e);
 /* whether the last run launched k_dp8_lowreg, the register-capped build of the 8-cell forward pass, in place of
  * k_dp<8> (the choice tba_engine_set_sharing describes; per read: TBA_GET_DP_FORM) */
 int  tba_engine_last_dp_lowreg(tba_engine *e);
+/* The forward pass divides by the level's sd.  Where every sd of the model (tba_set_model) is a divisor for which
+ * the two-operation form fma(a, yh, a * yl) -- yh + yl the reciprocal as a pair -- is proven to BE IEEE division,
+ * for every dividend, the batch form of the forward pass uses it (k_dp_cdiv: same results bit for bit, fewer float64
+ * operations); a batch whose sds came through TBA_PUT_REF_SDS, a main pass on k_dp8_lowreg and the per-kernel C
+ * entries keep the general division.
+ * tba_engine_last_dp_const_division: bit 0 -- the last run's main forward pass took it, bit 1 -- start discovery did.
+ * tba_engine_set_dp_const_division: mode 1 (default) as above, 0 never; from the next run.
+ * tba_engine_model_const_division: 1 when the model's table is proven.
+ * tba_prove_const_division: host only, no device needed: proven[i] = 1 when the form is proven for sd[i], else 0
+ * (not finite, not positive, subnormal, outside [2^-256, 2^256], an all-ones significand: 0). */
+int  tba_engine_last_dp_const_division(tba_engine *e);
+int  tba_engine_set_dp_const_division(tba_engine *e, int mode);
+int  tba_engine_model_const_division(tba_engine *e);
+int  tba_prove_const_division(const double *sd, int64_t n, int32_t *proven);
 /* TBA_ED_FORM_* of the last tba_c_valid_cpts_w_cap / tba_c_valid_cpts_w_cap_t_test call on this engine
  * (those entries follow the engine's dispatch like a batch of one read) */
 int  tba_c_last_ed_form(tba_engine *e);
@@ -906,6 +920,11 @@ int tba_selftest_division(tba_engine *e, const double *a, const double *b, int64
  * tombo_stats.py:401-425); its relative error must stay far inside the 1e-5 guard band */
 int tba_selftest_approx_quotient(tba_engine *e, const double *a, const double *b, int64_t n,
                                  double *out);
+/* self-test of the two-operation division (tba_engine_last_dp_const_division), the reciprocal pair of b[i] made
+ * as the forward pass makes it; out has 3 n values: out[i] the quotient of a[i] by b[i], out[n + i] the cell's
+ * z_shift - min(|quotient|, zcap) from it, out[2 n + i] the same from the general division */
+int tba_selftest_const_division(tba_engine *e, const double *a, const double *b, int64_t n,
+                                double z_shift, double zcap, double *out);
 
 #ifdef __cplusplus
 }

@@ -195,6 +195,10 @@ def _prototypes():
         'tba_engine_set_side_stream': (n, [v, n]),
         'tba_engine_last_side_stream': (n, [v]),
         'tba_engine_last_dp_lowreg': (n, [v]),
+        'tba_engine_last_dp_const_division': (n, [v]),
+        'tba_engine_set_dp_const_division': (n, [v, n]),
+        'tba_engine_model_const_division': (n, [v]),
+        'tba_prove_const_division': (n, [cD, q, I]),
         'tba_c_last_ed_form': (n, [v]),
         'tba_set_model': (n, [v, cD, cD, q, q]),
         # ---- host memory for streaming ----
@@ -288,6 +292,7 @@ def _prototypes():
         'tba_selftest_subsample': (n, [v, q, u, q, q, Q]),
         'tba_selftest_division': (n, [v, cD, cD, q, D]),
         'tba_selftest_approx_quotient': (n, [v, cD, cD, q, D]),
+        'tba_selftest_const_division': (n, [v, cD, cD, q, d, d, D]),
     }
 
 
@@ -327,6 +332,15 @@ def _call(L, name, *args):
     rc = getattr(L, name)(*args)
     if rc != 0:
         raise EngineError('%s failed (%d): %s' % (name, rc, L.tba_last_error().decode()))
+
+
+def prove_const_division(sds):
+    """bool[n]: for which of the divisors `sds` the forward pass's two-operation division is proven to be IEEE
+    division for every dividend (tba_prove_const_division: host code, no device needed)"""
+    sds = np.ascontiguousarray(sds, dtype=np.float64).ravel()
+    out = np.zeros(sds.shape[0], dtype=np.int32)
+    _call(lib(), 'tba_prove_const_division', sds, sds.shape[0], out)
+    return out.astype(bool)
 
 
 def _f64(a):
@@ -1086,6 +1100,29 @@ class Engine(object):
     def last_dp_lowreg(self):
         """whether the last run launched k_dp8_lowreg in place of k_dp<8> (tba_engine_last_dp_lowreg)"""
         return bool(self._L.tba_engine_last_dp_lowreg(self._h))
+
+    def last_dp_const_division(self):
+        """(main pass, start discovery): whether the last run's forward passes took k_dp_cdiv, the two-operation
+        division by a proven sd (tba_engine_last_dp_const_division)"""
+        bits = self._L.tba_engine_last_dp_const_division(self._h)
+        return bool(bits & 1), bool(bits & 2)
+
+    def set_dp_const_division(self, auto=True):
+        """True (default): batches of a proven model run k_dp_cdiv; False: never (tba_engine_set_dp_const_division)"""
+        self._call('tba_engine_set_dp_const_division', 1 if auto else 0)
+
+    def selftest_const_division(self, a, b, z_shift, zcap):
+        """float64[3][n] of tba_selftest_const_division: the two-operation quotients a / b, the cell values
+        z_shift - min(|q|, zcap) from them, and the same cell values from the general division"""
+        a, b = _f64(a), _f64(b)
+        assert a.ndim == 1 and a.shape == b.shape and a.shape[0] >= 1
+        out = np.empty(3 * a.shape[0], dtype=np.float64)
+        self._call('tba_selftest_const_division', a, b, a.shape[0], float(z_shift), float(zcap), out)
+        return out.reshape(3, -1)
+
+    def model_const_division(self):
+        """whether every sd of the uploaded model is a proven divisor (tba_engine_model_const_division)"""
+        return bool(self._L.tba_engine_model_const_division(self._h))
 
     def get_dispatch(self):
         a, b = i64(0), i64(0)

@@ -45,6 +45,20 @@ __global__ void k_c_div_check(const double *a, const double *b, i64 n, double *o
     }
 }
 
+// self-test of the two-operation division of k_dp_cdiv (div_const2, tba_common.h), reciprocal pair made as
+// load_levels makes it: out[i] the quotient, out[n + i] the cell's z = z_shift - min(|q|, zcap) from it,
+// out[2 n + i] the same z from div_by_recip
+__global__ void k_c_div_const_check(const double *a, const double *b, i64 n, double z_shift, double zcap, double *out)
+{
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
+        const double y = 1.0 / b[i], yl = recip_low(b[i], y);
+        const double q2 = div_const2(a[i], y, yl), q5 = div_by_recip(a[i], b[i], y);
+        out[i] = q2;
+        out[n + i] = z_shift - __builtin_fmin(fabs(q2), zcap);
+        out[2 * n + i] = z_shift - __builtin_fmin(fabs(q5), zcap);
+    }
+}
+
 // self-test of the approximate quotient k_theil_sen classifies pairs with: a * r, r =
 // v_rcp_f64(b) refined by one Newton step
 __global__ void k_c_rcp_check(const double *a, const double *b, i64 n, double *out)

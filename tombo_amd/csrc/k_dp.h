@@ -239,7 +239,10 @@ __device__ __forceinline__ double shift_cells(double (&Q)[CPL])
 template <bool B> struct BoolTag { static constexpr bool value = B; };
 template <int I> struct IntTag { static constexpr int value = I; };
 
-template <int CPL, bool DIRECT>
+// CDIV: the rows divide by their sd in two operations, div_const2 (tba_common.h) -- only for batches whose every sd
+// the host has proven (div_const_proof.h; the engine's choice, k_dp_cdiv below).  The lane register that holds sd
+// then holds the low word of its reciprocal: a row reads mu, yh, yl.
+template <int CPL, bool DIRECT, bool CDIV = false>
 // Waves per SIMD the register allocation of the classes up to 8 cells per lane is held to: 4 (128
 // VGPRs; k_dp<8> comes out at 133 without it since the row loop exists twice).  -DTBA_DP_WAVES=5 (96
 // VGPRs) was measured SLOWER, 70.4 against 65.6 ms at W = 500: the squeeze costs instructions and
@@ -419,13 +422,14 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
     __syncthreads();
 
     // expected level, sd and its reciprocal of 64 rows at a time: lane l holds row blk0 + l
-    // (one coalesced load and one true division per 64 rows), a row reads its lane
+    // (one coalesced load and one true division per 64 rows), a row reads its lane.  CDIV: sd_v is yl.
     double mu_v = 0, sd_v = 1, y_v = 1;
     auto load_levels = [&](int first) {
         int rc = first + lane;
         rc = rc < n_rows ? rc : n_rows - 1;
         mu_v = rmu[rc]; sd_v = rsd[rc];
         y_v = 1.0 / sd_v;
+        if constexpr (CDIV) sd_v = recip_low(sd_v, y_v);
         // the loads end HERE, once per 64 rows: left pending, the rows' read of these registers
         // sits behind a conditional load and the compiler guards it with s_waitcnt vmcnt(0) in
         // EVERY row (which on gfx9 also waits for the previous row's stores)
@@ -508,7 +512,7 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
             const double *er = ring + ((cur_start + RING + b0) & (RING - 1)); // + j < RING + CPL
 #pragma unroll
             for (int j = 0; j < CPL; j++) {
-                double pz = fabs(div_by_recip(er[j] - mu, sd, y));
+                double pz = fabs(CDIV ? div_const2(er[j] - mu, y, sd) : div_by_recip(er[j] - mu, sd, y));
                 pz = __builtin_fmin(pz, zcap);
                 z[j] = zs[j] - pz; // cells past the band: -inf - pz = -inf, stays -inf for good
             }
@@ -721,6 +725,13 @@ template <int CPL, bool DIRECT>
 __global__ __launch_bounds__(64) TBA_DP_WAVES_ATTR void k_dp(TBA_DP_ARGS)
 {
     dp_body<CPL, DIRECT>(TBA_DP_PASS);
+}
+// The batch form with the two-operation division (dp_body's CDIV): 24 float64 operations less per row of the
+// 8-cell class.  Kernels of their own: k_dp<CPL, DIRECT> keeps its name, its code and its register budget.
+template <int CPL>
+__global__ __launch_bounds__(64) TBA_DP_WAVES_ATTR void k_dp_cdiv(TBA_DP_ARGS)
+{
+    dp_body<CPL, false, true>(TBA_DP_PASS);
 }
 // The batch form of the 8-cell class (W = 500) under a register budget of 112 instead of 128
 // (amdgpu_num_vgpr counts in units of two on gfx90a+: 56; it takes no template-dependent value,

@@ -145,6 +145,17 @@ __device__ __forceinline__ double div_by_recip2(double a, double b, double yh, d
 }
 __device__ __forceinline__ double recip_low(double b, double yh) { return __builtin_fma(-b, yh, 1.0) * yh; }
 
+// The same quotient in TWO instructions, div_by_recip2 without its correction: RN(a yh + RN(a yl)) is within
+// 1.5 * 2^-105 of a / b before the rounding, so it IS RN(a / b) except for the few dividends whose quotient lies
+// that close to a rounding boundary -- and for a given b those can be listed and tried.  div_const_proof.h does
+// that on the host for the divisors of a level model (tba_set_model); k_dp_cdiv (k_dp.h) is launched only where
+// every divisor of the batch passed.  The divisor itself is not an operand: a row carries mu, yh, yl.
+__device__ __forceinline__ double div_const2(double a, double yh, double yl)
+{
+    const double p = a * yl;
+    return __builtin_fma(a, yh, p);
+}
+
 // Lanes of ONE wavefront handing values to each other through GLOBAL memory (k_main_tb_par: read_tb
 // entries between the lanes of a read; k_skip_dp_wave: the boundaries lane 0 found).
 // __threadfence_block() / __syncthreads() are not the fence for that in a workgroup of a single

@@ -3,6 +3,7 @@
 // SoA buffers that stay resident in HBM between upload and download.
 #include <atomic>
 #include "tba_common.h"
+#include "div_const_proof.h"
 #include "k_select.h"
 #include "k_segment.h"
 #include "k_detect.h"
@@ -31,6 +32,7 @@
 #include <cstring>
 #include <string>
 #include <type_traits>
+#include <unordered_set>
 #include <vector>
 
 static thread_local std::string g_last_error;
@@ -128,6 +130,10 @@ struct tba_engine {
     size_t n_segs() const { return (size_t)(z.B_tot + n_reads); } // segment boundaries of the batch: B + 1 per read
     bool any_stall = false, have_samp = false, have_sv = false;
     std::vector<i64> ne_override; // per-read num_events for the next upload (stepwise API)
+    // The two-operation division of the forward pass (k_dp_cdiv, k_dp.h): model_cdiv -- every sd of the level table
+    // is proven (div_const_proof.h, tba_set_model); refs_put -- the batch's d_refs came from the caller
+    // (TBA_PUT_REF_SDS), not from the table; cdiv_auto -- tba_engine_set_dp_const_division
+    bool model_cdiv = false, refs_put = false, cdiv_auto = true;
     int n_sharing = 1;            // engines fed concurrently on this device (tba_engine_set_sharing)
     int side_mode = -1;           // tba_engine_set_side_stream: -1 by the engines alive, 0 never, 1 always
     bool last_side = false;       // the last full run used the side stream
@@ -135,6 +141,7 @@ struct tba_engine {
     // stage clears them, a stage that runs records its own.
     struct DpLaunches {
         bool start = false, main = false, lowreg = false, wide = false;
+        bool cdiv_main = false, cdiv_start = false; // k_dp_cdiv took the main pass / start discovery (dp_cdiv)
         int retry_wcpl = 0;       // class of the retry's k_dp_wg; 0: k_dp<class of start_save_bw> in retry mode
     } last_dp;
     // latency / throughput forms of event detection and traceback (tba_engine_set_dispatch)
@@ -213,6 +220,33 @@ extern "C" void tba_engine_destroy(tba_engine *e)
     delete e;
 }
 
+// Whether every value of a level table's sd column is a proven divisor of the two-operation division.  The
+// prover runs once per DISTINCT value (Tombo's DNA and RNA models have one each: microseconds); a table with more
+// than TBA_CDIV_MAX_DISTINCT of them is left unproven rather than paid for.
+#define TBA_CDIV_MAX_DISTINCT 4096
+static bool sds_all_proven(const double *sds, size_t n)
+{
+    std::unordered_set<u64> seen; // (bit patterns: -0.0, NaNs and the like stay apart and fail the prover one by one)
+    u64 last = 0;
+    for (size_t i = 0; i < n; i++) {
+        u64 b;
+        memcpy(&b, sds + i, 8);
+        if (i > 0 && b == last) continue;
+        last = b;
+        if (seen.count(b)) continue;
+        if (seen.size() >= TBA_CDIV_MAX_DISTINCT || !div_const_proof::proven(sds[i])) return false;
+        seen.insert(b);
+    }
+    return n > 0;
+}
+
+extern "C" int tba_prove_const_division(const double *sd, int64_t n, int32_t *proven)
+{
+    if (n < 0 || (n > 0 && (!sd || !proven))) return set_err(TBA_E_ARG, "bad arguments");
+    for (int64_t i = 0; i < n; i++) proven[i] = div_const_proof::proven(sd[i]);
+    return 0;
+}
+
 extern "C" int tba_set_model(tba_engine *e, const double *kmer_means, const double *kmer_sds,
                              int64_t kmer_width, int64_t central_pos)
 {
@@ -227,6 +261,7 @@ extern "C" int tba_set_model(tba_engine *e, const double *kmer_means, const doub
     e->hp.kmer_width = kmer_width;
     e->hp.central_pos = central_pos;
     e->have_model = true;
+    e->model_cdiv = sds_all_proven(kmer_sds, n);
     // a batch uploaded under another model has stale per-read geometry (B depends on K)
     e->have_batch = e->ran = e->finished = false;
     return 0;
@@ -521,6 +556,7 @@ extern "C" int tba_batch_upload_async(tba_engine *e, const tba_params *p, const 
         HIP_TRY(hipGetLastError());
     }
     e->have_batch = true;
+    e->refs_put = false;
     return 0;
 }
 
@@ -548,6 +584,9 @@ extern "C" int tba_set_num_events(tba_engine *e, const int64_t *num_events, int6
 // this one (streaming slots) and the batch has more than 0.04 samples per DP cell, i.e. event
 // detection and normalisation, not the DP, are most of the work (RNA 3 kb: 0.087, DNA 10 kb: 0.018)
 static bool dp_lowreg(const tba_engine *e) { return e->n_sharing > 1 && e->z.cells > 0 && (double)e->z.S_tot > 0.04 * e->z.cells; }
+// k_dp<CPL> or k_dp_cdiv<CPL>, the two-operation division: the latter when every sd the rows can meet is a proven
+// divisor, i.e. the model's table is and d_refs was filled from it (k_ref_levels copies the table's values)
+static bool dp_cdiv(const tba_engine *e) { return e->cdiv_auto && e->model_cdiv && !e->refs_put; }
 
 // ---- the pipeline -----------------------------------------------------------------------------
 // One run over the uploaded batch, as its steps see it: the engine, its streams, the grid sizes, the kernel
@@ -601,7 +640,9 @@ struct Run {
 template <int CPL>
 static void launch_dp_t(Run &c, int mode)
 {
-    const auto k = CPL == 8 && mode == DP_MAIN && dp_lowreg(c.e) ? k_dp8_lowreg : k_dp<CPL, false>;
+    // (a main pass under k_dp8_lowreg's selector stays on the general division in every class: step_main_dp)
+    const bool lowreg = mode == DP_MAIN && dp_lowreg(c.e);
+    const auto k = CPL == 8 && lowreg ? k_dp8_lowreg : dp_cdiv(c.e) && !lowreg ? k_dp_cdiv<CPL> : k_dp<CPL, false>;
     k<<<dim3(c.nb), dim3(64), 0, c.s>>>(c.rs, c.dp, mode, c.evm, c.refm, c.refs, c.bst, c.lo, c.hi, mode == DP_MAIN ? c.moves : c.smoves, c.e->z.start_moves_stride, c.lastrow, nullptr);
 }
 template <int CPL, int RPW>
@@ -670,6 +711,7 @@ static int run_prelude(Run &c, int first, int last)
         HIP_TRY(hipEventRecord(e->ev_stalls, s2));
         // the expected levels need the sequence and the model only
         k_ref_levels<<<dim3(c.gB, c.nb), 256, 0, s2>>>(c.rs, c.dp, c.seq, c.kmeans, c.ksds, c.refm, c.refs, 1);
+        e->refs_put = false;
         HIP_TRY(hipEventRecord(e->ev_levels, s2));
     }
     return 0;
@@ -753,8 +795,10 @@ static int step_ref_levels(Run &c)
     if (c.side) {                                                  // (computed on the side stream)
         HIP_TRY(hipStreamWaitEvent(c.s, c.e->ev_levels, 0));
         k_seq_status<<<c.tpr, 64, 0, c.s>>>(c.rs, c.n);
-    } else
+    } else {
         k_ref_levels<<<dim3(c.gB, c.nb), 256, 0, c.s>>>(c.rs, c.dp, c.seq, c.kmeans, c.ksds, c.refm, c.refs);
+        c.e->refs_put = false;                                     // (d_refs holds the table's values again)
+    }
     return 0;
 }
 static void launch_start_tb(Run &c, int mode)
@@ -765,6 +809,7 @@ static void launch_start_tb(Run &c, int mode)
 static int step_start_dp(Run &c)
 {
     k_path0<<<c.tpr, 64, 0, c.s>>>(c.rs, c.n, c.dp);
+    c.e->last_dp.cdiv_start = dp_cdiv(c.e);
     launch_dp(c, cpl_class(c.P.start_bw), DP_START_TRY);
     launch_start_tb(c, DP_START_TRY);
     return 0;
@@ -791,6 +836,7 @@ static int step_main_dp(Run &c)
     const i64 wide_w = c.e->z.wide_w;
     c.e->last_dp.main = true, c.e->last_dp.wide = wide_w != 0;
     c.e->last_dp.lowreg = dp_lowreg(c.e); // (launch_dp_t's choice for the 8-cell class)
+    c.e->last_dp.cdiv_main = dp_cdiv(c.e) && !dp_lowreg(c.e); // (... and for every class)
     for (int cls : DpClasses::list) launch_dp(c, cls, DP_MAIN);
     const DpMultiClass m = dp_multi_class(c.P.bandwidth); // narrow adaptive bands: several reads per wavefront
     if (m.cpl == 4 && m.rpw == 2) launch_dp_multi_t<4, 2>(c);
@@ -968,7 +1014,7 @@ extern "C" int tba_batch_put(tba_engine *e, int what, const void *data, int64_t 
     case TBA_PUT_EVENT_MEANS: rc = put(e->d_evm, (size_t)e->z.E_tot * 8); break;
     case TBA_PUT_NORM: rc = put(e->d_norm, (size_t)e->z.S_tot * 8); break;
     case TBA_PUT_REF_MEANS: rc = put(e->d_refm, (size_t)e->z.B_tot * 8); break;
-    case TBA_PUT_REF_SDS: rc = put(e->d_refs, (size_t)e->z.B_tot * 8); break;
+    case TBA_PUT_REF_SDS: rc = put(e->d_refs, (size_t)e->z.B_tot * 8); e->refs_put = true; break; // (dp_cdiv: any divisor now)
     case TBA_PUT_DP_SEGS: // per_read[2i] = read_start_rel_to_raw, per_read[2i+1] = trimmed signal length
         if (!per_read) return set_err(TBA_E_ARG, "per_read (read_start, norm_len) required");
         if ((size_t)bytes < e->n_segs() * 8) return set_err(TBA_E_ARG, "segment array shorter than the batch");
@@ -2861,6 +2907,20 @@ extern "C" int tba_selftest_approx_quotient(tba_engine *e, const double *a, cons
     return c_div_selftest(e, k_c_rcp_check, a, b, n, out);
 }
 
+extern "C" int tba_selftest_const_division(tba_engine *e, const double *a, const double *b, int64_t n,
+                                           double z_shift, double zcap, double *out)
+{
+    if (!e || !a || !b || !out || n < 1) return set_err(TBA_E_ARG, "bad arguments");
+    Scratch sc(e);
+    const double *d_a = sc.in(a, n);
+    const double *d_b = sc.in(b, n);
+    double *d_o = sc.out<double>(3 * n);
+    if (sc.rc) return sc.rc;
+    k_c_div_const_check<<<grid_for(n), 256, 0, e->stream>>>(d_a, d_b, n, z_shift, zcap, d_o);
+    if (sc.sync()) return sc.rc;
+    return sc.get(out, d_o, 3 * n);
+}
+
 // ---- ts.identify_stalls (tombo_stats.py:269-368), one read, host buffers --------------------
 extern "C" int tba_identify_stalls(tba_engine *e, const void *raw, int raw_dtype, int64_t n,
     int64_t window_size, int64_t n_windows, int64_t mini_window_size, double threshold,
@@ -3202,6 +3262,21 @@ extern "C" int tba_engine_last_side_stream(tba_engine *e)
 extern "C" int tba_engine_last_dp_lowreg(tba_engine *e)
 {
     return e ? (e->last_dp.lowreg ? 1 : 0) : 0;
+}
+
+extern "C" int tba_engine_last_dp_const_division(tba_engine *e)
+{
+    return e ? (e->last_dp.cdiv_main ? 1 : 0) | (e->last_dp.cdiv_start ? 2 : 0) : 0;
+}
+extern "C" int tba_engine_set_dp_const_division(tba_engine *e, int mode)
+{
+    if (!e || mode < 0 || mode > 1) return set_err(TBA_E_ARG, "bad arguments");
+    e->cdiv_auto = mode == 1;
+    return 0;
+}
+extern "C" int tba_engine_model_const_division(tba_engine *e)
+{
+    return e && e->have_model && e->model_cdiv ? 1 : 0;
 }
 
 extern "C" int tba_engine_set_sharing(tba_engine *e, int n_engines)
