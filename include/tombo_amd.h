@@ -685,6 +685,36 @@ int tba_kmer_levels(tba_engine *e, const double *means, const uint8_t *codes,
     const int64_t *read_off, int64_t n_reads, int64_t kmer_width, int64_t central_pos,
     const uint8_t *completed, int64_t *out_counts, int64_t *out_lv_off, double *out_levels,
     int64_t levels_cap);
+/* K-mer level distributions (plot_kmer_dist, _plot_commands.py:451-559): which reads of a batch the plot
+ * takes, their levels grouped by k-mer and read, and the means the plot orders the k-mers by.
+ * means / codes / read_off and the windows as in tba_kmer_levels (a window with a code above 3 is skipped; a NaN
+ * level propagates); the reads are taken in the order given.  kmer_width K in [1, 9].
+ * A read is valid if kmer_thresh == 0, or if it shows all 4^K k-mers and (kmer_thresh == 1 or its rarest k-mer
+ * occurs MORE than kmer_thresh times -- the reference's comparison).  A read is examined while fewer than
+ * num_reads valid reads stand before it (the first read always is); an examined valid read is taken and gets
+ * the label 1, 2, ...: out_read_label[n_reads] (0: not taken), *out_n_sel the reads taken, *out_n_examined the
+ * reads examined.  A read shorter than K is valid under kmer_thresh == 0 and contributes nothing.
+ * Entries of a k-mer (index: first base most significant), in read order and inside a read in position order:
+ *   read_mean == 0  every level of the k-mer in the taken reads
+ *   read_mean != 0  per taken read that shows the k-mer, np.mean of its levels of the k-mer (np.add.reduce in
+ *                   numpy's order -- 8192-value blocks, pairwise from 8 values on -- divided by the count)
+ * out_counts[4^K]: entries per k-mer; out_off[4^K + 1]: their exclusive prefix.
+ * out_values NULL: the count form, nothing else is written (out_value_label and out_kmer_mean may be NULL).
+ * Else the fill form: out_values / out_value_label [out_off[k] .. out_off[k + 1]) = the entries of k-mer k and
+ * the labels of their reads; out_kmer_mean[4^K] = np.mean over the k-mer's entries as they stand in out_values
+ * (one contiguous run), NaN where there is none.  values_cap: the capacity of out_values and out_value_label
+ * (the windows of the batch, sum of max(len - K + 1, 0), always suffice); it is compared after the counting
+ * kernels, before any value is written.  No floating-point atomics: the same call gives the same bytes.
+ * out_kernel_ms (may be NULL): device time of the call's kernels.
+ * n_reads == 0 is valid: every count is 0, nothing is launched.
+ * TBA_E_ARG: NULL pointers other than those named optional, offsets that do not start at 0 or decrease, kmer_width
+ * outside [1, 9], central_pos outside [0, kmer_width), 2^31 bases or more, 4^K * n_reads above 2^27 (the dense
+ * per-read table), values_cap too small.  Nothing is launched for any of these but the last. */
+int tba_kmer_dist(tba_engine *e, const double *means, const uint8_t *codes, const int64_t *read_off,
+    int64_t n_reads, int64_t kmer_width, int64_t central_pos, int64_t kmer_thresh, int64_t num_reads,
+    int read_mean, int64_t *out_read_label, int64_t *out_n_sel, int64_t *out_n_examined, int64_t *out_counts,
+    int64_t *out_off, double *out_values, int64_t *out_value_label, int64_t values_cap, double *out_kmer_mean,
+    double *out_kernel_ms);
 /* Gaussian kernel densities (est_kernel_density, :1914-1939).  levels: n_seg segments, CSR by
  * lv_off[n_seg + 1] (any order inside a segment; the input is not changed).
  * out_dens[s * n_x + g] = sum_i exp(-0.5 ((x[g] - l_i) / bandwidth)^2) / (n bandwidth sqrt(2 pi))

@@ -259,6 +259,7 @@ def _prototypes():
         'tba_pdist_lds_row_max': (q, []),
         # ---- alternate-base model estimation ----
         'tba_kmer_levels': (n, [v, cD, cB, cQ, q, q, q, cB, Q, Q, D, q]),
+        'tba_kmer_dist': (n, [v, cD, cB, cQ, q, q, q, q, q, n, Q, Q, Q, Q, Q, D, Q, q, D, D]),
         'tba_kde_eval': (n, [v, cD, cQ, q, cD, q, d, D]),
         # ---- genome tracks ----
         'tba_tracks_begin': (n, [v, q, q, n]),
@@ -376,6 +377,32 @@ def _check_kmer_levels_args(means, codes, read_off, kmer_width, central_pos, com
     if completed.shape != (4 ** int(kmer_width),):
         raise ValueError('completed must have 4**kmer_width entries')
     return np.ascontiguousarray(means), np.ascontiguousarray(codes), off, np.ascontiguousarray(completed)
+
+
+KMER_DIST_MAX_WIDTH = 9          # the widest k-mer of tba_kmer_dist
+KMER_DIST_TABLE_MAX = 1 << 27    # ... and the most 4**K * n_reads, its dense per-read table
+
+
+def _check_kmer_dist_args(means, codes, read_off, kmer_width, central_pos, kmer_thresh, num_reads):
+    """the argument checks of Engine.kmer_dist (shared with the tests' stand-in engine): dtypes are checked, not
+    converted -> contiguous (means, codes, read_off)"""
+    means, codes = np.asarray(means), np.asarray(codes)
+    if means.dtype != np.float64 or codes.dtype != np.uint8:
+        raise ValueError('means must be float64, codes uint8')
+    if int(kmer_width) != kmer_width or not 1 <= kmer_width <= KMER_DIST_MAX_WIDTH:
+        raise ValueError('kmer_width must be an integer in [1, %d]' % KMER_DIST_MAX_WIDTH)
+    if int(central_pos) != central_pos or not 0 <= central_pos < kmer_width:
+        raise ValueError('central_pos must be an integer in [0, kmer_width)')
+    if int(kmer_thresh) != kmer_thresh or int(num_reads) != num_reads:
+        raise ValueError('kmer_thresh and num_reads must be integers')
+    off = _check_offsets(read_off, 'read_off')
+    if means.ndim != 1 or codes.ndim != 1 or not (means.shape[0] == codes.shape[0] == int(off[-1])):
+        raise ValueError('per-base arrays and offsets disagree')
+    if int(off[-1]) >= 1 << 31:
+        raise ValueError('2**31 bases or more in one batch')
+    if 4 ** int(kmer_width) * (off.shape[0] - 1) > KMER_DIST_TABLE_MAX:
+        raise ValueError('4**kmer_width * n_reads is above the table limit of 2**27 entries')
+    return np.ascontiguousarray(means), np.ascontiguousarray(codes), off
 
 
 def _check_kde_eval_args(levels, lv_off, x, bandwidth):
@@ -1407,6 +1434,29 @@ class Engine(object):
         self._call('tba_kmer_levels', m, codes, off, off.shape[0] - 1, int(kmer_width), int(central_pos), done, counts,
                    lv_off, levels, cap)
         return counts, levels[:int(lv_off[-1])].copy(), lv_off
+
+    def kmer_dist(self, means, codes, read_off, kmer_width, central_pos, kmer_thresh, num_reads, read_mean):
+        """tba_kmer_dist, the count form and then the fill: which reads of the batch (means / codes CSR by read_off,
+        in the order given) plot_kmer_dist takes, and their levels by k-mer -> (read_label int64[n_reads] (1, 2, ...;
+        0: not taken), n_sel, n_examined, counts int64[4**K], off int64[4**K + 1], values float64, value_label int64,
+        kmer_mean float64[4**K]).  The entries of k-mer k are values[off[k]:off[k + 1]] in read order, then position
+        order: its levels, or with read_mean np.mean of them per read; value_label: the label of each entry's read;
+        kmer_mean: np.mean over the k-mer's entries, NaN where it has none.  `last_kmer_dist_kernel_ms`: kernel time
+        of both calls."""
+        m, codes, off = _check_kmer_dist_args(means, codes, read_off, kmer_width, central_pos, kmer_thresh, num_reads)
+        n_reads, n_kmers = off.shape[0] - 1, 4 ** int(kmer_width)
+        label = np.zeros(n_reads, dtype=np.int64)
+        counts, voff = np.empty(n_kmers, dtype=np.int64), np.empty(n_kmers + 1, dtype=np.int64)
+        n_sel, n_exam, ms0, ms1 = i64(0), i64(0), f64(0.0), f64(0.0)
+        head = (m, codes, off, n_reads, int(kmer_width), int(central_pos), int(kmer_thresh), int(num_reads),
+                int(bool(read_mean)), label, C.byref(n_sel), C.byref(n_exam), counts, voff)
+        self._call('tba_kmer_dist', *(head + (None, None, 0, None, C.byref(ms0))))
+        cap = int(voff[-1])
+        values, vlabel = np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.int64)
+        kmer_mean = np.empty(n_kmers, dtype=np.float64)
+        self._call('tba_kmer_dist', *(head + (values, vlabel, cap, kmer_mean, C.byref(ms1))))
+        self.last_kmer_dist_kernel_ms = ms0.value + ms1.value
+        return label, int(n_sel.value), int(n_exam.value), counts, voff, values, vlabel, kmer_mean
 
     def kde_eval(self, levels, lv_off, x, bandwidth):
         """tba_kde_eval: the Gaussian kernel density of every segment of `levels` (CSR by lv_off) on the grid x

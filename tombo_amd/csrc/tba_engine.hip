@@ -19,6 +19,7 @@
 #include "k_group.h"
 #include "k_site.h"
 #include "k_kde.h"
+#include "k_kmer_dist.h"
 #include "k_tracks.h"
 #include "k_kmer_est.h"
 #include "k_roc.h"
@@ -2320,6 +2321,127 @@ extern "C" int tba_kde_eval(tba_engine *e, const double *levels, const int64_t *
         n_seg, cov, has_nan, d_off, d_lv, d_x, n_x, bandwidth, d_dens);
     if (sc.sync()) return sc.rc;
     return sc.get(out_dens, d_dens, n_seg * n_x);
+}
+
+// ---- k-mer level distributions (k_kmer_dist.h): plot_kmer_dist, _plot_commands.py:451-559 ----
+#define KD_TABLE_MAX ((i64)1 << 27)   // 4^K * n_reads, the dense per-read table; also the most chunk counters
+extern "C" int tba_kmer_dist(tba_engine *e, const double *means, const uint8_t *codes, const int64_t *read_off,
+    int64_t n_reads, int64_t kmer_width, int64_t central_pos, int64_t kmer_thresh, int64_t num_reads,
+    int read_mean, int64_t *out_read_label, int64_t *out_n_sel, int64_t *out_n_examined, int64_t *out_counts,
+    int64_t *out_off, double *out_values, int64_t *out_value_label, int64_t values_cap, double *out_kmer_mean,
+    double *out_kernel_ms)
+{
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (!e || !read_off || !out_read_label || !out_n_sel || !out_n_examined || !out_counts || !out_off || n_reads < 0 ||
+        kmer_width < 1 || kmer_width > 9 || central_pos < 0 || central_pos >= kmer_width ||
+        (out_values && (!out_value_label || !out_kmer_mean || values_cap < 0)))
+        return set_err(TBA_E_ARG, "bad arguments");
+    const i64 n_kmers = (i64)1 << (2 * kmer_width);
+    if (const int rc = check_csr_off(read_off, n_reads)) return rc;
+    const i64 total = n_reads > 0 ? read_off[n_reads] : 0;
+    if (total >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "more than 2^31 - 1 bases in one batch");
+    if (total > 0 && (!means || !codes)) return set_err(TBA_E_ARG, "bad arguments");
+    if (n_reads > KD_TABLE_MAX / n_kmers) return set_err(TBA_E_ARG, "4^kmer_width * n_reads above 2^27");
+    *out_n_sel = *out_n_examined = 0;
+    if (n_reads == 0) {
+        for (i64 q = 0; q < n_kmers; q++) out_counts[q] = 0;
+        for (i64 q = 0; q <= n_kmers; q++) out_off[q] = 0;
+        if (out_values) for (i64 q = 0; q < n_kmers; q++) out_kmer_mean[q] = NAN;
+        return TBA_OK;
+    }
+    // chunks that never cross a read: the shortest multiple-of-64 length from 4096 on that keeps the chunk
+    // counters within KD_TABLE_MAX (a read has at least one chunk, n_reads of them always fit)
+    i64 chunk = 4096, max_len = 0;
+    for (i64 r = 0; r < n_reads; r++) max_len = std::max<i64>(max_len, read_off[r + 1] - read_off[r]);
+    auto count_chunks = [&](i64 c) { i64 n = 0; for (i64 r = 0; r < n_reads; r++) n += (read_off[r + 1] - read_off[r] + c - 1) / c; return n; };
+    while (chunk < max_len && count_chunks(chunk) > KD_TABLE_MAX / n_kmers) chunk *= 2;
+    std::vector<KdChunk> chunks;
+    std::vector<i64> read_chunk0(n_reads + 1);
+    for (i64 r = 0; r < n_reads; r++) {
+        read_chunk0[r] = (i64)chunks.size();
+        for (i64 p = read_off[r]; p < read_off[r + 1]; p += chunk) chunks.push_back(KdChunk{r, p, std::min<i64>(p + chunk, read_off[r + 1])});
+    }
+    read_chunk0[n_reads] = (i64)chunks.size();
+    const i64 n_chunks = (i64)chunks.size();
+
+    Scratch sc(e);
+    KdArgs a{};
+    a.n_reads = n_reads; a.n_chunks = n_chunks; a.n_kmers = n_kmers; a.K = (int)kmer_width; a.cp = (int)central_pos;
+    a.read_mean = read_mean != 0;
+    a.read_off = sc.in(read_off, n_reads + 1);
+    a.chunks = sc.in(chunks.data(), n_chunks);
+    a.codes = sc.in(codes, total);
+    a.means = sc.in(means, total);
+    const i64 *d_chunk0 = sc.in(read_chunk0.data(), n_reads + 1);
+    u32 *rows = sc.out<u32>(n_chunks * n_kmers), *tab = sc.out<u32>(n_reads * n_kmers);
+    u32 *distinct = sc.out<u32>(n_reads), *min_cnt = sc.out<u32>(n_reads);
+    i64 *d_label = sc.out<i64>(n_reads), *d_nsel = sc.out<i64>(2);
+    i64 *lvl_tot = sc.out<i64>(n_kmers), *ent_tot = sc.out<i64>(n_kmers);
+    i64 *lv_off = sc.out<i64>(n_kmers + 1), *ent_off = sc.out<i64>(n_kmers + 1);
+    if (sc.rc) return sc.rc;
+    double ms = 0.0;
+    const unsigned scan_x = (unsigned)std::min<i64>((n_kmers + 255) / 256, 64);
+    {
+        KernelTimer t(sc, out_kernel_ms != nullptr);
+        sc.zero(rows, n_chunks * n_kmers * sizeof(u32));
+        sc.zero(distinct, n_reads * sizeof(u32));
+        sc.hip(hipMemsetAsync(min_cnt, 0xff, n_reads * sizeof(u32), sc.stream), "hipMemsetAsync");
+        if (sc.rc) return sc.rc;
+        if (n_chunks > 0) k_kd_gather<false><<<(unsigned)n_chunks, 64, 0, sc.stream>>>(a, rows, nullptr, nullptr, nullptr, nullptr);
+        for (i64 r0 = 0; r0 < n_reads; r0 += 65535)   // (blockIdx.y holds 65535 reads)
+            k_kd_read_scan<<<dim3(scan_x, (unsigned)std::min<i64>(n_reads - r0, 65535)), 256, 0, sc.stream>>>(
+                n_kmers, d_chunk0 + r0, rows, tab + r0 * n_kmers, distinct + r0, min_cnt + r0);
+        k_kd_select<<<1, 64, 0, sc.stream>>>(n_reads, n_kmers, kmer_thresh, num_reads, distinct, min_cnt, d_label, d_nsel);
+        t.stop();
+        ms += t.ms();
+    }
+    i64 sel_out[2];
+    if (sc.sync() || sc.get(out_read_label, d_label, n_reads) || sc.get(sel_out, d_nsel, 2)) return sc.rc;
+    const i64 n_sel = *out_n_sel = sel_out[0];
+    *out_n_examined = sel_out[1];
+    std::vector<i64> sel(n_sel);   // the taken reads in label order: a copy, no arithmetic
+    for (i64 r = 0; r < n_reads; r++) if (out_read_label[r] > 0) sel[out_read_label[r] - 1] = r;
+    const i64 *d_sel = sc.in(sel.data(), n_sel);
+    if (sc.rc) return sc.rc;
+    {
+        KernelTimer t(sc, out_kernel_ms != nullptr);
+        k_kd_kmer_totals<<<grid_for(n_kmers), 256, 0, sc.stream>>>(n_kmers, n_sel, d_sel, tab, lvl_tot, ent_tot);
+        k_kmer_offsets<<<1, 64, 0, sc.stream>>>(n_kmers, lvl_tot, lv_off);
+        k_kmer_offsets<<<1, 64, 0, sc.stream>>>(n_kmers, ent_tot, ent_off);
+        t.stop();
+        ms += t.ms();
+    }
+    const i64 *d_counts = read_mean ? ent_tot : lvl_tot, *d_off = read_mean ? ent_off : lv_off;
+    i64 n_lv = 0;
+    if (sc.sync() || sc.get(out_counts, d_counts, n_kmers) || sc.get(out_off, d_off, n_kmers + 1) ||
+        sc.get(&n_lv, lv_off + n_kmers, 1))
+        return sc.rc;
+    if (out_kernel_ms) *out_kernel_ms = ms;
+    if (!out_values) return TBA_OK;
+    const i64 n_val = out_off[n_kmers];
+    if (n_val > values_cap) return set_err(TBA_E_ARG, "values_cap is smaller than the number of values");
+    double *d_lv = sc.out<double>(n_lv), *d_val = read_mean ? sc.out<double>(n_val) : d_lv;
+    i64 *d_vlabel = sc.out<i64>(n_val);
+    u32 *seg_start = read_mean ? sc.out<u32>(n_val) : nullptr, *seg_len = read_mean ? sc.out<u32>(n_val) : nullptr;
+    double *d_kmean = sc.out<double>(n_kmers);
+    if (sc.rc) return sc.rc;
+    a.n_lv = n_lv;
+    {
+        KernelTimer t(sc, out_kernel_ms != nullptr);
+        k_kd_seg_bases<<<grid_for(n_kmers), 256, 0, sc.stream>>>(n_kmers, n_sel, d_sel, tab, lv_off, ent_off, seg_start, seg_len, d_vlabel);
+        if (n_chunks > 0 && n_lv > 0)
+            k_kd_gather<true><<<(unsigned)n_chunks, 64, 0, sc.stream>>>(a, rows, d_label, tab, d_lv, read_mean ? nullptr : d_vlabel);
+        if (read_mean && n_val > 0)
+            k_kd_seg_means<<<(unsigned)std::min<i64>((n_val + 63) / 64, 65536), 64, 0, sc.stream>>>(n_val, seg_start, seg_len, d_lv, d_val);
+        k_kd_kmer_means<<<(unsigned)std::min<i64>(n_kmers, 65536), 64, 0, sc.stream>>>(n_kmers, d_off, d_val, d_kmean);
+        t.stop();
+        ms += t.ms();
+    }
+    if (sc.sync() || sc.get(out_values, d_val, n_val) || sc.get(out_value_label, d_vlabel, n_val) ||
+        sc.get(out_kmer_mean, d_kmean, n_kmers))
+        return sc.rc;
+    if (out_kernel_ms) *out_kernel_ms = ms;
+    return TBA_OK;
 }
 
 // ---- genome tracks (k_tracks.h): pileup sums and coverages, compaction, difference, top N --------

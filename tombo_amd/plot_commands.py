@@ -420,3 +420,275 @@ def two_samples_plot_data(plot_intervals, reads_index, ctrl_reads_index, overplo
     frames1 = get_plot_types_data((all_reg_data1, plot_types, overplot_thresh, 'Group1'), 0.1, engine=engine)
     frames2 = get_plot_types_data((all_reg_data2, plot_types, overplot_thresh, 'Group2'), 0.5, engine=engine)
     return tuple(_rbind(f1, f2) for f1, f2 in zip(frames1, frames2)) + (BasesData, Titles)
+
+
+# ---------------------------------------------------------------------------------------------
+# K-mer level distributions: `tombo plot kmer` (plot_kmer_dist, _plot_commands.py:451-559)
+KMER_DIST_NO_READS_ERROR = (
+    'No valid reads present.\n\t\tCheck that [--corrected-group] matches value used in resquiggle.\n\t\tAlso consider '
+    'lowering [--num-kmer-threshold] especially for k-mer lengths greater than 4.')
+KMER_DIST_FEW_READS_WARNING = (
+    'Fewer valid reads present than requested.\n\tConsider lowering [--num-kmer-threshold] especially for k-mer '
+    'lengths greater than 4.')
+
+
+def kmer_dist_plot_data(reads, read_mean, upstrm_bases, dnstrm_bases, kmer_thresh, num_reads, engine=None):
+    """plot_kmer_dist up to its R calls -> (kmerDat, baseDat, kmer_levels).  `reads`: objects with `means` and `seq`
+    (th.resquiggledRead), taken in the order given (the reference shuffles them first); a read whose `means` is None
+    is skipped.  kmerDat: Kmer, Base (kmer[upstrm_bases]), Signal, Read (the label of the entry's read, as a str);
+    baseDat: Kmer, Base, Position, the frame the reference builds when R has gridExtra; kmer_levels: the k-mers in
+    plot order, the levels of the Kmer factor.
+
+    All numbers come from ONE `Engine.kmer_dist` call (csrc/k_kmer_dist.h): which reads are taken, the levels of
+    every (k-mer, read) in position order, np.mean of each in numpy's summation order and the mean of every k-mer.
+    Ordering the at most 4**K k-mer means by (mean, k-mer) and putting the k-mers' runs of entries into that order are
+    copies without arithmetic and stay on the host.
+
+    Raises th.TomboError where the reference exits (no or one valid read) and warns where it warns (fewer valid reads
+    than asked).  ValueError: options outside 0..4, levels and bases that differ in number, a base outside ACGT or a
+    NaN level (the reference's result for those is a by-product of dict keys and of sorting NaNs), a batch whose
+    4**K * reads is above the engine's table limit of 2**27 entries."""
+    from .tombo_stats import encode_seq
+    for name, v in (('upstrm_bases', upstrm_bases), ('dnstrm_bases', dnstrm_bases)):
+        if int(v) != v or not 0 <= v <= 4:
+            raise ValueError('%s must be an integer in [0, 4]' % name)
+    upstrm_bases, dnstrm_bases = int(upstrm_bases), int(dnstrm_bases)
+    K = upstrm_bases + dnstrm_bases + 1
+    reads = [rd for rd in reads if rd.means is not None]
+    means = [np.asarray(rd.means, dtype=np.float64) for rd in reads]
+    codes = [encode_seq(rd.seq) for rd in reads]
+    for rd, m, c in zip(reads, means, codes):
+        if m.shape[0] != c.shape[0]:
+            raise ValueError('read %r: levels and bases differ in number' % (getattr(rd, 'read_id', None),))
+        if (c > 3).any():
+            raise ValueError('read %r: a base outside ACGT' % (getattr(rd, 'read_id', None),))
+        if np.isnan(m).any():
+            raise ValueError('read %r: a NaN level' % (getattr(rd, 'read_id', None),))
+    if 4 ** K * len(reads) > _native.KMER_DIST_TABLE_MAX:
+        raise ValueError('%d reads at k-mer width %d are above the table limit of 2**27 (4**K * reads) entries' % (
+            len(reads), K))
+    n_sel = 0
+    if reads:
+        _, n_sel, _, counts, off, values, vlabel, kmer_mean = _engine(engine).kmer_dist(
+            _cat(means, np.float64), _cat(codes, np.uint8),
+            np.concatenate([[0], np.cumsum([m.shape[0] for m in means])]).astype(np.int64),
+            K, upstrm_bases, kmer_thresh, num_reads, read_mean)
+    if n_sel in (0, 1):
+        raise th.TomboError(KMER_DIST_NO_READS_ERROR)
+    if n_sel < num_reads:
+        warnings.warn(KMER_DIST_FEW_READS_WARNING)
+
+    have = np.flatnonzero(counts)
+    order = have[np.lexsort((have, kmer_mean[have]))]     # (mean, k-mer string): index order is string order
+    kmer_levels = [''.join('ACGT'[(q >> (2 * (K - 1 - j))) & 3] for j in range(K)) for q in order.tolist()]
+    rows = _cat([np.arange(off[q], off[q + 1]) for q in order.tolist()], np.int64)
+    row_kmers = np.repeat(_strs(kmer_levels), counts[order])
+    kmerDat = OrderedDict([
+        ('Kmer', row_kmers), ('Base', np.repeat(_strs([kmer[upstrm_bases] for kmer in kmer_levels]), counts[order])),
+        ('Signal', values[rows]), ('Read', _strs([str(x) for x in vlabel[rows].tolist()]))])
+    baseDat = OrderedDict([
+        ('Kmer', np.repeat(_strs(kmer_levels), K)),
+        ('Base', _strs([kmer[i] for kmer in kmer_levels for i in range(K)])),
+        ('Position', np.tile(np.arange(K, dtype=np.int64) - upstrm_bases, len(kmer_levels)))])
+    return kmerDat, baseDat, kmer_levels
+
+
+# ---------------------------------------------------------------------------------------------
+# Model overlays and per-read statistic frames (_plot_commands.py:1034-1096, :1435-1652).  Host code only: k-mer
+# look-ups, slices and copies; the one computation, the read order of the per-read plots, is ts.order_reads, which
+# runs on the device.
+PLOT_PVAL_MAX, PLOT_LLR_MAX = 4, 4        # _default_parameters.py:197
+MODEL_KMER_POS_ERROR = 'Standard model not based on the same kmer position as alternative model.'
+
+
+def get_reg_kmers(std_ref, plot_intervals, reads_index, min_reg_overlap=None, alt_ref=None):
+    """-> (all_reg_model_data, all_reg_alt_model_data): per region (reg_id, strand, [(pos, mean, sd)] of the plus
+    strand, the same of the minus strand) from the standard model, and the alternate model's window round the plot
+    centre (_plot_commands.py:1435-1524).  The intervals get their reads and sequence as a side effect, as in the
+    reference.  std_ref is a ts.TomboModel (arrays by k-mer code), alt_ref a ts.AltModel.  Kept as they are: only
+    central_pos of the two models is compared (the reference compares alt_ref.kmer_width with itself), and
+    `seq[expand_width:-expand_width]` is '' when expand_width is 0."""
+    def get_reg_reads(reads, int_start, int_end):
+        return [r_data for r_data in reads if not (r_data.start >= int_end or r_data.end <= int_start)]
+
+    def std_levels(kmer):
+        code = std_ref._kmer_code(kmer)
+        return float(std_ref.level_means[code]), float(std_ref.level_sds[code])
+    # compute kmer values to make strand specific calculations easier
+    dnstrm_bases = std_ref.kmer_width - std_ref.central_pos - 1
+    expand_width = max(std_ref.central_pos, dnstrm_bases)
+    filt_width = expand_width if min_reg_overlap is None else expand_width + min_reg_overlap
+    if alt_ref is not None:
+        if alt_ref.central_pos != std_ref.central_pos or alt_ref.kmer_width != alt_ref.kmer_width:
+            raise th.TomboError(MODEL_KMER_POS_ERROR)
+
+    # expand regions to get kmers at first and last positions, add reads and region sequence
+    for p_int in plot_intervals:
+        p_int.expand_interval(expand_width).add_reads(reads_index).add_seq()
+    expand_seqs = [p_int.seq for p_int in plot_intervals]
+    rev_expand_seqs = [th.rev_comp(p_int.seq) for p_int in plot_intervals]
+    # convert back to original plot_intervals with seq from expanded intervals
+    for p_int in plot_intervals:
+        p_int.expand_interval(-expand_width)
+        p_int.update(reads=get_reg_reads(p_int.reads, p_int.start + filt_width, p_int.end - filt_width),
+                     seq=p_int.seq[expand_width:-expand_width])
+
+    K = std_ref.kmer_width
+    all_reg_model_data, all_reg_alt_model_data = [], []
+    for reg_data, reg_seq, rev_seq in zip(plot_intervals, expand_seqs, rev_expand_seqs):
+        clipped_reg_seq, clipped_rev_seq = reg_seq, rev_seq
+        if std_ref.central_pos > dnstrm_bases:
+            clipped_reg_seq = reg_seq[:dnstrm_bases - std_ref.central_pos]
+            clipped_rev_seq = rev_seq[:dnstrm_bases - std_ref.central_pos]
+        elif dnstrm_bases > std_ref.central_pos:
+            clipped_reg_seq = reg_seq[dnstrm_bases - std_ref.central_pos:]
+            clipped_rev_seq = rev_seq[dnstrm_bases - std_ref.central_pos:]
+        fwd_kmers = [clipped_reg_seq[i:i + K] for i in range(len(clipped_reg_seq) - K + 1)]
+        rev_kmers = [clipped_rev_seq[i:i + K] for i in range(len(clipped_rev_seq) - K + 1)]
+        all_reg_model_data.append((
+            reg_data.reg_id, reg_data.strand,
+            [(reg_data.start + pos,) + std_levels(kmer) for pos, kmer in enumerate(fwd_kmers)
+             if not th.invalid_seq(kmer)],
+            [(reg_data.end - pos - 1,) + std_levels(kmer) for pos, kmer in enumerate(rev_kmers)
+             if not th.invalid_seq(kmer)]))
+        # if alternative model is supplied add info
+        if alt_ref is not None and len(fwd_kmers) >= alt_ref.kmer_width:
+            plot_center = len(fwd_kmers) // 2
+            window = slice(plot_center - alt_ref.central_pos - 1, plot_center + alt_ref.kmer_width - alt_ref.central_pos)
+            fwd_kmer_poss = list(zip(fwd_kmers[window], range(alt_ref.kmer_width - 1, -1, -1)))
+            reg_fwd_alt_data = [
+                (reg_data.start + (plot_center - pos + alt_ref.central_pos), alt_ref.means[(kmer, pos)],
+                 alt_ref.sds[(kmer, pos)])
+                for kmer, pos in fwd_kmer_poss] if all(kmer_pos in alt_ref.means for kmer_pos in fwd_kmer_poss) else []
+            rev_kmer_poss = list(zip(rev_kmers[window], range(alt_ref.kmer_width - 1, -1, -1)))
+            reg_rev_alt_data = [
+                (reg_data.end - (plot_center - pos + alt_ref.central_pos) - 1, alt_ref.means[(kmer, pos)],
+                 alt_ref.sds[(kmer, pos)])
+                for kmer, pos in rev_kmer_poss] if all(kmer_pos in alt_ref.means for kmer_pos in rev_kmer_poss) else []
+            all_reg_alt_model_data.append((reg_data.reg_id, reg_data.strand, reg_fwd_alt_data, reg_rev_alt_data))
+
+    return all_reg_model_data, all_reg_alt_model_data
+
+
+def get_model_r_data(all_reg_model_data, genome_centric=True):
+    """the model levels under the plots (_plot_commands.py:1034-1068): Position, Strand, Mean, SD, Region.  Not
+    genome-centric, the minus strand's positions are mirrored between its first and last entry."""
+    Position, Strand, Mean, SD, Region = [], [], [], [], []
+    for reg_id, strand, fwd_model_data, rev_model_data in all_reg_model_data:
+        if strand == '+' or strand is None:
+            for pos, base_model_mean, base_model_sd in fwd_model_data:
+                Position.append(pos)
+                Strand.append(FWD_STRAND)
+                Mean.append(base_model_mean)
+                SD.append(base_model_sd)
+                Region.append(reg_id)
+        if strand == '-' or strand is None:
+            if not genome_centric:
+                start_pos, end_pos = rev_model_data[0][0], rev_model_data[-1][0]
+            for pos, base_model_mean, base_model_sd in rev_model_data:
+                Position.append(pos if genome_centric else start_pos + end_pos - pos)
+                Strand.append(REV_STRAND)
+                Mean.append(base_model_mean)
+                SD.append(base_model_sd)
+                Region.append(reg_id)
+
+    return OrderedDict([('Position', np.array(Position, dtype=np.float64)), ('Strand', _strs(Strand)),
+                        ('Mean', np.array(Mean, dtype=np.float64)), ('SD', np.array(SD, dtype=np.float64)),
+                        ('Region', _strs(Region))])
+
+
+def get_reg_r_stats(all_reg_stats, are_pvals=False, engine=None):
+    """-> (StatsData, OrdData) of the per-read statistic plots (_plot_commands.py:1070-1096).  all_reg_stats:
+    (reg_id, strand, float64[reads, positions]) per region.  StatsData: Stats, Position, Read (all float64), Region,
+    read by read; a minus-strand region's positions are reversed.  OrdData: Read (float64), Region: the reads in
+    ts.order_reads order, taken before the reversal.  ts.transform_and_trim_stats trims likelihood ratios in the
+    array that was passed, as in the reference."""
+    from . import tombo_stats as ts
+    Stats, Position, Read, Region, OrdRead, OrdRegion = [], [], [], [], [], []
+    for reg_id, reg_strand, reg_stats in all_reg_stats:
+        # -log if p-values and trim/winsorize stats before clustering here
+        reg_stats = ts.transform_and_trim_stats(reg_stats, are_pvals, PLOT_PVAL_MAX if are_pvals else PLOT_LLR_MAX)
+        OrdRead.append(np.asarray(ts.order_reads(reg_stats, engine=engine), dtype=np.float64))
+        OrdRegion.extend([reg_id] * reg_stats.shape[0])
+        if reg_strand == '-':
+            reg_stats = reg_stats[:, ::-1]
+        n_reads, n_pos = reg_stats.shape
+        Stats.append(np.ascontiguousarray(reg_stats, dtype=np.float64).ravel())
+        Position.append(np.tile(np.arange(n_pos, dtype=np.float64), n_reads))
+        Read.append(np.repeat(np.arange(n_reads, dtype=np.float64), n_pos))
+        Region.extend([reg_id] * (n_reads * n_pos))
+
+    StatsData = OrderedDict([('Stats', _cat(Stats, np.float64)), ('Position', _cat(Position, np.float64)),
+                             ('Read', _cat(Read, np.float64)), ('Region', _strs(Region))])
+    OrdData = OrderedDict([('Read', _cat(OrdRead, np.float64)), ('Region', _strs(OrdRegion))])
+    return StatsData, OrdData
+
+
+def model_single_sample_plot_data(plot_intervals, reads_index, std_ref, overplot_type, overplot_thresh, alt_ref=None,
+                                  title_include_chrm=True, title_include_cov=True, is_rna=False, engine=None):
+    """plot_model_single_sample up to its R calls (_plot_commands.py:1592-1623) -> the frames it hands to
+    plotModelComp: (SignalData, QuantData, BoxData, EventData, BasesData, Titles, ModelData) and, with alt_ref,
+    AltModelData behind them.  is_rna: what th.is_sample_rna reads from the files."""
+    # get reads overlapping each region along with all kmers
+    all_reg_model_data, all_reg_alt_model_data = get_reg_kmers(std_ref, plot_intervals, reads_index, alt_ref=alt_ref)
+    plot_intervals = th.filter_empty_regions(plot_intervals)
+    Titles, plot_types = get_plots_titles(plot_intervals, None, overplot_type, overplot_thresh, True,
+                                          include_chrm=title_include_chrm, include_cov=title_include_cov)
+    ModelData = get_model_r_data(all_reg_model_data)
+    BasesData = get_base_r_data(plot_intervals, is_rna=is_rna)
+    SignalData, QuantData, BoxData, EventData = get_plot_types_data(
+        (plot_intervals, plot_types, overplot_thresh, 'Group1'), engine=engine)
+    frames = (SignalData, QuantData, BoxData, EventData, BasesData, Titles, ModelData)
+    return frames if alt_ref is None else frames + (get_model_r_data(all_reg_alt_model_data),)
+
+
+def motif_with_stats_plot_data(reads_index, ctrl_reads_index, plot_intervals, stat_locs, overplot_thresh, std_ref,
+                               alt_ref=None, engine=None):
+    """plot_motif_centered_with_stats up to its R calls (_plot_commands.py:1526-1587) -> the frames it hands to
+    plotMotifStats: (SignalData, BasesData, StatsData, ModelData) and, with alt_ref, AltModelData behind them.  All
+    frames are read direction-centric.  ModelData is None where the reference passes R's NULL (no std_ref, or a
+    control sample).  alt_ref with a control sample or without std_ref is a ValueError: the reference then names
+    an AltModelData it never made."""
+    if alt_ref is not None and (ctrl_reads_index is not None or std_ref is None):
+        raise ValueError('alt_ref needs std_ref and no control sample: the reference makes no AltModelData otherwise')
+    ModelData = AltModelData = None
+    plot_types = ['Downsample' for _ in plot_intervals]
+    if ctrl_reads_index is None:
+        if std_ref is None:
+            for p_int in plot_intervals:
+                p_int.add_reads(reads_index).add_seq()
+            SignalData = get_r_raw_signal_data(plot_intervals, plot_types, overplot_thresh, 'Group1',
+                                               genome_centric=False, engine=engine)
+        else:
+            all_reg_model_data, all_reg_alt_model_data = get_reg_kmers(std_ref, plot_intervals, reads_index,
+                                                                       alt_ref=alt_ref)
+            SignalData = get_r_raw_signal_data(plot_intervals, plot_types, overplot_thresh, 'Group1',
+                                               genome_centric=False, engine=engine)
+            ModelData = get_model_r_data(all_reg_model_data, genome_centric=False)
+            if alt_ref is not None:
+                AltModelData = get_model_r_data(all_reg_alt_model_data, genome_centric=False)
+    else:
+        all_reg_data = [p_int.copy().add_reads(reads_index) for p_int in plot_intervals]
+        ctrl_reg_data = [p_int.copy().add_reads(ctrl_reads_index) for p_int in plot_intervals]
+        plot_intervals, all_reg_data, ctrl_reg_data = filter_and_merge_regs(all_reg_data, ctrl_reg_data)
+        plot_types = ['Downsample' for _ in plot_intervals]
+        SignalData = _rbind(
+            get_r_raw_signal_data(all_reg_data, plot_types, overplot_thresh, 'Group1', genome_centric=False,
+                                  engine=engine),
+            get_r_raw_signal_data(ctrl_reg_data, plot_types, overplot_thresh, 'Group2', genome_centric=False,
+                                  engine=engine))
+
+    BasesData = get_base_r_data(plot_intervals, genome_centric=False)
+    plot_poss, plot_stats = zip(*stat_locs)
+    StatsData = OrderedDict([('Position', np.array(plot_poss, dtype=np.float64)),
+                             ('Stat', np.array(plot_stats, dtype=np.float64))])
+    frames = (SignalData, BasesData, StatsData, ModelData)
+    return frames if alt_ref is None else frames + (AltModelData,)
+
+
+def per_read_modification_plot_data(plot_intervals, all_reg_stats, are_pvals, box_center, engine=None):
+    """plot_per_read_modification up to its R calls (_plot_commands.py:1638-1649) -> what it hands to
+    plotPerReadStats: (StatData, OrdData, BasesData, box_center, are_pvals)"""
+    StatData, OrdData = get_reg_r_stats(all_reg_stats, are_pvals, engine=engine)
+    BasesData = get_base_r_data(plot_intervals, zero_start=True, genome_centric=False)
+    return StatData, OrdData, BasesData, box_center, are_pvals
