@@ -885,6 +885,36 @@ int tba_identify_stalls(tba_engine *e, const void *raw, int raw_dtype, int64_t n
     int64_t window_size, int64_t n_windows, int64_t mini_window_size, double threshold,
     int64_t min_consecutive_obs, int64_t edge_buffer, int64_t *ints, int64_t cap, int64_t *n_ints);
 
+/* ---- the documented per-read functions of tombo_stats, for a batch of reads (csrc/k_norm_api.h) ----
+ * ts.normalize_raw_signal (tombo_stats.py:482-573) of n_reads reads in host memory.  raw: the reads'
+ * samples one after the other (raw_dtype: TBA_RAW_I16 or TBA_RAW_F64), read i at raw_off[i] ..
+ * raw_off[i + 1]; its window is start[i] .. start[i] + len[i] of them (len >= 1).  norm_type:
+ * TBA_NORMTYPE_*.  sv_flags (or NULL) bit 0: read i takes shift and scale from sv_in[4 i], sv_in[4 i + 1]
+ * whatever the norm type, bit 1: and the limits sv_in[4 i + 2], sv_in[4 i + 3] (an outlier threshold
+ * overrides them).  channel (or NULL; TBA_NORMTYPE_PA_RAW needs it): offset, range, digitisation per read.
+ * has_outlier_thresh: the limits are median -/+ MAD * outlier_thresh of the normalised window.
+ * const_scale: the scale of TBA_NORMTYPE_MEDIAN_CONST_SCALE.  Out: status[i] 0, or 1 for a scale of exactly
+ * 0 (the reference's FloatingPointError; nothing else is written for that read); sv_out[4 i ..] shift,
+ * scale, lower, upper, the limits valid where has_lims[i]; norm: the normalised windows one after the
+ * other, read i at sum(len[0 .. i)); *out_kernel_ms (or NULL): the time of the two kernels. */
+enum { TBA_NORMTYPE_NONE = 0, TBA_NORMTYPE_PA_RAW = 1, TBA_NORMTYPE_MEDIAN = 2,
+       TBA_NORMTYPE_MEDIAN_CONST_SCALE = 3, TBA_NORMTYPE_ROBUST_MEDIAN = 4 };
+int tba_normalize_raw_batch(tba_engine *e, int64_t n_reads, const void *raw, int raw_dtype,
+    const int64_t *raw_off, const int64_t *start, const int64_t *len, int norm_type,
+    const double *sv_in, const int32_t *sv_flags, const double *channel, int has_outlier_thresh,
+    double outlier_thresh, double const_scale, double *sv_out, int32_t *has_lims, double *norm,
+    int32_t *status, double *out_kernel_ms);
+/* The five sums of the method-of-moments fit (ts.calc_kmer_fitted_shift_scale, tombo_stats.py:427-437), each
+ * in the order of numpy's .sum(): sums[5 i ..] = iv.sum(), (m * iv).sum(), (m * iv * m).sum(), (e * iv).sum(),
+ * (e * iv * m).sum() over the points off[i] .. off[i + 1] of read i (e event means, m model means, iv model
+ * inverse variances). */
+int tba_mom_sums(tba_engine *e, int64_t n_reads, const int64_t *off, const double *event_means,
+    const double *model_means, const double *model_inv_vars, double *sums);
+/* ts.get_read_seg_score (tombo_stats.py:2327-2338) of n_reads reads: scores[i] = np.mean(np.abs((means -
+ * ref_means) / ref_sds)) over the bases off[i] .. off[i + 1]. */
+int tba_seg_scores(tba_engine *e, int64_t n_reads, const int64_t *off, const double *means,
+    const double *ref_means, const double *ref_sds, double *scores);
+
 /* Host-side, no GPU involved: pack n_reads per-read sample arrays (raw_ptrs[i], raw_off[i+1] -
  * raw_off[i] samples of type raw_dtype; reverse != 0: copied back to front) and sequences
  * (seq_ptrs[i]: ASCII A/C/G/T, seq_off[i+1] - seq_off[i] letters, stored as codes 0..3, anything

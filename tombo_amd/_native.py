@@ -280,6 +280,10 @@ def _prototypes():
         'tba_batch_de_novo_stats': (n, [v, q, d, D, q]),
         # ---- the worker's per-read preparation; host-side packing ----
         'tba_identify_stalls': (n, [v, v, n, q, q, q, q, d, q, q, Q, q, Q]),
+        # ---- the documented per-read functions of tombo_stats ----
+        'tba_normalize_raw_batch': (n, [v, q, v, n, cQ, cQ, cQ, n, cD, cI, cD, n, d, d, D, I, D, I, D]),
+        'tba_mom_sums': (n, [v, q, cQ, cD, cD, cD, D]),
+        'tba_seg_scores': (n, [v, q, cQ, cD, cD, cD, D]),
         'tba_pack_reads': (n, [q, v, n, n, cQ, v, v, cQ, B, n]),
         'tba_unpack_reads': (n, [q, v, q, cQ, cQ, v, n]),
         # ---- synthetic reads made on the device ----
@@ -460,6 +464,50 @@ def _check_segment_medians_args(values, off):
     if off.shape[0] > 1 and np.diff(off).max() >= 2 ** 31:
         raise ValueError('a segment holds fewer than 2**31 values')
     return np.ascontiguousarray(values), off
+
+
+NORMTYPE_NONE, NORMTYPE_PA_RAW, NORMTYPE_MEDIAN, NORMTYPE_MEDIAN_CONST_SCALE, NORMTYPE_ROBUST_MEDIAN = range(5)
+
+
+def _check_normalize_raw_args(raws, starts, lens, norm_type, sv_in, sv_flags, channel):
+    """the argument checks of Engine.normalize_raw_batch -> (dtype, flat samples, raw_off, starts, lens)"""
+    n = len(raws)
+    if n == 0:
+        raise ValueError('no reads')
+    raws = [np.asarray(r) for r in raws]
+    dt = raws[0].dtype
+    if dt not in (np.dtype(np.int16), np.dtype(np.float64)) or any(r.dtype != dt or r.ndim != 1 for r in raws):
+        raise ValueError('the raw signals must be one-dimensional arrays, all int16 or all float64')
+    if norm_type not in range(5):
+        raise ValueError('unknown norm type')
+    starts, lens = _i64(starts), _i64(lens)
+    sizes = np.array([r.shape[0] for r in raws], dtype=np.int64)
+    if starts.shape != (n,) or lens.shape != (n,):
+        raise ValueError('one start and one length per read')
+    if (starts < 0).any() or (lens < 1).any() or (starts + lens > sizes).any() or (lens >= 2 ** 31).any():
+        raise ValueError('a window is empty or does not lie inside its read')
+    if (sv_in is None) != (sv_flags is None):
+        raise ValueError('scale values and their flags come together')
+    if sv_in is not None and (sv_in.dtype != np.float64 or sv_in.shape != (n, 4) or sv_flags.dtype != np.int32
+                              or sv_flags.shape != (n,)):
+        raise ValueError('sv_in must be float64 [n, 4] and sv_flags int32 [n]')
+    if channel is not None and (channel.dtype != np.float64 or channel.shape != (n, 3)):
+        raise ValueError('channel must be float64 [n, 3]: offset, range, digitisation')
+    if norm_type == NORMTYPE_PA_RAW and channel is None and (sv_flags is None or not (sv_flags & 1).all()):
+        raise ValueError('pA_raw needs the channel values')
+    return dt, np.ascontiguousarray(np.concatenate(raws)), _offsets(raws), starts, lens
+
+
+def _check_point_arrays(off, *arrays):
+    """offsets and the float64 arrays they cut into reads -> contiguous (off, *arrays)"""
+    off = _check_offsets(off, 'off')
+    out = []
+    for a in arrays:
+        a = np.asarray(a)
+        if a.dtype != np.float64 or a.ndim != 1 or a.shape[0] != int(off[-1]):
+            raise ValueError('float64 arrays of the length the offsets end at')
+        out.append(np.ascontiguousarray(a))
+    return (off,) + tuple(out)
 
 
 def _check_fractions(q, what):
@@ -1489,6 +1537,44 @@ class Engine(object):
         v, off = _check_segment_medians_args(values, off)
         out = np.empty(off.shape[0] - 1, dtype=np.float64)
         self._call('tba_segment_medians', v, off, off.shape[0] - 1, out)
+        return out
+
+    # ---- the documented per-read functions of tombo_stats (csrc/k_norm_api.h) ----
+    def normalize_raw_batch(self, raws, starts, lens, norm_type, sv_in=None, sv_flags=None, channel=None,
+                            outlier_thresh=None, const_scale=None):
+        """tba_normalize_raw_batch: ts.normalize_raw_signal of the windows [starts[i], starts[i] + lens[i]) of the
+        one-dimensional arrays `raws`, all int16 or all float64.  norm_type: NORMTYPE_*; sv_in / sv_flags:
+        pack_scale_values; channel: float64 [n, 3] offset, range, digitisation.  -> (sv float64 [n, 4]: shift, scale,
+        lower_lim, upper_lim; has_lims int32 [n]; the normalised windows as views of one float64 array; status
+        int32 [n]: 1 where the scale is exactly 0 and nothing was computed); last_normalize_raw_kernel_ms holds the
+        time of the two kernels"""
+        n = len(raws)
+        dt, raw, raw_off, starts, lens = _check_normalize_raw_args(raws, starts, lens, norm_type, sv_in, sv_flags, channel)
+        sv = np.zeros((n, 4), np.float64)
+        has_lims, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        out_off = np.zeros(n + 1, np.int64)
+        np.cumsum(lens, out=out_off[1:])
+        norm, ms = np.zeros(int(out_off[-1]), np.float64), np.zeros(1, np.float64)
+        self._call('tba_normalize_raw_batch', n, raw.ctypes, RAW_DTYPES[dt], raw_off, starts, lens, int(norm_type),
+                   sv_in, sv_flags, channel, int(outlier_thresh is not None),
+                   0.0 if outlier_thresh is None else float(outlier_thresh),
+                   0.0 if const_scale is None else float(const_scale), sv, has_lims, norm, status, ms)
+        self.last_normalize_raw_kernel_ms = float(ms[0])
+        return sv, has_lims, [norm[a:b] for a, b in zip(out_off[:-1].tolist(), out_off[1:].tolist())], status
+
+    def mom_sums(self, event_means, model_means, model_inv_vars, off):
+        """tba_mom_sums: float64 [n, 5], per read (CSR by off) iv.sum(), (m * iv).sum(), (m * iv * m).sum(),
+        (e * iv).sum(), (e * iv * m).sum() in the order of numpy's .sum()"""
+        off, e, m, iv = _check_point_arrays(off, event_means, model_means, model_inv_vars)
+        out = np.zeros((off.shape[0] - 1, 5), np.float64)
+        self._call('tba_mom_sums', off.shape[0] - 1, off, e, m, iv, out)
+        return out
+
+    def seg_scores(self, means, ref_means, ref_sds, off):
+        """tba_seg_scores: float64 [n], ts.get_read_seg_score of every read (CSR by off)"""
+        off, m, rm, rs = _check_point_arrays(off, means, ref_means, ref_sds)
+        out = np.zeros(off.shape[0] - 1, np.float64)
+        self._call('tba_seg_scores', off.shape[0] - 1, off, m, rm, rs, out)
         return out
 
     # ---- region plot data (csrc/k_plot.h) ----

@@ -25,6 +25,7 @@
 #include "k_roc.h"
 #include "k_pdist.h"
 #include "k_plot.h"
+#include "k_norm_api.h"
 
 #include <algorithm>
 #include <array>
@@ -3095,6 +3096,110 @@ extern "C" int tba_identify_stalls(tba_engine *e, const void *raw, int raw_dtype
     if (r.n_stall > cap) return set_err(TBA_E_ARG, "interval buffer too small (n_ints holds the count)");
     if (r.n_stall > 0) return sc.get(ints, d_ints, r.n_stall * 2);
     return TBA_OK;
+}
+
+// ---- the documented per-read functions of tombo_stats (k_norm_api.h), batches in host buffers ----
+extern "C" int tba_normalize_raw_batch(tba_engine *e, int64_t n_reads, const void *raw, int raw_dtype,
+    const int64_t *raw_off, const int64_t *start, const int64_t *len, int norm_type,
+    const double *sv_in, const int32_t *sv_flags, const double *channel, int has_outlier_thresh,
+    double outlier_thresh, double const_scale, double *sv_out, int32_t *has_lims, double *norm,
+    int32_t *status, double *out_kernel_ms)
+{
+    if (!e || n_reads < 0) return set_err(TBA_E_ARG, "bad arguments");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (n_reads == 0) return TBA_OK;
+    if (!raw || !raw_off || !start || !len || !sv_out || !has_lims || !norm || !status || (sv_flags && !sv_in))
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (raw_dtype != TBA_RAW_F64 && raw_dtype != TBA_RAW_I16) return set_err(TBA_E_ARG, "raw dtype must be int16 or float64");
+    if (norm_type < TBA_NORMTYPE_NONE || norm_type > TBA_NORMTYPE_ROBUST_MEDIAN) return set_err(TBA_E_ARG, "unknown norm type");
+    if (const int rc = check_csr_off(raw_off, n_reads)) return rc;
+    std::vector<i64> out_off(n_reads + 1, 0);
+    bool all_given = sv_flags != nullptr;
+    for (i64 r = 0; r < n_reads; r++) {
+        if (start[r] < 0 || len[r] < 1 || len[r] >= ((i64)1 << 31) || start[r] > raw_off[r + 1] - raw_off[r] - len[r])
+            return set_err(TBA_E_ARG, "a window is empty or does not lie inside its read");
+        out_off[r + 1] = out_off[r] + len[r];
+        all_given = all_given && (sv_flags[r] & 1);
+    }
+    if (norm_type == TBA_NORMTYPE_PA_RAW && !channel && !all_given) return set_err(TBA_E_ARG, "pA_raw needs the channel values");
+    const i64 total = out_off[n_reads];
+    Scratch sc(e);
+    NormApiArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_reads = n_reads;
+    const char *d_raw = sc.in((const char *)raw, (size_t)raw_off[n_reads] * raw_elem_bytes(raw_dtype));
+    a.raw_off = sc.in(raw_off, n_reads + 1);
+    a.start = sc.in(start, n_reads);
+    a.len = sc.in(len, n_reads);
+    a.out_off = sc.in(out_off.data(), n_reads + 1);
+    a.sv_in = sv_in ? sc.in(sv_in, 4 * n_reads) : nullptr;
+    a.sv_flags = sv_flags ? sc.in(sv_flags, n_reads) : nullptr;
+    a.chan = channel ? sc.in(channel, 3 * n_reads) : nullptr;
+    a.norm_type = norm_type; a.has_thresh = has_outlier_thresh != 0;
+    a.outlier_thresh = outlier_thresh; a.const_scale = const_scale;
+    a.sv_out = sc.out<double>(4 * n_reads);
+    a.has_lims = sc.out<i32>(n_reads);
+    a.status = sc.out<i32>(n_reads);
+    double *d_norm = sc.out<double>(total);
+    sc.zero(a.sv_out, 4 * n_reads * sizeof(double));
+    sc.zero(a.has_lims, n_reads * sizeof(i32));
+    if (sc.rc) return sc.rc;
+    KernelTimer tm(sc, out_kernel_ms != nullptr);
+    if (raw_dtype == TBA_RAW_I16) {
+        k_norm_scale<int16_t><<<dim3((unsigned)n_reads), SEL_NT, 0, e->stream>>>(a, (const int16_t *)d_raw);
+        k_norm_apply<int16_t><<<grid_for(total), 256, 0, e->stream>>>(a, (const int16_t *)d_raw, d_norm);
+    } else {
+        k_norm_scale<double><<<dim3((unsigned)n_reads), SEL_NT, 0, e->stream>>>(a, (const double *)d_raw);
+        k_norm_apply<double><<<grid_for(total), 256, 0, e->stream>>>(a, (const double *)d_raw, d_norm);
+    }
+    tm.stop();
+    if (out_kernel_ms) *out_kernel_ms = tm.ms();
+    if (sc.sync() || sc.get(sv_out, a.sv_out, 4 * n_reads) || sc.get(has_lims, a.has_lims, n_reads) ||
+        sc.get(status, a.status, n_reads)) return sc.rc;
+    return sc.get(norm, d_norm, total);
+}
+
+static int check_point_arrays(tba_engine *e, int64_t n_reads, const int64_t *off, std::initializer_list<const void *> arrays,
+                              const void *out)
+{
+    if (!e || n_reads < 0 || (n_reads > 0 && (!off || !out))) return set_err(TBA_E_ARG, "bad arguments");
+    if (n_reads == 0) return TBA_OK;
+    if (const int rc = check_csr_off(off, n_reads)) return rc;
+    for (const void *p : arrays)
+        if (off[n_reads] > 0 && !p) return set_err(TBA_E_ARG, "bad arguments");
+    return TBA_OK;
+}
+
+extern "C" int tba_mom_sums(tba_engine *e, int64_t n_reads, const int64_t *off, const double *event_means,
+    const double *model_means, const double *model_inv_vars, double *sums)
+{
+    if (const int rc = check_point_arrays(e, n_reads, off, {event_means, model_means, model_inv_vars}, sums)) return rc;
+    if (n_reads == 0) return TBA_OK;
+    const i64 n = off[n_reads];
+    Scratch sc(e);
+    const i64 *d_off = sc.in(off, n_reads + 1);
+    const double *d_e = sc.in(event_means, n), *d_m = sc.in(model_means, n), *d_iv = sc.in(model_inv_vars, n);
+    double *d_tmp = sc.out<double>(n), *d_sums = sc.out<double>(5 * n_reads);
+    if (sc.rc) return sc.rc;
+    k_mom_sums<<<dim3((unsigned)n_reads), 64, 0, e->stream>>>(n_reads, d_off, d_e, d_m, d_iv, d_tmp, d_sums);
+    if (sc.sync()) return sc.rc;
+    return sc.get(sums, d_sums, 5 * n_reads);
+}
+
+extern "C" int tba_seg_scores(tba_engine *e, int64_t n_reads, const int64_t *off, const double *means,
+    const double *ref_means, const double *ref_sds, double *scores)
+{
+    if (const int rc = check_point_arrays(e, n_reads, off, {means, ref_means, ref_sds}, scores)) return rc;
+    if (n_reads == 0) return TBA_OK;
+    const i64 n = off[n_reads];
+    Scratch sc(e);
+    const i64 *d_off = sc.in(off, n_reads + 1);
+    const double *d_m = sc.in(means, n), *d_rm = sc.in(ref_means, n), *d_rs = sc.in(ref_sds, n);
+    double *d_tmp = sc.out<double>(n), *d_scores = sc.out<double>(n_reads);
+    if (sc.rc) return sc.rc;
+    k_seg_scores<<<dim3((unsigned)n_reads), 64, 0, e->stream>>>(n_reads, d_off, d_m, d_rm, d_rs, d_tmp, d_scores);
+    if (sc.sync()) return sc.rc;
+    return sc.get(scores, d_scores, n_reads);
 }
 
 // self-test of the device-side subsample: out[t] = image of t under the keyed permutation of

@@ -7,6 +7,8 @@ Mirrors the part of /root/reference/tombo/tombo_stats.py the hot path touches:
   get_dynamic_prog_params              tombo_stats.py:2364-2370
   identify_stalls (mean-window method) tombo_stats.py:269-368  (P10, caller-side, RNA only)
   remove_stall_cpts                    tombo_stats.py:1576-1597
+  normalize_raw_signal, compute_base_means, get_read_seg_score, calc_kmer_fitted_shift_scale
+                                       tombo_stats.py:482-573, 203-215, 2327-2338, 370-450 (csrc/k_norm_api.h)
 The numeric kernels (normalisation, event detection, DP ...) live in csrc/ and are reached
 through tombo_amd.resquiggle.
 """
@@ -352,6 +354,179 @@ def remove_stall_cpts(stall_ints, valid_cpts):
         if not (cur[0] < cpt < cur[1]):
             keep.append(i)
     return valid_cpts[keep]
+
+
+# ---------------------------------------------------------------------------------------------
+# The documented per-read functions of tombo_stats.__all__ (tombo_stats.py:203-215, :370-450, :482-573,
+# :2327-2338): the kernels are csrc/k_norm_api.h, the `*_batch` forms run one engine call for all reads and
+# the reference's single-read functions are batches of one.
+NORM_TYPES = ('none', 'pA', 'pA_raw', 'median', 'robust_median', 'median_const_scale')     # tombo_stats.py:107
+_NORM_TYPE_CODES = {'none': _native.NORMTYPE_NONE, 'pA': _native.NORMTYPE_PA_RAW, 'pA_raw': _native.NORMTYPE_PA_RAW,
+                    'median': _native.NORMTYPE_MEDIAN, 'median_const_scale': _native.NORMTYPE_MEDIAN_CONST_SCALE,
+                    'robust_median': _native.NORMTYPE_ROBUST_MEDIAN}
+_SLOPE_ZERO_MSG = 'Read failed sequence-based signal re-scaling parameter estimation.'
+
+
+def compute_base_means(all_raw_signal, base_starts):
+    """tombo_stats.py:203-215: base mean levels from raw signal and 0-based base start positions (with the end)"""
+    from ._c_helper import c_new_means
+    return c_new_means(all_raw_signal.astype(np.float64), base_starts)
+
+
+def get_read_seg_scores_batch(reads, engine=None):
+    """get_read_seg_score of every (r_means, r_ref_means, r_ref_sds) triple of `reads` in one engine call -> a list
+    of float64 scores"""
+    reads = [tuple(np.ascontiguousarray(a, dtype=np.float64) for a in rd) for rd in reads]
+    if len(reads) == 0:
+        return []
+    if any(len(rd) != 3 or any(a.ndim != 1 or a.shape != rd[0].shape for a in rd) for rd in reads):
+        raise ValueError('every read is a triple of one-dimensional arrays of one length')
+    off = _csr_offsets([rd[0].shape[0] for rd in reads])
+    scores = _engine(engine).seg_scores(*(np.concatenate([rd[j] for rd in reads]) for j in range(3)), off)
+    return list(scores)
+
+
+def get_read_seg_score(r_means, r_ref_means, r_ref_sds):
+    """tombo_stats.py:2327-2338: np.mean(np.abs((r_means - r_ref_means) / r_ref_sds)), numpy's summation order"""
+    return _only(get_read_seg_scores_batch([(r_means, r_ref_means, r_ref_sds)]))
+
+
+def _mom_corr_factors(points, engine=None):
+    """the 'mom' branch of calc_kmer_fitted_shift_scale (:427-440) for a list of (event means, model means, model
+    inverse variances): the five sums of every read on the device in one call, the 2x2 solve on the host"""
+    points = [tuple(np.ascontiguousarray(a, dtype=np.float64) for a in p) for p in points]
+    off = _csr_offsets([p[0].shape[0] for p in points])
+    sums = _engine(engine).mom_sums(*(np.concatenate([p[j] for p in points]) for j in range(3)), off)
+    out = []
+    for iv_sum, mv_sum, mvm_sum, ev_sum, evm_sum in sums:
+        coef_mat = np.array(((iv_sum, mv_sum), (mv_sum, mvm_sum)))
+        out.append(tuple(np.linalg.solve(coef_mat, np.array((ev_sum, evm_sum)))))
+    return out
+
+
+def calc_kmer_fitted_shift_scale(prev_shift, prev_scale, r_event_means, r_model_means, r_model_inv_vars=None,
+                                 method='theil_sen'):
+    """tombo_stats.py:370-450 -> (shift, scale, shift_corr_factor, scale_corr_factor).  'theil_sen': the slopes of
+    c_compute_slopes and both medians on the device (above MAX_POINTS_FOR_THEIL_SEN points the np.random.choice draw is
+    made here, in the reference's place in the random stream); 'mom': the five sums on the device, np.linalg.solve
+    on the host; 'robust' (scipy's Nelder-Mead) is not built."""
+    if method == 'robust':
+        raise NotImplementedError("calc_kmer_fitted_shift_scale: method 'robust' (scipy Nelder-Mead) is not built")
+    elif method == 'theil_sen':
+        from ._c_helper import c_compute_slopes
+        n_points = r_model_means.shape[0]
+        if n_points > _native.MAX_POINTS_FOR_THEIL_SEN:
+            samp_ind = np.random.choice(n_points, _native.MAX_POINTS_FOR_THEIL_SEN, replace=False)
+            r_model_means = r_model_means[samp_ind]
+            r_event_means = r_event_means[samp_ind]
+        r_event_means = np.ascontiguousarray(r_event_means, dtype=np.float64)
+        r_model_means = np.ascontiguousarray(r_model_means, dtype=np.float64)
+        eng = _engine()
+        slopes = c_compute_slopes(r_event_means, r_model_means)
+        slope = eng.segment_medians(slopes, _csr_offsets([slopes.shape[0]]))[0]
+        inters = r_model_means - (slope * r_event_means)
+        inter = eng.segment_medians(inters, _csr_offsets([inters.shape[0]]))[0]
+        if slope == 0:
+            raise th.TomboError(_SLOPE_ZERO_MSG)
+        scale_corr_factor = 1 / slope
+        shift_corr_factor = -inter / slope
+    elif method == 'mom':
+        shift_corr_factor, scale_corr_factor = _only(_mom_corr_factors(
+            [(r_event_means, r_model_means, r_model_inv_vars)]))
+    else:
+        raise th.TomboError('Invalid k-mer fitted normalization parameter method: ' + method +
+                            '\n\t\tValid methods are "robust" and "mom".')
+    shift = prev_shift + (shift_corr_factor * prev_scale)
+    scale = prev_scale * scale_corr_factor
+    return shift, scale, shift_corr_factor, scale_corr_factor
+
+
+def _per_read(values, n, what):
+    if values is None:
+        return [None] * n
+    values = list(values)
+    if len(values) != n:
+        raise ValueError('%s: one entry per read' % what)
+    return values
+
+
+def normalize_raw_signal_batch(raws, read_starts=None, read_obs_lens=None, norm_type='median', outlier_thresh=None,
+                               channel_infos=None, scale_values=None, const_scale=None, event_means=None,
+                               model_means=None, model_inv_vars=None, engine=None):
+    """normalize_raw_signal of every read of `raws` in one engine call -> a list of (norm_signal, th.scaleValues); a
+    read whose scale is exactly 0 (the reference's FloatingPointError) gets None and the others are unaffected.
+    read_starts / read_obs_lens / channel_infos / scale_values / event_means / model_means / model_inv_vars: None, or
+    one entry per read (which may be None).  int16 and float64 signals are taken as they are (a batch that mixes
+    them is computed in float64, which gives int16 samples the same values), any other dtype is converted with
+    astype(np.float64) first."""
+    raws = [np.asarray(r) for r in raws]
+    n = len(raws)
+    if n == 0:
+        return []
+    starts = [0 if s is None else int(s) for s in _per_read(read_starts, n, 'read_starts')]
+    lens = [r.shape[0] - s if ln is None else int(ln)
+            for r, s, ln in zip(raws, starts, _per_read(read_obs_lens, n, 'read_obs_lens'))]
+    svs = _per_read(scale_values, n, 'scale_values')
+    chans = _per_read(channel_infos, n, 'channel_infos')
+    if norm_type not in NORM_TYPES and any(sv is None for sv in svs):
+        raise th.TomboError('Normalization type ' + norm_type + ' is not a valid ' +
+                            'option and shift or scale parameters were not provided.')
+    if norm_type == 'median_const_scale' and any(sv is None for sv in svs):
+        assert const_scale is not None
+    # the reference slices: a window that runs past the end is cut there
+    lens = [max(0, min(ln, r.shape[0] - s)) for r, s, ln in zip(raws, starts, lens)]
+    if any(r.ndim != 1 or s < 0 or ln < 1 for r, s, ln in zip(raws, starts, lens)):
+        raise ValueError('every read needs a one-dimensional signal and a window of at least one sample inside it')
+    if not all(r.dtype == np.int16 for r in raws):
+        raws = [r if r.dtype == np.float64 else r.astype(np.float64) for r in raws]
+    fitted = {}
+    if norm_type == 'pA':
+        todo = [i for i in range(n) if svs[i] is None]
+        pts = list(zip(*(_per_read(a, n, 'event_means, model_means, model_inv_vars')
+                         for a in (event_means, model_means, model_inv_vars))))
+        for i, (shift_corr, scale_corr) in zip(todo, _mom_corr_factors([pts[i] for i in todo], engine) if todo else ()):
+            shift, scale = -1 * chans[i].offset, chans[i].digitisation / chans[i].range
+            fitted[i] = th.scaleValues(shift + (shift_corr * scale), scale * scale_corr, None, None, None)
+    sv_in, sv_flags = _native.pack_scale_values([fitted.get(i, svs[i]) for i in range(n)])
+    channel = None
+    if norm_type == 'pA_raw' and any(sv is None for sv in svs):
+        channel = np.zeros((n, 3), np.float64)
+        for i in range(n):
+            if svs[i] is None:
+                channel[i] = chans[i].offset, chans[i].range, chans[i].digitisation
+    sv, _, norms, status = _engine(engine).normalize_raw_batch(
+        raws, starts, lens, _NORM_TYPE_CODES.get(norm_type, _native.NORMTYPE_NONE), sv_in, sv_flags, channel,
+        outlier_thresh, const_scale)
+    out = []
+    for i in range(n):
+        if status[i] != 0:
+            out.append(None)
+            continue
+        shift, scale, lower_lim, upper_lim = sv[i]
+        if svs[i] is not None:
+            shift, scale = svs[i].shift, svs[i].scale
+        elif norm_type == 'none':
+            shift, scale = 0, 1
+        elif norm_type == 'median_const_scale':
+            scale = const_scale
+        if outlier_thresh is None:
+            lower_lim, upper_lim = (None, None) if svs[i] is None else (svs[i].lower_lim, svs[i].upper_lim)
+        out.append((norms[i], th.scaleValues(shift, scale, lower_lim, upper_lim, outlier_thresh)))
+    return out
+
+
+def normalize_raw_signal(all_raw_signal, read_start_rel_to_raw=0, read_obs_len=None, norm_type='median',
+                         outlier_thresh=None, channel_info=None, scale_values=None, event_means=None, model_means=None,
+                         model_inv_vars=None, const_scale=None):
+    """tombo_stats.py:482-573 -> (normalised signal, th.scaleValues(shift, scale, lower_lim, upper_lim,
+    outlier_thresh)).  A scale of exactly 0 raises FloatingPointError, as the reference's division does under its
+    np.seterr(all='raise')."""
+    res = _only(normalize_raw_signal_batch(
+        [all_raw_signal], [read_start_rel_to_raw], [read_obs_len], norm_type, outlier_thresh, [channel_info],
+        [scale_values], const_scale, [event_means], [model_means], [model_inv_vars]))
+    if res is None:
+        raise FloatingPointError('divide by zero encountered in divide')
+    return res
 
 
 # ---------------------------------------------------------------------------------------------
