@@ -865,6 +865,34 @@ int tba_region_raw_signal(tba_engine *e, int64_t n_reads, const void *raw, int r
     const int64_t *pair_start, const int64_t *pair_end, int genome_centric, int64_t *out_sig_off,
     double *out_position, double *out_signal, int64_t *out_base_i, int64_t samples_cap, double *out_kernel_ms);
 
+/* ---- read filters: dwell percentiles (csrc/k_filter.h) -------------------------------------------
+ * The "stuck read" rule of tombo filter stuck (_filter_reads.py:58-96) and of the worker loop's
+ * --obs-per-base-filter (resquiggle.py:1449-1456) for n_reads reads: any(np.percentile(base_lens, pctl) >
+ * thresh for pctl, thresh in obs_filter).  segs: per read its base starts and its end (int64, CSR by
+ * seg_off[n_reads + 1]); the lengths are the successive differences, so a read of n bases has n + 1 entries
+ * and a read of 0 or 1 entries has no lengths.  Per pair j: q[j] the fraction numpy divides out
+ * (np.true_divide(pctl, 100)) and thresh[j].
+ *   out_vals[n_reads * n_pairs]  (may be NULL) np.percentile(lens, pctl) in the default linear form, bit for
+ *                                bit: the _lerp of tba_region_level_piles on the two order statistics, which
+ *                                are found by counting (an LDS histogram of the lengths, an exact radix select
+ *                                for a rank among the lengths of 4095 and more); nothing is sorted
+ *   out_flags[n_reads]           1 where any out_vals[i][j] > thresh[j] (strict)
+ * A read without lengths: NaN and flag 1 (np.percentile raises on an empty array and the reference's
+ * read_is_stuck answers True to any exception).  No floating-point atomics: the same call gives the same
+ * bits.  out_kernel_ms (may be NULL): kernel time.
+ * TBA_E_ARG: NULL pointers, offsets that do not start at 0 or decrease, n_pairs < 1, a fraction outside
+ * [0, 1], a NaN threshold, a decreasing boundary inside a read, a length of 2^31 or more, a read of 2^31
+ * entries or more.  Zero reads launch nothing. */
+int tba_dwell_pctl_flags(tba_engine *e, int64_t n_reads, const int64_t *segs, const int64_t *seg_off,
+    int64_t n_pairs, const double *q, const double *thresh, double *out_vals, uint8_t *out_flags,
+    double *out_kernel_ms);
+/* The same kernel on the boundaries of the resident batch after a run (what tba_batch_download returns as
+ * segs; nothing is uploaded except the pairs): out_vals[n * n_pairs] (may be NULL), out_flags[n] for the n
+ * reads of the batch.  A read whose status is not 0 gets NaN and flag 0: such a read is never indexed.
+ * TBA_E_STATE without a run batch. */
+int tba_batch_dwell_pctl_flags(tba_engine *e, int64_t n_pairs, const double *q, const double *thresh,
+    double *out_vals, uint8_t *out_flags, double *out_kernel_ms);
+
 /* The de novo statistic of every read of the finished resident batch, nothing uploaded: per-base
  * means (c_new_means over the final signal and boundaries, as tba_batch_base_stats) against the
  * batch's own expected levels, which are the canonical model's levels of the read sequence --

@@ -277,6 +277,9 @@ def _prototypes():
         'tba_segment_percentiles': (n, [v, cD, cQ, q, q, cD, q, cD, D, D, D]),
         'tba_region_raw_signal': (n, [v, q, v, n, cQ, cQ, cQ, cQ, cQ, cB, cB, cD, cD, cD, cD, q, cQ, cQ, cQ, n, Q, D, D, Q,
                                       q, D]),
+        # ---- read filters ----
+        'tba_dwell_pctl_flags': (n, [v, q, cQ, cQ, q, cD, cD, D, B, D]),
+        'tba_batch_dwell_pctl_flags': (n, [v, q, cD, cD, D, B, D]),
         'tba_batch_de_novo_stats': (n, [v, q, d, D, q]),
         # ---- the worker's per-read preparation; host-side packing ----
         'tba_identify_stalls': (n, [v, v, n, q, q, q, q, d, q, q, Q, q, Q]),
@@ -564,6 +567,40 @@ def _check_segment_percentiles_args(values, off, q_linear, q_nearest):
     if off.shape[0] - 1 >= 2 ** 31:
         raise ValueError('a call holds fewer than 2**31 segments')
     return v, off, _check_fractions(q_linear, 'q_linear'), _check_fractions(q_nearest, 'q_nearest')
+
+
+def _check_dwell_pairs(pairs):
+    """[(percentile, threshold), ...] of an observations-per-base filter -> (q float64[n] as numpy divides the
+    percentiles out, thresh float64[n]) (shared with the tests' stand-in engine)"""
+    pairs = list(pairs)
+    if len(pairs) < 1 or any(len(p) != 2 for p in pairs):
+        raise ValueError('pairs must be one or more (percentile, threshold)')
+    q = np.true_divide(np.array([p[0] for p in pairs], dtype=np.float64), 100)
+    thresh = np.array([p[1] for p in pairs], dtype=np.float64)
+    if not ((q >= 0.0) & (q <= 1.0)).all() or np.isnan(thresh).any():
+        raise ValueError('percentiles must lie in [0, 100] and thresholds must not be NaN')
+    return q, thresh
+
+
+def _check_dwell_pctl_args(segs, seg_off, pairs):
+    """the argument checks of Engine.dwell_pctl_flags (shared with the tests' stand-in engine): dtypes are checked,
+    not converted -> contiguous (segs, seg_off, q, thresh)"""
+    segs = np.asarray(segs)
+    if segs.dtype != np.int64 or segs.ndim != 1:
+        raise ValueError('segs must be a one-dimensional int64 array')
+    off = _check_offsets(seg_off, 'seg_off')
+    if segs.shape[0] != int(off[-1]):
+        raise ValueError('segs and offsets disagree')
+    q, thresh = _check_dwell_pairs(pairs)
+    if segs.shape[0] > 1:
+        inside = np.ones(segs.shape[0] - 1, dtype=bool)
+        inside[off[1:-1][(off[1:-1] > 0) & (off[1:-1] < segs.shape[0])] - 1] = False   # steps from one read to the next
+        d = np.diff(segs)[inside]
+        if (d < 0).any() or (d >= 2 ** 31).any():
+            raise ValueError('the boundaries of a read must not decrease and a length stays below 2**31')
+    if off.shape[0] > 1 and np.diff(off).max() >= 2 ** 31:
+        raise ValueError('a read holds fewer than 2**31 boundaries')
+    return np.ascontiguousarray(segs), off, q, thresh
 
 
 def raw_signal_fits(segs, read_start_rel_to_raw, n_raw):
@@ -1609,6 +1646,28 @@ class Engine(object):
         self._call('tba_segment_percentiles', v, off, n_seg, ql.shape[0], ql, qn.shape[0], qn, lin, near, C.byref(ms))
         self.last_plot_kernel_ms = ms.value
         return lin, near
+
+    def dwell_pctl_flags(self, segs, seg_off, pairs):
+        """tba_dwell_pctl_flags: the observations-per-base rule for reads given by their boundaries (int64 base starts
+        and the end, CSR by seg_off); pairs [(percentile, threshold), ...] -> (vals float64[n_reads, n_pairs]:
+        np.percentile(np.diff(segs of the read), percentile); flags bool[n_reads]: any value above its threshold).
+        A read of fewer than two boundaries: NaN and True.  `last_filter_kernel_ms`: kernel time."""
+        segs, off, q, thresh = _check_dwell_pctl_args(segs, seg_off, pairs)
+        n, ms = off.shape[0] - 1, f64(0.0)
+        vals, flags = np.empty((n, q.shape[0]), dtype=np.float64), np.zeros(n, dtype=np.uint8)
+        self._call('tba_dwell_pctl_flags', n, segs, off, q.shape[0], q, thresh, vals, flags, C.byref(ms))
+        self.last_filter_kernel_ms = ms.value
+        return vals, flags.astype(bool)
+
+    def batch_dwell_pctl_flags(self, pairs):
+        """tba_batch_dwell_pctl_flags: the same on the boundaries of the resident batch after a run (nothing but the
+        pairs is uploaded) -> (vals float64[n, n_pairs], flags bool[n]); a read that failed: NaN and False"""
+        q, thresh = _check_dwell_pairs(pairs)
+        ms = f64(0.0)
+        vals, flags = np.empty((self.n, q.shape[0]), dtype=np.float64), np.zeros(self.n, dtype=np.uint8)
+        self._call('tba_batch_dwell_pctl_flags', q.shape[0], q, thresh, vals, flags, C.byref(ms))
+        self.last_filter_kernel_ms = ms.value
+        return vals, flags.astype(bool)
 
     def region_raw_signal(self, raw, raw_off, segs, segs_off, read_start, rsrtr, minus, rna, shift, scale, lower_lim,
                           upper_lim, pair_read, pair_start, pair_end, genome_centric=True):

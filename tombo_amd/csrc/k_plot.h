@@ -16,7 +16,8 @@
 // np.percentile on a sorted pile v of n values, q the fraction numpy divides out on the host:
 //   nearest  v[around((n - 1) q)]                        (round half to even: rint)
 //   linear   vi = (n - 1) q, a = v[floor(vi)], b = v[min(floor(vi) + 1, n - 1)], t = vi - floor(vi):
-//            a + (b - a) t, and b - (b - a) (1 - t) where t >= 0.5      (numpy's _lerp)
+//            a + (b - a) t, and b - (b - a) (1 - t) where t >= 0.5      (numpy's _lerp: np_pctl_ranks and
+//            np_pctl_lerp of tba_common.h, shared with k_filter.h)
 // Products and sums stay apart (-ffp-contract=off, tba_common.h), so the bits are numpy's.
 //
 // Raw signal (get_r_raw_signal_data over th.get_raw_signal, tombo_helper.py:2090-2137, and
@@ -79,10 +80,10 @@ __global__ void k_plot_percentiles(i64 n_seg, const i32 *has_nan, const i64 *off
         if (j < n_ql) {
             double res = NAN;
             if (!none) {
-                const double vi = (double)(n - 1) * ql[j], fl = floor(vi);
-                const i64 lo = (i64)fl, hi = lo + 1 < n ? lo + 1 : n - 1;
-                const double lo_v = x[lo], hi_v = x[hi], t = vi - fl, d = hi_v - lo_v;
-                res = t >= 0.5 ? hi_v - d * (1.0 - t) : lo_v + d * t;
+                i64 lo, hi;
+                double t;
+                np_pctl_ranks(n, ql[j], lo, hi, t);
+                res = np_pctl_lerp(x[lo], x[hi], t);
             }
             lin[s * n_ql + j] = res;
         } else {

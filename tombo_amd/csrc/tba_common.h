@@ -242,6 +242,23 @@ __device__ __forceinline__ i64 shfl_i64(i64 v, int src)
     return ((i64)hi << 32) | (u32)lo;
 }
 
+// np.percentile's default linear form on n values sorted ascending, q the fraction numpy divides out
+// (k_plot.h, k_filter.h).  np_pctl_ranks: vi = (n - 1) q, the two ranks lo = floor(vi) and hi = min(lo + 1, n - 1)
+// it reads, and t = vi - floor(vi).  np_pctl_lerp: numpy's _lerp of the values at those ranks, a + (b - a) t, and
+// b - (b - a) (1 - t) where t >= 0.5; products and sums stay apart (-ffp-contract=off), so the bits are numpy's.
+__device__ __forceinline__ void np_pctl_ranks(i64 n, double q, i64 &lo, i64 &hi, double &t)
+{
+    const double vi = (double)(n - 1) * q, fl = floor(vi);
+    lo = (i64)fl;
+    hi = lo + 1 < n ? lo + 1 : n - 1;
+    t = vi - fl;
+}
+__device__ __forceinline__ double np_pctl_lerp(double lo_v, double hi_v, double t)
+{
+    const double d = hi_v - lo_v;
+    return t >= 0.5 ? hi_v - d * (1.0 - t) : lo_v + d * t;
+}
+
 // numpy pairwise summation of a contiguous float64 vector (DOUBLE_pairwise_sum); n <= 8192.
 // Iterative form of the recursion n -> (n2 = n/2 - (n/2)%8, n - n2) with leaves of <= 128.
 __device__ inline double np_pairwise_leaf(const double *a, i64 n)

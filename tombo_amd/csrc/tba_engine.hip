@@ -25,6 +25,7 @@
 #include "k_roc.h"
 #include "k_pdist.h"
 #include "k_plot.h"
+#include "k_filter.h"
 #include "k_norm_api.h"
 
 #include <algorithm>
@@ -521,8 +522,13 @@ extern "C" int tba_batch_upload_async(tba_engine *e, const tba_params *p, const 
     e->have_samp = samp_ind != nullptr;
     e->have_sv = sv_in != nullptr && sv_flags != nullptr;
     int rc = 0;
+    const size_t norm_out_was = e->d_norm_out.cap;
     for_each_batch_buffer(e, p, o, n, z, raw_dtype, [&](DevBuf *b, size_t bytes) { rc |= b->ensure(bytes); });
     if (rc) return TBA_E_NOMEM;
+    // a new d_norm_out starts as zeros: a download of it holds samples no kernel writes (past a read's norm_len, the
+    // reads that failed), and those must not be whatever the allocation held before (NaN left by another call's scratch)
+    if (e->d_norm_out.p && e->d_norm_out.cap != norm_out_was)
+        HIP_TRY(hipMemsetAsync(e->d_norm_out.p, 0, e->d_norm_out.cap, e->stream));
 
     hipStream_t s = e->stream;
     const size_t N = (size_t)n;
@@ -2843,6 +2849,84 @@ extern "C" int tba_segment_percentiles(tba_engine *e, const double *values, cons
     if (out_kernel_ms) *out_kernel_ms = tm.ms();
     if (n_ql > 0 && sc.get(out_lin, d_lin, n_seg * n_ql)) return sc.rc;
     return n_qn > 0 ? sc.get(out_near, d_near, n_seg * n_qn) : TBA_OK;
+}
+
+// ---- read filters (k_filter.h): dwell percentiles of every read and the "stuck" flag ----
+namespace {
+static int check_dwell_pairs(int64_t n_pairs, const double *q, const double *thresh)
+{
+    if (n_pairs < 1 || !q || !thresh) return set_err(TBA_E_ARG, "bad arguments");
+    if (const int rc = check_fractions(q, n_pairs)) return rc;
+    for (i64 j = 0; j < n_pairs; j++)
+        if (thresh[j] != thresh[j]) return set_err(TBA_E_ARG, "a NaN threshold");
+    return TBA_OK;
+}
+static unsigned dwell_grid(i64 n_reads) { return (unsigned)std::min<i64>(n_reads, 1024); }
+} // namespace
+
+extern "C" int tba_dwell_pctl_flags(tba_engine *e, int64_t n_reads, const int64_t *segs, const int64_t *seg_off,
+    int64_t n_pairs, const double *q, const double *thresh, double *out_vals, uint8_t *out_flags, double *out_kernel_ms)
+{
+    if (!e || n_reads < 0 || !seg_off || (n_reads > 0 && !out_flags)) return set_err(TBA_E_ARG, "bad arguments");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (const int rc = check_dwell_pairs(n_pairs, q, thresh)) return rc;
+    if (const int rc = check_csr_off(seg_off, n_reads)) return rc;
+    const i64 total = n_reads > 0 ? seg_off[n_reads] : 0;
+    if (total > 0 && !segs) return set_err(TBA_E_ARG, "bad arguments");
+    for (i64 r = 0; r < n_reads; r++) {
+        if (seg_off[r + 1] - seg_off[r] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "a read of 2^31 boundaries or more");
+        for (i64 i = seg_off[r]; i + 1 < seg_off[r + 1]; i++) {
+            if (segs[i + 1] < segs[i]) return set_err(TBA_E_ARG, "a decreasing boundary inside a read");
+            if ((u64)segs[i + 1] - (u64)segs[i] >= ((u64)1 << 31)) return set_err(TBA_E_ARG, "a length of 2^31 or more");
+        }
+    }
+    if (n_reads == 0) return TBA_OK;
+    Scratch sc(e);
+    DwellArgs a{};
+    a.n_reads = n_reads; a.n_pairs = n_pairs;
+    a.segs = sc.in(segs, total);
+    a.seg_off = sc.in(seg_off, n_reads + 1);
+    a.q = sc.in(q, n_pairs);
+    a.thresh = sc.in(thresh, n_pairs);
+    a.vals = out_vals ? sc.out<double>(n_reads * n_pairs) : nullptr;
+    a.flags = sc.out<uint8_t>(n_reads);
+    if (sc.rc) return sc.rc;
+    KernelTimer tm(sc, out_kernel_ms != nullptr);
+    k_dwell_pctl<false><<<dwell_grid(n_reads), DW_NT, 0, sc.stream>>>(a);
+    tm.stop();
+    if (sc.sync()) return sc.rc;
+    if (out_kernel_ms) *out_kernel_ms = tm.ms();
+    if (out_vals && sc.get(out_vals, a.vals, n_reads * n_pairs)) return sc.rc;
+    return sc.get(out_flags, a.flags, n_reads);
+}
+
+extern "C" int tba_batch_dwell_pctl_flags(tba_engine *e, int64_t n_pairs, const double *q, const double *thresh,
+    double *out_vals, uint8_t *out_flags, double *out_kernel_ms)
+{
+    if (!e || !e->ran) return set_err(TBA_E_STATE, "no batch has been run");
+    if (!out_flags) return set_err(TBA_E_ARG, "bad arguments");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (const int rc = check_dwell_pairs(n_pairs, q, thresh)) return rc;
+    const i64 n_reads = e->n_reads;
+    if (n_reads == 0) return TBA_OK;
+    Scratch sc(e);
+    sc.hip(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    DwellArgs a{};
+    a.n_reads = n_reads; a.n_pairs = n_pairs;
+    a.segs = e->d_segs.as<i64>();
+    a.rs = e->d_rs.as<ReadState>();
+    a.q = sc.in(q, n_pairs);
+    a.thresh = sc.in(thresh, n_pairs);
+    a.vals = out_vals ? sc.out<double>(n_reads * n_pairs) : nullptr;
+    a.flags = sc.out<uint8_t>(n_reads);
+    if (sc.rc) return sc.rc;
+    KernelTimer tm(sc, out_kernel_ms != nullptr);
+    k_dwell_pctl<true><<<dwell_grid(n_reads), DW_NT, 0, sc.stream>>>(a);
+    tm.stop();
+    if (sc.sync()) return sc.rc;
+    if (out_kernel_ms) *out_kernel_ms = tm.ms();
+    if (out_vals && sc.get(out_vals, a.vals, n_reads * n_pairs)) return sc.rc;
+    return sc.get(out_flags, a.flags, n_reads);
 }
 
 extern "C" int tba_region_raw_signal(tba_engine *e, int64_t n_reads, const void *raw, int raw_bytes,

@@ -178,6 +178,42 @@ def filter_and_index_record(rsqgl_res, fast5_fn, corr_grp, bc_subgrp, seq_samp_t
         rsqgl_res.mean_q_score, rsqgl_res.align_info.ID)
 
 
+def filter_and_index_records_batch(results, fast5_fns, corr_grp, bc_subgrp, seq_samp_type, sig_match_thresh,
+                                   obs_filter=None, engine=None, resident=False):
+    """`filter_and_index_record` for a whole finished batch, the observations-per-base percentiles on the device:
+    one Engine.dwell_pctl_flags call on the results' boundaries, or, with `resident`, Engine.batch_dwell_pctl_flags
+    on the boundaries the engine still holds -- `results` must then be the reads of its last batch, in order (an
+    entry that is an Exception, a failed read, gives None).  Returns the tuples of `filter_and_index_record`, read
+    by read."""
+    ok = [i for i, r in enumerate(results) if not isinstance(r, Exception)]
+    stuck = np.zeros(len(results), dtype=bool)
+    if obs_filter is not None and ok:
+        if engine is None:
+            from . import resquiggle as rq
+            engine = rq.get_engine()
+        if resident:
+            if engine.n != len(results):
+                raise ValueError('the resident batch holds %d reads, not %d' % (engine.n, len(results)))
+            stuck = engine.batch_dwell_pctl_flags(obs_filter)[1]
+        else:
+            segs = [np.asarray(results[i].segs, dtype=np.int64) for i in ok]
+            off = np.zeros(len(ok) + 1, dtype=np.int64)
+            np.cumsum([s.shape[0] for s in segs], out=off[1:])
+            stuck[ok] = engine.dwell_pctl_flags(np.concatenate(segs), off, obs_filter)[1]
+    out = []
+    for i, (res, fn) in enumerate(zip(results, fast5_fns)):
+        if isinstance(res, Exception):
+            out.append(None)
+            continue
+        loc = res.genome_loc
+        is_filtered = bool(res.sig_match_score > sig_match_thresh or stuck[i])
+        out.append((loc.Chrom, loc.Strand, th.readData(
+            loc.Start, loc.Start + len(res.segs) - 1, is_filtered, res.read_start_rel_to_raw, loc.Strand, fn,
+            corr_grp + '/' + bc_subgrp, seq_samp_type.rev_sig, res.sig_match_score, res.mean_q_score,
+            res.align_info.ID)))
+    return out
+
+
 def process_fast5_batch(fast5s, aligner, std_ref, rsqgl_params, seq_samp_type, save_params=None,
                         outlier_thresh=None, bc_grp='Basecall_1D_000',
                         bc_subgrp='BaseCalled_template', corr_grp='RawGenomeCorrected_000',

@@ -280,6 +280,44 @@ def parse_locs_file(locs_fn):
     return dict((cs, np.array(sorted(cs_poss))) for cs, cs_poss in raw_locs.items())
 
 
+def parse_genome_regions(all_regs_text):
+    """`--include-regions` texts ('chrm' or 'chrm:start-end', commas allowed in the numbers) -> {chrm: [[start,
+    end], ...], or None for a chromosome named whole anywhere} (tombo_helper.py:447-473); the message the
+    reference prints before exiting is raised as a TomboError"""
+    parsed_regs, include_whole_chrms = {}, set()
+    for reg_text in all_regs_text:
+        try:
+            chrm_reg = reg_text.replace('"', '').replace("'", "").split(':')
+            if len(chrm_reg) == 1:
+                chrm, reg_pos = chrm_reg[0], None
+                include_whole_chrms.add(chrm)
+            elif len(chrm_reg) == 2:
+                chrm, reg_pos = chrm_reg
+                reg_pos = [int(x.replace(',', '')) for x in reg_pos.split('-')]
+            else:
+                raise TomboError('Invalid region text provided.')
+        except Exception:
+            raise TomboError('Invalid [--include-region] format.')
+        parsed_regs.setdefault(chrm, []).append(reg_pos)
+    for chrm in include_whole_chrms:
+        parsed_regs[chrm] = None
+    return parsed_regs
+
+
+def parse_obs_filter(obs_filter):
+    """`--obs-per-base-filter` texts ('pctl:thresh', integers) -> [[pctl, thresh], ...], None for no text
+    (tombo_helper.py:508-524); a percentile outside [0, 100] is the reference's exit, raised here"""
+    if len(obs_filter) < 1:
+        return None
+    try:
+        obs_filter = [[int(v) for v in pctl_nobs.split(':')] for pctl_nobs in obs_filter]
+    except Exception:
+        raise TomboError('Invalid format for observation filter')
+    if any(pf[0] < 0 or pf[0] > 100 for pf in obs_filter):
+        raise TomboError('Invalid percentile value.')
+    return obs_filter
+
+
 class Fasta(object):
     """A FASTA file held in memory (tombo_helper.py:744-865, the branch without pyfaidx; `force_in_mem` is
     accepted for the reference's call sites and changes nothing).  Sequence is upper-cased and, when the first
