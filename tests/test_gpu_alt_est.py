@@ -1,4 +1,4 @@
-"""Alternate-model estimation on the device (csrc/k_kde.h: k_kmer_gather / k_kde_eval) against the live
+"""Alternate-model estimation on the device (csrc/k_kde.h: k_key_partition over KmerSrc / k_kde_eval) against the live
 reference (tests/golden/stats_alt_est.npz, written by gen_golden_alt_est.py).
 
 The gather has no tolerance: counts and levels are bit-equal and in the reference's order.  Densities:
@@ -49,6 +49,12 @@ def test_kmer_levels_one_call_many_chunks_and_a_completed_mask():
         counts, levels, lv_off = eng.kmer_levels(*args)
         assert counts.dtype == np.int64 and np.array_equal(counts, want[0]) and np.array_equal(lv_off, want[2])
         assert np.array_equal(ac.bits(levels), ac.bits(want[1]))
+    full = 3 * 4096   # the same batch cut off where its third chunk of 4096 positions is exactly full
+    cut = (args[0][:full], args[1][:full], np.minimum(off, full)) + args[3:]
+    want = stub.kmer_levels(*cut)
+    counts, levels, lv_off = eng.kmer_levels(*cut)
+    assert 0 < counts.sum() < full and np.array_equal(counts, want[0]) and np.array_equal(lv_off, want[2])
+    assert np.array_equal(ac.bits(levels), ac.bits(want[1]))
     empty = eng.kmer_levels(np.empty(0), np.empty(0, dtype=np.uint8), np.zeros(3, dtype=np.int64), ac.K, ac.CP, done)
     assert empty[0].sum() == 0 and empty[1].shape == (0,) and not empty[2].any()
 

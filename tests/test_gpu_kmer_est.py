@@ -79,10 +79,12 @@ def random_call(rng, n_reads, n_regions, n_keys, n_pos, n_ent, est_mean):
             rng.integers(0, n_pos, n_ent).astype(np.int64), ek.astype(np.int64), n_keys)
 
 
-@pytest.mark.parametrize('est_mean,n_keys,n_ent', [(False, 64, 9001), (True, 1000, 4097), (False, 1, 130), (True, 5, 0)])
+@pytest.mark.parametrize('est_mean,n_keys,n_ent', [(False, 64, 9001), (True, 1000, 4097), (False, 1, 130), (True, 5, 0),
+                                                   (False, 2, 4096), (True, 5, 8192)])
 def test_region_key_levels_against_the_numpy_form(est_mean, n_keys, n_ent):
-    """several chunks of entries, a key most entries share, keys nobody uses, positions no read covers, regions
-    without reads: counts, offsets and both columns bit-equal to the definition written out in numpy"""
+    """several chunks of entries (4096 each: one and two that are exactly full among them), a key most entries share,
+    keys nobody uses, one key (no key bits) and a key count that is no power of two, positions no read covers,
+    regions without reads: counts, offsets and both columns bit-equal to the definition written out in numpy"""
     eng = rq.get_engine()
     args = random_call(np.random.default_rng(n_keys + n_ent), 300, 9, n_keys, 700, n_ent, est_mean)
     want = stub.region_key_levels(*args[:-1], n_keys=n_keys)

@@ -147,6 +147,36 @@ def test_one_position_with_4100_reads(eng):
     assert off.tolist() == [0, n] and np.array_equal(levels, args[3][args[5]])
 
 
+@pytest.mark.parametrize('n_pos', [1, 63, 64, 65, 255, 256, 257, 513, 65537])
+def test_pile_offsets_across_the_steps_of_the_prefix_kernel(eng, n_pos):
+    """one region whose positions end on either side of a wavefront (64), of one 256-wide step of the exclusive
+    prefix, of two steps, and far beyond; a plus read over its first two thirds and a minus read over its middle,
+    so a position has 0, 1 or 2 levels, some of them NaN (dropped): the offsets are the running sum of the
+    coverage and the levels stand in read order"""
+    start = 100
+    a0, a_len = start - 3, 3 + (2 * n_pos + 2) // 3                 # read 0, '+': positions [0, (2 n + 2) / 3)
+    b0, b_len = start + n_pos // 3, n_pos - n_pos // 3 - n_pos // 5   # read 1, '-': positions [n / 3, n - n / 5)
+    a, b = np.arange(a_len, dtype=np.float64), 1e6 + np.arange(b_len, dtype=np.float64)
+    a[::7] = np.nan
+    b[::5] = np.nan
+    args = (np.array([a0, b0], dtype=np.int64), np.array([0, 1], dtype=np.uint8),
+            np.array([0, a_len, a_len + b_len], dtype=np.int64), np.concatenate([a, b]), np.array([0, 2], dtype=np.int64),
+            np.array([0, 1], dtype=np.int64), np.array([start], dtype=np.int64), np.array([start + n_pos], dtype=np.int64))
+    g = start + np.arange(n_pos, dtype=np.int64)
+    value = np.full((n_pos, 2), np.nan)
+    for k, (r0, genome_order) in enumerate(((a0, a), (b0, b[::-1]))):
+        inside = (g >= r0) & (g < r0 + genome_order.shape[0])
+        value[inside, k] = genome_order[g[inside] - r0]
+    kept = ~np.isnan(value)
+    cov = kept.sum(axis=1, dtype=np.int64)
+    if n_pos >= 63:
+        assert set(cov.tolist()) == {0, 1, 2}
+    off, levels, lin, near = eng.region_level_piles(*args)
+    assert lin is None and near is None
+    assert off.dtype == np.int64 and np.array_equal(off, np.concatenate([[0], np.cumsum(cov)]))
+    assert np.array_equal(levels, value[kept])
+
+
 def test_regions_without_a_covering_read(eng):
     args = list(pile_batch(np.random.default_rng(13), 4, 11, 3, 6))
     args[6] = args[6] + np.array([0, 5000, 0, 5000])        # two regions moved away from their reads

@@ -52,9 +52,10 @@ def test_deep_stack_twice_same_bits(c, eng):
         assert x.tobytes() == y.tobytes()
 
 
-@pytest.mark.parametrize('n', [1, 1023, 1024, 1025, 4097, 300001])
+@pytest.mark.parametrize('n', [1, 1023, 1024, 1025, 4097, 262143, 262144, 262145, 300001])
 def test_compaction_sizes(eng, n):
-    """around one block of 1024 elements, several blocks, and more blocks than one pass of the block scan (256)"""
+    """around one chunk of 1024 elements, several chunks, around the 256 chunks one step of the scan over the chunk
+    counts takes (1024 * 256 elements), and more chunks than that"""
     rng, stub = np.random.default_rng(n), NumpyTracksEngine()
     v = rng.normal(size=n)
     v[rng.random(n) < 0.4] = np.nan

@@ -2,6 +2,7 @@
 // device form of one Cython function, run as a batch of one.
 #pragma once
 #include "tba_common.h"
+#include "k_scan.h"
 #include "k_dp.h"
 #include "k_base_dp.h" // base_z, base_forward_row, base_traceback: one copy, shared with the batch pipeline (k_tail.h)
 
@@ -240,14 +241,6 @@ __global__ void k_c_llh_windows(int kind, const double *means, const double *ref
 //   floor_out (de novo): the result is floored at `smallest` once more (np.maximum keeps NaN).
 // Reads are CSR slices off[r]..off[r+1]; one thread per base.  erfc / log / exp / lgamma are the
 // device library's: parity with scipy is a stated tolerance (tests: 1e-12 relative).
-// row of flat index i in the CSR offsets off[n_rows + 1] (binary search)
-__device__ __forceinline__ i64 dev_csr_row(const i64 *off, i64 n_rows, i64 i)
-{
-    i64 lo = 0, hi = n_rows - 1;
-    while (lo < hi) { const i64 mid = (lo + hi + 1) >> 1; if (off[mid] <= i) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
 // the statistic of flat position i of a read that covers [a, b) of the three arrays
 __device__ __forceinline__ double dev_read_pval(const double *means, const double *ref_means,
     const double *ref_sds, i64 a, i64 b, i64 i, i64 fm, int floor_out, double smallest)

@@ -18,6 +18,7 @@
 //   k_ref_moments, k_ref_finish   get_reads_ref: mean / np.std in read order, median, prior blend
 #pragma once
 #include "tba_common.h"
+#include "k_scan.h"
 
 #define GRP_WAVE_MAX 64
 #define GRP_LDS_MAX 4096   // 32 KB of doubles per workgroup (four workgroups per CU by LDS)
@@ -64,26 +65,6 @@ __global__ void k_grp_pileup(GrpArgs a, i32 *cov, const i64 *lv_off, double *lev
         }
         if (!FILL) { cov[2 * gp] = n[0]; cov[2 * gp + 1] = n[1]; }
     }
-}
-
-// wavefront inclusive scans (64 lanes)
-__device__ __forceinline__ i64 wave_scan_add(i64 v)
-{
-    const int lane = threadIdx.x & 63;
-    for (int d = 1; d < 64; d <<= 1) { const i64 o = __shfl_up(v, d); if (lane >= d) v += o; }
-    return v;
-}
-__device__ __forceinline__ i32 wave_scan_max(i32 v)
-{
-    const int lane = threadIdx.x & 63;
-    for (int d = 1; d < 64; d <<= 1) { const i32 o = __shfl_up(v, d); if (lane >= d) v = o > v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ i32 wave_rscan_min(i32 v)   // suffix min
-{
-    const int lane = threadIdx.x & 63;
-    for (int d = 1; d < 64; d <<= 1) { const i32 o = __shfl_down(v, d); if (lane + d < 64) v = o < v ? o : v; }
-    return v;
 }
 
 // One wavefront (block of 64) per region.  A position is covered when every tested group has

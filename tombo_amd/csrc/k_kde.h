@@ -4,16 +4,12 @@
 //
 // Gather.  The reads are concatenated in read order (CSR by read_off: levels and base codes share
 // the offsets), so "read order, then position order" is ascending flat position p: the gather is a
-// stable partition of the window starts p by k-mer.  The positions are cut into chunks of
-// `chunk` consecutive positions, one wavefront per chunk, 64 positions per step:
-//   k_kmer_gather<false>  per chunk a row of 4^K counters
-//   k_kmer_colscan        per k-mer the exclusive prefix of its counters over the chunks, its total
-//   k_kmer_offsets        one wavefront: the k-mers' level offsets (exclusive prefix of the totals)
-//   k_kmer_gather<true>   the levels: lv_off[kmer] + the chunk's prefix + the rank inside the step
-// Inside a step the lanes that hold the same k-mer find each other with one ballot per key bit;
-// a lane's rank is the number of such lanes below it and the highest of them advances the chunk's
-// counter.  Work is split by position and never by k-mer, so the windows of a homopolymer run cost
-// what any other 64 windows cost.  No atomics: a row is touched by its own wavefront only.
+// stable partition of the window starts p by k-mer (k_scan.h), KmerSrc its source of keys:
+//   k_key_partition<false>  per chunk of positions a row of 4^K counters
+//   k_kmer_colscan          per k-mer the exclusive prefix of its counters over the chunks, its total
+//   k_exclusive_prefix      the k-mers' level offsets
+//   k_key_partition<true>   the levels: lv_off[kmer] + the chunk's prefix + the rank inside the step
+// The windows of a homopolymer run cost what any other 64 windows cost.
 //
 // Density.  dens[s][g] = sum_i exp(-0.5 ((x_g - l_i) / h)^2) / (n h sqrt(2 pi)) over the levels of
 // segment s, which is gaussian_kde(l, bw_method=h / l.std(ddof=1)).evaluate(x).
@@ -31,56 +27,33 @@
 // level left out contributes exactly zero.
 #pragma once
 #include "tba_common.h"
-#include "k_cabi.h"
-#include "k_group.h"
+#include "k_scan.h"
+#include "k_group.h"    // GRP_WAVE_MAX, GRP_LDS_MAX: the sorters' classes
 
 #define KDE_CUT 38.7
 
-struct KmerArgs {
-    i64 n_reads, total, chunk;      // total: all bases of the batch; chunk: positions per wavefront (multiple of 64)
+// the window starts of a read batch as the items of k_key_partition: the key of flat position p is the k-mer
+// of the window that starts there; -1: the window leaves its read, holds a base outside ACGT or its k-mer is
+// completed.  The level of the window's central base is what is gathered.
+struct KmerSrc {
+    i64 n_reads;
     int K, cp;
     const i64 *read_off;
     const uint8_t *codes, *completed;
     const double *means;
+    double *levels;
+
+    __device__ i64 key(i64 p) const
+    {
+        const i64 r = dev_csr_row(read_off, n_reads, p);
+        if (p + K > read_off[r + 1]) return -1;
+        const i64 k = window_kmer(codes + p, K);
+        return k >= 0 && !completed[k] ? k : -1;
+    }
+    __device__ void store(i64 p, i64 o) const { levels[o] = means[p + cp]; }
 };
 
-// One wavefront (block of 64) per chunk.  rows[chunk][kmer]: counted here (FILL false, zeroed
-// before), or the chunk's starting rank inside the k-mer's segment (FILL true, from k_kmer_colscan).
-template <bool FILL>
-__global__ void __launch_bounds__(64) k_kmer_gather(KmerArgs a, u32 *rows, const i64 *lv_off, double *levels)
-{
-    const int lane = threadIdx.x;
-    u32 *row = rows + ((i64)blockIdx.x << (2 * a.K));
-    const i64 p0 = (i64)blockIdx.x * a.chunk;
-    const i64 p1 = p0 + a.chunk < a.total ? p0 + a.chunk : a.total;
-    for (i64 c = p0; c < p1; c += 64) {
-        const i64 p = c + lane;
-        i64 key = -1;   // the k-mer of the window that starts at p; -1: no window, or not gathered
-        if (p < p1) {
-            const i64 r = dev_csr_row(a.read_off, a.n_reads, p);
-            if (p + a.K <= a.read_off[r + 1]) {
-                i64 k = 0;
-                bool acgt = true;
-                for (int j = 0; j < a.K; j++) { const unsigned b = a.codes[p + j]; acgt = acgt && b < 4; k = k * 4 + (b & 3); }
-                if (acgt && !a.completed[k]) key = k;
-            }
-        }
-        u64 peers = __ballot(key >= 0);
-        for (int b = 0; b < 2 * a.K; b++) {
-            const bool bit = (key >> b) & 1;
-            const u64 m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
-        if (key >= 0) {
-            const u32 rank = __popcll(peers & (((u64)1 << lane) - 1)), cnt = __popcll(peers);
-            const u32 cur = row[key];
-            if (FILL) levels[lv_off[key] + cur + rank] = a.means[p + a.cp];
-            if (rank == cnt - 1) row[key] = cur + cnt;
-        }
-        __syncthreads();   // (one wavefront: orders this step's counter stores before the next step's loads)
-    }
-}
-
+// rows[chunk][key] of a partition: the counts become each chunk's starting rank, counts[key] the key's total
 __global__ void k_kmer_colscan(i64 n_kmers, i64 n_chunks, u32 *rows, i64 *counts)
 {
     for (i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x; q < n_kmers; q += (i64)gridDim.x * blockDim.x) {
@@ -92,21 +65,6 @@ __global__ void k_kmer_colscan(i64 n_kmers, i64 n_chunks, u32 *rows, i64 *counts
         }
         counts[q] = run;
     }
-}
-
-// one wavefront: lv_off[n_kmers + 1]
-__global__ void k_kmer_offsets(i64 n_kmers, const i64 *counts, i64 *lv_off)
-{
-    const int lane = threadIdx.x;
-    i64 carry = 0;
-    for (i64 c = 0; c < n_kmers; c += 64) {
-        const i64 i = c + lane;
-        const i64 v = i < n_kmers ? counts[i] : 0;
-        const i64 inc = wave_scan_add(v);
-        if (i < n_kmers) lv_off[i] = carry + inc - v;
-        carry += __shfl(inc, 63);
-    }
-    if (lane == 0) lv_off[n_kmers] = carry;
 }
 
 // One wavefront per segment.  cov[s]: its size; has_nan[s]; lists: [0, S) wave, [S, 2S) workgroup,

@@ -4,14 +4,14 @@
 // Grouping.  The reads are concatenated in read order (CSR by read_off) as in k_kde.h, and the flat positions are cut
 // into chunks that never cross a read (the host lists them: KdChunk; a read's chunks are consecutive and every
 // chunk but a read's last is `chunk` positions long, a multiple of 64).  One wavefront per chunk, 64 windows a step,
-// the lanes of a k-mer found with one ballot per key bit, exactly as k_kmer_gather does:
+// each a step of the partition by key of k_scan.h:
 //   k_kd_gather<false>  per chunk a row of 4^K counters
 //   k_kd_read_scan      per (read, k-mer): the exclusive prefix of the counters over the read's chunks and the
 //                       read's count tab[read][kmer]; per read the number of distinct k-mers and the smallest count
 //   k_kd_select         one wavefront, an ordered scan over the reads: which are valid, which are examined before
 //                       num_reads were added, their labels 1, 2, ... (0: not taken)
 //   k_kd_kmer_totals    per k-mer over the taken reads: its levels and the reads that show it
-//   k_kmer_offsets      (k_kde.h) the exclusive prefixes of both
+//   k_exclusive_prefix  (k_scan.h) the exclusive prefixes of both
 //   k_kd_seg_bases      tab[read][kmer] becomes the first level of segment (kmer, read): k-mer major, taken reads in
 //                       label order; the read_mean form lists the non-empty segments per k-mer, compacted
 //   k_kd_gather<true>   the levels: tab[read][kmer] + the chunk's prefix + the rank inside the step
@@ -24,10 +24,10 @@
 //   k_kd_kmer_means     per k-mer, over its output run (the levels, or the compacted per-read means)
 // A lane sums a segment of at most 128 levels itself (one leaf of the pairwise tree: a serial loop is numpy's own
 // order); longer ones -- a homopolymer read makes one of thousands -- are summed by the whole wavefront
-// (wave_np_sum: the scheme of k_final_score, k_tail.h).
+// (wave_np_sum, k_scan.h: the scheme of k_final_score, k_tail.h).
 #pragma once
 #include "tba_common.h"
-#include "k_kde.h"
+#include "k_scan.h"
 
 struct KdChunk { i64 read, p0, p1; };   // flat positions [p0, p1) of one read
 
@@ -57,32 +57,17 @@ __global__ void __launch_bounds__(64) k_kd_gather(KdArgs a, u32 *rows, const i64
     const i64 read_end = a.read_off[ch.read + 1];
     for (i64 c = ch.p0; c < ch.p1; c += 64) {
         const i64 p = c + lane;
-        i64 key = -1;   // the k-mer of the window that starts at p; -1: no window, or a base outside ACGT
-        if (p < ch.p1 && p + a.K <= read_end) {
-            i64 k = 0;
-            bool acgt = true;
-            for (int j = 0; j < a.K; j++) { const unsigned b = a.codes[p + j]; acgt = acgt && b < 4; k = k * 4 + (b & 3); }
-            if (acgt) key = k;
-        }
-        u64 peers = __ballot(key >= 0);
-        for (int b = 0; b < 2 * a.K; b++) {
-            const bool bit = (key >> b) & 1;
-            const u64 m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
+        // the k-mer of the window that starts at p; -1: no window, or a base outside ACGT
+        const i64 key = p < ch.p1 && p + a.K <= read_end ? window_kmer(a.codes + p, a.K) : -1;
+        const u64 peers = wave_key_peers(key, 2 * a.K, key >= 0);
         if (key >= 0) {
-            const u32 rank = __popcll(peers & (((u64)1 << lane) - 1)), cnt = __popcll(peers);
-            const u32 cur = row[key];
-            if (FILL) {
-                const i64 at = (i64)base[key] + cur + rank;
-                if (at < a.n_lv) {   // (always: the offsets come from the same counts)
-                    levels[at] = a.means[p + a.cp];
-                    if (labels_out) labels_out[at] = lab;
-                }
+            const i64 at = (i64)partition_step(peers, row, key) + (FILL ? base[key] : 0);
+            if (FILL && at < a.n_lv) {   // (always: the offsets come from the same counts)
+                levels[at] = a.means[p + a.cp];
+                if (labels_out) labels_out[at] = lab;
             }
-            if (rank == cnt - 1) row[key] = cur + cnt;
         }
-        __syncthreads();   // (one wavefront: orders this step's counter stores before the next step's loads)
+        __syncthreads();   // between two steps: see partition_step
     }
 }
 
@@ -163,58 +148,6 @@ __global__ void k_kd_seg_bases(i64 n_kmers, i64 n_sel, const i64 *sel, u32 *tab,
             run += c;
         }
     }
-}
-
-// np.add.reduce of a[0 .. n) by one wavefront (all lanes call it with the same a, n; the result is valid in lane
-// 0): per block of 8192 values lane 0 lists the leaves of the pairwise tree (pre-order, left first: at most
-// 127), the lanes sum a leaf each, lane 0 adds the leaf sums in the recursion's order.
-struct WaveSumLds {
-    int l_start[128], l_len[128], n_leaf;
-    double l_sum[128];
-    int st_a[16], st_n[16], st_st[16];
-    double st_v[16];
-};
-__device__ inline double wave_np_sum(const double *a, i64 n, WaveSumLds &w, int lane)
-{
-    double acc = 0.0;
-    for (i64 c0 = 0; c0 < n; c0 += 8192) {
-        const int m = (int)(n - c0 < 8192 ? n - c0 : 8192);
-        if (lane == 0) {
-            int sp = 0, nl = 0;
-            w.st_a[0] = 0; w.st_n[0] = m;
-            while (sp >= 0) {
-                const int s0 = w.st_a[sp], len = w.st_n[sp];
-                sp--;
-                if (len <= 128) { w.l_start[nl] = s0; w.l_len[nl] = len; nl++; continue; }
-                int n2 = len / 2;
-                n2 -= n2 % 8;
-                w.st_a[sp + 1] = s0 + n2; w.st_n[sp + 1] = len - n2; // right, visited after ...
-                w.st_a[sp + 2] = s0; w.st_n[sp + 2] = n2;            // ... the left half
-                sp += 2;
-            }
-            w.n_leaf = nl;
-        }
-        __syncthreads();
-        for (int k = lane; k < w.n_leaf; k += 64) w.l_sum[k] = np_pairwise_leaf(a + c0 + w.l_start[k], w.l_len[k]);
-        __syncthreads();
-        if (lane == 0) { // the recursion again, leaf values from l_sum in visiting order
-            int sp = 0, next = 0;
-            double ret = 0;
-            w.st_n[0] = m; w.st_st[0] = 0;
-            while (sp >= 0) {
-                const int len = w.st_n[sp];
-                if (len <= 128) { ret = w.l_sum[next++]; sp--; continue; }
-                int n2 = len / 2;
-                n2 -= n2 % 8;
-                if (w.st_st[sp] == 0) { w.st_st[sp] = 1; w.st_n[sp + 1] = n2; w.st_st[sp + 1] = 0; sp++; }
-                else if (w.st_st[sp] == 1) { w.st_v[sp] = ret; w.st_st[sp] = 2; w.st_n[sp + 1] = len - n2; w.st_st[sp + 1] = 0; sp++; }
-                else { ret = w.st_v[sp] + ret; sp--; }
-            }
-            acc += ret;
-        }
-        __syncthreads();
-    }
-    return acc;
 }
 
 // The read_mean form: values[e] = np.mean of listed segment e.  One wavefront (block of 64) per 64 segments: a lane

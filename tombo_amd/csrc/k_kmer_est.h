@@ -9,73 +9,60 @@
 //   positions  the wanted positions: (region, genomic position), each computed once
 //   entries    (position index, key) in output order: region, position, entry
 // Steps of region_key_levels:
-//   k_kest_pileup<false>  reads per position (one thread per position, the region's reads in order)
-//   k_kest_offsets        one workgroup: level offsets of the positions (exclusive prefix)
-//   k_kest_pileup<true>   the levels in read order; a minus-strand read is reversed to genome order;
-//                         NaN levels are kept (they count towards the coverage, get_reads_events)
-//   k_kest_moments        per position np.std (np_sum_by order) in read order, or with est_mean the
-//                         pair of c_mean_std (_c_helper.pyx:22-36: left-to-right sums)
+//   k_region_pileup<false>  reads per position (one thread per position, the region's reads in order)
+//   k_exclusive_prefix      level offsets of the positions (k_scan.h)
+//   k_region_pileup<true>   the levels in read order; a minus-strand read is reversed to genome order;
+//                           NaN levels are kept (they count towards the coverage, get_reads_events)
+//   k_kest_moments          per position np.std (np_sum_by order) in read order, or with est_mean the
+//                           pair of c_mean_std (_c_helper.pyx:22-36: left-to-right sums)
 //   k_kde_classify, k_grp_sort_*   without est_mean: the positions' levels sorted (k_kde.h, k_group.h)
-//   k_kest_median         np.median of each sorted segment
-//   k_kest_partition      the entries stably partitioned by key into the two output columns
-// The partition is k_kmer_gather's scheme (k_kde.h) with the key read from the entry: entries are
-// cut into chunks, one wavefront per chunk, 64 entries a step; the lanes of a step that hold the
-// same key find each other with one ballot per key bit.  Work is split by entry and never by key.
+//   k_kest_median           np.median of each sorted segment
+//   k_key_partition         the entries stably partitioned by key into the two output columns (k_scan.h,
+//                           EntSrc its source of keys)
 // No floating-point atomics anywhere, every sum in a fixed order: two runs give the same bits.
 // segment_medians is k_kde_classify, the sorters and k_kest_median on a copy of the values.
+// k_region_pileup also piles the levels of the plot regions (k_plot.h), whose positions are dense.
 #pragma once
 #include "tba_common.h"
-#include "k_group.h"
-#include "k_kde.h"
+#include "k_scan.h"
 
-struct KestArgs {
-    i64 n_pos;
-    const i64 *pos_reg, *pos_g;              // per wanted position: its region, its genomic position
+// the reads of a batch of regions
+struct RegionReads {
     const i64 *reg_read_off, *reg_reads;     // per region: its reads, in its read order
     const i64 *read_start, *read_off;
     const uint8_t *read_minus;               // 1: minus strand (levels reversed to genome order)
     const double *means;                     // read-centric, CSR by read_off
 };
 
-// One thread per wanted position.  lv_off: n_pos + 1 offsets (FILL); cov: the reads per position.
-template <bool FILL>
-__global__ void k_kest_pileup(KestArgs a, i32 *cov, const i64 *lv_off, double *levels)
+// the positions of a pile-up: locate(p, r, g) gives position p's region and genomic position; keep_nan: a NaN
+// level counts and is stored like any other.  ListedPos: the wanted positions, each listed by the host.
+struct ListedPos {
+    static constexpr bool keep_nan = true;
+    const i64 *pos_reg, *pos_g;
+    __device__ void locate(i64 p, i64 &r, i64 &g) const { r = pos_reg[p]; g = pos_g[p]; }
+};
+
+// One thread per position.  lv_off: n_pos + 1 offsets (FILL); cov: the levels per position.
+template <bool FILL, class Pos>
+__global__ void k_region_pileup(RegionReads a, Pos pos, i64 n_pos, i32 *cov, const i64 *lv_off, double *levels)
 {
-    for (i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x; p < a.n_pos; p += (i64)gridDim.x * blockDim.x) {
-        const i64 r = a.pos_reg[p], g = a.pos_g[p];
+    for (i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x; p < n_pos; p += (i64)gridDim.x * blockDim.x) {
+        i64 r, g;
+        pos.locate(p, r, g);
         i64 cur = FILL ? lv_off[p] : 0;
         i32 n = 0;
         for (i64 q = a.reg_read_off[r]; q < a.reg_read_off[r + 1]; q++) {
             const i64 rd = a.reg_reads[q];
             const i64 len = a.read_off[rd + 1] - a.read_off[rd], s = a.read_start[rd];
             if (g < s || g >= s + len) continue;
-            if (FILL) levels[cur++] = a.means[a.read_off[rd] + (a.read_minus[rd] ? len - 1 - (g - s) : g - s)];
+            double v = 0.0;
+            if (FILL || !Pos::keep_nan) v = a.means[a.read_off[rd] + (a.read_minus[rd] ? len - 1 - (g - s) : g - s)];
+            if (!Pos::keep_nan && v != v) continue;
+            if (FILL) levels[cur++] = v;
             else n++;
         }
         if (!FILL) cov[p] = n;
     }
-}
-
-// One workgroup of 256: off[n + 1], the exclusive prefix of cov.  Every thread owns one run of
-// consecutive positions; the runs' totals are scanned in LDS.
-__global__ void __launch_bounds__(256) k_kest_offsets(i64 n, const i32 *cov, i64 *off)
-{
-    __shared__ i64 part[256];
-    const i64 run = (n + 255) / 256;
-    const i64 a = (i64)threadIdx.x * run < n ? (i64)threadIdx.x * run : n;
-    const i64 b = a + run < n ? a + run : n;
-    i64 tot = 0;
-    for (i64 i = a; i < b; i++) tot += cov[i];
-    part[threadIdx.x] = tot;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        i64 acc = 0;
-        for (int t = 0; t < 256; t++) { const i64 v = part[t]; part[t] = acc; acc += v; }
-        off[n] = acc;
-    }
-    __syncthreads();
-    i64 acc = part[threadIdx.x];
-    for (i64 i = a; i < b; i++) { off[i] = acc; acc += cov[i]; }
 }
 
 // One thread per position, levels in read order.  est_mean: level = the sequential mean, sd =
@@ -115,37 +102,18 @@ __global__ void k_kest_median(i64 n_seg, const i32 *has_nan, const i64 *lv_off, 
     }
 }
 
-// One wavefront (block of 64) per chunk of `chunk` consecutive entries (a multiple of 64).
-// rows[chunk][key]: counted here (FILL false, zeroed before), or the chunk's starting rank inside
-// the key's segment (FILL true, from k_kmer_colscan).  key_bits: bits that tell the keys apart.
-template <bool FILL>
-__global__ void __launch_bounds__(64) k_kest_partition(i64 n_ent, i64 chunk, i64 n_keys, int key_bits,
-    const i64 *ent_pos, const i64 *ent_key, u32 *rows, const i64 *key_off, const double *level,
-    const double *sd, double *out_levels, double *out_sds)
-{
-    const int lane = threadIdx.x;
-    u32 *row = rows + (i64)blockIdx.x * n_keys;
-    const i64 e0 = (i64)blockIdx.x * chunk;
-    const i64 e1 = e0 + chunk < n_ent ? e0 + chunk : n_ent;
-    for (i64 c = e0; c < e1; c += 64) {
-        const i64 e = c + lane;
-        const i64 key = e < e1 ? ent_key[e] : -1;
-        u64 peers = __ballot(key >= 0);
-        for (int b = 0; b < key_bits; b++) {
-            const bool bit = (key >> b) & 1;
-            const u64 m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
-        if (key >= 0) {
-            const u32 rank = __popcll(peers & (((u64)1 << lane) - 1)), cnt = __popcll(peers);
-            const u32 cur = row[key];
-            if (FILL) {
-                const i64 o = key_off[key] + cur + rank, p = ent_pos[e];
-                out_levels[o] = level[p];
-                out_sds[o] = sd[p];
-            }
-            if (rank == cnt - 1) row[key] = cur + cnt;
-        }
-        __syncthreads();   // (one wavefront: orders this step's counter stores before the next step's loads)
+// the entries as the items of k_key_partition: entry e has the key ent_key[e] and takes the level and the sd
+// of its position
+struct EntSrc {
+    const i64 *ent_pos, *ent_key;
+    const double *level, *sd;
+    double *out_levels, *out_sds;
+
+    __device__ i64 key(i64 e) const { return ent_key[e]; }
+    __device__ void store(i64 e, i64 o) const
+    {
+        const i64 p = ent_pos[e];
+        out_levels[o] = level[p];
+        out_sds[o] = sd[p];
     }
-}
+};

@@ -27,15 +27,14 @@
 // k_norm_apply.  (x - shift) / scale, clipped as c_apply_outlier_thresh clips (_c_helper.pyx:73-87) where the read
 // has limits; a grid over the samples of all reads, the read of a sample by binary search in the output offsets.
 //
-// Sums.  np.add.reduce of a contiguous float64 array: wave_np_sum (k_kmer_dist.h), one wavefront per read.  The
+// Sums.  np.add.reduce of a contiguous float64 array: wave_np_sum (k_scan.h), one wavefront per read.  The
 // terms are products and quotients of the inputs, so the wavefront writes them to a scratch row first (numpy
 // makes the same temporaries) and sums that.
 #pragma once
 #include "tba_common.h"
 #include "k_select.h"
 #include "k_segment.h"    // raw_is_int
-#include "k_cabi.h"       // dev_csr_row
-#include "k_kmer_dist.h"  // wave_np_sum
+#include "k_scan.h"
 
 struct NormApiArgs {
     i64 n_reads;

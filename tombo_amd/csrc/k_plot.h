@@ -4,11 +4,11 @@
 // Level piles (get_r_boxplot_data / get_r_quant_data / get_r_event_data over intervalData.get_base_levels,
 // tombo_helper.py:1976-2032).  Region r covers [reg_start[r], reg_end[r]); its positions are numbered
 // reg_pos_off[r] + i over the batch.  Steps of region_level_piles:
-//   k_plot_pileup<false>  levels per position: one thread per position, the region's reads in order; a read
-//                         that does not cover the position and a NaN level count nothing (the frames drop
-//                         NaN; the k-mer estimation's pile-up of k_kmer_est.h keeps it)
-//   k_kest_offsets        the positions' level offsets (k_kmer_est.h, as it is)
-//   k_plot_pileup<true>   the levels in read order; a minus-strand read is reversed to genome order
+//   k_region_pileup<false>  (k_kmer_est.h, over DensePos) levels per position: one thread per position, the
+//                         region's reads in order; a read that does not cover the position and a NaN level
+//                         count nothing (the frames drop NaN; the k-mer estimation's pile-up keeps it)
+//   k_exclusive_prefix    the positions' level offsets (k_scan.h)
+//   k_region_pileup<true> the levels in read order; a minus-strand read is reversed to genome order
 //   k_kde_classify, k_grp_sort_*   a copy of the piles sorted ascending (k_kde.h, k_group.h)
 //   k_plot_percentiles    one thread per (position, quantile): np.percentile, linear and 'nearest'
 // segment_percentiles is the last two steps on caller-given segments.
@@ -24,7 +24,7 @@
 // normalize_raw_signal with the read's stored scale values).  A pair is (read, region):
 //   k_plot_sig_sizes   one thread per pair: the overlap slice of the read's segments, the start offset, the
 //                      first raw sample and the sample count
-//   k_kest_offsets     the pairs' sample offsets
+//   k_exclusive_prefix the pairs' sample offsets
 //   k_plot_sig_fill    one thread per output sample: its base by binary search in the pair's slice, the raw
 //                      sample (whole signal reversed for RNA, window reversed for '-'), (raw - shift) / scale,
 //                      the clip of c_apply_outlier_thresh, Position = (start + base + offset) + i * (1.0 / n)
@@ -32,39 +32,20 @@
 // No floating-point atomics, every output at a fixed place: two runs give the same bits.
 #pragma once
 #include "tba_common.h"
-#include "k_cabi.h"      // dev_csr_row
-#include "k_kmer_est.h"  // k_kest_offsets
+#include "k_scan.h"
+#include "k_kmer_est.h"  // k_region_pileup
 
-struct PlotPileArgs {
-    i64 n_regions, n_pos;
+// the positions of k_region_pileup for plot regions: every position of every region, numbered over the batch
+struct DensePos {
+    static constexpr bool keep_nan = false;
+    i64 n_regions;
     const i64 *reg_pos_off, *reg_start;      // per region: its first position of the batch, its genomic start
-    const i64 *reg_read_off, *reg_reads;     // per region: its reads, in its read order
-    const i64 *read_start, *read_off;
-    const uint8_t *read_minus;               // 1: minus strand (levels reversed to genome order)
-    const double *means;                     // read-centric, CSR by read_off
-};
-
-// One thread per position.  lv_off: n_pos + 1 offsets (FILL); cov: the levels per position.
-template <bool FILL>
-__global__ void k_plot_pileup(PlotPileArgs a, i32 *cov, const i64 *lv_off, double *levels)
-{
-    for (i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x; p < a.n_pos; p += (i64)gridDim.x * blockDim.x) {
-        const i64 r = dev_csr_row(a.reg_pos_off, a.n_regions, p);
-        const i64 g = a.reg_start[r] + (p - a.reg_pos_off[r]);
-        i64 cur = FILL ? lv_off[p] : 0;
-        i32 n = 0;
-        for (i64 q = a.reg_read_off[r]; q < a.reg_read_off[r + 1]; q++) {
-            const i64 rd = a.reg_reads[q];
-            const i64 len = a.read_off[rd + 1] - a.read_off[rd], s = a.read_start[rd];
-            if (g < s || g >= s + len) continue;
-            const double v = a.means[a.read_off[rd] + (a.read_minus[rd] ? len - 1 - (g - s) : g - s)];
-            if (v != v) continue;
-            if (FILL) levels[cur++] = v;
-            else n++;
-        }
-        if (!FILL) cov[p] = n;
+    __device__ void locate(i64 p, i64 &r, i64 &g) const
+    {
+        r = dev_csr_row(reg_pos_off, n_regions, p);
+        g = reg_start[r] + (p - reg_pos_off[r]);
     }
-}
+};
 
 // One thread per (segment, quantile): the n_ql linear quantiles, then the n_qn nearest ones.  v: the
 // segments sorted ascending unless has_nan; an empty segment and one with a NaN give NaN.

@@ -15,8 +15,8 @@
 // label = in the modified one (binary searches).
 // Every read of the sequence and of the lists is bounds-checked against the block's own slice
 // before its address is formed.  The kept pairs are compacted per motif in record order: flags ->
-// per-workgroup counts (k_roc_count) -> scan (k_trk_scan_blocks) -> write (k_roc_scatter), chunks
-// of TRK_CHUNK records, grid.y = motif, all motifs back to back in one output.
+// per-chunk counts (k_chunk_total over RocKept) -> scan (k_exclusive_prefix) -> write (k_roc_scatter),
+// chunks of SCAN_CHUNK records (k_scan.h), grid.y = motif, all motifs back to back in one output.
 //
 // Rank counts.  tp_at[j] = number of True labels among the ranks[j] + 1 first entries in
 // (statistic, label) order.  The statistic becomes the order-preserving key of k_select.h (f64_key,
@@ -27,19 +27,19 @@
 // One pass = three kernels, each finished before the next starts (no workgroup ever waits for
 // another):
 //   k_roc_hist     digit counts of every tile of ROC_SORT_TILE entries -> table[digit][tile]
-//   scan           exclusive prefix of the table in that (digit-major) order: k_roc_tab_count,
-//                  k_trk_scan_blocks, k_roc_tab_apply
+//   scan           exclusive prefix of the table in that (digit-major) order: k_chunk_total over
+//                  ArrayCount<u32>, k_exclusive_prefix, k_roc_tab_apply
 //   k_roc_scatter_pass   each wavefront owns ROC_SORT_TILE / 4 consecutive entries of the tile; the
 //                  wavefronts' digit counts (LDS) give each its first output index per digit, then
 //                  a wavefront walks its entries 64 at a time in element order and ranks equal
-//                  digits by __ballot matching (64-bit masks), which keeps the order of equal digits.
+//                  digits among their peers (wave_key_peers), which keeps the order of equal digits.
 // All counters are integers (LDS and global integer atomics in the histograms only), so the result
 // does not depend on the order of those adds.  After the last pass the labels are scanned in
-// chunks of TRK_CHUNK and k_roc_gather reads the inclusive count at every rank.
+// chunks of SCAN_CHUNK (k_chunk_total over ArrayCount<uint8_t>) and k_roc_gather reads the inclusive
+// count at every rank.
 #pragma once
 #include "tba_common.h"
-#include "k_group.h"
-#include "k_tracks.h"
+#include "k_scan.h"
 
 #define ROC_SORT_TILE 4096          // entries per workgroup per pass: 4 wavefronts x 16 steps x 64
 #define ROC_WAVE_SPAN (ROC_SORT_TILE / 4)
@@ -120,17 +120,19 @@ struct RocLocLabel {
     }
 };
 
-// kept pairs per chunk of TRK_CHUNK records: block_cnt[motif * gridDim.x + chunk]
+// the count functors of k_chunk_total: whether (record i, motif m) is kept under the label functor f ...
 template <class F>
-__global__ void __launch_bounds__(256) k_roc_count(F f, RocRecs R, i64 *block_cnt)
-{
-    __shared__ i64 lds[4];
-    const i64 i0 = (i64)blockIdx.x * TRK_CHUNK + threadIdx.x * 4;
-    i64 c = 0, total;
-    for (int j = 0; j < 4; j++) if (i0 + j < R.n_rec) c += f(R, i0 + j, (int)blockIdx.y) & 1;
-    trk_block_scan(c, lds, total);
-    if (threadIdx.x == 0) block_cnt[(i64)blockIdx.y * gridDim.x + blockIdx.x] = total;
-}
+struct RocKept {
+    F f;
+    RocRecs R;
+    __device__ int operator()(i64 i, int m) const { return f(R, i, m) & 1; }
+};
+// ... and the words of an array themselves
+template <class T>
+struct ArrayCount {
+    const T *v;
+    __device__ T operator()(i64 i, int) const { return v[i]; }
+};
 
 // the kept pairs in (motif, record) order from block_base on; out_index (may be NULL): the record
 template <class F>
@@ -138,13 +140,13 @@ __global__ void __launch_bounds__(256) k_roc_scatter(F f, RocRecs R, const i64 *
     uint8_t *out_label, i64 *out_index)
 {
     __shared__ i64 lds[4];
-    const i64 i0 = (i64)blockIdx.x * TRK_CHUNK + threadIdx.x * 4;
+    const i64 i0 = (i64)blockIdx.x * SCAN_CHUNK + threadIdx.x * 4;
     int fl[4];
-    i64 c = 0, t;
-    for (int j = 0; j < 4; j++) { fl[j] = i0 + j < R.n_rec ? f(R, i0 + j, (int)blockIdx.y) : 0; c += fl[j] & 1; }
-    i64 at = block_base[(i64)blockIdx.y * gridDim.x + blockIdx.x] + trk_block_scan(c, lds, t);
+    i64 keep[4], t;
+    const auto flag = [&](i64 i, int m) { return (fl[i - i0] = f(R, i, m)) & 1; };
+    i64 at = block_base[(i64)blockIdx.y * gridDim.x + blockIdx.x] + chunk_scan(R.n_rec, flag, lds, keep, t);
     for (int j = 0; j < 4; j++)
-        if (fl[j] & 1) {
+        if (keep[j]) {
             out_stat[at] = R.rec_stat[i0 + j];
             out_label[at] = (uint8_t)(fl[j] >> 1);
             if (out_index) out_index[at] = i0 + j;
@@ -209,24 +211,14 @@ __global__ void __launch_bounds__(256) k_roc_hist(i64 n, int pass, int n_digits,
     for (int k = threadIdx.x; k < n_digits; k += 256) table[(i64)k * gridDim.x + blockIdx.x] = h[k];
 }
 
-// scan of the table (m words, every prefix below 2^31): chunk sums, then the exclusive prefix in place
-__global__ void __launch_bounds__(256) k_roc_tab_count(i64 m, const u32 *table, i64 *block_cnt)
-{
-    __shared__ i64 lds[4];
-    const i64 i0 = (i64)blockIdx.x * TRK_CHUNK + threadIdx.x * 4;
-    i64 c = 0, total;
-    for (int j = 0; j < 4; j++) if (i0 + j < m) c += table[i0 + j];
-    trk_block_scan(c, lds, total);
-    if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
-}
+// scan of the table (m words, every prefix below 2^31): after the chunk sums and their prefix (block_base),
+// the exclusive prefix in place
 __global__ void __launch_bounds__(256) k_roc_tab_apply(i64 m, u32 *table, const i64 *block_base)
 {
     __shared__ i64 lds[4];
-    const i64 i0 = (i64)blockIdx.x * TRK_CHUNK + threadIdx.x * 4;
-    u32 v[4];
-    i64 c = 0, t;
-    for (int j = 0; j < 4; j++) { v[j] = i0 + j < m ? table[i0 + j] : 0; c += v[j]; }
-    i64 at = block_base[blockIdx.x] + trk_block_scan(c, lds, t);
+    const i64 i0 = (i64)blockIdx.x * SCAN_CHUNK + threadIdx.x * 4;
+    i64 v[4], t;
+    i64 at = block_base[blockIdx.x] + chunk_scan(m, ArrayCount<u32>{table}, lds, v, t);
     for (int j = 0; j < 4; j++)
         if (i0 + j < m) { table[i0 + j] = (u32)at; at += v[j]; }
 }
@@ -257,12 +249,7 @@ __global__ void __launch_bounds__(256) k_roc_scatter_pass(i64 n, int pass, int n
         const u64 k = live ? key[i] : 0;
         const u32 lab = live ? label[i] : 0;
         const u32 d = roc_digit(k, lab, pass);
-        u64 peers = __ballot(live);
-        for (int b = 0; b < 9; b++) {
-            const bool bit = (d >> b) & 1;
-            const u64 m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
+        const u64 peers = wave_key_peers(d, 9, live);
         if (live) {
             const u32 rank = __popcll(peers & (((u64)1 << lane) - 1)), c = __popcll(peers);
             const u32 cur = cnt[w][d];
@@ -276,17 +263,6 @@ __global__ void __launch_bounds__(256) k_roc_scatter_pass(i64 n, int pass, int n
     }
 }
 
-// True labels per chunk of TRK_CHUNK sorted entries
-__global__ void __launch_bounds__(256) k_roc_label_count(i64 n, const uint8_t *label, i64 *block_cnt)
-{
-    __shared__ i64 lds[4];
-    const i64 i0 = (i64)blockIdx.x * TRK_CHUNK + threadIdx.x * 4;
-    i64 c = 0, total;
-    for (int j = 0; j < 4; j++) if (i0 + j < n) c += label[i0 + j];
-    trk_block_scan(c, lds, total);
-    if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
-}
-
 // tp_at[j]: True labels among the ranks[j] + 1 first sorted entries; a rank outside [0, n) sets *bad
 __global__ void k_roc_gather(i64 n, i64 n_ranks, const i64 *ranks, const uint8_t *label, const i64 *block_base,
     i64 *tp_at, i32 *bad)
@@ -294,9 +270,9 @@ __global__ void k_roc_gather(i64 n, i64 n_ranks, const i64 *ranks, const uint8_t
     for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < n_ranks; j += (i64)gridDim.x * blockDim.x) {
         const i64 r = ranks[j];
         if (r < 0 || r >= n) { *bad = 1; tp_at[j] = 0; continue; }
-        const i64 c = r / TRK_CHUNK;
+        const i64 c = r / SCAN_CHUNK;
         i64 sum = block_base[c];
-        for (i64 i = c * TRK_CHUNK; i <= r; i++) sum += label[i];
+        for (i64 i = c * SCAN_CHUNK; i <= r; i++) sum += label[i];
         tp_at[j] = sum;
     }
 }

@@ -19,7 +19,7 @@
 #pragma once
 #include "tba_common.h"
 #include "k_cabi.h"
-#include "k_group.h"
+#include "k_scan.h"
 
 struct SiteArgs {
     i64 n_tracks;

@@ -17,10 +17,10 @@
 // every thread takes them TRK_U at a time: the value loads of TRK_U reads are issued first, the
 // adds follow in list order (memory-level parallelism: the note at the top of k_select.h).
 //
-// Ordered compaction (k_trk_count, k_trk_scan_blocks, k_trk_scatter): flag, scan, scatter over
-// blocks of TRK_CHUNK consecutive elements, order kept.  The flag is one of TRK_KEEP_*; the same
-// three kernels serve the NaN filter, the run-length form of a coverage track and the two
-// selections of the top-N search.
+// Ordered compaction: flag, scan, scatter over chunks of SCAN_CHUNK consecutive elements, order kept
+// (k_chunk_total and k_exclusive_prefix of k_scan.h, then k_trk_scatter).  The flag is one of
+// TRK_KEEP_* (TrkKeep); the same three kernels serve the NaN filter, the run-length form of a coverage
+// track and the two selections of the top-N search.
 //
 // Top N.  |a - b| after nan_to_num is non-negative, so its bit pattern orders like the value.  Eight
 // passes of a 256-bin histogram over the whole grid (integer atomics: counts do not depend on
@@ -29,12 +29,11 @@
 // equal it as are still missing, the HIGHEST positions first.
 #pragma once
 #include "tba_common.h"
-#include "k_group.h"
+#include "k_scan.h"
 
 #define TRK_TILE 256        // positions per tile = threads per workgroup of k_trk_add
 #define TRK_MAX_SLOTS 3
 #define TRK_U 4             // reads whose loads are in flight together
-#define TRK_CHUNK 1024      // elements per workgroup of the compaction kernels: 256 threads x 4 consecutive
 
 // read_flags: bit 0 minus strand (the slot arrays are read-centric: reversed to genome order);
 // bit 1 + s: the read has slot s
@@ -136,33 +135,8 @@ __global__ void k_trk_diff(i64 n, const double *a, const double *b, double *out,
 // ---- ordered compaction ------------------------------------------------------------------------
 enum { TRK_KEEP_NOT_NAN = 0,   // x: float64 bits; keeps what is not NaN
        TRK_KEEP_RUN_START,     // x: int64; keeps i == 0 and every i with x[i] != x[i - 1]
-       TRK_KEEP_ABOVE,         // x: keys; keeps x[i] > K
-       TRK_KEEP_EQUAL };       // x: keys; keeps x[i] == K
-
-__device__ __forceinline__ bool trk_keep(int mode, const u64 *x, u64 K, i64 i)
-{
-    const u64 v = x[i];
-    switch (mode) {
-    case TRK_KEEP_NOT_NAN: return (v & 0x7fffffffffffffffull) <= 0x7ff0000000000000ull;
-    case TRK_KEEP_RUN_START: return i == 0 || v != x[i - 1];
-    case TRK_KEEP_ABOVE: return v > K;
-    default: return v == K;
-    }
-}
-
-// exclusive prefix of v over the 256 threads of the workgroup; total: their sum.  lds: 4 words.
-__device__ __forceinline__ i64 trk_block_scan(i64 v, i64 *lds, i64 &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const i64 inc = wave_scan_add(v);
-    __syncthreads();
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    i64 base = 0;
-    total = 0;
-    for (int k = 0; k < 4; k++) { if (k < w) base += lds[k]; total += lds[k]; }
-    return base + inc - v;
-}
+       TRK_KEEP_ABOVE,         // x: keys; keeps x[i] > sel->key
+       TRK_KEEP_EQUAL };       // x: keys; keeps x[i] == sel->key
 
 // the state of the top-N search, in device memory
 struct TrkSel {
@@ -172,47 +146,36 @@ struct TrkSel {
     unsigned long long hist[256];
 };
 
-__global__ void __launch_bounds__(256) k_trk_count(i64 n, int mode, const u64 *x, const TrkSel *sel, i64 *block_cnt)
-{
-    __shared__ i64 lds[4];
-    const u64 K = sel ? sel->key : 0;
-    const i64 i0 = (i64)blockIdx.x * TRK_CHUNK + threadIdx.x * 4;
-    i64 c = 0, total;
-    for (int j = 0; j < 4; j++) if (i0 + j < n) c += trk_keep(mode, x, K, i0 + j);
-    trk_block_scan(c, lds, total);
-    if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
-}
+// whether element i of x is kept under `mode` (sel: the search state of the two key modes, else NULL)
+struct TrkKeep {
+    int mode;
+    const u64 *x;
+    const TrkSel *sel;
 
-// one workgroup: block_cnt -> its exclusive prefix, in place; *total
-__global__ void __launch_bounds__(256) k_trk_scan_blocks(i64 nb, i64 *block_cnt, i64 *total)
-{
-    __shared__ i64 lds[4];
-    i64 carry = 0;
-    for (i64 c = 0; c < nb; c += 256) {
-        const i64 i = c + threadIdx.x;
-        const i64 v = i < nb ? block_cnt[i] : 0;
-        i64 t;
-        const i64 ex = trk_block_scan(v, lds, t);
-        if (i < nb) block_cnt[i] = carry + ex;
-        carry += t;
+    __device__ bool operator()(i64 i, int) const
+    {
+        const u64 v = x[i];
+        switch (mode) {
+        case TRK_KEEP_NOT_NAN: return (v & 0x7fffffffffffffffull) <= 0x7ff0000000000000ull;
+        case TRK_KEEP_RUN_START: return i == 0 || v != x[i - 1];
+        case TRK_KEEP_ABOVE: return v > sel->key;
+        default: return v == sel->key;
+        }
     }
-    if (threadIdx.x == 0) *total = carry;
-}
+};
 
 // the kept elements' indices and src words, in order, from output index -skip on (what falls before
 // index 0 is dropped: skip = the kept elements to leave out at the front; sel: skip = n_equal -
 // remaining).  TRK_KEEP_RUN_START also writes n behind the last index (iter_coverage_regions' end).
-__global__ void __launch_bounds__(256) k_trk_scatter(i64 n, int mode, const u64 *x, const TrkSel *sel, const u64 *src,
-    const i64 *block_base, const i64 *total, i64 *out_pos, u64 *out_val)
+__global__ void __launch_bounds__(256) k_trk_scatter(i64 n, TrkKeep f, const u64 *src, const i64 *block_base,
+    const i64 *total, i64 *out_pos, u64 *out_val)
 {
     __shared__ i64 lds[4];
-    const u64 K = sel ? sel->key : 0;
-    const i64 skip = mode == TRK_KEEP_EQUAL ? sel->n_equal - sel->remaining : 0;
-    const i64 i0 = (i64)blockIdx.x * TRK_CHUNK + threadIdx.x * 4;
-    bool keep[4];
-    i64 c = 0, t;
-    for (int j = 0; j < 4; j++) { keep[j] = i0 + j < n && trk_keep(mode, x, K, i0 + j); c += keep[j]; }
-    i64 at = block_base[blockIdx.x] + trk_block_scan(c, lds, t) - skip;
+    const int mode = f.mode;
+    const i64 skip = mode == TRK_KEEP_EQUAL ? f.sel->n_equal - f.sel->remaining : 0;
+    const i64 i0 = (i64)blockIdx.x * SCAN_CHUNK + threadIdx.x * 4;
+    i64 keep[4], t;
+    i64 at = block_base[blockIdx.x] + chunk_scan(n, f, lds, keep, t) - skip;
     for (int j = 0; j < 4; j++)
         if (keep[j]) {
             if (at >= 0) { out_pos[at] = i0 + j; out_val[at] = src[i0 + j]; }

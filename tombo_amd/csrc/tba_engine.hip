@@ -4,6 +4,7 @@
 #include <atomic>
 #include "tba_common.h"
 #include "div_const_proof.h"
+#include "k_scan.h"
 #include "k_select.h"
 #include "k_segment.h"
 #include "k_detect.h"
@@ -2218,16 +2219,18 @@ extern "C" int tba_site_aggregate(tba_engine *e, int64_t n_blocks, const int64_t
 // ---- estimate_alt_model (k_kde.h): levels gathered by k-mer, kernel densities ----------------
 namespace {
 // n items partitioned by one of n_keys keys, in chunks: a row of per-key counters per chunk (at most 1024
-// chunks and at most 2^24 counters; a chunk is a multiple of 64 items and at least 4096).  count() runs the
-// caller's counting pass over zeroed rows and leaves the per-key counts and their offsets on the device;
-// the caller's filling pass then reads rows and off.
+// chunks and at most 2^24 counters; a chunk is a multiple of 64 items and at least 4096).  src: the items' keys
+// and where a placed item is stored (k_key_partition, k_scan.h).  count() runs the counting pass over zeroed
+// rows and leaves the per-key counts and their offsets on the device; fill() then places the items.
 struct KeyPartition {
     Scratch &sc;
-    i64 n_keys, chunk, n_chunks;
+    i64 n, n_keys, chunk, n_chunks;
+    int key_bits = 0;   // bits that tell the keys apart
     u32 *rows;
     i64 *counts, *off;
-    KeyPartition(Scratch &sc_, i64 n, i64 n_keys_) : sc(sc_), n_keys(n_keys_)
+    KeyPartition(Scratch &sc_, i64 n_, i64 n_keys_) : sc(sc_), n(n_), n_keys(n_keys_)
     {
+        while (((i64)1 << key_bits) < n_keys) key_bits++;
         const i64 max_chunks = std::max<i64>(1, std::min<i64>(1024, ((i64)1 << 24) / n_keys));
         chunk = std::max<i64>(4096, ((n + max_chunks - 1) / max_chunks + 63) / 64 * 64);
         n_chunks = (n + chunk - 1) / chunk;
@@ -2235,14 +2238,46 @@ struct KeyPartition {
         counts = sc.out<i64>(n_keys);
         off = sc.out<i64>(n_keys + 1);
     }
-    template <class F> void count(F launch_count_pass)
+    template <class Src> void count(const Src &src)
     {
         if (sc.zero(rows, n_chunks * n_keys * sizeof(u32))) return;
-        launch_count_pass();
+        k_key_partition<false><<<(unsigned)n_chunks, 64, 0, sc.stream>>>(src, n, chunk, n_keys, key_bits, rows, nullptr);
         k_kmer_colscan<<<grid_for(n_keys), 256, 0, sc.stream>>>(n_keys, n_chunks, rows, counts);
-        k_kmer_offsets<<<1, 64, 0, sc.stream>>>(n_keys, counts, off);
+        k_exclusive_prefix<<<1, 256, 0, sc.stream>>>(n_keys, counts, off, off + n_keys);
+    }
+    template <class Src> void fill(const Src &src)
+    {
+        k_key_partition<true><<<(unsigned)n_chunks, 64, 0, sc.stream>>>(src, n, chunk, n_keys, key_bits, rows, off);
     }
 };
+
+// a call without items: every key's count and offset is zero
+static int empty_partition(i64 n_keys, int64_t *out_counts, int64_t *out_off)
+{
+    std::fill_n(out_counts, n_keys, 0);
+    if (out_off) std::fill_n(out_off, n_keys + 1, 0);
+    return TBA_OK;
+}
+
+// the levels and base codes of a read batch, CSR by read_off; total: its bases
+static int check_read_batch(const int64_t *read_off, i64 n_reads, const double *means, const uint8_t *codes, i64 &total)
+{
+    if (const int rc = check_csr_off(read_off, n_reads)) return rc;
+    total = n_reads > 0 ? read_off[n_reads] : 0;
+    if (total >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "more than 2^31 - 1 bases in one batch");
+    if (total > 0 && (!means || !codes)) return set_err(TBA_E_ARG, "bad arguments");
+    return TBA_OK;
+}
+
+// values in n_seg > 0 CSR segments, each of fewer than 2^31 values (too_long: the entry's message for a longer one)
+static int check_segments(const double *values, const int64_t *off, i64 n_seg, const char *too_long)
+{
+    if (const int rc = check_csr_off(off, n_seg)) return rc;
+    for (i64 s = 0; s < n_seg; s++)
+        if (off[s + 1] - off[s] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, too_long);
+    if (off[n_seg] > 0 && !values) return set_err(TBA_E_ARG, "bad arguments");
+    return TBA_OK;
+}
 } // namespace
 
 extern "C" int tba_kmer_levels(tba_engine *e, const double *means, const uint8_t *codes,
@@ -2254,26 +2289,18 @@ extern "C" int tba_kmer_levels(tba_engine *e, const double *means, const uint8_t
         central_pos < 0 || central_pos >= kmer_width || (out_levels && (!out_lv_off || levels_cap < 0)))
         return set_err(TBA_E_ARG, "bad arguments");
     const i64 n_kmers = (i64)1 << (2 * kmer_width);
-    if (const int rc = check_csr_off(read_off, n_reads)) return rc;
-    const i64 total = n_reads > 0 ? read_off[n_reads] : 0;
-    if (total >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "more than 2^31 - 1 bases in one batch");
-    if (total > 0 && (!means || !codes)) return set_err(TBA_E_ARG, "bad arguments");
-    if (total == 0) {
-        for (i64 q = 0; q < n_kmers; q++) out_counts[q] = 0;
-        if (out_lv_off) for (i64 q = 0; q <= n_kmers; q++) out_lv_off[q] = 0;
-        return TBA_OK;
-    }
+    i64 total;
+    if (const int rc = check_read_batch(read_off, n_reads, means, codes, total)) return rc;
+    if (total == 0) return empty_partition(n_kmers, out_counts, out_lv_off);
     Scratch sc(e);
     KeyPartition part(sc, total, n_kmers);
-    const unsigned n_chunks = (unsigned)part.n_chunks;
-    KmerArgs a{};
-    a.chunk = part.chunk;
-    a.n_reads = n_reads; a.total = total; a.K = (int)kmer_width; a.cp = (int)central_pos;
+    KmerSrc a{};
+    a.n_reads = n_reads; a.K = (int)kmer_width; a.cp = (int)central_pos;
     a.read_off = sc.in(read_off, n_reads + 1);
     a.codes = sc.in(codes, total);
     a.completed = sc.in(completed, n_kmers);
     a.means = sc.in(means, total);
-    part.count([&] { k_kmer_gather<false><<<n_chunks, 64, 0, sc.stream>>>(a, part.rows, nullptr, nullptr); });
+    part.count(a);
     if (sc.sync()) return sc.rc;
     if (sc.get(out_counts, part.counts, n_kmers)) return sc.rc;
     if (out_lv_off && sc.get(out_lv_off, part.off, n_kmers + 1)) return sc.rc;
@@ -2281,11 +2308,11 @@ extern "C" int tba_kmer_levels(tba_engine *e, const double *means, const uint8_t
     const i64 n_lv = out_lv_off[n_kmers];
     if (n_lv > levels_cap) return set_err(TBA_E_ARG, "levels_cap is smaller than the number of gathered levels");
     if (n_lv == 0) return TBA_OK;
-    double *d_lv = sc.out<double>(n_lv);
+    a.levels = sc.out<double>(n_lv);
     if (sc.rc) return sc.rc;
-    k_kmer_gather<true><<<n_chunks, 64, 0, sc.stream>>>(a, part.rows, part.off, d_lv);
+    part.fill(a);
     if (sc.sync()) return sc.rc;
-    return sc.get(out_levels, d_lv, n_lv);
+    return sc.get(out_levels, a.levels, n_lv);
 }
 
 namespace {
@@ -2311,11 +2338,8 @@ extern "C" int tba_kde_eval(tba_engine *e, const double *levels, const int64_t *
         n_x > (int64_t)65535 * 256 || (n_x > 0 && !x) || (n_seg > 0 && n_x > 0 && !out_dens))
         return set_err(TBA_E_ARG, "bad arguments");
     if (n_seg == 0 || n_x == 0) return TBA_OK;
-    if (const int rc = check_csr_off(lv_off, n_seg)) return rc;
-    for (i64 s = 0; s < n_seg; s++)
-        if (lv_off[s + 1] - lv_off[s] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "segment of more than 2^31 - 1 levels");
+    if (const int rc = check_segments(levels, lv_off, n_seg, "segment of more than 2^31 - 1 levels")) return rc;
     const i64 n_lv = lv_off[n_seg];
-    if (n_lv > 0 && !levels) return set_err(TBA_E_ARG, "bad arguments");
     Scratch sc(e);
     double *d_lv = sc.in(levels, n_lv);
     const i64 *d_off = sc.in(lv_off, n_seg + 1);
@@ -2344,17 +2368,13 @@ extern "C" int tba_kmer_dist(tba_engine *e, const double *means, const uint8_t *
         (out_values && (!out_value_label || !out_kmer_mean || values_cap < 0)))
         return set_err(TBA_E_ARG, "bad arguments");
     const i64 n_kmers = (i64)1 << (2 * kmer_width);
-    if (const int rc = check_csr_off(read_off, n_reads)) return rc;
-    const i64 total = n_reads > 0 ? read_off[n_reads] : 0;
-    if (total >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "more than 2^31 - 1 bases in one batch");
-    if (total > 0 && (!means || !codes)) return set_err(TBA_E_ARG, "bad arguments");
+    i64 total;
+    if (const int rc = check_read_batch(read_off, n_reads, means, codes, total)) return rc;
     if (n_reads > KD_TABLE_MAX / n_kmers) return set_err(TBA_E_ARG, "4^kmer_width * n_reads above 2^27");
     *out_n_sel = *out_n_examined = 0;
     if (n_reads == 0) {
-        for (i64 q = 0; q < n_kmers; q++) out_counts[q] = 0;
-        for (i64 q = 0; q <= n_kmers; q++) out_off[q] = 0;
-        if (out_values) for (i64 q = 0; q < n_kmers; q++) out_kmer_mean[q] = NAN;
-        return TBA_OK;
+        if (out_values) std::fill_n(out_kmer_mean, n_kmers, NAN);
+        return empty_partition(n_kmers, out_counts, out_off);
     }
     // chunks that never cross a read: the shortest multiple-of-64 length from 4096 on that keeps the chunk
     // counters within KD_TABLE_MAX (a read has at least one chunk, n_reads of them always fit)
@@ -2413,8 +2433,8 @@ extern "C" int tba_kmer_dist(tba_engine *e, const double *means, const uint8_t *
     {
         KernelTimer t(sc, out_kernel_ms != nullptr);
         k_kd_kmer_totals<<<grid_for(n_kmers), 256, 0, sc.stream>>>(n_kmers, n_sel, d_sel, tab, lvl_tot, ent_tot);
-        k_kmer_offsets<<<1, 64, 0, sc.stream>>>(n_kmers, lvl_tot, lv_off);
-        k_kmer_offsets<<<1, 64, 0, sc.stream>>>(n_kmers, ent_tot, ent_off);
+        k_exclusive_prefix<<<1, 256, 0, sc.stream>>>(n_kmers, lvl_tot, lv_off, lv_off + n_kmers);
+        k_exclusive_prefix<<<1, 256, 0, sc.stream>>>(n_kmers, ent_tot, ent_off, ent_off + n_kmers);
         t.stop();
         ms += t.ms();
     }
@@ -2453,19 +2473,20 @@ extern "C" int tba_kmer_dist(tba_engine *e, const double *means, const uint8_t *
 
 // ---- genome tracks (k_tracks.h): pileup sums and coverages, compaction, difference, top N --------
 namespace {
-static unsigned trk_chunks(i64 n) { return (unsigned)((n + TRK_CHUNK - 1) / TRK_CHUNK); }
+static unsigned scan_chunks(i64 n) { return (unsigned)((n + SCAN_CHUNK - 1) / SCAN_CHUNK); }
 
 // flag / scan / scatter of the n words x under `mode` (sel: the search state of the top-N modes); the kept
 // indices to d_pos (n + 1 words), the kept words of src to d_val (n words); d_total: how many were kept
 static void launch_compact(Scratch &sc, i64 n, int mode, const u64 *x, const TrkSel *sel, const u64 *src,
                            i64 *d_pos, u64 *d_val, i64 *d_total)
 {
-    const unsigned nb = trk_chunks(n);
+    const unsigned nb = scan_chunks(n);
+    const TrkKeep keep{mode, x, sel};
     i64 *d_cnt = sc.out<i64>(nb);
     if (sc.rc) return;
-    k_trk_count<<<nb, 256, 0, sc.stream>>>(n, mode, x, sel, d_cnt);
-    k_trk_scan_blocks<<<1, 256, 0, sc.stream>>>((i64)nb, d_cnt, d_total);
-    k_trk_scatter<<<nb, 256, 0, sc.stream>>>(n, mode, x, sel, src, d_cnt, d_total, d_pos, d_val);
+    k_chunk_total<<<nb, 256, 0, sc.stream>>>(n, keep, d_cnt);
+    k_exclusive_prefix<<<1, 256, 0, sc.stream>>>((i64)nb, d_cnt, d_cnt, d_total);
+    k_trk_scatter<<<nb, 256, 0, sc.stream>>>(n, keep, src, d_cnt, d_total, d_pos, d_val);
 }
 } // namespace
 
@@ -2628,6 +2649,38 @@ extern "C" int tba_tracks_topn(tba_engine *e, const double *a, const double *b, 
 }
 
 // ---- estimate_kmer_model / estimate_motif_alt_model (k_kmer_est.h) ------------------------------
+namespace {
+// The reads of a batch of regions as tba_region_key_levels and tba_region_level_piles take them (the pointers
+// that must not be NULL whatever the sizes are the entry's own first check).  Checked on the host in two steps,
+// between which an entry may place checks of its own, then uploaded.
+struct RegionReadsIn {
+    i64 n_reads; const int64_t *read_start; const uint8_t *read_minus; const int64_t *read_off; const double *means;
+    i64 n_regions; const int64_t *reg_read_off, *reg_reads;
+    i64 total = 0, n_rr = 0;   // after check_offsets: all levels, all (region, read) pairs
+
+    int check_offsets()
+    {
+        if (const int rc = check_csr_off(read_off, n_reads)) return rc;
+        if (const int rc = check_csr_off(reg_read_off, n_regions)) return rc;
+        total = n_reads > 0 ? read_off[n_reads] : 0;
+        n_rr = n_regions > 0 ? reg_read_off[n_regions] : 0;
+        return TBA_OK;
+    }
+    int check_reads() const
+    {
+        if ((total > 0 && !means) || (n_rr > 0 && !reg_reads)) return set_err(TBA_E_ARG, "bad arguments");
+        for (i64 q = 0; q < n_rr; q++)
+            if (reg_reads[q] < 0 || reg_reads[q] >= n_reads) return set_err(TBA_E_ARG, "a region names a read outside the batch");
+        return TBA_OK;
+    }
+    RegionReads upload(Scratch &sc) const
+    {
+        return RegionReads{sc.in(reg_read_off, n_regions + 1), sc.in(reg_reads, n_rr), sc.in(read_start, n_reads),
+                           sc.in(read_off, n_reads + 1), sc.in(read_minus, n_reads), sc.in(means, total)};
+    }
+};
+} // namespace
+
 extern "C" int tba_region_key_levels(tba_engine *e, int est_mean, int64_t n_reads, const int64_t *read_start,
     const uint8_t *read_minus, const int64_t *read_off, const double *means, int64_t n_regions,
     const int64_t *reg_read_off, const int64_t *reg_reads, int64_t n_pos, const int64_t *pos_reg,
@@ -2639,44 +2692,29 @@ extern "C" int tba_region_key_levels(tba_engine *e, int est_mean, int64_t n_read
         !out_counts || !out_off || (n_reads > 0 && (!read_start || !read_minus)) ||
         (n_pos > 0 && (!pos_reg || !pos_g)) || (n_ent > 0 && (!ent_pos || !ent_key || !out_levels || !out_sds)))
         return set_err(TBA_E_ARG, "bad arguments");
-    if (const int rc = check_csr_off(read_off, n_reads)) return rc;
-    if (const int rc = check_csr_off(reg_read_off, n_regions)) return rc;
-    const i64 total = n_reads > 0 ? read_off[n_reads] : 0, n_rr = n_regions > 0 ? reg_read_off[n_regions] : 0;
-    if ((total > 0 && !means) || (n_rr > 0 && !reg_reads)) return set_err(TBA_E_ARG, "bad arguments");
-    for (i64 q = 0; q < n_rr; q++)
-        if (reg_reads[q] < 0 || reg_reads[q] >= n_reads) return set_err(TBA_E_ARG, "a region names a read outside the batch");
+    RegionReadsIn in{n_reads, read_start, read_minus, read_off, means, n_regions, reg_read_off, reg_reads};
+    if (const int rc = in.check_offsets()) return rc;
+    if (const int rc = in.check_reads()) return rc;
     for (i64 p = 0; p < n_pos; p++)
         if (pos_reg[p] < 0 || pos_reg[p] >= n_regions) return set_err(TBA_E_ARG, "a position names a region outside the batch");
     for (i64 i = 0; i < n_ent; i++)
         if (ent_pos[i] < 0 || ent_pos[i] >= n_pos || ent_key[i] < 0 || ent_key[i] >= n_keys)
             return set_err(TBA_E_ARG, "an entry names a position or a key outside the batch");
-    if (n_ent == 0) {
-        for (i64 q = 0; q < n_keys; q++) out_counts[q] = 0;
-        for (i64 q = 0; q <= n_keys; q++) out_off[q] = 0;
-        return TBA_OK;
-    }
+    if (n_ent == 0) return empty_partition(n_keys, out_counts, out_off);
     Scratch sc(e);
-    KestArgs a{};
-    a.n_pos = n_pos;
-    a.pos_reg = sc.in(pos_reg, n_pos);
-    a.pos_g = sc.in(pos_g, n_pos);
-    a.reg_read_off = sc.in(reg_read_off, n_regions + 1);
-    a.reg_reads = sc.in(reg_reads, n_rr);
-    a.read_start = sc.in(read_start, n_reads);
-    a.read_minus = sc.in(read_minus, n_reads);
-    a.read_off = sc.in(read_off, n_reads + 1);
-    a.means = sc.in(means, total);
+    const ListedPos pos{sc.in(pos_reg, n_pos), sc.in(pos_g, n_pos)};
+    const RegionReads a = in.upload(sc);
     i32 *cov = sc.out<i32>(n_pos);
     i64 *lv_off = sc.out<i64>(n_pos + 1);
     double *d_level = sc.out<double>(n_pos), *d_sd = sc.out<double>(n_pos);
     if (sc.rc) return sc.rc;
-    k_kest_pileup<false><<<grid_for(n_pos), 256, 0, e->stream>>>(a, cov, nullptr, nullptr);
-    k_kest_offsets<<<1, 256, 0, e->stream>>>(n_pos, cov, lv_off);
+    k_region_pileup<false><<<grid_for(n_pos), 256, 0, e->stream>>>(a, pos, n_pos, cov, nullptr, nullptr);
+    k_exclusive_prefix<<<1, 256, 0, e->stream>>>(n_pos, cov, lv_off, lv_off + n_pos);
     i64 n_lv = 0;
     if (sc.sync() || sc.get(&n_lv, lv_off + n_pos, 1)) return sc.rc;
     double *d_lv = sc.out<double>(n_lv);
     if (sc.rc) return sc.rc;
-    k_kest_pileup<true><<<grid_for(n_pos), 256, 0, e->stream>>>(a, nullptr, lv_off, d_lv);
+    k_region_pileup<true><<<grid_for(n_pos), 256, 0, e->stream>>>(a, pos, n_pos, nullptr, lv_off, d_lv);
     k_kest_moments<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, est_mean, lv_off, d_lv, d_level, d_sd);
     if (!est_mean) {
         const i32 *has_nan = sort_segments(sc, n_pos, lv_off, d_lv);
@@ -2684,19 +2722,13 @@ extern "C" int tba_region_key_levels(tba_engine *e, int est_mean, int64_t n_read
         k_kest_median<<<grid_for(n_pos), 256, 0, e->stream>>>(n_pos, has_nan, lv_off, d_lv, d_level);
     }
     // the entries by key
-    int key_bits = 0;
-    while (((i64)1 << key_bits) < n_keys) key_bits++;
     const i64 *d_ep = sc.in(ent_pos, n_ent), *d_ek = sc.in(ent_key, n_ent);
     KeyPartition part(sc, n_ent, n_keys);
-    const unsigned n_chunks = (unsigned)part.n_chunks;
     double *d_ol = sc.out<double>(n_ent), *d_os = sc.out<double>(n_ent);
-    part.count([&] {
-        k_kest_partition<false><<<n_chunks, 64, 0, sc.stream>>>(n_ent, part.chunk, n_keys, key_bits, d_ep, d_ek, part.rows,
-            nullptr, nullptr, nullptr, nullptr, nullptr);
-    });
+    const EntSrc ent{d_ep, d_ek, d_level, d_sd, d_ol, d_os};
+    part.count(ent);
     if (sc.rc) return sc.rc;
-    k_kest_partition<true><<<n_chunks, 64, 0, sc.stream>>>(n_ent, part.chunk, n_keys, key_bits, d_ep, d_ek, part.rows,
-        part.off, d_level, d_sd, d_ol, d_os);
+    part.fill(ent);
     if (sc.sync()) return sc.rc;
     if (sc.get(out_counts, part.counts, n_keys) || sc.get(out_off, part.off, n_keys + 1) ||
         sc.get(out_levels, d_ol, n_ent))
@@ -2709,11 +2741,8 @@ extern "C" int tba_segment_medians(tba_engine *e, const double *values, const in
 {
     if (!e || !off || n_seg < 0 || (n_seg > 0 && !out_medians)) return set_err(TBA_E_ARG, "bad arguments");
     if (n_seg == 0) return TBA_OK;
-    if (const int rc = check_csr_off(off, n_seg)) return rc;
-    for (i64 s = 0; s < n_seg; s++)
-        if (off[s + 1] - off[s] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "segment of more than 2^31 - 1 values");
+    if (const int rc = check_segments(values, off, n_seg, "segment of more than 2^31 - 1 values")) return rc;
     const i64 n = off[n_seg];
-    if (n > 0 && !values) return set_err(TBA_E_ARG, "bad arguments");
     Scratch sc(e);
     double *d_v = sc.in(values, n);
     const i64 *d_off = sc.in(off, n_seg + 1);
@@ -2758,14 +2787,11 @@ extern "C" int tba_region_level_piles(tba_engine *e, int64_t n_reads, const int6
         (n_regions > 0 && (!reg_start || !reg_end)) || (n_ql > 0 && !q_linear) || (n_qn > 0 && !q_nearest))
         return set_err(TBA_E_ARG, "bad arguments");
     if (out_kernel_ms) *out_kernel_ms = 0.0;
-    if (const int rc = check_csr_off(read_off, n_reads)) return rc;
-    if (const int rc = check_csr_off(reg_read_off, n_regions)) return rc;
+    RegionReadsIn in{n_reads, read_start, read_minus, read_off, means, n_regions, reg_read_off, reg_reads};
+    if (const int rc = in.check_offsets()) return rc;
     if (const int rc = check_fractions(q_linear, n_ql)) return rc;
     if (const int rc = check_fractions(q_nearest, n_qn)) return rc;
-    const i64 total = n_reads > 0 ? read_off[n_reads] : 0, n_rr = n_regions > 0 ? reg_read_off[n_regions] : 0;
-    if ((total > 0 && !means) || (n_rr > 0 && !reg_reads)) return set_err(TBA_E_ARG, "bad arguments");
-    for (i64 q = 0; q < n_rr; q++)
-        if (reg_reads[q] < 0 || reg_reads[q] >= n_reads) return set_err(TBA_E_ARG, "a region names a read outside the batch");
+    if (const int rc = in.check_reads()) return rc;
     for (i64 q = 0; q < n_reads; q++)
         if (!plot_coord_ok(read_start[q])) return set_err(TBA_E_ARG, "a read start outside (-2^62, 2^62)");
     std::vector<i64> pos_off((size_t)n_regions + 1, 0);
@@ -2782,22 +2808,14 @@ extern "C" int tba_region_level_piles(tba_engine *e, int64_t n_reads, const int6
     if (n_pos == 0) return TBA_OK;
     if ((n_ql > 0 && !out_lin) || (n_qn > 0 && !out_near)) return set_err(TBA_E_ARG, "bad arguments");
     Scratch sc(e);
-    PlotPileArgs a{};
-    a.n_regions = n_regions; a.n_pos = n_pos;
-    a.reg_pos_off = sc.in(pos_off.data(), n_regions + 1);
-    a.reg_start = sc.in(reg_start, n_regions);
-    a.reg_read_off = sc.in(reg_read_off, n_regions + 1);
-    a.reg_reads = sc.in(reg_reads, n_rr);
-    a.read_start = sc.in(read_start, n_reads);
-    a.read_minus = sc.in(read_minus, n_reads);
-    a.read_off = sc.in(read_off, n_reads + 1);
-    a.means = sc.in(means, total);
+    const DensePos pos{n_regions, sc.in(pos_off.data(), n_regions + 1), sc.in(reg_start, n_regions)};
+    const RegionReads a = in.upload(sc);
     i32 *cov = sc.out<i32>(n_pos);
     i64 *lv_off = sc.out<i64>(n_pos + 1);
     if (sc.rc) return sc.rc;
     KernelTimer tm_count(sc, out_kernel_ms != nullptr);
-    k_plot_pileup<false><<<grid_for(n_pos), 256, 0, sc.stream>>>(a, cov, nullptr, nullptr);
-    k_kest_offsets<<<1, 256, 0, sc.stream>>>(n_pos, cov, lv_off);
+    k_region_pileup<false><<<grid_for(n_pos), 256, 0, sc.stream>>>(a, pos, n_pos, cov, nullptr, nullptr);
+    k_exclusive_prefix<<<1, 256, 0, sc.stream>>>(n_pos, cov, lv_off, lv_off + n_pos);
     tm_count.stop();
     i64 n_lv = 0;
     if (sc.sync() || sc.get(&n_lv, lv_off + n_pos, 1) || sc.get(out_off, lv_off, n_pos + 1)) return sc.rc;
@@ -2807,7 +2825,7 @@ extern "C" int tba_region_level_piles(tba_engine *e, int64_t n_reads, const int6
     if (out_levels && nq > 0) d_sorted = sc.out<double>(n_lv);   // the frames want read order and the sorters work in place
     if (sc.rc) return sc.rc;
     KernelTimer tm_fill(sc, out_kernel_ms != nullptr);
-    if (n_lv > 0) k_plot_pileup<true><<<grid_for(n_pos), 256, 0, sc.stream>>>(a, nullptr, lv_off, d_lv);
+    if (n_lv > 0) k_region_pileup<true><<<grid_for(n_pos), 256, 0, sc.stream>>>(a, pos, n_pos, nullptr, lv_off, d_lv);
     if (nq > 0) {
         if (d_sorted != d_lv && n_lv > 0)
             sc.hip(hipMemcpyAsync(d_sorted, d_lv, (size_t)n_lv * sizeof(double), hipMemcpyDeviceToDevice, sc.stream), "hipMemcpyAsync");
@@ -2833,11 +2851,8 @@ extern "C" int tba_segment_percentiles(tba_engine *e, const double *values, cons
     if (const int rc = check_fractions(q_nearest, n_qn)) return rc;
     if (n_seg == 0 || n_ql + n_qn == 0) return TBA_OK;
     if (n_seg >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "2^31 segments or more in one call");
-    if (const int rc = check_csr_off(off, n_seg)) return rc;
-    for (i64 s = 0; s < n_seg; s++)
-        if (off[s + 1] - off[s] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "a pile of 2^31 levels or more");
+    if (const int rc = check_segments(values, off, n_seg, "a pile of 2^31 levels or more")) return rc;
     const i64 n = off[n_seg];
-    if (n > 0 && !values) return set_err(TBA_E_ARG, "bad arguments");
     Scratch sc(e);
     double *d_v = sc.in(values, n);
     const i64 *d_off = sc.in(off, n_seg + 1);
@@ -2993,7 +3008,7 @@ extern "C" int tba_region_raw_signal(tba_engine *e, int64_t n_reads, const void 
     if (sc.rc) return sc.rc;
     KernelTimer tm_sizes(sc, out_kernel_ms != nullptr);
     k_plot_sig_sizes<<<grid_for(n_pair), 256, 0, sc.stream>>>(a, geom, cov, d_st);
-    k_kest_offsets<<<1, 256, 0, sc.stream>>>(n_pair, cov, sig_off);
+    k_exclusive_prefix<<<1, 256, 0, sc.stream>>>(n_pair, cov, sig_off, sig_off + n_pair);
     tm_sizes.stop();
     if (const int st = sc.sync(d_st)) return sc.rc ? sc.rc : set_err(st, "a pair failed the device's checks");
     if (sc.get(out_sig_off, sig_off, n_pair + 1)) return sc.rc;
@@ -3626,7 +3641,7 @@ template <class F>
 static int roc_compact(Scratch &sc, F f, RocRecs R, i64 n_motifs, double *out_stats,
     uint8_t *out_has_mod, int64_t *out_index, int64_t *out_counts, double *out_kernel_ms)
 {
-    const unsigned nb = trk_chunks(R.n_rec);
+    const unsigned nb = scan_chunks(R.n_rec);
     const i64 m = (i64)nb * n_motifs;
     i64 *d_cnt = sc.out<i64>(m + 1);
     double *d_stat = sc.out<double>(R.n_rec * n_motifs);
@@ -3636,8 +3651,8 @@ static int roc_compact(Scratch &sc, F f, RocRecs R, i64 n_motifs, double *out_st
     KernelTimer tm(sc, out_kernel_ms != nullptr);
     if (!sc.rc) {
         const dim3 grid(nb, (unsigned)n_motifs);
-        k_roc_count<<<grid, 256, 0, sc.stream>>>(f, R, d_cnt);
-        k_trk_scan_blocks<<<1, 256, 0, sc.stream>>>(m, d_cnt, d_cnt + m);
+        k_chunk_total<<<grid, 256, 0, sc.stream>>>(R.n_rec, RocKept<F>{f, R}, d_cnt);
+        k_exclusive_prefix<<<1, 256, 0, sc.stream>>>(m, d_cnt, d_cnt, d_cnt + m);
         k_roc_scatter<<<grid, 256, 0, sc.stream>>>(f, R, d_cnt, d_stat, d_lab, d_idx);
     }
     tm.stop();
@@ -3744,7 +3759,7 @@ extern "C" int tba_roc_rank_counts(tba_engine *e, int64_t n, const double *stats
     unsigned long long *d_hist = sc.out<unsigned long long>(ROC_HIST_BINS + 1);
     const unsigned n_tiles = (unsigned)((n + ROC_SORT_TILE - 1) / ROC_SORT_TILE);
     u32 *d_table = sc.out<u32>((i64)ROC_MAX_DIGITS * n_tiles);
-    const unsigned n_tab_chunks = trk_chunks((i64)ROC_MAX_DIGITS * n_tiles), n_lab_chunks = trk_chunks(n);
+    const unsigned n_tab_chunks = scan_chunks((i64)ROC_MAX_DIGITS * n_tiles), n_lab_chunks = scan_chunks(n);
     i64 *d_tab_cnt = sc.out<i64>(n_tab_chunks + 1), *d_lab_cnt = sc.out<i64>(n_lab_chunks + 1);
     i32 *d_bad = sc.status();
     if (sc.zero(d_hist, (ROC_HIST_BINS + 1) * 8)) return sc.rc;
@@ -3764,10 +3779,10 @@ extern "C" int tba_roc_rank_counts(tba_engine *e, int64_t n, const double *stats
         for (int d = 0; d < nd; d++) one_digit |= hist[roc_hist_base(pass) + d] == (unsigned long long)n;
         if (one_digit) continue;
         const i64 m = (i64)nd * n_tiles;
-        const unsigned nc = trk_chunks(m);
+        const unsigned nc = scan_chunks(m);
         k_roc_hist<<<n_tiles, 256, 0, e->stream>>>(n, pass, nd, key[cur], lab[cur], d_table);
-        k_roc_tab_count<<<nc, 256, 0, e->stream>>>(m, d_table, d_tab_cnt);
-        k_trk_scan_blocks<<<1, 256, 0, e->stream>>>((i64)nc, d_tab_cnt, d_tab_cnt + n_tab_chunks);
+        k_chunk_total<<<nc, 256, 0, e->stream>>>(m, ArrayCount<u32>{d_table}, d_tab_cnt);
+        k_exclusive_prefix<<<1, 256, 0, e->stream>>>((i64)nc, d_tab_cnt, d_tab_cnt, d_tab_cnt + n_tab_chunks);
         k_roc_tab_apply<<<nc, 256, 0, e->stream>>>(m, d_table, d_tab_cnt);
         k_roc_scatter_pass<<<n_tiles, 256, 0, e->stream>>>(n, pass, nd, key[cur], lab[cur], d_table, key[cur ^ 1],
             lab[cur ^ 1]);
@@ -3776,8 +3791,8 @@ extern "C" int tba_roc_rank_counts(tba_engine *e, int64_t n, const double *stats
     tm_sort.stop();
     KernelTimer tm_rank(sc, timed);
     if (!sc.rc) {
-        k_roc_label_count<<<n_lab_chunks, 256, 0, e->stream>>>(n, lab[cur], d_lab_cnt);
-        k_trk_scan_blocks<<<1, 256, 0, e->stream>>>((i64)n_lab_chunks, d_lab_cnt, d_lab_cnt + n_lab_chunks);
+        k_chunk_total<<<n_lab_chunks, 256, 0, e->stream>>>(n, ArrayCount<uint8_t>{lab[cur]}, d_lab_cnt);
+        k_exclusive_prefix<<<1, 256, 0, e->stream>>>((i64)n_lab_chunks, d_lab_cnt, d_lab_cnt, d_lab_cnt + n_lab_chunks);
         if (n_ranks > 0)
             k_roc_gather<<<grid_for(n_ranks), 256, 0, e->stream>>>(n, n_ranks, d_ranks, lab[cur], d_lab_cnt, d_tp, d_bad);
     }

@@ -13,6 +13,8 @@ import sys
 LABEL = re.compile(r'^([A-Za-z_$][\w$.]*):')
 HEADER = ('\t.protected', '\t.globl', '\t.weak', '\t.hidden', '\t.p2align', '\t.type', '\t.section', '\t.text')
 LOCAL = re.compile(r'\.L(BB|func_begin|func_end|JTI|tmp)\d+')
+LOOP_NOTE = re.compile(r'\bBB\d+(?=_\d+ Depth)')   # the same number in the loop comments: "Header=BB71_2 Depth=1"
+LABEL_PAD = re.compile(r'^(\.LBB#_\d+:)[ \t]+;', re.M)   # a label's comment column moves with the number's width
 KERNEL = re.compile(r'^\t\.amdhsa_kernel (\S+)\n.*?^\t\.end_amdhsa_kernel$', re.S | re.M)
 
 
@@ -20,7 +22,8 @@ def split(path):
     """-> ({symbol: body}, {kernel: descriptor block}, {kernel: metadata entry})"""
     text = re.sub(r'__hip_cuid_[0-9a-f]+', '__hip_cuid_', open(path).read())
     code, _, meta = text.partition('\t.amdgpu_metadata\n')
-    lines = LOCAL.sub(lambda m: '.L' + m.group(1) + '#', code).split('\n')
+    code = LOOP_NOTE.sub('BB#', LOCAL.sub(lambda m: '.L' + m.group(1) + '#', code))
+    lines = LABEL_PAD.sub(r'\1 ;', code).split('\n')
     starts = []
     for i, line in enumerate(lines):
         m = LABEL.match(line)
