@@ -7,12 +7,12 @@ import pytest
 import roc_cases as rc
 import roc_reference as ref
 from roc_stub_engine import NumpyRocEngine
+from launch_caps import GRID_PASS   # threads of one launch (grid_for in csrc/tba_engine.hip)
 from tombo_amd import tombo_stats as ts, resquiggle as rq, _native
 
 pytestmark = pytest.mark.gpu
 
 T = _native.ROC_SORT_TILE
-GRID_PASS = 4096 * 256     # threads of one launch (grid_for in csrc/tba_engine.hip caps the grid at 4096 blocks of 256)
 SIZES = [1, 2, 63, 64, 65, T - 1, T, T + 1, 2 * T + 1]
 CASES = sorted(rc.meta()['cases'])
 

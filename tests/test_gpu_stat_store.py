@@ -7,12 +7,12 @@ import pytest
 
 import stat_store_cases as sc
 from stat_store_stub_engine import NumpyStatStoreEngine
+from launch_caps import GRID_PASS   # threads of one launch (grid_for in csrc/tba_engine.hip)
 from tombo_amd import tombo_stats as ts, tombo_helper as th, resquiggle as rq, _native
 
 pytestmark = pytest.mark.gpu
 
 AGGS = ('lower', 'abs', 'all', 'lower_damp')
-GRID_PASS = 4096 * 256     # threads of one launch (grid_for in csrc/tba_engine.hip caps the grid at 4096 blocks of 256)
 
 
 @pytest.fixture(scope='module')
