@@ -323,6 +323,10 @@ enum {
                                * the predicates by which the kernels select their reads (k_dp.h, k_dp_multi.h, k_dp_wg.h)
                                * over the state the run left (TBA_GET_PATH, TBA_GET_START_FAIL, start state) */
     TBA_GET_NORM_FORM = 33,   /* int32[n]: TBA_NORM_FORM_*: the code that found the medians of the read's normalisation */
+    TBA_GET_TS_FORM = 34,     /* int32[n][2]: what k_theil_sen did with the read (ABI 13): TBA_TS_FORM_*, and the entries of
+                               * the one-pass form's list of pairs (0 where its pass over the pairs did not run; the pairs
+                               * inside the window or too close to tell, and for points beyond the float range some
+                               * partners of the padding to 64, dropped later).  Written by the kernel */
     TBA_GET_DEBUG_COUNTERS = 99 /* int64[n][8]: ReadState.dbg, only filled by the profiling builds (one of
                                    -DTBA_PHASE_DEBUG=<id>, -DTBA_SWEEP_STATS, -DTBA_SKIP_STATS, -DTBA_SKIP_CLASS_STATS;
                                    the slots of each: csrc/tba_phase.h), zeros otherwise */
@@ -341,6 +345,16 @@ enum {
     TBA_NORM_FORM_SELECT = 1,       /* k_normalize: one pass per median through a sampled window, or the generic bucket select */
     TBA_NORM_FORM_INT_COUNT = 2,    /* k_normalize, int16 samples: both medians from one counting pass */
     TBA_NORM_FORM_HIST = 3          /* k_normalize_hist, float samples: all medians from one histogram pass and one list pass */
+};
+enum {                              /* TBA_GET_TS_FORM column 0: the Theil-Sen fit's median slope (k_theil_sen) */
+    TBA_TS_FORM_NONE = 0,           /* no fit: the read had failed before, or skip_seq_scaling */
+    TBA_TS_FORM_SMALL = 1,          /* fewer than 256 points: the generic two-pass select over all slopes, by design */
+    TBA_TS_FORM_FAST = 2,           /* one pass over the pairs against a sampled window, exact select among the listed ones */
+    /* the generic select ran because the one-pass form declined: */
+    TBA_TS_FORM_NO_SCRATCH = 3,     /* room for fewer than 4096 listed pairs in the read's scratch slices */
+    TBA_TS_FORM_NO_WINDOW = 4,      /* the sampled median slope is outside (0.5, 1.5) */
+    TBA_TS_FORM_LIST_OVERFLOW = 5,  /* more pairs listed than the scratch holds */
+    TBA_TS_FORM_WINDOW_MISS = 6     /* the window did not hold the middle ranks of all slopes */
 };
 enum {
     TBA_TB_FORM_NONE = 0,
@@ -992,7 +1006,7 @@ int tba_synth_dwell_thresholds(const tba_synth_params *p, uint32_t *thr, int64_t
 /* out[0..2] = sizeof(tba_params), sizeof(tba_opts), sizeof(tba_read_result) of this build, out[3]
  * (n >= 4) = TBA_ABI_VERSION: lets a binding without a C compiler (ctypes) check its struct mirrors
  * and refuse a stale build of the library */
-#define TBA_ABI_VERSION 12
+#define TBA_ABI_VERSION 13
 int tba_abi_sizes(int64_t *out, int64_t n);
 
 /* self-test: out[t] = index t of the subsample tba_opts.device_subsample draws for read

@@ -361,13 +361,13 @@ def _footprint_cases():
     L_wide = [300, 1200, 50, 3]
     mk = _native.make_opts
     return [
-        ('dna_f64', 380747435.0, dna, mk(outlier_thresh=5.0), 6, np.float64, S, L),
-        ('dna_i16', 380663735.0, dna, mk(outlier_thresh=5.0), 6, np.int16, S, L),
-        ('dna_skip_norm_out', 380635507.0, dna, mk(outlier_thresh=5.0, skip_norm_out=True), 6, np.float64, S, L),
-        ('stalls_i16', 380667304.0, dna, mk(outlier_thresh=5.0, stall_params=stalls), 6, np.int16, S, L),
-        ('stalls_f64', 380862968.0, dna, mk(outlier_thresh=5.0, stall_params=stalls), 6, np.float64, S, L),
-        ('rna', 380904261.0, rna, mk(outlier_thresh=5.0), 5, np.float64, S, L),
-        ('dna_wide', 385015361.0, dna, mk(outlier_thresh=5.0), 6, np.float64, S_wide, L_wide),
+        ('dna_f64', 380747471.0, dna, mk(outlier_thresh=5.0), 6, np.float64, S, L),
+        ('dna_i16', 380663771.0, dna, mk(outlier_thresh=5.0), 6, np.int16, S, L),
+        ('dna_skip_norm_out', 380635543.0, dna, mk(outlier_thresh=5.0, skip_norm_out=True), 6, np.float64, S, L),
+        ('stalls_i16', 380667340.0, dna, mk(outlier_thresh=5.0, stall_params=stalls), 6, np.int16, S, L),
+        ('stalls_f64', 380863004.0, dna, mk(outlier_thresh=5.0, stall_params=stalls), 6, np.float64, S, L),
+        ('rna', 380904297.0, rna, mk(outlier_thresh=5.0), 5, np.float64, S, L),
+        ('dna_wide', 385015397.0, dna, mk(outlier_thresh=5.0), 6, np.float64, S_wide, L_wide),
     ]
 
 
@@ -375,7 +375,8 @@ def test_batch_footprint_is_what_it_was_before_the_buffer_list_moved():
     """tba_batch_footprint (host only) over every branch of the size table -- raw sample type, norm_out,
     the stall detector's scratch in both of its forms, the RNA parameter set, the wide static band --
     with failing reads (no signal, a sequence shorter than the k-mer) in the batch: the integer it
-    returned before the engine's host code was reorganised"""
+    returned before the engine's host code was reorganised, plus the eight bytes per read of ReadState.ts_form
+    (TBA_GET_TS_FORM, ABI 13: 36 bytes for these four reads with the planner's slack)"""
     from tombo_amd import planner, _native
     for name, want, params, o, K, dt, S, L in _footprint_cases():
         got = planner.exact_bytes(S, L, _native.make_params(params), o, K, dt)

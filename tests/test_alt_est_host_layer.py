@@ -16,9 +16,9 @@ def _args(**kw):
 
 
 def test_abi_version_and_symbols():
-    assert _native.ABI_VERSION == 12
+    assert _native.ABI_VERSION == 13
     hdr = open(_native.os.path.join(_native._HERE, '..', 'include', 'tombo_amd.h')).read()
-    assert '#define TBA_ABI_VERSION 12' in hdr and 'int tba_kmer_levels(' in hdr and 'int tba_kde_eval(' in hdr
+    assert '#define TBA_ABI_VERSION 13' in hdr and 'int tba_kmer_levels(' in hdr and 'int tba_kde_eval(' in hdr
     assert callable(_native.Engine.kmer_levels) and callable(_native.Engine.kde_eval)
 
 

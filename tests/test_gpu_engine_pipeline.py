@@ -57,7 +57,7 @@ def _batches():
 
 
 GETS = ('GET_STATUS', 'GET_N_CPTS', 'GET_VALID_CPTS', 'GET_EVENT_MEANS', 'GET_BAND_STARTS', 'GET_READ_TB',
-        'GET_DP_SEGS', 'GET_SEGS', 'GET_THEIL_SEN', 'GET_PATH', 'GET_DP_FORM')
+        'GET_DP_SEGS', 'GET_SEGS', 'GET_THEIL_SEN', 'GET_PATH', 'GET_DP_FORM', 'GET_TS_FORM')
 
 
 def test_full_run_equals_the_stages_run_one_at_a_time():

@@ -232,6 +232,6 @@ def test_binding_constants_and_symbols():
     assert int(re.search(r'#define PDIST_MAX_ROWS (\d+)', text).group(1)) == _native.PDIST_MAX_ROWS
     assert 2 * _native.PDIST_TILE * (_native.PDIST_LDS_ROW_MAX | 1) * 8 <= 65536
     header = open(os.path.join(root, 'include', 'tombo_amd.h')).read()
-    assert '#define TBA_ABI_VERSION 12' in header
+    assert '#define TBA_ABI_VERSION 13' in header
     for sym in ('tba_pairwise_window_dists', 'tba_pairwise_nanmean_dists', 'tba_pdist_tile', 'tba_pdist_lds_row_max'):
         assert re.search(r'\b%s\(' % sym, header), sym

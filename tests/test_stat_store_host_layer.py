@@ -185,4 +185,4 @@ def test_site_aggregate_argument_checks():
 def test_header_declares_the_entry_and_keeps_the_abi():
     text = open(os.path.join(ROOT, 'include', 'tombo_amd.h')).read()
     assert re.search(r'\bint tba_site_aggregate\(tba_engine \*e,', text)
-    assert re.search(r'#define TBA_ABI_VERSION 12\b', text)
+    assert re.search(r'#define TBA_ABI_VERSION 13\b', text)

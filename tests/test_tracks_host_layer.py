@@ -112,9 +112,9 @@ def test_argument_checks():
 
 
 def test_abi_and_entries():
-    assert _native.ABI_VERSION == 12
+    assert _native.ABI_VERSION == 13
     hdr = open(os.path.join(ROOT, 'include', 'tombo_amd.h')).read()
-    assert int(re.search(r'#define\s+TBA_ABI_VERSION\s+(\d+)', hdr).group(1)) == 12
+    assert int(re.search(r'#define\s+TBA_ABI_VERSION\s+(\d+)', hdr).group(1)) == 13
     assert int(re.search(r'#define\s+TBA_TRK_TILE\s+(\d+)', hdr).group(1)) == _native.TRK_TILE
     src = open(os.path.join(_native.CSRC, 'k_tracks.h')).read()
     assert int(re.search(r'#define\s+TRK_TILE\s+(\d+)', src).group(1)) == _native.TRK_TILE

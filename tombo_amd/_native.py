@@ -105,12 +105,16 @@ GET_VALID_CPTS, GET_N_CPTS, GET_EVENT_MEANS, GET_SEG_NORM, GET_SEG_SV, GET_START
     GET_BAND_STARTS, GET_READ_TB, GET_DP_SEGS, GET_THEIL_SEN, GET_PATH, GET_LAST_ROW, \
     GET_DP_READ_START, GET_KERNEL_MS, GET_REF_MEANS, GET_REF_SDS, GET_SEGS, GET_STATUS, GET_START_FAIL, \
     GET_STALL_INTS, GET_N_STALL, GET_STALL_OFF, GET_SAMP_IND, GET_TB_PARALLEL, GET_ED_FUSED, GET_ED_TAKEN_POS, GET_ED_N_TAKEN, \
-    GET_DP_WORKGROUP, GET_ED_FORM, GET_TB_FORM, GET_TB_VERIFY_FAIL, GET_DP_FORM, GET_NORM_FORM = range(1, 34)
+    GET_DP_WORKGROUP, GET_ED_FORM, GET_TB_FORM, GET_TB_VERIFY_FAIL, GET_DP_FORM, GET_NORM_FORM, GET_TS_FORM = range(1, 35)
 # TBA_ED_FORM_* / TBA_TB_FORM_*: which kernels produced a read's change points / main traceback
 ED_FORM_NONE, ED_FORM_WG_SCAN_PEAKS, ED_FORM_DETECT_PICK, ED_FORM_SCORES_PEAKS, ED_FORM_DETECT_TT_PICK, \
     ED_FORM_TTEST_PEAKS = range(6)
 # TBA_NORM_FORM_*: which code found the medians of a read's normalisation
 NORM_FORM_NONE, NORM_FORM_SELECT, NORM_FORM_INT_COUNT, NORM_FORM_HIST = range(4)
+# TBA_GET_TS_FORM, int32[n][2]: (TBA_TS_FORM_*: what k_theil_sen did with the read, the pairs its one-pass form listed).
+# The last four: the generic select ran, and why the one-pass form declined
+TS_FORM_NONE, TS_FORM_SMALL, TS_FORM_FAST, TS_FORM_NO_SCRATCH, TS_FORM_NO_WINDOW, TS_FORM_LIST_OVERFLOW, \
+    TS_FORM_WINDOW_MISS = range(7)
 TB_FORM_NONE, TB_FORM_LANE, TB_FORM_LONG, TB_FORM_PAR16, TB_FORM_PAR64 = 0, 1, 2, 16, 64
 # TBA_GET_DP_FORM, int32[n][4]: (TBA_DP_FORM_* of the main forward pass, its cells-per-lane class, TBA_DP_START_* of
 # start discovery, class of the retry kernel); derived on the host from the run's launch decisions and per-read state
@@ -124,7 +128,7 @@ STAGE_SEGMENT, STAGE_EVENT_MEANS, STAGE_REF_LEVELS, STAGE_START, STAGE_ASSIGN, S
 PUT_VALID_CPTS, PUT_EVENT_MEANS, PUT_NORM, PUT_REF_MEANS, PUT_REF_SDS, PUT_DP_SEGS, \
     PUT_START_STATE = range(1, 8)
 MAX_BAND = 3072
-ABI_VERSION = 12  # TBA_ABI_VERSION of include/tombo_amd.h
+ABI_VERSION = 13  # TBA_ABI_VERSION of include/tombo_amd.h
 STAGE_NAMES = ["normalize", "cumsum", "scores", "peaks", "event_means", "ref_levels",
                "start_dp", "start_tb", "prep", "main_dp", "main_tb", "skip_resolve", "theil_sen",
                "rescale_score", "stalls", "total"]
@@ -135,6 +139,7 @@ _GET_SHAPES = {
     GET_N_CPTS: (np.int64, ('n',)), GET_DP_READ_START: (np.int64, ('n',)),
     GET_SEG_SV: (np.float64, ('n', 4)), GET_START: (np.float64, ('n', 4)),
     GET_THEIL_SEN: (np.float64, ('n', 4)), GET_PATH: (np.int32, ('n', 4)), GET_DP_FORM: (np.int32, ('n', 4)),
+    GET_TS_FORM: (np.int32, ('n', 2)),
     GET_LAST_ROW: (np.float64, ('n', MAX_BAND)), GET_KERNEL_MS: (np.float32, (32,)),
     GET_DEBUG_COUNTERS: (np.int64, ('n', 8)),
     GET_VALID_CPTS: (np.int64, ('ev',)), GET_EVENT_MEANS: (np.float64, ('ev',)),

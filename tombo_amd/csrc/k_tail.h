@@ -796,8 +796,10 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
     __shared__ u32 s_ncand;
     __shared__ double s_win[2];
     __shared__ int s_win_ok;
+    __shared__ int s_form;   // TBA_TS_FORM_* of this read (thread 0 alone writes and reads it: TBA_GET_TS_FORM)
     __shared__ double s_ev[MAX_TS_POINTS], s_md[MAX_TS_POINTS];
     ReadState &r = rs[blockIdx.x];
+    if (threadIdx.x == 0) { r.ts_form[0] = TBA_TS_FORM_NONE; r.ts_form[1] = 0; }
     if (r.status != TBA_OK) return;
     if (dp->o.skip_seq_scaling) return;
     const int tid = threadIdx.x;
@@ -898,6 +900,8 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
     // score buffers (n_raw doubles each)
     const i64 cap1 = r.n_raw, cap2 = scratch2 != nullptr ? r.n_raw : 0;
     const i64 cap = cap1 + cap2 < 65536 ? cap1 + cap2 : 65536;
+    // (which form fits the read, and why the fast one declined: the code is moved on at every decline point below)
+    if (tid == 0) { s_ncand = 0; s_form = n < TSW_MIN_POINTS ? TBA_TS_FORM_SMALL : TBA_TS_FORM_NO_SCRATCH; }
     if (n >= TSW_MIN_POINTS && scratch != nullptr && cap >= 4096) {
         double *cl1 = scratch + r.raw_off + blockIdx.x, *cl2 = scratch2 + r.raw_off;
         auto pair_at = [=](i64 k) { return k < cap1 ? cl1 + k : cl2 + (k - cap1); };
@@ -917,7 +921,7 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
         }
         const double glo = 0.5, gsc = (double)BS_NB / 1.0;
         for (int b = tid; b < BS_NB; b += SEL_NT) sm.hist[b] = 0;
-        if (tid == 0) { s_ncand = 0; s_win_ok = 0; }
+        if (tid == 0) { s_win_ok = 0; s_form = TBA_TS_FORM_NO_WINDOW; }
         __syncthreads();
         for (int t0 = 0; t0 < ds; t0++) { // sample: distance 1 + t0 * dmax / ds
             const int d = 1 + (int)(((i64)t0 * dmax) / ds);
@@ -1125,6 +1129,7 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
             __syncthreads();
             stamps.stamp(2);
             const i64 n_c = s_ncand;
+            if (tid == 0) s_form = n_c > cap ? TBA_TS_FORM_LIST_OVERFLOW : TBA_TS_FORM_WINDOW_MISS;
             if (n_c <= cap) {
                 // exact slopes of the listed pairs; in-window ones stay (in place of their a),
                 // the rest becomes +inf and the ones below t1 are counted
@@ -1165,6 +1170,7 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
                     }
                     slope = (ns & 1) ? a : (a + b) / 2.0;
                     fast_done = true;
+                    if (tid == 0) s_form = TBA_TS_FORM_FAST;
                 }
             }
         }
@@ -1180,6 +1186,7 @@ __global__ __launch_bounds__(SEL_NT, 6) void k_theil_sen(ReadState *rs, const De
     stamps.stamp(5);
     stamps.end();
     if (tid == 0) {
+        r.ts_form[0] = s_form; r.ts_form[1] = (i32)s_ncand;
         if (slope == 0) { r.status = TBA_RESCALE_FAIL; return; }
         double scale_corr = 1 / slope;
         double shift_corr = -inter / slope;

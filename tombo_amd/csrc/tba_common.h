@@ -47,6 +47,8 @@ struct ReadState {
     i32 tb_verify_fail;       // rows where k_tb_par_verify disagreed with the chunk-parallel traceback (k_tb_par.h; 0 expected)
     i32 norm_form;            // which code found this read's normalisation medians (TBA_NORM_FORM_*: TBA_GET_NORM_FORM)
                               // (TBA_ED_FORM_* / TBA_TB_FORM_*, include/tombo_amd.h: TBA_GET_ED_FORM / TBA_GET_TB_FORM)
+    i32 ts_form[2];           // k_theil_sen: which form fitted the read (TBA_TS_FORM_*), the pairs its one-pass form listed
+                              // (TBA_GET_TS_FORM)
     i64 n_taken;              // entries of the taken (score, position) list k_detect left
     double ed_min, ed_max;    // ... and the range of its scores
     i64 n_cpts, n_ev;

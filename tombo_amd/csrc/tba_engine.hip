@@ -1213,6 +1213,7 @@ extern "C" int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_byt
 #define PER_READ(T, ...) per_read([](const ReadState &r) -> T { return __VA_ARGS__; })
     typedef std::array<double, 4> D4;
     typedef std::array<i32, 4> I4;
+    typedef std::array<i32, 2> I2;
     typedef std::array<i64, 8> I8;
     switch (what) {
     case TBA_GET_START_FAIL: return PER_READ(i32, r.pad0);
@@ -1233,6 +1234,7 @@ extern "C" int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_byt
     case TBA_GET_SEG_SV: return PER_READ(D4, D4{r.shift, r.scale, r.lower, r.upper});
     case TBA_GET_START: return PER_READ(D4, to_array(r.start_res));
     case TBA_GET_THEIL_SEN: return PER_READ(D4, to_array(r.ts));
+    case TBA_GET_TS_FORM: return PER_READ(I2, to_array(r.ts_form));
     case TBA_GET_PATH: return PER_READ(I4, I4{r.path, (i32)r.n_static, (i32)r.W, r.n_start_calls});
     case TBA_GET_DEBUG_COUNTERS: return PER_READ(I8, to_array(r.dbg)); // phase cycle / sweep counters of a profiling build
     case TBA_GET_DP_FORM: {
