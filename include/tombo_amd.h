@@ -181,6 +181,15 @@ int  tba_engine_last_dp_const_division(tba_engine *e);
 int  tba_engine_set_dp_const_division(tba_engine *e, int mode);
 int  tba_engine_model_const_division(tba_engine *e);
 int  tba_prove_const_division(const double *sd, int64_t n, int32_t *proven);
+/* A level table whose sd column holds ONE value (Tombo's DNA and RNA models), that value a proven divisor: the
+ * reciprocal pair is the same in every row of every read, so tba_set_model makes it once on the host and the forward
+ * pass gets it as two kernel arguments (k_dp_c1: k_dp_cdiv with the pair the same in every lane instead of a lane
+ * per row, the level mean as the only per-row load, and no arg-max in the static rows whose arg-max nobody reads; same results bit for bit).  It runs wherever
+ * k_dp_cdiv would (above) and the table has one sd; tba_engine_last_dp_const_division and TBA_GET_DP_FORM report it as
+ * the two-operation form it is, TBA_GET_DP_ONE_SD tells the two apart per read (ABI 13.1).
+ * tba_one_sd_words: host only, no device needed: *one_sd = 1 and words[0..2] = sd, yh = RN(1 / sd),
+ * yl = RN(RN(1 - sd yh) yh) when the n values of sd are one bit pattern and proven, else *one_sd = 0 and zeros. */
+int  tba_one_sd_words(const double *sd, int64_t n, int32_t *one_sd, double *words);
 /* TBA_ED_FORM_* of the last tba_c_valid_cpts_w_cap / tba_c_valid_cpts_w_cap_t_test call on this engine
  * (those entries follow the engine's dispatch like a batch of one read) */
 int  tba_c_last_ed_form(tba_engine *e);
@@ -327,6 +336,10 @@ enum {
                                * the one-pass form's list of pairs (0 where its pass over the pairs did not run; the pairs
                                * inside the window or too close to tell, and for points beyond the float range some
                                * partners of the padding to 64, dropped later).  Written by the kernel */
+    TBA_GET_DP_ONE_SD = 35,   /* int32[n][2]: whether the read's forward passes ran on k_dp_c1, the one-sd form of the
+                               * two-operation division (tba_one_sd_words; ABI 13.1): [0] 1 -- the main pass did; [1] bit 0
+                               * -- the first try of start discovery did, bit 1 -- its retry did (a retry by k_dp_wg never
+                               * does).  Derived on the host like TBA_GET_DP_FORM, which reports these reads as before */
     TBA_GET_DEBUG_COUNTERS = 99 /* int64[n][8]: ReadState.dbg, only filled by the profiling builds (one of
                                    -DTBA_PHASE_DEBUG=<id>, -DTBA_SWEEP_STATS, -DTBA_SKIP_STATS, -DTBA_SKIP_CLASS_STATS;
                                    the slots of each: csrc/tba_phase.h), zeros otherwise */
@@ -1007,6 +1020,9 @@ int tba_synth_dwell_thresholds(const tba_synth_params *p, uint32_t *thr, int64_t
  * (n >= 4) = TBA_ABI_VERSION: lets a binding without a C compiler (ctypes) check its struct mirrors
  * and refuse a stale build of the library */
 #define TBA_ABI_VERSION 13
+/* additions that leave every struct, every entry and every selector of TBA_ABI_VERSION as it was (not part of
+ * tba_abi_sizes: a binding asks for what it needs by name).  1: tba_one_sd_words, TBA_GET_DP_ONE_SD */
+#define TBA_ABI_MINOR 1
 int tba_abi_sizes(int64_t *out, int64_t n);
 
 /* self-test: out[t] = index t of the subsample tba_opts.device_subsample draws for read

@@ -120,6 +120,8 @@ TB_FORM_NONE, TB_FORM_LANE, TB_FORM_LONG, TB_FORM_PAR16, TB_FORM_PAR64 = 0, 1, 2
 # start discovery, class of the retry kernel); derived on the host from the run's launch decisions and per-read state
 DP_FORM_NONE, DP_FORM_K_DP, DP_FORM_K_DP8_LOWREG, DP_FORM_MULTI, DP_FORM_WIDE = range(5)
 DP_START_NONE, DP_START_FIRST_TRY, DP_START_RETRY_WG, DP_START_RETRY_K_DP = range(4)
+# TBA_GET_DP_ONE_SD, int32[n][2]: (the main pass ran on k_dp_c1, bit 0 / 1: the first try / the retry of start discovery did)
+GET_DP_ONE_SD = 35
 # ReadState.dbg of a profiling build: -DTBA_PHASE_DEBUG=<id>, -DTBA_SWEEP_STATS, -DTBA_SKIP_STATS or
 # -DTBA_SKIP_CLASS_STATS (what each leaves in the eight slots: the table in csrc/tba_phase.h)
 GET_DEBUG_COUNTERS = 99
@@ -139,7 +141,7 @@ _GET_SHAPES = {
     GET_N_CPTS: (np.int64, ('n',)), GET_DP_READ_START: (np.int64, ('n',)),
     GET_SEG_SV: (np.float64, ('n', 4)), GET_START: (np.float64, ('n', 4)),
     GET_THEIL_SEN: (np.float64, ('n', 4)), GET_PATH: (np.int32, ('n', 4)), GET_DP_FORM: (np.int32, ('n', 4)),
-    GET_TS_FORM: (np.int32, ('n', 2)),
+    GET_TS_FORM: (np.int32, ('n', 2)), GET_DP_ONE_SD: (np.int32, ('n', 2)),
     GET_LAST_ROW: (np.float64, ('n', MAX_BAND)), GET_KERNEL_MS: (np.float32, (32,)),
     GET_DEBUG_COUNTERS: (np.int64, ('n', 8)),
     GET_VALID_CPTS: (np.int64, ('ev',)), GET_EVENT_MEANS: (np.float64, ('ev',)),
@@ -204,6 +206,7 @@ def _prototypes():
         'tba_engine_set_dp_const_division': (n, [v, n]),
         'tba_engine_model_const_division': (n, [v]),
         'tba_prove_const_division': (n, [cD, q, I]),
+        'tba_one_sd_words': (n, [cD, q, I, D]),
         'tba_c_last_ed_form': (n, [v]),
         'tba_set_model': (n, [v, cD, cD, q, q]),
         # ---- host memory for streaming ----
@@ -354,6 +357,15 @@ def prove_const_division(sds):
     out = np.zeros(sds.shape[0], dtype=np.int32)
     _call(lib(), 'tba_prove_const_division', sds, sds.shape[0], out)
     return out.astype(bool)
+
+
+def one_sd_words(sds):
+    """(sd, yh, yl) of a level table with one distinct, proven sd -- the words the one-sd forward pass reads
+    (tba_one_sd_words: host code, no device needed) -- or None"""
+    sds = np.ascontiguousarray(sds, dtype=np.float64).ravel()
+    flag, words = np.zeros(1, dtype=np.int32), np.zeros(3, dtype=np.float64)
+    _call(lib(), 'tba_one_sd_words', sds, sds.shape[0], flag, words)
+    return tuple(float(w) for w in words) if flag[0] else None
 
 
 def _f64(a):

@@ -238,11 +238,25 @@ __device__ __forceinline__ double shift_cells(double (&Q)[CPL])
 //   mu/sd    : prefetched one row ahead
 template <bool B> struct BoolTag { static constexpr bool value = B; };
 template <int I> struct IntTag { static constexpr int value = I; };
+// a static row of the one-sd form (dp_body): WANT_AM -- somebody reads the arg-max of its cells
+template <bool WANT_AM> struct StaticRowTag { static constexpr bool value = false; };
+template <class Tag> struct RowWantsAm { static constexpr bool value = true; };
+template <> struct RowWantsAm<StaticRowTag<false>> { static constexpr bool value = false; };
 
 // CDIV: the rows divide by their sd in two operations, div_const2 (tba_common.h) -- only for batches whose every sd
 // the host has proven (div_const_proof.h; the engine's choice, k_dp_cdiv below).  The lane register that holds sd
 // then holds the low word of its reciprocal: a row reads mu, yh, yl.
-template <int CPL, bool DIRECT, bool CDIV = false>
+// ONE_SD (with CDIV): the level table has a single sd (tba_one_sd_words; the engine's choice, k_dp_c1 below), so yh
+// and yl are the same two numbers in every row of every read: the host makes them once per model, the kernel gets
+// them as arguments, and a row reads mu alone -- no sd load, no division and no recip_low per 64 rows, two v_readlane per row
+// instead of six at the head of the row's dependent chain.  Same operand values, same operations on them.  In this
+// form a static row also leaves the arg-max of its cells alone unless somebody reads it: the first adaptive row
+// places its band by the arg-max of the last static row, top_pos is the arg-max of the read's last row, and `am`
+// is dead everywhere else (start discovery is 250 static rows of which the last one counts).
+// (The pair is a parameter PACK, empty in every other form: their dp_body has the parameters it always had.)
+__device__ __forceinline__ double one_sd_arg(int) { return 1.0; }
+__device__ __forceinline__ double one_sd_arg(int i, double yh, double yl) { return i ? yl : yh; }
+template <int CPL, bool DIRECT, bool CDIV = false, bool ONE_SD = false, class... Pair>
 // Waves per SIMD the register allocation of the classes up to 8 cells per lane is held to: 4 (128
 // VGPRs; k_dp<8> comes out at 133 without it since the row loop exists twice).  -DTBA_DP_WAVES=5 (96
 // VGPRs) was measured SLOWER, 70.4 against 65.6 ms at W = 500: the squeeze costs instructions and
@@ -259,7 +273,8 @@ template <int CPL, bool DIRECT, bool CDIV = false>
 __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int mode,
     const double *event_means, const double *ref_means, const double *ref_sds,
     i64 *band_starts, const i32 *lo_arr, const i32 *hi_arr,
-    unsigned char *moves, i64 start_moves_stride, double *last_row, DpJob *job)
+    unsigned char *moves, i64 start_moves_stride, double *last_row, DpJob *job,
+    Pair... one_sd_pair) // (ONE_SD: yh, yl -- the model's reciprocal pair, kernel arguments of k_dp_c1)
 {
     constexpr int S = CPL < 8 ? CPL : 8;     // band offsets 0..S take the register-renaming path
     constexpr int RING = CPL <= 4 ? 512 : CPL <= 8 ? 1024 : CPL <= 16 ? 2048 : CPL <= 32 ? 4096 : 8192; // power of two >= 128*CPL
@@ -423,13 +438,26 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
 
     // expected level, sd and its reciprocal of 64 rows at a time: lane l holds row blk0 + l
     // (one coalesced load and one true division per 64 rows), a row reads its lane.  CDIV: sd_v is yl.
-    double mu_v = 0, sd_v = 1, y_v = 1;
+    // ONE_SD: the reciprocal pair is wave-uniform and made by the host (tba_set_model), lane l holds mu only.
+    // The pair lives in the registers of the lane form, y_v and sd_v, which nothing writes again (no name of this
+    // function exists for the one-sd form alone, so the other forms compile to the code they had before it).
+    static_assert(!ONE_SD || (CDIV && !DIRECT), "the one-sd form is a batch form of the two-operation division");
+    // Every lane holds the pair, in vector registers on purpose: the scalar file of this kernel is full (106 with
+    // spills to lanes of a vector register, i.e. more v_readlane / v_writelane in the rows), and as scalars the pair
+    // would be live from here to the last row -- measured in the ISA, the 8-cell kernel went from 11 to 17-25 spilled
+    // scalars.  As vector operands they cost the four registers the lane form spends on them and no instruction.
+    static_assert(sizeof...(Pair) == (ONE_SD ? 2 : 0), "yh and yl with the one-sd form, and only with it");
+    double mu_v = 0, sd_v = ONE_SD ? one_sd_arg(1, one_sd_pair...) : 1, y_v = ONE_SD ? one_sd_arg(0, one_sd_pair...) : 1;
+    if constexpr (ONE_SD) asm volatile("" : "+v"(sd_v), "+v"(y_v));
     auto load_levels = [&](int first) {
         int rc = first + lane;
         rc = rc < n_rows ? rc : n_rows - 1;
-        mu_v = rmu[rc]; sd_v = rsd[rc];
-        y_v = 1.0 / sd_v;
-        if constexpr (CDIV) sd_v = recip_low(sd_v, y_v);
+        mu_v = rmu[rc];
+        if constexpr (!ONE_SD) {
+            sd_v = rsd[rc];
+            y_v = 1.0 / sd_v;
+            if constexpr (CDIV) sd_v = recip_low(sd_v, y_v);
+        }
         // the loads end HERE, once per 64 rows: left pending, the rows' read of these registers
         // sits behind a conditional load and the compiler guards it with s_waitcnt vmcnt(0) in
         // EVERY row (which on gfx9 also waits for the previous row's stores)
@@ -464,7 +492,9 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         if (!use_z) {
             const int sel = (row - row0) & 63;
             if (sel == 0 && row != row0) load_levels(row);
-            mu = readlane_f64(mu_v, sel); sd = readlane_f64(sd_v, sel); y = readlane_f64(y_v, sel);
+            mu = readlane_f64(mu_v, sel);
+            if constexpr (ONE_SD) { sd = sd_v; y = y_v; }
+            else { sd = readlane_f64(sd_v, sel); y = readlane_f64(y_v, sel); }
         }
         int cur_start;
         int lo, hi;
@@ -598,6 +628,8 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         u32 mvw[(CPL + 15) / 16];
 #pragma unroll
         for (int q = 0; q < (CPL + 15) / 16; q++) mvw[q] = 0;
+        // (ONE_SD: a static row takes its maximum, and finds where it is, only where its arg-max is read)
+        constexpr bool WANT_AM = RowWantsAm<decltype(adapt_tag)>::value;
         double lmax = NEG_INF;
         {
             double x = in;
@@ -608,7 +640,7 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
                 mvw[j / 16] |= f << (2 * (j % 16));
                 x = max_f64_raw(cv[j], s);
                 v[j] = x;
-                lmax = max_f64_raw(lmax, x);
+                if constexpr (WANT_AM) lmax = max_f64_raw(lmax, x);
             }
         }
         {
@@ -673,21 +705,23 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         // lane is the common case, several fall back to the float64 ladder.  The cell index
         // inside the winning lane comes from one compare + ballot per cell, resolved on the
         // scalar unit.
-        double wm;
-        {
-            const float fl = (float)lmax;
-            const float fm = wave_max_f32(fl);
-            const u64 cm = __ballot(fl == fm);
-            if (__popcll(cm) == 1) wm = readlane_f64(lmax, __ffsll((unsigned long long)cm) - 1);
-            else wm = wave_max_f64(lmax);
-        }
-        const u64 eq = __ballot(lmax == wm) & has_cells; // (the AND on the scalar unit: a lane predicate in the
-                                                         // ballot went through a 0/1 register and a second compare)
-        const int wl = __ffsll((unsigned long long)eq) - 1; // first lane holding the maximum
-        int wj = CPL - 1;
+        if constexpr (WANT_AM) {
+            double wm;
+            {
+                const float fl = (float)lmax;
+                const float fm = wave_max_f32(fl);
+                const u64 cm = __ballot(fl == fm);
+                if (__popcll(cm) == 1) wm = readlane_f64(lmax, __ffsll((unsigned long long)cm) - 1);
+                else wm = wave_max_f64(lmax);
+            }
+            const u64 eq = __ballot(lmax == wm) & has_cells; // (the AND on the scalar unit: a lane predicate in the
+                                                             // ballot went through a 0/1 register and a second compare)
+            const int wl = __ffsll((unsigned long long)eq) - 1; // first lane holding the maximum
+            int wj = CPL - 1;
 #pragma unroll
-        for (int j = CPL - 2; j >= 0; j--) wj = ((__ballot(v[j] == wm) >> wl) & 1ull) ? j : wj;
-        am = wl * CPL + wj;
+            for (int j = CPL - 2; j >= 0; j--) wj = ((__ballot(v[j] == wm) >> wl) & 1ull) ? j : wj;
+            am = wl * CPL + wj;
+        }
         prev_start = cur_start;
         laps.lap(4);
         laps.count(6);
@@ -696,6 +730,12 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
     {
         int row = row0;
         const int n_stat_rows = n_static < n_rows ? n_static : n_rows;
+        // ONE_SD: the one static row whose arg-max is read is the last one -- the row before the first adaptive row, or,
+        // in a read that is static to its end, the read's last row (top_pos)
+        if constexpr (ONE_SD) {
+            for (; row < n_stat_rows - 1; row++) if (row_step(row, StaticRowTag<false>{})) return;
+            for (; row < n_stat_rows; row++) if (row_step(row, StaticRowTag<true>{})) return;
+        } else
         for (; row < n_stat_rows; row++) if (row_step(row, BoolTag<false>{})) return;
         for (; row < n_rows; row++) if (row_step(row, BoolTag<true>{})) return;
     }
@@ -732,6 +772,15 @@ template <int CPL>
 __global__ __launch_bounds__(64) TBA_DP_WAVES_ATTR void k_dp_cdiv(TBA_DP_ARGS)
 {
     dp_body<CPL, false, true>(TBA_DP_PASS);
+}
+// ... and of a model with ONE proven sd (dp_body's ONE_SD): the reciprocal pair made once by the host, mu the only
+// per-row level, static rows without the arg-max nobody reads.  Kernels of their own again: k_dp_cdiv<CPL> is the
+// form of a proven table with several sds and keeps its name, its code and its register budget.
+// (yh, yl: tba_one_sd_words.  Arguments, not DevParams fields: the struct's size is part of the batch footprint.)
+template <int CPL>
+__global__ __launch_bounds__(64) TBA_DP_WAVES_ATTR void k_dp_c1(TBA_DP_ARGS, double yh, double yl)
+{
+    dp_body<CPL, false, true, true>(TBA_DP_PASS, yh, yl);
 }
 // The batch form of the 8-cell class (W = 500) under a register budget of 112 instead of 128
 // (amdgpu_num_vgpr counts in units of two on gfx90a+: 56; it takes no template-dependent value,

@@ -145,7 +145,7 @@ __device__ __forceinline__ double div_by_recip2(double a, double b, double yh, d
     const double e = __builtin_fma(-b, q, a);
     return __builtin_fma(e, yh, q);
 }
-__device__ __forceinline__ double recip_low(double b, double yh) { return __builtin_fma(-b, yh, 1.0) * yh; }
+__host__ __device__ __forceinline__ double recip_low(double b, double yh) { return __builtin_fma(-b, yh, 1.0) * yh; }
 
 // The same quotient in TWO instructions, div_by_recip2 without its correction: RN(a yh + RN(a yl)) is within
 // 1.5 * 2^-105 of a / b before the rounding, so it IS RN(a / b) except for the few dividends whose quotient lies

@@ -138,6 +138,10 @@ struct tba_engine {
     // is proven (div_const_proof.h, tba_set_model); refs_put -- the batch's d_refs came from the caller
     // (TBA_PUT_REF_SDS), not from the table; cdiv_auto -- tba_engine_set_dp_const_division
     bool model_cdiv = false, refs_put = false, cdiv_auto = true;
+    // ... and its one-sd form (k_dp_c1): the model's table has ONE sd, proven; one_sd_w -- that sd, yh = RN(1 / sd),
+    // yl = recip_low(sd, yh) (one_sd_words, tba_set_model): model state, handed to the kernels as arguments
+    bool one_sd = false;
+    double one_sd_w[3] = {0.0, 0.0, 0.0};
     int n_sharing = 1;            // engines fed concurrently on this device (tba_engine_set_sharing)
     int side_mode = -1;           // tba_engine_set_side_stream: -1 by the engines alive, 0 never, 1 always
     bool last_side = false;       // the last full run used the side stream
@@ -146,6 +150,8 @@ struct tba_engine {
     struct DpLaunches {
         bool start = false, main = false, lowreg = false, wide = false;
         bool cdiv_main = false, cdiv_start = false; // k_dp_cdiv took the main pass / start discovery (dp_cdiv)
+        // ... in its one-sd form, k_dp_c1 (dp_one_sd): the main pass, the first try, a retry that went through k_dp
+        bool c1_main = false, c1_start = false, c1_retry = false;
         int retry_wcpl = 0;       // class of the retry's k_dp_wg; 0: k_dp<class of start_save_bw> in retry mode
     } last_dp;
     // latency / throughput forms of event detection and traceback (tba_engine_set_dispatch)
@@ -251,6 +257,28 @@ extern "C" int tba_prove_const_division(const double *sd, int64_t n, int32_t *pr
     return 0;
 }
 
+// The words of a level table with ONE distinct sd (by bit pattern), a proven divisor: the sd, yh = RN(1 / sd) and
+// yl = recip_low(sd, yh) -- the division and the function the rows of k_dp_cdiv make them with (k_dp.h,
+// load_levels), so the same bits.  false: the table has several sds, or its one sd is not proven.
+static bool one_sd_words(const double *sds, size_t n, double (&w)[3])
+{
+    if (n == 0 || !sds_all_proven(sds, n)) return false;
+    for (size_t i = 1; i < n; i++) if (memcmp(sds + i, sds, 8) != 0) return false;
+    w[0] = sds[0];
+    w[1] = 1.0 / w[0];
+    w[2] = recip_low(w[0], w[1]);
+    return true;
+}
+
+extern "C" int tba_one_sd_words(const double *sd, int64_t n, int32_t *one_sd, double *words)
+{
+    if (n < 0 || (n > 0 && !sd) || !one_sd || !words) return set_err(TBA_E_ARG, "bad arguments");
+    double w[3] = {0.0, 0.0, 0.0};
+    *one_sd = one_sd_words(sd, (size_t)n, w) ? 1 : 0;
+    memcpy(words, w, sizeof(w));
+    return 0;
+}
+
 extern "C" int tba_set_model(tba_engine *e, const double *kmer_means, const double *kmer_sds,
                              int64_t kmer_width, int64_t central_pos)
 {
@@ -266,6 +294,9 @@ extern "C" int tba_set_model(tba_engine *e, const double *kmer_means, const doub
     e->hp.central_pos = central_pos;
     e->have_model = true;
     e->model_cdiv = sds_all_proven(kmer_sds, n);
+    double w[3] = {0.0, 0.0, 0.0};
+    e->one_sd = one_sd_words(kmer_sds, n, w);
+    memcpy(e->one_sd_w, w, sizeof(w));
     // a batch uploaded under another model has stale per-read geometry (B depends on K)
     e->have_batch = e->ran = e->finished = false;
     return 0;
@@ -596,6 +627,8 @@ static bool dp_lowreg(const tba_engine *e) { return e->n_sharing > 1 && e->z.cel
 // k_dp<CPL> or k_dp_cdiv<CPL>, the two-operation division: the latter when every sd the rows can meet is a proven
 // divisor, i.e. the model's table is and d_refs was filled from it (k_ref_levels copies the table's values)
 static bool dp_cdiv(const tba_engine *e) { return e->cdiv_auto && e->model_cdiv && !e->refs_put; }
+// ... or k_dp_c1<CPL>, its form for a table with ONE sd (the reciprocal pair comes from one_sd_w as kernel arguments, not from d_refs)
+static bool dp_one_sd(const tba_engine *e) { return dp_cdiv(e) && e->one_sd; }
 
 // ---- the pipeline -----------------------------------------------------------------------------
 // One run over the uploaded batch, as its steps see it: the engine, its streams, the grid sizes, the kernel
@@ -651,6 +684,12 @@ static void launch_dp_t(Run &c, int mode)
 {
     // (a main pass under k_dp8_lowreg's selector stays on the general division in every class: step_main_dp)
     const bool lowreg = mode == DP_MAIN && dp_lowreg(c.e);
+    unsigned char *const mv = mode == DP_MAIN ? c.moves : c.smoves;
+    if (dp_one_sd(c.e) && !lowreg) {
+        k_dp_c1<CPL><<<dim3(c.nb), dim3(64), 0, c.s>>>(c.rs, c.dp, mode, c.evm, c.refm, c.refs, c.bst, c.lo, c.hi, mv, c.e->z.start_moves_stride, c.lastrow, nullptr,
+                                                       c.e->one_sd_w[1], c.e->one_sd_w[2]);
+        return;
+    }
     const auto k = CPL == 8 && lowreg ? k_dp8_lowreg : dp_cdiv(c.e) && !lowreg ? k_dp_cdiv<CPL> : k_dp<CPL, false>;
     k<<<dim3(c.nb), dim3(64), 0, c.s>>>(c.rs, c.dp, mode, c.evm, c.refm, c.refs, c.bst, c.lo, c.hi, mode == DP_MAIN ? c.moves : c.smoves, c.e->z.start_moves_stride, c.lastrow, nullptr);
 }
@@ -819,6 +858,7 @@ static int step_start_dp(Run &c)
 {
     k_path0<<<c.tpr, 64, 0, c.s>>>(c.rs, c.n, c.dp);
     c.e->last_dp.cdiv_start = dp_cdiv(c.e);
+    c.e->last_dp.c1_start = dp_one_sd(c.e);
     launch_dp(c, cpl_class(c.P.start_bw), DP_START_TRY);
     launch_start_tb(c, DP_START_TRY);
     return 0;
@@ -828,6 +868,7 @@ static int step_start_tb(Run &c)
     // the retry of the few reads whose first try failed: one workgroup per read (k_dp_wg.h)
     const int wcpl = c.P.start_n_bases <= WG_MAX_ROWS ? dp_wg_cpl(c.P.start_save_bw) : 0;
     c.e->last_dp.start = true, c.e->last_dp.retry_wcpl = wcpl;
+    c.e->last_dp.c1_retry = wcpl == 0 && dp_one_sd(c.e); // (k_dp_wg has the general division only)
     const auto wg = wcpl == 4 ? k_dp_wg<4> : wcpl == 8 ? k_dp_wg<8> : wcpl == 12 ? k_dp_wg<12> : nullptr;
     if (wg) wg<<<c.nb, 256, 0, c.s>>>(c.rs, c.dp, c.evm, c.refm, c.refs, c.smoves, c.e->z.start_moves_stride, c.lastrow);
     else launch_dp(c, cpl_class(c.P.start_save_bw), DP_START_RETRY);
@@ -846,6 +887,7 @@ static int step_main_dp(Run &c)
     c.e->last_dp.main = true, c.e->last_dp.wide = wide_w != 0;
     c.e->last_dp.lowreg = dp_lowreg(c.e); // (launch_dp_t's choice for the 8-cell class)
     c.e->last_dp.cdiv_main = dp_cdiv(c.e) && !dp_lowreg(c.e); // (... and for every class)
+    c.e->last_dp.c1_main = dp_one_sd(c.e) && !dp_lowreg(c.e);
     for (int cls : DpClasses::list) launch_dp(c, cls, DP_MAIN);
     const DpMultiClass m = dp_multi_class(c.P.bandwidth); // narrow adaptive bands: several reads per wavefront
     if (m.cpl == 4 && m.rpw == 2) launch_dp_multi_t<4, 2>(c);
@@ -1265,6 +1307,23 @@ extern "C" int tba_batch_get(tba_engine *e, int what, void *out, int64_t out_byt
                 f[2] = L.retry_wcpl ? TBA_DP_START_RETRY_WG : TBA_DP_START_RETRY_K_DP, f[3] = retry_cpl;
             else if (L.start && tried)
                 f[2] = TBA_DP_START_FIRST_TRY;
+            return f;
+        });
+    }
+    case TBA_GET_DP_ONE_SD: {
+        // Derived like TBA_GET_DP_FORM, whose predicates these are: the reads a k_dp launch of the last run took, where
+        // that launch was k_dp_c1
+        const tba_params &P = e->hp.p;
+        const tba_engine::DpLaunches L = e->last_dp;
+        const int multi_cpl = dp_multi_class(P.bandwidth).cpl;
+        return per_read([&](const ReadState &r) -> I2 {
+            I2 f{0, 0};
+            if (L.main && L.c1_main && r.path != PATH_NONE && cpl_class(r.W) != 0 &&
+                !(r.path == PATH_ADAPTIVE && r.W == P.bandwidth && multi_cpl != 0)) f[0] = 1;
+            const bool retried = r.n_start_calls == 2 || r.start_state == ST_RETRY;
+            const bool tried = retried || r.n_start_calls == 1 || r.pad0 != 0 || r.start_state == ST_TRY;
+            if (L.start && tried && L.c1_start) f[1] |= 1;
+            if (L.start && retried && L.c1_retry) f[1] |= 2;
             return f;
         });
     }

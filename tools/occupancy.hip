@@ -47,6 +47,11 @@ int main()
     report("k_dp8_lowreg", k_dp8_lowreg, 64);
     report("k_dp<5,false>", k_dp<5, false>, 64);
     report("k_dp<12,false>", k_dp<12, false>, 64);
+    report("k_dp_cdiv<8>", k_dp_cdiv<8>, 64);
+    report("k_dp_cdiv<12>", k_dp_cdiv<12>, 64);
+    report("k_dp_c1<8>", k_dp_c1<8>, 64);
+    report("k_dp_c1<5>", k_dp_c1<5>, 64);
+    report("k_dp_c1<12>", k_dp_c1<12>, 64);
     report("k_dp_multi<4,2>", k_dp_multi<4, 2>, 64);
     report("k_cumsum_scores<32,i16,1>", k_cumsum_scores<32, int16_t, 1>, 256);
     report("k_stall_metric<7>", k_stall_metric<7>, 256);
