@@ -456,6 +456,15 @@ int tba_c_adaptive_banded_forward_pass_z(tba_engine *e, double *fwd_pass, int64_
 int tba_c_banded_forward_pass(tba_engine *e, const double *shifted_z_scores, int64_t n_bases,
     int64_t bandwidth, const int64_t *event_starts, double skip_pen, double stay_pen,
     double *fwd_pass, int64_t *fwd_pass_tb);
+/* ... with adaptive rows behind the first n_static ones (1 <= n_static <= n_bases): from row n_static on a row's
+ * band start follows the arg-max of the row before (pyx:342-358, against n_events) and is written to
+ * event_starts[n_static..]; the row's band cells are its row of shifted_z_scores wherever the band lies.
+ * top_pos: the arg-max of the last row.
+ * FOR THE TESTS of the forward pass's kernel (a z matrix of the caller's making reaches rows the event path cannot
+ * be made to hold); no counterpart in the reference, not part of the drop-in surface, may change without notice. */
+int tba_c_banded_forward_pass_adaptive(tba_engine *e, const double *shifted_z_scores, int64_t n_bases,
+    int64_t bandwidth, int64_t *event_starts, int64_t n_static, int64_t n_events, double skip_pen,
+    double stay_pen, double *fwd_pass, int64_t *fwd_pass_tb, int64_t *top_pos);
 /* c_banded_traceback, pyx:281-310 */
 int tba_c_banded_traceback(tba_engine *e, const int64_t *fwd_pass_tb, int64_t n_bases,
     int64_t bandwidth, const int64_t *event_starts, int64_t band_pos,

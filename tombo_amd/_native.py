@@ -234,6 +234,7 @@ def _prototypes():
         'tba_c_adaptive_banded_forward_pass': (n, fwd_pass),
         'tba_c_adaptive_banded_forward_pass_z': (n, fwd_pass + [D]),
         'tba_c_banded_forward_pass': (n, [v, cD, q, q, cQ, d, d, D, Q]),
+        'tba_c_banded_forward_pass_adaptive': (n, [v, cD, q, q, Q, q, q, d, d, D, Q, Q]),
         'tba_c_banded_traceback': (n, [v, cQ, q, q, cQ, q, q, Q]),
         'tba_c_base_z_scores': (n, [v, cD, q, d, d, n, d, D]),
         'tba_c_new_means': (n, [v, cD, q, cQ, q, D]),

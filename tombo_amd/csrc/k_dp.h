@@ -173,6 +173,41 @@ __device__ __forceinline__ double max_f64_raw(double a, double b)
     return r;
 }
 
+// The first cell of the winning lane that holds the row's maximum (dp_body's arg-max; c_argmax, pyx:186-197: first
+// index among equal maxima), found in one float64 compare per LEVEL of a pairwise tree instead of one per cell.
+// lane_tree_max<LO, N>: the maximum of cells LO .. LO+N-1 as a tree (N - 1 v_max_f64, what a running maximum seeded
+// by its first cell takes); a node that splits behind cell k leaves the maximum of its LEFT half in t[k] (of a pair:
+// the cell itself, no register).  lane_tree_first<LO, N>: the left half holds a cell equal to wm exactly when its
+// maximum equals wm (a maximum is one of its operands; +0 and -0 compare equal here as they do cell by cell; a NaN
+// cell equals nothing and is dropped by v_max_f64), so the descent goes left there and right otherwise, and ends on
+// the first such cell.  The lane wl and every ballot are scalars: the branches are wave-uniform, and with the
+// lane's own `lmax == wm` four compares run for 8 cells where eight did.
+template <int LO, int N, int CPL>
+__device__ __forceinline__ double lane_tree_max(const double (&v)[CPL], double (&t)[CPL])
+{
+    if constexpr (N == 1) return v[LO];
+    else {
+        constexpr int H = (N + 1) / 2;
+        const double l = lane_tree_max<LO, H>(v, t), r = lane_tree_max<LO + H, N - H>(v, t);
+        t[LO + H - 1] = l;
+        return max_f64_raw(l, r);
+    }
+}
+template <int LO, int N, int CPL>
+__device__ __forceinline__ int lane_tree_first(const double (&v)[CPL], const double (&t)[CPL], double wm, int wl)
+{
+    if constexpr (N == 1) return LO;
+    else {
+        constexpr int H = (N + 1) / 2;
+        if ((__ballot(t[LO + H - 1] == wm) >> wl) & 1ull) return lane_tree_first<LO, H>(v, t, wm, wl);
+        return lane_tree_first<LO + H, N - H>(v, t, wm, wl);
+    }
+}
+// The class whose row takes this and drops its no-op arithmetic (dp_body's DIET): 8 cells per lane, W = 500, the main
+// pass of the flagship batch and the one class the change was measured in.  Every other class keeps the row it had,
+// statement for statement: its kernels are the same code as before (tools/isa_same.py).
+__host__ __device__ constexpr bool dp_row_diet(int cpl) { return cpl == 8; }
+
 // Previous-row access without memory: every lane keeps its CPL cells of the previous row in
 // registers; the cells a row needs are that row shifted by the (wave-uniform) band offset, i.e. a
 // compile-time register renaming per offset plus a few wave_shl DPP moves for the cells that come
@@ -601,11 +636,12 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         z[0] = lane == 0 ? NEG_INF : z[0];
         double in = lane == 0 ? 0.0 : NEG_INF;
         bool converged = false;
+        constexpr bool DIET = dp_row_diet(CPL);
         double exit0 = NEG_INF;                // sweep 1
-#pragma unroll
-        for (int j = 0; j < CPL; j++) exit0 = max_f64_raw(cv[j], (exit0 - stay_pen) + z[j]);
         i64 sw_row = 1;                        // sweeps of this row (-DTBA_SWEEP_STATS only: dead otherwise)
-        {
+        if constexpr (!DIET) {
+#pragma unroll
+            for (int j = 0; j < CPL; j++) exit0 = max_f64_raw(cv[j], (exit0 - stay_pen) + z[j]);
             double nin = wave_shr1_f64_zero(exit0);
             for (int it = 0; it < 66; it++) { // <= 64 sweeps by induction over lanes (NaN-proof bound)
                 if (__ballot(nin != in) == 0) { converged = true; break; }
@@ -615,6 +651,39 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
                 for (int j = 0; j < CPL; j++) c = (c - stay_pen) + z[j];
                 nin = wave_shr1_f64_zero(max_f64_raw(exit0, c));
                 if constexpr (TBA_SWEEP_STATS_ON) sw_row++;
+            }
+        } else {
+            // DIET leaves out what the row above computes for nothing.
+            // Sweep 1: its first cell is the candidate itself.  From -inf the stay term is (-inf - stay_pen) + z[0] =
+            // -inf (z is finite or -inf, never +inf) and max(cv[0], -inf) = cv[0]: three float64 instructions the
+            // compiler may not fold without fast-math.  NaNs: v_max_f64 returns its OTHER operand, so a NaN never
+            // survives a maximum with a number -- a NaN z[0] made the stay term NaN, which the maximum dropped: cv[0]
+            // again.  The one difference: a NaN cv[0] used to be dropped for -inf and is now kept, until cell 1's
+            // maximum drops it -- so exit0 differs only in a lane whose candidates are ALL NaN (NaN instead of -inf).
+            // That takes NaNs in CPL cells on end of the previous row, and a row writes a NaN into a lane's first cell
+            // at most (every other candidate is a maximum with the skip move's number): only a caller's own start row
+            // can hold them.  Such a row then fails with TBA_INTERNAL at the sweep bound (NaN != NaN) where it used
+            // to go on with the NaNs ignored.
+            exit0 = cv[0];
+#pragma unroll
+            for (int j = 1; j < CPL; j++) exit0 = max_f64_raw(cv[j], (exit0 - stay_pen) + z[j]);
+            // The convergence test follows the carry sweep, so the first carry sweep runs without one.  Before it `in`
+            // is -inf in every lane but lane 0 and nin the left neighbour's sweep-1 exit: a test there can only pass
+            // in a row whose lanes all left -inf -- one v_cmp_neq_f64 per row for nothing.  In such a row the sweep
+            // takes in = nin, the same bits (that test WOULD have passed), carries -inf through -inf (a NaN z is
+            // dropped by the maximum with exit0 = -inf), and the test after it passes: same `in`, same cells, one
+            // sweep more in TBA_SWEEP_STATS' count of those rows and of no other.  Every other test sits where it sat.
+            // (66 iterations as above, one test more than needed: a trip count the compiler unrolls by three as it
+            // does there; at 65 it left the loop rolled and every sweep paid the loop's branch.)
+            double nin = wave_shr1_f64_zero(exit0);
+            for (int it = 0; it < 66; it++) { // <= 64 sweeps by induction over lanes (NaN-proof bound)
+                in = nin;
+                double c = in;
+#pragma unroll
+                for (int j = 0; j < CPL; j++) c = (c - stay_pen) + z[j];
+                nin = wave_shr1_f64_zero(max_f64_raw(exit0, c));
+                if constexpr (TBA_SWEEP_STATS_ON) sw_row++;
+                if (__ballot(nin != in) == 0) { converged = true; break; }
             }
         }
         if constexpr (TBA_SWEEP_STATS_ON) sw_total += sw_row;
@@ -630,6 +699,7 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         for (int q = 0; q < (CPL + 15) / 16; q++) mvw[q] = 0;
         // (ONE_SD: a static row takes its maximum, and finds where it is, only where its arg-max is read)
         constexpr bool WANT_AM = RowWantsAm<decltype(adapt_tag)>::value;
+        // (DIET: the lane's maximum is taken below, as a tree over the finished cells, where the arg-max reads it)
         double lmax = NEG_INF;
         {
             double x = in;
@@ -640,7 +710,7 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
                 mvw[j / 16] |= f << (2 * (j % 16));
                 x = max_f64_raw(cv[j], s);
                 v[j] = x;
-                if constexpr (WANT_AM) lmax = max_f64_raw(lmax, x);
+                if constexpr (WANT_AM && !DIET) lmax = max_f64_raw(lmax, x);
             }
         }
         {
@@ -704,8 +774,10 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
         // ladder on 32-bit values is one instruction per step instead of three); one candidate
         // lane is the common case, several fall back to the float64 ladder.  The cell index
         // inside the winning lane comes from one compare + ballot per cell, resolved on the
-        // scalar unit.
+        // scalar unit -- or, DIET, from lane_tree_first's descent: one compare per level of the lane's tree.
         if constexpr (WANT_AM) {
+            double lhalf[CPL];                 // DIET: lane_tree_max's left-half maxima (unused otherwise)
+            if constexpr (DIET) lmax = lane_tree_max<0, CPL>(v, lhalf);
             double wm;
             {
                 const float fl = (float)lmax;
@@ -718,8 +790,11 @@ __device__ __forceinline__ void dp_body(ReadState *rs, const DevParams *dp, int 
                                                              // ballot went through a 0/1 register and a second compare)
             const int wl = __ffsll((unsigned long long)eq) - 1; // first lane holding the maximum
             int wj = CPL - 1;
+            if constexpr (DIET) wj = lane_tree_first<0, CPL>(v, lhalf, wm, wl);
+            else {
 #pragma unroll
-            for (int j = CPL - 2; j >= 0; j--) wj = ((__ballot(v[j] == wm) >> wl) & 1ull) ? j : wj;
+                for (int j = CPL - 2; j >= 0; j--) wj = ((__ballot(v[j] == wm) >> wl) & 1ull) ? j : wj;
+            }
             am = wl * CPL + wj;
         }
         prev_start = cur_start;

@@ -1474,7 +1474,8 @@ static void launch_direct(tba_engine *e, int cpl, DpJob *job)
 
 // shared by the two forward-pass entry points
 static int run_direct_dp(tba_engine *e, DpJob hj, int cpl, i64 n_rows, i64 W, i64 row0,
-                         double *fwd_host, int64_t *tb_host, int64_t *starts_host, i64 starts_from)
+                         double *fwd_host, int64_t *tb_host, int64_t *starts_host, i64 starts_from,
+                         int64_t *top_pos_host = nullptr)
 {
     const i64 stride = (i64)cpl * 64;            // forward rows
     const i64 mstride = mv_class_rowb(cpl);      // packed 2-bit move rows
@@ -1491,6 +1492,7 @@ static int run_direct_dp(tba_engine *e, DpJob hj, int cpl, i64 n_rows, i64 W, i6
     launch_direct(e, cpl, d_job);
     if (sc.sync() || sc.get(&hj, d_job, 1)) return sc.rc;
     if (hj.status != TBA_OK) return hj.status;
+    if (top_pos_host) *top_pos_host = hj.top_pos;
     std::vector<unsigned char> mv((size_t)(n_rows + 1) * mstride);
     std::vector<double> fw((size_t)(n_rows + 1) * stride);
     if (sc.get(mv.data(), d_mv, mv.size()) || sc.get(fw.data(), d_fwd, fw.size())) return sc.rc;
@@ -1587,6 +1589,35 @@ extern "C" int tba_c_banded_forward_pass(tba_engine *e, const double *shifted_z_
     j.skip_pen = skip_pen; j.stay_pen = stay_pen;
     int rc = run_direct_dp(e, j, cpl, n_bases, bandwidth, 0, fwd_pass, fwd_pass_tb, nullptr, 0);
     if (rc == TBA_OK) // row 0 of the move matrix is never read; the reference leaves it empty
+        for (i64 b = 0; b < bandwidth; b++) fwd_pass_tb[b] = 0;
+    return rc;
+}
+
+// The forward pass over a given z matrix with adaptive rows behind the static ones: k_dp<CPL, true>'s zmat form
+// with n_static < n_rows (a row's band cells are its z row whatever its start; the start moves the previous row)
+extern "C" int tba_c_banded_forward_pass_adaptive(tba_engine *e, const double *shifted_z_scores,
+    int64_t n_bases, int64_t bandwidth, int64_t *event_starts, int64_t n_static, int64_t n_events,
+    double skip_pen, double stay_pen, double *fwd_pass, int64_t *fwd_pass_tb, int64_t *top_pos)
+{
+    if (!e || !shifted_z_scores || !event_starts || !fwd_pass || !fwd_pass_tb || !top_pos || n_bases < 1 ||
+        bandwidth < 2 || n_static < 1 || n_static > n_bases || n_events < 1 || n_events > 0x7fffffff)
+        return set_err(TBA_E_ARG, "bad arguments");
+    const int cpl = cpl_class(bandwidth);
+    if (!cpl) return TBA_UNSUPPORTED;
+    for (i64 i = 0; i < n_static; i++)
+        if (event_starts[i] < 0 || event_starts[i] >= n_events || (i > 0 && event_starts[i] < event_starts[i - 1]))
+            return set_err(TBA_E_ARG, "event_starts must be non-decreasing inside [0, n_events)");
+    DpJob j;
+    memset(&j, 0, sizeof(j));
+    Scratch sc(e);
+    j.zmat = sc.in(shifted_z_scores, (size_t)n_bases * bandwidth);
+    j.starts = sc.in(event_starts, n_bases);
+    if (sc.rc) return sc.rc;
+    j.W = bandwidth; j.n_rows = n_bases; j.row0 = 0; j.n_static = n_static; j.n_ev = n_events;
+    j.init_row = nullptr;
+    j.skip_pen = skip_pen; j.stay_pen = stay_pen;
+    int rc = run_direct_dp(e, j, cpl, n_bases, bandwidth, 0, fwd_pass, fwd_pass_tb, event_starts, n_static, top_pos);
+    if (rc == TBA_OK)
         for (i64 b = 0; b < bandwidth; b++) fwd_pass_tb[b] = 0;
     return rc;
 }

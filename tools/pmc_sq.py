@@ -4,7 +4,7 @@ instruction figures bench.py's roofline_valu entry uses.
     python tools/pmc_sq.py <results.db> <reads> <rows_per_read> [<key>]   # e.g. DNA_b10000_w500
 
 Prints, per kernel, the sum of every collected counter, and for the main banded DP
-(k_dp<CPL, false> with the most SQ_INSTS_VALU) the VALU wave-instructions per read and per DP
+(the k_dp<CPL, false>, k_dp_cdiv, k_dp_c1 or k_dp_multi kernel with the most SQ_INSTS_VALU) the VALU wave-instructions per read and per DP
 row; with <key> it also prints the JSON fragment for profiles/valu_counts.json."""
 import sys
 import json
@@ -26,7 +26,7 @@ def main(db, reads, rows, key=None):
         if kname.startswith('__amd'):
             continue
         print('%-40s %s' % (kname[:40], ' '.join('%18.4g' % tab[kname].get(x, (0, 0))[0] for x in ctrs)))
-    dp = [k for k in tab if k.startswith(('k_dp<', 'k_dp_multi<')) and 'SQ_INSTS_VALU' in tab[k]]
+    dp = [k for k in tab if k.startswith(('k_dp<', 'k_dp_cdiv<', 'k_dp_c1<', 'k_dp_multi<')) and 'SQ_INSTS_VALU' in tab[k]]
     if dp:
         main_dp = max(dp, key=lambda k: tab[k]['SQ_INSTS_VALU'][0])
         v, n = tab[main_dp]['SQ_INSTS_VALU']
