@@ -843,6 +843,37 @@ int tba_region_key_levels(tba_engine *e, int est_mean, int64_t n_reads, const in
  * for an even count, NaN for an empty segment or one that holds a NaN.  values is not modified. */
 int tba_segment_medians(tba_engine *e, const double *values, const int64_t *off, int64_t n_seg,
     double *out_medians);
+/* center_model_to_median_norm (tombo_stats.py:1599-1705) for a batch of reads, in two calls (csrc/k_center.h; ABI
+ * minor 2).  The reference draws the Theil-Sen subsample of a read of more than 1000 points with np.random.choice, in
+ * read order, and only for a read that got as far as the fit: the caller draws between the two calls, for the reads
+ * whose status after the first is TBA_OK.
+ * tba_center_prepare: the batch as tba_batch_upload_async takes it (raw int16 / float32 / float64, same bits for the
+ * same values; seq = the `base` column as codes), plus the `start` column of every read's Events table (starts, CSR
+ * by start_off[n_reads + 1]) and read_start_rel_to_raw[n_reads].  It normalises every read's whole raw signal and
+ * keeps it on the device -- p->use_t_test_seg == 0 (DNA): ts.normalize_raw_signal alone; otherwise (RNA) what
+ * get_event_scale_values does: the samples are reversed (o->reverse_raw), stalls detected on them
+ * (o->detect_stalls), t-test change points with num_events[read] of compute_num_events, stall change points
+ * removed, scale values from the events (o->use_rna_event_scale, limits +-o->outlier_thresh), normalisation
+ * with them.  num_events is required for RNA and ignored for DNA.  Then the expected levels of seq under the
+ * model of tba_set_model, and the read's own boundaries: with up = central_pos, dn = kmer_width - up - 1 >= 1 a read
+ * of n rows gets read_start = read_start_rel_to_raw + start[up] and the n - kmer_width + 2 boundaries
+ * start[up .. n - dn] - start[up].  status[n_reads]: TBA_SEQ_SEG_MISMATCH where rows and bases differ in number or
+ * are fewer than kmer_width + 1, TBA_ZERO_LEN where the boundaries do not strictly increase, TBA_NEG_START /
+ * TBA_PAST_END where they leave the raw signal, TBA_INVALID_SEQ, TBA_FEWER_CPTS and the other codes of the steps
+ * above; TBA_INTERNAL for a signal of fewer than 4 * running_stat_width + 2 samples.  kernel_ms (may be NULL): device
+ * time of the call's kernels.
+ * tba_center_fit, on the batch tba_center_prepare left: samp_ind[n_reads][1000] as in tba_batch_upload (NULL when no
+ * read of the batch has more than 1000 points), k_theil_sen over the boundaries, then the pick: the successes of
+ * the calls before (prior[n_prior][2], their factors in order) followed by this batch's in read order, the first
+ * max_reads of them counted.  status[n_reads] (TBA_RESCALE_FAIL for a slope of 0), factors[n_reads][2] =
+ * (shift_corr_factor, scale_corr_factor) = (-inter / slope, 1 / slope), NaN for a failed read; medians[2] =
+ * np.median of the counted factors (untouched when none counted); *n_used = how many counted. */
+int tba_center_prepare(tba_engine *e, const tba_params *p, const tba_opts *o, int64_t n_reads,
+    const void *raw, int raw_dtype, const int64_t *raw_off, const uint8_t *seq, const int64_t *seq_off,
+    const int64_t *starts, const int64_t *start_off, const int64_t *read_start_rel_to_raw,
+    const int64_t *num_events, int32_t *status, double *kernel_ms);
+int tba_center_fit(tba_engine *e, const int64_t *samp_ind, const double *prior, int64_t n_prior,
+    int64_t max_reads, int32_t *status, double *factors, double *medians, int64_t *n_used, double *kernel_ms);
 
 /* ---- region plot data (csrc/k_plot.h): the numbers behind the frames of tombo/_plot_commands.py:784-984 ----
  * Level piles of a batch of plot regions: get_r_boxplot_data, get_r_quant_data and get_r_event_data over
@@ -1030,8 +1061,9 @@ int tba_synth_dwell_thresholds(const tba_synth_params *p, uint32_t *thr, int64_t
  * and refuse a stale build of the library */
 #define TBA_ABI_VERSION 13
 /* additions that leave every struct, every entry and every selector of TBA_ABI_VERSION as it was (not part of
- * tba_abi_sizes: a binding asks for what it needs by name).  1: tba_one_sd_words, TBA_GET_DP_ONE_SD */
-#define TBA_ABI_MINOR 1
+ * tba_abi_sizes: a binding asks for what it needs by name).  1: tba_one_sd_words, TBA_GET_DP_ONE_SD;
+ * 2: tba_center_prepare, tba_center_fit */
+#define TBA_ABI_MINOR 2
 int tba_abi_sizes(int64_t *out, int64_t n);
 
 /* self-test: out[t] = index t of the subsample tba_opts.device_subsample draws for read

@@ -130,6 +130,7 @@ STAGE_SEGMENT, STAGE_EVENT_MEANS, STAGE_REF_LEVELS, STAGE_START, STAGE_ASSIGN, S
 PUT_VALID_CPTS, PUT_EVENT_MEANS, PUT_NORM, PUT_REF_MEANS, PUT_REF_SDS, PUT_DP_SEGS, \
     PUT_START_STATE = range(1, 8)
 MAX_BAND = 3072
+MAX_CENTER_READS = 1 << 62   # Engine.center_fit without a limit on the successes that count
 ABI_VERSION = 13  # TBA_ABI_VERSION of include/tombo_amd.h
 STAGE_NAMES = ["normalize", "cumsum", "scores", "peaks", "event_means", "ref_levels",
                "start_dp", "start_tb", "prep", "main_dp", "main_tb", "skip_resolve", "theil_sen",
@@ -281,6 +282,8 @@ def _prototypes():
         # ---- estimate_kmer_model / estimate_motif_alt_model ----
         'tba_region_key_levels': (n, [v, n, q, cQ, cB, cQ, cD, q, cQ, cQ, q, cQ, cQ, q, cQ, cQ, q, Q, Q, D, D]),
         'tba_segment_medians': (n, [v, cD, cQ, q, D]),
+        'tba_center_prepare': (n, [v, P, O, q, v, n, cQ, cB, cQ, cQ, cQ, cQ, cQ, I, D]),
+        'tba_center_fit': (n, [v, cQ, cD, q, q, I, D, D, Q, D]),
         # ---- region plot data ----
         'tba_region_level_piles': (n, [v, q, cQ, cB, cQ, cD, q, cQ, cQ, cQ, cQ, q, cD, q, cD, Q, D, q, D, D, D]),
         'tba_segment_percentiles': (n, [v, cD, cQ, q, q, cD, q, cD, D, D, D]),
@@ -485,6 +488,61 @@ def _check_segment_medians_args(values, off):
     if off.shape[0] > 1 and np.diff(off).max() >= 2 ** 31:
         raise ValueError('a segment holds fewer than 2**31 values')
     return np.ascontiguousarray(values), off
+
+
+def _check_center_prepare_args(raws, codes, event_starts, read_start_rel_to_raw, num_events, rna):
+    """the argument checks of Engine.center_prepare -> (flat samples, raw_off, flat codes, seq_off, flat starts,
+    start_off, read_start_rel_to_raw, num_events or None).  The samples: int16 when every read is, else float64"""
+    n = len(raws)
+    if n == 0:
+        raise ValueError('no reads')
+    if n > 65535:
+        raise ValueError('more than TBA_MAX_BATCH_READS reads in one call')
+    if len(codes) != n or len(event_starts) != n:
+        raise ValueError('one sequence and one start column per read')
+    raws = [np.asarray(r) for r in raws]
+    if any(r.ndim != 1 or r.dtype.kind not in 'iuf' for r in raws):
+        raise ValueError('the raw signals must be one-dimensional numeric arrays')
+    dt = np.dtype(np.int16) if all(r.dtype == np.int16 for r in raws) else np.dtype(np.float64)
+    codes = [np.asarray(c) for c in codes]
+    if any(c.ndim != 1 or c.dtype != np.uint8 for c in codes):
+        raise ValueError('the sequences must be one-dimensional uint8 code arrays')
+    starts = [np.asarray(s) for s in event_starts]
+    if any(s.ndim != 1 or s.dtype.kind not in 'iu' for s in starts):
+        raise ValueError('the start columns must be one-dimensional integer arrays')
+    rsr = _i64(read_start_rel_to_raw)
+    if rsr.shape != (n,):
+        raise ValueError('one read_start_rel_to_raw per read')
+    if num_events is not None:
+        num_events = _i64(num_events)
+        if num_events.shape != (n,) or (num_events < 1).any():
+            raise ValueError('one positive num_events per read')
+    elif rna:
+        raise ValueError('RNA reads need num_events')
+    raw = np.concatenate(raws).astype(dt, copy=False) if n else np.zeros(0, dt)
+    return (np.ascontiguousarray(raw), _offsets(raws), np.ascontiguousarray(np.concatenate(codes)), _offsets(codes),
+            np.ascontiguousarray(np.concatenate(starts), dtype=np.int64), _offsets(starts), rsr, num_events)
+
+
+def _check_center_fit_args(n_reads, n_points, samp_ind, prior, max_reads):
+    """the argument checks of Engine.center_fit -> (samp_ind int64 [n, 1000] or None, prior float64 [m, 2]).
+    n_points: the points of every read of the prepared batch (bases - kmer_width + 1)"""
+    if n_reads is None:
+        raise ValueError('center_prepare has not been called')
+    if int(max_reads) < 1:
+        raise ValueError('max_reads must be positive')
+    if samp_ind is not None:
+        samp_ind = _i64(samp_ind)
+        if samp_ind.shape != (n_reads, MAX_POINTS_FOR_THEIL_SEN):
+            raise ValueError('samp_ind must be int64 [n_reads, %d] (pack_samp_inds)' % MAX_POINTS_FOR_THEIL_SEN)
+        # (a row of -1 marks a read without a draw, and the kernel checks every index it takes against the read's
+        # points: a bad row fails that read alone)
+    elif (np.asarray(n_points) > MAX_POINTS_FOR_THEIL_SEN).any():
+        raise ValueError('a read of more than %d points needs samp_ind' % MAX_POINTS_FOR_THEIL_SEN)
+    prior = np.zeros((0, 2), np.float64) if prior is None else np.ascontiguousarray(prior, dtype=np.float64)
+    if prior.ndim != 2 or prior.shape[1] != 2:
+        raise ValueError('prior must be float64 [m, 2]: the factors of the earlier successes')
+    return samp_ind, prior
 
 
 NORMTYPE_NONE, NORMTYPE_PA_RAW, NORMTYPE_MEDIAN, NORMTYPE_MEDIAN_CONST_SCALE, NORMTYPE_ROBUST_MEDIAN = range(5)
@@ -1139,20 +1197,13 @@ class Engine(object):
                            sv_flags=sv_flags, samp_ind=samp_ind, stall_ints=st, stall_off=sto,
                            wait=True)
 
-    def upload_packed(self, params, opts, raw, raw_off, seq, seq_off, sv_in=None, sv_flags=None,
-                      samp_ind=None, stall_ints=None, stall_off=None, wait=False):
-        """One batch as flat CSR arrays (tba_batch_upload_async): raw (int16 / float32 / float64)
-        and seq (uint8 codes) concatenated, offsets int64[n+1].  Enqueue only unless `wait`; the
-        arrays are kept referenced until the next upload, but must not be modified before
-        `sync()`.  Arrays in PinnedArray memory are transferred by DMA."""
+    def _batch_layout(self, params, opts, raw_off, seq_off):
+        """the CSR layouts of the batch about to be uploaded (what `get` and the downloads index by) -> the two
+        offset arrays as contiguous int64; takes the event counts set_num_events forced on this upload"""
         raw_off = np.ascontiguousarray(raw_off, dtype=np.int64)
         seq_off = np.ascontiguousarray(seq_off, dtype=np.int64)
         n = raw_off.shape[0] - 1
         self.n = n
-        if not isinstance(raw, DeviceArray):       # (else a Synth batch: copied device to device)
-            if raw.dtype not in RAW_DTYPES or not raw.flags.c_contiguous:
-                raw = np.ascontiguousarray(raw, dtype=np.float64)
-            seq = np.ascontiguousarray(seq, dtype=np.uint8)
         K = self.kmer_width
         self.raw_off, self.seq_off = raw_off, seq_off
         self.B = np.maximum(np.diff(seq_off) - K + 1, 0)
@@ -1168,16 +1219,30 @@ class Engine(object):
         self._ne_override = None
         self.num_events = ne
         self.ev_off = np.concatenate([[0], np.cumsum(ne)]).astype(np.int64)
+        self.n_raw_total = int(raw_off[-1])
+        self.skip_norm_out = bool(opts.skip_norm_out)
+        return raw_off, seq_off
+
+    def upload_packed(self, params, opts, raw, raw_off, seq, seq_off, sv_in=None, sv_flags=None,
+                      samp_ind=None, stall_ints=None, stall_off=None, wait=False):
+        """One batch as flat CSR arrays (tba_batch_upload_async): raw (int16 / float32 / float64)
+        and seq (uint8 codes) concatenated, offsets int64[n+1].  Enqueue only unless `wait`; the
+        arrays are kept referenced until the next upload, but must not be modified before
+        `sync()`.  Arrays in PinnedArray memory are transferred by DMA."""
+        if not isinstance(raw, DeviceArray):       # (else a Synth batch: copied device to device)
+            if raw.dtype not in RAW_DTYPES or not raw.flags.c_contiguous:
+                raw = np.ascontiguousarray(raw, dtype=np.float64)
+            seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        raw_off, seq_off = self._batch_layout(params, opts, raw_off, seq_off)
+        n = self.n
         svi = None if sv_in is None else np.ascontiguousarray(sv_in, dtype=np.float64)
         svf = None if sv_flags is None else np.ascontiguousarray(sv_flags, dtype=np.int32)
         si = None if samp_ind is None else np.ascontiguousarray(samp_ind, dtype=np.int64)
         st = None if stall_ints is None else np.ascontiguousarray(stall_ints, dtype=np.int64)
         sto = None if stall_off is None else np.ascontiguousarray(stall_off, dtype=np.int64)
         self._keep = (raw, seq, raw_off, seq_off, svi, svf, si, st, sto)
-        self.skip_norm_out = bool(opts.skip_norm_out)
         self._call('tba_batch_upload_async', params, opts, n, raw.ctypes, RAW_DTYPES[raw.dtype], raw_off, seq, seq_off,
                    svi, svf, si, st, sto)
-        self.n_raw_total = int(raw_off[-1])
         if wait:
             self.sync()
 
@@ -1593,6 +1658,46 @@ class Engine(object):
         out = np.empty(off.shape[0] - 1, dtype=np.float64)
         self._call('tba_segment_medians', v, off, off.shape[0] - 1, out)
         return out
+
+    # ---- centring a k-mer model on a batch of reads (csrc/k_center.h) ----
+    def center_prepare(self, params, opts, raws, codes, event_starts, read_start_rel_to_raw, num_events=None):
+        """tba_center_prepare, the first half of center_model_to_median_norm for a batch of reads: every read's
+        whole raw signal (int16 or float64: same bits) normalised and kept on the device -- by its medians (DNA
+        parameters), or as get_event_scale_values does under RNA parameters (params.use_t_test_seg; opts with
+        reverse_raw, stall_params and outlier_thresh; num_events: compute_num_events per read) --, the model's
+        levels of `codes` (the reads' `base` columns as uint8 codes), and the reads' own boundaries from their
+        `start` columns and read_start_rel_to_raw.  -> status int32 [n]: 0 for a read the fit will take.  The caller
+        draws the subsamples of those reads, in read order, and calls center_fit; last_center_kernel_ms: device
+        time of the two calls"""
+        rna = bool(params.use_t_test_seg)
+        raw, raw_off, seq, seq_off, starts, start_off, rsr, ne = _check_center_prepare_args(
+            raws, codes, event_starts, read_start_rel_to_raw, num_events, rna)
+        n = len(raws)
+        # (the entry forces these event counts itself; here they give the layout `get` indexes by)
+        self._ne_override = ne if rna else np.full(n, 2, dtype=np.int64)
+        raw_off, seq_off = self._batch_layout(params, opts, raw_off, seq_off)
+        status, ms = np.zeros(n, np.int32), np.zeros(1, np.float64)
+        self._center_n = None
+        self._call('tba_center_prepare', params, opts, n, raw.ctypes, RAW_DTYPES[raw.dtype], raw_off, seq, seq_off,
+                   starts, start_off, rsr, ne if rna else None, status, ms)
+        self._center_n, self.last_center_kernel_ms = n, [float(ms[0]), 0.0]
+        return status
+
+    def center_fit(self, samp_ind=None, prior=None, max_reads=MAX_CENTER_READS):
+        """tba_center_fit on the batch center_prepare left: samp_ind int64 [n, 1000] (pack_samp_inds; None when no
+        read has more than 1000 points), prior float64 [m, 2]: the factors of the successes of earlier calls, in
+        order.  -> (status int32 [n], factors float64 [n, 2]: shift_corr_factor and scale_corr_factor, NaN for a
+        failed read; medians (shift, scale) of the first max_reads successes -- prior first, then this batch in
+        read order -- in np.median's arithmetic, None without a success; how many successes that were)"""
+        n = getattr(self, '_center_n', None)
+        samp_ind, prior = _check_center_fit_args(n, None if n is None else self.B, samp_ind, prior, max_reads)
+        status, factors = np.zeros(n, np.int32), np.zeros((n, 2), np.float64)
+        med, used, ms = np.zeros(2, np.float64), np.zeros(1, np.int64), np.zeros(1, np.float64)
+        self._center_n = None
+        self._call('tba_center_fit', samp_ind, prior if prior.shape[0] else None, prior.shape[0], int(max_reads), status,
+                   factors, med, used, ms)
+        self.last_center_kernel_ms[1] = float(ms[0])
+        return status, factors, (float(med[0]), float(med[1])) if used[0] else None, int(used[0])
 
     # ---- the documented per-read functions of tombo_stats (csrc/k_norm_api.h) ----
     def normalize_raw_batch(self, raws, starts, lens, norm_type, sv_in=None, sv_flags=None, channel=None,

@@ -28,6 +28,7 @@
 #include "k_plot.h"
 #include "k_filter.h"
 #include "k_norm_api.h"
+#include "k_center.h"
 
 #include <algorithm>
 #include <array>
@@ -112,7 +113,8 @@ struct BatchSizes {
     X(d_skipq);                       /* window queues of k_skip_dp_wave */                                           \
     X(d_order); X(d_long);            /* read indices by decreasing length (k_dp_multi's grouping); the long reads (k_long.h) */ \
     X(d_stall_csum); X(d_stall_bits); /* the stall detector's own scratch (it runs beside event detection) */ \
-    X(d_trk_sum); X(d_trk_cov); X(d_trk_rcov); /* the resident genome tracks (tba_tracks_begin .. tba_tracks_finish) */
+    X(d_trk_sum); X(d_trk_cov); X(d_trk_rcov); /* the resident genome tracks (tba_tracks_begin .. tba_tracks_finish) */ \
+    X(d_cstart); X(d_cout); X(d_csel); /* centring (tba_center_prepare / tba_center_fit): the `start` columns, the results, the pick's lists */
 
 struct tba_engine {
     int device = 0;
@@ -128,6 +130,7 @@ struct tba_engine {
     float stage_ms[32] = {};
     bool have_model = false, have_batch = false, ran = false;
     bool finished = false; // the last stage (rescale + score) has run on the uploaded batch
+    bool center_ready = false; // tba_center_prepare has left the uploaded batch for tba_center_fit
     DevParams hp;
     i64 n_reads = 0;
     BatchSizes z;                 // of the uploaded batch
@@ -534,7 +537,7 @@ extern "C" int tba_batch_upload_async(tba_engine *e, const tba_params *p, const 
     HIP_TRY(hipSetDevice(e->device));
     // the previous batch of this engine must be done with the buffers (and with h_rs)
     HIP_TRY(hipStreamSynchronize(e->stream));
-    e->have_batch = e->ran = e->finished = false;
+    e->have_batch = e->ran = e->finished = e->center_ready = false;
     e->hp.p = *p;
     e->hp.o = *o;
     e->hp.fill_masked = (MASK_FILL_Z_SCORE - p->z_shift) + p->z_shift;
@@ -2844,6 +2847,107 @@ extern "C" int tba_segment_medians(tba_engine *e, const double *values, const in
     k_kest_median<<<grid_for(n_seg), 256, 0, e->stream>>>(n_seg, has_nan, d_off, d_v, d_out);
     if (sc.sync()) return sc.rc;
     return sc.get(out_medians, d_out, n_seg);
+}
+
+// ---- centring a k-mer model on a batch of reads (k_center.h): center_model_to_median_norm, tombo_stats.py:1599-1705 ----
+// The centring step list over the uploaded batch, in two halves (the caller draws the Theil-Sen subsamples between
+// them); the normalised signal stays in d_norm from the first to the second.
+//   prepare  the whole raw signal normalised -- DNA: launch_normalize alone (no cumulative sum, scores or peaks);
+//            RNA (get_event_scale_values, :1603-1622): run_prelude's stall detection over the reversed samples, then
+//            step_scores and step_peaks, i.e. t-test scores, peaks, k_remove_stalls, event means, k_rna_event_scale
+//            and the normalisation with those scale values --, k_ref_levels over the read's own bases,
+//            k_center_place.  (The levels come before the placement: a read with an invalid base AND misplaced
+//            events fails as an invalid sequence, the check the per-read form of the host layer makes first.)
+//   fit      k_theil_sen (base means over norm + read_start + segs, as in the resquiggle pass), k_center_pick
+// d_cout: factors[n][2], medians[2] (float64), n_used (int64), status[n] (int32).
+struct CenterOut {
+    double *factors, *medians; i64 *n_used; i32 *status;
+    static size_t bytes(size_t N) { return (2 * N + 3) * 8 + N * 4; }
+    CenterOut(void *p, size_t N) : factors((double *)p), medians(factors + 2 * N), n_used((i64 *)(medians + 2)), status((i32 *)(n_used + 1)) {}
+};
+
+extern "C" int tba_center_prepare(tba_engine *e, const tba_params *p, const tba_opts *o, int64_t n_reads,
+    const void *raw, int raw_dtype, const int64_t *raw_off, const uint8_t *seq, const int64_t *seq_off,
+    const int64_t *starts, const int64_t *start_off, const int64_t *read_start_rel_to_raw,
+    const int64_t *num_events, int32_t *status, double *kernel_ms)
+{
+    if (!e || !p || !o || n_reads <= 0 || !starts || !start_off || !read_start_rel_to_raw || !status)
+        return set_err(TBA_E_ARG, "bad centring arguments");
+    const bool rna = p->use_t_test_seg != 0;
+    if (rna && !num_events) return set_err(TBA_E_ARG, "RNA centring needs num_events");
+    if (o->has_const_scale || o->device_subsample || o->skip_seq_scaling)
+        return set_err(TBA_E_ARG, "const_scale, device_subsample and skip_seq_scaling do not apply to centring");
+    if (!e->have_model) return set_err(TBA_E_STATE, "tba_set_model has not been called");
+    if (e->hp.central_pos < 0 || e->hp.kmer_width - e->hp.central_pos - 1 < 1)
+        return set_err(TBA_E_ARG, "centring needs a model with at least one downstream base");
+    if (start_off[0] != 0) return set_err(TBA_E_ARG, "offset arrays must start at 0");
+    for (i64 i = 0; i < n_reads; i++)
+        if (start_off[i + 1] < start_off[i]) return set_err(TBA_E_ARG, "offset arrays must be non-decreasing");
+    // DNA: the change points are not looked for (two is the least plan_batch takes); RNA: compute_num_events per read
+    std::vector<i64> ne((size_t)n_reads, 2);
+    if (rna) ne.assign(num_events, num_events + n_reads);
+    if (int rc = tba_set_num_events(e, ne.data(), n_reads)) return rc;
+    if (int rc = tba_batch_upload_async(e, p, o, n_reads, raw, raw_dtype, raw_off, seq, seq_off, nullptr, nullptr,
+                                        nullptr, nullptr, nullptr)) return rc;
+    const size_t N = (size_t)n_reads, n_st = (size_t)start_off[n_reads];
+    if (e->d_cstart.ensure((n_st + 2 * N + 1) * 8) || e->d_cout.ensure(CenterOut::bytes(N))) return TBA_E_NOMEM;
+    i64 *d_starts = e->d_cstart.as<i64>(), *d_soff = d_starts + n_st, *d_rsr = d_soff + N + 1;
+    const CenterOut out(e->d_cout.p, N);
+    const hipStream_t s = e->stream;
+    if (n_st > 0) HIP_TRY(hipMemcpyAsync(d_starts, starts, n_st * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_soff, start_off, (N + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_rsr, read_start_rel_to_raw, N * 8, hipMemcpyHostToDevice, s));
+    Run c{e};
+    HIP_TRY(hipEventRecord(e->ev[0], s));
+    if (int rc = run_prelude(c, TBA_STAGE_SEGMENT, TBA_STAGE_SEGMENT)) return rc;
+    if (c.rna) {
+        if (int rc = step_scores(c)) return rc;
+        if (int rc = step_peaks(c)) return rc;
+    } else launch_normalize(c, 0, 1);
+    k_ref_levels<<<dim3(c.gB, c.nb), 256, 0, s>>>(c.rs, c.dp, c.seq, c.kmeans, c.ksds, c.refm, c.refs);
+    e->refs_put = false;
+    k_center_place<<<c.nb, 256, 0, s>>>(c.rs, c.dp, d_starts, d_soff, d_rsr, c.segs, out.status);
+    HIP_TRY(hipEventRecord(e->ev[N_STEP], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(status, out.status, N * 4, hipMemcpyDeviceToHost));
+    if (kernel_ms) { float t = 0; (void)hipEventElapsedTime(&t, e->ev[0], e->ev[N_STEP]); *kernel_ms = t; }
+    e->ran = e->center_ready = true;
+    return 0;
+}
+
+extern "C" int tba_center_fit(tba_engine *e, const int64_t *samp_ind, const double *prior, int64_t n_prior,
+    int64_t max_reads, int32_t *status, double *factors, double *medians, int64_t *n_used, double *kernel_ms)
+{
+    if (!e || !status || !factors || !medians || !n_used || n_prior < 0 || (n_prior > 0 && !prior) || max_reads < 1)
+        return set_err(TBA_E_ARG, "bad centring arguments");
+    if (!e->have_batch || !e->center_ready) return set_err(TBA_E_STATE, "tba_center_prepare has not left a batch to fit");
+    e->center_ready = false; // (k_theil_sen moves the reads' scale values on: one fit per prepared batch)
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t N = (size_t)e->n_reads, NP = (size_t)n_prior;
+    if (e->d_csel.ensure((2 * (NP + N) + 2 * NP + 2) * 8)) return TBA_E_NOMEM;
+    double *d_sel = e->d_csel.as<double>(), *d_prior = d_sel + 2 * (NP + N);
+    const CenterOut out(e->d_cout.p, N);
+    const hipStream_t s = e->stream;
+    e->have_samp = samp_ind != nullptr;
+    if (samp_ind) HIP_TRY(hipMemcpyAsync(e->d_samp.p, samp_ind, N * MAX_TS_POINTS * 8, hipMemcpyHostToDevice, s));
+    if (NP > 0) HIP_TRY(hipMemcpyAsync(d_prior, prior, NP * 16, hipMemcpyHostToDevice, s));
+    Run c{e};
+    HIP_TRY(hipEventRecord(e->ev[0], s));
+    if (int rc = step_theil_sen(c)) return rc;
+    k_center_pick<<<1, SEL_NT, 0, s>>>(c.rs, c.n, d_prior, n_prior, max_reads, out.factors, out.status, d_sel, out.medians, out.n_used);
+    HIP_TRY(hipEventRecord(e->ev[N_STEP], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<char> h(CenterOut::bytes(N));
+    HIP_TRY(hipMemcpy(h.data(), e->d_cout.p, h.size(), hipMemcpyDeviceToHost));
+    const CenterOut ho(h.data(), N);
+    memcpy(factors, ho.factors, N * 16);
+    memcpy(status, ho.status, N * 4);
+    *n_used = *ho.n_used;
+    if (*ho.n_used > 0) { medians[0] = ho.medians[0]; medians[1] = ho.medians[1]; }
+    if (kernel_ms) { float t = 0; (void)hipEventElapsedTime(&t, e->ev[0], e->ev[N_STEP]); *kernel_ms = t; }
+    return 0;
 }
 
 // ---- region plot data (k_plot.h): the numbers of the box, quantile, density and raw-signal frames ----

@@ -24,7 +24,7 @@ from . import tombo_helper as th, _native
 from ._c_helper import llh_ratio_windows
 from ._default_parameters import (
     ALGN_PARAMS_TABLE, SEG_PARAMS_TABLE, RNA_SAMP_TYPE, DNA_SAMP_TYPE, STANDARD_MODELS,
-    HALF_NORM_EXPECTED_VAL, MIN_EVENT_TO_SEQ_RATIO, STALL_PARAMS, SMALLEST_PVAL, FM_OFFSET_DEFAULT,
+    HALF_NORM_EXPECTED_VAL, MIN_EVENT_TO_SEQ_RATIO, STALL_PARAMS, OUTLIER_THRESH, COLLAPSE_RNA_STALLS, SMALLEST_PVAL, FM_OFFSET_DEFAULT,
     SAMP_COMP_TXT, DE_NOVO_TXT, ALT_MODEL_TXT, CONST_SD_MODEL, OCLLHR_SCALE, OCLLHR_HEIGHT,
     OCLLHR_POWER, MEAN_PRIOR_CONST, SD_PRIOR_CONST, ALT_EST_BATCH, MAX_KMER_OBS, MIN_KMER_OBS_TO_EST,
     KERNEL_DENSITY_RANGE, NUM_DENS_POINTS, ROC_PLOT_POINTS)
@@ -2663,8 +2663,11 @@ def tabulate_mod_kmer_levels(table, min_kmer_obs, motif, engine=None):
 
 # what center_model_to_median_norm takes per read, in memory: the raw signal, the `start` column of the read's
 # Events table, its bases (read-centric, one per event) and read_start_rel_to_raw
-CenterRead = namedtuple('CenterRead', 'raw_signal event_starts seq read_start_rel_to_raw rna')
-CenterRead.__new__.__defaults__ = (False,)
+# (center_model_to_median_norm_batch also takes RNA reads: raw_signal in acquisition order, as the FAST5 file has
+# it, and map_len: the read's mapped length end - start, which the reference hands to compute_num_events; None:
+# the number of bases)
+CenterRead = namedtuple('CenterRead', 'raw_signal event_starts seq read_start_rel_to_raw rna map_len')
+CenterRead.__new__.__defaults__ = (False, None)
 _NO_CENTER_READS_MSG = 'No reads succcessfully processed for sequence-based normalization parameter re-fitting.'
 _FEW_CENTER_READS_MSG = ('Fewer reads succcessfully processed for sequence-based normalization parameter '
                          're-fitting than requested.')
@@ -2755,17 +2758,126 @@ def center_model_to_median_norm(reads, init_ref, max_reads=NUM_READS_TO_ADJUST_M
     init_ref._center_model(np.median(shifts), np.median(scales))
     return init_ref
 
+_CENTER_MEM_FRACTION = 0.5      # of the device's free memory, for one centring call
+
+
+def _default_center_chunk(engine, reads, params, opts, kmer_width):
+    """reads per centring call that fit into half of the engine's free memory, counting every read as the longest
+    one (the footprint of a resquiggle batch of such reads: the centring entries use its buffers); a stand-in
+    engine without `device_mem`: 4096"""
+    from . import planner
+    if not hasattr(engine, 'device_mem'):
+        return 4096
+    n_raw = max(max(len(rd.raw_signal) for rd in reads), 1)
+    n_seq = max(max(len(rd.seq) for rd in reads), 1)
+    some, more = (planner.exact_bytes([n_raw] * k, [n_seq] * k, params, opts, kmer_width) for k in (8, 16))
+    per_read = max((more - some) / 8.0, 1.0)
+    room = engine.device_mem()[0] * _CENTER_MEM_FRACTION - some
+    return int(min(max(room // per_read + 8, 1), planner.MAX_READS))
+
+
+def center_model_to_median_norm_batch(reads, init_ref, max_reads=NUM_READS_TO_ADJUST_MODEL, engine=None,
+                                      chunk_reads=None):
+    """center_model_to_median_norm for all reads at once, RNA too: the reads go to the device in chunks of
+    chunk_reads (default: what fits into half of the engine's free memory, and no more than the successes still
+    wanted, but at least 256), each chunk two calls -- Engine.center_prepare (normalisation of the whole raw
+    signal, which stays on the device; the model's levels; the reads' own boundaries) and Engine.center_fit
+    (Theil-Sen fit, the pick of the first max_reads successes, the medians of their factors).  Between the two the
+    subsamples of the reads of more than MAX_POINTS_FOR_THEIL_SEN points are drawn with np.random.choice, in read
+    order, for the reads that came through the first call: the reference's order of draws.  The work ends with the
+    chunk that holds the max_reads-th success.
+
+    reads: CenterRead-like objects, all DNA or all RNA (rna; a mixed list is a ValueError: th.is_sample_rna decides
+    the type for a whole sample).  RNA (get_event_scale_values, tombo_stats.py:1603-1622): raw_signal in acquisition
+    order; it is reversed, stalls are detected and their change points removed, and the scale values come from
+    the events of compute_num_events(len(raw_signal), map_len, ...) t-test change points.  The raw signal may be
+    int16 DAC values or float64 with the same bits in the result (the reference itself fails on int16 RNA input:
+    identify_stalls assigns NaN into an array of the signal's dtype, and every read is skipped).
+
+    The factors handed to init_ref._center_model equal, bit for bit, those of the per-read loop under the same
+    seed.  The state of the global random generator AFTER the call may differ from the per-read form's: a chunk
+    draws for all its reads, those behind the read that ended the per-read loop included.  Raises and warns with
+    the per-read form's messages."""
+    reads = list(reads)
+    rna = set(bool(getattr(rd, 'rna', False)) for rd in reads)
+    if len(rna) > 1:
+        raise ValueError('center_model_to_median_norm_batch: RNA and DNA reads in one list')
+    rna = bool(rna.pop()) if rna else False
+    max_reads = int(max_reads)
+    if max_reads < 1:
+        raise ValueError('max_reads must be positive')
+    if chunk_reads is not None and int(chunk_reads) < 1:
+        raise ValueError('chunk_reads must be positive')
+    eng = _engine(engine)
+    K, up = init_ref.kmer_width, init_ref.central_pos
+    if rna:
+        rsqgl_params = load_resquiggle_parameters(th.seqSampleType(RNA_SAMP_TYPE, True))
+        opts = _native.make_opts(outlier_thresh=OUTLIER_THRESH, reverse_raw=True,
+                                 stall_params=th.stallParams(**STALL_PARAMS) if COLLAPSE_RNA_STALLS else None)
+    else:
+        rsqgl_params = load_resquiggle_parameters(th.seqSampleType(DNA_SAMP_TYPE, False))
+        opts = _native.make_opts()
+    params = _native.make_params(rsqgl_params)
+    eng.ensure_model(init_ref)
+    np.random.shuffle(reads)
+    factors = np.zeros((0, 2), dtype=np.float64)    # of the successes so far, in read order
+    medians, at = None, 0
+    if K - up - 1 < 1:      # ('Must have at least one upstream and downstream base for a Tombo model.': every read fails)
+        reads = []
+    mem_chunk = None
+    while at < len(reads) and factors.shape[0] < max_reads:
+        if chunk_reads is not None:
+            n_chunk = int(chunk_reads)
+        else:
+            if mem_chunk is None:
+                mem_chunk = _default_center_chunk(eng, reads, params, opts, K)
+            n_chunk = min(mem_chunk, max(max_reads - factors.shape[0], 256))
+        chunk = reads[at:at + n_chunk]
+        at += len(chunk)
+        codes = [encode_seq(rd.seq) for rd in chunk]
+        num_events = None
+        if rna:
+            num_events = [max(compute_num_events(len(rd.raw_signal), len(rd.seq) if getattr(rd, 'map_len', None) is None
+                                                 else int(rd.map_len), rsqgl_params.mean_obs_per_event), 1)
+                          for rd in chunk]
+        status = eng.center_prepare(params, opts, [rd.raw_signal for rd in chunk], codes,
+                                    [rd.event_starts for rd in chunk],
+                                    [int(rd.read_start_rel_to_raw) for rd in chunk], num_events)
+        # the draws, in read order, of the reads that got as far as the fit (tombo_stats.py:411-414)
+        n_points = [c.shape[0] - K + 1 for c in codes]
+        samp = None
+        if max(n_points) > _native.MAX_POINTS_FOR_THEIL_SEN:
+            samp = _native.pack_samp_inds([
+                np.random.choice(n, _native.MAX_POINTS_FOR_THEIL_SEN, replace=False)
+                if st == 0 and n > _native.MAX_POINTS_FOR_THEIL_SEN else None
+                for n, st in zip(n_points, status.tolist())])
+        status, chunk_factors, medians, n_used = eng.center_fit(samp, factors, max_reads)
+        factors = np.concatenate([factors, chunk_factors[status == 0]])[:max_reads]
+        assert n_used == factors.shape[0]
+    if factors.shape[0] < max_reads:
+        if factors.shape[0] == 0:
+            raise th.TomboError(_NO_CENTER_READS_MSG)
+        warnings.warn(_FEW_CENTER_READS_MSG)
+    init_ref._center_model(np.float64(medians[0]), np.float64(medians[1]))
+    return init_ref
+
 
 def estimate_kmer_model(reads_index, cov_thresh, upstrm_bases, dnstrm_bases, min_kmer_obs, kmer_specific_sd,
-                        cs_cov_thresh, est_mean, region_size, center_reads=None, engine=None):
+                        cs_cov_thresh, est_mean, region_size, center_reads=None, engine=None, center_batch=False):
     """The canonical k-mer model of the reads; WITHOUT center_reads it is left uncentred, which the reference never
     returns (a warning says so).  tombo_stats.py:1716-1740 after the file access.  center_reads: the reads
-    center_model_to_median_norm takes; the reference centres on reads of the same index."""
+    center_model_to_median_norm takes; the reference centres on reads of the same index.  center_batch, or an RNA
+    read among center_reads: centred by center_model_to_median_norm_batch (the same factors, all reads in a few
+    device calls; the only form that takes RNA reads)."""
     table = extract_kmer_levels(reads_index, region_size, cov_thresh, upstrm_bases, dnstrm_bases, cs_cov_thresh,
                                 est_mean, engine=engine)
     ref = TomboModel(kmer_ref=tabulate_kmer_levels(table, min_kmer_obs, engine=engine), central_pos=upstrm_bases)
     if center_reads is not None:
-        ref = center_model_to_median_norm(center_reads, ref, engine=engine)
+        center_reads = list(center_reads)
+        if center_batch or any(getattr(rd, 'rna', False) for rd in center_reads):
+            ref = center_model_to_median_norm_batch(center_reads, ref, engine=engine)
+        else:
+            ref = center_model_to_median_norm(center_reads, ref, engine=engine)
     else:
         warnings.warn('estimate_kmer_model: no center_reads given, the model is not centred to median normalisation')
     if not kmer_specific_sd:
