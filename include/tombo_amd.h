@@ -607,6 +607,52 @@ int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, const int64_t 
     int64_t *out_valid_cov, double *out_damp_frac, int64_t *out_counts, int64_t *out_n_stats,
     double *out_per_read);
 
+/* The z tests (form 0: de_novo, form 1: sample_compare) of tba_site_fractions straight from a READS
+ * TABLE: the per-read preparation of compute_reg_stats (region clip, strand flip, expected levels)
+ * runs on the device, every read is uploaded once however many regions it spans.
+ *   regions   track r is [reg_start[r] - fm_offset, reg_end[r] + fm_offset); outputs are laid out by
+ *             P_r = sum of the earlier tracks' lengths, as in tba_site_fractions.
+ *   reads     read q covers genomic [read_start[q], read_start[q] + n_q), n_q = read_off[q + 1] -
+ *             read_off[q], on strand read_strand[q] (0: '+', 1: '-'); `means` and, form 0, `seq`
+ *             (base codes, 0..3 = ACGT, anything else invalid) are read-centric, CSR by read_off.
+ *   pairs     region r tests reads pair_read[reg_pair_off[r] .. reg_pair_off[r + 1]), in that order.
+ *   form 0    expected levels from the engine's model (tba_set_model: K, cp, dn = K - cp - 1);
+ *             floor_out of tba_read_pvals is 1.  pos_means / pos_sds are ignored.
+ *   form 1    pos_means / pos_sds[P_r + g - (reg_start[r] - fm_offset)]: the control levels per
+ *             extended position (the layout of tba_reads_ref_levels' outputs, NaN: no level);
+ *             floor_out is 0.  seq is ignored.
+ * A pair, read [s, e) in region [a, b), fm = fm_offset:
+ *   form 0    (lag_b, lag_e) = (cp, dn) on '+', (dn, cp) on '-'; cs = max(s, a - lag_b - fm), ce =
+ *             min(e, b + lag_e + fm); statistics at genomic g in [cs + lag_b, ce - lag_e).  The pair
+ *             fails when ce - cs < K, when a base code of the clipped part (read indices [cs - s,
+ *             ce - s) on '+', [e - ce, e - cs) on '-') is invalid, or when fm > 0 and it has fewer
+ *             than 2 fm + 1 statistics.  The level at g is means[i], i = g - s on '+', e - 1 - g on
+ *             '-'; the expected level is the model's row of the k-mer at read indices [i - cp, i - cp + K).
+ *   form 1    cs = max(s, a - fm), ce = min(e, b + fm); statistics at g in [cs, ce), same i.  The pair
+ *             fails when no g has level, pos_means and pos_sds all non-NaN, or when fm > 0 and
+ *             ce - cs < 2 fm + 1.
+ * A failed pair contributes nothing (the TomboError of the reference's per-read function).  The
+ * statistics of the pairs, in pair order, then go through the kernels of tba_site_fractions form 0
+ * unchanged.  Outputs: those of tba_site_fractions, and per pair out_pair_ok (1: not failed),
+ * out_pair_pos (genomic position of its first statistic), out_pair_off[n_pairs + 1] (its first
+ * statistic's index; a failed pair has none).  out_per_read (may be NULL; per_read_cap values): the
+ * statistics in that layout.  out_kernel_ms (may be NULL; 2 values): device time (hipEvents) of the
+ * plan, scan and gather kernels, and of the statistic and collation kernels behind them.
+ * TBA_E_ARG, before anything is launched: NULL pointers, offsets that do not start at 0 or decrease,
+ * a region with end <= start, pair_read outside [0, n_reads), a strand that is not 0 or 1, a read
+ * that does not overlap [reg_start, reg_end) of its region, fm_offset outside [0, 64], 2^31
+ * positions or more, form 0 without a model.  TBA_E_ARG after the plan: per_read_cap below the
+ * number of statistics (no output is written). */
+int tba_site_fractions_reads(tba_engine *e, int form, int64_t n_regions, const int64_t *reg_start,
+    const int64_t *reg_end, int64_t n_reads, const int64_t *read_start, const int8_t *read_strand,
+    const int64_t *read_off, const double *means, const uint8_t *seq, const int64_t *reg_pair_off,
+    const int64_t *pair_read, const double *pos_means, const double *pos_sds, int64_t fm_offset,
+    double smallest_pval, double single_read_thresh, const double *lower_thresh,
+    const double *damp_counts, double *out_frac, int64_t *out_pos, int64_t *out_cov,
+    int64_t *out_valid_cov, double *out_damp_frac, int64_t *out_counts, int64_t *out_n_stats,
+    int32_t *out_pair_ok, int64_t *out_pair_pos, int64_t *out_pair_off, double *out_per_read,
+    int64_t per_read_cap, double *out_kernel_ms);
+
 /* The same per-site outputs from STORED per-read statistics (aggregate_per_read_stats,
  * tombo_stats.py:4699-4777): n_blocks blocks of a per-read statistics file, block t covering
  * genomic [blk_start[t], blk_end[t]) and owning records rec_off[t] .. rec_off[t + 1] of `records`,
@@ -1062,8 +1108,8 @@ int tba_synth_dwell_thresholds(const tba_synth_params *p, uint32_t *thr, int64_t
 #define TBA_ABI_VERSION 13
 /* additions that leave every struct, every entry and every selector of TBA_ABI_VERSION as it was (not part of
  * tba_abi_sizes: a binding asks for what it needs by name).  1: tba_one_sd_words, TBA_GET_DP_ONE_SD;
- * 2: tba_center_prepare, tba_center_fit */
-#define TBA_ABI_MINOR 2
+ * 2: tba_center_prepare, tba_center_fit; 3: tba_site_fractions_reads */
+#define TBA_ABI_MINOR 3
 int tba_abi_sizes(int64_t *out, int64_t n);
 
 /* self-test: out[t] = index t of the subsample tba_opts.device_subsample draws for read

@@ -256,6 +256,8 @@ def _prototypes():
         # ---- per-site modified fractions ----
         'tba_site_fractions': (n, [v, n, q, cQ, cQ, cD, cD, cD, cQ, q, cQ, cQ, q, n, d,
                                    n, cD, cD, cD, q, q, cQ, q, cD, cQ, cQ, d, cD, cD] + site_outs + [D]),
+        'tba_site_fractions_reads': (n, [v, n, q, cQ, cQ, q, cQ, cS, cQ, cD, cB, cQ, cQ, cD, cD, q, d, d, cD, cD] +
+                                     site_outs + [I, Q, Q, D, q, D]),
         'tba_site_aggregate': (n, [v, q, cQ, cQ, cQ, v, d, cD, n, cD] + site_outs + [D]),
         # ---- ROC / precision-recall ----
         'tba_roc_motif_labels': (n, [v, q, cB, cQ, cQ, cB, cQ, cQ, cD, q, cI, cB, n, n, D, B, Q, Q, D]),
@@ -803,6 +805,82 @@ def _check_compact_args(values):
 SiteFractions = namedtuple('SiteFractions', 'pos_off frac poss cov valid damp counts n_stats per_read')
 
 
+# the reads table and the (region, read) pairs of one tba_site_fractions_reads call; pos_off: the regions'
+# extended positions [reg_start - fm_offset, reg_end + fm_offset); seq (uint8 base codes) None for form 1,
+# pos_means / pos_sds (control levels per extended position) None for form 0
+SiteReads = namedtuple('SiteReads', 'reg_start reg_end read_start read_strand read_off means seq reg_pair_off '
+                                    'pair_read pos_means pos_sds fm_offset pos_off')
+
+
+def site_reads_stat_bound(form, t, kmer_width=1, central_pos=0):
+    """per pair of a SiteReads the number of statistics it yields when it does not fail (the geometry of
+    tba_site_fractions_reads, vectorised): an upper bound of what the call produces"""
+    rd = t.pair_read
+    reg = np.repeat(np.arange(t.reg_start.shape[0], dtype=np.int64), np.diff(t.reg_pair_off))
+    s = t.read_start[rd]
+    e = s + np.diff(t.read_off)[rd]
+    lag_b = lag_e = np.zeros(rd.shape[0], dtype=np.int64)
+    if form == 0:
+        dn, minus = kmer_width - central_pos - 1, t.read_strand[rd] != 0
+        lag_b, lag_e = np.where(minus, dn, central_pos), np.where(minus, central_pos, dn)
+    cs = np.maximum(s, t.reg_start[reg] - lag_b - t.fm_offset)
+    ce = np.minimum(e, t.reg_end[reg] + lag_e + t.fm_offset)
+    return np.maximum(ce - cs - lag_b - lag_e, 0).astype(np.int64)
+
+
+def _check_site_reads_args(form, reg_start, reg_end, read_start, read_strand, read_off, means, seq, reg_pair_off,
+                           pair_read, pos_means, pos_sds, fm_offset):
+    """the argument checks of Engine.site_fractions_reads (shared with the tests' stand-in engine), those
+    tba_site_fractions_reads makes: dtypes are checked, not converted -> SiteReads of contiguous arrays"""
+    if form not in (0, 1):
+        raise ValueError('form must be 0 (de_novo) or 1 (sample_compare)')
+    if int(fm_offset) != fm_offset or fm_offset < 0 or fm_offset > 64:
+        raise ValueError('fm_offset must be an integer in [0, 64]')
+    fm = int(fm_offset)
+    a = dict(reg_start=(reg_start, np.int64), reg_end=(reg_end, np.int64), read_start=(read_start, np.int64),
+             read_strand=(read_strand, np.int8), means=(means, np.float64), pair_read=(pair_read, np.int64))
+    if form == 0:
+        a.update(seq=(seq, np.uint8))
+    else:
+        a.update(pos_means=(pos_means, np.float64), pos_sds=(pos_sds, np.float64))
+    c = dict(seq=None, pos_means=None, pos_sds=None)
+    for name, (arr, dt) in a.items():
+        if arr is None:
+            raise ValueError('%s is needed for form %d' % (name, form))
+        arr = np.asarray(arr)
+        if arr.dtype != dt or arr.ndim != 1:
+            raise ValueError('%s must be a one-dimensional %s array' % (name, np.dtype(dt).name))
+        c[name] = np.ascontiguousarray(arr)
+    read_off, pair_off = _check_offsets(read_off, 'read_off'), _check_offsets(reg_pair_off, 'reg_pair_off')
+    n_reg, n_reads = c['reg_start'].shape[0], c['read_start'].shape[0]
+    if c['reg_end'].shape[0] != n_reg or pair_off.shape[0] != n_reg + 1:
+        raise ValueError('reg_start, reg_end must have one entry per region and reg_pair_off one more')
+    if c['read_strand'].shape[0] != n_reads or read_off.shape[0] != n_reads + 1:
+        raise ValueError('read_start, read_strand must have one entry per read and read_off one more')
+    if c['means'].shape[0] != int(read_off[-1]) or (form == 0 and c['seq'].shape[0] != int(read_off[-1])):
+        raise ValueError('means%s must have read_off[-1] values' % (' and seq' if form == 0 else ''))
+    if c['pair_read'].shape[0] != int(pair_off[-1]):
+        raise ValueError('pair_read must have reg_pair_off[-1] values')
+    if (c['reg_end'] <= c['reg_start']).any():
+        raise ValueError('a region must have end > start')
+    if ((c['read_strand'] != 0) & (c['read_strand'] != 1)).any():
+        raise ValueError('read_strand must be 0 or 1')
+    pos_off = np.concatenate([[0], np.cumsum(c['reg_end'] - c['reg_start'] + 2 * fm)]).astype(np.int64)
+    if int(pos_off[-1]) >= 2 ** 31:
+        raise ValueError('2^31 positions or more in one call')
+    if form == 1 and not (c['pos_means'].shape[0] == c['pos_sds'].shape[0] == int(pos_off[-1])):
+        raise ValueError('pos_means and pos_sds must have one value per extended position')
+    rd = c['pair_read']
+    if ((rd < 0) | (rd >= n_reads)).any():
+        raise ValueError('pair_read outside [0, n_reads)')
+    reg = np.repeat(np.arange(n_reg, dtype=np.int64), np.diff(pair_off))
+    s = c['read_start'][rd]
+    if ((s >= c['reg_end'][reg]) | (s + np.diff(read_off)[rd] <= c['reg_start'][reg])).any():
+        raise ValueError('a read does not overlap its region')
+    return SiteReads(c['reg_start'], c['reg_end'], c['read_start'], c['read_strand'], read_off, c['means'], c['seq'],
+                     pair_off, rd, c['pos_means'], c['pos_sds'], fm, pos_off)
+
+
 # a stored per-read record (PerReadStats block_stats): numpy's packed layout, 16 bytes, the float64 at offset 4
 PER_READ_DTYPE = np.dtype([('pos', 'u4'), ('stat', 'f8'), ('read_id', 'u4')])
 
@@ -1142,7 +1220,7 @@ class Engine(object):
         self._L = lib()
         self._h = C.c_void_p()
         self.device = int(device)
-        self.kmer_width = None
+        self.kmer_width = self.central_pos = None
         self._model_key = None
         self._keep = self._keep_out = None    # the arrays of the upload / the downloads in flight
         self._stage = None                    # page-locked staging, made on first use (host_stage)
@@ -1172,7 +1250,7 @@ class Engine(object):
         s = np.ascontiguousarray(level_sds, dtype=np.float64)
         assert m.shape[0] == 4 ** kmer_width == s.shape[0]
         self._call('tba_set_model', m, s, kmer_width, central_pos)
-        self.kmer_width = int(kmer_width)
+        self.kmer_width, self.central_pos = int(kmer_width), int(central_pos)
         self._model_key = None
 
     def ensure_model(self, std_ref):
@@ -1502,6 +1580,37 @@ class Engine(object):
         win_args = (int(kind), a, rv, av, n, int(width), st, st.shape[0], (f64 * 3)(*par), w_trk, w_pos)
         return self._site_fractions(1, trk_start, trk_end, (m, r) + self._NO_Z_FORM, win_args, st.shape[0],
                                     single_read_thresh, lower_thresh, damp_counts, return_per_read)
+
+    def site_fractions_reads(self, form, reg_start, reg_end, read_start, read_strand, read_off, means, seq,
+                             reg_pair_off, pair_read, pos_means, pos_sds, fm_offset, smallest_pval,
+                             single_read_thresh, lower_thresh=None, damp_counts=None, return_per_read=False):
+        """tba_site_fractions_reads: the z tests (form 0: de_novo under the engine's model, form 1: sample_compare
+        under pos_means / pos_sds) of region r on reads pair_read[reg_pair_off[r]:reg_pair_off[r + 1]] of a reads
+        table that holds every read once; clip, flip and expected levels are made on the device
+        -> (SiteFractions, pair_ok, pair_pos, pair_off): per pair whether it did not fail, the position of its
+        first statistic and its offset into per_read.  `last_site_reads_kernel_ms`: device time of the plan,
+        scan and gather kernels, and of the kernels behind them."""
+        t = _check_site_reads_args(form, reg_start, reg_end, read_start, read_strand, read_off, means, seq,
+                                   reg_pair_off, pair_read, pos_means, pos_sds, fm_offset)
+        if form == 0 and self.kmer_width is None:
+            raise ValueError('form 0 (de_novo) needs a model (set_model)')
+        n_pairs = t.pair_read.shape[0]
+        pos_off, outs = _site_outputs(t.reg_start - t.fm_offset, t.reg_end + t.fm_offset, damp_counts)
+        cap = int(site_reads_stat_bound(form, t, self.kmer_width or 1, self.central_pos or 0).sum()) if return_per_read else 0
+        per_read = np.empty(cap, dtype=np.float64) if return_per_read else None
+        pair_ok = np.zeros(n_pairs, dtype=np.int32)
+        pair_pos, pair_off = np.zeros(n_pairs, dtype=np.int64), np.zeros(n_pairs + 1, dtype=np.int64)
+        ms = np.zeros(2, dtype=np.float64)
+        self._call('tba_site_fractions_reads', form, t.reg_start.shape[0], t.reg_start, t.reg_end,
+                   t.read_start.shape[0], t.read_start, t.read_strand, t.read_off, t.means, t.seq, t.reg_pair_off,
+                   t.pair_read, t.pos_means, t.pos_sds, t.fm_offset, smallest_pval, float(single_read_thresh),
+                   None if lower_thresh is None else (f64 * 1)(float(lower_thresh)),
+                   None if damp_counts is None else (f64 * 2)(*damp_counts), *outs, pair_ok, pair_pos, pair_off,
+                   per_read, cap, ms)
+        self.last_site_reads_kernel_ms = (float(ms[0]), float(ms[1]))
+        if per_read is not None:
+            per_read = per_read[:int(pair_off[-1])]
+        return SiteFractions(pos_off, *outs, per_read), pair_ok, pair_pos, pair_off
 
     def site_aggregate(self, blk_start, blk_end, rec_off, records, single_read_thresh, lower_thresh=None,
                        abs_rule=False, damp_counts=None):

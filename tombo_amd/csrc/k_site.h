@@ -15,6 +15,10 @@
 //                           file: aggregate_per_read_stats), a track being one stored block
 //   k_site_finish           one wavefront per track: positions with cov > 0 compacted in ascending
 //                           order, fraction / coverage / dampened fraction written out
+//   k_site_pair_plan /      the z form's inputs made on the device from a reads table (every read uploaded
+//   k_site_gather           once) and (region, read) pairs: the region clip, the failure scans and the count
+//                           of each pair, then one thread per statistic fills means / ref_means / ref_sds in
+//                           the layout k_site_z and k_read_pvals take
 // The counters are integers, so the sums do not depend on the order the atomics land in.
 #pragma once
 #include "tba_common.h"
@@ -138,4 +142,111 @@ __global__ void k_site_finish(SiteArgs a, double unmod, double damp_sum, double 
         n_carry += __shfl(n_inc, 63);
     }
     if (lane == 0) { out_counts[t] = k_carry; out_n_stats[t] = n_carry; }
+}
+
+// ---- the z form's inputs from a reads table (tba_site_fractions_reads) -----------------------------
+// Every read is on the device once (read-centric levels and, form 0, base codes, CSR by read_off); a
+// pair is one (region, read): pair p tests read pair_read[p] in region pair_reg[p].  What a pair
+// contributes is the reference's per-read preparation (compute_de_novo_read_stats :3796-3855,
+// compute_sample_compare_read_stats :3700-3750) as index arithmetic.  Read [s, e), region [a, b),
+// fm = fm_offset, K / cp of the model, dn = K - cp - 1:
+//   form 0 (de_novo)         (lag_b, lag_e) = (cp, dn) on '+', (dn, cp) on '-';
+//                            cs = max(s, a - lag_b - fm), ce = min(e, b + lag_e + fm); statistics at genomic
+//                            g in [cs + lag_b, ce - lag_e); fails when ce - cs < K, when a base code of the
+//                            clipped part is not 0..3, or (fm > 0) when fewer than 2 fm + 1 statistics
+//   form 1 (sample_compare)  cs = max(s, a - fm), ce = min(e, b + fm); statistics at g in [cs, ce); fails when no g
+//                            has level, control mean and control sd all non-NaN, or (fm > 0) when fewer than
+//                            2 fm + 1 statistics
+// At g the read index is i = g - s on '+' and e - 1 - g on '-'; the clipped part is read indices
+// [cs - s, ce - s) on '+' and [e - ce, e - cs) on '-'.  The host has checked that every read overlaps
+// its region, so cs < ce, and every index below stays inside the read and the region's extended positions.
+struct SitePairArgs {
+    int form, K, cp;
+    i64 fm, n_pairs;
+    const i64 *reg_start, *reg_end, *pos_off;            // per region; pos_off: its first extended position
+    const i64 *pair_reg, *pair_read;                     // per pair
+    const i64 *read_start, *read_off;                    // per read
+    const int8_t *read_strand;
+    const double *means;                                 // read-centric levels
+    const uint8_t *seq;                                  // form 0: read-centric base codes
+    const double *pos_means, *pos_sds;                   // form 1: control levels per extended position
+    const double *kmeans, *ksds;                         // form 0: the model's level table
+};
+
+struct SitePairGeom { i64 s, e, cs, ce, first, count; bool minus; };
+
+__device__ __forceinline__ SitePairGeom site_pair_geom(const SitePairArgs &a, i64 p)
+{
+    SitePairGeom q;
+    const i64 rd = a.pair_read[p], r = a.pair_reg[p];
+    q.s = a.read_start[rd];
+    q.e = q.s + (a.read_off[rd + 1] - a.read_off[rd]);
+    q.minus = a.read_strand[rd] != 0;
+    const i64 dn = a.K - a.cp - 1;
+    const i64 lag_b = a.form != 0 ? 0 : q.minus ? dn : a.cp;
+    const i64 lag_e = a.form != 0 ? 0 : q.minus ? a.cp : dn;
+    const i64 lo = a.reg_start[r] - lag_b - a.fm, hi = a.reg_end[r] + lag_e + a.fm;
+    q.cs = q.s > lo ? q.s : lo;
+    q.ce = q.e < hi ? q.e : hi;
+    q.first = q.cs + lag_b;
+    q.count = (q.ce - lag_e) - q.first;
+    return q;
+}
+
+// One wavefront per pair (blocks of 256: four pairs a block, the rest by the stride loop).  pair_ok: the
+// pair did not fail; pair_pos: the genomic position of its first statistic; pair_cnt: its statistics (0
+// when it failed).
+__global__ void __launch_bounds__(256) k_site_pair_plan(SitePairArgs a, i32 *pair_ok, i64 *pair_pos, i64 *pair_cnt)
+{
+    const int lane = threadIdx.x & 63;
+    const i64 wave = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((i64)gridDim.x * blockDim.x) >> 6;
+    for (i64 p = wave; p < a.n_pairs; p += n_waves) {
+        const SitePairGeom q = site_pair_geom(a, p);
+        const i64 rd = a.pair_read[p], base = a.read_off[rd];
+        bool ok = a.form != 0 || q.ce - q.cs >= a.K;
+        if (a.fm > 0 && q.count < 2 * a.fm + 1) ok = false;
+        if (ok && a.form == 0) {   // any base of the clipped part outside ACGT
+            const i64 i0 = q.minus ? q.e - q.ce : q.cs - q.s, n = q.ce - q.cs;
+            bool bad = false;
+            for (i64 k = lane; k < n; k += 64) bad = bad || a.seq[base + i0 + k] > 3;
+            ok = !__any(bad);
+        } else if (ok) {           // any position with level, control mean and control sd
+            const i64 r = a.pair_reg[p];
+            const i64 c0 = a.pos_off[r] + (q.cs - (a.reg_start[r] - a.fm));
+            bool have = false;
+            for (i64 k = lane; k < q.count; k += 64) {
+                const i64 g = q.cs + k;
+                const double m = a.means[base + (q.minus ? q.e - 1 - g : g - q.s)], cm = a.pos_means[c0 + k], sd = a.pos_sds[c0 + k];
+                have = have || (m == m && cm == cm && sd == sd);
+            }
+            ok = __any(have) != 0;
+        }
+        if (lane == 0) { pair_ok[p] = ok ? 1 : 0; pair_pos[p] = q.first; pair_cnt[p] = ok ? q.count : 0; }
+    }
+}
+
+// One thread per statistic: j lies in pair p = the row of j in pair_off (the exclusive scan of pair_cnt),
+// k = j - pair_off[p] positions behind the pair's first.  Writes the three arrays of k_read_pvals /
+// k_site_z in their layout: off = pair_off, read_track = pair_reg, read_pos = pair_pos.
+__global__ void k_site_gather(SitePairArgs a, const i64 *pair_off, const i64 *pair_pos, i64 total,
+    double *out_means, double *out_ref_means, double *out_ref_sds)
+{
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += (i64)gridDim.x * blockDim.x) {
+        const i64 p = dev_csr_row(pair_off, a.n_pairs, j);
+        const i64 g = pair_pos[p] + (j - pair_off[p]);
+        const i64 rd = a.pair_read[p], base = a.read_off[rd], s = a.read_start[rd];
+        const i64 e = s + (a.read_off[rd + 1] - base);
+        const i64 i = a.read_strand[rd] != 0 ? e - 1 - g : g - s;
+        out_means[j] = a.means[base + i];
+        if (a.form == 0) {
+            const i64 km = window_kmer(a.seq + base + i - a.cp, a.K);   // (>= 0: the plan has scanned these bases)
+            out_ref_means[j] = km >= 0 ? a.kmeans[km] : NAN;
+            out_ref_sds[j] = km >= 0 ? a.ksds[km] : NAN;
+        } else {
+            const i64 r = a.pair_reg[p];
+            const i64 c = a.pos_off[r] + (g - (a.reg_start[r] - a.fm));
+            out_ref_means[j] = a.pos_means[c];
+            out_ref_sds[j] = a.pos_sds[c];
+        }
+    }
 }

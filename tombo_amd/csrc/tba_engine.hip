@@ -2270,6 +2270,126 @@ extern "C" int tba_site_fractions(tba_engine *e, int form, int64_t n_tracks, con
     return TBA_OK;
 }
 
+// ---- per-site fractions of the z tests from a reads table: the per-read preparation on the device --
+extern "C" int tba_site_fractions_reads(tba_engine *e, int form, int64_t n_regions, const int64_t *reg_start,
+    const int64_t *reg_end, int64_t n_reads, const int64_t *read_start, const int8_t *read_strand,
+    const int64_t *read_off, const double *means, const uint8_t *seq, const int64_t *reg_pair_off,
+    const int64_t *pair_read, const double *pos_means, const double *pos_sds, int64_t fm_offset,
+    double smallest_pval, double single_read_thresh, const double *lower_thresh,
+    const double *damp_counts, double *out_frac, int64_t *out_pos, int64_t *out_cov,
+    int64_t *out_valid_cov, double *out_damp_frac, int64_t *out_counts, int64_t *out_n_stats,
+    int32_t *out_pair_ok, int64_t *out_pair_pos, int64_t *out_pair_off, double *out_per_read,
+    int64_t per_read_cap, double *out_kernel_ms)
+{
+    if (!e || (form != 0 && form != 1) || n_regions < 0 || n_reads < 0 || !reg_start || !reg_end ||
+        !read_start || !read_strand || !read_off || !means || !reg_pair_off || !pair_read ||
+        !out_frac || !out_pos || !out_cov || !out_valid_cov || !out_counts || !out_n_stats ||
+        !out_pair_ok || !out_pair_pos || !out_pair_off || (!damp_counts) != (!out_damp_frac) ||
+        fm_offset < 0 || fm_offset > 64 || (out_per_read && per_read_cap < 0))
+        return set_err(TBA_E_ARG, "bad arguments");
+    if (form == 0 && !seq) return set_err(TBA_E_ARG, "bad arguments (de_novo form: no base codes)");
+    if (form == 1 && (!pos_means || !pos_sds)) return set_err(TBA_E_ARG, "bad arguments (sample_compare form: no control levels)");
+    if (form == 0 && (!e->have_model || e->hp.central_pos < 0 || e->hp.central_pos >= e->hp.kmer_width))
+        return set_err(TBA_E_ARG, "the de_novo form needs a model (tba_set_model)");
+    if (const int rc = check_csr_off(read_off, n_reads)) return rc;
+    if (const int rc = check_csr_off(reg_pair_off, n_regions)) return rc;
+    for (i64 q = 0; q < n_reads; q++)
+        if (read_strand[q] < 0 || read_strand[q] > 1) return set_err(TBA_E_ARG, "read strand must be 0 or 1");
+    const i64 n_pairs = n_regions > 0 ? reg_pair_off[n_regions] : 0;
+    std::vector<i64> pos_off(n_regions + 1, 0), pair_reg(n_pairs);
+    for (i64 r = 0; r < n_regions; r++) {
+        if (reg_end[r] <= reg_start[r] || reg_end[r] - reg_start[r] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "bad region");
+        pos_off[r + 1] = pos_off[r] + (reg_end[r] - reg_start[r]) + 2 * fm_offset;
+        if (pos_off[r + 1] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "2^31 positions or more in one call");
+        for (i64 p = reg_pair_off[r]; p < reg_pair_off[r + 1]; p++) {
+            const i64 q = pair_read[p];
+            if (q < 0 || q >= n_reads) return set_err(TBA_E_ARG, "pair_read outside the reads");
+            const i64 s = read_start[q], t = s + (read_off[q + 1] - read_off[q]);
+            if (s >= reg_end[r] || t <= reg_start[r]) return set_err(TBA_E_ARG, "a read does not overlap its region");
+            pair_reg[p] = r;
+        }
+    }
+    if (n_pairs == 0) {   // no region, or nothing to test: every track is empty
+        if (out_kernel_ms) out_kernel_ms[0] = out_kernel_ms[1] = 0.0;
+        out_pair_off[0] = 0;
+        std::fill_n(out_counts, n_regions, 0);
+        std::fill_n(out_n_stats, n_regions, 0);
+        return TBA_OK;
+    }
+    const i64 n_bases = read_off[n_reads], n_pos = pos_off[n_regions];
+    std::vector<i64> trk_start(n_regions);
+    for (i64 r = 0; r < n_regions; r++) trk_start[r] = reg_start[r] - fm_offset;
+    Scratch sc(e);
+    SiteCollate S(sc, n_regions, trk_start.data(), pos_off, single_read_thresh, lower_thresh, 0, damp_counts);
+    SitePairArgs a{};
+    a.form = form; a.fm = fm_offset; a.n_pairs = n_pairs;
+    a.K = form == 0 ? (int)e->hp.kmer_width : 1;
+    a.cp = form == 0 ? (int)e->hp.central_pos : 0;
+    a.reg_start = sc.in(reg_start, n_regions);
+    a.reg_end = sc.in(reg_end, n_regions);
+    a.pos_off = S.a.pos_off;
+    a.pair_reg = sc.in(pair_reg.data(), n_pairs);
+    a.pair_read = sc.in(pair_read, n_pairs);
+    a.read_start = sc.in(read_start, n_reads);
+    a.read_off = sc.in(read_off, n_reads + 1);
+    a.read_strand = sc.in(read_strand, n_reads);
+    a.means = sc.in(means, n_bases);
+    if (form == 0) {
+        a.seq = sc.in(seq, n_bases);
+        a.kmeans = e->d_kmeans.as<double>();
+        a.ksds = e->d_ksds.as<double>();
+    } else {
+        a.pos_means = sc.in(pos_means, n_pos);
+        a.pos_sds = sc.in(pos_sds, n_pos);
+    }
+    i32 *d_ok = sc.out<i32>(n_pairs);
+    i64 *d_ppos = sc.out<i64>(n_pairs), *d_cnt = sc.out<i64>(n_pairs), *d_poff = sc.out<i64>(n_pairs + 1);
+    if (sc.rc) return sc.rc;
+    // the plan and the scan; the number of statistics comes back before the buffers for them are made
+    KernelTimer t_plan(sc, out_kernel_ms != nullptr);
+    k_site_pair_plan<<<grid_for(64 * n_pairs), 256, 0, sc.stream>>>(a, d_ok, d_ppos, d_cnt);
+    k_exclusive_prefix<i64><<<1, 256, 0, sc.stream>>>(n_pairs, d_cnt, d_poff, d_poff + n_pairs);
+    t_plan.stop();
+    i64 total = 0;
+    if (sc.sync() || sc.get(&total, d_poff + n_pairs, 1)) return sc.rc;
+    if (out_per_read && per_read_cap < total) return set_err(TBA_E_ARG, "per_read_cap is smaller than the number of statistics");
+    double *d_pr = nullptr;
+    KernelTimer t_gather(sc, out_kernel_ms != nullptr);
+    KernelTimer t_stat(sc, out_kernel_ms != nullptr);
+    S.zero_counters();
+    if (total > 0) {
+        double *d_m = sc.out<double>(total), *d_r = sc.out<double>(total), *d_s = sc.out<double>(total);
+        if (out_per_read || fm_offset > 0) d_pr = sc.out<double>(total);
+        if (sc.rc) return sc.rc;
+        k_site_gather<<<grid_for(total), 256, 0, sc.stream>>>(a, d_poff, d_ppos, total, d_m, d_r, d_s);
+        t_gather.stop();
+        const int floor_out = form == 0 ? 1 : 0;
+        if (fm_offset == 0)
+            k_site_z<<<grid_for(total), 256, 0, sc.stream>>>(S.a, d_m, d_r, d_s, d_poff, n_pairs, total, a.pair_reg,
+                d_ppos, floor_out, smallest_pval, d_pr);
+        else {
+            k_read_pvals<<<grid_for(total), 256, 0, sc.stream>>>(d_m, d_r, d_s, d_poff, n_pairs, total,
+                fm_offset, floor_out, smallest_pval, d_pr);
+            k_site_stat<<<grid_for(total), 256, 0, sc.stream>>>(S.a, d_pr, d_poff, n_pairs, total, a.pair_reg, d_ppos);
+        }
+    } else
+        t_gather.stop();
+    S.finish();
+    t_stat.stop();
+    if (sc.sync()) return sc.rc;
+    if (out_kernel_ms) {
+        const double g = t_gather.ms();
+        out_kernel_ms[0] = t_plan.ms() + g;
+        out_kernel_ms[1] = t_stat.ms() - g;
+    }
+    if (S.read_back(out_frac, out_pos, out_cov, out_valid_cov, out_damp_frac, out_counts, out_n_stats) ||
+        sc.get(out_pair_ok, d_ok, n_pairs) || sc.get(out_pair_pos, d_ppos, n_pairs) ||
+        sc.get(out_pair_off, d_poff, n_pairs + 1))
+        return sc.rc;
+    if (out_per_read && total > 0) return sc.get(out_per_read, d_pr, total);
+    return TBA_OK;
+}
+
 // ---- per-site fractions from stored per-read records: aggregate_per_read_stats -----------------
 extern "C" int tba_site_aggregate(tba_engine *e, int64_t n_blocks, const int64_t *blk_start,
     const int64_t *blk_end, const int64_t *rec_off, const void *records, double single_read_thresh,

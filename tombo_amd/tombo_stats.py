@@ -1267,6 +1267,127 @@ def compute_reg_stats(reg_data, fm_offset, min_test_reads, single_read_thresh, l
     return _only(res)
 
 
+# The same results with the per-read preparation on the device (`Engine.site_fractions_reads`, kernels
+# k_site_pair_plan / k_site_gather of csrc/k_site.h).  `_reg_stats_z_inputs` slices, flips and looks up every
+# (region, read) pair in Python and uploads 24 bytes per statistic; here every read goes up once (8 bytes per
+# level, 1 per base) with the (region, read) pairs, and clip, flip and expected levels are index arithmetic
+# in the kernels.  The statistics then run through the kernels of the route above, so the results are its
+# bits.
+class _ReadsInputs(object):
+    """the inputs of one `Engine.site_fractions_reads` call, one track per region: what `_ZInputs` offers to
+    `_region_stats` and `_per_read_blocks`, built from the pair arrays the call returns"""
+
+    def __init__(self, form, table, read_ids):
+        self.form, self.table, self.read_ids = form, table, read_ids
+        self.pair_reg = np.repeat(np.arange(table[0].shape[0], dtype=np.int64), np.diff(table[7]))
+        self.pair_ok = self.pair_pos = self.pair_off = None
+
+    def site_fractions(self, eng, *thresholds):
+        res, self.pair_ok, self.pair_pos, self.pair_off = eng.site_fractions_reads(
+            self.form, *self.table, SMALLEST_PVAL, *thresholds)
+        return res
+
+    @property
+    def n_ok(self):
+        """per region the number of pairs that did not fail"""
+        return np.bincount(self.pair_reg, weights=self.pair_ok, minlength=self.table[0].shape[0]).astype(np.int64)
+
+    def stat_index(self):
+        lens = np.diff(self.pair_off)
+        return (np.repeat(self.pair_reg, lens),
+                np.repeat(self.pair_pos - self.pair_off[:-1], lens) + np.arange(self.pair_off[-1]),
+                np.repeat(self.table[8], lens), self.read_ids)
+
+
+def _reads_table(regions, need_seq, skip):
+    """the unique reads (by identity) of the regions that have levels (need_seq: and a sequence), and the
+    regions' pairs in `reg.reads` order; skip[r]: region r gets no pairs.  The loops collect references and
+    lengths only -> (reads, reg_pair_off, pair_read)"""
+    index, reads, pair_read, counts = {}, [], [], []
+    for reg, no in zip(regions, skip):
+        n0 = len(pair_read)
+        for rd in (() if no else (reg.reads or ())):
+            if rd.means is None or (need_seq and rd.seq is None):
+                continue   # (the TomboError of the per-read functions: left out of the region)
+            q = index.get(id(rd))
+            if q is None:
+                q = index[id(rd)] = len(reads)
+                reads.append(rd)
+            pair_read.append(q)
+        counts.append(len(pair_read) - n0)
+    return reads, _csr_offsets(counts), np.array(pair_read, dtype=np.int64)
+
+
+def _reg_stats_reads_inputs(regions, fm_offset, stat_type, ctrl_levels=None):
+    """the _ReadsInputs of a list of regions.  ctrl_levels[r]: (ctrl_means, ctrl_sds) over the extended
+    region or None (region already failed)."""
+    de_novo = stat_type == DE_NOVO_TXT
+    skip = [ctrl_levels is not None and ctrl_levels[r] is None for r in range(len(regions))]
+    reads, pair_off, pair_read = _reads_table(regions, de_novo, skip)
+    means = [np.asarray(rd.means, dtype=np.float64) for rd in reads]
+    lens = np.array([m.shape[0] for m in means], dtype=np.int64)
+    start = np.array([rd.start for rd in reads], dtype=np.int64)
+    if any(rd.strand not in ('+', '-') for rd in reads):
+        raise ValueError('read strand must be "+" or "-"')
+    bad = lens != np.array([rd.end for rd in reads], dtype=np.int64) - start
+    seq = None
+    if de_novo:
+        bad |= lens != np.array([len(rd.seq) for rd in reads], dtype=np.int64)
+        seq = encode_seq(b''.join(rd.seq.encode() if isinstance(rd.seq, str) else bytes(rd.seq) for rd in reads))
+    if bad.any():
+        raise ValueError('read %r: end - start, its number of levels and its sequence length disagree'
+                         % (reads[int(np.flatnonzero(bad)[0])].read_id,))
+    reg_start = np.array([reg.start for reg in regions], dtype=np.int64)
+    reg_end = np.array([reg.end for reg in regions], dtype=np.int64)
+    pos_means = pos_sds = None
+    if not de_novo:   # the control levels once per region (NaN under a region that failed)
+        ext = reg_end - reg_start + 2 * fm_offset
+        cols = [[np.full(n, np.nan) if lv is None else np.asarray(lv[k], dtype=np.float64)
+                 for lv, n in zip(ctrl_levels, ext.tolist())] for k in range(2)]
+        if any(c.shape[0] != n for c, n in zip(cols[0] + cols[1], ext.tolist() * 2)):
+            raise ValueError('control levels do not cover the extended region')
+        pos_means, pos_sds = _concat_f64(cols[0]), _concat_f64(cols[1])
+    table = (reg_start, reg_end, start, np.array([rd.strand == '-' for rd in reads], dtype=np.int8),
+             _csr_offsets(lens), _concat_f64(means), seq, pair_off, pair_read, pos_means, pos_sds, int(fm_offset))
+    return _ReadsInputs(0 if de_novo else 1, table, [rd.read_id for rd in reads])
+
+
+def compute_reg_stats_reads_batch(regions, fm_offset, min_test_reads, single_read_thresh, lower_thresh,
+                                  ctrl_regions, std_ref, alt_refs, use_standard_llhr, stat_type,
+                                  prior_weights, cov_damp_counts=None, return_per_read=False, engine=None):
+    """`compute_reg_stats_batch` (same arguments, same return value) with the per-read preparation of de_novo
+    and sample_compare on the device: ONE `tba_site_fractions_reads` call on a reads table that holds every
+    read of the regions once, however many regions it spans.  The reads of a region must overlap it (as
+    `intervalData.add_reads` selects them); end - start, the levels and the sequence of a read must agree in
+    length (ValueError).  model_compare goes through `compute_reg_stats_batch`."""
+    if stat_type == ALT_MODEL_TXT:
+        return compute_reg_stats_batch(regions, fm_offset, min_test_reads, single_read_thresh, lower_thresh,
+                                       ctrl_regions, std_ref, alt_refs, use_standard_llhr, stat_type,
+                                       prior_weights, cov_damp_counts, return_per_read, engine)
+    _check_reg_stats_args(regions, fm_offset, min_test_reads, ctrl_regions, std_ref, alt_refs, stat_type)
+    fm_offset, min_test_reads = int(fm_offset), int(min_test_reads)
+    failed = ctrl_cov = [None] * len(regions)
+    names, eng = [stat_type], _engine(engine)
+    if stat_type == SAMP_COMP_TXT:
+        levels, ctrl_cov, failed = _ctrl_levels(ctrl_regions, min_test_reads, fm_offset, std_ref,
+                                                prior_weights, engine)
+        inp = _reg_stats_reads_inputs(regions, fm_offset, stat_type, levels)
+    else:
+        eng.ensure_model(std_ref)
+        inp = _reg_stats_reads_inputs(regions, fm_offset, stat_type)
+    no_stats = th.TomboError('Reads contains no statistics in this region.')
+    if inp.pair_reg.shape[0] == 0:   # (nothing to compute: no engine call)
+        out = [e if e is not None else no_stats for e in failed]
+        return (out, [[] for _ in regions]) if return_per_read else out
+    res = inp.site_fractions(eng, single_read_thresh, lower_thresh, _damp_pair(cov_damp_counts), return_per_read)
+    failed = [e if e is not None or n else no_stats for e, n in zip(failed, inp.n_ok.tolist())]
+    out = [e if e is not None else _region_stats(reg, r, names, res, ctrl_cov[r] if stat_type == SAMP_COMP_TXT else None)
+           for r, (reg, e) in enumerate(zip(regions, failed))]
+    if return_per_read:
+        return out, _per_read_blocks(inp, res, regions, names, failed)
+    return out
+
+
 def calc_damp_fraction(cov_damp_counts, fracs, valid_cov):
     """tombo_stats.py:2537-2552: (round(frac * valid) + unmod) / (valid + unmod + mod), np.round
     being round-half-even"""
@@ -1798,6 +1919,130 @@ def write_stats_from_regions(results, per_read, stats, pr_stats=None):
         if not isinstance(reg_res, Exception):
             for _, reg_stats in reg_res:
                 stats._write_stat_block(reg_stats)
+
+
+# ---------------------------------------------------------------------------------------------
+# test_significance (tombo_stats.py:4574-4657, worker :4400-4438): the reference cuts the covered genome into
+# regions, hands them to worker processes and collects their results in writer processes.  Here the regions
+# are taken in the order `th.iter_cov_regs` gives them and go to the engine in batches; one process, no queues.
+TEST_SIGNIF_MAX_STATS = 1 << 24     # upper bound on the statistics of one engine call (24 bytes each on the device)
+
+
+def _region_stat_bound(reg, fm_offset, n_names=1):
+    """an upper bound on the statistics region `reg` yields: its reads' overlaps with the extended region"""
+    s = np.array([rd.start for rd in reg.reads], dtype=np.int64)
+    e = np.array([rd.end for rd in reg.reads], dtype=np.int64)
+    ov = np.minimum(e, reg.end + fm_offset) - np.maximum(s, reg.start - fm_offset)
+    return int(np.maximum(ov, 0).sum()) * n_names
+
+
+def _ctrl_region_seq(ctrl, fm_offset, std_ref):
+    """the sequence of a control region as the prior blend reads it (compute_posterior_samp_dists,
+    :3575-3584): from the control reads over [start - lag_b - fm, end + lag_e + fm), padded with '-' to the
+    span `_prior_levels` takes"""
+    K, cp = std_ref.kmer_width, std_ref.central_pos
+    dn = K - cp - 1
+    lag_b, lag_e = (cp, dn) if ctrl.strand == '+' else (dn, cp)
+    seq = th.get_region_seq(ctrl.reads, ctrl.start - lag_b - fm_offset, ctrl.end + lag_e + fm_offset)
+    return '-' * (K - 1 - lag_b) + seq + '-' * (K - 1 - lag_e)
+
+
+def iter_signif_region_batches(reads_index, stat_type, region_size, fm_offset, ctrl_reads_index=None, std_ref=None,
+                               alt_refs=None, max_stats_per_call=TEST_SIGNIF_MAX_STATS, engine=None):
+    """The region batches of `test_significance` -> (regions, ctrl_regions or None) per engine call: the
+    regions of `th.iter_cov_regs(reads_index, 1, region_size, ctrl_reads_index)` in that order, each with its
+    reads (`intervalData.add_reads`; the control copy likewise), those without sample reads left out; a batch
+    ends before the upper bound on its statistics passes max_stats_per_call (a region above it goes alone)."""
+    n_names = len(alt_refs) if stat_type == ALT_MODEL_TXT else 1
+    regs, ctrls, n = [], [], 0
+    for chrm, strand, start in th.iter_cov_regs(reads_index, 1, region_size, ctrl_reads_index, engine=engine):
+        reg = th.intervalData(chrm, start, start + region_size, strand).add_reads(reads_index)
+        if len(reg.reads) == 0:
+            continue
+        ctrl = None
+        if ctrl_reads_index is not None:
+            ctrl = reg.copy(include_reads=False).add_reads(ctrl_reads_index)
+            if stat_type in LEVEL_STATS_TXTS and len(ctrl.reads) == 0:
+                continue   # (get_base_levels of the control raises: the worker skips the region)
+            if stat_type == SAMP_COMP_TXT and std_ref is not None:
+                ctrl.update(seq=_ctrl_region_seq(ctrl, fm_offset, std_ref))
+        bound = _region_stat_bound(reg, fm_offset, n_names)
+        if regs and n + bound > max_stats_per_call:
+            yield regs, (ctrls if ctrl_reads_index is not None else None)
+            regs, ctrls, n = [], [], 0
+        regs.append(reg)
+        ctrls.append(ctrl)
+        n += bound
+    if regs:
+        yield regs, (ctrls if ctrl_reads_index is not None else None)
+
+
+def signif_store_names(stat_type, stats_file_bn, per_read_bn=None, alt_refs=None):
+    """the file names of `test_significance` (_get_stats_queue :4452-4470, _get_per_read_queue :4507-4516)
+    -> ({statistic name: statistics file}, {statistic name: per-read file})"""
+    names = [n for n, _ in alt_refs] if stat_type == ALT_MODEL_TXT else [stat_type]
+    infix = dict((n, '.' + n if stat_type == ALT_MODEL_TXT else '') for n in names)
+    return (dict((n, stats_file_bn + infix[n] + '.tombo.stats') for n in names),
+            {} if per_read_bn is None else dict((n, per_read_bn + infix[n] + '.tombo.per_read_stats') for n in names))
+
+
+def test_significance(reads_index, stat_type, stats_file_bn, region_size, num_processes, min_test_reads,
+                      num_most_signif, per_read_bn=None, single_read_thresh=None, lower_thresh=None,
+                      cov_damp_counts=None, fm_offset=None, ctrl_reads_index=None, std_ref=None, alt_refs=None,
+                      use_standard_llhr=False, prior_weights=None, engine=None, stores=None,
+                      max_stats_per_call=TEST_SIGNIF_MAX_STATS):
+    """tombo_stats.py:4574-4657 on an in-memory reads index ({(chrm, strand): [reads]}): modified base
+    detection over every covered region, written to the statistics file(s) `<stats_file_bn>[.<alt name>]
+    .tombo.stats` and, with per_read_bn, `<per_read_bn>[.<alt name>].tombo.per_read_stats`.  de_novo and
+    sample_compare run through `compute_reg_stats_reads_batch`, model_compare through
+    `compute_reg_stats_batch`, the six level tests through `compute_group_reg_stats_batch` (a LevelStats
+    file).  Regions without sample reads, and regions whose computation raises th.TomboError, are skipped.
+    stores: {file name: open group-interface object} to write into instead of opening the files (h5py).
+    num_processes is accepted and ignored: the regions go to the engine in batches of at most
+    max_stats_per_call statistics (an upper bound)."""
+    is_level = stat_type in LEVEL_STATS_TXTS
+    if not is_level and stat_type not in PER_READ_STATS:
+        raise NotImplementedError('Unrecognized test type.')
+    fm_offset = FM_OFFSET_DEFAULT if fm_offset is None else int(fm_offset)
+    if is_level and ctrl_reads_index is None:
+        raise ValueError('%s needs control reads (ctrl_reads_index)' % stat_type)
+    if not is_level and (single_read_thresh is None or cov_damp_counts is None):
+        raise ValueError('%s needs single_read_thresh and cov_damp_counts' % stat_type)
+    stores = stores or {}
+    stat_fns, pr_fns = signif_store_names(stat_type, stats_file_bn, None if is_level else per_read_bn, alt_refs)
+    if is_level:
+        all_stats = dict((n, LevelStats(stores.get(fn, fn), stat_type, region_size, min_test_reads, num_most_signif))
+                         for n, fn in stat_fns.items())
+    else:
+        cd = cov_damp_counts   # (stored as given: a pair, or the reference's dict)
+        damp = (cd['unmod'], cd['mod']) if isinstance(cd, dict) else tuple(cd)
+        all_stats = dict((n, ModelStats(stores.get(fn, fn), stat_type, region_size, damp, min_test_reads,
+                                        num_most_signif)) for n, fn in stat_fns.items())
+    all_pr = dict((n, PerReadStats(stores.get(fn, fn), stat_type, region_size)) for n, fn in pr_fns.items())
+    try:
+        for regs, ctrls in iter_signif_region_batches(reads_index, stat_type, region_size, fm_offset, ctrl_reads_index,
+                                                      std_ref, alt_refs, max_stats_per_call, engine):
+            if is_level:
+                results = compute_group_reg_stats_batch(regs, ctrls, fm_offset, min_test_reads, stat_type, engine)
+                per_read = [[] for _ in regs]
+            else:
+                compute = compute_reg_stats_batch if stat_type == ALT_MODEL_TXT else compute_reg_stats_reads_batch
+                results = compute(regs, fm_offset, min_test_reads, single_read_thresh, lower_thresh, ctrls, std_ref,
+                                  alt_refs, use_standard_llhr, stat_type, prior_weights,
+                                  return_per_read=bool(all_pr), engine=engine)
+                results, per_read = results if all_pr else (results, [[] for _ in regs])
+            for reg_res, reg_blocks in zip(results, per_read):
+                for name, block in reg_blocks:
+                    all_pr[name]._write_per_read_block(*block)
+                if not isinstance(reg_res, Exception):
+                    for name, reg_stats in reg_res:
+                        all_stats[name]._write_stat_block(reg_stats)
+    finally:
+        for container in list(all_stats.values()) + list(all_pr.values()):
+            container.close()
+
+
+test_significance.__test__ = False   # (the reference's name; not a test)
 
 
 # ---------------------------------------------------------------------------------------------
