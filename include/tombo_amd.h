@@ -55,6 +55,7 @@ enum {
     TBA_SEQ_SEG_MISMATCH = 20,      /* resquiggle.py:1201 */
     TBA_NO_RAW = 21,                /* resquiggle.py:1148 */
     TBA_INVALID_SEQ = 22,           /* tombo_stats.py:858 */
+    TBA_TRIM_TOO_FEW_EVENTS = 23,   /* tombo_stats.py:250,258: numpy's ValueError, too few events for the windows */
     TBA_INTERNAL = 100,             /* the reference would raise a non-Tombo exception here */
     TBA_UNSUPPORTED = 101           /* valid in the reference, outside this engine's limits
                                        (band wider than TBA_MAX_BAND, scratch arena exhausted) */
@@ -1056,6 +1057,39 @@ int tba_mom_sums(tba_engine *e, int64_t n_reads, const int64_t *off, const doubl
 int tba_seg_scores(tba_engine *e, int64_t n_reads, const int64_t *off, const double *means,
     const double *ref_means, const double *ref_sds, double *scores);
 
+/* ---- RNA adapter trimming and the global scale estimate (csrc/k_trim_rna.h) ----
+ * ts.trim_rna (tombo_stats.py:235-267) of n_reads reads in host memory.  raw: the reads' samples one after the
+ * other (raw_dtype: TBA_RAW_I16 or TBA_RAW_F64), read i at raw_off[i] .. raw_off[i + 1]; only its first max_raw_obs
+ * samples are uploaded and touched.  min_obs_per_base, running_stat_width, mean_obs_per_event: th.resquiggleParams;
+ * moving_window_size, min_running_values, thresh_scale, max_raw_obs: th.trimRnaParams.  The change points come from
+ * the batch kernels of event detection (th.valid_cpts_w_cap: the plain detector, sorted; equal scores as
+ * INTEGRATION.md section 6 states), in the form tba_engine_set_dispatch selects: above small_batch_reads reads, with
+ * 2 * running_stat_width <= 32 and min_obs_per_base 3, k_detect + k_pick, else the kernels that keep the scores.
+ * Out: adapter_end[i] (0 where status[i] is not TBA_OK); status[i]: TBA_OK, TBA_FEWER_CPTS (the detector's
+ * TomboError), TBA_TRIM_TOO_FEW_EVENTS (fewer than moving_window_size + min_running_values - 2 event SDs: numpy's
+ * ValueError 'negative dimensions are not allowed'), TBA_INTERNAL (a prefix without a score or an event: the
+ * reference indexes an empty array); ed_form (or NULL): TBA_ED_FORM_* of the kernels that produced each read's
+ * change points; *out_kernel_ms (or NULL): the time of the kernels.  No read count or max_raw_obs is refused for
+ * its size: reads with more event SDs than the LDS form holds take the global-memory form of the window kernel,
+ * batches are cut inside the call by a budget of uploaded samples (tba_engine_set_trim_budget), and zero reads
+ * launch nothing.  The same call gives the same bytes (no floating-point atomics).
+ * TBA_E_ARG: NULL pointers, offsets that do not start at 0 or decrease, a raw dtype other than the two, a parameter
+ * below 1, a thresh_scale that is NaN, a prefix of 2^31 samples or more, a moving_window_size above 8192 (a row of
+ * the window stage is one block of numpy's pairwise sum: wider rows are refused, not answered differently). */
+int tba_trim_rna_batch(tba_engine *e, int64_t n_reads, const void *raw, int raw_dtype, const int64_t *raw_off,
+    int64_t min_obs_per_base, int64_t running_stat_width, int64_t mean_obs_per_event, int64_t moving_window_size,
+    int64_t min_running_values, double thresh_scale, int64_t max_raw_obs, int64_t *adapter_end, int32_t *status,
+    int32_t *ed_form, double *out_kernel_ms);
+/* the most prefix samples one device pass of tba_trim_rna_batch holds (a read above it goes alone); samples < 1:
+ * back to the default, TBA_TRIM_BUDGET_DEFAULT */
+#define TBA_TRIM_BUDGET_DEFAULT (1ll << 26)
+int tba_engine_set_trim_budget(tba_engine *e, int64_t samples);
+/* np.median(raw) and np.median(np.abs(raw - median)) of n_reads reads (one sample or more each), by exact
+ * selection on int16 or float64 samples: what ts.estimate_global_scale (tombo_stats.py:452-480) takes of a read.
+ * No normalised signal is made.  *out_kernel_ms (or NULL): the time of the kernel. */
+int tba_raw_med_mad(tba_engine *e, int64_t n_reads, const void *raw, int raw_dtype, const int64_t *raw_off,
+    double *med, double *mad, double *out_kernel_ms);
+
 /* Host-side, no GPU involved: pack n_reads per-read sample arrays (raw_ptrs[i], raw_off[i+1] -
  * raw_off[i] samples of type raw_dtype; reverse != 0: copied back to front) and sequences
  * (seq_ptrs[i]: ASCII A/C/G/T, seq_off[i+1] - seq_off[i] letters, stored as codes 0..3, anything
@@ -1108,8 +1142,9 @@ int tba_synth_dwell_thresholds(const tba_synth_params *p, uint32_t *thr, int64_t
 #define TBA_ABI_VERSION 13
 /* additions that leave every struct, every entry and every selector of TBA_ABI_VERSION as it was (not part of
  * tba_abi_sizes: a binding asks for what it needs by name).  1: tba_one_sd_words, TBA_GET_DP_ONE_SD;
- * 2: tba_center_prepare, tba_center_fit; 3: tba_site_fractions_reads */
-#define TBA_ABI_MINOR 3
+ * 2: tba_center_prepare, tba_center_fit; 3: tba_site_fractions_reads; 4: tba_trim_rna_batch,
+ * tba_engine_set_trim_budget, tba_raw_med_mad, TBA_TRIM_TOO_FEW_EVENTS */
+#define TBA_ABI_MINOR 4
 int tba_abi_sizes(int64_t *out, int64_t n);
 
 /* self-test: out[t] = index t of the subsample tba_opts.device_subsample draws for read

@@ -24,6 +24,8 @@ MIN_EVENT_TO_SEQ_RATIO = 1.1
 USE_RNA_EVENT_SCALE = True
 RNA_SCALE_NUM_EVENTS = 10000
 RNA_SCALE_MAX_FRAC_EVENTS = 0.75
+TRIM_RNA_ADAPTER = False
+NUM_READS_FOR_SCALE = 1000
 COLLAPSE_RNA_STALLS = True
 COLLAPSE_DNA_STALLS = False
 MEAN_STALL_PARAMS = dict(window_size=7 * 50, threshold=40, edge_buffer=100,

@@ -301,6 +301,10 @@ def _prototypes():
         'tba_normalize_raw_batch': (n, [v, q, v, n, cQ, cQ, cQ, n, cD, cI, cD, n, d, d, D, I, D, I, D]),
         'tba_mom_sums': (n, [v, q, cQ, cD, cD, cD, D]),
         'tba_seg_scores': (n, [v, q, cQ, cD, cD, cD, D]),
+        # ---- RNA adapter trimming, the global scale estimate ----
+        'tba_trim_rna_batch': (n, [v, q, v, n, cQ, q, q, q, q, q, d, q, Q, I, I, D]),
+        'tba_engine_set_trim_budget': (n, [v, q]),
+        'tba_raw_med_mad': (n, [v, q, v, n, cQ, D, D, D]),
         'tba_pack_reads': (n, [q, v, n, n, cQ, v, v, cQ, B, n]),
         'tba_unpack_reads': (n, [q, v, q, cQ, cQ, v, n]),
         # ---- synthetic reads made on the device ----
@@ -577,6 +581,46 @@ def _check_normalize_raw_args(raws, starts, lens, norm_type, sv_in, sv_flags, ch
     if norm_type == NORMTYPE_PA_RAW and channel is None and (sv_flags is None or not (sv_flags & 1).all()):
         raise ValueError('pA_raw needs the channel values')
     return dt, np.ascontiguousarray(np.concatenate(raws)), _offsets(raws), starts, lens
+
+
+TRIM_TOO_FEW_EVENTS = 23    # TBA_TRIM_TOO_FEW_EVENTS: a read with too few events for the windows of trim_rna
+TRIM_MAX_WINDOW = 8192      # the widest moving_window_size tba_trim_rna_batch takes
+
+
+def _check_raw_reads(raws, min_len=0):
+    """the reads of Engine.trim_rna / Engine.raw_med_mad: one-dimensional arrays, all int16 or all float64 (checked,
+    not converted) -> (dtype, the arrays)"""
+    raws = [np.asarray(r) for r in raws]
+    dt = raws[0].dtype if raws else np.dtype(np.float64)
+    if dt not in (np.dtype(np.int16), np.dtype(np.float64)) or any(r.dtype != dt or r.ndim != 1 for r in raws):
+        raise ValueError('the raw signals must be one-dimensional arrays, all int16 or all float64')
+    if any(r.shape[0] < min_len for r in raws):
+        raise ValueError('every read needs %d sample(s) or more' % min_len)
+    return dt, raws
+
+
+def _check_trim_rna_args(raws, seg_params, trim_params):
+    """the argument checks of Engine.trim_rna (shared with the tests' stand-in engine) -> (dtype, the reads' prefixes,
+    (running_stat_width, min_obs_per_base, mean_obs_per_event), (moving_window_size, min_running_values, thresh_scale,
+    max_raw_obs))"""
+    seg, trim = tuple(seg_params), tuple(trim_params)
+    if len(seg) != 3 or any(int(v) != v or v < 1 for v in seg):
+        raise ValueError('seg_params must be (running_stat_width, min_obs_per_base, mean_obs_per_event), integers of 1 '
+                         'or more')
+    if len(trim) != 4 or any(int(v) != v or v < 1 for v in (trim[0], trim[1], trim[3])):
+        raise ValueError('trim_params must be (moving_window_size, min_running_values, thresh_scale, max_raw_obs), the '
+                         'sizes integers of 1 or more')
+    if trim[0] > TRIM_MAX_WINDOW:
+        raise ValueError('moving_window_size above %d' % TRIM_MAX_WINDOW)
+    thresh_scale = float(trim[2])
+    if thresh_scale != thresh_scale:
+        raise ValueError('thresh_scale must be a number')
+    dt, raws = _check_raw_reads(raws)
+    mro = int(trim[3])
+    if mro >= 2 ** 31 and any(r.shape[0] >= 2 ** 31 for r in raws):
+        raise ValueError('a prefix holds fewer than 2**31 samples')
+    return (dt, [r[:mro] for r in raws], tuple(int(v) for v in seg),
+            (int(trim[0]), int(trim[1]), thresh_scale, mro))
 
 
 def _check_point_arrays(off, *arrays):
@@ -1845,6 +1889,41 @@ class Engine(object):
         out = np.zeros(off.shape[0] - 1, np.float64)
         self._call('tba_seg_scores', off.shape[0] - 1, off, m, rm, rs, out)
         return out
+
+    # ---- RNA adapter trimming, the global scale estimate (csrc/k_trim_rna.h) ----
+    def trim_rna(self, raws, seg_params, trim_params):
+        """tba_trim_rna_batch: ts.trim_rna of the one-dimensional arrays `raws`, all int16 or all float64; only their
+        first max_raw_obs samples are handed over.  seg_params: (running_stat_width, min_obs_per_base,
+        mean_obs_per_event); trim_params: (moving_window_size, min_running_values, thresh_scale, max_raw_obs).
+        -> (adapter ends int64 [n], status int32 [n]: 0, 2 (fewer change points than requested), TRIM_TOO_FEW_EVENTS,
+        100); last_trim_ed_form holds ED_FORM_* per read, last_trim_kernel_ms the time of the kernels"""
+        dt, pre, (width, mob, mope), (mw, mr, ts_, mro) = _check_trim_rna_args(raws, seg_params, trim_params)
+        n = len(pre)
+        ends, status, form = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        ms = np.zeros(1, np.float64)
+        if n:
+            raw = np.ascontiguousarray(np.concatenate(pre))
+            self._call('tba_trim_rna_batch', n, raw.ctypes, RAW_DTYPES[dt], _offsets(pre), mob, width, mope, mw, mr, ts_,
+                       mro, ends, status, form, ms)
+        self.last_trim_ed_form, self.last_trim_kernel_ms = form, float(ms[0])
+        return ends, status
+
+    def set_trim_budget(self, samples=0):
+        """tba_engine_set_trim_budget: the most prefix samples one device pass of trim_rna holds (0: the default)"""
+        self._call('tba_engine_set_trim_budget', int(samples))
+
+    def raw_med_mad(self, raws):
+        """tba_raw_med_mad: (np.median(r), np.median(np.abs(r - median))) of the one-dimensional arrays `raws` (one
+        sample or more each), all int16 or all float64 -> two float64 [n]; last_med_mad_kernel_ms holds the kernel's
+        time"""
+        dt, raws = _check_raw_reads(raws, 1)
+        n = len(raws)
+        med, mad, ms = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(1, np.float64)
+        if n:
+            raw = np.ascontiguousarray(np.concatenate(raws))
+            self._call('tba_raw_med_mad', n, raw.ctypes, RAW_DTYPES[dt], _offsets(raws), med, mad, ms)
+        self.last_med_mad_kernel_ms = float(ms[0])
+        return med, mad
 
     # ---- region plot data (csrc/k_plot.h) ----
     def region_level_piles(self, read_start, read_minus, read_off, means, reg_read_off, reg_reads, reg_start, reg_end,

@@ -29,6 +29,7 @@
 #include "k_filter.h"
 #include "k_norm_api.h"
 #include "k_center.h"
+#include "k_trim_rna.h"
 
 #include <algorithm>
 #include <array>
@@ -160,6 +161,7 @@ struct tba_engine {
     // latency / throughput forms of event detection and traceback (tba_engine_set_dispatch)
     i64 small_batch = TBA_SMALL_BATCH, tb_wave_below = TBP_WAVE_BELOW;
     int last_c_ed_form = 0;       // tba_c_last_ed_form
+    i64 trim_budget = TBA_TRIM_BUDGET_DEFAULT; // tba_engine_set_trim_budget
     int raw_dtype = TBA_RAW_F64;
     // the open genome-track set (k_tracks.h): window [trk_start, trk_start + trk_W), trk_slots sum arrays (0: none open)
     i64 trk_start = 0, trk_W = 0;
@@ -3615,6 +3617,181 @@ extern "C" int tba_seg_scores(tba_engine *e, int64_t n_reads, const int64_t *off
     k_seg_scores<<<dim3((unsigned)n_reads), 64, 0, e->stream>>>(n_reads, d_off, d_m, d_rm, d_rs, d_tmp, d_scores);
     if (sc.sync()) return sc.rc;
     return sc.get(scores, d_scores, n_reads);
+}
+
+// ---- ts.trim_rna / ts.estimate_global_scale (k_trim_rna.h) ----
+// One device pass of tba_trim_rna_batch over reads [g0, g1): the prefixes (n_raw[i] samples of read i) go up as one
+// CSR, the kernels c_valid_cpts launches for one read run over the ReadStates of all of them (shift 0, scale 1: the
+// loaders' normalised copy of a signal is the signal), then the segment SDs and the window stage.
+// (int16 or float64 samples: the two types these entries take)
+#define TRIM_RAW(dt_, call_)                                                                   \
+    do {                                                                                       \
+        if ((dt_) == TBA_RAW_I16) { typedef int16_t RT; call_; }                               \
+        else { typedef double RT; call_; }                                                     \
+    } while (0)
+struct TrimArgs {
+    i64 min_obs_per_base, width, mean_obs_per_event, mw, mr;
+    double thresh_scale;
+};
+static int trim_rna_pass(tba_engine *e, i64 g0, i64 g1, const char *raw, int raw_dtype, const int64_t *raw_off,
+                         const i64 *n_raw, const TrimArgs &a, int64_t *adapter_end, int32_t *status, int32_t *ed_form,
+                         double *kernel_ms)
+{
+    const i64 n = g1 - g0;
+    const size_t eb = raw_elem_bytes(raw_dtype);
+    std::vector<ReadState> hrs(n);
+    std::vector<i64> sd_off(n + 1, 0);
+    memset(hrs.data(), 0, sizeof(ReadState) * n);
+    i64 S = 0, E = 0, max_sds = 0;
+    bool whole = true, any_long = false;
+    for (i64 i = 0; i < n; i++) {
+        ReadState &r = hrs[i];
+        r.raw_off = S; r.n_raw = n_raw[g0 + i];
+        r.ev_off = E; r.num_events = r.n_raw / a.mean_obs_per_event;
+        r.shift = 0.0; r.scale = 1.0;
+        // (a prefix without a score or an event: the kernels leave the read out)
+        r.status = r.n_raw + 1 - 2 * a.width <= 0 || r.num_events < 1 ? TBA_INTERNAL : TBA_OK;
+        whole = whole && r.n_raw == raw_off[g0 + i + 1] - raw_off[g0 + i];
+        any_long = any_long || r.n_raw > TBA_LONG_RAW;
+        const i64 n_sd = std::max<i64>(r.num_events - 1, 0);
+        sd_off[i + 1] = sd_off[i] + n_sd;
+        max_sds = std::max(max_sds, n_sd);
+        S += r.n_raw; E += r.num_events;
+    }
+    // the prefixes as one run of samples: the reads as they lie when every prefix is its whole read
+    std::vector<char> packed;
+    const char *src = raw + (size_t)raw_off[g0] * eb;
+    if (!whole) {
+        packed.resize((size_t)S * eb);
+        for (i64 i = 0; i < n; i++)
+            memcpy(packed.data() + (size_t)hrs[i].raw_off * eb, raw + (size_t)raw_off[g0 + i] * eb, (size_t)hrs[i].n_raw * eb);
+        src = packed.data();
+    }
+    // the score-free kernels (k_detect.h) as the batch pipeline takes them: past the latency form's batch size, at the
+    // parameters they are compiled for (k_detect leaves reads above TBA_LONG_RAW to kernels this entry does not run)
+    const bool detect = n > e->small_batch && 2 * a.width <= DT_W2MAX && a.min_obs_per_base == 3 && !any_long;
+    const bool fused_scores = 2 * a.width <= 64, in_lds = max_sds <= TRIM_LDS_SDS;
+    const bool widen = !fused_scores && raw_dtype != TBA_RAW_F64;
+    DevParams dp;
+    memset(&dp, 0, sizeof(dp));
+    dp.p.running_stat_width = a.width; dp.p.min_obs_per_base = a.min_obs_per_base;
+    Scratch sc(e);
+    const char *d_raw = sc.in(src, (size_t)S * eb, 64);
+    double *d_norm = detect ? sc.out<double>(S + 2 + 8) : widen ? sc.out<double>(S + 8) : nullptr;
+    double *d_csum = sc.out<double>(S + n + 8);
+    double *d_score = sc.out<double>(S + 8);
+    unsigned char *d_state = sc.out<unsigned char>(S + 64);
+    i64 *d_cpts = sc.out<i64>(E);
+    ReadState *d_rs = sc.in(hrs.data(), n);
+    const DevParams *d_dp = sc.in(&dp, 1);
+    const i64 *d_sd_off = sc.in(sd_off.data(), n + 1);
+    double *d_sds = sc.out<double>(sd_off[n]);
+    double *d_means = in_lds ? nullptr : sc.out<double>(sd_off[n]);
+    i64 *d_end = sc.out<i64>(n);
+    i32 *d_status = sc.out<i32>(n);
+    if (sc.rc) return sc.rc;
+    hipStream_t s = e->stream;
+    const unsigned nb = (unsigned)n;
+    KernelTimer tm(sc, kernel_ms != nullptr);
+    if (detect) {
+        TRIM_RAW(raw_dtype, (k_detect<2, RT><<<(unsigned)((n + DT_READS - 1) / DT_READS), 256, 0, s>>>(d_rs, n, d_dp, (const RT *)d_raw, d_norm, d_csum, d_score, S)));
+        k_pick<<<nb, SEL_NT, 0, s>>>(d_rs, d_dp, d_csum, d_score, d_cpts, 0);
+    }
+    const int only_flagged = detect ? 1 : 0;
+    if (fused_scores) { // (from the samples themselves: what k_detect wrote as their normalised copy is not read)
+        if (cs_reads_for(n) == 20) TRIM_RAW(raw_dtype, (k_cumsum_scores<20, RT><<<(unsigned)((n + 19) / 20), 256, 0, s>>>(d_rs, n, d_dp, (const RT *)d_raw, d_score, only_flagged)));
+        else TRIM_RAW(raw_dtype, (k_cumsum_scores<32, RT><<<(unsigned)((n + 31) / 32), 256, 0, s>>>(d_rs, n, d_dp, (const RT *)d_raw, d_score, only_flagged)));
+    } else {
+        const double *d_sig = (const double *)d_raw;
+        if (widen) {
+            k_trim_widen<int16_t><<<grid_for(S), 256, 0, s>>>((const int16_t *)d_raw, S, d_norm);
+            d_sig = d_norm;
+        }
+        i64 max_raw = 1;
+        for (i64 i = 0; i < n; i++) max_raw = std::max(max_raw, hrs[i].n_raw);
+        k_cumsum<<<(unsigned)((n + 63) / 64), 64, 0, s>>>(d_rs, n, d_sig, d_csum);
+        k_scores_dna<<<dim3(std::min(grid_for(max_raw), 128u), nb), 256, 0, s>>>(d_rs, d_dp, d_csum, d_score);
+    }
+    launch_peaks(a.min_obs_per_base, nb, s, d_rs, d_dp, d_score, d_state, d_csum, d_cpts, 0, only_flagged, TBA_ED_FORM_SCORES_PEAKS);
+    if (sd_off[n] > 0)
+        TRIM_RAW(raw_dtype, (k_trim_seg_sds<RT><<<grid_for(sd_off[n]), 256, 0, s>>>(d_rs, n, (const RT *)d_raw, d_cpts, d_sd_off, d_sds)));
+    if (in_lds) k_trim_pick<true><<<nb, TRIM_NT, 0, s>>>(d_rs, d_cpts, d_sd_off, d_sds, d_means, a.mw, a.mr, a.thresh_scale, d_end, d_status);
+    else k_trim_pick<false><<<nb, TRIM_NT, 0, s>>>(d_rs, d_cpts, d_sd_off, d_sds, d_means, a.mw, a.mr, a.thresh_scale, d_end, d_status);
+    tm.stop();
+    if (kernel_ms) *kernel_ms += tm.ms();
+    if (sc.sync() || sc.get(adapter_end + g0, d_end, n) || sc.get(status + g0, d_status, n)) return sc.rc;
+    if (ed_form) {
+        if (sc.get(hrs.data(), d_rs, n)) return sc.rc;
+        for (i64 i = 0; i < n; i++) ed_form[g0 + i] = hrs[i].ed_form;
+    }
+    return TBA_OK;
+}
+
+extern "C" int tba_trim_rna_batch(tba_engine *e, int64_t n_reads, const void *raw, int raw_dtype, const int64_t *raw_off,
+    int64_t min_obs_per_base, int64_t running_stat_width, int64_t mean_obs_per_event, int64_t moving_window_size,
+    int64_t min_running_values, double thresh_scale, int64_t max_raw_obs, int64_t *adapter_end, int32_t *status,
+    int32_t *ed_form, double *out_kernel_ms)
+{
+    if (!e || n_reads < 0) return set_err(TBA_E_ARG, "bad arguments");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (n_reads == 0) return TBA_OK;
+    if (!raw_off || !adapter_end || !status) return set_err(TBA_E_ARG, "bad arguments");
+    if (raw_dtype != TBA_RAW_F64 && raw_dtype != TBA_RAW_I16) return set_err(TBA_E_ARG, "raw dtype must be int16 or float64");
+    if (const int rc = check_csr_off(raw_off, n_reads)) return rc;
+    if (!raw && raw_off[n_reads] > 0) return set_err(TBA_E_ARG, "bad arguments");
+    if (min_obs_per_base < 1 || running_stat_width < 1 || mean_obs_per_event < 1 || moving_window_size < 1 ||
+        min_running_values < 1 || max_raw_obs < 1 || thresh_scale != thresh_scale)
+        return set_err(TBA_E_ARG, "the segmentation and trimming parameters must be 1 or more, thresh_scale a number");
+    if (moving_window_size > TRIM_MAX_WINDOW) return set_err(TBA_E_ARG, "moving_window_size above 8192");
+    std::vector<i64> n_raw(n_reads);
+    for (i64 i = 0; i < n_reads; i++) {
+        n_raw[i] = std::min<i64>(raw_off[i + 1] - raw_off[i], max_raw_obs);
+        if (n_raw[i] >= ((i64)1 << 31)) return set_err(TBA_E_ARG, "a prefix of 2^31 samples or more");
+    }
+    const TrimArgs a = {min_obs_per_base, running_stat_width, mean_obs_per_event, moving_window_size, min_running_values,
+                        thresh_scale};
+    // passes of at most trim_budget prefix samples and TBA_MAX_BATCH_READS reads (one read at least)
+    for (i64 g0 = 0; g0 < n_reads;) {
+        i64 g1 = g0, tot = 0;
+        while (g1 < n_reads && g1 - g0 < TBA_MAX_BATCH_READS && (g1 == g0 || tot + n_raw[g1] <= e->trim_budget)) tot += n_raw[g1++];
+        if (const int rc = trim_rna_pass(e, g0, g1, (const char *)raw, raw_dtype, raw_off, n_raw.data(), a, adapter_end,
+                                         status, ed_form, out_kernel_ms))
+            return rc;
+        g0 = g1;
+    }
+    return TBA_OK;
+}
+
+extern "C" int tba_engine_set_trim_budget(tba_engine *e, int64_t samples)
+{
+    if (!e) return set_err(TBA_E_ARG, "engine is NULL");
+    e->trim_budget = samples < 1 ? TBA_TRIM_BUDGET_DEFAULT : samples;
+    return 0;
+}
+
+extern "C" int tba_raw_med_mad(tba_engine *e, int64_t n_reads, const void *raw, int raw_dtype, const int64_t *raw_off,
+    double *med, double *mad, double *out_kernel_ms)
+{
+    if (!e || n_reads < 0) return set_err(TBA_E_ARG, "bad arguments");
+    if (out_kernel_ms) *out_kernel_ms = 0.0;
+    if (n_reads == 0) return TBA_OK;
+    if (!raw || !raw_off || !med || !mad) return set_err(TBA_E_ARG, "bad arguments");
+    if (raw_dtype != TBA_RAW_F64 && raw_dtype != TBA_RAW_I16) return set_err(TBA_E_ARG, "raw dtype must be int16 or float64");
+    if (const int rc = check_csr_off(raw_off, n_reads)) return rc;
+    for (i64 i = 0; i < n_reads; i++)
+        if (raw_off[i + 1] - raw_off[i] < 1 || raw_off[i + 1] - raw_off[i] >= ((i64)1 << 31))
+            return set_err(TBA_E_ARG, "every read needs one sample or more, and fewer than 2^31");
+    Scratch sc(e);
+    const char *d_raw = sc.in((const char *)raw, (size_t)raw_off[n_reads] * raw_elem_bytes(raw_dtype), 64);
+    const i64 *d_off = sc.in(raw_off, n_reads + 1);
+    double *d_med = sc.out<double>(n_reads), *d_mad = sc.out<double>(n_reads);
+    if (sc.rc) return sc.rc;
+    KernelTimer tm(sc, out_kernel_ms != nullptr);
+    TRIM_RAW(raw_dtype, (k_raw_med_mad<RT><<<dim3((unsigned)n_reads), SEL_NT, 0, e->stream>>>(d_off, (const RT *)d_raw, d_med, d_mad)));
+    tm.stop();
+    if (out_kernel_ms) *out_kernel_ms = tm.ms();
+    if (sc.sync() || sc.get(med, d_med, n_reads)) return sc.rc;
+    return sc.get(mad, d_mad, n_reads);
 }
 
 // self-test of the device-side subsample: out[t] = image of t under the keyed permutation of

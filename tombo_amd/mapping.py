@@ -219,7 +219,7 @@ def process_fast5_batch(fast5s, aligner, std_ref, rsqgl_params, seq_samp_type, s
                         bc_subgrp='BaseCalled_template', corr_grp='RawGenomeCorrected_000',
                         compute_sd=False, obs_filter=None, q_score_thresh=0, sig_match_thresh=None,
                         sig_len_rng=None, seq_len_rng=None, map_thr_buf=None, write=True,
-                        engine=None, overwrite=False):
+                        engine=None, overwrite=False, trim_rna_adapter=False):
     """One worker's share of `tombo resquiggle` for a list of reads, batch-shaped: what the
     reference does per read across `_io_and_map_read` and `_resquiggle_worker`
     (resquiggle.py:1385-1602) -- read the FAST5, map, resquiggle with the scale-iteration and
@@ -238,6 +238,11 @@ def process_fast5_batch(fast5s, aligner, std_ref, rsqgl_params, seq_samp_type, s
     attributes) -- before any mapping or GPU work is spent on it; the failures of that step carry
     the bare file name, as the reference's do.  A read that fails with a Tombo error afterwards
     gets the message as the `status` of its corrected subgroup (`th.write_error_status`).
+
+    `trim_rna_adapter` (the reference's `TRIM_RNA_ADAPTER`): the DNA adapter is cut off the head of every
+    RNA read's signal before the first pass (`resquiggle_batch_iters`); a read `ts.trim_rna` fails on is
+    reported like any other failed read -- a Tombo error for too few change points, numpy's
+    ValueError for too few events with `is_tombo_error` False.
     """
     from . import resquiggle as rq
     from ._default_parameters import SIG_MATCH_THRESH, OUTLIER_THRESH
@@ -277,7 +282,8 @@ def process_fast5_batch(fast5s, aligner, std_ref, rsqgl_params, seq_samp_type, s
     # part of every pass
     results = rq.resquiggle_batch_iters(
         mapped, std_ref, rsqgl_params, save_params=save_params, outlier_thresh=outlier_thresh,
-        seq_samp_type=seq_samp_type, engine=engine, device_prep=True) if mapped else []
+        seq_samp_type=seq_samp_type, engine=engine, device_prep=True,
+        trim_rna_adapter=trim_rna_adapter) if mapped else []
     index_records = []
     for k, res in zip(owners, results):
         f5, fn = fast5s[k]

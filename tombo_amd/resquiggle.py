@@ -675,13 +675,22 @@ def resolve_skipped_bases_with_raw(dp_res, norm_signal, rsqgl_params, max_raw_cp
 
 
 # ---- the caller's loop: _resquiggle_worker, resquiggle.py:1488-1602 ------
-def adjust_map_res(map_res, seq_samp_type):
+def adjust_map_res(map_res, seq_samp_type, trim_rna_adapter=None, rsqgl_params=None):
     """What `_resquiggle_worker.adjust_map_res` (resquiggle.py:1506-1530) does to a mapped read
-    before resquiggling: RNA signal is flipped into 5'->3' order and stall intervals are
-    detected on it (`COLLAPSE_RNA_STALLS`); DNA is passed through (`COLLAPSE_DNA_STALLS` and
-    `USE_START_CLIP_BASES` are off in the reference, `TRIM_RNA_ADAPTER` too)."""
-    from ._default_parameters import COLLAPSE_RNA_STALLS, COLLAPSE_DNA_STALLS
+    before resquiggling, in its order: with `trim_rna_adapter` (None: the module constant
+    `TRIM_RNA_ADAPTER`, off in the reference) the DNA adapter is cut off the head of an RNA read's
+    signal (`ts.trim_rna`, which needs `rsqgl_params`; a view, no copy), RNA signal is flipped into
+    5'->3' order, and stall intervals are detected on it (`COLLAPSE_RNA_STALLS`); DNA is passed
+    through (`COLLAPSE_DNA_STALLS` and `USE_START_CLIP_BASES` are off in the reference)."""
+    from ._default_parameters import COLLAPSE_RNA_STALLS, COLLAPSE_DNA_STALLS, TRIM_RNA_ADAPTER
+    if trim_rna_adapter is None:
+        trim_rna_adapter = TRIM_RNA_ADAPTER
     if seq_samp_type.name == RNA_SAMP_TYPE:
+        if trim_rna_adapter:
+            if rsqgl_params is None:
+                raise ValueError('trimming the RNA adapter needs rsqgl_params')
+            adapter_end = ts.trim_rna(map_res.raw_signal, rsqgl_params)
+            map_res = map_res._replace(raw_signal=map_res.raw_signal[adapter_end:])
         map_res = map_res._replace(raw_signal=map_res.raw_signal[::-1])
     if (COLLAPSE_RNA_STALLS and seq_samp_type.name == RNA_SAMP_TYPE) or \
             (COLLAPSE_DNA_STALLS and seq_samp_type.name == DNA_SAMP_TYPE):
@@ -716,7 +725,8 @@ def resquiggle_batch_iters(map_results, std_ref, rsqgl_params, save_params=None,
                            outlier_thresh=None, const_scale=None, skip_seq_scaling=False,
                            seq_samp_type=th.seqSampleType(DNA_SAMP_TYPE, False),
                            max_scaling_iters=None, engine=None, return_passes=False,
-                           device_prep=False, subsample_seed=None, rng_order='round_major'):
+                           device_prep=False, subsample_seed=None, rng_order='round_major',
+                           trim_rna_adapter=False):
     """The per-read loop of `_resquiggle_worker` (resquiggle.py:1578-1589) over a batch.
 
     Every read is resquiggled; while `norm_params_changed` it is re-run with the fitted
@@ -745,12 +755,25 @@ def resquiggle_batch_iters(map_results, std_ref, rsqgl_params, save_params=None,
     file's int16 samples and gets an int16-truncated metric: intervals within one unit of the
     threshold or at the signal's edges can differ -- INTEGRATION.md section 6.  Pass `stall_ints`
     on the reads, without `device_prep`, for the reference's own intervals.)
+
+    `trim_rna_adapter` (RNA; the reads in acquisition order, so with `device_prep`): before the first
+    pass one `ts.trim_rna_batch` call finds every read's adapter end and the read goes on as the view
+    `raw_signal[adapter_end:]` (no copy).  A read `trim_rna` fails on has that exception as its result
+    and 0 passes: the call sits outside the worker's save-parameter retry (resquiggle.py:1575).
     """
     from ._default_parameters import MAX_SCALING_ITERS
     if max_scaling_iters is None:
         max_scaling_iters = MAX_SCALING_ITERS
     n = len(map_results)
     n_passes = [0] * n
+    trim_failed = {}
+    if trim_rna_adapter and n and seq_samp_type is not None and seq_samp_type.name == RNA_SAMP_TYPE:
+        if not device_prep:
+            raise ValueError('trim_rna_adapter works on the signal in acquisition order: device_prep=True')
+        ends, errs = ts.trim_rna_batch([mr.raw_signal for mr in map_results], rsqgl_params, engine=engine)
+        map_results = [mr if err is not None else mr._replace(raw_signal=mr.raw_signal[int(end):])
+                       for mr, end, err in zip(map_results, ends, errs)]
+        trim_failed = dict((i, err) for i, err in enumerate(errs) if err is not None)
     prep = dict(subsample_seed=subsample_seed)
     if device_prep:
         from ._default_parameters import COLLAPSE_RNA_STALLS, STALL_PARAMS
@@ -765,8 +788,9 @@ def resquiggle_batch_iters(map_results, std_ref, rsqgl_params, save_params=None,
             kw.update(const_scale=const_scale, skip_seq_scaling=skip_seq_scaling)
         return resquiggle_batch(mrs, std_ref, params, outlier_thresh, seq_samp_type=seq_samp_type,
                                 engine=engine, **prep, **kw)
-    res = {}
-    for group in ([[i] for i in range(n)] if rng_order == 'read_major' else [list(range(n))]):
+    res = dict(trim_failed)
+    todo = [i for i in range(n) if i not in trim_failed]
+    for group in ([[i] for i in todo] if rng_order == 'read_major' else [todo] if todo or not trim_failed else []):
         res.update(_run_iters(run_pass, map_results, group, rsqgl_params, max_scaling_iters, n_passes))
         failed = [i for i in group if isinstance(res[i], Exception)]
         if failed and save_params is not None:

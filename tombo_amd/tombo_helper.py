@@ -47,6 +47,9 @@ stallParams = namedtuple('stallParams', (
     'upper_pctl', 'mini_window_size', 'n_windows'))
 stallParams.__new__.__defaults__ = (None,) * 4
 
+trimRnaParams = namedtuple('trimRnaParams', (
+    'moving_window_size', 'min_running_values', 'thresh_scale', 'max_raw_obs'))
+
 startClipParams = namedtuple('startClipParams', ('bandwidth', 'num_genome_bases'))
 
 resquiggleResults = namedtuple('resquiggleResults', (

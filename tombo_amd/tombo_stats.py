@@ -9,6 +9,7 @@ Mirrors the part of /root/reference/tombo/tombo_stats.py the hot path touches:
   remove_stall_cpts                    tombo_stats.py:1576-1597
   normalize_raw_signal, compute_base_means, get_read_seg_score, calc_kmer_fitted_shift_scale
                                        tombo_stats.py:482-573, 203-215, 2327-2338, 370-450 (csrc/k_norm_api.h)
+  trim_rna, estimate_global_scale      tombo_stats.py:235-267, 452-480 (csrc/k_trim_rna.h)
 The numeric kernels (normalisation, event detection, DP ...) live in csrc/ and are reached
 through tombo_amd.resquiggle.
 """
@@ -20,14 +21,14 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import tombo_helper as th, _native
+from . import tombo_helper as th, _native, errors
 from ._c_helper import llh_ratio_windows
 from ._default_parameters import (
     ALGN_PARAMS_TABLE, SEG_PARAMS_TABLE, RNA_SAMP_TYPE, DNA_SAMP_TYPE, STANDARD_MODELS,
     HALF_NORM_EXPECTED_VAL, MIN_EVENT_TO_SEQ_RATIO, STALL_PARAMS, OUTLIER_THRESH, COLLAPSE_RNA_STALLS, SMALLEST_PVAL, FM_OFFSET_DEFAULT,
     SAMP_COMP_TXT, DE_NOVO_TXT, ALT_MODEL_TXT, CONST_SD_MODEL, OCLLHR_SCALE, OCLLHR_HEIGHT,
     OCLLHR_POWER, MEAN_PRIOR_CONST, SD_PRIOR_CONST, ALT_EST_BATCH, MAX_KMER_OBS, MIN_KMER_OBS_TO_EST,
-    KERNEL_DENSITY_RANGE, NUM_DENS_POINTS, ROC_PLOT_POINTS)
+    KERNEL_DENSITY_RANGE, NUM_DENS_POINTS, ROC_PLOT_POINTS, NUM_READS_FOR_SCALE)
 
 _MODEL_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tombo_models')
 _BASE_CODE = np.full(256, 255, dtype=np.uint8)
@@ -354,6 +355,87 @@ def remove_stall_cpts(stall_ints, valid_cpts):
         if not (cur[0] < cpt < cur[1]):
             keep.append(i)
     return valid_cpts[keep]
+
+
+# ---- RNA adapter trimming and the global scale estimate (tombo_stats.py:235-267, :452-480; csrc/k_trim_rna.h) ----
+DEFAULT_TRIM_RNA_PARAMS = th.trimRnaParams(moving_window_size=50, min_running_values=100, thresh_scale=0.7,
+                                           max_raw_obs=40000)     # tombo_stats.py:98-100
+_TRIM_TOO_FEW_MSG = 'negative dimensions are not allowed'          # numpy's, from as_strided's shape
+_NO_SCALE_READS_MSG = 'No reads contain raw signal for global scale parameter estimation.'
+_FEW_SCALE_READS_MSG = ('Few reads contain raw signal for global scale parameter estimation. Results may not be '
+                        'optimal.')
+
+
+def _trim_error(status):
+    """the exception the reference's trim_rna ends in for a read of this status, or None"""
+    status = int(status)
+    if status == 0:
+        return None
+    if status == _native.TRIM_TOO_FEW_EVENTS:
+        return ValueError(_TRIM_TOO_FEW_MSG)
+    try:
+        errors.raise_for_status(status)
+    except Exception as e:
+        return e
+
+
+def _raw_for_device(raws):
+    """the reads as the raw-signal entries take them: int16 where every read is, else float64 (astype(np.float64)
+    gives int16 samples the same values, which is what the reference computes on)"""
+    raws = [np.asarray(r) for r in raws]
+    if any(r.ndim != 1 for r in raws):
+        raise ValueError('every read needs a one-dimensional signal')
+    if not all(r.dtype == np.int16 for r in raws):
+        raws = [r if r.dtype == np.float64 else r.astype(np.float64) for r in raws]
+    return raws
+
+
+def trim_rna_batch(raws, rsqgl_params, trim_rna_params=DEFAULT_TRIM_RNA_PARAMS, engine=None):
+    """trim_rna of every read of `raws` in one engine call -> (int64 adapter ends, a list holding None or, for a read
+    the reference's trim_rna raises on, that exception: th.TomboError('Fewer changepoints found than requested'),
+    ValueError('negative dimensions are not allowed')); a failing read's end is 0 and the others are unaffected.
+    Only the first max_raw_obs samples of a read are handed to the device."""
+    raws = _raw_for_device(raws)
+    if len(raws) == 0:
+        return np.zeros(0, np.int64), []
+    ends, status = _engine(engine).trim_rna(
+        raws, (rsqgl_params.running_stat_width, rsqgl_params.min_obs_per_base, rsqgl_params.mean_obs_per_event),
+        trim_rna_params)
+    return ends, [_trim_error(st) for st in status]
+
+
+def trim_rna(all_raw_signal, rsqgl_params, trim_rna_params=DEFAULT_TRIM_RNA_PARAMS, engine=None):
+    """tombo_stats.py:235-267 -> the end of the DNA adapter at the head of a direct-RNA read's signal (acquisition
+    order), 0 when no window qualifies; raises what the reference raises"""
+    ends, errs = trim_rna_batch([all_raw_signal], rsqgl_params, trim_rna_params, engine)
+    if errs[0] is not None:
+        raise errs[0]
+    return int(ends[0])
+
+
+def estimate_global_scale(fast5s, num_reads=NUM_READS_FOR_SCALE, engine=None):
+    """tombo_stats.py:452-480: np.mean of the MADs of up to num_reads reads.  fast5s: a list of open FAST5-like objects
+    (th.get_raw_read_slot) or raw signal arrays, shuffled in place with numpy's global RNG as the reference shuffles
+    its file names; items without a raw slot (or without a sample) are skipped, the first num_reads others are taken
+    and go through one engine call (np.median and the MAD by exact selection, no normalised signal)."""
+    np.random.shuffle(fast5s)
+    sigs = []
+    for item in fast5s:
+        try:
+            sig = np.asarray(item if isinstance(item, np.ndarray) else th.get_raw_read_slot(item)['Signal'][:])
+            if sig.ndim != 1 or sig.shape[0] < 1:
+                continue
+        except Exception:
+            continue
+        sigs.append(sig)
+        if len(sigs) >= num_reads:
+            break
+    if len(sigs) == 0:
+        raise th.TomboError(_NO_SCALE_READS_MSG)
+    if len(sigs) < num_reads:
+        warnings.warn(_FEW_SCALE_READS_MSG)
+    _, mads = _engine(engine).raw_med_mad(_raw_for_device(sigs))
+    return np.mean(mads)
 
 
 # ---------------------------------------------------------------------------------------------
